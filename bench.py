@@ -23,6 +23,12 @@ The line carries ``roofline`` (dominant kernel: algorithmic bytes per launch, as
 the host code that issues the launches, over the hipEvent-measured launch time of the timed
 steps) and ``cpu_baseline`` (the reference's DuckDB path when ``import duckdb`` works on the box,
 else the oracle's OpenMP sort-merge port), which is also the run's parity check.
+
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (float64, under 64 MB in
+all): INNER -> ``n_pairs`` and a seeded, order-independent sample of the pairs as ``row_a`` / ``row_b`` sorted by
+(row_a, row_b); SEMI / ANTI -> ``row_a``; COUNT -> ``count``; NEAREST -> ``row_b`` and ``distance`` per A row
+(with ``position`` when only a seeded subset of the rows fits).  The inputs are seeded, so two builds run with the
+same arguments can be compared file for file.
 """
 
 from __future__ import annotations
@@ -114,9 +120,18 @@ def parse_args():
                         "export; the local one-call join; the expansion of all N ranks' plan blocks), each verified "
                         "against the CPU leg.  An extra line, never the headline")
     p.add_argument("--shard-rank", type=int, default=0)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64; "
+                        "a fixed, seeded sample of an output larger than 64 MB) so that two builds can be compared")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    if a.warmup < 0:
+        p.error("--warmup must not be negative")
     if a.no_gather:
         a.exchange = "none"
+    if a.dump_outputs and a.gpus > 1 and a.exchange == "none":
+        p.error("--dump-outputs at N > 1 needs the gathered result: not with --exchange none")
     a.verify = (a.gpus > 1 or a.verify or a.force_exchange) and not a.no_verify
     return a
 
@@ -231,6 +246,90 @@ def pmc_traffic(workload, form, phase, launches):
         return round(t[workload][form][phase] / max(launches, 1))
     except (OSError, KeyError, ValueError, TypeError):
         return None
+
+
+# --------------------------------------------------------------------------- outputs
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs: all arrays of a run together stay under 64 MB
+DUMP_SEED = 20_241_015           # the sample of an output too large to dump whole is fixed by this seed
+DUMP_PAIR_TARGET = 1 << 21       # pairs: aim at about this many sampled pairs (32 MB as two float64 arrays)
+
+
+def pair_sample_hash(row_a, row_b):
+    """A 31-bit hash of each ``(row_a, row_b)`` pair (int64 tensors, any device); every intermediate stays below
+    2^63, so the int64 arithmetic never wraps.  Pairs whose low bits are zero form the sample of a pair output."""
+    x = (row_a * 0x9E3779B1) ^ (row_b * 0x7FEB352D) ^ DUMP_SEED
+    x = x ^ (x >> 31)
+    x = (x & 0x7FFFFFFF) * 0x2C1B3C6D
+    x = x ^ (x >> 29)
+    x = (x & 0x7FFFFFFF) * 0x297A2D39
+    x = x ^ (x >> 32)
+    return x & 0x7FFFFFFF
+
+
+def pair_sample(row_a, row_b, budget=DUMP_BUDGET_BYTES, target=DUMP_PAIR_TARGET, chunk=1 << 25):
+    """Seeded sample of an INNER result as host ``(row_a, row_b)`` int64 arrays in (row_a, row_b) order, plus the
+    sampling shift.  A pair is kept when the low ``shift`` bits of its hash are zero, so the sample depends on the
+    multiset of pairs only -- not on the order the join wrote them in; ``shift`` grows with the pair count until
+    about ``target`` pairs remain, and a sample over the budget is cut after sorting."""
+    import numpy as np
+    import torch
+
+    n = int(row_a.shape[0])
+    shift = 0
+    while (n >> shift) > target:
+        shift += 1
+    mask = (1 << shift) - 1
+    keep_a, keep_b = [], []
+    for lo in range(0, n, chunk):
+        a = row_a[lo:lo + chunk].to(torch.int64)
+        b = row_b[lo:lo + chunk].to(torch.int64)
+        if mask:
+            sel = (pair_sample_hash(a, b) & mask) == 0
+            a, b = a[sel], b[sel]
+        keep_a.append(a.cpu().numpy())
+        keep_b.append(b.cpu().numpy())
+    a = np.concatenate(keep_a) if keep_a else np.empty(0, np.int64)
+    b = np.concatenate(keep_b) if keep_b else np.empty(0, np.int64)
+    order = np.lexsort((b, a))
+    cap = budget // 16
+    return a[order][:cap], b[order][:cap], shift
+
+
+def dump_outputs(out_dir, pairs=None, rows=None):
+    """``--dump-outputs``: write what the last timed step computed as ``out_dir/<name>.npy`` (float64: row ids,
+    counts and distances are integers below 2^53, exact in it).  ``pairs`` = ``(row_a, row_b)`` of an INNER join:
+    ``n_pairs.npy`` and a seeded sample from :func:`pair_sample`.  ``rows`` = ``{name: 1-D tensor}`` of equal
+    length (SEMI / ANTI row ids, COUNT / NEAREST per A row): written whole, or -- above the budget -- at a seeded
+    set of positions that ``position.npy`` lists.  Returns the summary the JSON line carries."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays, info = {}, {}
+    if pairs is not None:
+        ra, rb = pairs
+        n = int(ra.shape[0])
+        sa, sb, shift = pair_sample(ra, rb)
+        arrays.update({"n_pairs": np.array([n]), "row_a": sa, "row_b": sb})
+        info["sample"] = (f"pairs whose seeded hash has {shift} low zero bits, in (row_a, row_b) order"
+                          if shift else "every pair, in (row_a, row_b) order")
+    if rows:
+        n = int(next(iter(rows.values())).shape[0])
+        host = {k: v.cpu().numpy() for k, v in rows.items()}
+        per_row = 8 * len(host)
+        if n * per_row > DUMP_BUDGET_BYTES:
+            m = DUMP_BUDGET_BYTES // (per_row + 8)
+            pos = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(n, m, replace=False))
+            host = {k: v[pos] for k, v in host.items()}
+            host["position"] = pos
+            info["sample"] = f"{m} of {n} rows at seeded positions (position.npy)"
+        else:
+            info["sample"] = f"all {n} rows"
+        arrays.update(host)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+    info.update({"dir": out_dir, "dtype": "float64", "files": {k + ".npy": int(v.shape[0]) for k, v in arrays.items()},
+                 "bytes": int(sum(8 * v.shape[0] for v in arrays.values()))})
+    return info
 
 
 # ---------------------------------------------------------------------------- inputs
@@ -509,6 +608,7 @@ def run_shard(args):
                                rs[offs[q]:offs[q] + n_q_pairs], n_pairs_expected=n_q_pairs)
 
     part_c = timed(expand_all, args.steps, args.warmup)
+    dumped = dump_outputs(args.dump_outputs, pairs=(gout[0][:total], gout[1][:total])) if args.dump_outputs else None
     gpu_all = (int(total), eng.pairs_checksum(gout[0][:total], gout[1][:total]))
     parity = {"local_join_pairs_equal": gpu_local[0] == cpu_local[0] == n_mine,
               "local_join_checksum_equal": gpu_local[1] == cpu_local[1]}
@@ -535,6 +635,8 @@ def run_shard(args):
         "parity": parity,
         "gen_seconds": round(gen_s, 1),
     }
+    if dumped:
+        line["dump_outputs"] = dumped
     eng.close()
     return line
 
@@ -593,6 +695,7 @@ def run_indexed(args):
     st = eng.stats()
     eng.set_profiling(False)
     step_ms = [ev[k].elapsed_time(ev[k + 1]) for k in range(args.steps)]
+    dumped = dump_outputs(args.dump_outputs, pairs=(out[0][:n_pairs], out[1][:n_pairs])) if args.dump_outputs else None
     dom_ms /= args.steps
     dom_bytes = float(st["phase_bytes"]["sort_local"])
     join_bytes = op_bytes("inner", n_a, n_b, n_pairs)
@@ -624,6 +727,8 @@ def run_indexed(args):
                                     "frac_of_wall_step": round(join_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4)}},
         "cpu_baseline": cpu_baseline, "gen_seconds": round(gen_s, 1),
     }
+    if dumped:
+        line["dump_outputs"] = dumped
     index.close()
     eng.close()
     return line
@@ -912,6 +1017,12 @@ def run_inner(args):
 
     line = None
     if rank == 0:
+        dumped = None
+        if args.dump_outputs and last_pairs[0] is not None:
+            pa_, pb_ = last_pairs[0] if not isinstance(last_pairs[0], list) else (
+                torch.cat([x[0] for x in last_pairs[0]]), torch.cat([x[1] for x in last_pairs[0]]))
+            dumped = dump_outputs(args.dump_outputs, pairs=(pa_, pb_))
+            del pa_, pb_
         per_step_launches = {k: v // args.steps for k, v in phase_launches.items()}
         form, span_hist = st["join_form"], bool(st.get("span_hist", False))
         pbytes = inner_phase_bytes(loc_na, loc_nb, n_local, form, span_hist, st.get("phase_bytes"),
@@ -1027,6 +1138,8 @@ def run_inner(args):
             "gen_seconds": round(gen_s, 1),
         }
         line.update(extras)
+        if dumped:
+            line["dump_outputs"] = dumped
         if distributed:
             line["exchange"] = {"mode": exchange, "impl": (xplan.impl if xplan is not None else "allgather"),
                                 "gather": "root" if root is not None else "all",
@@ -1282,6 +1395,11 @@ def run_rowop(args):
             ha = tuple(np.concatenate([p[1][k] for p in parts]) for k in range(3))
             hb = tuple(np.concatenate([p[2][k] for p in parts]) for k in range(3))
     g_na, g_nb = (tot_na, tot_nb) if distributed else (loc_na, loc_nb)   # the whole job's rows
+    dumped = None
+    if args.dump_outputs:
+        out_rows = ({"row_b": res[0], "distance": res[1]} if op == "nearest" else
+                    {"count": res} if op == "count" else {"row_a": res})
+        dumped = dump_outputs(args.dump_outputs, rows=out_rows)
     n_out = int((res[0] if isinstance(res, tuple) else res).shape[0])
     device_ms = sum(phases.values())
     alg = op_bytes(op, loc_na, loc_nb, last_local[0])   # this rank's shard: what its kernels (device_ms) moved
@@ -1354,6 +1472,8 @@ def run_rowop(args):
                       "device_ms": round(device_ms, 3)}],
         "roofline": roofline, "cpu_baseline": cpu_baseline, "gen_seconds": round(gen_s, 1),
     }
+    if dumped:
+        line["dump_outputs"] = dumped
     eng.close()
     if distributed:
         dist.barrier()

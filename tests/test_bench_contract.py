@@ -93,3 +93,64 @@ def test_gpus_n_starts_the_ranks_as_a_child_process(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     bench.self_launch(bench.parse_args())   # N = 1: nothing to launch
     assert len(calls) == 1
+
+
+def test_steps_and_warmup_are_checked(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "0"])
+    args = bench.parse_args()
+    assert args.steps == 7 and args.warmup == 0 and args.dump_outputs is None
+    for argv in (["--steps", "0"], ["--warmup", "-1"], ["--gpus", "2", "--exchange", "none", "--dump-outputs", "d"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit):
+            bench.parse_args()
+
+
+def test_pair_sample_depends_on_the_pairs_not_their_order():
+    import numpy as np
+    import torch
+
+    rng = np.random.default_rng(11)
+    n = 300_000
+    a = rng.integers(0, 10_000_000, n).astype(np.int32)
+    b = rng.integers(0, 100_000_000, n).astype(np.int32)
+    perm = rng.permutation(n)
+    sa, sb, shift = bench.pair_sample(torch.from_numpy(a), torch.from_numpy(b), target=1 << 14, chunk=1 << 16)
+    pa, pb, shift2 = bench.pair_sample(torch.from_numpy(a[perm]), torch.from_numpy(b[perm]), target=1 << 14, chunk=1 << 15)
+    assert shift == shift2 == 5
+    assert np.array_equal(sa, pa) and np.array_equal(sb, pb)
+    assert 0.5 * (n >> shift) < sa.shape[0] < 1.5 * (n >> shift)
+    # the sample is a sub-multiset of the pairs, sorted by (row_a, row_b)
+    key = a.astype(np.int64) << 32 | b.astype(np.int64)
+    skey = sa << 32 | sb
+    assert np.all(np.diff(skey) >= 0) and np.isin(skey, key).all()
+    # small outputs are kept whole; the byte budget cuts a sample after sorting
+    wa, wb, s0 = bench.pair_sample(torch.from_numpy(a[:1000]), torch.from_numpy(b[:1000]))
+    assert s0 == 0 and wa.shape[0] == 1000 and np.array_equal(np.sort(wa), wa)
+    ca, _cb, _ = bench.pair_sample(torch.from_numpy(a[:1000]), torch.from_numpy(b[:1000]), budget=16 * 100)
+    assert np.array_equal(ca, wa[:100])
+
+
+def test_dump_outputs_writes_float64_under_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    ra = torch.tensor([3, 1, 2, 1], dtype=torch.int32)
+    rb = torch.tensor([99_999_999, 7, 5, 2], dtype=torch.int32)
+    info = bench.dump_outputs(str(tmp_path / "inner"), pairs=(ra, rb))
+    got = {k: np.load(tmp_path / "inner" / f"{k}.npy") for k in ("n_pairs", "row_a", "row_b")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["n_pairs"].tolist() == [4]
+    assert got["row_a"].tolist() == [1, 1, 2, 3] and got["row_b"].tolist() == [2, 7, 5, 99_999_999]
+    assert info["bytes"] == 8 * 9
+    # per-row outputs above the budget: a seeded subset of positions, the same on every run
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 24 * 1000)
+    idx = torch.arange(5000, dtype=torch.int32) * 3
+    dist = torch.arange(5000, dtype=torch.int64)
+    runs = []
+    for tag in ("x", "y"):
+        info = bench.dump_outputs(str(tmp_path / tag), rows={"row_b": idx, "distance": dist})
+        runs.append({k: np.load(tmp_path / tag / f"{k}.npy") for k in ("row_b", "distance", "position")})
+        assert info["bytes"] <= 24 * 1000
+    pos = runs[0]["position"]
+    assert pos.shape[0] == 1000 and np.array_equal(runs[0]["row_b"], pos * 3) and np.array_equal(runs[0]["distance"], pos)
+    assert all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
