@@ -3517,6 +3517,9 @@ int giql_hip_take_utf8_plan_dev(giql_hip_ctx* ctx, const int32_t* offsets, int64
   if (!ctx || !out_offsets || !n_bytes || n < 0 || n > 0x7FFFFFF0ll || n_rows < 0 || n_rows > 0x7FFFFFFFll)
     return set_err(GIQL_ERR_INVALID, "bad arguments");
   if ((n > 0 && !idx) || (n_rows > 0 && !offsets)) return set_err(GIQL_ERR_INVALID, "NULL buffer");
+  // its scan partials are carved from the start of the arena, where an INNER plan keeps its arrays
+  ctx->planned = false;
+  ctx->plan_is_join = false;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   reset_stats(ctx);
@@ -3618,6 +3621,9 @@ int giql_hip_select_expr_dev(giql_hip_ctx* ctx, const giql_pred* preds, int32_t 
   // a side given neither ids nor a row count is addressed by the candidate index
   if (!idx_a && n_rows_a == 0 && !uses[0]) n_rows_a = n;
   if (!idx_b && n_rows_b == 0 && !uses[1]) n_rows_b = n;
+  // the mask and scan partials are carved from the start of the arena, where an INNER plan keeps its arrays
+  ctx->planned = false;
+  ctx->plan_is_join = false;
   *n_kept = 0;
   if (n == 0) return GIQL_OK;
   HIP_TRY(hipSetDevice(ctx->device));

@@ -339,6 +339,17 @@ def _sorted_union_codes(parts):
     return out, dictionary
 
 
+def _refuse_null_chroms(values: np.ndarray) -> None:
+    """SQL NULL never matches (and the reference never joins NULL chroms): every element is checked, not
+    the first -- a later None would otherwise become the string 'None' in a dictionary and NULL-chrom rows
+    of the two sides would join each other."""
+    if values.size:
+        null = np.fromiter((v is None or (isinstance(v, float) and v != v) for v in values.astype(object, copy=False)),
+                           dtype=bool, count=values.size)
+        if null.any():
+            raise ValueError("chrom contains NULLs: not supported by dialect='hip'")
+
+
 def encode_chroms(col_a, col_b):
     """Shared dictionary encoding of both chrom columns -> (ids_a, ids_b, dictionary)."""
     fast = [_arrow_codes(col_a, "left chrom column"), _arrow_codes(col_b, "right chrom column")]
@@ -366,13 +377,7 @@ def encode_chroms(col_a, col_b):
                     dictionary.tolist())
         return ia, ib, list(range(n))
     both = np.concatenate([a.astype(object), b.astype(object)])
-    # SQL NULL never matches (and the reference never joins NULL chroms): every element is checked, not
-    # the first -- a later None would otherwise become the string 'None' in the shared dictionary and
-    # NULL-chrom rows of the two sides would join each other
-    if both.size:
-        null = np.fromiter((v is None or (isinstance(v, float) and v != v) for v in both), dtype=bool, count=both.size)
-        if null.any():
-            raise ValueError("chrom contains NULLs: not supported by dialect='hip'")
+    _refuse_null_chroms(both)
     dictionary, inverse = np.unique(both.astype(str), return_inverse=True)
     inverse = inverse.astype(np.int32)
     return (np.ascontiguousarray(inverse[: a.size]), np.ascontiguousarray(inverse[a.size:]),
@@ -1000,8 +1005,26 @@ def _chrom_values(col):
     if x.dtype.kind in "iu":
         dictionary, inverse = np.unique(x, return_inverse=True)
         return np.ascontiguousarray(inverse.astype(np.int32)), dictionary.tolist()
+    _refuse_null_chroms(x)
     dictionary, inverse = np.unique(x.astype(str), return_inverse=True)
     return np.ascontiguousarray(inverse.astype(np.int32)), dictionary.tolist()
+
+
+def _chrom_lookup(index_values, query_values) -> np.ndarray:
+    """Position of each of a query table's chrom values in an index's dictionary (``len(index_values)``: no such
+    chromosome), both as ``_chrom_values`` returns them.  Matched as :func:`encode_chroms` matches the two columns of
+    an ordinary join: integers as integers (never negative) when both columns hold integers, otherwise as ``str``
+    -- an int column joins a string column on ``str(id)``."""
+    def ints(values):
+        return all(isinstance(v, int) and not isinstance(v, bool) for v in values)
+
+    both_int = ints(index_values) and ints(query_values)
+    if both_int and any(v < 0 for v in (*index_values, *query_values)):
+        raise ValueError("integer chrom ids must be non-negative")
+    key = (lambda v: v) if both_int else str
+    pos = {key(v): i for i, v in enumerate(index_values)}
+    return np.fromiter((pos.get(key(v), len(index_values)) for v in query_values), dtype=np.int32,
+                       count=len(query_values))
 
 
 def _indexed_inner(plan: JoinPlan, lt, rt, pins, eng: HipEngine):
@@ -1033,8 +1056,7 @@ def _indexed_inner(plan: JoinPlan, lt, rt, pins, eng: HipEngine):
         if index is None:
             continue
         qcodes, qvalues = _chrom_values(_column(qt, qside.chrom_col))
-        pos = {v: i for i, v in enumerate(dictionary)}
-        lut = np.fromiter((pos.get(v, len(dictionary)) for v in qvalues), dtype=np.int32, count=len(qvalues))
+        lut = _chrom_lookup(dictionary, qvalues)
         q = DeviceSide.from_numpy(lut[qcodes] if len(qvalues) else qcodes,
                                   _int32_column(_column(qt, qside.start_col), qside.start_col),
                                   _int32_column(_column(qt, qside.end_col), qside.end_col), qside.encoding, device=eng.device)

@@ -161,7 +161,13 @@ int giql_hip_get_stats(giql_hip_ctx* ctx, giql_hip_stats* out);
 /* ---- device-resident entry points -------------------------------------- */
 /* INNER join in two calls so the caller owns the output:
  *   plan: sort + count + scan; returns the exact number of pairs;
- *   fill: writes row_a[i], row_b[i] for i < n_pairs (capacity >= n_pairs). */
+ *   fill: writes row_a[i], row_b[i] for i < n_pairs (capacity >= n_pairs).
+ * The plan lives in the context's workspace.  It is consumed by fill and by
+ * giql_hip_inner_plan_export_dev (each as often as wanted) only until the next call
+ * on the context that launches work and is neither: the operators, the index entry
+ * points, chrom_spans, select and take_utf8_plan reuse that workspace and make fill /
+ * export return GIQL_ERR_STATE; after any other such call a fill is not supported.
+ * Calls that launch nothing -- get_stats, set_profiling, last_error -- keep the plan. */
 int giql_hip_inner_plan_dev(giql_hip_ctx* ctx, const giql_side* a,
                             const giql_side* b, int32_t n_chrom, void* stream,
                             int64_t* n_pairs);
@@ -178,7 +184,9 @@ int giql_hip_inner_fill_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b,
  * that call, so giql_hip_inner_fill_dev / giql_hip_inner_plan_export_dev after it
  * return GIQL_ERR_STATE -- they follow a giql_hip_inner_plan_dev.  The ORDER of the
  * pairs is unspecified in every form (and not reproducible from call to call in this
- * one); the multiset of pairs is exact. */
+ * one); the multiset of pairs is exact.  Entries past *n_pairs (up to capacity) are left
+ * untouched when the guesses hold; a call whose guesses missed repeats its work, and the
+ * abandoned attempt may have written pairs there. */
 int giql_hip_inner_join_dev(giql_hip_ctx* ctx, const giql_side* a,
                             const giql_side* b, int32_t n_chrom, int32_t* row_a,
                             int32_t* row_b, int64_t capacity, void* stream,

@@ -1,0 +1,637 @@
+"""Every change of input and of call sequence on one long-lived HIP context, against the C oracle.
+
+A ``giql_hip_ctx`` speculates: each call starts from what the previous call saw -- the INNER join form and its fixed
+length, the fixed-length B of SEMI / ANTI / COUNT, the NEAREST plan and layout, sides that arrived sorted, whether the
+fused count may run, the density (``last_span``) that picks the bucket width, the sticky switch to the four-pass sort --
+and checks the guess at its own read-back (``giql_amd/csrc/giql_hip.hip``; the engine adds ``_pairs_guess``).  A guess
+that is not checked properly shows only on the call AFTER a change of input, which hand-picked sequences rarely reach:
+round 4's one state bug (ties of NEAREST / group_rows in input order after pile-ups and a dense table, commit 25a7a2b)
+was found by a long random soak.  So here:
+
+* Walk 1: per operator family, one fresh context walks an Eulerian circuit of the complete directed graph over the
+  input classes (self-loops included): every ordered pair (X, Y) is a call on Y right after the context's last call
+  on X.  Each visit runs the family twice; the second run must reach the path its class names (``SIGNATURES``).
+* Walk 2: one context, all twelve operators in a shuffled order per visit, with ``select`` / ``take_utf8`` put
+  between some plans and their fill -- which must then refuse (``GIQL_ERR_STATE``): those calls reuse the workspace
+  the plan lives in.
+* Leg 3: the sticky four-pass fallback after a bucket too large for the bucket stage, reached from every class.
+* Leg 4: production density on a default context: every ordered pair of bucket widths.
+
+Pairs are compared as sorted multisets, per-row outputs exactly, NEAREST rows by the (start, end) of the matched row
+(ties count), group_rows by its groups (``tools/soak_ops.py``).
+"""
+
+import functools
+
+import numpy as np
+import pytest
+
+from oracle import pyoracle as ora
+
+torch = pytest.importorskip("torch")
+
+
+# ---------------------------------------------------------------- the schedule (pure; checked on the CPU below)
+def eulerian_circuit(k: int) -> list:
+    """Visit order over ``k`` classes that takes every ordered pair (i, j), i == j included, exactly once as two
+    consecutive visits: an Eulerian circuit of the complete directed graph with self-loops (Hierholzer), from 0."""
+    unused = {v: list(range(k - 1, -1, -1)) for v in range(k)}
+    stack, circuit = [0], []
+    while stack:
+        v = stack[-1]
+        if unused[v]:
+            stack.append(unused[v].pop())
+        else:
+            circuit.append(stack.pop())
+    return circuit[::-1]
+
+
+@pytest.mark.parametrize("k", [1, 2, 5, 15, 16])
+def test_schedule_takes_every_ordered_pair_once(k):
+    walk = eulerian_circuit(k)
+    assert len(walk) == k * k + 1 and walk[0] == walk[-1] == 0
+    edges = list(zip(walk, walk[1:]))
+    assert sorted(edges) == [(i, j) for i in range(k) for j in range(k)]
+
+
+# ---------------------------------------------------------------- input classes
+BS_FUSE_WCAP = 1 << 15     # longest query row the fused count's windows allow for (bucket_sort.hip.h)
+BS_BIG_MAX = 1 << 18       # rows of one bucket the bucket stage sorts at all (bucket_sort.hip.h)
+
+
+def _rows(r, n, nch, span, lens, lo=0):
+    """n rows on nch chromosomes, starts uniform in [lo, lo + span), lengths ``lens`` (an int: fixed; a pair:
+    uniform in [lens[0], lens[1]))."""
+    ch = r.integers(0, nch, n).astype(np.int32)
+    st = (lo + r.integers(0, span, n)).astype(np.int32)
+    ln = np.full(n, lens, np.int64) if np.isscalar(lens) else r.integers(lens[0], lens[1], n)
+    return ora.Side(ch, st, (st + ln).astype(np.int32))
+
+
+def _density_span(n_b, per_65536):
+    """The axis length over which n_b rows have per_65536 rows per 65,536 positions."""
+    return int(n_b * 65536 / per_65536)
+
+
+def _dense(seed, n_b, per_65536, n_a=2000, b_lens=150):
+    """A B at a given density on one chromosome (fixed length 150 unless ``b_lens`` says otherwise), a short
+    variable-length A over the same axis."""
+    r = np.random.default_rng(seed)
+    span = _density_span(n_b, per_65536)
+    return _rows(r, n_a, 1, span, (1, 300)), _rows(r, n_b, 1, span, b_lens), 1
+
+
+def _build_classes():
+    out = {}
+    r = np.random.default_rng(3001)
+    out["general"] = (_rows(r, 3000, 4, 8_000_000, (1, 2000)), _rows(r, 20_000, 4, 8_000_000, (1, 800)), 4)
+    out["uniform_b"] = (_rows(r, 3000, 4, 8_000_000, (1, 2000)), _rows(r, 20_000, 4, 8_000_000, 150), 4)
+    out["uniform_a"] = (_rows(r, 20_000, 4, 8_000_000, 200), _rows(r, 3000, 4, 8_000_000, (1, 2000)), 4)
+    out["larger_first"] = (_rows(r, 16_000, 4, 8_000_000, (1, 1500)), _rows(r, 4000, 4, 8_000_000, (1, 1500)), 4)
+    a, b = _rows(r, 3000, 4, 8_000_000, (1, 2000)), _rows(r, 20_000, 4, 8_000_000, (1, 800))
+    sa, sb = np.lexsort((a.start, a.chrom)), np.lexsort((b.start, b.chrom))
+    out["presorted"] = (ora.Side(a.chrom[sa], a.start[sa], a.end[sa]), ora.Side(b.chrom[sb], b.start[sb], b.end[sb]), 4)
+    # ~1 % of A inverted (raw end < start: irregular in every encoding), A 1-based closed beside a 0-based half-open B
+    a = _rows(r, 3000, 3, 5_000_000, (1, 2000))
+    inv = r.random(a.n) < 0.01
+    a.end[inv] = a.start[inv] - 1 - r.integers(0, 5, int(inv.sum())).astype(np.int32)
+    off = ora.ENCODING_OFFSETS[("1based", "closed")]
+    out["irregular"] = (ora.Side(a.chrom, a.start, a.end, *off), _rows(r, 20_000, 3, 5_000_000, (1, 800)), 3)
+    # runs of ~100 equal starts in B (NEAREST's two-sort plan)
+    b = _rows(r, 20_000, 2, 4_000_000, (1, 3000))
+    b.start[:] = (r.integers(0, 200, b.n) * 20_000).astype(np.int32)
+    b.end[:] = b.start + r.integers(1, 3000, b.n).astype(np.int32)
+    out["pileups"] = (_rows(r, 3000, 2, 4_000_000, (1, 2000)), b, 2)
+    out["many_chroms"] = (_rows(r, 3000, 40, 2_000_000, (1, 2000)), _rows(r, 20_000, 40, 2_000_000, (1, 800)), 40)
+    out["negative"] = (_rows(r, 3000, 3, 6_000_000, (1, 2000), lo=-3_000_000),
+                       _rows(r, 20_000, 3, 6_000_000, (1, 800), lo=-3_000_000), 3)
+    a, b, nch = _dense(3002, 100_000, 1000)
+    a.end[:5] = a.start[:5] + np.arange(40_000, 65_000, 5000, dtype=np.int32)   # longer than BS_FUSE_WCAP
+    out["long_rows"] = (a, b, nch)
+    out["w16"] = _dense(3016, 100_000, 1000)
+    # the narrow ones: lengths 100-199.  A fixed-length B is linearised on the aligned axis (2^24-position blocks),
+    # whose span -- the density guess -- makes a table of a few 100k rows look sparse there: the narrow widths of
+    # fixed-length tables are Leg 4's (production sizes).  And rows sharing a start differ in their end here: with a
+    # fixed length, rows of equal start are equal rows, and an order among them that ignores the end cannot be told
+    # from the right one (the 25a7a2b bug returned exactly such ties in input order)
+    out["w15"] = _dense(3015, 100_000, 4000, b_lens=(100, 200))
+    out["w14"] = _dense(3014, 150_000, 8000, b_lens=(100, 200))
+    out["w13"] = _dense(3013, 250_000, 18_000, b_lens=(100, 200))
+    out["sparse"] = _dense(3030, 20_000, 30)
+    return out
+
+
+def _oversized():
+    """~300k B rows inside 4,000 positions of one chromosome -- more than BS_BIG_MAX rows in any bucket -- and a few
+    rows of both sides spread over 10M positions, so that the table's own span asks for the bucket stage."""
+    r = np.random.default_rng(3099)
+    n_pile, n_wide = BS_BIG_MAX + 40_000, 50
+    st = np.concatenate([r.integers(0, 4000, n_pile), r.integers(0, 10_000_000, n_wide)]).astype(np.int32)
+    b = ora.Side(np.zeros(st.size, np.int32), st, st + 150)
+    sa = np.concatenate([[100, 2500], r.integers(10_000, 10_000_000, 18)]).astype(np.int32)
+    a = ora.Side(np.zeros(sa.size, np.int32), sa, sa + r.integers(1, 100, sa.size).astype(np.int32))
+    return a, b, 1
+
+
+SIGNATURES = {   # the settled (second) INNER call of a visit: it reached the path its class names
+    "general": lambda st: st["join_form"] == "general",
+    "uniform_b": lambda st: st["join_form"] == "uniform_b",
+    "uniform_a": lambda st: st["join_form"] == "uniform_a",
+    "larger_first": lambda st: st["swapped"],
+    "presorted": lambda st: st["presorted"],
+    "irregular": lambda st: st["n_irregular_a"] > 0,
+    "pileups": lambda st: True,                     # (its path is NEAREST's two-sort plan: checked by its results)
+    "many_chroms": lambda st: True,                 # (the index declines it: INDEX_DECLINES)
+    "negative": lambda st: True,                    # (the index declines it: INDEX_DECLINES)
+    "long_rows": lambda st: not st["count_fused"],      # (w16 with a few query rows too long for the fused count)
+    "w16": lambda st: st["sort_local"] and st["bucket_bits"] == 16,
+    # (INNER keys its sides on the 2^24-aligned axis, whose span makes these tables look sparse: its settled call takes
+    # 16-bit buckets here.  The width each density asks for is asserted on the operators that sort on the tight span --
+    # SEMI / ANTI / COUNT and NEAREST, SETTLED_WIDTH below -- and for INNER at production sizes, Leg 4)
+    "w15": lambda st: st["sort_local"],
+    "w14": lambda st: st["sort_local"],
+    "w13": lambda st: st["sort_local"],
+    "sparse": lambda st: not st["sort_local"],
+}
+INDEX_DECLINES = {"many_chroms": "chromosomes", "negative": "aligned axis"}   # class -> words of the documented reason
+INDEX_QUERY_DECLINES = {"irregular", "long_rows"}   # query sides the indexed join may refuse (the ordinary join answers)
+WIDTHS = {"w16": 16, "w15": 15, "w14": 14, "w13": 13}
+WIDTH_FAMILIES = ("row", "nearest")   # sorts on the tight span: every settled call takes the width of its density
+
+
+@functools.lru_cache(maxsize=None)
+def classes():
+    return _build_classes()
+
+
+NAMES = ["general", "uniform_b", "uniform_a", "larger_first", "presorted", "irregular", "pileups", "many_chroms",
+         "negative", "long_rows", "w16", "w15", "w14", "w13", "sparse"]
+
+
+def test_class_constructions_are_what_they_claim():
+    """CPU: the classes have the shapes their names promise (densities, lengths, orders, chromosome counts)."""
+    cl = classes()
+    assert sorted(cl) == sorted(NAMES) and sorted(SIGNATURES) == sorted(NAMES)
+    for name, w in WIDTHS.items():
+        a, b, _ = cl[name]
+        per = b.n * 65536 / (int(b.end.max()) - int(b.start.min()))
+        lo, hi = (300, 2800) if w == 16 else (2800 * 2 ** (15 - w), 2800 * 2 ** (16 - w))
+        assert lo < per <= hi, (name, per)
+        assert (len(np.unique(b.end - b.start)) == 1) == (w == 16), name
+        if w <= 15:     # rows of equal start with different ends
+            s = np.lexsort((b.end, b.start))
+            assert np.sum((np.diff(b.start[s]) == 0) & (np.diff(b.end[s]) != 0)) > 1000, name
+        assert a.n * 65536 / (int(b.end.max()) - int(b.start.min())) < 300     # A alone stays in the four passes
+    a, b, _ = cl["sparse"]
+    assert b.n * 65536 / (int(b.end.max()) - int(b.start.min())) < 300
+    assert (cl["long_rows"][0].end - cl["long_rows"][0].start).max() > BS_FUSE_WCAP
+    assert cl["larger_first"][0].n == 4 * cl["larger_first"][1].n
+    a, b, _ = cl["presorted"]
+    for s in (a, b):
+        assert np.all(np.diff(s.chrom.astype(np.int64) * 2**32 + s.start) >= 0)
+    a = cl["irregular"][0]
+    assert 0.005 < np.mean(a.ce <= a.cs) < 0.02 and np.all((a.end < a.start) == (a.ce <= a.cs))
+    _, b, _ = cl["pileups"]
+    assert np.unique(b.start, return_counts=True)[1].min() > 32
+    assert cl["many_chroms"][2] == 40 and cl["negative"][0].start.min() < 0 and cl["negative"][1].start.min() < 0
+    a, b, _ = _oversized()
+    assert np.sum(b.start < 4000) > BS_BIG_MAX and b.start.max() > 9_000_000
+
+
+# ---------------------------------------------------------------- GPU side: resident sides, cached oracle answers
+def _dev(side):
+    from giql_amd.engine import DeviceSide
+
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.int32)).to("cuda:0")
+    return DeviceSide(t(side.chrom), t(side.start), t(side.end), side.start_off, side.end_off)
+
+
+@functools.lru_cache(maxsize=None)
+def resident(name):
+    a, b, nch = _oversized() if name == "oversized" else classes()[name]
+    return a, b, nch, _dev(a), _dev(b)
+
+
+@functools.lru_cache(maxsize=None)
+def want(name, what, *args):
+    a, b, _nch, _da, _db = resident(name)
+    if what == "pairs":
+        return ora.sort_pairs(*ora.c_inner(a, b, "sweep"))
+    if what == "semi":
+        return ora.c_semi_anti(a, b, False)
+    if what == "anti":
+        return ora.c_semi_anti(a, b, True)
+    if what == "count":
+        return ora.c_count(a, b, "sweep")
+    if what == "nearest":
+        return ora.c_nearest_k1(a, b, signed=args[0], method="sweep")
+    if what == "nearest_k":
+        return ora.c_nearest_k(a, b, args[0])
+    raise AssertionError(what)
+
+
+def _rows_equal(b, got, exp):
+    ok = exp >= 0
+    return (np.array_equal(got >= 0, ok) and np.array_equal(b.start[got[ok]], b.start[exp[ok]])
+            and np.array_equal(b.end[got[ok]], b.end[exp[ok]]))
+
+
+def _pairs(ra, rb):
+    return ora.sort_pairs(ra.cpu().numpy(), rb.cpu().numpy())
+
+
+def _density_engine(monkeypatch):
+    """A context with the production density rules but without the 2^21-row floor (giql_hip.hip reads the three
+    variables in this order: the floor first, then the two density bounds it reset)."""
+    from giql_amd.engine import HipEngine
+
+    monkeypatch.setenv("GIQL_HIP_LOCAL_MIN_ROWS", "1")
+    monkeypatch.setenv("GIQL_HIP_LOCAL_MIN_BUCKET_ROWS", "300")
+    monkeypatch.setenv("GIQL_HIP_LOCAL_MAX_BUCKET_ROWS", "2800")
+    e = HipEngine(0)
+    monkeypatch.delenv("GIQL_HIP_LOCAL_MIN_ROWS")
+    monkeypatch.delenv("GIQL_HIP_LOCAL_MIN_BUCKET_ROWS")
+    monkeypatch.delenv("GIQL_HIP_LOCAL_MAX_BUCKET_ROWS")
+    return e
+
+
+class Log:
+    """Every call of a walk: (family, class, round, operator, stats of that call)."""
+
+    def __init__(self):
+        self.calls = []
+
+    def add(self, eng, family, name, rnd, op):
+        self.calls.append((family, name, rnd, op, eng.stats()))
+
+    def transitions(self, family):
+        seq = [c[1] for c in self.calls if c[0] == family]
+        return set(zip(seq, seq[1:]))
+
+
+# ---- the twelve operators: each runs one call sequence on (class) and checks it against the oracle
+def op_inner_join(eng, name, log, fam, rnd):
+    _a, _b, nch, da, db = resident(name)
+    ra, rb = eng.inner_join(da, db, nch)
+    log.add(eng, fam, name, rnd, "inner_join")
+    assert np.array_equal(_pairs(ra, rb), want(name, "pairs")), (name, "inner_join")
+
+
+def _into(eng, name, cap):
+    _a, _b, nch, da, db = resident(name)
+    ra = torch.full((cap,), -7, dtype=torch.int32, device="cuda:0")
+    rb = torch.full((cap,), -7, dtype=torch.int32, device="cuda:0")
+    return ra, rb, eng.inner_join_into(da, db, nch, ra, rb)
+
+
+def op_into_exact(eng, name, log, fam, rnd):
+    w = want(name, "pairs")
+    ra, rb, n = _into(eng, name, w.shape[0])
+    log.add(eng, fam, name, rnd, "into_exact")
+    assert n == w.shape[0] and np.array_equal(_pairs(ra, rb), w), (name, "into_exact")
+
+
+def op_into_short(eng, name, log, fam, rnd):
+    from giql_amd import _lib
+
+    w = want(name, "pairs")
+    n = w.shape[0]
+    assert n > 0
+    with pytest.raises(_lib.GiqlHipError) as exc:
+        _into(eng, name, n - 1)
+    log.add(eng, fam, name, rnd, "into_short")
+    assert exc.value.code == _lib.GIQL_ERR_CAPACITY and eng.last_pairs == n, (name, str(exc.value), eng.last_pairs, n)
+    ra = torch.empty(n, dtype=torch.int32, device="cuda:0")
+    rb = torch.empty(n, dtype=torch.int32, device="cuda:0")
+    eng.inner_fill(ra, rb)
+    assert np.array_equal(_pairs(ra, rb), w), (name, "fill after GIQL_ERR_CAPACITY")
+
+
+def op_into_ample(eng, name, log, fam, rnd):
+    w = want(name, "pairs")
+    ra, rb, n = _into(eng, name, w.shape[0] + 4096)
+    log.add(eng, fam, name, rnd, "into_ample")
+    assert n == w.shape[0] and np.array_equal(_pairs(ra[:n], rb[:n]), w), (name, "into_ample")
+    if rnd == 2:    # (a call whose guesses missed may leave its abandoned attempt's pairs past the count: giql_hip.h)
+        assert int((ra[n:] != -7).sum()) == 0 and int((rb[n:] != -7).sum()) == 0, (name, "written past the count")
+
+
+def op_plan_fill(eng, name, log, fam, rnd, intruder=None):
+    from giql_amd import _lib
+
+    _a, _b, nch, da, db = resident(name)
+    w = want(name, "pairs")
+    n = eng.inner_plan(da, db, nch)
+    log.add(eng, fam, name, rnd, "plan")
+    assert n == w.shape[0], (name, "plan count")
+    ra = torch.empty(n, dtype=torch.int32, device="cuda:0")
+    rb = torch.empty(n, dtype=torch.int32, device="cuda:0")
+    if intruder is not None:
+        # a call that reuses the plan's workspace between the plan and its fill: the plan is gone
+        intruder(eng, name)
+        for consume in (lambda: eng.inner_fill(ra, rb), lambda: eng.plan_export(ra, ra, ra, rb)):
+            with pytest.raises(_lib.GiqlHipError) as exc:
+                consume()
+            assert exc.value.code == _lib.GIQL_ERR_STATE and "without a successful inner_plan" in str(exc.value), exc.value
+        assert eng.inner_plan(da, db, nch) == n
+    eng.inner_fill(ra, rb)
+    assert np.array_equal(_pairs(ra, rb), w), (name, "plan + fill")
+
+
+def op_semi(eng, name, log, fam, rnd):
+    _a, _b, nch, da, db = resident(name)
+    got = eng.semi_join(da, db, nch).cpu().numpy()
+    log.add(eng, fam, name, rnd, "semi")
+    assert np.array_equal(got, want(name, "semi")), (name, "semi")
+
+
+def op_anti(eng, name, log, fam, rnd):
+    _a, _b, nch, da, db = resident(name)
+    got = eng.anti_join(da, db, nch).cpu().numpy()
+    log.add(eng, fam, name, rnd, "anti")
+    assert np.array_equal(got, want(name, "anti")), (name, "anti")
+
+
+def op_count(eng, name, log, fam, rnd):
+    _a, _b, nch, da, db = resident(name)
+    got = eng.count_overlaps(da, db, nch).cpu().numpy()
+    log.add(eng, fam, name, rnd, "count")
+    assert np.array_equal(got, want(name, "count")), (name, "count")
+
+
+def _nearest_refused(eng, call):
+    """Inverted rows: NEAREST refuses them (the walk goes on on the same context: it must stay usable)."""
+    from giql_amd import _lib
+
+    with pytest.raises(_lib.GiqlHipError) as exc:
+        call()
+    assert exc.value.code == _lib.GIQL_ERR_INVALID, exc.value
+
+
+def op_nearest(eng, name, log, fam, rnd):
+    _a, b, nch, da, db = resident(name)
+    signed = len(log.calls) % 2 == 1                # alternating signed / unsigned along the walk
+    if name == "irregular":
+        _nearest_refused(eng, lambda: eng.nearest(da, db, nch, signed=signed))
+        log.add(eng, fam, name, rnd, "nearest")
+        return
+    idx, dist = eng.nearest(da, db, nch, signed=signed)
+    log.add(eng, fam, name, rnd, "nearest")
+    wi, wd = want(name, "nearest", signed)
+    assert np.array_equal(dist.cpu().numpy(), wd), (name, "nearest distance", signed)
+    assert _rows_equal(b, idx.cpu().numpy(), wi), (name, "nearest rows", signed)
+
+
+def op_nearest_k(eng, name, log, fam, rnd):
+    _a, b, nch, da, db = resident(name)
+    if name == "irregular":
+        _nearest_refused(eng, lambda: eng.nearest_k(da, db, nch, 3))
+        log.add(eng, fam, name, rnd, "nearest_k")
+        return
+    idx, dist = eng.nearest_k(da, db, nch, 3)
+    log.add(eng, fam, name, rnd, "nearest_k")
+    wi, wd = want(name, "nearest_k", 3)
+    assert np.array_equal(dist.cpu().numpy(), wd), (name, "nearest_k distance")
+    assert _rows_equal(b, idx.cpu().numpy(), wi), (name, "nearest_k rows")
+
+
+def op_group_rows(eng, name, log, fam, rnd):
+    _a, b, nch, _da, db = resident(name)
+    gid, rep = eng.group_rows(db, nch)
+    log.add(eng, fam, name, rnd, "group_rows")
+    gid, rep = gid.cpu().numpy(), rep.cpu().numpy()
+    trip = np.stack([b.chrom, b.start, b.end], 1)
+    assert rep.shape[0] == np.unique(trip, axis=0).shape[0], (name, "group count")
+    assert np.array_equal(trip[rep[gid]], trip), (name, "group rows")
+
+
+def op_index(eng, name, log, fam, rnd):
+    from giql_amd import _lib
+
+    _a, _b, nch, da, db = resident(name)
+    try:
+        index = eng.index_create(db, nch)
+    except _lib.GiqlHipError as exc:
+        log.add(eng, fam, name, rnd, "index_declined")
+        assert exc.code == _lib.GIQL_ERR_STATE and name in INDEX_DECLINES, (name, str(exc))
+        assert INDEX_DECLINES[name] in str(exc), (name, str(exc))
+        return
+    assert name not in INDEX_DECLINES, (name, "an index was built")
+    try:
+        ra, rb = eng.inner_join_indexed(da, index)
+        log.add(eng, fam, name, rnd, "indexed")
+        assert np.array_equal(_pairs(ra, rb), want(name, "pairs")), (name, "indexed")
+    except _lib.GiqlHipError as exc:
+        log.add(eng, fam, name, rnd, "indexed_declined")
+        assert exc.code == _lib.GIQL_ERR_STATE and name in INDEX_QUERY_DECLINES, (name, str(exc))
+    finally:
+        index.close()
+
+
+FAMILIES = {
+    "inner": [op_inner_join, op_into_exact, op_into_short, op_into_ample, op_plan_fill],
+    "row": [op_semi, op_anti, op_count],
+    "nearest": [op_nearest, op_nearest_k],
+    "group_rows": [op_group_rows],
+    "index": [op_index],
+}
+ALL_OPS = [op for ops in FAMILIES.values() for op in ops]
+
+
+def _check_signature(log, name):
+    st = log.calls[-1][4]
+    assert SIGNATURES[name](st), (name, [(k, st[k]) for k in ("sort_local", "bucket_bits", "count_fused", "join_form",
+                                                                "swapped", "presorted", "n_irregular_a", "sort_resorted")])
+
+
+def _check_width(log, name):
+    """A settled call of a family that sorts on the tight span: the bucket width its density asks for."""
+    st = log.calls[-1][4]
+    if name in WIDTHS:
+        assert st["sort_local"] and st["bucket_bits"] == WIDTHS[name], (name, log.calls[-1][3], st["sort_local"],
+                                                                        st["bucket_bits"], st["span"])
+    elif name == "sparse":
+        assert not st["sort_local"], (name, log.calls[-1][3])
+
+
+def _visit(eng, family, name, log):
+    for rnd in (1, 2):          # 1: on the previous class's guesses; 2: on this class's own
+        for op in FAMILIES[family]:
+            op(eng, name, log, family, rnd)
+            if family == "inner" and rnd == 2 and op is op_inner_join:
+                _check_signature(log, name)
+            if family in WIDTH_FAMILIES and rnd == 2:
+                _check_width(log, name)
+
+
+# ---------------------------------------------------------------- Walk 1
+@pytest.mark.gpu
+@pytest.mark.parametrize("family", list(FAMILIES))
+def test_walk_every_ordered_pair_of_classes(monkeypatch, family):
+    eng = _density_engine(monkeypatch)
+    log = Log()
+    try:
+        for v in eulerian_circuit(len(NAMES)):
+            _visit(eng, family, NAMES[v], log)
+    finally:
+        eng.close()
+    pairs = log.transitions(family)
+    print(f"\n[{family}] ordered class pairs covered: {len(pairs)} of {len(NAMES) ** 2}")
+    assert pairs == {(x, y) for x in NAMES for y in NAMES}
+    if family in WIDTH_FAMILIES:
+        # the wrong-width guess was crossed: a first call on a narrow class ran the bucket stage at another width
+        # than the one its settled calls took (asserted equal to WIDTHS[name] by _check_width)
+        for name in ("w15", "w14", "w13"):
+            firsts = [c[4] for c in log.calls if c[1] == name and c[2] == 1]
+            crossed = {st["bucket_bits"] for st in firsts if st["sort_local"] and st["bucket_bits"] != WIDTHS[name]}
+            print(f"[{family}] {name}: first calls ran at widths {sorted(crossed)} before settling on {WIDTHS[name]}")
+            assert crossed, (family, name)
+    if family == "inner":
+        assert any(c[4]["bucket_join"] for c in log.calls if c[2] == 2), "no settled INNER call joined in the bucket stage"
+
+
+# ---------------------------------------------------------------- Walk 2 (mixed operators, plans interrupted)
+def _intrude_select(eng, name):
+    _a, _b, _nch, da, _db = resident(name)
+    keep = eng.select([(("a", da.start), ">=", ("lit", 0))], n=da.n, n_rows_a=da.n, want=("a",))[0].cpu().numpy()
+    assert np.array_equal(keep, np.nonzero(resident(name)[0].start >= 0)[0]), (name, "select")
+
+
+def _intrude_take_utf8(eng, name):
+    words = [f"row{i}" * (i % 4) for i in range(300)]
+    offsets = np.concatenate([[0], np.cumsum([len(w) for w in words])]).astype(np.int32)
+    data = np.frombuffer("".join(words).encode(), np.uint8).copy()
+    idx = np.random.default_rng(len(name)).integers(0, len(words), 5000).astype(np.int32)
+    d = lambda x: torch.from_numpy(x).to("cuda:0")
+    o, b = eng.take_utf8(d(offsets), d(data), d(idx))
+    got = bytes(b.cpu().numpy()).decode()
+    assert got == "".join(words[i] for i in idx) and o.cpu().numpy()[-1] == len(got), (name, "take_utf8")
+
+
+@pytest.mark.gpu
+def test_walk_mixed_operators_with_interrupted_plans(monkeypatch):
+    eng = _density_engine(monkeypatch)
+    log = Log()
+    r = np.random.default_rng(2027)
+    visits = list(r.permutation(len(NAMES))) + list(r.permutation(len(NAMES)))
+    interrupted = {"select": 0, "take_utf8": 0}
+    try:
+        for v in visits:
+            name = NAMES[v]
+            for k in r.permutation(len(ALL_OPS)):
+                op = ALL_OPS[k]
+                if op is op_plan_fill:
+                    which = ("select", "take_utf8", None)[int(r.integers(0, 3))]
+                    intruder = {"select": _intrude_select, "take_utf8": _intrude_take_utf8, None: None}[which]
+                    op(eng, name, log, "mixed", 1, intruder=intruder)
+                    if which:
+                        interrupted[which] += 1
+                else:
+                    op(eng, name, log, "mixed", 1)
+    finally:
+        eng.close()
+    print(f"\n[mixed] ordered class pairs covered: {len(log.transitions('mixed'))}; interrupted plans: {interrupted}")
+    assert interrupted["select"] > 0 and interrupted["take_utf8"] > 0
+
+
+# ---------------------------------------------------------------- Leg 3: the sticky four-pass fallback
+@pytest.mark.gpu
+def test_oversized_bucket_switches_every_context_to_four_passes_for_good(monkeypatch):
+    log = Log()
+    eng = None
+    try:
+        for x in NAMES:
+            if eng is not None:
+                eng.close()
+            eng = _density_engine(monkeypatch)
+            for _ in range(2):
+                op_inner_join(eng, x, log, "settle", 1)
+                op_count(eng, x, log, "settle", 1)
+            for rnd in (1, 2):   # the first call decides its width from X's span, the second from its own
+                op_inner_join(eng, "oversized", log, "oversized", rnd)
+                op_count(eng, "oversized", log, "oversized", rnd)
+            assert log.calls[-1][4]["sort_resorted"], (x, "no four-pass fallback after an oversized bucket")
+        # on the last of these contexts -- today's behaviour is one-way: it stays in the four-pass sort (exact results)
+        for name in NAMES:
+            for op in ALL_OPS:
+                op(eng, name, log, "after", 1)
+                st = log.calls[-1][4]
+                if op is not op_index:      # (an index is built in three stages whatever the context: index_bits)
+                    assert not st["sort_local"] and st["sort_resorted"], (name, op.__name__)
+    finally:
+        if eng is not None:
+            eng.close()
+
+
+# ---------------------------------------------------------------- the 25a7a2b regression, as a walk finds it
+@pytest.mark.gpu
+def test_pileups_then_narrow_buckets_nearest_and_group_rows_seed_777(monkeypatch):
+    """After pile-ups (NEAREST's two-sort plan), a dense table (narrow buckets): NEAREST k = 1 / k = 3 and group_rows
+    must order ties by (start, end), not by input order (commit 25a7a2b, found by tools/soak.py seed 777).  The bug
+    path is the two-sort plan (sticky after pile-ups) with buckets narrower than 2^16 keys: asserted on the NEAREST
+    calls, so that a change of the density rules cannot quietly move this test off it.  (group_rows reports no sort
+    statistics; its results are checked all the same.)"""
+    for dense in ("w13", "w14"):
+        for op in (op_nearest, op_nearest_k, op_group_rows):
+            eng = _density_engine(monkeypatch)
+            log = Log()
+            try:
+                op(eng, "pileups", log, "regression", 1)
+                op(eng, dense, log, "regression", 1)
+                op(eng, dense, log, "regression", 2)
+                if op is not op_group_rows:
+                    st = log.calls[-1][4]
+                    assert st["sort_local"] and st["bucket_bits"] == WIDTHS[dense], (dense, op.__name__, st["bucket_bits"])
+            finally:
+                eng.close()
+
+
+# ---------------------------------------------------------------- Leg 4: production density, default context
+LEG4 = {   # name -> (reads: rows, chromosomes, axis per chromosome), the bucket width the density asks for (0: none)
+    16: (3_000_000, 1, 131_000_000),         # ~1,500 rows per 65,536 keys
+    15: (3_000_000, 1, 60_000_000),          # (tests/test_bucket_width.py::test_the_density_chooses_the_width)
+    14: (3_000_000, 1, 30_000_000),
+    13: (4_000_000, 1, 12_000_000),
+    0: (3_000_000, 8, 200_000_000),          # ~120 rows per 65,536 keys: the four global passes
+}
+
+
+@functools.lru_cache(maxsize=None)
+def leg4(bits):
+    n_u, nch, span = LEG4[bits]
+    reads = _rows(np.random.default_rng(4500 + bits), n_u, nch, span, 100)
+    peaks = _rows(np.random.default_rng(4600 + bits), 4000, nch, span, (50, 600))
+    return (peaks, reads, nch, _dev(peaks), _dev(reads), ora.sort_pairs(*ora.c_inner(peaks, reads, "sweep")),
+            ora.c_nearest_k1(peaks, reads, method="sweep"))
+
+
+@pytest.mark.gpu
+def test_production_density_every_ordered_pair_of_widths():
+    from giql_amd.engine import HipEngine
+
+    order = list(LEG4)
+    eng = HipEngine(0)
+    seen = set()
+    prev = None
+    try:
+        for v in eulerian_circuit(len(order)):
+            bits = order[v]
+            _peaks, reads, nch, da, db, pairs, (wi, wd) = leg4(bits)
+            for rnd in (1, 2):
+                ra, rb = eng.inner_join(da, db, nch)
+                st = eng.stats()
+                assert np.array_equal(_pairs(ra, rb), pairs), (prev, bits, rnd)
+                if rnd == 2:
+                    if bits:
+                        assert st["sort_local"] and st["bucket_bits"] == bits and not st["sort_resorted"], (prev, bits, st)
+                    else:
+                        assert not st["sort_local"], (prev, bits)
+                idx, dist = eng.nearest(da, db, nch)
+                assert np.array_equal(dist.cpu().numpy(), wd) and _rows_equal(reads, idx.cpu().numpy(), wi), (prev, bits)
+            if prev is not None:
+                seen.add((prev, bits))
+            prev = bits
+    finally:
+        eng.close()
+    print(f"\n[production density] ordered width pairs covered: {len(seen)} of {len(order) ** 2}")
+    assert seen == {(x, y) for x in order for y in order}

@@ -1609,3 +1609,74 @@ def test_nearest_sorts_both_sides_from_their_raw_columns_once_the_layout_is_know
     b40 = rand_side(1954, 30_000, 40, 500_000, 300)
     check(a40, b40, 40)
     check(a40, b40, 40)
+
+
+@pytest.mark.parametrize("intruder", ["select", "select_expr", "take_utf8_plan"])
+def test_calls_that_reuse_the_workspace_end_the_plan(eng_fresh, intruder):
+    """giql_hip_select_dev / giql_hip_select_expr_dev / giql_hip_take_utf8_plan_dev carve their scratch from the start
+    of the context's workspace, where an INNER plan keeps its sorted ids, bounds and offsets: after one of them,
+    inner_fill and plan_export refuse with GIQL_ERR_STATE instead of reading a clobbered plan (include/giql_hip.h).
+    The plan here is in the compact single-range form, so that without the intruder both calls succeed."""
+    import ctypes
+
+    from giql_amd import _lib
+
+    e = eng_fresh
+    a = rand_side(2101, 30_000, 4, 3_000_000, 900)
+    b = uniform_side(2102, 200_000, 4, 3_000_000, 150)
+    want = ora.sort_pairs(*ora.c_inner(a, b, "sweep"))
+    da, db = dev(a), dev(b)
+    i32 = dict(dtype=torch.int32, device="cuda:0")
+    n_rows = a.n
+
+    def intrude():
+        if intruder == "take_utf8_plan":
+            offsets = torch.arange(0, 3 * (n_rows + 1), 3, **i32)
+            data = torch.zeros(3 * n_rows, dtype=torch.uint8, device="cuda:0")
+            idx = torch.arange(n_rows - 1, -1, -1, **i32)
+            off, out = e.take_utf8(offsets, data, idx)
+            assert int(off[-1]) == 3 * n_rows and out.numel() == 3 * n_rows
+            return
+        keep_expected = np.nonzero(a.start >= 1_000_000)[0]
+        preds = [(("a", da.start), ">=", ("lit", 1_000_000))]
+        if intruder == "select_expr":
+            preds = [(("expr", ("+", ("a", da.start), ("lit", 0))), ">=", ("lit", 1_000_000))]
+            kept = e.select(preds, n=n_rows, n_rows_a=n_rows, want=("a",))[0]
+        else:      # the plain entry point (the engine itself always calls the expression one)
+            c_preds, k, _keep_alive, _nodes, n_nodes = e._c_preds(preds)
+            assert n_nodes == 0
+            out_a = torch.empty(n_rows, **i32)
+            n_kept = ctypes.c_int64(0)
+            _lib.check(e._L.giql_hip_select_dev(e._h, c_preds, k, None, n_rows, None, 0, n_rows, out_a.data_ptr(), None,
+                                                ctypes.byref(n_kept), e._stream()))
+            kept = out_a[: int(n_kept.value)]
+        assert np.array_equal(kept.cpu().numpy(), keep_expected)
+
+    def plan():
+        n = e.inner_plan(da, db, 4)
+        assert n == want.shape[0]
+        return n
+
+    # without the intruder: fill and export both follow the plan
+    n = plan()
+    _qa, n_q, n_s = e.plan_sizes()
+    assert n_q > 0 and n_s > 0
+    ra, rb = torch.empty(n, **i32), torch.empty(n, **i32)
+    e.inner_fill(ra, rb)
+    assert np.array_equal(ora.sort_pairs(ra.cpu().numpy(), rb.cpu().numpy()), want)
+    q_rid, lo, cnt, s_rid = torch.empty(n_q, **i32), torch.empty(n_q, **i32), torch.empty(n_q, **i32), torch.empty(n_s, **i32)
+    e.plan_export(q_rid, lo, cnt, s_rid)
+    # with it: both refuse
+    for consume in ("fill", "export"):
+        plan()
+        intrude()
+        with pytest.raises(_lib.GiqlHipError) as exc:
+            if consume == "fill":
+                e.inner_fill(ra, rb)
+            else:
+                e.plan_export(q_rid, lo, cnt, s_rid)
+        assert exc.value.code == _lib.GIQL_ERR_STATE and "without a successful inner_plan" in str(exc.value)
+    # ... and the context plans again as before
+    plan()
+    e.inner_fill(ra, rb)
+    assert np.array_equal(ora.sort_pairs(ra.cpu().numpy(), rb.cpu().numpy()), want)
