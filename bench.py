@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the INTERSECTS hot path on MI355X, one JSON line per run.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--full]
 
 A *step* is one full pass of the hot path over one batch of synthetic input already resident
 in HBM.  The default workload is BASELINE.json configs[3] (cfg 4): 10M
@@ -21,8 +21,14 @@ work is fixed as N grows ("strong" scaling).
 
 The line carries ``roofline`` (dominant kernel: algorithmic bytes per launch, as accounted by
 the host code that issues the launches, over the hipEvent-measured launch time of the timed
-steps) and ``cpu_baseline`` (the reference's DuckDB path when ``import duckdb`` works on the box,
-else the oracle's OpenMP sort-merge port), which is also the run's parity check.
+steps).  A plain run stops there: set up, warm up, time the steps, dump (``--dump-outputs``), print.
+
+``--full`` adds every leg that follows the timed region and that the headline does not need:
+``cpu_baseline`` (the reference's DuckDB path when ``import duckdb`` works on the box, else the
+oracle's OpenMP sort-merge port), which is also the run's parity check (at N > 1: the verification
+of the gathered result; with ``--shard-of``: the shard's own check too); and, after an INNER
+workload at N = 1, the general-form, end-to-end and copy-probe legs.  ``--no-cpu-baseline``,
+``--no-extras`` and ``--no-verify`` leave parts of it out.
 
 ``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (float64, under 64 MB in
 all): INNER -> ``n_pairs`` and a seeded, order-independent sample of the pairs as ``row_a`` / ``row_b`` sorted by
@@ -90,9 +96,13 @@ def parse_args():
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what follows the timed region beyond the headline: the CPU leg (cpu_baseline and "
+                        "its parity check; at N > 1 the verification of the gathered result) and the general-form / "
+                        "end-to-end / copy-probe legs.  Without it a run only warms up, times, dumps and prints")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU leg")
     p.add_argument("--no-extras", action="store_true",
-                   help="skip the general-form / end-to-end / copy-probe legs that follow the timed region")
+                   help="--full without the general-form / end-to-end / copy-probe legs that follow the timed region")
     p.add_argument("--exchange", default="plan", choices=["plan", "pairs", "none"],
                    help="N>1: what the ranks all-gather -- the compact plan (default), the expanded pairs, nothing")
     p.add_argument("--no-gather", action="store_true", help="same as --exchange none (compute-only scaling)")
@@ -108,17 +118,18 @@ def parse_args():
     p.add_argument("--gather", default="all", choices=["all", "root"],
                    help="N>1: who ends up with the result -- every rank (the all-gatherv of the north star) or rank 0 "
                         "only (the other ranks send their block there and skip the expansion)")
-    p.add_argument("--verify", action="store_true", help="(the default at N>1; kept for old command lines)")
+    p.add_argument("--verify", action="store_true",
+                   help="N>1: run the CPU leg's check of the gathered result without --full (the default with it)")
     p.add_argument("--no-verify", action="store_true",
-                   help="N>1: skip the CPU leg.  By default rank 0 runs it on the WHOLE workload after the timed region "
-                        "(the other ranks wait), checks the gathered result against it (count + multiset checksum) and "
-                        "the run exits non-zero on a mismatch")
+                   help="N>1 --full: skip the CPU leg.  By default rank 0 runs it on the WHOLE workload after the timed "
+                        "region (the other ranks wait), checks the gathered result against it (count + multiset "
+                        "checksum) and the run exits non-zero on a mismatch")
     p.add_argument("--master-port", type=int, default=29531)
     p.add_argument("--shard-of", type=int, default=0,
                    help="--gpus 1 only: measure what ONE rank of an N-rank run of the INNER headline executes -- rank "
                         "--shard-rank's LPT share of the chromosomes through exactly the per-rank code (local plan + "
-                        "export; the local one-call join; the expansion of all N ranks' plan blocks), each verified "
-                        "against the CPU leg.  An extra line, never the headline")
+                        "export; the local one-call join; the expansion of all N ranks' plan blocks), with --full each "
+                        "verified against the CPU leg.  An extra line, never the headline")
     p.add_argument("--shard-rank", type=int, default=0)
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64; "
@@ -132,7 +143,9 @@ def parse_args():
         a.exchange = "none"
     if a.dump_outputs and a.gpus > 1 and a.exchange == "none":
         p.error("--dump-outputs at N > 1 needs the gathered result: not with --exchange none")
-    a.verify = (a.gpus > 1 or a.verify or a.force_exchange) and not a.no_verify
+    if not a.full:   # a plain run: nothing after the timed region but the dump and the line
+        a.no_cpu_baseline = a.no_extras = True
+    a.verify = ((a.full and (a.gpus > 1 or a.force_exchange)) or a.verify) and not a.no_verify
     return a
 
 
@@ -487,7 +500,7 @@ def run_shard(args):
     ``execute(devices=[...])``: results stay sharded); (C) the expansion of ALL N ranks' plan blocks into the global
     pairs -- what follows the exchange on every rank (the peers' blocks are made here, one shard after the other,
     outside the timed region).  Wire time is not measured (DESIGN.md section 6 keeps a stated model for it).
-    Parity: (B) against the oracle on the shard's rows, (A) + (C) against the oracle on the whole workload."""
+    Parity (``--full``): (B) against the oracle on the shard's rows, (A) + (C) against the oracle on the whole workload."""
     import numpy as np
     import torch
 
@@ -580,9 +593,12 @@ def run_shard(args):
     phb = eng_b.stats()
     part_b["phase_ms"] = {k: round(v, 3) for k, v in phb["phase_ms"].items() if v > 0}
     part_b["launches"] = int(sum(phb["phase_launches"].values()))
-    wa, wb = ora.c_inner(ora.Side(*ha), ora.Side(*hb), "sweep")
-    cpu_local = (int(wa.shape[0]), ora.c_pairs_checksum(wa, wb))
-    del wa, wb, out
+    cpu_local = None
+    if args.full:   # the CPU leg of the shard's own rows
+        wa, wb = ora.c_inner(ora.Side(*ha), ora.Side(*hb), "sweep")
+        cpu_local = (int(wa.shape[0]), ora.c_pairs_checksum(wa, wb))
+        del wa, wb
+    del out
     eng_b.close()
 
     # ---- (C) every rank's block (peers planned here one after the other), then the timed expansion of all of them
@@ -610,8 +626,10 @@ def run_shard(args):
     part_c = timed(expand_all, args.steps, args.warmup)
     dumped = dump_outputs(args.dump_outputs, pairs=(gout[0][:total], gout[1][:total])) if args.dump_outputs else None
     gpu_all = (int(total), eng.pairs_checksum(gout[0][:total], gout[1][:total]))
-    parity = {"local_join_pairs_equal": gpu_local[0] == cpu_local[0] == n_mine,
-              "local_join_checksum_equal": gpu_local[1] == cpu_local[1]}
+    parity = {}
+    if cpu_local is not None:
+        parity = {"local_join_pairs_equal": gpu_local[0] == cpu_local[0] == n_mine,
+                  "local_join_checksum_equal": gpu_local[1] == cpu_local[1]}
     cpu_baseline = None
     if not args.no_cpu_baseline:
         cpu_baseline, ref = cpu_baseline_inner(args, wl, n_chrom, layout, whole=True)
@@ -644,7 +662,8 @@ def run_shard(args):
 # ------------------------------------------------------- the join against a table index
 def run_indexed(args):
     """``--workload cfg4_indexed_...``: table B indexed once (outside the timed region, its build time reported), a
-    step = ``giql_hip_inner_join_indexed_dev`` of table A against the index.  Full parity against the CPU leg."""
+    step = ``giql_hip_inner_join_indexed_dev`` of table A against the index.  ``--full``: full parity against the CPU
+    leg."""
     import torch
 
     from giql_amd.engine import DeviceSide, HipEngine
@@ -1074,7 +1093,7 @@ def run_inner(args):
 
         cpu_baseline = None
         if (not args.no_cpu_baseline and world == 1 and not distributed) or (distributed and args.verify):
-            # rank 0 at N = 1 (the contract); at N > 1 the same leg checks the GATHERED result (--no-verify skips it)
+            # --full: rank 0 at N = 1; at N > 1 the same leg checks the GATHERED result (--no-verify skips it)
             layout = ([[c for c in range(n_chrom) if assign[c] == r] for r in range(world)]
                       if world > 1 and genome == HG38 else None)
             cpu_baseline, ref = cpu_baseline_inner(args, wl, n_chrom, layout, whole=distributed)
@@ -1425,7 +1444,7 @@ def run_rowop(args):
         roofline.update({"kernel": f"whole operator (dominant phase: {dom})", "achieved": w["achieved"], "frac": w["frac"]})
 
     cpu_baseline = None
-    # the CPU leg: at N = 1 (the contract); at N > 1 only to verify the gathered result (--verify)
+    # the CPU leg (--full): at N = 1; at N > 1 only to verify the gathered result (--verify)
     if (not args.no_cpu_baseline and not distributed) or (distributed and args.verify):
         from oracle import pyoracle as ora
 

@@ -105,6 +105,26 @@ def test_steps_and_warmup_are_checked(monkeypatch):
             bench.parse_args()
 
 
+def test_only_full_runs_the_legs_after_the_timed_region(monkeypatch):
+    def parsed(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + list(argv))
+        a = bench.parse_args()
+        return a.full, a.no_cpu_baseline, a.no_extras, a.verify
+
+    # a plain run: no CPU leg, no extras, no verification of a gathered result unless asked for by name
+    assert parsed("--gpus", "1", "--steps", "3", "--warmup", "1") == (False, True, True, False)
+    assert parsed("--gpus", "2") == (False, True, True, False)
+    assert parsed("--force-exchange") == (False, True, True, False)
+    assert parsed("--gpus", "2", "--verify") == (False, True, True, True)
+    # --full: every leg, as the switches that leave parts of it out say
+    assert parsed("--full") == (True, False, False, False)
+    assert parsed("--full", "--no-cpu-baseline") == (True, True, False, False)
+    assert parsed("--full", "--no-extras") == (True, False, True, False)
+    assert parsed("--full", "--gpus", "2") == (True, False, False, True)
+    assert parsed("--full", "--force-exchange") == (True, False, False, True)
+    assert parsed("--full", "--gpus", "2", "--no-verify") == (True, False, False, False)
+
+
 def test_pair_sample_depends_on_the_pairs_not_their_order():
     import numpy as np
     import torch

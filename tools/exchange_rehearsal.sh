@@ -1,18 +1,20 @@
 #!/usr/bin/env bash
 # The N > 1 paths of bench.py on the ONE GPU this pool gives: 2 ranks over gloo (ranks share the card; the
-# exchange runs through host memory -- correctness of sharding + exchange, verified against the CPU leg by
-# default) and 1 rank over RCCL with the exchange forced, for every exchange implementation / gather mode.
-# usage: tools/exchange_rehearsal.sh <tag>
+# exchange runs through host memory -- correctness of sharding + exchange, verified against the CPU leg: --full)
+# and 1 rank over RCCL with the exchange forced, for every exchange implementation / gather mode.
+# usage: [OUT=dir] tools/exchange_rehearsal.sh <tag>
 TAG="${1:-x}"
+OUT="${OUT:-logs}"
 REPO="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 cd "${REPO}"
+mkdir -p "${OUT}"
 run() {
   name="$1"; shift
-  echo "=== ${name}: python bench.py $*"
-  timeout -k 10 280 python3 bench.py "$@" > "gpurun_out/${TAG}_${name}.json.log" 2> "gpurun_out/${TAG}_${name}.err"
+  echo "=== ${name}: python bench.py --full $*"
+  timeout -k 10 280 python3 bench.py --full "$@" > "${OUT}/${TAG}_${name}.json.log" 2> "${OUT}/${TAG}_${name}.err"
   rc=$?
   echo "rc=${rc}"
-  tail -n 1 "gpurun_out/${TAG}_${name}.json.log" | python3 -c "
+  tail -n 1 "${OUT}/${TAG}_${name}.json.log" | python3 -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read())
