@@ -675,7 +675,10 @@ class HipEngine:
 
     def take_utf8(self, offsets, data, idx):
         """``take`` of an Arrow utf8/binary column held as device tensors: int32
-        ``offsets[n_rows + 1]`` and uint8 ``data``.  Returns ``(out_offsets, out_data)``."""
+        ``offsets[n_rows + 1]`` and uint8 ``data``.  Returns ``(out_offsets, out_data)``.
+        One call takes at most 0x7FFFFFF0 ids and 0x7FFFFFFF gathered bytes (int32 output
+        offsets): past either it raises ``GiqlHipError``; ``execute`` splits such a gather
+        by rows (``execute.plan_utf8_slices``)."""
         torch = _torch()
         if offsets.dtype != torch.int32 or data.dtype != torch.uint8 or idx.dtype != torch.int32:
             raise ValueError("offsets/idx must be int32 and data uint8")
@@ -801,6 +804,9 @@ class HipEngine:
             o.valid = valid.data_ptr() if valid.numel() else None
         return o, (t, valid)
 
+    #: candidates per ``giql_hip_select_expr_dev`` call; the C ABI takes at most 0x7FFFFFF0
+    SELECT_SLICE = 1 << 30
+
     def select(self, preds, idx_a=None, idx_b=None, n=None, n_rows_a=0, n_rows_b=0, want=("a", "b")):
         """Stable filter by residual predicates (the extra ON / WHERE conditions the
         reference inlines beside the INTERSECTS, ``intersects_duckdb.py:1164-1177,
@@ -810,24 +816,44 @@ class HipEngine:
         or ``("lit", value)`` and ``op`` one of ``= != <> < <= > >= isnull notnull``; the
         predicates are AND-ed, adjacent ones sharing a non-zero ``group`` are OR-ed.  Candidates are the
         pairs ``(idx_a[i], idx_b[i])``; a missing id array means "the candidate index".
-        Returns the kept ``(ids_a, ids_b)`` (``None`` for a side not in ``want``)."""
+        Returns the kept ``(ids_a, ids_b)`` (``None`` for a side not in ``want``).
+
+        Any ``n`` is accepted: the C ABI takes at most 0x7FFFFFF0 candidates per call, so they
+        are filtered in slices of :attr:`SELECT_SLICE`, each slice's kept ids written straight
+        after the previous slice's into the one output.  A slice past the first addresses a
+        side without an id array through ``arange(lo, hi)``: the candidate index stays global."""
         torch = _torch()
         if n is None:
             n = int((idx_a if idx_a is not None else idx_b).shape[0])
+        n = int(n)
         c_preds, k, _keep_alive, c_nodes, n_nodes = self._c_preds(preds)
         for t in (idx_a, idx_b):
             if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or int(t.shape[0]) != n):
                 raise ValueError("id arrays must be contiguous int32 tensors of n rows")
         out_a = torch.empty(n, dtype=torch.int32, device=self.device) if "a" in want else None
         out_b = torch.empty(n, dtype=torch.int32, device=self.device) if "b" in want else None
-        kept = ctypes.c_int64(0)
-        _lib.check(self._L.giql_hip_select_expr_dev(
-            self._h, c_preds, k, c_nodes if n_nodes else None, n_nodes,
-            idx_a.data_ptr() if idx_a is not None and n else None, int(n_rows_a),
-            idx_b.data_ptr() if idx_b is not None and n else None, int(n_rows_b), int(n),
-            out_a.data_ptr() if out_a is not None and n else None,
-            out_b.data_ptr() if out_b is not None and n else None, ctypes.byref(kept), self._stream()))
-        m = int(kept.value)
+        m = 0
+        for lo in range(0, max(n, 1), self.SELECT_SLICE):
+            hi = min(n, lo + self.SELECT_SLICE)
+            ids, rows = [], []
+            for t, n_rows in ((idx_a, int(n_rows_a)), (idx_b, int(n_rows_b))):
+                if t is not None:
+                    t = t[lo:hi]
+                elif lo:
+                    # the first slice has checked a side addressed by the candidate index against its
+                    # row count: a used side with n_rows 0 has failed there, so 0 here means "unused"
+                    t = torch.arange(lo, hi, dtype=torch.int32, device=self.device)
+                    n_rows = n_rows or n
+                ids.append(t)
+                rows.append(n_rows)
+            kept = ctypes.c_int64(0)
+            _lib.check(self._L.giql_hip_select_expr_dev(
+                self._h, c_preds, k, c_nodes if n_nodes else None, n_nodes,
+                ids[0].data_ptr() if ids[0] is not None and hi > lo else None, rows[0],
+                ids[1].data_ptr() if ids[1] is not None and hi > lo else None, rows[1], hi - lo,
+                out_a[m:].data_ptr() if out_a is not None and hi > lo else None,
+                out_b[m:].data_ptr() if out_b is not None and hi > lo else None, ctypes.byref(kept), self._stream()))
+            m += int(kept.value)
         return (out_a[:m] if out_a is not None else None, out_b[:m] if out_b is not None else None)
 
     def mark(self, idx, n_rows: int):

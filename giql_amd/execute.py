@@ -878,6 +878,49 @@ def _to_host(t) -> np.ndarray:
     return host.numpy()
 
 
+#: what one ``giql_hip_take_utf8_plan_dev`` call accepts: int32 output offsets, at most 0x7FFFFFF0 rows
+UTF8_MAX_BYTES = 0x7FFFFFFF
+UTF8_MAX_ROWS = 0x7FFFFFF0
+
+
+def plan_utf8_slices(lengths: np.ndarray, max_bytes: int = UTF8_MAX_BYTES,
+                     max_rows: int = UTF8_MAX_ROWS) -> list[tuple[int, int]]:
+    """Split the gathered rows of a string column, whose byte lengths are ``lengths``, into
+    consecutive ``(row_lo, row_hi)`` slices of at most ``max_rows`` rows and ``max_bytes`` bytes
+    each, every slice as long as the limits allow.  Empty input gives no slice; a single row
+    longer than ``max_bytes`` is a ``ValueError``."""
+    lengths = np.asarray(lengths)
+    n = int(lengths.shape[0])
+    if max_bytes < 1 or max_rows < 1:
+        raise ValueError("max_bytes and max_rows must be positive")
+    if n and int(lengths.min()) < 0:
+        raise ValueError("negative string length")
+    ends = np.cumsum(lengths, dtype=np.int64)   # ends[i]: bytes of rows [0, i]
+    out = []
+    lo = 0
+    while lo < n:
+        base = int(ends[lo - 1]) if lo else 0
+        hi = min(int(np.searchsorted(ends, base + max_bytes, side="right")), lo + max_rows, n)
+        if hi == lo:
+            raise ValueError(f"row {lo} is {int(lengths[lo])} bytes: longer than a string column's "
+                             f"{max_bytes}-byte limit")
+        out.append((lo, hi))
+        lo = hi
+    return out
+
+
+def _utf8_lengths(off_dev, idx_dev):
+    """Byte length of every gathered row, on the device (int64; 0 for ``idx < 0`` and for an id past the
+    column, which the take kernel itself refuses)."""
+    import torch
+
+    n_rows = int(off_dev.shape[0]) - 1
+    ok = (idx_dev >= 0) & (idx_dev < n_rows)
+    ix = torch.where(ok, idx_dev, 0).long()
+    lens = off_dev[ix + 1].long() - off_dev[ix].long()
+    return torch.where(ok, lens, 0)
+
+
 def _device_take(table, names, idx_dev, eng: HipEngine):
     """Gather the projected columns ``names`` of ``table`` by the device-resident
     row ids ``idx_dev`` ON THE GPU (``giql_hip_take_dev`` / ``giql_hip_take_utf8_*``;
@@ -885,7 +928,9 @@ def _device_take(table, names, idx_dev, eng: HipEngine):
 
     Fixed-width numeric columns go through one fused launch; utf8/binary columns
     through the two-call offsets+bytes take; a validity bitmap travels as a
-    byte-per-row column.  Returns ``{name: pyarrow.Array}``.  Column types the
+    byte-per-row column.  Returns ``{name: pyarrow.Array}``; a string column whose gather exceeds
+    what one take accepts (``UTF8_MAX_BYTES`` bytes, ``UTF8_MAX_ROWS`` rows) comes back as a
+    ``pyarrow.ChunkedArray`` of the column's own type (``plan_utf8_slices``).  Column types the
     kernels do not cover (nested, dictionary, large_*) use ``pyarrow.take`` on
     the host ids -- boundary plumbing, no join arithmetic.
     """
@@ -928,15 +973,27 @@ def _device_take(table, names, idx_dev, eng: HipEngine):
         bufs = col.buffers()
         off = np.frombuffer(bufs[1], dtype=np.int32, count=len(col) + 1 + col.offset)[col.offset:]
         data = np.frombuffer(bufs[2], dtype=np.uint8) if bufs[2] is not None else np.zeros(0, np.uint8)
-        o_dev, d_dev = eng.take_utf8(torch.from_numpy(np.ascontiguousarray(off)).to(dev),
-                                     torch.from_numpy(np.ascontiguousarray(data)).to(dev), idx_dev)
-        vbuf = None
-        nulls = 0
-        if name in valid:
-            vbuf = pa.py_buffer(np.packbits(valid[name], bitorder="little").tobytes())
-            nulls = int(n - valid[name].sum())
-        out[name] = pa.Array.from_buffers(t, n, [vbuf, pa.py_buffer(o_dev.cpu().numpy().tobytes()),
-                                                 pa.py_buffer(d_dev.cpu().numpy().tobytes())], null_count=nulls)
+        off_dev = torch.from_numpy(np.ascontiguousarray(off)).to(dev)
+        data_dev = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
+        # a gather past int32 offsets comes back in row slices that each fit, as chunks of the column's own type
+        slices = [(0, n)]
+        if n:
+            lens = _utf8_lengths(off_dev, idx_dev)
+            if n > UTF8_MAX_ROWS or int(lens.sum()) > UTF8_MAX_BYTES:
+                slices = plan_utf8_slices(lens.int().cpu().numpy(), UTF8_MAX_BYTES, UTF8_MAX_ROWS)
+            del lens
+        chunks = []
+        for lo, hi in slices:
+            o_dev, d_dev = eng.take_utf8(off_dev, data_dev, idx_dev[lo:hi])
+            vbuf = None
+            nulls = 0
+            if name in valid:
+                vbuf = pa.py_buffer(np.packbits(valid[name][lo:hi], bitorder="little").tobytes())
+                nulls = int((hi - lo) - valid[name][lo:hi].sum())
+            chunks.append(pa.Array.from_buffers(t, hi - lo, [vbuf, pa.py_buffer(_to_host(o_dev)),
+                                                             pa.py_buffer(_to_host(d_dev))], null_count=nulls))
+            del o_dev, d_dev
+        out[name] = chunks[0] if len(chunks) == 1 else pa.chunked_array(chunks, type=t)
     if host:
         idx_h = pa.array(idx_dev.cpu().numpy(), type=pa.int64())
         for name in host:

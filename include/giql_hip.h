@@ -300,7 +300,11 @@ int giql_hip_take_dev(giql_hip_ctx* ctx, const void* const* cols,
                       void* stream);
 /* utf8 / binary columns (Arrow int32 offsets[n_rows + 1] + data bytes), in two
  * calls so the caller owns the output: plan writes out_offsets[n + 1] and
- * returns the byte count; fill copies the bytes into out_data[n_bytes]. */
+ * returns the byte count; fill copies the bytes into out_data[n_bytes].
+ * idx[i] < 0 yields an empty value.  Limits of one call: n <= 0x7FFFFFF0 rows
+ * (GIQL_ERR_INVALID past it) and at most 0x7FFFFFFF gathered bytes; a larger
+ * total is GIQL_ERR_CAPACITY with *n_bytes = 0, and the caller splits the rows
+ * (the Python layer returns such a column as several Arrow chunks). */
 int giql_hip_take_utf8_plan_dev(giql_hip_ctx* ctx, const int32_t* offsets,
                                 int64_t n_rows, const int32_t* idx, int64_t n,
                                 int32_t* out_offsets, int64_t* n_bytes,
@@ -364,7 +368,10 @@ typedef struct giql_pred {
  * B by idx_b[i] likewise; the kept candidates' ids are written, in input order,
  * to out_a / out_b (capacity n each; either may be NULL) and *n_kept receives
  * their number.  With idx_a / idx_b = the join's pairs this is the post-join
- * residual filter; with both NULL it filters the rows of one table. */
+ * residual filter; with both NULL it filters the rows of one table.
+ * One call takes n <= 0x7FFFFFF0 candidates (GIQL_ERR_INVALID past it); a
+ * caller with more filters them in slices and appends each slice's kept ids
+ * (HipEngine.select does, 2^30 candidates at a time). */
 int giql_hip_select_dev(giql_hip_ctx* ctx, const giql_pred* preds, int32_t n_preds,
                         const int32_t* idx_a, int64_t n_rows_a,
                         const int32_t* idx_b, int64_t n_rows_b, int64_t n,
