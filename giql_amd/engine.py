@@ -507,6 +507,26 @@ class HipEngine:
         torch = _torch()
         self._check_sides(a, b)
         k = int(k)
+        try:
+            return self._nearest_k_once(a, b, n_chrom, k, signed, max_distance)
+        except _lib.GiqlHipError as exc:
+            if exc.code != _lib.GIQL_ERR_SPAN:
+                raise
+        idx = torch.full((a.n, k), -1, dtype=torch.int32, device=self.device)
+        dist = torch.zeros((a.n, k), dtype=torch.int64, device=self.device)
+        for ra, rb, (gi, gd) in self._retry_by_groups(
+                lambda sa, sb: self._nearest_k_once(sa, sb, n_chrom, k, signed, max_distance), a, b, n_chrom):
+            hit = gi >= 0
+            mapped = torch.full_like(gi, -1)
+            if rb.numel():
+                mapped[hit] = rb[gi[hit].long()].to(torch.int32)
+            idx[ra] = mapped
+            dist[ra] = gd
+        return idx, dist
+
+    def _nearest_k_once(self, a: DeviceSide, b: DeviceSide, n_chrom: int, k: int, signed: bool = False,
+                        max_distance=None):
+        torch = _torch()
         # (no pre-fill: the library writes every slot, unused ones as idx -1 / distance 0)
         idx = torch.empty((a.n, k), dtype=torch.int32, device=self.device)
         dist = torch.empty((a.n, k), dtype=torch.int64, device=self.device)
@@ -520,7 +540,37 @@ class HipEngine:
     def group_rows(self, s: DeviceSide, n_chrom: int):
         """Rows with identical (chrom, raw start, raw end) share a group: returns
         ``(group_of_row int32[n], rep_row int32[n_groups])`` -- the GROUP BY half of
-        count_overlaps (``intersects_duckdb.py:806-854``)."""
+        count_overlaps (``intersects_duckdb.py:806-854``).  Group ids ascend with
+        (chrom, start, end), the order of the linear axis, also when a genome wider
+        than 32 bits is grouped by chromosomes."""
+        torch = _torch()
+        try:
+            return self._group_rows_once(s, n_chrom)
+        except _lib.GiqlHipError as exc:
+            if exc.code != _lib.GIQL_ERR_SPAN:
+                raise
+        raw = DeviceSide(s.chrom, s.start, s.end, 0, 0)  # the kernel groups RAW coordinates: so are the spans taken
+        parts = []
+        for sub, rows, _sb, _rb in self._groups(raw, self._empty_side(raw), n_chrom):
+            gid, rep = self._group_rows_once(sub, n_chrom)
+            parts.append((rows, gid, rows[rep.long()]))
+        gid = torch.empty(s.n, dtype=torch.int32, device=self.device)
+        if not parts:
+            return gid, gid.clone()
+        # each group numbers its groups along its own axis: renumber them in (chrom, start, end) order
+        rep = torch.cat([p[2] for p in parts])
+        order = torch.argsort(s.end[rep], stable=True)
+        order = order[torch.argsort(s.start[rep][order], stable=True)]
+        order = order[torch.argsort(s.chrom[rep][order], stable=True)]
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(order.numel(), dtype=order.dtype, device=self.device)
+        first = 0
+        for rows, g, r in parts:
+            gid[rows] = rank[first + g.long()].to(torch.int32)
+            first += int(r.numel())
+        return gid, rep[order].to(torch.int32)
+
+    def _group_rows_once(self, s: DeviceSide, n_chrom: int):
         torch = _torch()
         gid = torch.empty(s.n, dtype=torch.int32, device=self.device)
         rep = torch.empty(s.n, dtype=torch.int32, device=self.device)
@@ -567,12 +617,39 @@ class HipEngine:
             ids[rows] = self._cluster_once(sub, n_chrom, distance)
         return ids
 
-    def _cluster_pred(self, s: DeviceSide, n_chrom: int, distance: int, preds):
-        torch = _torch()
+    @staticmethod
+    def _check_pred_rows(s: DeviceSide, preds) -> None:
         for p in preds:
             for o in (p[0], p[2]):
                 if o[0] in ("a", "b") and int(o[1].shape[0]) != s.n:
                     raise ValueError("a predicate column must have one value per row of the table")
+
+    @staticmethod
+    def _preds_of_rows(preds, rows):
+        """CLUSTER / MERGE predicates over the rows ``rows`` of their table (one chromosome group): every
+        column operand and its validity mask indexed by ``rows``; literals as they are."""
+        def operand(o):
+            if o[0] not in ("a", "b"):
+                return o
+            return (o[0],) + tuple(None if t is None else t[rows].contiguous() for t in o[1:])
+
+        return [(operand(p[0]), p[1], operand(p[2])) + tuple(p[3:]) for p in preds]
+
+    def _cluster_pred(self, s: DeviceSide, n_chrom: int, distance: int, preds):
+        torch = _torch()
+        self._check_pred_rows(s, preds)
+        try:
+            return self._cluster_pred_once(s, n_chrom, distance, preds)
+        except _lib.GiqlHipError as exc:
+            if exc.code != _lib.GIQL_ERR_SPAN:
+                raise
+        ids = torch.zeros(s.n, dtype=torch.int64, device=self.device)
+        for sub, rows, _sb, _rb in self._groups(s, self._empty_side(s), n_chrom):
+            ids[rows] = self._cluster_pred_once(sub, n_chrom, distance, self._preds_of_rows(preds, rows))
+        return ids
+
+    def _cluster_pred_once(self, s: DeviceSide, n_chrom: int, distance: int, preds):
+        torch = _torch()
         c_preds, k, _keep_alive, _nodes, n_nodes = self._c_preds(preds)
         if n_nodes:
             raise ValueError("arithmetic in a CLUSTER / MERGE predicate is not supported")
@@ -594,18 +671,14 @@ class HipEngine:
         argument, as for :meth:`cluster` (merge.py:201-210 hands it to the CLUSTER underneath)."""
         torch = _torch()
         if preds:
-            for p in preds:
-                for o in (p[0], p[2]):
-                    if o[0] in ("a", "b") and int(o[1].shape[0]) != s.n:
-                        raise ValueError("a predicate column must have one value per row of the table")
-            return self._merge_once(s, n_chrom, distance, preds)
+            self._check_pred_rows(s, preds)
         try:
-            return self._merge_once(s, n_chrom, distance)
+            return self._merge_once(s, n_chrom, distance, preds)
         except _lib.GiqlHipError as exc:
             if exc.code != _lib.GIQL_ERR_SPAN:
                 raise
-        parts = [self._merge_once(sub, n_chrom, distance)
-                 for sub, _rows, _sb, _rb in self._groups(s, self._empty_side(s), n_chrom)]
+        parts = [self._merge_once(sub, n_chrom, distance, self._preds_of_rows(preds, rows) if preds else None)
+                 for sub, rows, _sb, _rb in self._groups(s, self._empty_side(s), n_chrom)]
         if not parts:
             return self._merge_once(self._empty_side(s), n_chrom, distance)
         c, st, en, cnt = (torch.cat([p[k] for p in parts]) for k in range(4))

@@ -836,7 +836,7 @@ def _finish_count(plan, lt, rt, counts, n_chrom, eng, ia, return_indices, a_dev=
         a = a_dev if a_dev is not None else _device_side(lt, plan.left, ia, eng)   # (the join's own upload)
         try:
             gid, rep = eng.group_rows(a, n_chrom)
-        except Exception as exc:  # e.g. a genome wider than 32 bits: group on the host below
+        except Exception as exc:  # (group_rows splits a genome wider than 32 bits itself: a safety net only)
             if getattr(exc, "code", None) != -5:
                 raise
             gid = None
