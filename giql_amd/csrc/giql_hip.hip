@@ -110,111 +110,141 @@ struct InnerState {
   int uniform = 0;
 };
 
+// tuning constants the context does not vary
+constexpr size_t C1_SMALL_ROWS = (size_t)4 << 20;  // class-1 sides up to this many rows take 2 rows per thread
+// second stream: the smaller side's linearize + sort run beside the larger side's when that side is small enough to
+// be latency-bound (a chain of ~10 short launches)
+constexpr u64 OVERLAP_MAX_ROWS = (u64)4 << 20;
+
+// The GIQL_HIP_* environment switches: read once by giql_hip_create (read_switches), constant afterwards.
+struct Switches {
+  bool classic_sort = false;  // GIQL_HIP_SORT=classic: three-launch radix passes
+  int os_variant = 0;         // GIQL_HIP_OS_VARIANT: onesweep block shape (tuning)
+  int os_order = 2;           // GIQL_HIP_OS_ORDER: the onesweep tile order a context starts with (see k_onesweep)
+  u32 os_help_after = OS_HELP_AFTER;  // GIQL_HIP_OS_HELP_AFTER: look-back polls before a block helps
+  int inject_timeout = 0;     // GIQL_HIP_INJECT_TIMEOUT=n (test hook): the n-th clean read-back reports a timeout
+  bool no_uniform = false;    // GIQL_HIP_NO_UNIFORM=1: always run the general two-class join
+  bool no_span_hist = false;  // GIQL_HIP_NO_SPAN_HIST=1: always linearize the fixed-length side (A/B aid)
+  bool no_coarse_b = false;   // GIQL_HIP_NO_COARSE_B=1: the fixed-length B of SEMI / ANTI / COUNT is sorted on every digit
+  double coarse_max_group_rows = 8.0;  // ... and coarsely only while the rows sharing their upper 24 key bits are at most this many on average
+  bool no_fuse_count = false;  // GIQL_HIP_NO_FUSE_COUNT=1: the separate count kernel always
+  // three-stage sort (two global passes on bits 16-31 + the in-LDS bucket sort, bucket_sort.hip.h) for sides of at
+  // least local_min_rows rows whose 16-bit buckets hold between local_min_bucket_rows and local_max_bucket_rows rows
+  // on average (smaller sides have too few rows per bucket to pay for a block each)
+  bool no_local_sort = false;  // GIQL_HIP_NO_LOCAL_SORT=1: never
+  u64 local_min_rows = 1u << 21;  // GIQL_HIP_LOCAL_MIN_ROWS (round 4: a floor only; the density bounds decide)
+  double local_min_bucket_rows = 300.0;   // GIQL_HIP_LOCAL_MIN_BUCKET_ROWS (below: a block per bucket is mostly overhead)
+  double local_max_bucket_rows = 2800.0;  // GIQL_HIP_LOCAL_MAX_BUCKET_ROWS
+  // denser tables keep the form with NARROWER buckets (15 / 14 / 13 key bits, three global passes): sort_local_bits()
+  bool no_narrow = false;  // GIQL_HIP_NO_NARROW_BUCKETS=1: 16 bits or nothing (round 3)
+  int force_bits = 0;      // GIQL_HIP_LOCAL_BITS=w: every three-stage sort takes w (tests)
+};
+
+// What one call leaves for the next to speculate on, and the fallbacks a context keeps for good once taken.  Written
+// by the calls that validate them (at their read-back); never reset.  A guess that missed makes its call return
+// GIQL_STATUS_GUESS_MISSED with the guess dropped, and with_order_fallback repeats the call.
+struct Guesses {
+  bool local_sort = true;     // the three-stage sort; off for good once a bucket outgrew the LDS stage (GIQL_HIP_NO_LOCAL_SORT)
+  int os_order = 2;           // onesweep tile order in force; 0 for good after a look-back timeout (GIQL_HIP_OS_ORDER)
+  int inject_timeout = 0;     // clean read-backs left before the injected timeout (GIQL_HIP_INJECT_TIMEOUT)
+  u64 last_span = 0;          // linearised span of the context's last call: the density guess of row_skip() / sort_is_local()
+  bool last_no_irr = false;   // the previous plan met no irregular row
+  bool nearest_two_sorts = false;  // NEAREST / group_rows: a B table with long equal-start runs was seen
+  // NEAREST k = 1: both sides sorted straight from their raw columns (digits counted in the span pass, aligned layout;
+  // no linearize pass) -- -1: not known yet (the next call probes the layout), 0: this data does not take the aligned
+  // layout, 1: the previous call did
+  int nearest_aligned = -1;
+  bool spec_valid = false;    // INNER: the previous plan's form decision
+  int spec_form = 0;
+  i64 spec_len = 0;
+  bool spec_aligned = false;  // ... and whether the aligned layout (histogram in the span pass) held
+  bool spec_fuse_len_ok = false;  // the previous plan's query rows were all short enough for the fused windows
+  // sorted inputs: a side the span pass found in (chrom id, start) order is not sorted again (plan labels, after the
+  // exchange of sides)
+  bool spec_sorted[2] = {false, false};
+  // per-row operators (SEMI / ANTI / COUNT): the fixed length of B seen by the previous call (0 = B was not
+  // fixed-length), speculated on like the INNER form
+  bool row_spec_valid = false;
+  i64 row_spec_len = 0;
+  int spec_misses = 0;        // INNER plans repeated after a guess missed
+  int local_resorts = 0;      // calls repeated with the four-pass sort
+  int order_fallbacks = 0;    // calls repeated in the ticket order after a timeout
+};
+
+// Everything that lives for one call: reset by value in reset_stats() at the start of every call that reports
+// stats (and so of every attempt with_order_fallback repeats).  The values giql_hip_get_stats reports stay until
+// the next such call.
+struct CallState {
+  bool prezeroed = false;       // the call zeroed its histograms and status words in ONE memset up front
+  // a sort's FIRST pass may rank its rows with LDS atomics (unstable: rows of equal digits in any order) when the caller
+  // does not need equal keys in input order -- the INNER join's sides (onesweep.hip.h)
+  bool first_unstable = false;
+  u32* span_hist_dirty[2] = {nullptr, nullptr};  // histograms the span pass counted into (a side that is linearized after all must zero its own again)
+  int force_local = 0;          // +1 while a table index is built: the three-stage sort whatever the guesses say; -1: global passes only
+  int index_bits = 16;          // the width of the index being built (force_local > 0)
+  bool used_sorted[2] = {false, false};  // the call skipped that side's sort
+  bool last_sort_local = false;  // the call sorted at least one side in three stages
+  int last_local_bits = 16;      // ... the key bits of its buckets (the last bucket stage launched)
+  // fused range count (fixed-length INNER form whose sorted side takes the three-stage sort): the bucket sort answers
+  // the queries' bounds from LDS, the sorted keys never return to HBM (bucket_sort.hip.h)
+  bool count_fused = false;
+  // the join itself in the bucket stage (bucket_sort.hip.h, FUSE == 2): one-call form only, on the same guesses as the
+  // early fill; the pairs leave from the bucket blocks, no sorted id / bound / offset array is written
+  bool bucket_join = false;
+};
+
+// What inner_plan keeps for inner_fill / export (all inside the arena).  Dropped (planned = false) by every call that
+// claims the arena (claim_arena); written by inner_plan_core.
+struct InnerPlan {
+  bool planned = false;
+  bool plan_is_join = false;  // the pairs left from the bucket stage: no plan arrays (fill / export need a plan of their own)
+  bool swapped = false;       // planned with the sides exchanged (giql_hip_inner_plan_dev_impl)
+  // one-call join (giql_hip_inner_join_dev): the caller's outputs offered to the plan for a fill launched before the
+  // host has learned the pair count (set around the plan), and whether that fill stood
+  int32_t* fuse_a = nullptr;
+  int32_t* fuse_b = nullptr;
+  u64 fuse_cap = 0;
+  bool fuse_done = false;
+  giql_side side_a, side_b;
+  u32 n_a = 0, n_b = 0;
+  int n_chrom = 0;
+  u64 n_reg = 0, n_irr = 0, n_c1 = 0;
+  InnerState inner;
+  u32* irr_a_list = nullptr;
+  u32* irr_b_list = nullptr;
+  u64* irr_off = nullptr;
+};
+
 struct giql_hip_ctx {
+  explicit giql_hip_ctx(const Switches& s) : sw(s) {
+    guess.local_sort = !s.no_local_sort;
+    guess.os_order = s.os_order;
+    guess.inject_timeout = s.inject_timeout;
+  }
+  const Switches sw;
+  Guesses guess;
+  CallState call;
+  InnerPlan plan;
+
+  // device resources
   int device = 0;
+  int n_cu = 256;             // compute units of the device
   char* arena = nullptr;
   size_t arena_cap = 0;
   DevMeta* d_meta = nullptr;
   DevMeta* h_meta = nullptr;  // pinned
   u32* part = nullptr;        // fill partition (grown on demand)
+  size_t part_cap = 0;        // (bytes)
   void* stage_out = nullptr;  // device staging of the host-buffer entry points' outputs (grown on demand)
   size_t stage_out_cap = 0;
-  size_t part_cap = 0;
-  u64* d_scratch64 = nullptr;  // small device scratch (checksum)
-
-  bool classic_sort = false;  // GIQL_HIP_SORT=classic: three-launch radix passes
-  int os_variant = 0;         // GIQL_HIP_OS_VARIANT: onesweep block shape (tuning)
-  int c1_items = 0;           // GIQL_HIP_C1_ITEMS: class-1 rows per thread, 2 or 8 (0 = by size)
-  size_t c1_small_rows = (size_t)4 << 20;  // class-1 sides up to this many rows take 2 rows per thread
-  bool no_uniform = false;    // GIQL_HIP_NO_UNIFORM=1: always run the general two-class join
-  int n_cu = 256;             // compute units of the device
-  int os_order = 2;           // onesweep tile order (GIQL_HIP_OS_ORDER, see k_onesweep)
-  u32 os_help_after = OS_HELP_AFTER;  // look-back polls before a block helps (GIQL_HIP_OS_HELP_AFTER)
-  // fused join (giql_hip_inner_join_dev): outputs offered to the plan for a fill launched
-  // before the host has learned the pair count
-  int32_t* fuse_a = nullptr;
-  int32_t* fuse_b = nullptr;
-  u64 fuse_cap = 0;
-  bool fuse_done = false;
-  bool no_c1_fill = false;  // GIQL_HIP_NO_C1_FILL=1: class 1 always through k_c1_count / k_c1_emit
-  bool no_keygen_general = false;  // GIQL_HIP_NO_KEYGEN_GENERAL=1: the general form always linearises both sides
-  bool swapped = false;  // the last INNER plan ran with the sides exchanged (giql_hip_inner_plan_dev_impl)
-  bool no_swap = false;  // GIQL_HIP_NO_SWAP=1: plan the sides as given
-  bool last_no_irr = false;   // the previous plan met no irregular row
-  bool nearest_two_sorts = false;  // NEAREST: a B table with long equal-start runs was seen
-  // NEAREST k = 1: both sides sorted straight from their raw columns (digits counted in the span pass, aligned layout;
-  // no linearize pass) -- -1: not known yet (the next call probes the layout), 0: this data does not take the aligned
-  // layout, 1: the previous call did (a guess, validated at the read-back)
-  int nearest_aligned = -1;
-  bool spec_valid = false;    // INNER: the previous plan's form decision, speculated on next time
-  int spec_form = 0;
-  i64 spec_len = 0;
-  int spec_misses = 0;
-  // per-row operators (SEMI / ANTI / COUNT): the fixed length of B seen by the previous call
-  // (0 = B was not fixed-length), speculated on like the INNER form
-  bool row_spec_valid = false;
-  i64 row_spec_len = 0;
-  bool spec_aligned = false;  // ... and whether the aligned layout (histogram in the span pass) held
-  bool no_span_hist = false;  // GIQL_HIP_NO_SPAN_HIST=1: always linearize the fixed-length side (A/B aid)
-  int inject_timeout = 0;     // test hook: report one look-back timeout
-  int order_fallbacks = 0;    // calls repeated in the ticket order after a timeout
-  // three-stage sort (two global passes on bits 16-31 + the in-LDS bucket sort, bucket_sort.hip.h)
-  // for sides of at least local_min_rows rows (smaller sides have too few rows per bucket to pay for a block each); switched off for good on a context once a bucket
-  // turned out larger than the LDS sort holds (GIQL_HIP_NO_LOCAL_SORT=1: never)
-  // second stream: the smaller side's linearize + sort run beside the larger side's when that side is
-  // small enough to be latency-bound (a chain of ~10 short launches); GIQL_HIP_NO_OVERLAP=1: never
-  hipStream_t side_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  u64 overlap_max_rows = 4u << 20;
-  bool overlap_large = true;  // GIQL_HIP_OVERLAP_LARGE=0: the small side's chain runs beside the other side's only when that is small too
-  int overlap_mask = 3;  // GIQL_HIP_OVERLAP_MASK: 1 = the sides' sort chains, 2 = the two count classes
-  int row_skip_digits = -1;    // GIQL_HIP_ROW_SKIP_DIGITS: low digits the per-row operators leave unsorted on their query side (-1: by density, row_skip())
-  u64 last_span = 0;           // linearised span of the context's last call: the density guess of row_skip() / sort_is_local()
-  double local_max_bucket_rows = 2800.0;  // three-stage sort only while a 16-bit bucket holds at most this many rows on average
-  double local_min_bucket_rows = 300.0;   // ... and at least this many (below: a block per bucket is mostly overhead)
-  // denser tables keep the form with NARROWER buckets (15 / 14 / 13 key bits, three global passes): sort_local_bits().
-  // GIQL_HIP_NO_NARROW_BUCKETS=1: 16 bits or nothing (round 3); GIQL_HIP_LOCAL_BITS=w: every three-stage sort takes w (tests)
-  bool no_narrow = false;
-  int force_bits = 0;
-  int index_bits = 16;  // the width of the index being built (force_local > 0)
-  bool no_skip_digit = false;  // GIQL_HIP_NO_SKIP_DIGIT=1: query sides are sorted on every digit
-  // a sort's FIRST pass may rank its rows with LDS atomics (unstable: rows of equal digits in any order) when the caller
-  // does not need equal keys in input order -- the INNER join's sides (onesweep.hip.h); GIQL_HIP_NO_UNSTABLE_FIRST=1: never
-  bool first_unstable = false;
-  bool no_unstable_first = false;
-  bool no_dual_span = false;   // GIQL_HIP_NO_DUAL_SPAN=1: one span launch per side (round 3)
-  bool no_coarse_b = false;    // GIQL_HIP_NO_COARSE_B=1: the fixed-length B of SEMI / ANTI / COUNT is sorted on every digit
-  double coarse_max_group_rows = 8.0;  // ... and coarsely only while the rows sharing their upper 24 key bits are at most this many on average
-  bool local_sort = true;
-  int force_local = 0;         // +1 while a table index is built (giql_hip_index_create_dev): the three-stage sort whatever the guesses say; -1: global passes only
-  u64 local_min_rows = 1u << 21;  // (round 4: a floor only; the density bounds above decide)
-  int local_resorts = 0;      // calls repeated with the four-pass sort
-  bool last_sort_local = false;  // the call in flight sorted at least one side in three stages
-  int last_local_bits = 16;      // ... the key bits of its buckets (the last bucket stage launched)
-  // fused range count (fixed-length INNER form whose sorted side takes the three-stage sort): the bucket
-  // sort answers the queries' bounds from LDS, the sorted keys never return to HBM (bucket_sort.hip.h)
-  // sorted inputs: a side the span pass found in (chrom id, start) order is not sorted again.  The answer of the
-  // previous plan is the guess of the next (validated at the read-back); plan labels (after the exchange of sides)
-  bool spec_sorted[2] = {false, false};
-  bool used_sorted[2] = {false, false};  // the call in flight skipped that side's sort
-  bool no_sorted = false;       // GIQL_HIP_NO_SORTED_INPUT=1: every side is sorted whatever its order
-  bool no_keygen_q = false;     // GIQL_HIP_NO_KEYGEN_Q=1: the fixed-length form always linearizes its query side
-  u32* span_hist_dirty[2] = {nullptr, nullptr};  // histograms the span pass of the call in flight counted into (a side that is linearized after all must zero its own again)
-  bool prezeroed = false;       // the call in flight zeroed its histograms and status words in ONE memset up front
-  bool no_fuse_count = false;   // GIQL_HIP_NO_FUSE_COUNT=1: the separate count kernel always
-  int fuse_q_skip = 2;          // GIQL_HIP_Q_SKIP_DIGITS: low digits the fused form leaves unsorted on the query side
-  bool spec_fuse_len_ok = false;  // the previous plan's query rows were all short enough for the fused windows
-  bool count_fused = false;     // the call in flight answered its bounds in the bucket sort
-  // the join itself in the bucket stage (bucket_sort.hip.h, FUSE == 2): one-call form only, on the same guesses as the
-  // early fill; the pairs leave from the bucket blocks, no sorted id / bound / offset array is written
-  bool no_bucket_join = false;  // GIQL_HIP_NO_BUCKET_JOIN=1: bounds from the bucket sort, then scan + fill as before
-  bool bucket_join = false;     // the call in flight emitted its pairs from the bucket stage
-  bool plan_is_join = false;    // ... and so left no plan arrays behind (fill / export need a plan of their own)
-  u32* bucket_qwin = nullptr;   // [2 * BS_MAX_BUCKETS] query window per bucket
-  u32* bucket_bnd = nullptr;  // [BS_MAX_BUCKETS + 1] bucket boundaries of the sort in flight
-  u32* bucket_big = nullptr;  // [1 + BS_MAX_BUCKETS] buckets too large for LDS, queued for k_bucket_sort_big ([0] = count)
   char* xplan = nullptr;      // scratch of giql_hip_fill_from_plan_dev (offsets + scan partials), grown on demand
   size_t xplan_cap = 0;
+  u64* d_scratch64 = nullptr;  // small device scratch (checksum)
+  hipStream_t side_stream = nullptr;  // the second stream (SideChain)
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  u32* bucket_qwin = nullptr;  // [2 * BS_MAX_BUCKETS] query window per bucket
+  u32* bucket_bnd = nullptr;   // [BS_MAX_BUCKETS + 1] bucket boundaries of the sort in flight
+  u32* bucket_big = nullptr;   // [1 + BS_MAX_BUCKETS] buckets too large for LDS, queued for k_bucket_sort_big ([0] = count)
 
   // profiling
   int profiling = 0;          // 0 off, 1 every phase, 2 only profile_phase (the dominant kernel's)
@@ -227,17 +257,6 @@ struct giql_hip_ctx {
   std::vector<Span> spans;
   size_t ev_used = 0;
   giql_hip_stats stats;
-
-  // state kept between inner_plan and inner_fill
-  bool planned = false;
-  giql_side side_a, side_b;
-  u32 n_a = 0, n_b = 0;
-  int n_chrom = 0;
-  u64 n_reg = 0, n_irr = 0, n_c1 = 0;
-  InnerState inner;
-  u32* irr_a_list = nullptr;
-  u32* irr_b_list = nullptr;
-  u64* irr_off = nullptr;
 };
 
 struct Carver {
@@ -252,20 +271,43 @@ struct Carver {
   }
 };
 
+// A device buffer grown on demand: at least `need` bytes, `want` of them when it has to grow (the buffer's slack).
+// The old one may still be read by work on `stream`; it is freed after that work.
+static int grow_buffer(void** buf, size_t* cap, size_t need, size_t want, hipStream_t stream, const char* what) {
+  if (need <= *cap) return GIQL_OK;
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (*buf) HIP_TRY(hipFree(*buf));
+  *buf = nullptr;
+  *cap = 0;
+  const hipError_t e = hipMalloc(buf, want);
+  if (e != hipSuccess)
+    return set_err(GIQL_ERR_NOMEM, "hipMalloc(%zu bytes) for %s failed: %s", want, what, hipGetErrorString(e));
+  *cap = want;
+  return GIQL_OK;
+}
+
 static int ensure_arena(giql_hip_ctx* ctx, size_t bytes, hipStream_t stream) {
   if (bytes <= ctx->arena_cap) return GIQL_OK;
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (ctx->arena) HIP_TRY(hipFree(ctx->arena));
-  ctx->arena = nullptr;
-  ctx->arena_cap = 0;
-  ctx->planned = false;
+  ctx->plan.planned = false;  // (giql_hip_reserve: a new arena holds no plan)
   const size_t want = align_up(bytes + bytes / 8, (size_t)1 << 20);
-  hipError_t e = hipMalloc((void**)&ctx->arena, want);
-  if (e != hipSuccess)
-    return set_err(GIQL_ERR_NOMEM, "hipMalloc(%zu bytes) for the workspace failed: %s", want,
-                   hipGetErrorString(e));
-  ctx->arena_cap = want;
+  GIQL_TRY(grow_buffer((void**)&ctx->arena, &ctx->arena_cap, bytes, want, stream, "the workspace"));
   if (getenv("GIQL_HIP_DEBUG_ADDR")) fprintf(stderr, "[giql_hip] arena %p + %zu bytes\n", (void*)ctx->arena, want);
+  return GIQL_OK;
+}
+
+// the fill's merge-path partition: at least `words` entries
+static int grow_part(giql_hip_ctx* ctx, size_t words, hipStream_t stream) {
+  return grow_buffer((void**)&ctx->part, &ctx->part_cap, words * sizeof(u32), (words + words / 4) * sizeof(u32), stream,
+                     "the fill partition");
+}
+
+// The workspace of a call: `carve` lays its buffers out from a base (nullptr: a dry run that returns the size), once
+// to size the arena and once for real.  The call reuses what an INNER plan keeps there: the plan is dropped.
+template <typename Carve>
+static int claim_arena(giql_hip_ctx* ctx, hipStream_t stream, Carve&& carve) {
+  ctx->plan.planned = false;
+  GIQL_TRY(ensure_arena(ctx, carve(nullptr), stream));
+  carve(ctx->arena);
   return GIQL_OK;
 }
 
@@ -294,16 +336,51 @@ struct Phase {
   }
 };
 
+// The one place that resets per-call state (at the start of every call that reports stats).
 static void reset_stats(giql_hip_ctx* ctx) {
   memset(&ctx->stats, 0, sizeof(ctx->stats));
-  ctx->last_sort_local = false;
-  ctx->last_local_bits = 16;
-  ctx->count_fused = false;
-  ctx->bucket_join = false;
-  ctx->used_sorted[0] = ctx->used_sorted[1] = false;
+  ctx->call = CallState{};
   ctx->spans.clear();
   ctx->ev_used = 0;
 }
+
+static int begin_call(giql_hip_ctx* ctx) {
+  HIP_TRY(hipSetDevice(ctx->device));
+  reset_stats(ctx);
+  return GIQL_OK;
+}
+
+// The prologue of the operators on two sides: the checks, then begin_call and the sides' sizes.
+static int check_side(const giql_side* s, const char* name);
+static int begin_pair_call(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, int32_t n_chrom) {
+  GIQL_TRY(check_side(a, "a"));
+  GIQL_TRY(check_side(b, "b"));
+  if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
+  GIQL_TRY(begin_call(ctx));
+  ctx->stats.n_a = a->n;
+  ctx->stats.n_b = b->n;
+  return GIQL_OK;
+}
+
+// Clears the prezeroed state (and the unstable first pass that goes with the INNER plan's) when a call's frame ends:
+// the sort helpers zero their own histograms and status words again.
+struct PrezeroGuard {
+  giql_hip_ctx* c;
+  ~PrezeroGuard() {
+    c->call.prezeroed = false;
+    c->call.first_unstable = false;
+  }
+};
+
+// The three-stage sort forced on (+1: an index build) or off (-1: an indexed join's query side) for a scope.
+struct ForceLocal {
+  giql_hip_ctx* c;
+  ForceLocal(giql_hip_ctx* ctx, int v) : c(ctx) { c->call.force_local = v; }
+  ~ForceLocal() {
+    c->call.force_local = 0;
+    c->call.index_bits = 16;
+  }
+};
 
 // Call only after the stream has been synchronised.
 static void collect_spans(giql_hip_ctx* ctx) {
@@ -419,8 +496,8 @@ static int run_spans(giql_hip_ctx* ctx, hipStream_t st, const giql_side& a, cons
   const bool hist = hist_side >= 0 && hist_partial && lb.abase && lb.top_partial &&
                     n_chrom <= MM_HIST_CHROMS && (hist_side ? b.n : a.n) > 0;
   // both sides count their digits (lb.hist_partial2 / top_partial2 for the other one; prezeroed plans only)
-  const bool hist2 = hist && lb.hist_partial2 && lb.top_partial2 && ctx->prezeroed && (hist_side ? a.n : b.n) > 0;
-  if (hist && !ctx->prezeroed) {
+  const bool hist2 = hist && lb.hist_partial2 && lb.top_partial2 && ctx->call.prezeroed && (hist_side ? a.n : b.n) > 0;
+  if (hist && !ctx->call.prezeroed) {
     HIP_TRY(hipMemsetAsync(hist_partial, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
     HIP_TRY(hipMemsetAsync(lb.top_partial, 0, (size_t)LIN_HIST_REPLICAS * MM_TOP_WORDS * sizeof(u32), st));
   }
@@ -430,7 +507,7 @@ static int run_spans(giql_hip_ctx* ctx, hipStream_t st, const giql_side& a, cons
   const size_t lds = n_chrom <= MM_LDS_CHROMS ? (size_t)n_chrom * 2 * sizeof(int) : 0;
   const giql_side* sides[2] = {&a, &b};
   int nblk[2] = {0, 0};
-  if (a.n > 0 && b.n > 0 && !ctx->no_dual_span) {
+  if (a.n > 0 && b.n > 0) {
     // both sides in ONE launch: the grid (one resident wave of 512-thread blocks) is shared in proportion to the rows
     MmSide ms[2];
     const double tot = (double)a.n + (double)b.n;
@@ -438,7 +515,7 @@ static int run_spans(giql_hip_ctx* ctx, hipStream_t st, const giql_side& a, cons
       const giql_side& s = *sides[k];
       const bool with_hist = hist && (k == hist_side || hist2);
       u32* const hp = k == hist_side ? hist_partial : lb.hist_partial2;
-      if (with_hist) ctx->span_hist_dirty[k] = hp;
+      if (with_hist) ctx->call.span_hist_dirty[k] = hp;
       u32 grid = (u32)((double)MM_MAX_BLOCKS * (double)s.n / tot + 0.5);
       const u32 need = cdiv((u64)s.n, (u64)MM_NT_HIST * 4);   // a block per tile at most
       if (grid > need) grid = need;
@@ -464,7 +541,7 @@ static int run_spans(giql_hip_ctx* ctx, hipStream_t st, const giql_side& a, cons
     if (s.n == 0) continue;
     const bool with_hist = hist && (k == hist_side || hist2);
     u32* const hp = k == hist_side ? hist_partial : lb.hist_partial2;
-    if (with_hist) ctx->span_hist_dirty[k] = hp;
+    if (with_hist) ctx->call.span_hist_dirty[k] = hp;
     u32* const tp = k == hist_side ? lb.top_partial : lb.top_partial2;
     u32 grid = cdiv((u64)s.n, (u64)(with_hist ? MM_NT_HIST : MM_NT) * MM_ITEMS);
     if (grid > (u32)MM_MAX_BLOCKS) grid = MM_MAX_BLOCKS;
@@ -505,13 +582,13 @@ static int run_linearize(giql_hip_ctx* ctx, hipStream_t st, const giql_side& s, 
   // turned out to need the linearize pass after all: layout or form guess not taken)
   bool dirty = false;
   for (int k = 0; k < 2; k++)
-    if (hist_partial && ctx->span_hist_dirty[k] == hist_partial) {
+    if (hist_partial && ctx->call.span_hist_dirty[k] == hist_partial) {
       dirty = true;
-      ctx->span_hist_dirty[k] = nullptr;
+      ctx->call.span_hist_dirty[k] = nullptr;
     }
-  if (hist_partial && (!ctx->prezeroed || dirty))
+  if (hist_partial && (!ctx->call.prezeroed || dirty))
     HIP_TRY(hipMemsetAsync(hist_partial, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
-  if (hist_end && !ctx->prezeroed)
+  if (hist_end && !ctx->call.prezeroed)
     HIP_TRY(hipMemsetAsync(hist_end, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
   Phase ph(ctx, st, GIQL_PH_LINEARIZE, hist_partial ? 2 : 1);
   u32 grid = cdiv((u64)s.n, LIN_NT);
@@ -542,7 +619,7 @@ static inline size_t os_pass_words(size_t n) {
 // ... and what a pass of this context really uses (the default 1024 x 8 block shape has 8192-row tiles: half
 // of the worst case, half the bytes to zero); the ticket word is the stride's 16th-last
 static inline size_t os_pass_stride(const giql_hip_ctx* ctx, size_t n) {
-  return ctx->os_variant == 0 ? (size_t)cdiv(n ? n : 1, 8192) * OS_BINS + 16 : os_pass_words(n);
+  return ctx->sw.os_variant == 0 ? (size_t)cdiv(n ? n : 1, 8192) * OS_BINS + 16 : os_pass_words(n);
 }
 
 template <int NT, int ITEMS>
@@ -556,7 +633,7 @@ static void launch_onesweep(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, int
   hipLaunchKernelGGL((k_onesweep<M, NT, ITEMS>), dim3(grid), dim3(NT), 0, st, sb.key[src],           \
                      sb.end[0] ? sb.end[src] : (const u32*)nullptr, rin, sb.key[dst],                 \
                      sb.end[0] ? sb.end[dst] : (u32*)nullptr, sb.rid[0] ? sb.rid[dst] : (u32*)nullptr, \
-                     n, shift, gbase, status, claim, meta, ctx->os_order, ctx->os_help_after, (const u32*)nullptr, 0u, 0u,  \
+                     n, shift, gbase, status, claim, meta, ctx->guess.os_order, ctx->sw.os_help_after, (const u32*)nullptr, 0u, 0u,  \
                      unstable)
   switch (mode) {
     case 0: GIQL_OS_LAUNCH(0); break;
@@ -572,25 +649,25 @@ static void launch_onesweep(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, int
 // keygen (with abase): the first pass builds the keys from that side's raw (chrom, start)
 // columns instead of reading sb.key[0] (k_onesweep<.., KEYGEN>; (key, rid) sorts, default
 // block shape only).
-// Sides of ctx->local_min_rows rows and more take the three-stage form: global passes on bits
+// Sides of ctx->sw.local_min_rows rows and more take the three-stage form: global passes on bits
 // 16-23 and 24-31 only, then every 16-bit bucket sorted on its low bits inside LDS, in place
 // (bucket_sort.hip.h) -- three trips through HBM instead of four.
 // the narrowest-needed bucket for a table of per_bucket rows per 65,536 keys on average (0: too dense for any)
 static inline int density_bits(const giql_hip_ctx* ctx, double per_bucket) {
   int w = 16;
-  while (per_bucket > ctx->local_max_bucket_rows && w > BS_MIN_WBITS && !ctx->no_narrow) {
+  while (per_bucket > ctx->sw.local_max_bucket_rows && w > BS_MIN_WBITS && !ctx->sw.no_narrow) {
     per_bucket *= 0.5;
     w--;
   }
-  return per_bucket <= ctx->local_max_bucket_rows ? w : 0;
+  return per_bucket <= ctx->sw.local_max_bucket_rows ? w : 0;
 }
 
 // Returns 0 (four global passes) or the key bits of a bucket: 16 (two global passes), or 15 / 14 / 13 for denser
 // tables (three global passes -- bits 8-15, 16-23, 24-31 -- and buckets of 2^W keys: bucket_sort.hip.h).
 static inline int sort_local_bits(const giql_hip_ctx* ctx, size_t n) {
-  if (ctx->force_local > 0 && ctx->bucket_bnd && ctx->os_variant == 0) return ctx->index_bits;
-  if (ctx->force_local < 0) return 0;
-  if (!(ctx->local_sort && ctx->bucket_bnd && ctx->os_variant == 0 && n >= ctx->local_min_rows)) return 0;
+  if (ctx->call.force_local > 0 && ctx->bucket_bnd && ctx->sw.os_variant == 0) return ctx->call.index_bits;
+  if (ctx->call.force_local < 0) return 0;
+  if (!(ctx->guess.local_sort && ctx->bucket_bnd && ctx->sw.os_variant == 0 && n >= ctx->sw.local_min_rows)) return 0;
   // The in-LDS stage holds 4096 rows per bucket; larger buckets go through a slow queue (one block each, two
   // more passes: 30M x 300M reads, ~6000 rows per bucket, spent 10.4 of 21 ms there).  So the form is taken
   // only while the AVERAGE bucket is comfortably below that -- by the span of the context's previous call
@@ -602,10 +679,10 @@ static inline int sort_local_bits(const giql_hip_ctx* ctx, size_t n) {
   // (0.135 ms against 0.106 for the two passes it replaces).
   // Round 4, bucket width by density: past 2,800 rows per 65,536 keys (132M rows on a human-genome axis) the bucket
   // narrows -- 2^15, 2^14, 2^13 keys, up to ~1G rows -- instead of the form being given up.
-  const double span = ctx->last_span ? (double)ctx->last_span : 3.2e9;
+  const double span = ctx->guess.last_span ? (double)ctx->guess.last_span : 3.2e9;
   double per_bucket = (double)n * 65536.0 / span;
-  if (per_bucket < ctx->local_min_bucket_rows) return 0;
-  if (ctx->force_bits) return ctx->force_bits;
+  if (per_bucket < ctx->sw.local_min_bucket_rows) return 0;
+  if (ctx->sw.force_bits) return ctx->sw.force_bits;
   return density_bits(ctx, per_bucket);
 }
 static inline int local_passes(int wbits) { return wbits == 16 ? 2 : 3; }  // global passes before the bucket stage
@@ -641,9 +718,9 @@ static void launch_bucket_stage_fused(giql_hip_ctx* ctx, hipStream_t st, SortBuf
   fuse.dev.wbits = (u32)wbits;
   const u32 BS_BUCKETS = bs_n_buckets((u32)wbits);  // (shadows the 16-bit constant: every launch below is per bucket)
   ctx->stats.phase_bytes[GIQL_PH_SORT_LOCAL] += bucket_stage_fused_bytes(n, fuse);
-  ctx->count_fused = true;
-  ctx->bucket_join = fuse.join;
-  ctx->last_local_bits = wbits;
+  ctx->call.count_fused = true;
+  ctx->call.bucket_join = fuse.join;
+  ctx->call.last_local_bits = wbits;
   {
     Phase ph(ctx, st, GIQL_PH_COUNT, 1);
     hipLaunchKernelGGL(k_bucket_bounds_fused, dim3(cdiv((u64)3 * BS_BUCKETS + 1, 256)), dim3(256), 0, st, sb.key[0], n,
@@ -722,18 +799,18 @@ static int run_sort_onesweep(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u3
       GIQL_TRY(post_launch("sorted input (no sort)"));
     }
     if (!local_fused) return GIQL_OK;   // sorted already: the bucket stage only runs as the carrier of the fused count
-    ctx->last_sort_local = true;
+    ctx->call.last_sort_local = true;
     launch_bucket_stage_fused(ctx, st, sb, n, gbase, *fuse, wbits_pre);
     return post_launch("bucket stage (sorted input, fused count)");
   }
   const int wbits = sort_local_bits(ctx, n);
   const bool local = wbits != 0;
-  if (local) ctx->last_sort_local = true;
-  if (local || ctx->no_skip_digit) skip_digits = 0;
+  if (local) ctx->call.last_sort_local = true;
+  if (local) skip_digits = 0;
   const int n_pass = local ? local_passes(wbits) : 4 - skip_digits;
   const int first_digit = local ? 4 - n_pass : skip_digits;
   const size_t per_pass = os_pass_stride(ctx, n);
-  if (!ctx->prezeroed) HIP_TRY(hipMemsetAsync(status, 0, n_pass * per_pass * sizeof(u32), st));
+  if (!ctx->call.prezeroed) HIP_TRY(hipMemsetAsync(status, 0, n_pass * per_pass * sizeof(u32), st));
   {
     // one event pair around the passes (an event record between two launches costs the
     // stream ~8 us of idle time; the per-launch time is phase time / launches)
@@ -752,7 +829,7 @@ static int run_sort_onesweep(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u3
                                                : 1 + ((sb.rid[0] && !first) ? 1 : 0) + (sb.end[0] ? 1 : 0);
         ctx->stats.phase_bytes[GIQL_PH_SORT_SCATTER] += (int64_t)4 * (w_in + w_out) * n;
       }
-      const int unstable = (pass == 0 && !keep_rids && ctx->first_unstable && !ctx->no_unstable_first) ? 1 : 0;
+      const int unstable = (pass == 0 && !keep_rids && ctx->call.first_unstable) ? 1 : 0;
       if (pass == 0 && keygen) {
         const u32 grid = cdiv(n, 1024 * 8);
         u32* claim = stat + per_pass - 16;
@@ -760,16 +837,16 @@ static int run_sort_onesweep(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u3
           hipLaunchKernelGGL((k_onesweep<3, 1024, 8, true>), dim3(grid), dim3(1024), 0, st,
                              reinterpret_cast<const u32*>(keygen->start), reinterpret_cast<const u32*>(keygen->end),
                              reinterpret_cast<const u32*>(keygen->chrom), sb.key[dst], sb.end[dst], sb.rid[dst], n,
-                             digit * 8, gb, stat, claim, ctx->d_meta, ctx->os_order, ctx->os_help_after, abase,
+                             digit * 8, gb, stat, claim, ctx->d_meta, ctx->guess.os_order, ctx->sw.os_help_after, abase,
                              (u32)keygen->start_off, (u32)keygen->end_off, unstable);
         else
           hipLaunchKernelGGL((k_onesweep<1, 1024, 8, true>), dim3(grid), dim3(1024), 0, st,
                              reinterpret_cast<const u32*>(keygen->start), reinterpret_cast<const u32*>(keygen->chrom),
                              (const u32*)nullptr, sb.key[dst], (u32*)nullptr, sb.rid[dst], n, digit * 8, gb, stat, claim,
-                             ctx->d_meta, ctx->os_order, ctx->os_help_after, abase, (u32)keygen->start_off, 0u, unstable);
+                             ctx->d_meta, ctx->guess.os_order, ctx->sw.os_help_after, abase, (u32)keygen->start_off, 0u, unstable);
         continue;
       }
-      switch (ctx->os_variant) {  // block-shape sweep (tools/os_variants.py); default 1024 x 8
+      switch (ctx->sw.os_variant) {  // block-shape sweep (tools/os_variants.py); default 1024 x 8
         case 1: launch_onesweep<512, 8>(ctx, st, sb, src, dst, first, n, digit * 8, gb, stat, ctx->d_meta, unstable); break;
         case 2: launch_onesweep<512, 16>(ctx, st, sb, src, dst, first, n, digit * 8, gb, stat, ctx->d_meta, unstable); break;
         case 3: launch_onesweep<256, 16>(ctx, st, sb, src, dst, first, n, digit * 8, gb, stat, ctx->d_meta, unstable); break;
@@ -796,7 +873,7 @@ static int run_sort_onesweep(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u3
     }
     BsFuse bw;  // the plain sort: only the bucket width travels
     bw.wbits = (u32)wbits;
-    ctx->last_local_bits = wbits;
+    ctx->call.last_local_bits = wbits;
     const u32 BS_BUCKETS = bs_n_buckets((u32)wbits);
     HIP_TRY(hipMemsetAsync(ctx->bucket_big, 0, sizeof(u32), st));
     Phase ph(ctx, st, GIQL_PH_SORT_LOCAL, 3);
@@ -888,12 +965,12 @@ static int read_meta(giql_hip_ctx* ctx, hipStream_t st) {
   HIP_TRY(hipStreamSynchronize(st));
   int status = ctx->h_meta->status;
   // test hook (GIQL_HIP_INJECT_TIMEOUT=n): the n-th clean read-back of the context reports a timeout
-  if (ctx->inject_timeout > 0 && ctx->os_order != 0 && status == 0 && --ctx->inject_timeout == 0)
+  if (ctx->guess.inject_timeout > 0 && ctx->guess.os_order != 0 && status == 0 && --ctx->guess.inject_timeout == 0)
     status = ctx->h_meta->status = GIQL_ERR_HIP;
   if (status == GIQL_STATUS_RESORT)  // internal: with_order_fallback repeats the call with the four-pass sort
     return set_err(GIQL_STATUS_RESORT, "a 16-bit key bucket holds more than %u rows", BS_CAP);
   if (status == GIQL_ERR_HIP)
-    return set_err(GIQL_ERR_HIP, "onesweep look-back timed out (tile order %d)", ctx->os_order);
+    return set_err(GIQL_ERR_HIP, "onesweep look-back timed out (tile order %d)", ctx->guess.os_order);
   if (status == GIQL_ERR_CHROM)
     return set_err(GIQL_ERR_CHROM, "a chrom id is outside [0, n_chrom)");
   if (status == GIQL_ERR_SPAN)
@@ -927,9 +1004,8 @@ static void sort_sizes(Carver& c, size_t n, SortBufs& sb, bool payload) {
 // bracket then covers at least -- still fits the LDS stage of k_nearest (cfg 5: 1.115 -> 1.063 ms).  The
 // density comes from the span of the context's previous per-row call: a guess that only ever costs speed.
 static inline int row_skip(const giql_hip_ctx* ctx, size_t nb) {
-  if (ctx->row_skip_digits >= 0) return ctx->row_skip_digits;
-  if (ctx->last_span == 0) return 1;
-  return (double)nb * 65536.0 / (double)ctx->last_span <= 1024.0 ? 2 : 1;
+  if (ctx->guess.last_span == 0) return 1;
+  return (double)nb * 65536.0 / (double)ctx->guess.last_span <= 1024.0 ? 2 : 1;
 }
 
 // Fixed-length B of the per-row operators (SEMI / ANTI / COUNT): sorted without its lowest digit (three passes
@@ -937,8 +1013,8 @@ static inline int row_skip(const giql_hip_ctx* ctx, size_t nb) {
 // (aux_kernels.hip.h, "sorted COARSELY") -- by the density of the context's previous call, like row_skip(): a guess
 // that only costs speed.
 static inline bool coarse_b_ok(const giql_hip_ctx* ctx, size_t nb) {
-  if (ctx->no_coarse_b || ctx->no_skip_digit || ctx->last_span == 0 || sort_is_local(ctx, nb)) return false;
-  return (double)nb * 256.0 / (double)ctx->last_span <= ctx->coarse_max_group_rows;
+  if (ctx->sw.no_coarse_b || ctx->guess.last_span == 0 || sort_is_local(ctx, nb)) return false;
+  return (double)nb * 256.0 / (double)ctx->guess.last_span <= ctx->sw.coarse_max_group_rows;
 }
 
 // Fork / join of the context's second stream.  A side of a few million rows is a chain of ~10 launches
@@ -950,13 +1026,10 @@ struct SideChain {
   giql_hip_ctx* ctx;
   hipStream_t main;
   bool active = false, joined = false;
-  // n_small / n_large: rows of the side given to the second stream / of the side that stays.  The small
-  // side must be small (<= overlap_max_rows): its chain is then latency-bound and costs the other side's
+  // n_small: rows of the side given to the second stream.  It must be small (<= OVERLAP_MAX_ROWS): its chain is then latency-bound and costs the other side's
   // kernels little (SEMI 1M x 10M: 0.378 -> 0.349 ms; 1M x 1M: 0.387 -> 0.351 ms).
-  SideChain(giql_hip_ctx* c, hipStream_t m, size_t n_small, size_t n_large, int which = 1) : ctx(c), main(m) {
-    if (!c->side_stream || !(c->overlap_mask & which) || n_small == 0 || n_small > c->overlap_max_rows ||
-        (n_large > c->overlap_max_rows && !c->overlap_large))
-      return;
+  SideChain(giql_hip_ctx* c, hipStream_t m, size_t n_small) : ctx(c), main(m) {
+    if (!c->side_stream || n_small == 0 || n_small > OVERLAP_MAX_ROWS) return;
     if (sort_is_local(c, n_small)) return;  // the bucket sort's boundary / queue buffers are one per context
     if (hipEventRecord(c->ev_fork, m) != hipSuccess) return;
     if (hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) != hipSuccess) return;
@@ -976,25 +1049,50 @@ struct SideChain {
   }
 };
 
-// Belt and braces around the sort: its look-back makes progress whatever the dispatch
-// order (blocks compute silent predecessors themselves, k_onesweep), so a timeout status
-// is never expected; should one be reported all the same, the call is repeated ONCE in
-// the ticket order (order 0) and the context stays in that order.
+// A call returns this (internal, never across the C ABI) when one of the context's guesses turned out wrong at its
+// read-back: its result is not valid, the guess has been dropped (set from what the read-back showed), and
+// with_order_fallback repeats the call.  Each repeat runs with one guess fewer, so a call drops at most:
+//   INNER plan / join: 1 -- the speculated form, layout, fused count, sorted inputs and join in the bucket stage are
+//     all dropped together (spec_valid = false): the repeat reads the lengths back and speculates on nothing;
+//   SEMI / ANTI / COUNT: 1 -- the fixed length of B (row_spec_valid = false): the repeat reads it back;
+//   NEAREST k = 1: 2 -- the aligned layout (nearest_aligned = 0: the repeat builds no keys from the raw columns), then
+//     the pile-ups (nearest_two_sorts = true, which also turns the layout off): the two-sort plan guesses nothing;
+//   NEAREST k > 1, group_rows: 1 -- the pile-ups (nearest_two_sorts = true).
+constexpr int GIQL_STATUS_GUESS_MISSED = -101;
+constexpr int MAX_GUESS_MISSES = 2;
+
+// The one loop that repeats a call:
+//   a guess that missed (GIQL_STATUS_GUESS_MISSED): repeat, at most MAX_GUESS_MISSES times;
+//   a bucket too large for the in-LDS stage (GIQL_STATUS_RESORT, bucket_sort.hip.h): this table wants the four-pass
+//     sort -- for good on this context, so once;
+//   a look-back timeout: belt and braces around the sort -- its look-back makes progress whatever the dispatch order
+//     (blocks compute silent predecessors themselves, k_onesweep), so a timeout status is never expected; should one
+//     be reported all the same, the call is repeated in the ticket order (order 0) and the context stays in it: once.
+// Every attempt is a call of its own (its own prologue and guards); nothing of one attempt outlives it.
 template <typename F>
 static int with_order_fallback(giql_hip_ctx* ctx, F&& call) {
-  int rc = call();
-  if (rc == GIQL_STATUS_RESORT && ctx && ctx->local_sort) {
-    // a bucket too large for the in-LDS stage (bucket_sort.hip.h): this table wants the four-pass sort
-    ctx->local_sort = false;
-    ctx->local_resorts++;
-    rc = call();
+  int misses = 0;
+  for (;;) {
+    const int rc = call();
+    if (rc == GIQL_STATUS_GUESS_MISSED) {
+      if (++misses > MAX_GUESS_MISSES)
+        return set_err(GIQL_ERR_STATE, "internal: more than %d guesses missed in one call", MAX_GUESS_MISSES);
+      continue;
+    }
+    if (rc == GIQL_STATUS_RESORT && ctx && ctx->guess.local_sort) {
+      ctx->guess.local_sort = false;
+      ctx->guess.local_resorts++;
+      misses = 0;  // (the guesses the failed attempt met are still in place: the repeat may drop them again)
+      continue;
+    }
+    if (rc == GIQL_ERR_HIP && ctx && ctx->guess.os_order != 0 && ctx->h_meta && ctx->h_meta->status == GIQL_ERR_HIP) {
+      ctx->guess.os_order = 0;
+      ctx->guess.order_fallbacks++;
+      misses = 0;
+      continue;
+    }
+    return rc;
   }
-  if (rc == GIQL_ERR_HIP && ctx && ctx->os_order != 0 && ctx->h_meta && ctx->h_meta->status == GIQL_ERR_HIP) {
-    ctx->os_order = 0;
-    ctx->order_fallbacks++;
-    rc = call();
-  }
-  return rc;
 }
 
 // Fixed-length B side of the per-row operators: the canonical length every B row has (all of
@@ -1010,15 +1108,15 @@ static inline i64 uniform_len_b(const DevMeta& m) {
 static int row_form_guess(giql_hip_ctx* ctx, hipStream_t st, i64& uni_len, bool& speculated) {
   uni_len = 0;
   speculated = false;
-  if (ctx->no_uniform) return GIQL_OK;
-  if (ctx->row_spec_valid) {
-    uni_len = ctx->row_spec_len;
+  if (ctx->sw.no_uniform) return GIQL_OK;
+  if (ctx->guess.row_spec_valid) {
+    uni_len = ctx->guess.row_spec_len;
     speculated = true;
     return GIQL_OK;
   }
   GIQL_TRY(read_meta(ctx, st));
   uni_len = uniform_len_b(*ctx->h_meta);
-  ctx->last_span = ctx->h_meta->total_span;  // known before anything is sorted: the sort form follows the real density
+  ctx->guess.last_span = ctx->h_meta->total_span;  // known before anything is sorted: the sort form follows the real density
   return GIQL_OK;
 }
 
@@ -1026,12 +1124,62 @@ static int row_form_guess(giql_hip_ctx* ctx, hipStream_t st, i64& uni_len, bool&
 // B does not have (its result is wrong: repeat it; the general form is right on any input, so a
 // wrong "not fixed-length" guess only costs speed).
 static bool row_form_settled(giql_hip_ctx* ctx, i64 uni_len, bool speculated) {
-  if (ctx->no_uniform) return true;
+  if (ctx->sw.no_uniform) return true;
   const i64 actual = uniform_len_b(*ctx->h_meta);
   const bool ok = !(speculated && uni_len != 0 && actual != uni_len);
-  ctx->row_spec_valid = ok;
-  ctx->row_spec_len = actual;
+  ctx->guess.row_spec_valid = ok;
+  ctx->guess.row_spec_len = actual;
   return ok;
+}
+
+// ------------------------------------------------------------- switches
+static void parse_flag(const char* v, void* f) { *(bool*)f = atoi(v) != 0; }
+static void parse_int(const char* v, void* f) { *(int*)f = atoi(v); }
+static void parse_u32(const char* v, void* f) { *(u32*)f = (u32)strtoul(v, nullptr, 10); }
+static void parse_classic(const char* v, void* f) { *(bool*)f = strcmp(v, "classic") == 0; }
+static void parse_positive(const char* v, void* f) {
+  if (atof(v) > 0) *(double*)f = atof(v);
+}
+static void parse_nonnegative(const char* v, void* f) {
+  if (atof(v) >= 0) *(double*)f = atof(v);
+}
+static void parse_local_bits(const char* v, void* f) {
+  if (atoi(v) >= BS_MIN_WBITS && atoi(v) <= 16) *(int*)f = atoi(v);
+}
+static void parse_local_min_rows(const char* v, void* f) {
+  Switches& s = *(Switches*)f;
+  s.local_min_rows = strtoull(v, nullptr, 10);
+  s.local_max_bucket_rows = 1e30;  // a forced size threshold (tests, sweeps) is not second-guessed by density
+  s.local_min_bucket_rows = 0.0;
+}
+
+static Switches read_switches() {
+  Switches s;
+  const struct {
+    const char* name;
+    void (*parse)(const char*, void*);
+    void* field;
+  } table[] = {
+      {"GIQL_HIP_SORT", parse_classic, &s.classic_sort},
+      {"GIQL_HIP_OS_VARIANT", parse_int, &s.os_variant},
+      {"GIQL_HIP_OS_ORDER", parse_int, &s.os_order},
+      {"GIQL_HIP_OS_HELP_AFTER", parse_u32, &s.os_help_after},
+      {"GIQL_HIP_INJECT_TIMEOUT", parse_int, &s.inject_timeout},
+      {"GIQL_HIP_NO_UNIFORM", parse_flag, &s.no_uniform},
+      {"GIQL_HIP_NO_SPAN_HIST", parse_flag, &s.no_span_hist},
+      {"GIQL_HIP_NO_COARSE_B", parse_flag, &s.no_coarse_b},
+      {"GIQL_HIP_COARSE_MAX_GROUP_ROWS", parse_positive, &s.coarse_max_group_rows},
+      {"GIQL_HIP_NO_FUSE_COUNT", parse_flag, &s.no_fuse_count},
+      {"GIQL_HIP_NO_LOCAL_SORT", parse_flag, &s.no_local_sort},
+      {"GIQL_HIP_LOCAL_MIN_ROWS", parse_local_min_rows, &s},  // (before the two bounds it lifts: they may be set too)
+      {"GIQL_HIP_LOCAL_MIN_BUCKET_ROWS", parse_nonnegative, &s.local_min_bucket_rows},
+      {"GIQL_HIP_LOCAL_MAX_BUCKET_ROWS", parse_positive, &s.local_max_bucket_rows},
+      {"GIQL_HIP_NO_NARROW_BUCKETS", parse_flag, &s.no_narrow},
+      {"GIQL_HIP_LOCAL_BITS", parse_local_bits, &s.force_bits},
+  };
+  for (const auto& row : table)
+    if (const char* v = getenv(row.name)) row.parse(v, row.field);
+  return s;
 }
 
 // ================================================================= C ABI
@@ -1057,71 +1205,9 @@ int giql_hip_create(int device, giql_hip_ctx** out) {
   if (device < 0 || device >= n)
     return set_err(GIQL_ERR_INVALID, "device %d not in [0,%d)", device, n);
   HIP_TRY(hipSetDevice(device));
-  giql_hip_ctx* ctx = new (std::nothrow) giql_hip_ctx();
+  giql_hip_ctx* ctx = new (std::nothrow) giql_hip_ctx(read_switches());
   if (!ctx) return set_err(GIQL_ERR_NOMEM, "out of host memory");
   ctx->device = device;
-  {
-    const char* e = getenv("GIQL_HIP_SORT");
-    ctx->classic_sort = e && strcmp(e, "classic") == 0;
-    const char* v = getenv("GIQL_HIP_OS_VARIANT");
-    ctx->os_variant = v ? atoi(v) : 0;
-    const char* nc1 = getenv("GIQL_HIP_NO_C1_FILL");
-    ctx->no_c1_fill = nc1 && atoi(nc1) != 0;
-    const char* nkg = getenv("GIQL_HIP_NO_KEYGEN_GENERAL");
-    ctx->no_keygen_general = nkg && atoi(nkg) != 0;
-    const char* nsw = getenv("GIQL_HIP_NO_SWAP");
-    ctx->no_swap = nsw && atoi(nsw) != 0;
-    const char* c1i = getenv("GIQL_HIP_C1_ITEMS");
-    if (c1i && (atoi(c1i) == 2 || atoi(c1i) == C1_ITEMS_MAX)) ctx->c1_items = atoi(c1i);
-    const char* o = getenv("GIQL_HIP_OS_ORDER");
-    if (o) ctx->os_order = atoi(o);
-    const char* ha = getenv("GIQL_HIP_OS_HELP_AFTER");
-    if (ha) ctx->os_help_after = (u32)strtoul(ha, nullptr, 10);
-    const char* it = getenv("GIQL_HIP_INJECT_TIMEOUT");
-    if (it) ctx->inject_timeout = atoi(it);
-    const char* u = getenv("GIQL_HIP_NO_UNIFORM");
-    ctx->no_uniform = u && atoi(u) != 0;
-    const char* nh = getenv("GIQL_HIP_NO_SPAN_HIST");
-    ctx->no_span_hist = nh && atoi(nh) != 0;
-    const char* nsd = getenv("GIQL_HIP_NO_SKIP_DIGIT");
-    ctx->no_skip_digit = nsd && atoi(nsd) != 0;
-    const char* nuf = getenv("GIQL_HIP_NO_UNSTABLE_FIRST");
-    ctx->no_unstable_first = nuf && atoi(nuf) != 0;
-    const char* nds = getenv("GIQL_HIP_NO_DUAL_SPAN");
-    ctx->no_dual_span = nds && atoi(nds) != 0;
-    const char* ncb = getenv("GIQL_HIP_NO_COARSE_B");
-    ctx->no_coarse_b = ncb && atoi(ncb) != 0;
-    const char* cmb = getenv("GIQL_HIP_COARSE_MAX_GROUP_ROWS");
-    if (cmb && atof(cmb) > 0) ctx->coarse_max_group_rows = atof(cmb);
-    const char* rsd = getenv("GIQL_HIP_ROW_SKIP_DIGITS");
-    if (rsd && atoi(rsd) >= 0 && atoi(rsd) <= 3) ctx->row_skip_digits = atoi(rsd);
-    const char* nfc = getenv("GIQL_HIP_NO_FUSE_COUNT");
-    ctx->no_fuse_count = nfc && atoi(nfc) != 0;
-    const char* nbj = getenv("GIQL_HIP_NO_BUCKET_JOIN");
-    ctx->no_bucket_join = nbj && atoi(nbj) != 0;
-    const char* nso = getenv("GIQL_HIP_NO_SORTED_INPUT");
-    ctx->no_sorted = nso && atoi(nso) != 0;
-    const char* nkq = getenv("GIQL_HIP_NO_KEYGEN_Q");
-    ctx->no_keygen_q = nkq && atoi(nkq) != 0;
-    const char* qsd = getenv("GIQL_HIP_Q_SKIP_DIGITS");
-    if (qsd && atoi(qsd) >= 1 && atoi(qsd) <= 2) ctx->fuse_q_skip = atoi(qsd);
-    const char* nl = getenv("GIQL_HIP_NO_LOCAL_SORT");
-    if (nl && atoi(nl) != 0) ctx->local_sort = false;
-    const char* lm = getenv("GIQL_HIP_LOCAL_MIN_ROWS");
-    if (lm) {
-      ctx->local_min_rows = strtoull(lm, nullptr, 10);
-      ctx->local_max_bucket_rows = 1e30;  // a forced size threshold (tests, sweeps) is not second-guessed by density
-      ctx->local_min_bucket_rows = 0.0;
-    }
-    const char* lnb = getenv("GIQL_HIP_LOCAL_MIN_BUCKET_ROWS");
-    if (lnb && atof(lnb) >= 0) ctx->local_min_bucket_rows = atof(lnb);
-    const char* lmb = getenv("GIQL_HIP_LOCAL_MAX_BUCKET_ROWS");
-    if (lmb && atof(lmb) > 0) ctx->local_max_bucket_rows = atof(lmb);
-    const char* nnb = getenv("GIQL_HIP_NO_NARROW_BUCKETS");
-    ctx->no_narrow = nnb && atoi(nnb) != 0;
-    const char* lbw = getenv("GIQL_HIP_LOCAL_BITS");
-    if (lbw && atoi(lbw) >= BS_MIN_WBITS && atoi(lbw) <= 16) ctx->force_bits = atoi(lbw);
-  }
   memset(&ctx->stats, 0, sizeof(ctx->stats));
   {
     hipDeviceProp_t prop;
@@ -1131,21 +1217,11 @@ int giql_hip_create(int device, giql_hip_ctx** out) {
   hipError_t e = hipMalloc((void**)&ctx->d_meta, sizeof(DevMeta));
   if (e == hipSuccess) e = hipHostMalloc((void**)&ctx->h_meta, sizeof(DevMeta), hipHostMallocDefault);
   if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_scratch64, 64);
-  {
-    const char* om = getenv("GIQL_HIP_OVERLAP_MASK");
-    if (om) ctx->overlap_mask = atoi(om);
-    const char* no = getenv("GIQL_HIP_NO_OVERLAP");
-    if (!(no && atoi(no) != 0) && e == hipSuccess) {
-      const char* omr = getenv("GIQL_HIP_OVERLAP_MAX_ROWS");
-      if (omr && atoll(omr) > 0) ctx->overlap_max_rows = (u64)atoll(omr);
-      const char* ol = getenv("GIQL_HIP_OVERLAP_LARGE");
-      if (ol) ctx->overlap_large = atoi(ol) != 0;
-      if (hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking) != hipSuccess ||
-          hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess)
-        ctx->side_stream = nullptr;  // no second stream: everything stays on the caller's
-    }
-  }
+  if (e == hipSuccess &&
+      (hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking) != hipSuccess ||
+       hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
+       hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess))
+    ctx->side_stream = nullptr;  // no second stream: everything stays on the caller's
   if (e == hipSuccess) e = hipMalloc((void**)&ctx->bucket_bnd, ((size_t)BS_MAX_BUCKETS + 16) * sizeof(u32));
   if (e == hipSuccess) e = hipMalloc((void**)&ctx->bucket_big, ((size_t)BS_MAX_BUCKETS + 16) * sizeof(u32));
   if (e == hipSuccess) e = hipMalloc((void**)&ctx->bucket_qwin, ((size_t)2 * BS_MAX_BUCKETS + 16) * sizeof(u32));
@@ -1209,56 +1285,53 @@ int giql_hip_get_stats(giql_hip_ctx* ctx, giql_hip_stats* out) {
   // byte 0: join form (+ bit 5: a side was sorted in three stages, bit 6: this context fell back to
   // the four-pass sort for good); byte 1: sort tile order in force; bits 16-26: order fallbacks so far; bits 27-28:
   // 16 - the key bits of the last bucket stage's buckets (0: 65,536-key buckets)
-  out->reserved = (ctx->stats.reserved & 0x1F) | (ctx->last_sort_local ? 0x20 : 0) |
-                  (ctx->local_resorts ? 0x40 : 0) | (ctx->swapped ? 0x80 : 0) | ((ctx->os_order & 0x7F) << 8) |
-                  (ctx->count_fused ? 0x8000 : 0) | ((ctx->used_sorted[0] || ctx->used_sorted[1]) ? (int32_t)0x80000000u : 0) |
-                  ((ctx->order_fallbacks & 0x7FF) << 16) | (((16 - ctx->last_local_bits) & 3) << 27) |
-                  (ctx->bucket_join ? (1 << 29) : 0) |
-                  (ctx->fuse_done ? (1 << 30) : 0);
+  out->reserved = (ctx->stats.reserved & 0x1F) | (ctx->call.last_sort_local ? 0x20 : 0) |
+                  (ctx->guess.local_resorts ? 0x40 : 0) | (ctx->plan.swapped ? 0x80 : 0) | ((ctx->guess.os_order & 0x7F) << 8) |
+                  (ctx->call.count_fused ? 0x8000 : 0) | ((ctx->call.used_sorted[0] || ctx->call.used_sorted[1]) ? (int32_t)0x80000000u : 0) |
+                  ((ctx->guess.order_fallbacks & 0x7FF) << 16) | (((16 - ctx->call.last_local_bits) & 3) << 27) |
+                  (ctx->call.bucket_join ? (1 << 29) : 0) |
+                  (ctx->plan.fuse_done ? (1 << 30) : 0);
   return GIQL_OK;
 }
 
 // ------------------------------------------------------------------ INNER
 static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b,
                            int32_t n_chrom, void* stream, int64_t* n_pairs) {
-  HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  ctx->planned = false;
-  ctx->fuse_done = false;
-  reset_stats(ctx);
-  ctx->stats.n_a = a->n;
+  ctx->plan.fuse_done = false;
+  ctx->stats.n_a = a->n;  // (in the plan's labels: giql_hip_inner_plan_dev_impl labels them back)
   ctx->stats.n_b = b->n;
-  ctx->side_a = *a;
-  ctx->side_b = *b;
-  ctx->n_a = (u32)a->n;
-  ctx->n_b = (u32)b->n;
-  ctx->n_chrom = n_chrom;
-  ctx->n_reg = ctx->n_irr = ctx->n_c1 = 0;
+  ctx->plan.side_a = *a;
+  ctx->plan.side_b = *b;
+  ctx->plan.n_a = (u32)a->n;
+  ctx->plan.n_b = (u32)b->n;
+  ctx->plan.n_chrom = n_chrom;
+  ctx->plan.n_reg = ctx->plan.n_irr = ctx->plan.n_c1 = 0;
   *n_pairs = 0;
   if (a->n == 0 || b->n == 0 || n_chrom == 0) {  // empty result (tests :4173-4229)
-    ctx->planned = true;
-    ctx->plan_is_join = false;
+    ctx->plan.planned = true;
+    ctx->plan.plan_is_join = false;
     return GIQL_OK;
   }
   const size_t na = (size_t)a->n, nb = (size_t)b->n, nq = na + nb;
 
   // ---- carve the arena (dry run for the size, then for real)
   LinBufs lb;
-  InnerState& S = ctx->inner;
+  InnerState& S = ctx->plan.inner;
   u32 *tile_hist = nullptr, *cnt2 = nullptr, *irr_cnt = nullptr;
   u32 *hist_a = nullptr, *hist_b = nullptr, *gbase_a = nullptr, *gbase_b = nullptr;
   u32 *os_status = nullptr, *os_status2 = nullptr, *top_partial_q = nullptr;
   u64 *bsums = nullptr, *bsums1 = nullptr, *scan_chain = nullptr;
   size_t zero_off = 0, zero_end = 0;  // arena offsets of the region zeroed up front ([zero_off, zero_end + the larger side's status words))
-  const bool onesweep = !ctx->classic_sort && na <= OS_MAX_ROWS && nb <= OS_MAX_ROWS;
+  const bool onesweep = !ctx->sw.classic_sort && na <= OS_MAX_ROWS && nb <= OS_MAX_ROWS;
   const size_t n_max = na > nb ? na : nb;
   const size_t n_tiles_max = cdiv(n_max, RS_TILE);
   const size_t scan_max = (nq > n_tiles_max * RS_BINS ? nq : n_tiles_max * RS_BINS);
   constexpr u32 TQ2 = RC_NT * RC_ITEMS_C2;
-  S.c1_items = ctx->c1_items ? ctx->c1_items : (nb <= ctx->c1_small_rows ? 2 : C1_ITEMS_MAX);
+  S.c1_items = nb <= C1_SMALL_ROWS ? 2 : C1_ITEMS_MAX;
   const u32 c1_tq = (u32)(C1_NT * S.c1_items);  // class-1 rows per block
   S.nt1 = cdiv(nb, c1_tq);
-  S.c1_fill = !ctx->no_c1_fill && nb <= ctx->c1_small_rows;
+  S.c1_fill = nb <= C1_SMALL_ROWS;
   S.nt2 = cdiv(na, TQ2);
   auto carve = [&](char* base) {
     Carver c{base};
@@ -1292,41 +1365,31 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
     S.cnt1 = c.take<u32>(n1);
     S.off1 = c.take<u64>(n1 + 1);
     bsums1 = c.take<u64>(cdiv(n1 ? n1 : 1, SCAN_TILE) + 2);
-    const size_t nq2 = ctx->no_uniform ? na : n_max;  // the uniform form may query the other side
+    const size_t nq2 = ctx->sw.no_uniform ? na : n_max;  // the uniform form may query the other side
     S.wlo2 = c.take<u32>((size_t)cdiv(nq2, TQ2) + 2);
     cnt2 = c.take<u32>(nq2);
     S.cnt2 = cnt2;
     S.lo2 = c.take<u32>(nq2);
     S.off2 = c.take<u64>(nq2 + 1);
     scan_chain = c.take<u64>((size_t)cdiv(nq2, SCAN_TILE) + 4);  // chained scan: a status word per tile + the ticket
-    ctx->irr_a_list = c.take<u32>(na);
-    ctx->irr_b_list = c.take<u32>(nb);
+    ctx->plan.irr_a_list = c.take<u32>(na);
+    ctx->plan.irr_b_list = c.take<u32>(nb);
     irr_cnt = c.take<u32>(nq);
-    ctx->irr_off = c.take<u64>(nq + 1);
+    ctx->plan.irr_off = c.take<u64>(nq + 1);
     return c.off;
   };
-  const size_t need = carve(nullptr);
-  GIQL_TRY(ensure_arena(ctx, need, st));
-  carve(ctx->arena);
+  GIQL_TRY(claim_arena(ctx, st, carve));
   SortBufs& sa = S.sa;
   SortBufs& sbb = S.sb;
-  struct Prezero {  // the helpers skip their own memsets while this plan runs
-    giql_hip_ctx* c;
-    ~Prezero() {
-      c->prezeroed = false;
-      c->first_unstable = false;
-    }
-  } prezero_guard{ctx};
-  ctx->first_unstable = true;  // an INNER join needs no order among rows of equal keys: first passes rank by LDS atomics
-  ctx->prezeroed = false;
-  ctx->span_hist_dirty[0] = ctx->span_hist_dirty[1] = nullptr;
+  PrezeroGuard prezero_guard{ctx};  // the helpers skip their own memsets while this plan runs
+  ctx->call.first_unstable = true;  // an INNER join needs no order among rows of equal keys: first passes rank by LDS atomics
   int big_passes_zeroed = 0;
   if (onesweep) {
     // the larger side takes at most 4 passes (2 in the three-stage form)
     big_passes_zeroed = sort_is_local(ctx, n_max) ? local_passes(sort_local_bits(ctx, n_max)) : 4;
     const size_t big_words = (size_t)big_passes_zeroed * os_pass_stride(ctx, n_max);
     HIP_TRY(hipMemsetAsync(ctx->arena + zero_off, 0, (zero_end - zero_off) + big_words * sizeof(u32), st));
-    ctx->prezeroed = true;
+    ctx->call.prezeroed = true;
   }
 
   // The larger side is the one the uniform form prefers as its fixed-length side: its span pass
@@ -1334,17 +1397,17 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
   // hold, it is sorted straight from its raw columns with no linearize pass.  A context that
   // has planned before asks for it only when its last plan ended that way.
   const int big_side = nb >= na ? 1 : 0;
-  bool want_hist = onesweep && !ctx->no_span_hist && ctx->os_variant == 0 &&
+  bool want_hist = onesweep && !ctx->sw.no_span_hist && ctx->sw.os_variant == 0 &&
                    n_chrom <= MM_HIST_CHROMS;
-  if (want_hist && ctx->spec_valid)  // ... or in the general form without irregular rows (its larger side)
-    want_hist = ctx->spec_aligned && (ctx->spec_form == (big_side ? 1 : 2) ||
-                                      (ctx->spec_form == 0 && ctx->last_no_irr && !ctx->no_keygen_general));
+  if (want_hist && ctx->guess.spec_valid)  // ... or in the general form without irregular rows (its larger side)
+    want_hist = ctx->guess.spec_aligned && (ctx->guess.spec_form == (big_side ? 1 : 2) ||
+                                      (ctx->guess.spec_form == 0 && ctx->guess.last_no_irr));
   // ... and the QUERY side of the fixed-length form too (round 3): its (key, end, rid) sort starts from the raw
   // columns as well (k_onesweep<3, .., KEYGEN>), so neither side has a linearize pass -- on the guesses that the
   // form and the layout hold AND that the query side has no irregular row (those carry the sentinel key and a
   // list entry, which only the linearize pass produces): validated at the read-back like the others.
-  const bool want_hist_q = want_hist && ctx->spec_valid && ctx->spec_form == (big_side ? 1 : 2) && ctx->last_no_irr &&
-                           !ctx->no_keygen_q && (big_side ? na : nb) > 0;
+  const bool want_hist_q = want_hist && ctx->guess.spec_valid && ctx->guess.spec_form == (big_side ? 1 : 2) && ctx->guess.last_no_irr &&
+                           (big_side ? na : nb) > 0;
   if (want_hist_q) {
     lb.hist_partial2 = big_side ? hist_a : hist_b;
     lb.top_partial2 = top_partial_q;
@@ -1366,7 +1429,7 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
     const bool ua = m.len_min_a == m.len_max_a && m.len_max_a > 0;
     form = 0;
     len = 0;
-    if (ctx->no_uniform) return;  // GIQL_HIP_NO_UNIFORM: the general form whatever the lengths
+    if (ctx->sw.no_uniform) return;  // GIQL_HIP_NO_UNIFORM: the general form whatever the lengths
     // sort the uniform side without its end; prefer the larger side when both are
     if (ub && (!ua || nb >= na)) {
       form = 1;
@@ -1380,10 +1443,10 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
   bool coarse_q = false;  // the query side was sorted without its lowest digit (a guess: no irregular rows)
   bool keygen_q = false;  // ... and from its raw columns (the same guess)
   if (onesweep) {
-    if (ctx->spec_valid) {
-      S.uniform = ctx->spec_form;
-      uni_len = ctx->spec_len;
-      aligned = want_hist;  // = ctx->spec_aligned when the form matches
+    if (ctx->guess.spec_valid) {
+      S.uniform = ctx->guess.spec_form;
+      uni_len = ctx->guess.spec_len;
+      aligned = want_hist;  // = ctx->guess.spec_aligned when the form matches
       speculated = true;
     } else {
       GIQL_TRY(read_meta(ctx, st));
@@ -1395,7 +1458,7 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
       // is linearized (which counts all four digits)
       const size_t n_big = big_side ? nb : na;
       const int expected_bits = sort_local_bits(ctx, n_big);
-      ctx->last_span = ctx->h_meta->total_span;
+      ctx->guess.last_span = ctx->h_meta->total_span;
       // (the high-digits-only histogram serves 16-bit buckets alone: narrower ones sort on bits 8-15 too)
       if (expected_bits == 16 && sort_local_bits(ctx, n_big) != 16) aligned = false;
       const int passes_now = sort_is_local(ctx, n_max) ? local_passes(sort_local_bits(ctx, n_max)) : 4;
@@ -1411,18 +1474,18 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
   // Sorted inputs: a side the span pass found in (chrom id, start) order (and free of irregular rows) skips its
   // sort -- from the read-back on a first plan, the previous plan's answer afterwards (validated below)
   bool pre_a = false, pre_b = false;
-  if (onesweep && !ctx->no_sorted) {
-    pre_a = speculated ? ctx->spec_sorted[0] : ctx->h_meta->unsorted_a == 0;
-    pre_b = speculated ? ctx->spec_sorted[1] : ctx->h_meta->unsorted_b == 0;
+  if (onesweep) {
+    pre_a = speculated ? ctx->guess.spec_sorted[0] : ctx->h_meta->unsorted_a == 0;
+    pre_b = speculated ? ctx->guess.spec_sorted[1] : ctx->h_meta->unsorted_b == 0;
   }
-  ctx->used_sorted[0] = pre_a;
-  ctx->used_sorted[1] = pre_b;
+  ctx->call.used_sorted[0] = pre_a;
+  ctx->call.used_sorted[1] = pre_b;
   const bool keygen = aligned && S.uniform == (big_side ? 1 : 2);
   // General form: the larger side's (key, end, rid) sort can start from the raw columns too, as long as
   // that side holds no irregular row (those carry the sentinel key, which depends on `end`; the span pass
   // counted digits of start alone).  Known from the read-back on a first plan, a guess afterwards.
-  const bool keygen_g = aligned && S.uniform == 0 && !ctx->no_keygen_general &&
-                        (speculated ? ctx->last_no_irr
+  const bool keygen_g = aligned && S.uniform == 0 &&
+                        (speculated ? ctx->guess.last_no_irr
                                     : (big_side ? ctx->h_meta->len_min_b : ctx->h_meta->len_min_a) > 0);
   const u32* irr_a = &ctx->d_meta->irr_a;
   const u32* irr_b = &ctx->d_meta->irr_b;
@@ -1439,8 +1502,8 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
     // (bucket_sort.hip.h) -- as long as no query row is longer than the windows allow for: known from the
     // read-back on a first plan, the previous plan's answer afterwards (validated below like the other guesses)
     const int q_len_max = q_is_a ? ctx->h_meta->len_max_a : ctx->h_meta->len_max_b;
-    const bool fuse_cnt = !ctx->no_fuse_count && sort_is_local(ctx, nu) &&
-                          (speculated ? ctx->spec_fuse_len_ok : q_len_max <= (int)BS_FUSE_WCAP);
+    const bool fuse_cnt = !ctx->sw.no_fuse_count && sort_is_local(ctx, nu) &&
+                          (speculated ? ctx->guess.spec_fuse_len_ok : q_len_max <= (int)BS_FUSE_WCAP);
     // the query side's chain (linearize + sort) beside the other side's when it is small (the fused count
     // needs the sorted queries before U's last stage: one stream)
     // the query side sorted from its raw columns too (its digits were counted in the span pass)
@@ -1464,15 +1527,15 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
       GIQL_TRY(post_launch("digit offsets (span histogram)"));
     }
     // (the fork comes AFTER the digit offsets above: the query side's sort on the second stream reads them)
-    SideChain sc(ctx, st, (nqr <= nu && !fuse_cnt) ? nqr : 0, nu);
+    SideChain sc(ctx, st, (nqr <= nu && !fuse_cnt) ? nqr : 0);
     if (!keygen_q) {
       GIQL_TRY(run_linearize(ctx, sc.stream(), qs_, n_chrom, lb, sq.key[0], sq.end[0],
-                             q_is_a ? ctx->irr_a_list : ctx->irr_b_list, q_is_a ? 0 : 1, 0,
+                             q_is_a ? ctx->plan.irr_a_list : ctx->plan.irr_b_list, q_is_a ? 0 : 1, 0,
                              hist_q, q_is_a ? gbase_a : gbase_b));
     }
     if (!keygen) {
       GIQL_TRY(run_linearize(ctx, st, us_, n_chrom, lb, su.key[0], nullptr,
-                             q_is_a ? ctx->irr_b_list : ctx->irr_a_list, q_is_a ? 1 : 0, 0,
+                             q_is_a ? ctx->plan.irr_b_list : ctx->plan.irr_a_list, q_is_a ? 1 : 0, 0,
                              q_is_a ? hist_b : hist_a, q_is_a ? gbase_b : gbase_a, nullptr, nullptr,
                              /*skip_end=*/true));  // uniform => no irregular row: `end` is not read
     }
@@ -1482,11 +1545,11 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
     // only on the context's guess that there are none, validated with the other guesses below.
     // With the fused count the queries only have to be grouped by the bucket their key falls into (the windows
     // of k_bucket_bounds_fused are computed under the same mask and then cover whole query buckets): TWO digits
-    // unsorted, two passes (GIQL_HIP_Q_SKIP_DIGITS=1 keeps three).
-    int q_skip = (speculated && ctx->last_no_irr && !ctx->no_skip_digit && !sort_is_local(ctx, nqr)) ? 1 : 0;
+    // unsorted, two passes.
+    int q_skip = (speculated && ctx->guess.last_no_irr && !sort_is_local(ctx, nqr)) ? 1 : 0;
     // (narrower buckets: the queries stay grouped by key >> 8 -- a window under the 16-bit mask would span 2-8 buckets)
     const int wb_u = sort_local_bits(ctx, nu);
-    if (q_skip && fuse_cnt && ctx->fuse_q_skip > 1 && wb_u == 16) q_skip = ctx->fuse_q_skip;
+    if (q_skip && fuse_cnt && wb_u == 16) q_skip = 2;
     coarse_q = q_skip != 0;
     const u32 q_mask = q_skip == 2 ? 0xFFFF0000u : (q_skip == 1 ? 0xFFFFFF00u : 0xFFFFFFFFu);
     // (the smaller side's passes use the smaller status buffer: both were zeroed up front, neither is reused)
@@ -1500,9 +1563,9 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
     // plan, with a grid bounded by the capacity and the true count read on the device.
     constexpr u32 T2 = FILL_NT * FILL_ITEMS_C2;
     static_assert((T2 & (T2 - 1)) == 0, "fill tiles are a power of two (k_scan_chain_diff shifts)");
-    const u64 nt_cap64 = (ctx->fuse_cap + T2 - 1) / T2;
-    const bool early_fill = ctx->fuse_a && speculated && ctx->last_no_irr && ctx->fuse_cap > 0 &&
-                            nt_cap64 <= 0x7FFFFFF0ull && (size_t)nt_cap64 + 2 <= ctx->part_cap;
+    const u64 nt_cap64 = (ctx->plan.fuse_cap + T2 - 1) / T2;
+    const bool early_fill = ctx->plan.fuse_a && speculated && ctx->guess.last_no_irr && ctx->plan.fuse_cap > 0 &&
+                            nt_cap64 <= 0x7FFFFFF0ull && ((size_t)nt_cap64 + 2) * sizeof(u32) <= ctx->part_cap;
     bool part_done = false;  // the scan wrote the fill's partition
     // ... and, when the other side's bucket stage answers the bounds anyway, the pairs are written right there
     // (bucket_sort.hip.h, FUSE == 2) -- as long as the query windows stay well inside what a block holds in
@@ -1511,17 +1574,17 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
     const double win_keys = q_skip == 2 ? 3.0 * 65536.0 + (double)uni_len
                                         : (double)(1u << (wb_u ? wb_u : 16)) + 512.0 + (double)uni_len +
                                               (double)(q_len_max > 0 ? q_len_max : 0);
-    const bool join_in_buckets = fuse_cnt && !ctx->no_bucket_join && ctx->fuse_a && speculated && ctx->last_no_irr &&
-                                 ctx->fuse_cap > 0 && ctx->last_span > 0 &&
-                                 (double)nqr * win_keys / (double)ctx->last_span <= 0.75 * (double)BJ_WCAP;
+    const bool join_in_buckets = fuse_cnt && ctx->plan.fuse_a && speculated && ctx->guess.last_no_irr &&
+                                 ctx->plan.fuse_cap > 0 && ctx->guess.last_span > 0 &&
+                                 (double)nqr * win_keys / (double)ctx->guess.last_span <= 0.75 * (double)BJ_WCAP;
     FuseCount fc;
     if (fuse_cnt) {
       if (join_in_buckets) {
         fc.join = true;
         fc.dev.qrid = sq.rid[0];
-        fc.dev.row_q = q_is_a ? ctx->fuse_a : ctx->fuse_b;
-        fc.dev.row_s = q_is_a ? ctx->fuse_b : ctx->fuse_a;
-        fc.dev.cap = ctx->fuse_cap;
+        fc.dev.row_q = q_is_a ? ctx->plan.fuse_a : ctx->plan.fuse_b;
+        fc.dev.row_s = q_is_a ? ctx->plan.fuse_b : ctx->plan.fuse_a;
+        fc.dev.cap = ctx->plan.fuse_cap;
         fc.dev.cursor = reinterpret_cast<unsigned long long*>(&ctx->d_meta->n_out);  // zeroed by the span pass
       }
       fc.zero_ptr = reinterpret_cast<u32*>(scan_chain);
@@ -1544,9 +1607,9 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
     GIQL_TRY(sc.join());
     constexpr u32 TQ = RC_NT * RC_ITEMS_C2;
     S.nt2 = cdiv(nqr, TQ);
-    if (ctx->bucket_join) {
+    if (ctx->call.bucket_join) {
       // the pairs are out already, counted in DevMeta::n_out
-    } else if (ctx->count_fused) {
+    } else if (ctx->call.count_fused) {
       u32 log2_t2 = 0;
       while ((1u << log2_t2) < T2) log2_t2++;
       GIQL_TRY(run_scan_chain(ctx, st, GIQL_PH_SCAN, cnt2, S.lo2, nqr, q_is_a ? irr_a : irr_b, S.off2, scan_chain,
@@ -1572,49 +1635,49 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
     {
       // The early fill: no stream sync between plan and fill.  Validated below; a wrong guess leaves the
       // buffers to the ordinary fill.
-      if (ctx->bucket_join) {
+      if (ctx->call.bucket_join) {
         fused = true;
       } else if (early_fill) {
         const u32 nt_cap = (u32)nt_cap64;
         const u32* qrid = q_is_a ? sa.rid[0] : sbb.rid[0];
         const u32* srid = q_is_a ? sbb.rid[0] : sa.rid[0];
-        int32_t* rq = q_is_a ? ctx->fuse_a : ctx->fuse_b;
-        int32_t* rs = q_is_a ? ctx->fuse_b : ctx->fuse_a;
+        int32_t* rq = q_is_a ? ctx->plan.fuse_a : ctx->plan.fuse_b;
+        int32_t* rs = q_is_a ? ctx->plan.fuse_b : ctx->plan.fuse_a;
         if (!part_done) {
           Phase ph(ctx, st, GIQL_PH_PARTITION);
           hipLaunchKernelGGL(k_partition, dim3(cdiv((u64)nt_cap + 1, 256)), dim3(256), 0, st, S.off2,
-                             (u32)nqr, (u64)0, T2, nt_cap, ctx->part, (const u64*)(S.off2 + nqr), ctx->fuse_cap);
+                             (u32)nqr, (u64)0, T2, nt_cap, ctx->part, (const u64*)(S.off2 + nqr), ctx->plan.fuse_cap);
         }
         {
           Phase ph(ctx, st, GIQL_PH_FILL);
           hipLaunchKernelGGL((k_fill<FILL_ITEMS_C2>), dim3(nt_cap), dim3(FILL_NT), 0, st, S.off2, S.lo2, qrid,
-                             (u32)nqr, srid, ctx->part, (u64)0, (u64)0, rq, rs, (const u64*)(S.off2 + nqr), ctx->fuse_cap);
+                             (u32)nqr, srid, ctx->part, (u64)0, (u64)0, rq, rs, (const u64*)(S.off2 + nqr), ctx->plan.fuse_cap);
         }
         GIQL_TRY(post_launch("fused fill"));
         fused = true;
       }
     }
     GIQL_TRY(read_meta(ctx, st));
-    ctx->n_c1 = 0;
-    ctx->n_reg = ctx->h_meta->n_out;
+    ctx->plan.n_c1 = 0;
+    ctx->plan.n_reg = ctx->h_meta->n_out;
     // the early fill stands only if every guess held and the pairs fitted
-    ctx->fuse_done = fused && ctx->h_meta->irr_a + ctx->h_meta->irr_b == 0 && ctx->n_reg <= ctx->fuse_cap;
-    if (ctx->bucket_join) ctx->stats.phase_bytes[GIQL_PH_SORT_LOCAL] += (int64_t)8 * (int64_t)ctx->n_reg;  // the pairs
+    ctx->plan.fuse_done = fused && ctx->h_meta->irr_a + ctx->h_meta->irr_b == 0 && ctx->plan.n_reg <= ctx->plan.fuse_cap;
+    if (ctx->call.bucket_join) ctx->stats.phase_bytes[GIQL_PH_SORT_LOCAL] += (int64_t)8 * (int64_t)ctx->plan.n_reg;  // the pairs
   } else {
   // The join itself in B's bucket stage (bucket_sort.hip.h, FUSE == 3): one-call form, on the context's guesses (the
   // general form again, no irregular row, no row longer than the windows allow for), B the three-stage side, the A
   // rows -- fully sorted -- sparse enough for a bucket's window to stay in a block's registers.
-  const bool general_join = onesweep && !ctx->no_bucket_join && ctx->fuse_a && speculated && ctx->last_no_irr &&
-                            ctx->fuse_cap > 0 && nb >= na && sort_is_local(ctx, nb) && ctx->spec_fuse_len_ok &&
-                            ctx->last_span > 0 &&
+  const bool general_join = onesweep && ctx->plan.fuse_a && speculated && ctx->guess.last_no_irr &&
+                            ctx->plan.fuse_cap > 0 && nb >= na && sort_is_local(ctx, nb) && ctx->guess.spec_fuse_len_ok &&
+                            ctx->guess.last_span > 0 &&
                             // (a window = the A rows within the bucket's 65536 keys + the longest rows of either side: the
                             // previous plan's maxima, like the guess they validate)
                             (double)na * ((double)(1u << (sort_local_bits(ctx, nb) ? sort_local_bits(ctx, nb) : 16)) +
                                           (double)ctx->h_meta->len_max_a + (double)ctx->h_meta->len_max_b) /
-                                    (double)ctx->last_span <= 0.5 * (double)BJ_WCAP;
+                                    (double)ctx->guess.last_span <= 0.5 * (double)BJ_WCAP;
   // the smaller side's chain (linearize + sort) beside the larger side's when it is small (not in the form above:
   // B's last stage reads the sorted A)
-  SideChain sc(ctx, st, (onesweep && !general_join) ? (na < nb ? na : nb) : 0, na < nb ? nb : na);
+  SideChain sc(ctx, st, (onesweep && !general_join) ? (na < nb ? na : nb) : 0);
   const bool a_small = na < nb;
   hipStream_t st_a = a_small ? sc.stream() : st, st_b = a_small ? st : sc.stream();
   const bool kg_a = keygen_g && !big_side, kg_b = keygen_g && big_side;
@@ -1630,10 +1693,10 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
                          is_b ? gbase_b : gbase_a);
       GIQL_TRY(post_launch("digit offsets (span histogram, general form)"));
     } else if (is_b) {
-      GIQL_TRY(run_linearize(ctx, st_b, *b, n_chrom, lb, sbb.key[0], sbb.end[0], ctx->irr_b_list, 1, 0,
+      GIQL_TRY(run_linearize(ctx, st_b, *b, n_chrom, lb, sbb.key[0], sbb.end[0], ctx->plan.irr_b_list, 1, 0,
                              hist_b, gbase_b));
     } else {
-      GIQL_TRY(run_linearize(ctx, st_a, *a, n_chrom, lb, sa.key[0], sa.end[0], ctx->irr_a_list, 0, 0,
+      GIQL_TRY(run_linearize(ctx, st_a, *a, n_chrom, lb, sa.key[0], sa.end[0], ctx->plan.irr_a_list, 0, 0,
                              hist_a, gbase_a));
     }
   }
@@ -1651,9 +1714,9 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
       fg.dev.qwin = ctx->bucket_qwin;
       fg.dev.lo_out = fg.dev.hi_out = nullptr;
       fg.dev.lo_off = 1;  // class 2: b.start in (a.start, a.end)
-      fg.dev.row_q = ctx->fuse_a;
-      fg.dev.row_s = ctx->fuse_b;
-      fg.dev.cap = ctx->fuse_cap;
+      fg.dev.row_q = ctx->plan.fuse_a;
+      fg.dev.row_s = ctx->plan.fuse_b;
+      fg.dev.cap = ctx->plan.fuse_cap;
       fg.dev.cursor = reinterpret_cast<unsigned long long*>(&ctx->d_meta->n_out);  // zeroed by the span pass
       fg.nq_total = (u32)na;
       fg.irr_q = irr_a;
@@ -1669,16 +1732,16 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
     GIQL_TRY(run_sort(ctx, st, sa, (u32)na, tile_hist, bsums));
     GIQL_TRY(run_sort(ctx, st, sbb, (u32)nb, tile_hist, bsums));
   }
-  if (ctx->bucket_join) {
+  if (ctx->call.bucket_join) {
     // the pairs are out already, counted in DevMeta::n_out
     GIQL_TRY(read_meta(ctx, st));
-    ctx->n_c1 = 0;
-    ctx->n_reg = ctx->h_meta->n_out;
-    ctx->fuse_done = ctx->h_meta->irr_a + ctx->h_meta->irr_b == 0 && ctx->n_reg <= ctx->fuse_cap;
-    ctx->stats.phase_bytes[GIQL_PH_SORT_LOCAL] += (int64_t)8 * (int64_t)ctx->n_reg;  // the pairs
+    ctx->plan.n_c1 = 0;
+    ctx->plan.n_reg = ctx->h_meta->n_out;
+    ctx->plan.fuse_done = ctx->h_meta->irr_a + ctx->h_meta->irr_b == 0 && ctx->plan.n_reg <= ctx->plan.fuse_cap;
+    ctx->stats.phase_bytes[GIQL_PH_SORT_LOCAL] += (int64_t)8 * (int64_t)ctx->plan.n_reg;  // the pairs
   } else {
   // class 1 (count + the scan of its block totals) runs beside class 2 when both sides are small
-  SideChain sc1(ctx, st, onesweep ? (na < nb ? na : nb) : 0, na < nb ? nb : na, 2);
+  SideChain sc1(ctx, st, onesweep ? (na < nb ? na : nb) : 0);
   hipStream_t st1 = sc1.stream();
   {
     Phase ph(ctx, st, GIQL_PH_COUNT, 4);
@@ -1719,8 +1782,8 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
   GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, cnt2, na, S.off2, bsums, S.off2 + na, &ctx->d_meta->n_out));
   GIQL_TRY(sc1.join());
   GIQL_TRY(read_meta(ctx, st));
-  ctx->n_c1 = ctx->h_meta->n_out_c1;
-  ctx->n_reg = ctx->h_meta->n_out + ctx->n_c1;
+  ctx->plan.n_c1 = ctx->h_meta->n_out_c1;
+  ctx->plan.n_reg = ctx->h_meta->n_out + ctx->plan.n_c1;
   }
   }
   if (onesweep) {
@@ -1733,66 +1796,63 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
     // range starts above 0); such a row was keyed as if regular, and never listed
     const bool keygen_wrong = (keygen_g && (big_side ? ctx->h_meta->len_min_b : ctx->h_meta->len_min_a) <= 0) ||
                               (keygen_q && (big_side ? ctx->h_meta->len_min_a : ctx->h_meta->len_min_b) <= 0);
-    if (keygen_wrong) ctx->last_no_irr = false;
+    if (keygen_wrong) ctx->guess.last_no_irr = false;
     // the fused count's windows allow for query rows up to BS_FUSE_WCAP long (the query side of the form just decided)
     const int q_len_now = form == 1 ? ctx->h_meta->len_max_a : ctx->h_meta->len_max_b;
     const bool fuse_len_ok_now = form != 0 ? q_len_now <= (int)BS_FUSE_WCAP
                                            : (ctx->h_meta->len_max_a <= (int)BS_FUSE_WCAP &&
                                               ctx->h_meta->len_max_b <= (int)BS_FUSE_WCAP);  // (general form: both sides' rows)
-    const bool fuse_wrong = ctx->count_fused && !fuse_len_ok_now;
-    ctx->spec_fuse_len_ok = fuse_len_ok_now;
+    const bool fuse_wrong = ctx->call.count_fused && !fuse_len_ok_now;
+    ctx->guess.spec_fuse_len_ok = fuse_len_ok_now;
     // a side taken as sorted must be: an out-of-order row was left where it was
-    const bool sorted_wrong = (ctx->used_sorted[0] && ctx->h_meta->unsorted_a != 0) ||
-                              (ctx->used_sorted[1] && ctx->h_meta->unsorted_b != 0);
-    ctx->spec_sorted[0] = ctx->h_meta->unsorted_a == 0;
-    ctx->spec_sorted[1] = ctx->h_meta->unsorted_b == 0;
+    const bool sorted_wrong = (ctx->call.used_sorted[0] && ctx->h_meta->unsorted_a != 0) ||
+                              (ctx->call.used_sorted[1] && ctx->h_meta->unsorted_b != 0);
+    ctx->guess.spec_sorted[0] = ctx->h_meta->unsorted_a == 0;
+    ctx->guess.spec_sorted[1] = ctx->h_meta->unsorted_b == 0;
     // a join in the bucket stage that did not stand (the pairs did not fit the caller's buffers, or a guess failed)
     // left no plan arrays for the ordinary fill: plan again, unspeculated -- which never takes that form
-    const bool join_wrong = ctx->bucket_join && !ctx->fuse_done;
-    if (join_wrong && getenv("GIQL_HIP_DEBUG_JOIN"))
-      fprintf(stderr, "[giql_hip] join in the bucket stage did not stand: %llu pairs, capacity %llu, irregular %u + %u\n",
-              (unsigned long long)ctx->n_reg, (unsigned long long)ctx->fuse_cap, ctx->h_meta->irr_a, ctx->h_meta->irr_b);
+    const bool join_wrong = ctx->call.bucket_join && !ctx->plan.fuse_done;
     if (speculated && (form != S.uniform || len != uni_len || (want_hist && !aligned_now) || coarse_wrong || keygen_wrong || fuse_wrong || sorted_wrong || join_wrong)) {
-      ctx->spec_valid = false;  // wrong guess: plan again from the numbers just read
-      ctx->spec_misses++;
-      ctx->fuse_done = false;
-      return inner_plan_core(ctx, a, b, n_chrom, stream, n_pairs);
+      ctx->guess.spec_valid = false;  // wrong guess: plan again from the numbers just read
+      ctx->guess.spec_misses++;
+      ctx->plan.fuse_done = false;
+      return GIQL_STATUS_GUESS_MISSED;
     }
-    ctx->spec_valid = true;
-    ctx->spec_form = form;
-    ctx->spec_len = len;
+    ctx->guess.spec_valid = true;
+    ctx->guess.spec_form = form;
+    ctx->guess.spec_len = len;
     // the layout is probed only when the span histogram ran; a plan that skipped it for a
     // form mismatch leaves the last answer (a later form change re-plans unspeculated anyway)
-    if (want_hist) ctx->spec_aligned = aligned_now;
+    if (want_hist) ctx->guess.spec_aligned = aligned_now;
   }
   ctx->stats.n_irregular_a = ctx->h_meta->irr_a;
   ctx->stats.n_irregular_b = ctx->h_meta->irr_b;
   ctx->stats.span = (int64_t)ctx->h_meta->total_span;
-  ctx->last_span = ctx->h_meta->total_span;
-  ctx->last_no_irr = ctx->h_meta->irr_a + ctx->h_meta->irr_b == 0;
+  ctx->guess.last_span = ctx->h_meta->total_span;
+  ctx->guess.last_no_irr = ctx->h_meta->irr_a + ctx->h_meta->irr_b == 0;
 
   if (ctx->h_meta->irr_a + ctx->h_meta->irr_b > 0) {
     {
       Phase ph(ctx, st, GIQL_PH_IRREGULAR);
       hipLaunchKernelGGL(k_irr_count, dim3(cdiv(nq, 256)), dim3(256), 0, st, view_of(*a), view_of(*b),
-                         ctx->irr_a_list, ctx->irr_b_list, ctx->d_meta, irr_cnt);
+                         ctx->plan.irr_a_list, ctx->plan.irr_b_list, ctx->d_meta, irr_cnt);
       GIQL_TRY(post_launch("irregular count"));
     }
-    GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_IRREGULAR, irr_cnt, nq, ctx->irr_off, bsums,
-                           ctx->irr_off + nq));
-    HIP_TRY(hipMemcpyAsync(&ctx->d_meta->n_out_irr, ctx->irr_off + nq, sizeof(u64),
+    GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_IRREGULAR, irr_cnt, nq, ctx->plan.irr_off, bsums,
+                           ctx->plan.irr_off + nq));
+    HIP_TRY(hipMemcpyAsync(&ctx->d_meta->n_out_irr, ctx->plan.irr_off + nq, sizeof(u64),
                            hipMemcpyDeviceToDevice, st));
     GIQL_TRY(read_meta(ctx, st));
-    ctx->n_irr = ctx->h_meta->n_out_irr;
+    ctx->plan.n_irr = ctx->h_meta->n_out_irr;
   }
   collect_spans(ctx);
   // which form ran: 0 general, 1 B uniform, 2 A uniform; bit 4: the fixed-length side was sorted
   // from its raw columns (histogram in the span pass, no linearize pass)
   ctx->stats.reserved = S.uniform | ((keygen || keygen_g) ? 0x10 : 0);
-  ctx->stats.n_out = (int64_t)(ctx->n_reg + ctx->n_irr);
-  *n_pairs = (int64_t)(ctx->n_reg + ctx->n_irr);
-  ctx->planned = true;
-  ctx->plan_is_join = ctx->bucket_join;
+  ctx->stats.n_out = (int64_t)(ctx->plan.n_reg + ctx->plan.n_irr);
+  *n_pairs = (int64_t)(ctx->plan.n_reg + ctx->plan.n_irr);
+  ctx->plan.planned = true;
+  ctx->plan.plan_is_join = ctx->call.bucket_join;
   return GIQL_OK;
 }
 
@@ -1805,22 +1865,20 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
 static int giql_hip_inner_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b,
                                         int32_t n_chrom, void* stream, int64_t* n_pairs) {
   if (!ctx || !n_pairs) return set_err(GIQL_ERR_INVALID, "ctx/n_pairs is NULL");
-  GIQL_TRY(check_side(a, "a"));
-  GIQL_TRY(check_side(b, "b"));
-  if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
-  const bool swap = !ctx->no_swap && a->n > b->n;
-  ctx->swapped = swap;
+  GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
+  const bool swap = a->n > b->n;
+  ctx->plan.swapped = swap;
   if (!swap) return inner_plan_core(ctx, a, b, n_chrom, stream, n_pairs);
   // The offered output buffers follow the sides for the duration of THIS attempt only: with_order_fallback
-  // may run this function again (a resort, a look-back timeout), and an exchange left in place would then
+  // may run this function again (a missed guess, a resort, a look-back timeout), and an exchange left in place would then
   // be undone by the second one -- the retry's early fill writing B ids into row_a.
-  int32_t* const fa = ctx->fuse_a;
-  int32_t* const fb = ctx->fuse_b;
-  ctx->fuse_a = fb;
-  ctx->fuse_b = fa;
+  int32_t* const fa = ctx->plan.fuse_a;
+  int32_t* const fb = ctx->plan.fuse_b;
+  ctx->plan.fuse_a = fb;
+  ctx->plan.fuse_b = fa;
   const int rc = inner_plan_core(ctx, b, a, n_chrom, stream, n_pairs);
-  ctx->fuse_a = fa;
-  ctx->fuse_b = fb;
+  ctx->plan.fuse_a = fa;
+  ctx->plan.fuse_b = fb;
   // stats in the caller's labels
   giql_hip_stats& stt = ctx->stats;
   const int64_t tn = stt.n_a;
@@ -1842,10 +1900,10 @@ int giql_hip_inner_plan_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_si
 int giql_hip_inner_fill_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, int64_t capacity,
                             void* stream) {
   if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
-  if (!ctx->planned) return set_err(GIQL_ERR_STATE, "inner_fill without a successful inner_plan");
-  const u64 total = ctx->n_reg + ctx->n_irr;
+  if (!ctx->plan.planned) return set_err(GIQL_ERR_STATE, "inner_fill without a successful inner_plan");
+  const u64 total = ctx->plan.n_reg + ctx->plan.n_irr;
   if (total == 0) return GIQL_OK;
-  if (ctx->plan_is_join)
+  if (ctx->plan.plan_is_join)
     return set_err(GIQL_ERR_STATE, "the last giql_hip_inner_join_dev wrote its pairs itself and kept no plan: "
                                    "call giql_hip_inner_plan_dev first");
   if (!row_a || !row_b) return set_err(GIQL_ERR_INVALID, "row_a/row_b is NULL");
@@ -1854,20 +1912,20 @@ int giql_hip_inner_fill_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, i
                    (unsigned long long)total);
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  if (ctx->swapped) {  // planned with the sides exchanged: the plan's "A" rows are the caller's B rows
+  if (ctx->plan.swapped) {  // planned with the sides exchanged: the plan's "A" rows are the caller's B rows
     int32_t* t = row_a;
     row_a = row_b;
     row_b = t;
   }
-  const u32 nq = ctx->n_a + ctx->n_b;
-  InnerState& S = ctx->inner;
+  const u32 nq = ctx->plan.n_a + ctx->plan.n_b;
+  InnerState& S = ctx->plan.inner;
   const u32* irr_a = &ctx->d_meta->irr_a;
   const u32* irr_b = &ctx->d_meta->irr_b;
-  const u64 p1 = ctx->n_c1, p2 = ctx->n_reg - ctx->n_c1;
+  const u64 p1 = ctx->plan.n_c1, p2 = ctx->plan.n_reg - ctx->plan.n_c1;
   // who plays "query" in the range-fill: A rows (general class 2, or B uniform),
   // or B rows (A uniform)
   const bool q_is_a = S.uniform != 2;
-  const u32 nq2 = q_is_a ? ctx->n_a : ctx->n_b;
+  const u32 nq2 = q_is_a ? ctx->plan.n_a : ctx->plan.n_b;
   u32 nt2 = 0, nt1f = 0;
   const bool c1_fill = S.uniform == 0 && S.c1_fill && p1 > 0;
   if (p2 > 0 || c1_fill) {
@@ -1877,21 +1935,13 @@ int giql_hip_inner_fill_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, i
     nt2 = (u32)nt2_64;
     nt1f = (u32)nt1_64;
     const size_t part_need = (size_t)nt2 + 2 + (c1_fill ? (size_t)nt1f + 2 : 0);
-    if (part_need > ctx->part_cap) {
-      HIP_TRY(hipStreamSynchronize(st));
-      if (ctx->part) HIP_TRY(hipFree(ctx->part));
-      ctx->part = nullptr;
-      ctx->part_cap = 0;
-      const size_t want = part_need + part_need / 4;
-      HIP_TRY(hipMalloc((void**)&ctx->part, want * sizeof(u32)));
-      ctx->part_cap = want;
-    }
+    GIQL_TRY(grow_part(ctx, part_need, st));
     Phase ph(ctx, st, GIQL_PH_PARTITION);
     if (p2 > 0)
       hipLaunchKernelGGL(k_partition, dim3(cdiv((u64)nt2 + 1, 256)), dim3(256), 0, st, S.off2, nq2,
                          (u64)0, T2, nt2, ctx->part);
     if (c1_fill)  // class 1's tiles behind class 2's in the partition array
-      hipLaunchKernelGGL(k_partition, dim3(cdiv((u64)nt1f + 1, 256)), dim3(256), 0, st, S.off1, ctx->n_b,
+      hipLaunchKernelGGL(k_partition, dim3(cdiv((u64)nt1f + 1, 256)), dim3(256), 0, st, S.off1, ctx->plan.n_b,
                          (u64)0, T2, nt1f, ctx->part + nt2 + 2);
   }
   {
@@ -1899,14 +1949,14 @@ int giql_hip_inner_fill_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, i
     // class 1 -> outputs [0, p1): query = B row, matches = A rows
     if (c1_fill)
       hipLaunchKernelGGL((k_fill<FILL_ITEMS_C2>), dim3(nt1f), dim3(FILL_NT), 0, st, S.off1, S.lo1, S.sb.rid[0],
-                         ctx->n_b, S.sa.rid[0], ctx->part + nt2 + 2, (u64)0, p1, row_b, row_a);
+                         ctx->plan.n_b, S.sa.rid[0], ctx->part + nt2 + 2, (u64)0, p1, row_b, row_a);
     else if (p1 > 0 && S.c1_items == 2)
       hipLaunchKernelGGL(k_c1_emit<2>, dim3(S.nt1), dim3(C1_NT), 0, st, S.sb.key[0], S.sb.end[0],
-                         S.sb.rid[0], ctx->n_b, irr_b, S.sa.key[0], S.sa.rid[0], ctx->n_a, irr_a,
+                         S.sb.rid[0], ctx->plan.n_b, irr_b, S.sa.key[0], S.sa.rid[0], ctx->plan.n_a, irr_a,
                          S.wlo1, S.c1_base, (u64)0, row_b, row_a);
     else if (p1 > 0)
       hipLaunchKernelGGL(k_c1_emit<C1_ITEMS_MAX>, dim3(S.nt1), dim3(C1_NT), 0, st, S.sb.key[0], S.sb.end[0],
-                         S.sb.rid[0], ctx->n_b, irr_b, S.sa.key[0], S.sa.rid[0], ctx->n_a, irr_a,
+                         S.sb.rid[0], ctx->plan.n_b, irr_b, S.sa.key[0], S.sa.rid[0], ctx->plan.n_a, irr_a,
                          S.wlo1, S.c1_base, (u64)0, row_b, row_a);
     // range fill -> outputs [p1, p1 + p2)
     if (p2 > 0) {
@@ -1919,11 +1969,11 @@ int giql_hip_inner_fill_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, i
     }
     GIQL_TRY(post_launch("fill"));
   }
-  if (ctx->n_irr > 0) {
+  if (ctx->plan.n_irr > 0) {
     Phase ph(ctx, st, GIQL_PH_IRREGULAR);
-    hipLaunchKernelGGL(k_irr_fill, dim3(cdiv(nq, 256)), dim3(256), 0, st, view_of(ctx->side_a),
-                       view_of(ctx->side_b), ctx->irr_a_list, ctx->irr_b_list, ctx->d_meta,
-                       ctx->irr_off, row_a + ctx->n_reg, row_b + ctx->n_reg);
+    hipLaunchKernelGGL(k_irr_fill, dim3(cdiv(nq, 256)), dim3(256), 0, st, view_of(ctx->plan.side_a),
+                       view_of(ctx->plan.side_b), ctx->plan.irr_a_list, ctx->plan.irr_b_list, ctx->d_meta,
+                       ctx->plan.irr_off, row_a + ctx->plan.n_reg, row_b + ctx->plan.n_reg);
     GIQL_TRY(post_launch("irregular fill"));
   }
   return GIQL_OK;
@@ -1945,25 +1995,16 @@ int giql_hip_inner_join_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_si
   {  // the merge-path partition array must exist before the plan can launch the fill
     constexpr u32 T2 = FILL_NT * FILL_ITEMS_C2;
     const u64 nt_cap = ((u64)capacity + T2 - 1) / T2;
-    const size_t part_need = (size_t)nt_cap + 2;
-    if (nt_cap <= 0x7FFFFFF0ull && part_need > ctx->part_cap) {
-      HIP_TRY(hipStreamSynchronize(st));
-      if (ctx->part) HIP_TRY(hipFree(ctx->part));
-      ctx->part = nullptr;
-      ctx->part_cap = 0;
-      const size_t want = part_need + part_need / 4;
-      HIP_TRY(hipMalloc((void**)&ctx->part, want * sizeof(u32)));
-      ctx->part_cap = want;
-    }
+    if (nt_cap <= 0x7FFFFFF0ull) GIQL_TRY(grow_part(ctx, (size_t)nt_cap + 2, st));
   }
-  ctx->fuse_a = row_a;
-  ctx->fuse_b = row_b;
-  ctx->fuse_cap = (u64)capacity;
+  ctx->plan.fuse_a = row_a;
+  ctx->plan.fuse_b = row_b;
+  ctx->plan.fuse_cap = (u64)capacity;
   const int rc = giql_hip_inner_plan_dev(ctx, a, b, n_chrom, stream, n_pairs);
-  ctx->fuse_a = ctx->fuse_b = nullptr;
-  ctx->fuse_cap = 0;
+  ctx->plan.fuse_a = ctx->plan.fuse_b = nullptr;
+  ctx->plan.fuse_cap = 0;
   if (rc != GIQL_OK) return rc;
-  if (ctx->fuse_done) return GIQL_OK;
+  if (ctx->plan.fuse_done) return GIQL_OK;
   if (*n_pairs > capacity)
     return set_err(GIQL_ERR_CAPACITY, "capacity %lld < %lld pairs", (long long)capacity, (long long)*n_pairs);
   return giql_hip_inner_fill_dev(ctx, row_a, row_b, capacity, stream);
@@ -2020,12 +2061,10 @@ int giql_hip_index_create_dev(giql_hip_ctx* ctx, const giql_side* side, int32_t 
   if (n_chrom < 1 || n_chrom > MM_HIST_CHROMS)
     return set_err(GIQL_ERR_STATE, "a table index takes 1..%d chromosomes (the 2^24-aligned axis), got %d", MM_HIST_CHROMS, n_chrom);
   if (side->n < 1 || (size_t)side->n > OS_MAX_ROWS) return set_err(GIQL_ERR_STATE, "a table index takes 1..2^30-1 rows");
-  if (ctx->classic_sort || ctx->os_variant != 0 || !ctx->bucket_bnd)
+  if (ctx->sw.classic_sort || ctx->sw.os_variant != 0 || !ctx->bucket_bnd)
     return set_err(GIQL_ERR_STATE, "this context cannot run the three-stage sort (GIQL_HIP_SORT / GIQL_HIP_OS_VARIANT)");
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
-  ctx->planned = false;
-  reset_stats(ctx);
   const size_t n = (size_t)side->n;
   LinBufs lb;
   SortBufs scratch;  // buffer 1 of the sort (buffer 0 = the index's own arrays)
@@ -2048,28 +2087,23 @@ int giql_hip_index_create_dev(giql_hip_ctx* ctx, const giql_side* side, int32_t 
     zero_end = c.off;
     return c.off;
   };
-  GIQL_TRY(ensure_arena(ctx, carve(nullptr), st));
-  carve(ctx->arena);
+  GIQL_TRY(claim_arena(ctx, st, carve));
   giql_hip_index* idx = new (std::nothrow) giql_hip_index();
   if (!idx) return set_err(GIQL_ERR_NOMEM, "out of host memory");
   struct Fail {  // released on every early way out
     giql_hip_index* p;
-    giql_hip_ctx* c;
     ~Fail() {
-      c->force_local = 0;
-      c->index_bits = 16;
-      c->prezeroed = false;
       if (p) giql_hip_index_destroy(p);
     }
-  } guard{idx, ctx};
+  } guard{idx};
+  PrezeroGuard prezero_guard{ctx};
   idx->device = ctx->device;
   idx->n = (u32)n;
   idx->n_chrom = n_chrom;
   HIP_TRY(hipMemsetAsync(ctx->arena + zero_off, 0, zero_end - zero_off, st));
-  ctx->prezeroed = true;
-  ctx->force_local = 1;
-  ctx->index_bits = 15;  // (not 16: the span pass counts the bits 8-15 digit too -- the density is not known yet)
-  ctx->span_hist_dirty[0] = ctx->span_hist_dirty[1] = nullptr;
+  ctx->call.prezeroed = true;
+  ForceLocal force_local{ctx, 1};
+  ctx->call.index_bits = 15;  // (not 16: the span pass counts the bits 8-15 digit too -- the density is not known yet)
   giql_side none = *side;
   none.n = 0;
   none.chrom = none.start = none.end = nullptr;
@@ -2084,12 +2118,12 @@ int giql_hip_index_create_dev(giql_hip_ctx* ctx, const giql_side* side, int32_t 
   if (m.len_max_b > (int)BS_FUSE_WCAP)
     return set_err(GIQL_ERR_STATE, "a row of %d positions is longer than the bucket stage's windows allow (%u)", m.len_max_b, BS_FUSE_WCAP);
   const double per_bucket = (double)n * 65536.0 / (double)(m.total_span ? m.total_span : 1);
-  idx->wbits = ctx->force_bits ? ctx->force_bits : density_bits(ctx, per_bucket);
+  idx->wbits = ctx->sw.force_bits ? ctx->sw.force_bits : density_bits(ctx, per_bucket);
   if (idx->wbits == 0)
     return set_err(GIQL_ERR_STATE, "%.0f rows per 65,536 positions: too dense for the in-LDS bucket stage (at most %.0f per %d)",
-                   per_bucket, ctx->local_max_bucket_rows, 1 << BS_MIN_WBITS);
-  ctx->index_bits = idx->wbits;
-  idx->general = ctx->no_uniform || m.len_min_b != m.len_max_b;
+                   per_bucket, ctx->sw.local_max_bucket_rows, 1 << BS_MIN_WBITS);
+  ctx->call.index_bits = idx->wbits;
+  idx->general = ctx->sw.no_uniform || m.len_min_b != m.len_max_b;
   idx->uni_len = idx->general ? 0 : m.len_max_b;
   idx->len_max = m.len_max_b;
   idx->span = m.total_span;
@@ -2150,13 +2184,12 @@ int giql_hip_inner_join_indexed_dev(giql_hip_ctx* ctx, const giql_hip_index* idx
   if (idx->device != ctx->device) return set_err(GIQL_ERR_INVALID, "the index lives on device %d, the context on %d", idx->device, ctx->device);
   if (capacity < 0 || (capacity > 0 && (!row_a || !row_idx))) return set_err(GIQL_ERR_INVALID, "bad output buffers");
   *n_pairs = 0;
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
-  ctx->planned = false;
-  ctx->fuse_done = false;
-  reset_stats(ctx);
+  ctx->plan.fuse_done = false;
   ctx->stats.n_a = a->n;
   ctx->stats.n_b = idx->n;
+  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   if (a->n == 0) return GIQL_OK;
   const size_t na = (size_t)a->n, nb = (size_t)idx->n;
   if (na > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
@@ -2179,14 +2212,10 @@ int giql_hip_inner_join_indexed_dev(giql_hip_ctx* ctx, const giql_hip_index* idx
     zero_end = c.off;
     return c.off;
   };
-  GIQL_TRY(ensure_arena(ctx, carve(nullptr), st));
-  carve(ctx->arena);
-  struct Guard {
-    giql_hip_ctx* c;
-    ~Guard() { c->prezeroed = false; }
-  } guard{ctx};
+  GIQL_TRY(claim_arena(ctx, st, carve));
+  PrezeroGuard prezero_guard{ctx};
   HIP_TRY(hipMemsetAsync(ctx->arena + zero_off, 0, zero_end - zero_off, st));
-  ctx->prezeroed = true;
+  ctx->call.prezeroed = true;
   const u32* first = idx->small + 1024;
   u32* const dead = flags;           // rows of a that cannot match (sorted last, skipped by the windows)
   u32* const irregular = flags + 1;
@@ -2209,10 +2238,10 @@ int giql_hip_inner_join_indexed_dev(giql_hip_ctx* ctx, const giql_hip_index* idx
   // (narrower buckets: grouped by key >> 8, three passes)
   const int q_skip = idx->general ? 0 : (idx->wbits == 16 ? 2 : 1);
   const u32 q_mask = q_skip == 2 ? 0xFFFF0000u : (q_skip == 1 ? 0xFFFFFF00u : 0xFFFFFFFFu);
-  ctx->force_local = -1;  // a's own sort: global passes only (its bucket stage would reuse the context's boundary arrays)
-  const int rc_sort = run_sort_onesweep(ctx, st, sa, (u32)na, gbase, status, false, nullptr, nullptr, q_skip, nullptr, false);
-  ctx->force_local = 0;
-  GIQL_TRY(rc_sort);
+  {
+    ForceLocal global_only{ctx, -1};  // a's own sort: global passes only (its bucket stage would reuse the context's boundary arrays)
+    GIQL_TRY(run_sort_onesweep(ctx, st, sa, (u32)na, gbase, status, false, nullptr, nullptr, q_skip, nullptr, false));
+  }
   FuseCount fc;
   fc.join = true;
   fc.general = idx->general;
@@ -2238,7 +2267,7 @@ int giql_hip_inner_join_indexed_dev(giql_hip_ctx* ctx, const giql_hip_index* idx
   sb.key[0] = idx->key;
   sb.rid[0] = idx->rid;
   sb.end[0] = idx->end;
-  ctx->last_sort_local = true;
+  ctx->call.last_sort_local = true;
   launch_bucket_stage_fused(ctx, st, sb, (u32)nb, idx->small, fc, idx->wbits);
   GIQL_TRY(post_launch("bucket stage (index)"));
   u32 h_flags[4] = {0, 0, 0, 0};
@@ -2274,18 +2303,14 @@ struct OsScratch {
 // ONE memset for everything two sides' histograms and sort passes need at zero, instead of one per histogram and per
 // sort (four launches of ~5 us on a path of ~60): `first` is carved right before `second`, so the range runs from
 // first's histograms to the end of second's four passes of status words.  Only for calls that sort each side ONCE (a
-// second sort through the same status words must zero them again: ctx->prezeroed makes the helpers skip theirs).
-struct PrezeroGuard {
-  giql_hip_ctx* c;
-  ~PrezeroGuard() { c->prezeroed = false; }
-};
+// second sort through the same status words must zero them again: ctx->call.prezeroed makes the helpers skip theirs).
 static int prezero_row_scratch(giql_hip_ctx* ctx, hipStream_t st, const OsScratch& first, const OsScratch& second,
                                size_t n_second) {
   char* const lo = reinterpret_cast<char*>(first.hist);
   char* const hi = reinterpret_cast<char*>(second.status + 4 * os_pass_stride(ctx, n_second));
   if (!first.hist || hi <= lo) return GIQL_OK;
   HIP_TRY(hipMemsetAsync(lo, 0, (size_t)(hi - lo), st));
-  ctx->prezeroed = true;
+  ctx->call.prezeroed = true;
   return GIQL_OK;
 }
 
@@ -2302,16 +2327,9 @@ static int giql_hip_semi_anti_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
                            int32_t n_chrom, int anti, int32_t* rows_out, int64_t* n_out,
                            void* stream) {
   if (!ctx || !n_out) return set_err(GIQL_ERR_INVALID, "ctx/n_out is NULL");
-  GIQL_TRY(check_side(a, "a"));
-  GIQL_TRY(check_side(b, "b"));
-  if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
   hipStream_t st = (hipStream_t)stream;
-  ctx->planned = false;
-  ctx->prezeroed = false;  // (a repeated call -- a guess that missed -- starts over: the caller's frame may still hold its guard)
-  reset_stats(ctx);
-  ctx->stats.n_a = a->n;
-  ctx->stats.n_b = b->n;
+  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   *n_out = 0;
   if (a->n == 0) return GIQL_OK;
   if (!rows_out) return set_err(GIQL_ERR_INVALID, "rows_out is NULL");
@@ -2343,8 +2361,7 @@ static int giql_hip_semi_anti_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
     dummy_irr = c.take<u32>(16);
     return c.off;
   };
-  GIQL_TRY(ensure_arena(ctx, carve(nullptr), st));
-  carve(ctx->arena);
+  GIQL_TRY(claim_arena(ctx, st, carve));
   PrezeroGuard prezero_guard{ctx};
   GIQL_TRY(prezero_row_scratch(ctx, st, os_a, os, nb ? nb : 1));  // each side is sorted once, in either form
 
@@ -2355,7 +2372,7 @@ static int giql_hip_semi_anti_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
   const bool coarse_b = nb > 0 && uni_len > 0 && coarse_b_ok(ctx, nb);
   {
     // the query side's chain (linearize + sort) beside B's when it is small
-    SideChain sc(ctx, st, nb > 0 ? na : 0, nb);
+    SideChain sc(ctx, st, nb > 0 ? na : 0);
     GIQL_TRY(run_linearize(ctx, sc.stream(), *a, nch, lb, sa.key[0], sa.end[0], dummy_irr + 8, 0, 1, os_a.hist, os_a.gbase));
     GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sa, (u32)na, os_a.gbase, os_a.status, false, nullptr, nullptr,
                                /*skip_digits=*/row_skip(ctx, nb)));  // the query side's order only serves locality; every row keeps its real key here
@@ -2405,13 +2422,13 @@ static int giql_hip_semi_anti_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
   }
   GIQL_TRY(read_meta(ctx, st));
   if (nb > 0 && !row_form_settled(ctx, uni_len, speculated))  // B is not fixed-length after all
-    return giql_hip_semi_anti_dev_impl(ctx, a, b, n_chrom, anti, rows_out, n_out, stream);
+    return GIQL_STATUS_GUESS_MISSED;
   collect_spans(ctx);
   ctx->stats.reserved = (uni_len > 0 ? 1 : 0) | (coarse_b ? 0x10 : 0);  // form: fixed-length B or general; bit 4: B sorted coarsely (without its lowest digit)
   *n_out = (int64_t)ctx->h_meta->n_out;
   ctx->stats.n_out = *n_out;
   ctx->stats.span = (int64_t)ctx->h_meta->total_span;
-  ctx->last_span = ctx->h_meta->total_span;
+  ctx->guess.last_span = ctx->h_meta->total_span;
   return GIQL_OK;
 }
 
@@ -2424,16 +2441,9 @@ int giql_hip_semi_anti_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
 static int giql_hip_count_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, int32_t n_chrom,
                        int64_t* counts_out, void* stream) {
   if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
-  GIQL_TRY(check_side(a, "a"));
-  GIQL_TRY(check_side(b, "b"));
-  if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
   hipStream_t st = (hipStream_t)stream;
-  ctx->planned = false;
-  ctx->prezeroed = false;  // (a repeated call -- a guess that missed -- starts over: the caller's frame may still hold its guard)
-  reset_stats(ctx);
-  ctx->stats.n_a = a->n;
-  ctx->stats.n_b = b->n;
+  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   if (a->n == 0) return GIQL_OK;
   if (!counts_out) return set_err(GIQL_ERR_INVALID, "counts_out is NULL");
   const size_t na = (size_t)a->n, nb = (size_t)b->n;
@@ -2462,8 +2472,7 @@ static int giql_hip_count_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const 
     irr_b_list = c.take<u32>(nb);
     return c.off;
   };
-  GIQL_TRY(ensure_arena(ctx, carve(nullptr), st));
-  carve(ctx->arena);
+  GIQL_TRY(claim_arena(ctx, st, carve));
 
   GIQL_TRY(run_spans(ctx, st, *a, *b, n_chrom, lb));
   i64 uni_len = 0;
@@ -2473,7 +2482,7 @@ static int giql_hip_count_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const 
   PrezeroGuard prezero_guard{ctx};
   if (uni_len > 0) GIQL_TRY(prezero_row_scratch(ctx, st, os_a, os, nb));  // (the general form sorts B twice through one set of status words)
   {
-  SideChain sc(ctx, st, na, nb);
+  SideChain sc(ctx, st, na);
   GIQL_TRY(run_linearize(ctx, sc.stream(), *a, n_chrom, lb, sa.key[0], sa.end[0], irr_a_list, 0, 0, os_a.hist,
                          os_a.gbase));
   GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sa, (u32)na, os_a.gbase, os_a.status, false, nullptr, nullptr,
@@ -2501,7 +2510,7 @@ static int giql_hip_count_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const 
   }
   GIQL_TRY(read_meta(ctx, st));
   if (!row_form_settled(ctx, uni_len, speculated))  // B is not fixed-length after all
-    return giql_hip_count_dev_impl(ctx, a, b, n_chrom, counts_out, stream);
+    return GIQL_STATUS_GUESS_MISSED;
   ctx->stats.reserved = (uni_len > 0 ? 1 : 0) | (coarse_b ? 0x10 : 0);
   ctx->stats.n_irregular_a = ctx->h_meta->irr_a;
   ctx->stats.n_irregular_b = ctx->h_meta->irr_b;
@@ -2515,7 +2524,7 @@ static int giql_hip_count_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const 
   collect_spans(ctx);
   ctx->stats.n_out = a->n;
   ctx->stats.span = (int64_t)ctx->h_meta->total_span;
-  ctx->last_span = ctx->h_meta->total_span;
+  ctx->guess.last_span = ctx->h_meta->total_span;
   return GIQL_OK;
 }
 
@@ -2530,16 +2539,9 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
                          int is_signed, int64_t max_distance, int32_t* idx_b_out, int64_t* dist_out,
                          void* stream, int32_t* out32 = nullptr) {
   if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
-  GIQL_TRY(check_side(a, "a"));
-  GIQL_TRY(check_side(b, "b"));
-  if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
   hipStream_t st = (hipStream_t)stream;
-  ctx->planned = false;
-  ctx->prezeroed = false;  // (a repeated call -- a guess that missed -- starts over: the caller's frame may still hold its guard)
-  reset_stats(ctx);
-  ctx->stats.n_a = a->n;
-  ctx->stats.n_b = b->n;
+  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   if (a->n == 0) return GIQL_OK;
   if (!out32 && (!idx_b_out || !dist_out)) return set_err(GIQL_ERR_INVALID, "idx_b_out/dist_out is NULL");
   if (out32 && ((uintptr_t)out32 & 7)) return set_err(GIQL_ERR_INVALID, "idx_dist_out must be 8-byte aligned");
@@ -2576,10 +2578,9 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
     dummy_irr = c.take<u32>(16);
     return c.off;
   };
-  GIQL_TRY(ensure_arena(ctx, carve(nullptr), st));
-  carve(ctx->arena);
+  GIQL_TRY(claim_arena(ctx, st, carve));
 
-  const bool two_sorts = ctx->nearest_two_sorts;
+  const bool two_sorts = ctx->guess.nearest_two_sorts;
   PrezeroGuard prezero_guard{ctx};
   if (!two_sorts) GIQL_TRY(prezero_row_scratch(ctx, st, os_a, os, nb));  // (the two-sort plan reuses B's status words)
   // Both sides sorted from their raw columns (round 3): with every chromosome base a multiple of 2^24 the span pass
@@ -2588,10 +2589,10 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
   // ~2 x 22 more in the span pass and the first sort pass).  Every NEAREST row keeps its real key, zero-length rows
   // included, so the only guess is the layout: taken when the previous call's data took it, validated at the
   // read-back; a first call probes it (digits counted for B only) and sorts the ordinary way.
-  const bool hist_ok = !two_sorts && ctx->prezeroed && !ctx->no_span_hist && ctx->os_variant == 0 &&
+  const bool hist_ok = !two_sorts && ctx->call.prezeroed && !ctx->sw.no_span_hist && ctx->sw.os_variant == 0 &&
                        n_chrom <= MM_HIST_CHROMS && !sort_is_local(ctx, na) && !sort_is_local(ctx, nb);
-  const bool keygen = hist_ok && ctx->nearest_aligned == 1;
-  const bool probe = hist_ok && ctx->nearest_aligned == -1;
+  const bool keygen = hist_ok && ctx->guess.nearest_aligned == 1;
+  const bool probe = hist_ok && ctx->guess.nearest_aligned == -1;
   if (keygen) lb.hist_partial2 = os_a.hist;
   if (!(keygen || probe)) lb.abase = nullptr;  // (run_spans: no digit counting)
   GIQL_TRY(run_spans(ctx, st, *a, *b, n_chrom, lb, (keygen || probe) ? 1 : -1, os.hist));
@@ -2603,7 +2604,7 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
                        os.gbase, os_a.gbase);
     GIQL_TRY(post_launch("digit offsets (span histogram, NEAREST)"));
   }
-  SideChain sc(ctx, st, na, nb);
+  SideChain sc(ctx, st, na);
   if (!keygen)
     GIQL_TRY(run_linearize(ctx, sc.stream(), *a, n_chrom, lb, sa.key[0], sa.end[0], dummy_irr + 8, 0, 1, os_a.hist,
                            os_a.gbase));
@@ -2652,22 +2653,22 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
   GIQL_TRY(read_meta(ctx, st));
   if (keygen || probe) {
     const bool aligned_now = ctx->h_meta->aligned_ok != 0;
-    ctx->nearest_aligned = aligned_now ? 1 : 0;
+    ctx->guess.nearest_aligned = aligned_now ? 1 : 0;
     if (keygen && !aligned_now)  // the layout did not hold for this data: its keys were built on bases that overlap
-      return giql_hip_nearest_dev_impl(ctx, a, b, n_chrom, is_signed, max_distance, idx_b_out, dist_out, stream, out32);
+      return GIQL_STATUS_GUESS_MISSED;
   }
   if (ctx->h_meta->inverted_b) return set_err(GIQL_ERR_INVALID, "NEAREST: a target row has end < start");
   if (!two_sorts && ctx->h_meta->aux0 != 0) {
     // a long run of equal starts (pile-ups): this table wants the two-sort plan
-    ctx->nearest_two_sorts = true;
-    return giql_hip_nearest_dev_impl(ctx, a, b, n_chrom, is_signed, max_distance, idx_b_out, dist_out, stream, out32);
+    ctx->guess.nearest_two_sorts = true;
+    return GIQL_STATUS_GUESS_MISSED;
   }
   if (out32 && ctx->h_meta->aux1 != 0)
     return set_err(GIQL_ERR_INVALID, "NEAREST: a distance does not fit int32; use giql_hip_nearest_dev (int64 distances)");
   collect_spans(ctx);
   ctx->stats.n_out = a->n;
   ctx->stats.span = (int64_t)ctx->h_meta->total_span;
-  ctx->last_span = ctx->h_meta->total_span;
+  ctx->guess.last_span = ctx->h_meta->total_span;
   return GIQL_OK;
 }
 
@@ -2689,16 +2690,10 @@ static int giql_hip_nearest_k_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
                                        int32_t k, int is_signed, int64_t max_distance, int32_t* idx_b_out,
                                        int64_t* dist_out, void* stream) {
   if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
-  GIQL_TRY(check_side(a, "a"));
-  GIQL_TRY(check_side(b, "b"));
-  if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
   if (k < 1 || k > NEAREST_K_MAX) return set_err(GIQL_ERR_INVALID, "k=%d outside [1, %d]", k, NEAREST_K_MAX);
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
   hipStream_t st = (hipStream_t)stream;
-  ctx->planned = false;
-  reset_stats(ctx);
-  ctx->stats.n_a = a->n;
-  ctx->stats.n_b = b->n;
+  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   if (a->n == 0) return GIQL_OK;
   if (!idx_b_out || !dist_out) return set_err(GIQL_ERR_INVALID, "idx_b_out/dist_out is NULL");
   const size_t na = (size_t)a->n, nb = (size_t)b->n;
@@ -2729,15 +2724,14 @@ static int giql_hip_nearest_k_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
     dummy_irr = c.take<u32>(16);
     return c.off;
   };
-  GIQL_TRY(ensure_arena(ctx, carve(nullptr), st));
-  carve(ctx->arena);
+  GIQL_TRY(claim_arena(ctx, st, carve));
 
   GIQL_TRY(run_spans(ctx, st, *a, *b, n_chrom, lb));
   // Two sorted views of B from ONE linearize pass (it counts the digits of the starts and of the ends):
   //   by (start, end) and by (end, start).
   GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, sbb.key[0], sbb.end[0], dummy_irr, 1, 1, os.hist, os.gbase,
                          os.hist_e, os.gbase_e));
-  const bool two_sorts = ctx->nearest_two_sorts;
+  const bool two_sorts = ctx->guess.nearest_two_sorts;
   if (two_sorts) {
     // tables with long runs of equal starts or ends: stable two-key sorts -- (start, end) = by end, then stably by
     // start; (end, start) = that order stably re-sorted by end
@@ -2798,14 +2792,14 @@ static int giql_hip_nearest_k_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
   GIQL_TRY(read_meta(ctx, st));
   if (!two_sorts && ctx->h_meta->aux0 != 0) {
     // a long run of equal starts or ends (pile-ups): this table wants the two-key sorts
-    ctx->nearest_two_sorts = true;
-    return giql_hip_nearest_k_dev_impl(ctx, a, b, n_chrom, k, is_signed, max_distance, idx_b_out, dist_out, stream);
+    ctx->guess.nearest_two_sorts = true;
+    return GIQL_STATUS_GUESS_MISSED;
   }
   if (ctx->h_meta->inverted_b) return set_err(GIQL_ERR_INVALID, "NEAREST: a target row has end < start");
   collect_spans(ctx);
   ctx->stats.n_out = a->n * (int64_t)k;
   ctx->stats.span = (int64_t)ctx->h_meta->total_span;
-  ctx->last_span = ctx->h_meta->total_span;
+  ctx->guess.last_span = ctx->h_meta->total_span;
   return GIQL_OK;
 }
 
@@ -2854,8 +2848,7 @@ static int cluster_front(giql_hip_ctx* ctx, hipStream_t st, const giql_side* s, 
     cb.seg_end = want_heads && preds && preds->n > 0 ? c.take<u32>(n + 1) : nullptr;
     return c.off;
   };
-  GIQL_TRY(ensure_arena(ctx, carve(nullptr), st));
-  carve(ctx->arena);
+  GIQL_TRY(claim_arena(ctx, st, carve));
   giql_side none;
   memset(&none, 0, sizeof(none));
   GIQL_TRY(run_spans(ctx, st, *s, none, n_chrom, cb.lb));
@@ -2908,11 +2901,10 @@ static int cluster_status(giql_hip_ctx* ctx, hipStream_t st) {
 static int giql_hip_cluster_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom, int64_t distance,
                          int64_t* cluster_id_out, void* stream, const DevPreds* preds = nullptr) {
   GIQL_TRY(check_cluster_args(ctx, s, n_chrom));
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
-  ctx->planned = false;
-  reset_stats(ctx);
   ctx->stats.n_a = s->n;
+  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   if (s->n == 0) return GIQL_OK;
   if (!cluster_id_out) return set_err(GIQL_ERR_INVALID, "cluster_id_out is NULL");
   if (n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
@@ -3014,11 +3006,10 @@ static int giql_hip_merge_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int32_
                        const DevPreds* preds = nullptr) {
   GIQL_TRY(check_cluster_args(ctx, s, n_chrom));
   if (!n_out) return set_err(GIQL_ERR_INVALID, "n_out is NULL");
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
-  ctx->planned = false;
-  reset_stats(ctx);
   ctx->stats.n_a = s->n;
+  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   *n_out = 0;
   if (s->n == 0) return GIQL_OK;
   if (!out_chrom || !out_start || !out_end) return set_err(GIQL_ERR_INVALID, "output buffer is NULL");
@@ -3081,11 +3072,10 @@ static int giql_hip_group_rows_dev_impl(giql_hip_ctx* ctx, const giql_side* s, i
   GIQL_TRY(check_side(s, "s"));
   if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
   if ((size_t)s->n > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
-  ctx->planned = false;
-  reset_stats(ctx);
   ctx->stats.n_a = s->n;
+  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   *n_groups = 0;
   if (s->n == 0) return GIQL_OK;
   if (!group_of_row || !rep_row) return set_err(GIQL_ERR_INVALID, "output buffer is NULL");
@@ -3108,13 +3098,12 @@ static int giql_hip_group_rows_dev_impl(giql_hip_ctx* ctx, const giql_side* s, i
     dummy_irr = c.take<u32>(16);
     return c.off;
   };
-  GIQL_TRY(ensure_arena(ctx, carve(nullptr), st));
-  carve(ctx->arena);
+  GIQL_TRY(claim_arena(ctx, st, carve));
   giql_side raw = *s;  // identical RAW coordinates are what GROUP BY compares
   raw.start_off = raw.end_off = 0;
   giql_side none;
   memset(&none, 0, sizeof(none));
-  const bool two_sorts = ctx->nearest_two_sorts;
+  const bool two_sorts = ctx->guess.nearest_two_sorts;
   GIQL_TRY(run_spans(ctx, st, raw, none, n_chrom, lb));
   GIQL_TRY(run_linearize(ctx, st, raw, n_chrom, lb, sb.key[0], sb.end[0], dummy_irr, 0, 1, os.hist,
                          os.gbase, two_sorts ? os.hist_e : nullptr, two_sorts ? os.gbase_e : nullptr));
@@ -3150,8 +3139,8 @@ static int giql_hip_group_rows_dev_impl(giql_hip_ctx* ctx, const giql_side* s, i
   HIP_TRY(hipMemcpyAsync(&h_total, total, sizeof(u64), hipMemcpyDeviceToHost, st));
   GIQL_TRY(read_meta(ctx, st));
   if (!two_sorts && ctx->h_meta->aux0 != 0) {  // a long run of equal starts: two-sort plan
-    ctx->nearest_two_sorts = true;
-    return giql_hip_group_rows_dev_impl(ctx, s, n_chrom, group_of_row, rep_row, n_groups, stream);
+    ctx->guess.nearest_two_sorts = true;
+    return GIQL_STATUS_GUESS_MISSED;
   }
   collect_spans(ctx);
   *n_groups = (int64_t)h_total;
@@ -3171,9 +3160,8 @@ int giql_hip_segment_sum_dev(giql_hip_ctx* ctx, const int64_t* values, const int
   if (!ctx || n < 0 || n_groups < 0 || n_groups > 0x7FFFFFFFll) return set_err(GIQL_ERR_INVALID, "bad arguments");
   if ((n > 0 && (!values || !group_of_row)) || (n_groups > 0 && !sums))
     return set_err(GIQL_ERR_INVALID, "NULL buffer");
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
-  reset_stats(ctx);
   if (n_groups > 0) HIP_TRY(hipMemsetAsync(sums, 0, (size_t)n_groups * sizeof(int64_t), st));
   if (n == 0) return GIQL_OK;
   HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
@@ -3199,15 +3187,13 @@ int giql_hip_chrom_spans_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_s
   if (n_chrom <= 0) return set_err(GIQL_ERR_INVALID, "n_chrom <= 0");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  ctx->planned = false;
   LinBufs lb;
   auto carve = [&](char* base) {
     Carver c{base};
     common_sizes(c, n_chrom, lb);
     return c.off;
   };
-  GIQL_TRY(ensure_arena(ctx, carve(nullptr), st));
-  carve(ctx->arena);
+  GIQL_TRY(claim_arena(ctx, st, carve));
   GIQL_TRY(run_spans(ctx, st, *a, *b, n_chrom, lb));
   std::vector<int> mn((size_t)n_chrom), mx((size_t)n_chrom);
   HIP_TRY(hipMemcpyAsync(mn.data(), lb.gmin, (size_t)n_chrom * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -3279,24 +3265,24 @@ int giql_hip_inner_plan_export_dev(giql_hip_ctx* ctx, int32_t* q_rid_out, uint32
                                    int32_t rid_add_a, int32_t rid_add_b, int32_t* query_is_a, int64_t* n_q,
                                    int64_t* n_s, void* stream) {
   if (!ctx || !query_is_a || !n_q || !n_s) return set_err(GIQL_ERR_INVALID, "NULL argument");
-  if (!ctx->planned) return set_err(GIQL_ERR_STATE, "plan export without a successful inner_plan");
-  if (ctx->plan_is_join && ctx->n_reg + ctx->n_irr != 0)
+  if (!ctx->plan.planned) return set_err(GIQL_ERR_STATE, "plan export without a successful inner_plan");
+  if (ctx->plan.plan_is_join && ctx->plan.n_reg + ctx->plan.n_irr != 0)
     return set_err(GIQL_ERR_STATE, "the last giql_hip_inner_join_dev wrote its pairs itself and kept no plan: "
                                    "call giql_hip_inner_plan_dev first");
-  InnerState& S = ctx->inner;
-  const bool empty = ctx->n_reg + ctx->n_irr == 0;
-  if (!empty && (S.uniform == 0 || ctx->n_irr != 0 || ctx->n_c1 != 0))
+  InnerState& S = ctx->plan.inner;
+  const bool empty = ctx->plan.n_reg + ctx->plan.n_irr == 0;
+  if (!empty && (S.uniform == 0 || ctx->plan.n_irr != 0 || ctx->plan.n_c1 != 0))
     return set_err(GIQL_ERR_STATE, "the last plan is not in the compact single-range form "
                                    "(general two-class join or irregular rows): exchange the pairs instead");
   const bool q_is_a = S.uniform != 2;  // in the plan's labels
-  *query_is_a = (q_is_a != ctx->swapped) ? 1 : 0;
-  if (ctx->swapped) {
+  *query_is_a = (q_is_a != ctx->plan.swapped) ? 1 : 0;
+  if (ctx->plan.swapped) {
     const int32_t t = rid_add_a;
     rid_add_a = rid_add_b;
     rid_add_b = t;
   }
-  *n_q = empty ? 0 : (q_is_a ? ctx->n_a : ctx->n_b);
-  *n_s = empty ? 0 : (q_is_a ? ctx->n_b : ctx->n_a);
+  *n_q = empty ? 0 : (q_is_a ? ctx->plan.n_a : ctx->plan.n_b);
+  *n_s = empty ? 0 : (q_is_a ? ctx->plan.n_b : ctx->plan.n_a);
   if (empty) return GIQL_OK;
   if (*n_q > q_capacity || *n_s > s_capacity)
     return set_err(GIQL_ERR_CAPACITY, "plan export needs %lld query rows and %lld sorted rows", (long long)*n_q,
@@ -3340,16 +3326,8 @@ int giql_hip_fill_from_plan_dev(giql_hip_ctx* ctx, const int32_t* q_rid, const u
     return c.off;
   };
   const size_t need = carve(nullptr);
-  if (need > ctx->xplan_cap) {
-    HIP_TRY(hipStreamSynchronize(st));
-    if (ctx->xplan) HIP_TRY(hipFree(ctx->xplan));
-    ctx->xplan = nullptr;
-    ctx->xplan_cap = 0;
-    const size_t want = align_up(need + need / 8, (size_t)1 << 20);
-    hipError_t e = hipMalloc((void**)&ctx->xplan, want);
-    if (e != hipSuccess) return set_err(GIQL_ERR_NOMEM, "hipMalloc(%zu bytes) for the plan scratch failed", want);
-    ctx->xplan_cap = want;
-  }
+  GIQL_TRY(grow_buffer((void**)&ctx->xplan, &ctx->xplan_cap, need, align_up(need + need / 8, (size_t)1 << 20), st,
+                       "the plan scratch"));
   carve(ctx->xplan);
   GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, cnt, (u64)n_q, off, bsums, off + n_q));
   u64 total = 0;
@@ -3483,9 +3461,8 @@ int giql_hip_take_dev(giql_hip_ctx* ctx, const void* const* cols, const int32_t*
       return set_err(GIQL_ERR_INVALID, "column %d: buffer not aligned to its element size", c);
   }
   if (n == 0 || n_cols == 0) return GIQL_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
-  reset_stats(ctx);
   HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
   u32 grid = cdiv((u64)n, (u64)TK_NT * 4 * 4);
   if (grid > GIQL_STREAM_GRID) grid = GIQL_STREAM_GRID;
@@ -3517,25 +3494,23 @@ int giql_hip_take_utf8_plan_dev(giql_hip_ctx* ctx, const int32_t* offsets, int64
   if (!ctx || !out_offsets || !n_bytes || n < 0 || n > 0x7FFFFFF0ll || n_rows < 0 || n_rows > 0x7FFFFFFFll)
     return set_err(GIQL_ERR_INVALID, "bad arguments");
   if ((n > 0 && !idx) || (n_rows > 0 && !offsets)) return set_err(GIQL_ERR_INVALID, "NULL buffer");
-  // its scan partials are carved from the start of the arena, where an INNER plan keeps its arrays
-  ctx->planned = false;
-  ctx->plan_is_join = false;
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
-  reset_stats(ctx);
   *n_bytes = 0;
+  // its scan partials are carved from the start of the arena, where an INNER plan keeps its arrays
+  ctx->plan.planned = false;  // (so the way out with no rows drops the plan too)
   if (n == 0) {
     HIP_TRY(hipMemsetAsync(out_offsets, 0, sizeof(int32_t), st));
     HIP_TRY(hipStreamSynchronize(st));
     return GIQL_OK;
   }
-  Carver c{nullptr};
-  u64* bsums = c.take<u64>(cdiv((u64)n, SCAN_TILE) + 1);
-  u64* total = c.take<u64>(1);
-  GIQL_TRY(ensure_arena(ctx, c.off, st));
-  c = Carver{ctx->arena};
-  bsums = c.take<u64>(cdiv((u64)n, SCAN_TILE) + 1);
-  total = c.take<u64>(1);
+  u64 *bsums = nullptr, *total = nullptr;
+  GIQL_TRY(claim_arena(ctx, st, [&](char* base) {
+    Carver c{base};
+    bsums = c.take<u64>(cdiv((u64)n, SCAN_TILE) + 1);
+    total = c.take<u64>(1);
+    return c.off;
+  }));
   HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
   u32 grid = cdiv((u64)n, (u64)TK_NT * 4);
   if (grid > GIQL_STREAM_GRID) grid = GIQL_STREAM_GRID;
@@ -3566,9 +3541,8 @@ int giql_hip_take_utf8_fill_dev(giql_hip_ctx* ctx, const int32_t* offsets, const
   if (!ctx || n < 0 || n_rows < 0 || n_rows > 0x7FFFFFFFll) return set_err(GIQL_ERR_INVALID, "bad arguments");
   if (n == 0) return GIQL_OK;
   if (!idx || !out_offsets || (n_rows > 0 && !offsets)) return set_err(GIQL_ERR_INVALID, "NULL buffer");
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
-  reset_stats(ctx);
   u32 grid = cdiv((u64)n, (u64)TK_NT * 2);
   if (grid > 2u * GIQL_STREAM_GRID) grid = 2u * GIQL_STREAM_GRID;
   {
@@ -3622,29 +3596,24 @@ int giql_hip_select_expr_dev(giql_hip_ctx* ctx, const giql_pred* preds, int32_t 
   if (!idx_a && n_rows_a == 0 && !uses[0]) n_rows_a = n;
   if (!idx_b && n_rows_b == 0 && !uses[1]) n_rows_b = n;
   // the mask and scan partials are carved from the start of the arena, where an INNER plan keeps its arrays
-  ctx->planned = false;
-  ctx->plan_is_join = false;
+  ctx->plan.planned = false;  // (so the way out with no candidates drops the plan too)
   *n_kept = 0;
   if (n == 0) return GIQL_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
-  reset_stats(ctx);
   const u32 nb = cdiv((u64)n, SEL_TILE);
-  Carver c{nullptr};
   DevOperand* prog = nullptr;
-  auto carve = [&](Carver& cv, u64*& mask, u32*& cnt, u64*& bsums, u64*& total) {
-    mask = cv.take<u64>(((size_t)n + 63) / 64);
-    cnt = cv.take<u32>(nb);
-    bsums = cv.take<u64>(cdiv((u64)nb, SCAN_TILE) + 1);
-    total = cv.take<u64>(1);
-    prog = cv.take<DevOperand>(SEL_MAX_NODES);
-  };
-  u64 *mask, *bsums, *total;
-  u32* cnt;
-  carve(c, mask, cnt, bsums, total);
-  GIQL_TRY(ensure_arena(ctx, c.off, st));
-  c = Carver{ctx->arena};
-  carve(c, mask, cnt, bsums, total);
+  u64 *mask = nullptr, *bsums = nullptr, *total = nullptr;
+  u32* cnt = nullptr;
+  GIQL_TRY(claim_arena(ctx, st, [&](char* base) {
+    Carver c{base};
+    mask = c.take<u64>(((size_t)n + 63) / 64);
+    cnt = c.take<u32>(nb);
+    bsums = c.take<u64>(cdiv((u64)nb, SCAN_TILE) + 1);
+    total = c.take<u64>(1);
+    prog = c.take<DevOperand>(SEL_MAX_NODES);
+    return c.off;
+  }));
   HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
   if (any_expr)  // (pageable source: staged by the runtime before the call returns)
     HIP_TRY(hipMemcpyAsync(prog, nodes, (size_t)n_nodes * sizeof(DevOperand), hipMemcpyHostToDevice, st));
@@ -3679,9 +3648,8 @@ int giql_hip_mark_dev(giql_hip_ctx* ctx, const int32_t* idx, int64_t n, uint8_t*
   if (!ctx || n < 0 || n_rows < 0 || n_rows > 0x7FFFFFFFll || (n > 0 && (!idx || !flags)))
     return set_err(GIQL_ERR_INVALID, "bad arguments");
   if (n == 0) return GIQL_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
-  reset_stats(ctx);
   HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
   u32 grid = cdiv((u64)n, 256 * 8);
   if (grid > GIQL_STREAM_GRID) grid = GIQL_STREAM_GRID;
@@ -4006,21 +3974,14 @@ struct CompactHost {  // page-locked staging of the plan, back to the pool on ev
 // returns GIQL_OK with *done = false when the plan has no compact form (the caller fills and downloads)
 static int inner_host_compact_tail(giql_hip_ctx* ctx, int64_t n, int32_t* ha, int32_t* hb, bool* done) {
   *done = false;
-  InnerState& S = ctx->inner;
-  if (n <= 0 || S.uniform == 0 || ctx->n_irr != 0 || ctx->n_c1 != 0 || ctx->plan_is_join) return GIQL_OK;
+  InnerState& S = ctx->plan.inner;
+  if (n <= 0 || S.uniform == 0 || ctx->plan.n_irr != 0 || ctx->plan.n_c1 != 0 || ctx->plan.plan_is_join) return GIQL_OK;
   const bool q_is_a_plan = S.uniform != 2;
-  const size_t nq = (size_t)(q_is_a_plan ? ctx->n_a : ctx->n_b), ns = (size_t)(q_is_a_plan ? ctx->n_b : ctx->n_a);
+  const size_t nq = (size_t)(q_is_a_plan ? ctx->plan.n_a : ctx->plan.n_b), ns = (size_t)(q_is_a_plan ? ctx->plan.n_b : ctx->plan.n_a);
   if (nq == 0 || ns == 0) return GIQL_OK;
   // device staging: the context's output staging buffer (3 nq + ns words)
   const size_t need = (3 * nq + ns + 64) * sizeof(u32);
-  if (need > ctx->stage_out_cap) {
-    if (ctx->stage_out) (void)hipFree(ctx->stage_out);
-    ctx->stage_out = nullptr;
-    ctx->stage_out_cap = 0;
-    if (hipMalloc(&ctx->stage_out, need + need / 16) != hipSuccess)
-      return set_err(GIQL_ERR_NOMEM, "hipMalloc for the compact plan (%zu bytes) failed", need);
-    ctx->stage_out_cap = need + need / 16;
-  }
+  GIQL_TRY(grow_buffer(&ctx->stage_out, &ctx->stage_out_cap, need, need + need / 16, nullptr, "the compact plan"));
   int32_t* d_qrid = (int32_t*)ctx->stage_out;
   u32* d_lo = (u32*)d_qrid + nq;
   u32* d_cnt = d_lo + nq;
@@ -4225,7 +4186,7 @@ int giql_hip_inner(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, in
   const char* e_compact = getenv("GIQL_HIP_E2E_COMPACT");
   const int compact_mode = e_compact ? (atoi(e_compact) != 0 ? 1 : 0) : -1;
   const bool try_compact = compact_mode == 1 ||
-                           (compact_mode < 0 && !(ctx->spec_valid && (ctx->spec_form == 0 || !ctx->last_no_irr)));
+                           (compact_mode < 0 && !(ctx->guess.spec_valid && (ctx->guess.spec_form == 0 || !ctx->guess.last_no_irr)));
   if (!try_compact) {
     const char* e = getenv("GIQL_HIP_E2E_BLOCK_ROWS");
     const size_t block_rows = e ? (size_t)strtoull(e, nullptr, 10) : ((size_t)4 << 20);
@@ -4252,9 +4213,9 @@ int giql_hip_inner(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, in
   *n_pairs = n;
   // The compact plan pays when it is smaller than the pairs (and the result is worth a team of threads)
   bool compact = false;
-  if (try_compact && n > 0 && ctx->inner.uniform != 0 && ctx->n_irr == 0 && ctx->n_c1 == 0 && !ctx->plan_is_join) {
-    const bool q_is_a_plan = ctx->inner.uniform != 2;
-    const int64_t nq = q_is_a_plan ? ctx->n_a : ctx->n_b, ns = q_is_a_plan ? ctx->n_b : ctx->n_a;
+  if (try_compact && n > 0 && ctx->plan.inner.uniform != 0 && ctx->plan.n_irr == 0 && ctx->plan.n_c1 == 0 && !ctx->plan.plan_is_join) {
+    const bool q_is_a_plan = ctx->plan.inner.uniform != 2;
+    const int64_t nq = q_is_a_plan ? ctx->plan.n_a : ctx->plan.n_b, ns = q_is_a_plan ? ctx->plan.n_b : ctx->plan.n_a;
     // ... on a host with the cores to expand it: 16 threads write ~150 GB/s of pairs, 4 would lose against the link
     const unsigned hw = std::thread::hardware_concurrency();
     compact = compact_mode == 1 || (n >= (4ll << 20) && 8 * n >= 12 * nq + 4 * ns && hw >= 16);
@@ -4288,17 +4249,7 @@ int giql_hip_inner(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, in
     const size_t stride = align_up((size_t)n, (size_t)1 << 19);
     // the device staging of the pairs is kept by the context (a fresh 3.2 GB hipMalloc costs ~160 ms)
     const size_t need = 2 * stride * sizeof(int32_t);
-    int rc = GIQL_OK;
-    if (need > ctx->stage_out_cap) {
-      if (ctx->stage_out) (void)hipFree(ctx->stage_out);
-      ctx->stage_out = nullptr;
-      ctx->stage_out_cap = 0;
-      const size_t want = need + need / 16;
-      if (hipMalloc(&ctx->stage_out, want) != hipSuccess)
-        rc = set_err(GIQL_ERR_NOMEM, "hipMalloc for %lld pairs failed", (long long)n);
-      else
-        ctx->stage_out_cap = want;
-    }
+    int rc = grow_buffer(&ctx->stage_out, &ctx->stage_out_cap, need, need + need / 16, nullptr, "the pairs");
     int32_t* d_a = (int32_t*)ctx->stage_out;
     int32_t* d_b = d_a + stride;
     if (rc == GIQL_OK) rc = giql_hip_inner_fill_dev(ctx, d_a, d_b, n, nullptr);
