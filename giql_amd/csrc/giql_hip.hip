@@ -1295,6 +1295,621 @@ int giql_hip_get_stats(giql_hip_ctx* ctx, giql_hip_stats* out) {
 }
 
 // ------------------------------------------------------------------ INNER
+// One side of an INNER plan (A or B in the plan's labels): everything a side owns, bound once in inner_plan_core.  The
+// forms take the two sides by ROLE -- query / sorted (Q, U) in the fixed-length form, A / B in the general one -- and
+// never select between "the A one" and "the B one" themselves.
+struct PlanSide {
+  const giql_side* side = nullptr;
+  size_t n = 0;
+  int label = 0;             // 0 = A, 1 = B: run_linearize, DevMeta's per-side fields, guess.spec_sorted
+  SortBufs* sort = nullptr;  // inside InnerState: the sorted (key, end, rid) stay for inner_fill
+  u32 *hist = nullptr, *gbase = nullptr;  // digit histogram replicas / digit offsets of its sort
+  u32* status = nullptr;     // its sort's status words (bind_status)
+  u32* irr_list = nullptr;
+  const u32* irr = nullptr;      // DevMeta: its irregular rows
+  const int* len_max = nullptr;  // DevMeta: its longest regular row
+  int32_t* out_row = nullptr;    // one-call join: the caller's output row for this side's ids (else NULL)
+};
+
+// The plan's scratch, as carve_inner lays it out in the arena.
+struct InnerScratch {
+  LinBufs lb;
+  u32 *tile_hist = nullptr, *irr_cnt = nullptr, *top_partial_q = nullptr;
+  u32 *hist[2] = {nullptr, nullptr}, *gbase[2] = {nullptr, nullptr};  // [label]
+  u32 *os_status = nullptr, *os_status2 = nullptr;  // status words: the larger side's, the smaller side's
+  u64 *bsums = nullptr, *bsums1 = nullptr, *scan_chain = nullptr;
+  // arena offsets of the region zeroed up front ([zero_off, zero_end + the larger side's status words)), and how many
+  // passes of those status words are zeroed so far (zero_inner_scratch)
+  size_t zero_off = 0, zero_end = 0;
+  int big_passes_zeroed = 0;
+};
+
+// What ONE attempt at a plan assumed.  begin_attempt fills the upper part right after the span pass; the forms add the
+// choices that depend on sizes; settle_guesses checks all of it against the final read-back.  The stages read these
+// fields, they do not derive them again.
+struct InnerAttempt {
+  bool onesweep = false;
+  int big_side = 0;          // the larger side's label: the one the fixed-length form prefers as its sorted side
+  bool speculated = false;   // form, layout and the guesses below come from the context's previous plan, not from a read-back
+  int form = 0;              // 0 general, 1 B fixed-length (queries = A rows), 2 A fixed-length
+  i64 uni_len = 0;
+  bool want_hist = false;    // the larger side's span pass counted the digits of its aligned keys
+  bool want_hist_q = false;  // ... and the other side's too
+  bool aligned = false;      // the aligned layout holds (a guess when speculated)
+  bool keygen_u = false;     // fixed-length form: the sorted side is sorted straight from its raw columns
+  bool keygen_q = false;     // ... and the query side too (on no_irr)
+  bool keygen_g = false;     // general form: the larger side is (on no irregular row IN IT)
+  bool presorted[2] = {false, false};  // [label] the side arrives in (chrom id, start) order: its sort is skipped
+  bool no_irr = false;       // guess.last_no_irr as used: speculated, and the previous plan met no irregular row
+  bool fuse_len_ok = false;  // no query row longer than the fused windows allow for
+  // chosen by the forms
+  int q_skip = 0;            // low digits the query side's sort left out (on no_irr)
+  bool fuse_cnt = false;     // the sorted side's bucket stage answers the queries' bounds
+  bool early_fill = false;   // the fill is launched inside the plan
+  bool join_in_buckets = false;  // fixed-length form: the bucket stage writes the pairs (FUSE == 2)
+  bool general_join = false;     // general form: the same (FUSE == 3)
+
+  bool count_fused() const { return fuse_cnt || general_join; }
+  bool bucket_join() const { return join_in_buckets || general_join; }
+};
+
+static inline int len_min_of(const DevMeta& m, int label) { return label ? m.len_min_b : m.len_min_a; }
+static inline int len_max_of(const DevMeta& m, int label) { return label ? m.len_max_b : m.len_max_a; }
+static inline u32 skip_mask(int q_skip) { return q_skip == 2 ? 0xFFFF0000u : (q_skip == 1 ? 0xFFFFFF00u : 0xFFFFFFFFu); }
+
+// Uniform-length side?  (fixed-length reads: min == max canonical length > 0 over ALL its rows; a single irregular
+// row makes the minimum 0.)  The form follows from the length ranges of the span pass.
+static void decide_form(const DevMeta& m, size_t na, size_t nb, bool no_uniform, int& form, i64& len) {
+  const bool ub = m.len_min_b == m.len_max_b && m.len_max_b > 0;
+  const bool ua = m.len_min_a == m.len_max_a && m.len_max_a > 0;
+  form = 0;
+  len = 0;
+  if (no_uniform) return;  // GIQL_HIP_NO_UNIFORM: the general form whatever the lengths
+  // sort the uniform side without its end; prefer the larger side when both are
+  if (ub && (!ua || nb >= na)) {
+    form = 1;
+    len = m.len_max_b;
+  } else if (ua) {
+    form = 2;
+    len = m.len_max_a;
+  }
+}
+
+// the fused count's windows allow for query rows up to BS_FUSE_WCAP long (general form: both sides' rows)
+static bool fuse_len_ok(const DevMeta& m, int form) {
+  if (form != 0) return len_max_of(m, form == 1 ? 0 : 1) <= (int)BS_FUSE_WCAP;
+  return m.len_max_a <= (int)BS_FUSE_WCAP && m.len_max_b <= (int)BS_FUSE_WCAP;
+}
+
+// The arena layout of a plan.  (The order and sizes of the take<> calls are public through stats.workspace_bytes, and
+// the single up-front memset depends on the order.)
+static size_t carve_inner(giql_hip_ctx* ctx, char* base, size_t na, size_t nb, int n_chrom, bool onesweep,
+                          InnerScratch& W) {
+  InnerState& S = ctx->plan.inner;
+  const size_t nq = na + nb, n_max = na > nb ? na : nb;
+  const size_t n_tiles_max = cdiv(n_max, RS_TILE);
+  const size_t scan_max = (nq > n_tiles_max * RS_BINS ? nq : n_tiles_max * RS_BINS);
+  constexpr u32 TQ2 = RC_NT * RC_ITEMS_C2;
+  Carver c{base};
+  common_sizes(c, n_chrom, W.lb);
+  sort_sizes(c, na, S.sa, true);
+  sort_sizes(c, nb, S.sb, true);
+  if (onesweep) {
+    // everything that has to start at zero lies back to back, the larger side's status words last: ONE memset
+    // up front instead of one per histogram and per sort (5 launches of ~5 us at the headline sizes)
+    c.off = align_up(c.off, 256);
+    W.zero_off = c.off;
+    W.hist[0] = c.take<u32>((size_t)LIN_HIST_REPLICAS * 1024);
+    W.hist[1] = c.take<u32>((size_t)LIN_HIST_REPLICAS * 1024);
+    W.lb.top_partial = c.take<u32>((size_t)LIN_HIST_REPLICAS * MM_TOP_WORDS);
+    W.top_partial_q = c.take<u32>((size_t)LIN_HIST_REPLICAS * MM_TOP_WORDS);
+    W.gbase[0] = c.take<u32>(1024);
+    W.gbase[1] = c.take<u32>(1024);
+    W.lb.abase = c.take<u32>(MM_HIST_CHROMS);
+    W.os_status2 = c.take<u32>(4 * os_pass_words(na < nb ? na : nb));  // the smaller side's
+    c.off = align_up(c.off, 256);
+    W.zero_end = c.off;
+    W.os_status = c.take<u32>(4 * os_pass_words(n_max));               // the larger side's
+  } else {
+    W.tile_hist = c.take<u32>(n_tiles_max * RS_BINS);
+  }
+  W.bsums = c.take<u64>(cdiv(scan_max, SCAN_TILE) + 2);
+  S.wlo1 = c.take<u32>((size_t)S.nt1 + 2 + (S.c1_fill ? cdiv(nb, TQ2) : 0));
+  S.c1_base = c.take<u64>((size_t)S.nt1 + 2);
+  const size_t n1 = S.c1_fill ? nb : 0;
+  S.lo1 = c.take<u32>(n1);
+  S.cnt1 = c.take<u32>(n1);
+  S.off1 = c.take<u64>(n1 + 1);
+  W.bsums1 = c.take<u64>(cdiv(n1 ? n1 : 1, SCAN_TILE) + 2);
+  const size_t nq2 = ctx->sw.no_uniform ? na : n_max;  // the uniform form may query the other side
+  S.wlo2 = c.take<u32>((size_t)cdiv(nq2, TQ2) + 2);
+  S.cnt2 = c.take<u32>(nq2);
+  S.lo2 = c.take<u32>(nq2);
+  S.off2 = c.take<u64>(nq2 + 1);
+  W.scan_chain = c.take<u64>((size_t)cdiv(nq2, SCAN_TILE) + 4);  // chained scan: a status word per tile + the ticket
+  ctx->plan.irr_a_list = c.take<u32>(na);
+  ctx->plan.irr_b_list = c.take<u32>(nb);
+  W.irr_cnt = c.take<u32>(nq);
+  ctx->plan.irr_off = c.take<u64>(nq + 1);
+  return c.off;
+}
+
+// The one place that knows how many passes of the larger side's status words are zeroed.  First call: the whole zero
+// region in ONE memset (the larger side takes at most 4 passes, 2 or 3 in the three-stage form).  Later calls: the
+// larger side turned out to take more global passes than expected (the density is known now): those need zeroed
+// status words too.
+static int zero_inner_scratch(giql_hip_ctx* ctx, hipStream_t st, InnerScratch& W, size_t n_max) {
+  const int passes = sort_is_local(ctx, n_max) ? local_passes(sort_local_bits(ctx, n_max)) : 4;
+  const size_t stride = os_pass_stride(ctx, n_max);
+  if (W.big_passes_zeroed == 0) {
+    HIP_TRY(hipMemsetAsync(ctx->arena + W.zero_off, 0,
+                           (W.zero_end - W.zero_off) + (size_t)passes * stride * sizeof(u32), st));
+    ctx->call.prezeroed = true;
+  } else if (W.big_passes_zeroed < passes) {
+    HIP_TRY(hipMemsetAsync(W.os_status + (size_t)W.big_passes_zeroed * stride, 0,
+                           (size_t)(passes - W.big_passes_zeroed) * stride * sizeof(u32), st));
+  } else {
+    return GIQL_OK;
+  }
+  W.big_passes_zeroed = passes;
+  return GIQL_OK;
+}
+
+// (the smaller side's passes use the smaller status buffer: both were zeroed up front, neither is reused; of two
+// sides of equal size, `x` takes it)
+static void bind_status(const InnerScratch& W, PlanSide& x, PlanSide& y) {
+  const bool x_small = x.n <= y.n;
+  x.status = x_small ? W.os_status2 : W.os_status;
+  y.status = x_small ? W.os_status : W.os_status2;
+}
+
+// The span pass, and what this attempt assumes from here on.
+//
+// The larger side is the one the uniform form prefers as its fixed-length side: its span pass also counts the
+// digits of its keys (aligned layout), so that, if the form and the layout hold, it is sorted straight from its raw
+// columns with no linearize pass.  A context that has planned before asks for it only when its last plan ended that
+// way.
+//
+// The form is decided from the length ranges the min/max pass produces.  Reading them back costs a stream sync in
+// the middle of the plan (one 100-byte readback; it also surfaces chrom / span errors before the sort), so a context
+// that has planned before SPECULATES on its previous decision and validates it against the same numbers at the
+// read-back the plan ends with anyway (settle_guesses); a wrong guess (the kernels are memory-safe on any input)
+// repeats the plan once without speculation.
+static int begin_attempt(giql_hip_ctx* ctx, hipStream_t st, PlanSide& A, PlanSide& B, int n_chrom, InnerScratch& W,
+                         InnerAttempt& T) {
+  const Guesses& g = ctx->guess;
+  PlanSide& big = T.big_side ? B : A;
+  PlanSide& other = T.big_side ? A : B;
+  const int big_form = T.big_side ? 1 : 2;  // the fixed-length form whose sorted side is the larger one
+  T.speculated = T.onesweep && g.spec_valid;
+  T.no_irr = T.speculated && g.last_no_irr;
+  T.want_hist = T.onesweep && !ctx->sw.no_span_hist && ctx->sw.os_variant == 0 && n_chrom <= MM_HIST_CHROMS;
+  if (T.want_hist && T.speculated)  // ... or in the general form without irregular rows (its larger side)
+    T.want_hist = g.spec_aligned && (g.spec_form == big_form || (g.spec_form == 0 && g.last_no_irr));
+  // ... and the QUERY side of the fixed-length form too (round 3): its (key, end, rid) sort starts from the raw
+  // columns as well (k_onesweep<3, .., KEYGEN>), so neither side has a linearize pass -- on the guesses that the
+  // form and the layout hold AND that the query side has no irregular row (those carry the sentinel key and a
+  // list entry, which only the linearize pass produces): validated at the read-back like the others.
+  T.want_hist_q = T.want_hist && T.no_irr && g.spec_form == big_form && other.n > 0;
+  if (T.want_hist_q) {
+    W.lb.hist_partial2 = other.hist;
+    W.lb.top_partial2 = W.top_partial_q;
+  }
+  GIQL_TRY(run_spans(ctx, st, *A.side, *B.side, n_chrom, W.lb, T.want_hist ? T.big_side : -1, big.hist));
+  if (T.speculated) {
+    T.form = g.spec_form;
+    T.uni_len = g.spec_len;
+    T.aligned = T.want_hist;  // = g.spec_aligned when the form matches
+    T.fuse_len_ok = g.spec_fuse_len_ok;
+    // Sorted inputs: a side the span pass found in (chrom id, start) order (and free of irregular rows) skips its
+    // sort -- from the read-back on a first plan, the previous plan's answer afterwards (validated in settle_guesses)
+    T.presorted[0] = g.spec_sorted[0];
+    T.presorted[1] = g.spec_sorted[1];
+  } else if (T.onesweep) {
+    GIQL_TRY(read_meta(ctx, st));
+    const DevMeta& m = *ctx->h_meta;
+    decide_form(m, A.n, B.n, ctx->sw.no_uniform, T.form, T.uni_len);
+    T.aligned = T.want_hist && m.aligned_ok != 0;
+    T.fuse_len_ok = fuse_len_ok(m, T.form);
+    T.presorted[0] = m.unsorted_a == 0;
+    T.presorted[1] = m.unsorted_b == 0;
+    // the span is known now, before anything is sorted: the sort form follows the table's real density
+    // already on this first plan (the one write of a guess outside settle_guesses).  The span pass counted its
+    // digits for the form it expected: if the larger side leaves the three-stage sort, its high-digits-only
+    // histogram is of no use and that side is linearized (which counts all four digits)
+    const int expected_bits = sort_local_bits(ctx, big.n);
+    ctx->guess.last_span = m.total_span;
+    // (the high-digits-only histogram serves 16-bit buckets alone: narrower ones sort on bits 8-15 too)
+    if (expected_bits == 16 && sort_local_bits(ctx, big.n) != 16) T.aligned = false;
+    GIQL_TRY(zero_inner_scratch(ctx, st, W, big.n));
+  }
+  T.keygen_u = T.aligned && T.form == big_form;
+  T.keygen_q = T.keygen_u && T.want_hist_q;
+  // General form: the larger side's (key, end, rid) sort can start from the raw columns too, as long as
+  // that side holds no irregular row (those carry the sentinel key, which depends on `end`; the span pass
+  // counted digits of start alone).  Known from the read-back on a first plan, a guess afterwards.
+  T.keygen_g = T.aligned && T.form == 0 && (T.speculated ? g.last_no_irr : len_min_of(*ctx->h_meta, T.big_side) > 0);
+  return GIQL_OK;
+}
+
+// The span pass counted a side's digits already: fold the per-chromosome top digits onto the bases and scan, and let
+// the first sort pass build the keys from (chrom, start) -- no linearize pass.  hist2 / gbase2: the other side's as
+// well (lb.top_partial2), both in one launch pair.
+static int span_digit_offsets(giql_hip_ctx* ctx, hipStream_t st, const LinBufs& lb, u32* hist, u32* gbase,
+                              u32* hist2, u32* gbase2, const char* what) {
+  Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
+  if (hist2) {
+    hipLaunchKernelGGL(k_fold_top2, dim3(MM_HIST_CHROMS, 2), dim3(256), 0, st, lb.top_partial, lb.top_partial2,
+                       lb.abase, hist, hist2);
+    hipLaunchKernelGGL(k_digit_offsets2, dim3(4, 2), dim3(256), 0, st, hist, hist2, (u32)LIN_HIST_REPLICAS, gbase,
+                       gbase2);
+  } else {
+    hipLaunchKernelGGL(k_fold_top, dim3(MM_HIST_CHROMS), dim3(256), 0, st, lb.top_partial, lb.abase, hist);
+    hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, hist, (u32)LIN_HIST_REPLICAS, gbase);
+  }
+  return post_launch(what);
+}
+
+// The query side of a fused bucket stage as its own sort left it, and where a join writes its pairs.
+struct FuseQuery {
+  const SortBufs* sort;
+  size_t n;
+  const u32* irr;      // rows of it that match nothing (sorted last, skipped by the windows)
+  const u32* gbase;    // its sort's digit offsets
+  const int* len_max;  // device: its longest row
+};
+struct FuseTarget {
+  int32_t *row_q, *row_s;
+  u64 cap;
+};
+static inline FuseQuery fuse_query(const PlanSide& q) { return FuseQuery{q.sort, q.n, q.irr, q.gbase, q.len_max}; }
+
+// The FuseCount of a bucket stage: bounds only (join == NULL; the caller adds its outputs: dev.lo_out / hi_out and the
+// words to zero), or the join itself, with the pairs counted in DevMeta::n_out (zeroed by the span pass / by
+// k_init_minmax).  general: rows of any length on both sides; len_max_u = how far the windows then reach up.
+static FuseCount make_fuse_count(giql_hip_ctx* ctx, const FuseQuery& q, i64 lo_off, u32 key_mask,
+                                 const FuseTarget* join, bool general, const int* len_max_u, u32* zero_ptr) {
+  FuseCount fc = {};  // (no bounds outputs, no words to zero, no pairs target unless set below)
+  fc.join = join != nullptr;
+  fc.general = general;
+  fc.zero_ptr = zero_ptr;
+  fc.dev.qkey = q.sort->key[0];
+  fc.dev.qend = q.sort->end[0];
+  fc.dev.qwin = ctx->bucket_qwin;
+  fc.dev.lo_off = lo_off;
+  if (join) {
+    fc.dev.qrid = q.sort->rid[0];
+    fc.dev.row_q = join->row_q;
+    fc.dev.row_s = join->row_s;
+    fc.dev.cap = join->cap;
+    fc.dev.cursor = reinterpret_cast<unsigned long long*>(&ctx->d_meta->n_out);
+  }
+  fc.nq_total = (u32)q.n;
+  fc.irr_q = q.irr;
+  fc.gbq3 = q.gbase + 3 * OS_BINS;
+  fc.key_mask = key_mask;
+  fc.len_max_q = q.len_max;
+  fc.len_max_u = general ? len_max_u : nullptr;
+  return fc;
+}
+
+// The bucket stage wrote the pairs, counted in DevMeta::n_out: read the count back; the join stands only if every
+// guess held and the pairs fitted.
+static int finish_bucket_join(giql_hip_ctx* ctx, hipStream_t st) {
+  GIQL_TRY(read_meta(ctx, st));
+  ctx->plan.n_c1 = 0;
+  ctx->plan.n_reg = ctx->h_meta->n_out;
+  ctx->plan.fuse_done = ctx->h_meta->irr_a + ctx->h_meta->irr_b == 0 && ctx->plan.n_reg <= ctx->plan.fuse_cap;
+  ctx->stats.phase_bytes[GIQL_PH_SORT_LOCAL] += (int64_t)8 * (int64_t)ctx->plan.n_reg;  // the pairs
+  return GIQL_OK;
+}
+
+// ---- uniform-length form: queries Q (full rows) against points U (starts only)
+static int plan_uniform(giql_hip_ctx* ctx, hipStream_t st, int n_chrom, PlanSide& Q, PlanSide& U, InnerScratch& W,
+                        InnerAttempt& T) {
+  InnerState& S = ctx->plan.inner;
+  const LinBufs& lb = W.lb;
+  SortBufs& sq = *Q.sort;
+  SortBufs& su = *U.sort;
+  su.end[0] = su.end[1] = nullptr;  // the uniform side carries (key, rid) only
+  bind_status(W, Q, U);
+  // Fused range count: when U takes the three-stage sort, its bucket sort answers the queries' bounds
+  // (bucket_sort.hip.h) -- as long as no query row is longer than the windows allow for: known from the
+  // read-back on a first plan, the previous plan's answer afterwards (validated like the other guesses)
+  T.fuse_cnt = !ctx->sw.no_fuse_count && sort_is_local(ctx, U.n) && T.fuse_len_ok;
+  // KNOWN ODDITY (kept as it is): on a speculated attempt this is not the previous INNER plan's maximum but the last
+  // read-back of ANY call on the context (h_meta is shared); it only sizes the window estimate below.
+  const int q_len_max = len_max_of(*ctx->h_meta, Q.label);
+  if (T.keygen_u) {
+    // (the query side sorted from its raw columns too: its digits were counted in the span pass)
+    GIQL_TRY(span_digit_offsets(ctx, st, lb, U.hist, U.gbase, T.keygen_q ? Q.hist : nullptr, Q.gbase,
+                                "digit offsets (span histogram)"));
+  }
+  // the query side's chain (linearize + sort) beside the other side's when it is small (the fused count
+  // needs the sorted queries before U's last stage: one stream)
+  // (the fork comes AFTER the digit offsets above: the query side's sort on the second stream reads them)
+  SideChain sc(ctx, st, (Q.n <= U.n && !T.fuse_cnt) ? Q.n : 0);
+  if (!T.keygen_q) {
+    GIQL_TRY(run_linearize(ctx, sc.stream(), *Q.side, n_chrom, lb, sq.key[0], sq.end[0], Q.irr_list, Q.label, 0,
+                           Q.hist, Q.gbase));
+  }
+  if (!T.keygen_u) {
+    GIQL_TRY(run_linearize(ctx, st, *U.side, n_chrom, lb, su.key[0], nullptr, U.irr_list, U.label, 0, U.hist,
+                           U.gbase, nullptr, nullptr, /*skip_end=*/true));  // uniform => no irregular row: `end` is not read
+  }
+  // The query side's order only serves locality (its bounds are searched per row, its pairs are laid
+  // out by the scan), so its lowest digit stays unsorted: three passes.  Irregular rows would break
+  // that (their sentinel keys must end up LAST, after every row of the top 256-key block): taken
+  // only on the context's guess that there are none, validated with the other guesses.
+  // With the fused count the queries only have to be grouped by the bucket their key falls into (the windows
+  // of k_bucket_bounds_fused are computed under the same mask and then cover whole query buckets): TWO digits
+  // unsorted, two passes.
+  T.q_skip = (T.no_irr && !sort_is_local(ctx, Q.n)) ? 1 : 0;
+  // (narrower buckets: the queries stay grouped by key >> 8 -- a window under the 16-bit mask would span 2-8 buckets)
+  const int wb_u = sort_local_bits(ctx, U.n);
+  if (T.q_skip && T.fuse_cnt && wb_u == 16) T.q_skip = 2;
+  const u32 q_mask = skip_mask(T.q_skip);
+  GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sq, (u32)Q.n, Q.gbase, Q.status, false,
+                             T.keygen_q ? Q.side : nullptr, lb.abase, T.q_skip, nullptr, T.presorted[Q.label]));
+  // One-call join (giql_hip_inner_join_dev): the caller's buffers are here and everything about this plan is a
+  // guess that has held so far (same form as last time, no irregular rows), so the fill is launched inside the
+  // plan, with a grid bounded by the capacity and the true count read on the device.
+  constexpr u32 T2 = FILL_NT * FILL_ITEMS_C2;
+  static_assert((T2 & (T2 - 1)) == 0, "fill tiles are a power of two (k_scan_chain_diff shifts)");
+  const u64 nt_cap64 = (ctx->plan.fuse_cap + T2 - 1) / T2;
+  const bool offered = Q.out_row && T.no_irr && ctx->plan.fuse_cap > 0;
+  T.early_fill = offered && nt_cap64 <= 0x7FFFFFF0ull && ((size_t)nt_cap64 + 2) * sizeof(u32) <= ctx->part_cap;
+  // ... and, when the other side's bucket stage answers the bounds anyway, the pairs are written right there
+  // (bucket_sort.hip.h, FUSE == 2) -- as long as the query windows stay well inside what a block holds in
+  // registers: a window covers the query buckets (coarsely grouped: whole 65536-key buckets) that a bucket's
+  // reach -- its own 65536 keys, the fixed length above it, the longest query below it -- touches
+  const double win_keys = T.q_skip == 2 ? 3.0 * 65536.0 + (double)T.uni_len
+                                        : (double)(1u << (wb_u ? wb_u : 16)) + 512.0 + (double)T.uni_len +
+                                              (double)(q_len_max > 0 ? q_len_max : 0);
+  T.join_in_buckets = T.fuse_cnt && offered && ctx->guess.last_span > 0 &&
+                      (double)Q.n * win_keys / (double)ctx->guess.last_span <= 0.75 * (double)BJ_WCAP;
+  FuseCount fc = {};
+  if (T.fuse_cnt) {
+    const FuseTarget out{Q.out_row, U.out_row, ctx->plan.fuse_cap};
+    // u.start in [q.start - L + 1, q.end)
+    fc = make_fuse_count(ctx, fuse_query(Q), 1 - T.uni_len, q_mask, T.join_in_buckets ? &out : nullptr, false, nullptr,
+                         reinterpret_cast<u32*>(W.scan_chain));
+    fc.zero_words = (u32)(2 * (cdiv(Q.n, SC_TILE) + 2));
+    fc.dev.lo_out = S.lo2;
+    fc.dev.hi_out = S.cnt2;  // the scan below turns the upper bounds into counts in place
+  }
+  GIQL_TRY(run_sort_onesweep(ctx, st, su, (u32)U.n, U.gbase, U.status, false, T.keygen_u ? U.side : nullptr, lb.abase,
+                             0, T.fuse_cnt ? &fc : nullptr, T.presorted[U.label]));
+  GIQL_TRY(sc.join());
+  constexpr u32 TQ = RC_NT * RC_ITEMS_C2;
+  S.nt2 = cdiv(Q.n, TQ);
+  if (T.join_in_buckets) return finish_bucket_join(ctx, st);
+  bool part_done = false;  // the scan wrote the fill's partition
+  if (T.fuse_cnt) {
+    u32 log2_t2 = 0;
+    while ((1u << log2_t2) < T2) log2_t2++;
+    GIQL_TRY(run_scan_chain(ctx, st, GIQL_PH_SCAN, S.cnt2, S.lo2, Q.n, Q.irr, S.off2, W.scan_chain,
+                            &ctx->d_meta->n_out, T.early_fill ? ctx->part : nullptr, log2_t2, (u32)nt_cap64 + 1));
+    part_done = T.early_fill;
+  } else {
+    {
+      Phase ph(ctx, st, GIQL_PH_COUNT, 2);
+      const i64 lo_off = 1 - T.uni_len;  // u.start in [q.start - L + 1, q.end)
+      hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)S.nt2 + 1, 256)), dim3(256), 0, st,
+                         sq.key[0], (u32)Q.n, Q.irr, su.key[0], (u32)U.n, U.irr, lo_off, TQ, S.nt2,
+                         S.wlo2, q_mask);
+      hipLaunchKernelGGL((k_range_count<RC_ITEMS_C2, RC_LDS_CAP>), dim3(S.nt2), dim3(RC_NT), 0, st,
+                         sq.key[0], sq.end[0], (u32)Q.n, Q.irr, su.key[0], (u32)U.n, U.irr, lo_off,
+                         S.wlo2, S.lo2, S.cnt2);
+      GIQL_TRY(post_launch("range count (uniform)"));
+    }
+    GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, S.cnt2, Q.n, S.off2, W.bsums, S.off2 + Q.n, &ctx->d_meta->n_out));
+  }
+  if (T.early_fill) {
+    // The early fill: no stream sync between plan and fill.  Validated at the read-back below and in
+    // settle_guesses; a wrong guess leaves the buffers to the ordinary fill.
+    const u32 nt_cap = (u32)nt_cap64;
+    if (!part_done) {
+      Phase ph(ctx, st, GIQL_PH_PARTITION);
+      hipLaunchKernelGGL(k_partition, dim3(cdiv((u64)nt_cap + 1, 256)), dim3(256), 0, st, S.off2,
+                         (u32)Q.n, (u64)0, T2, nt_cap, ctx->part, (const u64*)(S.off2 + Q.n), ctx->plan.fuse_cap);
+    }
+    {
+      Phase ph(ctx, st, GIQL_PH_FILL);
+      hipLaunchKernelGGL((k_fill<FILL_ITEMS_C2>), dim3(nt_cap), dim3(FILL_NT), 0, st, S.off2, S.lo2, sq.rid[0],
+                         (u32)Q.n, su.rid[0], ctx->part, (u64)0, (u64)0, Q.out_row, U.out_row,
+                         (const u64*)(S.off2 + Q.n), ctx->plan.fuse_cap);
+    }
+    GIQL_TRY(post_launch("fused fill"));
+  }
+  GIQL_TRY(read_meta(ctx, st));
+  ctx->plan.n_c1 = 0;
+  ctx->plan.n_reg = ctx->h_meta->n_out;
+  // the early fill stands only if every guess held and the pairs fitted
+  ctx->plan.fuse_done = T.early_fill && ctx->h_meta->irr_a + ctx->h_meta->irr_b == 0 && ctx->plan.n_reg <= ctx->plan.fuse_cap;
+  return GIQL_OK;
+}
+
+// ---- general form: two classes of pairs -- class 1: a.start in [b.start, b.end), counted per B row against the
+// sorted A starts; class 2: b.start in (a.start, a.end), counted per A row against the sorted B starts
+static int plan_general(giql_hip_ctx* ctx, hipStream_t st, int n_chrom, PlanSide& A, PlanSide& B, InnerScratch& W,
+                        InnerAttempt& T) {
+  InnerState& S = ctx->plan.inner;
+  const LinBufs& lb = W.lb;
+  SortBufs& sa = *A.sort;
+  SortBufs& sbb = *B.sort;
+  constexpr u32 TQ2 = RC_NT * RC_ITEMS_C2;
+  const size_t n_small = A.n < B.n ? A.n : B.n;
+  bind_status(W, B, A);
+  // The join itself in B's bucket stage (bucket_sort.hip.h, FUSE == 3): one-call form, on the context's guesses (the
+  // general form again, no irregular row, no row longer than the windows allow for), B the three-stage side, the A
+  // rows -- fully sorted -- sparse enough for a bucket's window to stay in a block's registers.
+  // (a window = the A rows within the bucket's 65536 keys + the longest rows of either side: the previous plan's
+  // maxima, like the guess they validate)
+  // KNOWN ODDITY (kept as it is): h_meta holds the last read-back of ANY call on the context, not of the last INNER
+  // plan, so "the previous plan's maxima" may be another operator's numbers.  A candidate for a later fix with a test.
+  const int wb_b = sort_local_bits(ctx, B.n);
+  T.general_join = T.onesweep && A.out_row && T.no_irr && ctx->plan.fuse_cap > 0 && B.n >= A.n && wb_b != 0 &&
+                   T.fuse_len_ok && ctx->guess.last_span > 0 &&
+                   (double)A.n * ((double)(1u << (wb_b ? wb_b : 16)) + (double)ctx->h_meta->len_max_a +
+                                  (double)ctx->h_meta->len_max_b) /
+                           (double)ctx->guess.last_span <= 0.5 * (double)BJ_WCAP;
+  // the smaller side's chain (linearize + sort) beside the larger side's when it is small (not in the form above:
+  // B's last stage reads the sorted A)
+  SideChain sc(ctx, st, (T.onesweep && !T.general_join) ? n_small : 0);
+  PlanSide* const sides[2] = {&A, &B};
+  hipStream_t stream_of[2] = {A.n < B.n ? sc.stream() : st, A.n < B.n ? st : sc.stream()};
+  const giql_side* keygen_of[2] = {nullptr, nullptr};
+  if (T.keygen_g) keygen_of[T.big_side] = sides[T.big_side]->side;
+  for (PlanSide* s : sides) {
+    if (keygen_of[s->label]) {
+      GIQL_TRY(span_digit_offsets(ctx, stream_of[s->label], lb, s->hist, s->gbase, nullptr, nullptr,
+                                  "digit offsets (span histogram, general form)"));
+    } else {
+      GIQL_TRY(run_linearize(ctx, stream_of[s->label], *s->side, n_chrom, lb, s->sort->key[0], s->sort->end[0],
+                             s->irr_list, s->label, 0, s->hist, s->gbase));
+    }
+  }
+  if (T.onesweep) {
+    GIQL_TRY(run_sort_onesweep(ctx, stream_of[0], sa, (u32)A.n, A.gbase, A.status, false, keygen_of[0], lb.abase, 0,
+                               nullptr, T.presorted[0]));
+    FuseCount fg = {};
+    if (T.general_join) {
+      const FuseTarget out{A.out_row, B.out_row, ctx->plan.fuse_cap};
+      // class 2: b.start in (a.start, a.end)
+      fg = make_fuse_count(ctx, fuse_query(A), 1, 0xFFFFFFFFu, &out, true, B.len_max,
+                           reinterpret_cast<u32*>(W.scan_chain));
+    }
+    GIQL_TRY(run_sort_onesweep(ctx, stream_of[1], sbb, (u32)B.n, B.gbase, B.status, false, keygen_of[1], lb.abase, 0,
+                               T.general_join ? &fg : nullptr, T.presorted[1]));
+    GIQL_TRY(sc.join());
+  } else {
+    GIQL_TRY(run_sort(ctx, st, sa, (u32)A.n, W.tile_hist, W.bsums));
+    GIQL_TRY(run_sort(ctx, st, sbb, (u32)B.n, W.tile_hist, W.bsums));
+  }
+  if (T.general_join) return finish_bucket_join(ctx, st);
+  // class 1 (count + the scan of its block totals) runs beside class 2 when both sides are small
+  SideChain sc1(ctx, st, T.onesweep ? n_small : 0);
+  hipStream_t st1 = sc1.stream();
+  {
+    Phase ph(ctx, st, GIQL_PH_COUNT, 4);
+    // class 1: queries = sorted B, points = sorted A starts, range [b.start, b.end);
+    // only one total per block is kept (see k_c1_count)
+    if (S.c1_fill) {
+      const u32 nt1r = cdiv(B.n, TQ2);
+      hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)nt1r + 1, 256)), dim3(256), 0, st1,
+                         sbb.key[0], (u32)B.n, B.irr, sa.key[0], (u32)A.n, A.irr, (i64)0, TQ2, nt1r, S.wlo1);
+      hipLaunchKernelGGL((k_range_count<RC_ITEMS_C2, RC_LDS_CAP>), dim3(nt1r), dim3(RC_NT), 0, st1,
+                         sbb.key[0], sbb.end[0], (u32)B.n, B.irr, sa.key[0], (u32)A.n, A.irr, (i64)0, S.wlo1,
+                         S.lo1, S.cnt1);
+    } else {
+      const u32 c1_tq = (u32)(C1_NT * S.c1_items);  // class-1 rows per block
+      hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)S.nt1 + 1, 256)), dim3(256), 0, st1,
+                         sbb.key[0], (u32)B.n, B.irr, sa.key[0], (u32)A.n, A.irr, (i64)0, c1_tq, S.nt1,
+                         S.wlo1);
+      if (S.c1_items == 2)
+        hipLaunchKernelGGL(k_c1_count<2>, dim3(S.nt1), dim3(C1_NT), 0, st1, sbb.key[0], sbb.end[0], (u32)B.n,
+                           B.irr, sa.key[0], (u32)A.n, A.irr, S.wlo1, S.c1_base);
+      else
+        hipLaunchKernelGGL(k_c1_count<C1_ITEMS_MAX>, dim3(S.nt1), dim3(C1_NT), 0, st1, sbb.key[0], sbb.end[0], (u32)B.n,
+                           B.irr, sa.key[0], (u32)A.n, A.irr, S.wlo1, S.c1_base);
+      // class-1 block totals -> block bases (one block, in place); total -> n_out_c1
+      hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, st1, S.c1_base, S.nt1,
+                         &ctx->d_meta->n_out_c1);
+    }
+    // class 2: queries = sorted A, points = sorted B starts, range (a.start, a.end)
+    hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)S.nt2 + 1, 256)), dim3(256), 0, st,
+                       sa.key[0], (u32)A.n, A.irr, sbb.key[0], (u32)B.n, B.irr, (i64)1, TQ2, S.nt2, S.wlo2);
+    hipLaunchKernelGGL((k_range_count<RC_ITEMS_C2, RC_LDS_CAP>), dim3(S.nt2), dim3(RC_NT), 0, st,
+                       sa.key[0], sa.end[0], (u32)A.n, A.irr, sbb.key[0], (u32)B.n, B.irr, (i64)1, S.wlo2,
+                       S.lo2, S.cnt2);
+    GIQL_TRY(post_launch("range count"));
+  }
+  if (S.c1_fill) {
+    GIQL_TRY(run_scan<u64>(ctx, st1, GIQL_PH_SCAN, S.cnt1, B.n, S.off1, W.bsums1, S.off1 + B.n, &ctx->d_meta->n_out_c1));
+  }
+  GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, S.cnt2, A.n, S.off2, W.bsums, S.off2 + A.n, &ctx->d_meta->n_out));
+  GIQL_TRY(sc1.join());
+  GIQL_TRY(read_meta(ctx, st));
+  ctx->plan.n_c1 = ctx->h_meta->n_out_c1;
+  ctx->plan.n_reg = ctx->h_meta->n_out + ctx->plan.n_c1;
+  return GIQL_OK;
+}
+
+// After the attempt's final read-back: the ONLY place that decides whether a guess missed, and (bar last_span's early
+// write in begin_attempt) that writes the INNER guesses.  false: a guess missed -- the result is not valid, the
+// guesses are dropped, and the plan is repeated from the numbers just read.
+static bool settle_guesses(giql_hip_ctx* ctx, const InnerAttempt& T, size_t na, size_t nb) {
+  const DevMeta& m = *ctx->h_meta;
+  Guesses& g = ctx->guess;
+  const bool any_irr = m.irr_a + m.irr_b > 0;
+  if (T.onesweep) {
+    int form;
+    i64 len;
+    decide_form(m, na, nb, ctx->sw.no_uniform, form, len);
+    const bool aligned_now = m.aligned_ok != 0;
+    const bool fuse_len_ok_now = fuse_len_ok(m, form);  // (the query side of the form just decided)
+    // the lengths say another form, or another fixed length
+    const bool form_wrong = form != T.form || len != T.uni_len;
+    // the span pass counted digits of aligned keys, and the data does not take the aligned layout
+    const bool layout_wrong = T.want_hist && !aligned_now;
+    // a query side sorted without its low digits must hold no irregular row (their sentinel keys must come last)
+    const bool coarse_wrong = T.q_skip != 0 && any_irr;
+    // a side sorted from its raw columns must hold no irregular row (its length range starts above 0); such a row
+    // was keyed as if regular, and never listed
+    const bool keygen_wrong = (T.keygen_g && len_min_of(m, T.big_side) <= 0) ||
+                              (T.keygen_q && len_min_of(m, 1 - T.big_side) <= 0);
+    // the fused count's windows allow for rows up to BS_FUSE_WCAP long
+    const bool fuse_wrong = T.count_fused() && !fuse_len_ok_now;
+    // a side taken as sorted must be: an out-of-order row was left where it was
+    const bool sorted_wrong = (T.presorted[0] && m.unsorted_a != 0) || (T.presorted[1] && m.unsorted_b != 0);
+    // a join in the bucket stage that did not stand (the pairs did not fit the caller's buffers, or a guess failed)
+    // left no plan arrays for the ordinary fill: plan again, unspeculated -- which never takes that form
+    const bool join_wrong = T.bucket_join() && !ctx->plan.fuse_done;
+    // (these three are stored before a missed guess returns)
+    if (keygen_wrong) g.last_no_irr = false;
+    g.spec_fuse_len_ok = fuse_len_ok_now;
+    g.spec_sorted[0] = m.unsorted_a == 0;
+    g.spec_sorted[1] = m.unsorted_b == 0;
+    if (T.speculated && (form_wrong || layout_wrong || coarse_wrong || keygen_wrong || fuse_wrong || sorted_wrong ||
+                         join_wrong)) {
+      g.spec_valid = false;  // wrong guess: plan again from the numbers just read
+      g.spec_misses++;
+      ctx->plan.fuse_done = false;
+      return false;
+    }
+    g.spec_valid = true;
+    g.spec_form = form;
+    g.spec_len = len;
+    // the layout is probed only when the span histogram ran; a plan that skipped it for a
+    // form mismatch leaves the last answer (a later form change re-plans unspeculated anyway)
+    if (T.want_hist) g.spec_aligned = aligned_now;
+  }
+  g.last_span = m.total_span;
+  g.last_no_irr = !any_irr;
+  return true;
+}
+
+// The pairs of irregular rows (canonical end <= start), counted per row of either side against the other's list.
+static int plan_irregular(giql_hip_ctx* ctx, hipStream_t st, const PlanSide& A, const PlanSide& B, InnerScratch& W) {
+  const size_t nq = A.n + B.n;
+  {
+    Phase ph(ctx, st, GIQL_PH_IRREGULAR);
+    hipLaunchKernelGGL(k_irr_count, dim3(cdiv(nq, 256)), dim3(256), 0, st, view_of(*A.side), view_of(*B.side),
+                       A.irr_list, B.irr_list, ctx->d_meta, W.irr_cnt);
+    GIQL_TRY(post_launch("irregular count"));
+  }
+  GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_IRREGULAR, W.irr_cnt, nq, ctx->plan.irr_off, W.bsums,
+                         ctx->plan.irr_off + nq));
+  HIP_TRY(hipMemcpyAsync(&ctx->d_meta->n_out_irr, ctx->plan.irr_off + nq, sizeof(u64),
+                         hipMemcpyDeviceToDevice, st));
+  GIQL_TRY(read_meta(ctx, st));
+  ctx->plan.n_irr = ctx->h_meta->n_out_irr;
+  return GIQL_OK;
+}
+
+// One attempt at a plan, in the plan's labels (A = the smaller side when giql_hip_inner_plan_dev_impl exchanged them:
+// ctx->plan.swapped).
 static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b,
                            int32_t n_chrom, void* stream, int64_t* n_pairs) {
   hipStream_t st = (hipStream_t)stream;
@@ -1313,546 +1928,63 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
     ctx->plan.plan_is_join = false;
     return GIQL_OK;
   }
-  const size_t na = (size_t)a->n, nb = (size_t)b->n, nq = na + nb;
+  const size_t na = (size_t)a->n, nb = (size_t)b->n;
 
   // ---- carve the arena (dry run for the size, then for real)
-  LinBufs lb;
   InnerState& S = ctx->plan.inner;
-  u32 *tile_hist = nullptr, *cnt2 = nullptr, *irr_cnt = nullptr;
-  u32 *hist_a = nullptr, *hist_b = nullptr, *gbase_a = nullptr, *gbase_b = nullptr;
-  u32 *os_status = nullptr, *os_status2 = nullptr, *top_partial_q = nullptr;
-  u64 *bsums = nullptr, *bsums1 = nullptr, *scan_chain = nullptr;
-  size_t zero_off = 0, zero_end = 0;  // arena offsets of the region zeroed up front ([zero_off, zero_end + the larger side's status words))
-  const bool onesweep = !ctx->sw.classic_sort && na <= OS_MAX_ROWS && nb <= OS_MAX_ROWS;
-  const size_t n_max = na > nb ? na : nb;
-  const size_t n_tiles_max = cdiv(n_max, RS_TILE);
-  const size_t scan_max = (nq > n_tiles_max * RS_BINS ? nq : n_tiles_max * RS_BINS);
-  constexpr u32 TQ2 = RC_NT * RC_ITEMS_C2;
+  InnerScratch W;
+  InnerAttempt T;
+  T.onesweep = !ctx->sw.classic_sort && na <= OS_MAX_ROWS && nb <= OS_MAX_ROWS;
+  T.big_side = nb >= na ? 1 : 0;
   S.c1_items = nb <= C1_SMALL_ROWS ? 2 : C1_ITEMS_MAX;
-  const u32 c1_tq = (u32)(C1_NT * S.c1_items);  // class-1 rows per block
-  S.nt1 = cdiv(nb, c1_tq);
+  S.nt1 = cdiv(nb, (u32)(C1_NT * S.c1_items));
   S.c1_fill = nb <= C1_SMALL_ROWS;
-  S.nt2 = cdiv(na, TQ2);
-  auto carve = [&](char* base) {
-    Carver c{base};
-    common_sizes(c, n_chrom, lb);
-    sort_sizes(c, na, S.sa, true);
-    sort_sizes(c, nb, S.sb, true);
-    if (onesweep) {
-      // everything that has to start at zero lies back to back, the larger side's status words last: ONE memset
-      // up front instead of one per histogram and per sort (5 launches of ~5 us at the headline sizes)
-      c.off = align_up(c.off, 256);
-      zero_off = c.off;
-      hist_a = c.take<u32>((size_t)LIN_HIST_REPLICAS * 1024);
-      hist_b = c.take<u32>((size_t)LIN_HIST_REPLICAS * 1024);
-      lb.top_partial = c.take<u32>((size_t)LIN_HIST_REPLICAS * MM_TOP_WORDS);
-      top_partial_q = c.take<u32>((size_t)LIN_HIST_REPLICAS * MM_TOP_WORDS);
-      gbase_a = c.take<u32>(1024);
-      gbase_b = c.take<u32>(1024);
-      lb.abase = c.take<u32>(MM_HIST_CHROMS);
-      os_status2 = c.take<u32>(4 * os_pass_words(na < nb ? na : nb));  // the smaller side's
-      c.off = align_up(c.off, 256);
-      zero_end = c.off;
-      os_status = c.take<u32>(4 * os_pass_words(n_max));               // the larger side's
-    } else {
-      tile_hist = c.take<u32>(n_tiles_max * RS_BINS);
-    }
-    bsums = c.take<u64>(cdiv(scan_max, SCAN_TILE) + 2);
-    S.wlo1 = c.take<u32>((size_t)S.nt1 + 2 + (S.c1_fill ? cdiv(nb, TQ2) : 0));
-    S.c1_base = c.take<u64>((size_t)S.nt1 + 2);
-    const size_t n1 = S.c1_fill ? nb : 0;
-    S.lo1 = c.take<u32>(n1);
-    S.cnt1 = c.take<u32>(n1);
-    S.off1 = c.take<u64>(n1 + 1);
-    bsums1 = c.take<u64>(cdiv(n1 ? n1 : 1, SCAN_TILE) + 2);
-    const size_t nq2 = ctx->sw.no_uniform ? na : n_max;  // the uniform form may query the other side
-    S.wlo2 = c.take<u32>((size_t)cdiv(nq2, TQ2) + 2);
-    cnt2 = c.take<u32>(nq2);
-    S.cnt2 = cnt2;
-    S.lo2 = c.take<u32>(nq2);
-    S.off2 = c.take<u64>(nq2 + 1);
-    scan_chain = c.take<u64>((size_t)cdiv(nq2, SCAN_TILE) + 4);  // chained scan: a status word per tile + the ticket
-    ctx->plan.irr_a_list = c.take<u32>(na);
-    ctx->plan.irr_b_list = c.take<u32>(nb);
-    irr_cnt = c.take<u32>(nq);
-    ctx->plan.irr_off = c.take<u64>(nq + 1);
-    return c.off;
-  };
-  GIQL_TRY(claim_arena(ctx, st, carve));
-  SortBufs& sa = S.sa;
-  SortBufs& sbb = S.sb;
+  S.nt2 = cdiv(na, RC_NT * RC_ITEMS_C2);
+  GIQL_TRY(claim_arena(ctx, st, [&](char* base) { return carve_inner(ctx, base, na, nb, n_chrom, T.onesweep, W); }));
+  // ---- the two sides.  The caller's output rows follow the sides HERE, for this attempt only: plan.fuse_a / fuse_b
+  // stay in the caller's labels, so an attempt that with_order_fallback repeats binds them afresh.
+  PlanSide A, B;
+  A.side = a, B.side = b;
+  A.n = na, B.n = nb;
+  A.label = 0, B.label = 1;
+  A.sort = &S.sa, B.sort = &S.sb;
+  A.hist = W.hist[0], B.hist = W.hist[1];
+  A.gbase = W.gbase[0], B.gbase = W.gbase[1];
+  A.irr_list = ctx->plan.irr_a_list, B.irr_list = ctx->plan.irr_b_list;
+  A.irr = &ctx->d_meta->irr_a, B.irr = &ctx->d_meta->irr_b;
+  A.len_max = &ctx->d_meta->len_max_a, B.len_max = &ctx->d_meta->len_max_b;
+  A.out_row = ctx->plan.swapped ? ctx->plan.fuse_b : ctx->plan.fuse_a;
+  B.out_row = ctx->plan.swapped ? ctx->plan.fuse_a : ctx->plan.fuse_b;
+
   PrezeroGuard prezero_guard{ctx};  // the helpers skip their own memsets while this plan runs
   ctx->call.first_unstable = true;  // an INNER join needs no order among rows of equal keys: first passes rank by LDS atomics
-  int big_passes_zeroed = 0;
-  if (onesweep) {
-    // the larger side takes at most 4 passes (2 in the three-stage form)
-    big_passes_zeroed = sort_is_local(ctx, n_max) ? local_passes(sort_local_bits(ctx, n_max)) : 4;
-    const size_t big_words = (size_t)big_passes_zeroed * os_pass_stride(ctx, n_max);
-    HIP_TRY(hipMemsetAsync(ctx->arena + zero_off, 0, (zero_end - zero_off) + big_words * sizeof(u32), st));
-    ctx->call.prezeroed = true;
-  }
+  if (T.onesweep) GIQL_TRY(zero_inner_scratch(ctx, st, W, na > nb ? na : nb));
 
-  // The larger side is the one the uniform form prefers as its fixed-length side: its span pass
-  // also counts the digits of its keys (aligned layout), so that, if the form and the layout
-  // hold, it is sorted straight from its raw columns with no linearize pass.  A context that
-  // has planned before asks for it only when its last plan ended that way.
-  const int big_side = nb >= na ? 1 : 0;
-  bool want_hist = onesweep && !ctx->sw.no_span_hist && ctx->sw.os_variant == 0 &&
-                   n_chrom <= MM_HIST_CHROMS;
-  if (want_hist && ctx->guess.spec_valid)  // ... or in the general form without irregular rows (its larger side)
-    want_hist = ctx->guess.spec_aligned && (ctx->guess.spec_form == (big_side ? 1 : 2) ||
-                                      (ctx->guess.spec_form == 0 && ctx->guess.last_no_irr));
-  // ... and the QUERY side of the fixed-length form too (round 3): its (key, end, rid) sort starts from the raw
-  // columns as well (k_onesweep<3, .., KEYGEN>), so neither side has a linearize pass -- on the guesses that the
-  // form and the layout hold AND that the query side has no irregular row (those carry the sentinel key and a
-  // list entry, which only the linearize pass produces): validated at the read-back like the others.
-  const bool want_hist_q = want_hist && ctx->guess.spec_valid && ctx->guess.spec_form == (big_side ? 1 : 2) && ctx->guess.last_no_irr &&
-                           (big_side ? na : nb) > 0;
-  if (want_hist_q) {
-    lb.hist_partial2 = big_side ? hist_a : hist_b;
-    lb.top_partial2 = top_partial_q;
-  }
-  GIQL_TRY(run_spans(ctx, st, *a, *b, n_chrom, lb, want_hist ? big_side : -1, big_side ? hist_b : hist_a));
-  bool aligned = false;
-  // Uniform-length side?  (fixed-length reads: min == max canonical length > 0 over ALL its
-  // rows; a single irregular row makes the minimum 0).
-  // One 100-byte readback; it also surfaces chrom / span errors before the sort.
-  S.uniform = 0;
-  i64 uni_len = 0;
-  // The form is decided from the length ranges the min/max pass just produced.  Reading
-  // them back costs a stream sync in the middle of the plan, so a context that has
-  // planned before SPECULATES on its previous decision and validates it against the same
-  // numbers at the read-back the plan ends with anyway; a wrong guess (the kernels are
-  // memory-safe on any input) repeats the plan once without speculation.
-  auto decide = [&](const DevMeta& m, int& form, i64& len) {
-    const bool ub = m.len_min_b == m.len_max_b && m.len_max_b > 0;
-    const bool ua = m.len_min_a == m.len_max_a && m.len_max_a > 0;
-    form = 0;
-    len = 0;
-    if (ctx->sw.no_uniform) return;  // GIQL_HIP_NO_UNIFORM: the general form whatever the lengths
-    // sort the uniform side without its end; prefer the larger side when both are
-    if (ub && (!ua || nb >= na)) {
-      form = 1;
-      len = m.len_max_b;
-    } else if (ua) {
-      form = 2;
-      len = m.len_max_a;
-    }
-  };
-  bool speculated = false;
-  bool coarse_q = false;  // the query side was sorted without its lowest digit (a guess: no irregular rows)
-  bool keygen_q = false;  // ... and from its raw columns (the same guess)
-  if (onesweep) {
-    if (ctx->guess.spec_valid) {
-      S.uniform = ctx->guess.spec_form;
-      uni_len = ctx->guess.spec_len;
-      aligned = want_hist;  // = ctx->guess.spec_aligned when the form matches
-      speculated = true;
-    } else {
-      GIQL_TRY(read_meta(ctx, st));
-      decide(*ctx->h_meta, S.uniform, uni_len);
-      aligned = want_hist && ctx->h_meta->aligned_ok != 0;
-      // the span is known now, before anything is sorted: the sort form follows the table's real density
-      // already on this first plan.  The span pass counted its digits for the form it expected: if the
-      // larger side leaves the three-stage sort, its high-digits-only histogram is of no use and that side
-      // is linearized (which counts all four digits)
-      const size_t n_big = big_side ? nb : na;
-      const int expected_bits = sort_local_bits(ctx, n_big);
-      ctx->guess.last_span = ctx->h_meta->total_span;
-      // (the high-digits-only histogram serves 16-bit buckets alone: narrower ones sort on bits 8-15 too)
-      if (expected_bits == 16 && sort_local_bits(ctx, n_big) != 16) aligned = false;
-      const int passes_now = sort_is_local(ctx, n_max) ? local_passes(sort_local_bits(ctx, n_max)) : 4;
-      if (big_passes_zeroed < passes_now) {
-        // the larger side takes more global passes than expected: those need zeroed status words too
-        const size_t stride = os_pass_stride(ctx, n_max);
-        HIP_TRY(hipMemsetAsync(os_status + (size_t)big_passes_zeroed * stride, 0,
-                               (size_t)(passes_now - big_passes_zeroed) * stride * sizeof(u32), st));
-        big_passes_zeroed = passes_now;
-      }
-    }
-  }
-  // Sorted inputs: a side the span pass found in (chrom id, start) order (and free of irregular rows) skips its
-  // sort -- from the read-back on a first plan, the previous plan's answer afterwards (validated below)
-  bool pre_a = false, pre_b = false;
-  if (onesweep) {
-    pre_a = speculated ? ctx->guess.spec_sorted[0] : ctx->h_meta->unsorted_a == 0;
-    pre_b = speculated ? ctx->guess.spec_sorted[1] : ctx->h_meta->unsorted_b == 0;
-  }
-  ctx->call.used_sorted[0] = pre_a;
-  ctx->call.used_sorted[1] = pre_b;
-  const bool keygen = aligned && S.uniform == (big_side ? 1 : 2);
-  // General form: the larger side's (key, end, rid) sort can start from the raw columns too, as long as
-  // that side holds no irregular row (those carry the sentinel key, which depends on `end`; the span pass
-  // counted digits of start alone).  Known from the read-back on a first plan, a guess afterwards.
-  const bool keygen_g = aligned && S.uniform == 0 &&
-                        (speculated ? ctx->guess.last_no_irr
-                                    : (big_side ? ctx->h_meta->len_min_b : ctx->h_meta->len_min_a) > 0);
-  const u32* irr_a = &ctx->d_meta->irr_a;
-  const u32* irr_b = &ctx->d_meta->irr_b;
-  if (S.uniform) {
-    // ---- uniform-length form: queries Q (full rows) against points U (starts only)
-    const bool q_is_a = S.uniform == 1;
-    const giql_side& qs_ = q_is_a ? *a : *b;
-    const giql_side& us_ = q_is_a ? *b : *a;
-    SortBufs& sq = q_is_a ? sa : sbb;
-    SortBufs& su = q_is_a ? sbb : sa;
-    const size_t nqr = q_is_a ? na : nb, nu = q_is_a ? nb : na;
-    su.end[0] = su.end[1] = nullptr;  // the uniform side carries (key, rid) only
-    // Fused range count: when U takes the three-stage sort, its bucket sort answers the queries' bounds
-    // (bucket_sort.hip.h) -- as long as no query row is longer than the windows allow for: known from the
-    // read-back on a first plan, the previous plan's answer afterwards (validated below like the other guesses)
-    const int q_len_max = q_is_a ? ctx->h_meta->len_max_a : ctx->h_meta->len_max_b;
-    const bool fuse_cnt = !ctx->sw.no_fuse_count && sort_is_local(ctx, nu) &&
-                          (speculated ? ctx->guess.spec_fuse_len_ok : q_len_max <= (int)BS_FUSE_WCAP);
-    // the query side's chain (linearize + sort) beside the other side's when it is small (the fused count
-    // needs the sorted queries before U's last stage: one stream)
-    // the query side sorted from its raw columns too (its digits were counted in the span pass)
-    keygen_q = keygen && want_hist_q;
-    u32* const hist_q = q_is_a ? hist_a : hist_b;
-    if (keygen) {
-      // the span pass counted U's digits already: fold the per-chromosome top digits onto the
-      // bases, scan, and let the first sort pass build the keys from (chrom, start)
-      Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
-      u32* hist_u = q_is_a ? hist_b : hist_a;
-      if (keygen_q) {  // both sides, one launch each
-        hipLaunchKernelGGL(k_fold_top2, dim3(MM_HIST_CHROMS, 2), dim3(256), 0, st, lb.top_partial, lb.top_partial2,
-                           lb.abase, hist_u, hist_q);
-        hipLaunchKernelGGL(k_digit_offsets2, dim3(4, 2), dim3(256), 0, st, hist_u, hist_q, (u32)LIN_HIST_REPLICAS,
-                           q_is_a ? gbase_b : gbase_a, q_is_a ? gbase_a : gbase_b);
-      } else {
-        hipLaunchKernelGGL(k_fold_top, dim3(MM_HIST_CHROMS), dim3(256), 0, st, lb.top_partial, lb.abase, hist_u);
-        hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, hist_u, (u32)LIN_HIST_REPLICAS,
-                           q_is_a ? gbase_b : gbase_a);
-      }
-      GIQL_TRY(post_launch("digit offsets (span histogram)"));
-    }
-    // (the fork comes AFTER the digit offsets above: the query side's sort on the second stream reads them)
-    SideChain sc(ctx, st, (nqr <= nu && !fuse_cnt) ? nqr : 0);
-    if (!keygen_q) {
-      GIQL_TRY(run_linearize(ctx, sc.stream(), qs_, n_chrom, lb, sq.key[0], sq.end[0],
-                             q_is_a ? ctx->plan.irr_a_list : ctx->plan.irr_b_list, q_is_a ? 0 : 1, 0,
-                             hist_q, q_is_a ? gbase_a : gbase_b));
-    }
-    if (!keygen) {
-      GIQL_TRY(run_linearize(ctx, st, us_, n_chrom, lb, su.key[0], nullptr,
-                             q_is_a ? ctx->plan.irr_b_list : ctx->plan.irr_a_list, q_is_a ? 1 : 0, 0,
-                             q_is_a ? hist_b : hist_a, q_is_a ? gbase_b : gbase_a, nullptr, nullptr,
-                             /*skip_end=*/true));  // uniform => no irregular row: `end` is not read
-    }
-    // The query side's order only serves locality (its bounds are searched per row, its pairs are laid
-    // out by the scan), so its lowest digit stays unsorted: three passes.  Irregular rows would break
-    // that (their sentinel keys must end up LAST, after every row of the top 256-key block): taken
-    // only on the context's guess that there are none, validated with the other guesses below.
-    // With the fused count the queries only have to be grouped by the bucket their key falls into (the windows
-    // of k_bucket_bounds_fused are computed under the same mask and then cover whole query buckets): TWO digits
-    // unsorted, two passes.
-    int q_skip = (speculated && ctx->guess.last_no_irr && !sort_is_local(ctx, nqr)) ? 1 : 0;
-    // (narrower buckets: the queries stay grouped by key >> 8 -- a window under the 16-bit mask would span 2-8 buckets)
-    const int wb_u = sort_local_bits(ctx, nu);
-    if (q_skip && fuse_cnt && wb_u == 16) q_skip = 2;
-    coarse_q = q_skip != 0;
-    const u32 q_mask = q_skip == 2 ? 0xFFFF0000u : (q_skip == 1 ? 0xFFFFFF00u : 0xFFFFFFFFu);
-    // (the smaller side's passes use the smaller status buffer: both were zeroed up front, neither is reused)
-    u32* const stat_q = nqr <= nu ? os_status2 : os_status;
-    u32* const stat_u = nqr <= nu ? os_status : os_status2;
-    GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sq, (u32)nqr, q_is_a ? gbase_a : gbase_b,
-                               stat_q, false, keygen_q ? &qs_ : nullptr, lb.abase, q_skip, nullptr,
-                               q_is_a ? pre_a : pre_b));
-    // One-call join (giql_hip_inner_join_dev): the caller's buffers are here and everything about this plan is a
-    // guess that has held so far (same form as last time, no irregular rows), so the fill is launched inside the
-    // plan, with a grid bounded by the capacity and the true count read on the device.
-    constexpr u32 T2 = FILL_NT * FILL_ITEMS_C2;
-    static_assert((T2 & (T2 - 1)) == 0, "fill tiles are a power of two (k_scan_chain_diff shifts)");
-    const u64 nt_cap64 = (ctx->plan.fuse_cap + T2 - 1) / T2;
-    const bool early_fill = ctx->plan.fuse_a && speculated && ctx->guess.last_no_irr && ctx->plan.fuse_cap > 0 &&
-                            nt_cap64 <= 0x7FFFFFF0ull && ((size_t)nt_cap64 + 2) * sizeof(u32) <= ctx->part_cap;
-    bool part_done = false;  // the scan wrote the fill's partition
-    // ... and, when the other side's bucket stage answers the bounds anyway, the pairs are written right there
-    // (bucket_sort.hip.h, FUSE == 2) -- as long as the query windows stay well inside what a block holds in
-    // registers: a window covers the query buckets (coarsely grouped: whole 65536-key buckets) that a bucket's
-    // reach -- its own 65536 keys, the fixed length above it, the longest query below it -- touches
-    const double win_keys = q_skip == 2 ? 3.0 * 65536.0 + (double)uni_len
-                                        : (double)(1u << (wb_u ? wb_u : 16)) + 512.0 + (double)uni_len +
-                                              (double)(q_len_max > 0 ? q_len_max : 0);
-    const bool join_in_buckets = fuse_cnt && ctx->plan.fuse_a && speculated && ctx->guess.last_no_irr &&
-                                 ctx->plan.fuse_cap > 0 && ctx->guess.last_span > 0 &&
-                                 (double)nqr * win_keys / (double)ctx->guess.last_span <= 0.75 * (double)BJ_WCAP;
-    FuseCount fc;
-    if (fuse_cnt) {
-      if (join_in_buckets) {
-        fc.join = true;
-        fc.dev.qrid = sq.rid[0];
-        fc.dev.row_q = q_is_a ? ctx->plan.fuse_a : ctx->plan.fuse_b;
-        fc.dev.row_s = q_is_a ? ctx->plan.fuse_b : ctx->plan.fuse_a;
-        fc.dev.cap = ctx->plan.fuse_cap;
-        fc.dev.cursor = reinterpret_cast<unsigned long long*>(&ctx->d_meta->n_out);  // zeroed by the span pass
-      }
-      fc.zero_ptr = reinterpret_cast<u32*>(scan_chain);
-      fc.zero_words = (u32)(2 * (cdiv(nqr, SC_TILE) + 2));
-      fc.dev.qkey = sq.key[0];
-      fc.dev.qend = sq.end[0];
-      fc.dev.qwin = ctx->bucket_qwin;
-      fc.dev.lo_out = S.lo2;
-      fc.dev.hi_out = cnt2;  // the scan below turns the upper bounds into counts in place
-      fc.dev.lo_off = 1 - uni_len;  // u.start in [q.start - L + 1, q.end)
-      fc.nq_total = (u32)nqr;
-      fc.irr_q = q_is_a ? irr_a : irr_b;
-      fc.gbq3 = (q_is_a ? gbase_a : gbase_b) + 3 * OS_BINS;
-      fc.key_mask = q_mask;
-      fc.len_max_q = q_is_a ? &ctx->d_meta->len_max_a : &ctx->d_meta->len_max_b;
-    }
-    GIQL_TRY(run_sort_onesweep(ctx, st, su, (u32)nu, q_is_a ? gbase_b : gbase_a, stat_u, false,
-                               keygen ? &us_ : nullptr, lb.abase, 0, fuse_cnt ? &fc : nullptr,
-                               q_is_a ? pre_b : pre_a));
-    GIQL_TRY(sc.join());
-    constexpr u32 TQ = RC_NT * RC_ITEMS_C2;
-    S.nt2 = cdiv(nqr, TQ);
-    if (ctx->call.bucket_join) {
-      // the pairs are out already, counted in DevMeta::n_out
-    } else if (ctx->call.count_fused) {
-      u32 log2_t2 = 0;
-      while ((1u << log2_t2) < T2) log2_t2++;
-      GIQL_TRY(run_scan_chain(ctx, st, GIQL_PH_SCAN, cnt2, S.lo2, nqr, q_is_a ? irr_a : irr_b, S.off2, scan_chain,
-                              &ctx->d_meta->n_out, early_fill ? ctx->part : nullptr, log2_t2, (u32)nt_cap64 + 1));
-      part_done = early_fill;
-    } else {
-    {
-      Phase ph(ctx, st, GIQL_PH_COUNT, 2);
-      const u32* irr_q = q_is_a ? irr_a : irr_b;
-      const u32* irr_u = q_is_a ? irr_b : irr_a;
-      const i64 lo_off = 1 - uni_len;  // u.start in [q.start - L + 1, q.end)
-      hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)S.nt2 + 1, 256)), dim3(256), 0, st,
-                         sq.key[0], (u32)nqr, irr_q, su.key[0], (u32)nu, irr_u, lo_off, TQ, S.nt2,
-                         S.wlo2, q_mask);
-      hipLaunchKernelGGL((k_range_count<RC_ITEMS_C2, RC_LDS_CAP>), dim3(S.nt2), dim3(RC_NT), 0, st,
-                         sq.key[0], sq.end[0], (u32)nqr, irr_q, su.key[0], (u32)nu, irr_u, lo_off,
-                         S.wlo2, S.lo2, cnt2);
-      GIQL_TRY(post_launch("range count (uniform)"));
-    }
-    GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, cnt2, nqr, S.off2, bsums, S.off2 + nqr, &ctx->d_meta->n_out));
-    }
-    bool fused = false;
-    {
-      // The early fill: no stream sync between plan and fill.  Validated below; a wrong guess leaves the
-      // buffers to the ordinary fill.
-      if (ctx->call.bucket_join) {
-        fused = true;
-      } else if (early_fill) {
-        const u32 nt_cap = (u32)nt_cap64;
-        const u32* qrid = q_is_a ? sa.rid[0] : sbb.rid[0];
-        const u32* srid = q_is_a ? sbb.rid[0] : sa.rid[0];
-        int32_t* rq = q_is_a ? ctx->plan.fuse_a : ctx->plan.fuse_b;
-        int32_t* rs = q_is_a ? ctx->plan.fuse_b : ctx->plan.fuse_a;
-        if (!part_done) {
-          Phase ph(ctx, st, GIQL_PH_PARTITION);
-          hipLaunchKernelGGL(k_partition, dim3(cdiv((u64)nt_cap + 1, 256)), dim3(256), 0, st, S.off2,
-                             (u32)nqr, (u64)0, T2, nt_cap, ctx->part, (const u64*)(S.off2 + nqr), ctx->plan.fuse_cap);
-        }
-        {
-          Phase ph(ctx, st, GIQL_PH_FILL);
-          hipLaunchKernelGGL((k_fill<FILL_ITEMS_C2>), dim3(nt_cap), dim3(FILL_NT), 0, st, S.off2, S.lo2, qrid,
-                             (u32)nqr, srid, ctx->part, (u64)0, (u64)0, rq, rs, (const u64*)(S.off2 + nqr), ctx->plan.fuse_cap);
-        }
-        GIQL_TRY(post_launch("fused fill"));
-        fused = true;
-      }
-    }
-    GIQL_TRY(read_meta(ctx, st));
-    ctx->plan.n_c1 = 0;
-    ctx->plan.n_reg = ctx->h_meta->n_out;
-    // the early fill stands only if every guess held and the pairs fitted
-    ctx->plan.fuse_done = fused && ctx->h_meta->irr_a + ctx->h_meta->irr_b == 0 && ctx->plan.n_reg <= ctx->plan.fuse_cap;
-    if (ctx->call.bucket_join) ctx->stats.phase_bytes[GIQL_PH_SORT_LOCAL] += (int64_t)8 * (int64_t)ctx->plan.n_reg;  // the pairs
+  GIQL_TRY(begin_attempt(ctx, st, A, B, n_chrom, W, T));
+  S.uniform = T.form;
+  ctx->call.used_sorted[0] = T.presorted[0];
+  ctx->call.used_sorted[1] = T.presorted[1];
+  if (T.form == 1) {
+    GIQL_TRY(plan_uniform(ctx, st, n_chrom, /*Q=*/A, /*U=*/B, W, T));
+  } else if (T.form == 2) {
+    GIQL_TRY(plan_uniform(ctx, st, n_chrom, /*Q=*/B, /*U=*/A, W, T));
   } else {
-  // The join itself in B's bucket stage (bucket_sort.hip.h, FUSE == 3): one-call form, on the context's guesses (the
-  // general form again, no irregular row, no row longer than the windows allow for), B the three-stage side, the A
-  // rows -- fully sorted -- sparse enough for a bucket's window to stay in a block's registers.
-  const bool general_join = onesweep && ctx->plan.fuse_a && speculated && ctx->guess.last_no_irr &&
-                            ctx->plan.fuse_cap > 0 && nb >= na && sort_is_local(ctx, nb) && ctx->guess.spec_fuse_len_ok &&
-                            ctx->guess.last_span > 0 &&
-                            // (a window = the A rows within the bucket's 65536 keys + the longest rows of either side: the
-                            // previous plan's maxima, like the guess they validate)
-                            (double)na * ((double)(1u << (sort_local_bits(ctx, nb) ? sort_local_bits(ctx, nb) : 16)) +
-                                          (double)ctx->h_meta->len_max_a + (double)ctx->h_meta->len_max_b) /
-                                    (double)ctx->guess.last_span <= 0.5 * (double)BJ_WCAP;
-  // the smaller side's chain (linearize + sort) beside the larger side's when it is small (not in the form above:
-  // B's last stage reads the sorted A)
-  SideChain sc(ctx, st, (onesweep && !general_join) ? (na < nb ? na : nb) : 0);
-  const bool a_small = na < nb;
-  hipStream_t st_a = a_small ? sc.stream() : st, st_b = a_small ? st : sc.stream();
-  const bool kg_a = keygen_g && !big_side, kg_b = keygen_g && big_side;
-  for (int k = 0; k < 2; k++) {
-    const bool is_b = k == 1;
-    hipStream_t stk = is_b ? st_b : st_a;
-    if (is_b ? kg_b : kg_a) {
-      // the span pass counted this side's digits: fold the top ones onto the bases and scan (no linearize pass)
-      Phase ph(ctx, stk, GIQL_PH_LINEARIZE, 2);
-      u32* hist_k = is_b ? hist_b : hist_a;
-      hipLaunchKernelGGL(k_fold_top, dim3(MM_HIST_CHROMS), dim3(256), 0, stk, lb.top_partial, lb.abase, hist_k);
-      hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, stk, hist_k, (u32)LIN_HIST_REPLICAS,
-                         is_b ? gbase_b : gbase_a);
-      GIQL_TRY(post_launch("digit offsets (span histogram, general form)"));
-    } else if (is_b) {
-      GIQL_TRY(run_linearize(ctx, st_b, *b, n_chrom, lb, sbb.key[0], sbb.end[0], ctx->plan.irr_b_list, 1, 0,
-                             hist_b, gbase_b));
-    } else {
-      GIQL_TRY(run_linearize(ctx, st_a, *a, n_chrom, lb, sa.key[0], sa.end[0], ctx->plan.irr_a_list, 0, 0,
-                             hist_a, gbase_a));
-    }
+    GIQL_TRY(plan_general(ctx, st, n_chrom, A, B, W, T));
   }
-  if (onesweep) {
-    GIQL_TRY(run_sort_onesweep(ctx, st_a, sa, (u32)na, gbase_a, a_small ? os_status2 : os_status,
-                               false, kg_a ? a : nullptr, lb.abase, 0, nullptr, pre_a));
-    FuseCount fg;
-    if (general_join) {
-      fg.join = fg.general = true;
-      fg.zero_ptr = reinterpret_cast<u32*>(scan_chain);
-      fg.zero_words = 0;
-      fg.dev.qkey = sa.key[0];
-      fg.dev.qend = sa.end[0];
-      fg.dev.qrid = sa.rid[0];
-      fg.dev.qwin = ctx->bucket_qwin;
-      fg.dev.lo_out = fg.dev.hi_out = nullptr;
-      fg.dev.lo_off = 1;  // class 2: b.start in (a.start, a.end)
-      fg.dev.row_q = ctx->plan.fuse_a;
-      fg.dev.row_s = ctx->plan.fuse_b;
-      fg.dev.cap = ctx->plan.fuse_cap;
-      fg.dev.cursor = reinterpret_cast<unsigned long long*>(&ctx->d_meta->n_out);  // zeroed by the span pass
-      fg.nq_total = (u32)na;
-      fg.irr_q = irr_a;
-      fg.gbq3 = gbase_a + 3 * OS_BINS;
-      fg.key_mask = 0xFFFFFFFFu;
-      fg.len_max_q = &ctx->d_meta->len_max_a;
-      fg.len_max_u = &ctx->d_meta->len_max_b;
-    }
-    GIQL_TRY(run_sort_onesweep(ctx, st_b, sbb, (u32)nb, gbase_b, a_small ? os_status : os_status2,
-                               false, kg_b ? b : nullptr, lb.abase, 0, general_join ? &fg : nullptr, pre_b));
-    GIQL_TRY(sc.join());
-  } else {
-    GIQL_TRY(run_sort(ctx, st, sa, (u32)na, tile_hist, bsums));
-    GIQL_TRY(run_sort(ctx, st, sbb, (u32)nb, tile_hist, bsums));
-  }
-  if (ctx->call.bucket_join) {
-    // the pairs are out already, counted in DevMeta::n_out
-    GIQL_TRY(read_meta(ctx, st));
-    ctx->plan.n_c1 = 0;
-    ctx->plan.n_reg = ctx->h_meta->n_out;
-    ctx->plan.fuse_done = ctx->h_meta->irr_a + ctx->h_meta->irr_b == 0 && ctx->plan.n_reg <= ctx->plan.fuse_cap;
-    ctx->stats.phase_bytes[GIQL_PH_SORT_LOCAL] += (int64_t)8 * (int64_t)ctx->plan.n_reg;  // the pairs
-  } else {
-  // class 1 (count + the scan of its block totals) runs beside class 2 when both sides are small
-  SideChain sc1(ctx, st, onesweep ? (na < nb ? na : nb) : 0);
-  hipStream_t st1 = sc1.stream();
-  {
-    Phase ph(ctx, st, GIQL_PH_COUNT, 4);
-    // class 1: queries = sorted B, points = sorted A starts, range [b.start, b.end);
-    // only one total per block is kept (see k_c1_count)
-    if (S.c1_fill) {
-      const u32 nt1r = cdiv(nb, TQ2);
-      hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)nt1r + 1, 256)), dim3(256), 0, st1,
-                         sbb.key[0], (u32)nb, irr_b, sa.key[0], (u32)na, irr_a, (i64)0, TQ2, nt1r, S.wlo1);
-      hipLaunchKernelGGL((k_range_count<RC_ITEMS_C2, RC_LDS_CAP>), dim3(nt1r), dim3(RC_NT), 0, st1,
-                         sbb.key[0], sbb.end[0], (u32)nb, irr_b, sa.key[0], (u32)na, irr_a, (i64)0, S.wlo1,
-                         S.lo1, S.cnt1);
-    } else {
-    hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)S.nt1 + 1, 256)), dim3(256), 0, st1,
-                       sbb.key[0], (u32)nb, irr_b, sa.key[0], (u32)na, irr_a, (i64)0, c1_tq, S.nt1,
-                       S.wlo1);
-    if (S.c1_items == 2)
-      hipLaunchKernelGGL(k_c1_count<2>, dim3(S.nt1), dim3(C1_NT), 0, st1, sbb.key[0], sbb.end[0], (u32)nb,
-                         irr_b, sa.key[0], (u32)na, irr_a, S.wlo1, S.c1_base);
-    else
-      hipLaunchKernelGGL(k_c1_count<C1_ITEMS_MAX>, dim3(S.nt1), dim3(C1_NT), 0, st1, sbb.key[0], sbb.end[0], (u32)nb,
-                         irr_b, sa.key[0], (u32)na, irr_a, S.wlo1, S.c1_base);
-    // class-1 block totals -> block bases (one block, in place); total -> n_out_c1
-    hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, st1, S.c1_base, S.nt1,
-                       &ctx->d_meta->n_out_c1);
-    }
-    // class 2: queries = sorted A, points = sorted B starts, range (a.start, a.end)
-    hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)S.nt2 + 1, 256)), dim3(256), 0, st,
-                       sa.key[0], (u32)na, irr_a, sbb.key[0], (u32)nb, irr_b, (i64)1, TQ2, S.nt2, S.wlo2);
-    hipLaunchKernelGGL((k_range_count<RC_ITEMS_C2, RC_LDS_CAP>), dim3(S.nt2), dim3(RC_NT), 0, st,
-                       sa.key[0], sa.end[0], (u32)na, irr_a, sbb.key[0], (u32)nb, irr_b, (i64)1, S.wlo2,
-                       S.lo2, cnt2);
-    GIQL_TRY(post_launch("range count"));
-  }
-  if (S.c1_fill) {
-    GIQL_TRY(run_scan<u64>(ctx, st1, GIQL_PH_SCAN, S.cnt1, nb, S.off1, bsums1, S.off1 + nb, &ctx->d_meta->n_out_c1));
-  }
-  GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, cnt2, na, S.off2, bsums, S.off2 + na, &ctx->d_meta->n_out));
-  GIQL_TRY(sc1.join());
-  GIQL_TRY(read_meta(ctx, st));
-  ctx->plan.n_c1 = ctx->h_meta->n_out_c1;
-  ctx->plan.n_reg = ctx->h_meta->n_out + ctx->plan.n_c1;
-  }
-  }
-  if (onesweep) {
-    int form;
-    i64 len;
-    decide(*ctx->h_meta, form, len);
-    const bool aligned_now = ctx->h_meta->aligned_ok != 0;
-    const bool coarse_wrong = coarse_q && ctx->h_meta->irr_a + ctx->h_meta->irr_b > 0;
-    // a side sorted from its raw columns in the general form must hold no irregular row (its length
-    // range starts above 0); such a row was keyed as if regular, and never listed
-    const bool keygen_wrong = (keygen_g && (big_side ? ctx->h_meta->len_min_b : ctx->h_meta->len_min_a) <= 0) ||
-                              (keygen_q && (big_side ? ctx->h_meta->len_min_a : ctx->h_meta->len_min_b) <= 0);
-    if (keygen_wrong) ctx->guess.last_no_irr = false;
-    // the fused count's windows allow for query rows up to BS_FUSE_WCAP long (the query side of the form just decided)
-    const int q_len_now = form == 1 ? ctx->h_meta->len_max_a : ctx->h_meta->len_max_b;
-    const bool fuse_len_ok_now = form != 0 ? q_len_now <= (int)BS_FUSE_WCAP
-                                           : (ctx->h_meta->len_max_a <= (int)BS_FUSE_WCAP &&
-                                              ctx->h_meta->len_max_b <= (int)BS_FUSE_WCAP);  // (general form: both sides' rows)
-    const bool fuse_wrong = ctx->call.count_fused && !fuse_len_ok_now;
-    ctx->guess.spec_fuse_len_ok = fuse_len_ok_now;
-    // a side taken as sorted must be: an out-of-order row was left where it was
-    const bool sorted_wrong = (ctx->call.used_sorted[0] && ctx->h_meta->unsorted_a != 0) ||
-                              (ctx->call.used_sorted[1] && ctx->h_meta->unsorted_b != 0);
-    ctx->guess.spec_sorted[0] = ctx->h_meta->unsorted_a == 0;
-    ctx->guess.spec_sorted[1] = ctx->h_meta->unsorted_b == 0;
-    // a join in the bucket stage that did not stand (the pairs did not fit the caller's buffers, or a guess failed)
-    // left no plan arrays for the ordinary fill: plan again, unspeculated -- which never takes that form
-    const bool join_wrong = ctx->call.bucket_join && !ctx->plan.fuse_done;
-    if (speculated && (form != S.uniform || len != uni_len || (want_hist && !aligned_now) || coarse_wrong || keygen_wrong || fuse_wrong || sorted_wrong || join_wrong)) {
-      ctx->guess.spec_valid = false;  // wrong guess: plan again from the numbers just read
-      ctx->guess.spec_misses++;
-      ctx->plan.fuse_done = false;
-      return GIQL_STATUS_GUESS_MISSED;
-    }
-    ctx->guess.spec_valid = true;
-    ctx->guess.spec_form = form;
-    ctx->guess.spec_len = len;
-    // the layout is probed only when the span histogram ran; a plan that skipped it for a
-    // form mismatch leaves the last answer (a later form change re-plans unspeculated anyway)
-    if (want_hist) ctx->guess.spec_aligned = aligned_now;
-  }
+  if (!settle_guesses(ctx, T, na, nb)) return GIQL_STATUS_GUESS_MISSED;
   ctx->stats.n_irregular_a = ctx->h_meta->irr_a;
   ctx->stats.n_irregular_b = ctx->h_meta->irr_b;
   ctx->stats.span = (int64_t)ctx->h_meta->total_span;
-  ctx->guess.last_span = ctx->h_meta->total_span;
-  ctx->guess.last_no_irr = ctx->h_meta->irr_a + ctx->h_meta->irr_b == 0;
 
-  if (ctx->h_meta->irr_a + ctx->h_meta->irr_b > 0) {
-    {
-      Phase ph(ctx, st, GIQL_PH_IRREGULAR);
-      hipLaunchKernelGGL(k_irr_count, dim3(cdiv(nq, 256)), dim3(256), 0, st, view_of(*a), view_of(*b),
-                         ctx->plan.irr_a_list, ctx->plan.irr_b_list, ctx->d_meta, irr_cnt);
-      GIQL_TRY(post_launch("irregular count"));
-    }
-    GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_IRREGULAR, irr_cnt, nq, ctx->plan.irr_off, bsums,
-                           ctx->plan.irr_off + nq));
-    HIP_TRY(hipMemcpyAsync(&ctx->d_meta->n_out_irr, ctx->plan.irr_off + nq, sizeof(u64),
-                           hipMemcpyDeviceToDevice, st));
-    GIQL_TRY(read_meta(ctx, st));
-    ctx->plan.n_irr = ctx->h_meta->n_out_irr;
-  }
+  if (ctx->h_meta->irr_a + ctx->h_meta->irr_b > 0) GIQL_TRY(plan_irregular(ctx, st, A, B, W));
   collect_spans(ctx);
   // which form ran: 0 general, 1 B uniform, 2 A uniform; bit 4: the fixed-length side was sorted
   // from its raw columns (histogram in the span pass, no linearize pass)
-  ctx->stats.reserved = S.uniform | ((keygen || keygen_g) ? 0x10 : 0);
+  ctx->stats.reserved = S.uniform | ((T.keygen_u || T.keygen_g) ? 0x10 : 0);
   ctx->stats.n_out = (int64_t)(ctx->plan.n_reg + ctx->plan.n_irr);
   *n_pairs = (int64_t)(ctx->plan.n_reg + ctx->plan.n_irr);
   ctx->plan.planned = true;
-  ctx->plan.plan_is_join = ctx->call.bucket_join;
+  ctx->plan.plan_is_join = T.bucket_join();
   return GIQL_OK;
 }
 
@@ -1861,7 +1993,8 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
 // sides' roles are not symmetric in cost (10M x 100M reads: 4.4 ms; the same tables as (100M, 10M):
 // 12.9 ms before this swap).  INTERSECTS is symmetric, so a call with the larger table first is planned
 // with the sides exchanged and everything that leaves the context (pairs, stats, the exported plan) is
-// labelled back; only the order of the pairs -- never part of the contract -- differs.
+// labelled back; only the order of the pairs -- never part of the contract -- differs.  (The offered output
+// buffers follow the sides where inner_plan_core binds them.)
 static int giql_hip_inner_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b,
                                         int32_t n_chrom, void* stream, int64_t* n_pairs) {
   if (!ctx || !n_pairs) return set_err(GIQL_ERR_INVALID, "ctx/n_pairs is NULL");
@@ -1869,16 +2002,7 @@ static int giql_hip_inner_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* a, c
   const bool swap = a->n > b->n;
   ctx->plan.swapped = swap;
   if (!swap) return inner_plan_core(ctx, a, b, n_chrom, stream, n_pairs);
-  // The offered output buffers follow the sides for the duration of THIS attempt only: with_order_fallback
-  // may run this function again (a missed guess, a resort, a look-back timeout), and an exchange left in place would then
-  // be undone by the second one -- the retry's early fill writing B ids into row_a.
-  int32_t* const fa = ctx->plan.fuse_a;
-  int32_t* const fb = ctx->plan.fuse_b;
-  ctx->plan.fuse_a = fb;
-  ctx->plan.fuse_b = fa;
   const int rc = inner_plan_core(ctx, b, a, n_chrom, stream, n_pairs);
-  ctx->plan.fuse_a = fa;
-  ctx->plan.fuse_b = fb;
   // stats in the caller's labels
   giql_hip_stats& stt = ctx->stats;
   const int64_t tn = stt.n_a;
@@ -1923,9 +2047,15 @@ int giql_hip_inner_fill_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, i
   const u32* irr_b = &ctx->d_meta->irr_b;
   const u64 p1 = ctx->plan.n_c1, p2 = ctx->plan.n_reg - ctx->plan.n_c1;
   // who plays "query" in the range-fill: A rows (general class 2, or B uniform),
-  // or B rows (A uniform)
-  const bool q_is_a = S.uniform != 2;
-  const u32 nq2 = q_is_a ? ctx->plan.n_a : ctx->plan.n_b;
+  // or B rows (A uniform) -- bound once, like the plan's PlanSides
+  struct FillSide {
+    const u32* rid;
+    u32 n;
+    int32_t* row;
+  };
+  const FillSide fa{S.sa.rid[0], ctx->plan.n_a, row_a}, fb{S.sb.rid[0], ctx->plan.n_b, row_b};
+  const FillSide& Q = S.uniform != 2 ? fa : fb;
+  const FillSide& U = S.uniform != 2 ? fb : fa;
   u32 nt2 = 0, nt1f = 0;
   const bool c1_fill = S.uniform == 0 && S.c1_fill && p1 > 0;
   if (p2 > 0 || c1_fill) {
@@ -1938,7 +2068,7 @@ int giql_hip_inner_fill_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, i
     GIQL_TRY(grow_part(ctx, part_need, st));
     Phase ph(ctx, st, GIQL_PH_PARTITION);
     if (p2 > 0)
-      hipLaunchKernelGGL(k_partition, dim3(cdiv((u64)nt2 + 1, 256)), dim3(256), 0, st, S.off2, nq2,
+      hipLaunchKernelGGL(k_partition, dim3(cdiv((u64)nt2 + 1, 256)), dim3(256), 0, st, S.off2, Q.n,
                          (u64)0, T2, nt2, ctx->part);
     if (c1_fill)  // class 1's tiles behind class 2's in the partition array
       hipLaunchKernelGGL(k_partition, dim3(cdiv((u64)nt1f + 1, 256)), dim3(256), 0, st, S.off1, ctx->plan.n_b,
@@ -1959,14 +2089,9 @@ int giql_hip_inner_fill_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, i
                          S.sb.rid[0], ctx->plan.n_b, irr_b, S.sa.key[0], S.sa.rid[0], ctx->plan.n_a, irr_a,
                          S.wlo1, S.c1_base, (u64)0, row_b, row_a);
     // range fill -> outputs [p1, p1 + p2)
-    if (p2 > 0) {
-      const u32* qrid = q_is_a ? S.sa.rid[0] : S.sb.rid[0];
-      const u32* srid = q_is_a ? S.sb.rid[0] : S.sa.rid[0];
-      int32_t* rq = (q_is_a ? row_a : row_b) + p1;
-      int32_t* rs = (q_is_a ? row_b : row_a) + p1;
-      hipLaunchKernelGGL((k_fill<FILL_ITEMS_C2>), dim3(nt2), dim3(FILL_NT), 0, st, S.off2, S.lo2, qrid,
-                         nq2, srid, ctx->part, (u64)0, p2, rq, rs);
-    }
+    if (p2 > 0)
+      hipLaunchKernelGGL((k_fill<FILL_ITEMS_C2>), dim3(nt2), dim3(FILL_NT), 0, st, S.off2, S.lo2, Q.rid,
+                         Q.n, U.rid, ctx->part, (u64)0, p2, Q.row + p1, U.row + p1);
     GIQL_TRY(post_launch("fill"));
   }
   if (ctx->plan.n_irr > 0) {
@@ -2133,12 +2258,7 @@ int giql_hip_index_create_dev(giql_hip_ctx* ctx, const giql_side* side, int32_t 
   if (idx->general) HIP_TRY(hipMalloc((void**)&idx->end, n * sizeof(u32)));
   HIP_TRY(hipMalloc((void**)&idx->small, (1024 + (size_t)n_chrom + 1) * sizeof(u32)));
   idx->bytes = n * sizeof(u32) * (idx->general ? 3 : 2) + (1024 + (size_t)n_chrom + 1) * sizeof(u32);
-  {
-    Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
-    hipLaunchKernelGGL(k_fold_top, dim3(MM_HIST_CHROMS), dim3(256), 0, st, lb.top_partial, lb.abase, hist);
-    hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, hist, (u32)LIN_HIST_REPLICAS, gbase);
-    GIQL_TRY(post_launch("digit offsets (index)"));
-  }
+  GIQL_TRY(span_digit_offsets(ctx, st, lb, hist, gbase, nullptr, nullptr, "digit offsets (index)"));
   SortBufs sb = scratch;
   sb.key[0] = idx->key;
   sb.rid[0] = idx->rid;
@@ -2237,32 +2357,13 @@ int giql_hip_inner_join_indexed_dev(giql_hip_ctx* ctx, const giql_hip_index* idx
   // window's keys against the bucket rows and wants them fully sorted.
   // (narrower buckets: grouped by key >> 8, three passes)
   const int q_skip = idx->general ? 0 : (idx->wbits == 16 ? 2 : 1);
-  const u32 q_mask = q_skip == 2 ? 0xFFFF0000u : (q_skip == 1 ? 0xFFFFFF00u : 0xFFFFFFFFu);
   {
     ForceLocal global_only{ctx, -1};  // a's own sort: global passes only (its bucket stage would reuse the context's boundary arrays)
     GIQL_TRY(run_sort_onesweep(ctx, st, sa, (u32)na, gbase, status, false, nullptr, nullptr, q_skip, nullptr, false));
   }
-  FuseCount fc;
-  fc.join = true;
-  fc.general = idx->general;
-  fc.zero_ptr = flags + 8;
-  fc.zero_words = 0;
-  fc.dev.qkey = sa.key[0];
-  fc.dev.qend = sa.end[0];
-  fc.dev.qrid = sa.rid[0];
-  fc.dev.qwin = ctx->bucket_qwin;
-  fc.dev.lo_out = fc.dev.hi_out = nullptr;
-  fc.dev.lo_off = idx->general ? 1 : 1 - idx->uni_len;
-  fc.dev.row_q = row_a;
-  fc.dev.row_s = row_idx;
-  fc.dev.cap = (u64)capacity;
-  fc.dev.cursor = reinterpret_cast<unsigned long long*>(&ctx->d_meta->n_out);  // zeroed by k_init_minmax
-  fc.nq_total = (u32)na;
-  fc.irr_q = dead;
-  fc.gbq3 = gbase + 3 * OS_BINS;
-  fc.key_mask = q_mask;
-  fc.len_max_q = len_max_q;
-  fc.len_max_u = idx->general ? len_max_u : nullptr;
+  const FuseTarget out{row_a, row_idx, (u64)capacity};
+  const FuseCount fc = make_fuse_count(ctx, FuseQuery{&sa, na, dead, gbase, len_max_q}, idx->general ? 1 : 1 - idx->uni_len,
+                                       skip_mask(q_skip), &out, idx->general, len_max_u, flags + 8);
   SortBufs sb = sq;
   sb.key[0] = idx->key;
   sb.rid[0] = idx->rid;
