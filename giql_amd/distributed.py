@@ -426,6 +426,56 @@ def sharded_inner_join_compact(a, b, n_chrom: int, local_plan: Callable, expand:
     return (torch.cat(out_a) if out_a else z), (torch.cat(out_b) if out_b else z.clone())
 
 
+def hip_local_plan(engine):
+    """``local_plan`` of :func:`sharded_inner_join_compact` backed by a :class:`giql_amd.engine.HipEngine`:
+    plan, sizes, export.  The row ids are shard-local unless ``rid_add_a`` / ``rid_add_b`` are given (a shard that
+    is a contiguous row range of its table: the first global row of the range).  ``None`` when the plan has no
+    compact form (``GIQL_ERR_STATE`` from the export); the empty plan for an empty shard."""
+    import torch
+
+    from . import _lib
+    from .engine import DeviceSide
+
+    def run(ca, sa, ea, offs_a, cb, sb, eb, offs_b, n_chrom, rid_add_a=0, rid_add_b=0):
+        i32 = dict(dtype=torch.int32, device=engine.device)
+        if len(ca) == 0 or len(cb) == 0:
+            z = torch.zeros(0, **i32)
+            return True, z, z.clone(), z.clone(), z.clone(), 0
+        a = DeviceSide.from_numpy(ca, sa, ea, device=engine.device)
+        a.start_off, a.end_off = offs_a
+        b = DeviceSide.from_numpy(cb, sb, eb, device=engine.device)
+        b.start_off, b.end_off = offs_b
+        n_pairs = engine.inner_plan(a, b, n_chrom)
+        try:
+            _q_is_a, n_q, n_s = engine.plan_sizes()
+            q_rid, lo, cnt = (torch.empty(n_q, **i32) for _ in range(3))
+            s_rid = torch.empty(n_s, **i32)
+            q_is_a, _, _ = engine.plan_export(q_rid, lo, cnt, s_rid, rid_add_a=rid_add_a, rid_add_b=rid_add_b)
+        except _lib.GiqlHipError as exc:
+            if exc.code != _lib.GIQL_ERR_STATE:
+                raise
+            return None
+        return q_is_a, q_rid, lo, cnt, s_rid, n_pairs
+
+    return run
+
+
+def hip_expand(engine):
+    """``expand`` of :func:`sharded_inner_join_compact` backed by a :class:`giql_amd.engine.HipEngine`
+    (``giql_hip_fill_from_plan_dev`` with the pair count known: no read-back)."""
+    import torch
+
+    def run(q_rid, lo, cnt, s_rid, n_pairs):
+        i32 = dict(dtype=torch.int32, device=engine.device)
+        row_q, row_s = torch.empty(int(n_pairs), **i32), torch.empty(int(n_pairs), **i32)
+        if n_pairs:
+            q_rid, lo, cnt, s_rid = (x.to(**i32).contiguous() for x in (q_rid, lo, cnt, s_rid))
+            engine.fill_from_plan(q_rid, lo, cnt, s_rid, row_q, row_s, n_pairs_expected=int(n_pairs))
+        return row_q, row_s
+
+    return run
+
+
 # ------------------------------------------------------------------ the per-row operators
 ROW_OPS = ("semi", "anti", "count", "nearest")
 

@@ -15,6 +15,8 @@ torch = pytest.importorskip("torch")
 import torch.distributed as dist  # noqa: E402
 import torch.multiprocessing as mp  # noqa: E402
 
+from _plans import _np_expand  # noqa: E402  (the numpy stand-in for giql_hip_fill_from_plan_dev)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -119,17 +121,6 @@ def _np_plan(ca, sa, ea, offs_a, cb, sb, eb, offs_b, n_chrom):
     cnt = np.maximum(hi - lo, 0)
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.int32))
     return True, t(np.arange(len(ca))), t(lo), t(cnt), t(order), int(cnt.sum())
-
-
-def _np_expand(q_rid, lo, cnt, s_rid, n_pairs):
-    """numpy stand-in for giql_hip_fill_from_plan_dev."""
-    c = cnt.numpy().astype(np.int64)
-    row_q = np.repeat(q_rid.numpy(), c)
-    start = np.repeat(lo.numpy().astype(np.int64), c)
-    within = np.arange(int(c.sum())) - np.repeat(np.cumsum(c) - c, c)
-    row_s = s_rid.numpy()[start + within]
-    assert row_q.shape[0] == n_pairs
-    return torch.from_numpy(row_q.astype(np.int32)), torch.from_numpy(row_s.astype(np.int32))
 
 
 def _compact_worker(rank, world, port, out_dir, skew=False):
