@@ -26,6 +26,7 @@
 #include "take_kernels.hip.h"
 #include "select_kernels.hip.h"
 #include "cluster_kernels.hip.h"
+#include "disjoin_kernels.hip.h"
 #include "dev_common.hip.h"
 #include "join_kernels.hip.h"
 #include "onesweep.hip.h"
@@ -215,6 +216,21 @@ struct InnerPlan {
   u64* irr_off = nullptr;
 };
 
+// What disjoin_plan keeps for disjoin_fill (all inside the arena).  Dropped like the INNER plan by every call that
+// claims the arena.
+struct DisjoinPlan {
+  bool planned = false;
+  giql_side target;
+  u64 total = 0;
+  i64* chrom_base = nullptr;
+  u64* off = nullptr;        // exclusive output offsets per target row
+  u32* lo_first = nullptr;   // first breakpoint past the row's start | DJ_FIRST
+  u32* bp = nullptr;         // distinct breakpoints
+  u64* n_bp = nullptr;
+  u32* ncov = nullptr;       // covered breakpoints below each (NULL in self mode)
+  u32* cbp = nullptr;        // indices of the covered breakpoints
+};
+
 struct giql_hip_ctx {
   explicit giql_hip_ctx(const Switches& s) : sw(s) {
     guess.local_sort = !s.no_local_sort;
@@ -225,6 +241,7 @@ struct giql_hip_ctx {
   Guesses guess;
   CallState call;
   InnerPlan plan;
+  DisjoinPlan dj;
 
   // device resources
   int device = 0;
@@ -289,6 +306,7 @@ static int grow_buffer(void** buf, size_t* cap, size_t need, size_t want, hipStr
 static int ensure_arena(giql_hip_ctx* ctx, size_t bytes, hipStream_t stream) {
   if (bytes <= ctx->arena_cap) return GIQL_OK;
   ctx->plan.planned = false;  // (giql_hip_reserve: a new arena holds no plan)
+  ctx->dj.planned = false;
   const size_t want = align_up(bytes + bytes / 8, (size_t)1 << 20);
   GIQL_TRY(grow_buffer((void**)&ctx->arena, &ctx->arena_cap, bytes, want, stream, "the workspace"));
   if (getenv("GIQL_HIP_DEBUG_ADDR")) fprintf(stderr, "[giql_hip] arena %p + %zu bytes\n", (void*)ctx->arena, want);
@@ -306,6 +324,7 @@ static int grow_part(giql_hip_ctx* ctx, size_t words, hipStream_t stream) {
 template <typename Carve>
 static int claim_arena(giql_hip_ctx* ctx, hipStream_t stream, Carve&& carve) {
   ctx->plan.planned = false;
+  ctx->dj.planned = false;
   GIQL_TRY(ensure_arena(ctx, carve(nullptr), stream));
   carve(ctx->arena);
   return GIQL_OK;
@@ -3161,6 +3180,172 @@ int giql_hip_merge_pred_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chr
   DevPreds ps;
   GIQL_TRY(convert_preds(preds, n_preds, ps, nullptr));
   return with_order_fallback(ctx, [&] { return giql_hip_merge_dev_impl(ctx, s, n_chrom, distance, out_chrom, out_start, out_end, out_count, capacity, n_out, stream, &ps); });
+}
+
+// ----------------------------------------------------------------- DISJOIN
+// Count-then-fill, like the INNER pair.  Stages (disjoin_kernels.hip.h): spans of both sides on one axis ->
+// the reference's 2n event keys -> ONE (key, id) sort -> breakpoints + coverage through two scans -> per-target
+// counts in input order -> int64 offsets; the fill is output-major.
+struct DisjoinBufs {
+  LinBufs lb;
+  SortBufs sb;
+  OsScratch os;
+  u32 *last = nullptr, *is_start = nullptr, *last_excl = nullptr, *start_excl = nullptr;
+  u32 *bp = nullptr, *cov = nullptr, *ncov = nullptr, *cbp = nullptr, *cnt = nullptr, *lo_first = nullptr;
+  u64 *bsums = nullptr, *n_bp = nullptr, *scratch_total = nullptr, *off = nullptr, *total = nullptr;
+};
+
+static int giql_hip_disjoin_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* t, const giql_side* r, int32_t n_chrom,
+                                          int64_t* n_out, void* stream) {
+  if (!ctx || !n_out) return set_err(GIQL_ERR_INVALID, "ctx/n_out is NULL");
+  GIQL_TRY(check_side(t, "target"));
+  if (r) GIQL_TRY(check_side(r, "reference"));
+  if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
+  const bool self = r == nullptr;  // the reference defaults to the target: every piece is covered by its parent
+  const giql_side* ref = self ? t : r;
+  if ((u64)ref->n * 2 > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "DISJOIN reference larger than 2^29 rows");
+  GIQL_TRY(begin_call(ctx));
+  hipStream_t st = (hipStream_t)stream;
+  ctx->stats.n_a = t->n;
+  ctx->stats.n_b = ref->n;
+  ctx->plan.planned = false;
+  ctx->dj.planned = false;
+  *n_out = 0;
+  if (t->n == 0) return GIQL_OK;
+  if (n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
+  const size_t nt = (size_t)t->n, nr = (size_t)ref->n, nev = 2 * nr;
+  DisjoinBufs W;
+  auto carve = [&](char* base) {
+    Carver c{base};
+    common_sizes(c, n_chrom, W.lb);
+    for (int k = 0; k < 2; k++) {
+      W.sb.key[k] = c.take<u32>(nev);
+      W.sb.end[k] = nullptr;
+      W.sb.rid[k] = c.take<u32>(nev);
+    }
+    os_scratch_sizes(c, nev, W.os);
+    W.last = c.take<u32>(nev);
+    W.is_start = c.take<u32>(nev);
+    W.last_excl = c.take<u32>(nev + 1);
+    W.start_excl = c.take<u32>(nev + 1);
+    W.bsums = c.take<u64>(cdiv((u64)(nev + 1 > nt ? nev + 1 : nt), SCAN_TILE) + 1);
+    W.n_bp = c.take<u64>(1);
+    W.scratch_total = c.take<u64>(1);
+    W.total = c.take<u64>(1);
+    W.bp = c.take<u32>(nev + 1);
+    if (!self) {
+      W.cov = c.take<u32>(nev + 1);
+      W.ncov = c.take<u32>(nev + 1);
+      W.cbp = c.take<u32>(nev + 1);
+    }
+    W.cnt = c.take<u32>(nt);
+    W.lo_first = c.take<u32>(nt);
+    W.off = c.take<u64>(nt + 1);
+    return c.off;
+  };
+  GIQL_TRY(claim_arena(ctx, st, carve));
+  giql_side none;
+  memset(&none, 0, sizeof(none));
+  GIQL_TRY(run_spans(ctx, st, *t, self ? none : *r, n_chrom, W.lb));
+  if (nev > 0) {
+    HIP_TRY(hipMemsetAsync(W.os.hist, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
+    Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
+    ctx->stats.phase_bytes[GIQL_PH_LINEARIZE] += (int64_t)20 * nr;  // three columns read, two keys written
+    u32 grid = cdiv((u64)nr, LIN_NT);
+    if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_dj_events, dim3(grid), dim3(LIN_NT), 0, st, view_of(*ref), n_chrom, W.lb.chrom_base,
+                       W.sb.key[0], W.os.hist, ctx->d_meta, self ? DJ_BAD_TARGET : DJ_BAD_REFERENCE);
+    hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, W.os.hist, (u32)LIN_HIST_REPLICAS, W.os.gbase);
+    GIQL_TRY(post_launch("disjoin events"));
+  }
+  GIQL_TRY(run_sort_onesweep(ctx, st, W.sb, (u32)nev, W.os.gbase, W.os.status));
+  if (nev > 0) {
+    Phase ph(ctx, st, GIQL_PH_COUNT, 1);
+    ctx->stats.phase_bytes[GIQL_PH_COUNT] += (int64_t)16 * nev;  // keys + ids read, two flags written
+    hipLaunchKernelGGL(k_dj_flags, dim3(cdiv(nev, 256)), dim3(256), 0, st, W.sb.key[0], W.sb.rid[0], (u32)nev, (u32)nr,
+                       W.last, W.is_start);
+    GIQL_TRY(post_launch("disjoin flags"));
+  }
+  GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, W.last, (u64)nev, W.last_excl, W.bsums, W.n_bp));
+  GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, W.is_start, (u64)nev, W.start_excl, W.bsums, W.scratch_total));
+  if (!self) HIP_TRY(hipMemsetAsync(W.cov, 0, (nev + 1) * sizeof(u32), st));
+  if (nev > 0) {
+    Phase ph(ctx, st, GIQL_PH_AUX, 1);
+    ctx->stats.phase_bytes[GIQL_PH_AUX] += (int64_t)20 * nev + (int64_t)(self ? 4 : 8) * nev;  // (at most: every key distinct)
+    hipLaunchKernelGGL(k_dj_compact, dim3(cdiv(nev, 256)), dim3(256), 0, st, W.sb.key[0], W.last, W.last_excl,
+                       W.is_start, W.start_excl, (u32)nev, W.bp, W.cov);
+    GIQL_TRY(post_launch("disjoin breakpoints"));
+  }
+  if (!self) {
+    GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, W.cov, (u64)nev + 1, W.ncov, W.bsums, W.scratch_total));
+    if (nev > 0) {
+      Phase ph(ctx, st, GIQL_PH_AUX, 1);
+      ctx->stats.phase_bytes[GIQL_PH_AUX] += (int64_t)12 * nev;
+      hipLaunchKernelGGL(k_dj_covered, dim3(cdiv(nev, 256)), dim3(256), 0, st, W.cov, W.ncov, (u32)nev, W.cbp);
+      GIQL_TRY(post_launch("disjoin covered breakpoints"));
+    }
+  }
+  {
+    Phase ph(ctx, st, GIQL_PH_COUNT, 1);
+    ctx->stats.phase_bytes[GIQL_PH_COUNT] += (int64_t)20 * nt;  // three columns read, count + first breakpoint written
+    hipLaunchKernelGGL(k_dj_count, dim3(cdiv(nt, 256)), dim3(256), 0, st, view_of(*t), n_chrom, W.lb.chrom_base, W.bp,
+                       W.n_bp, self ? (const u32*)nullptr : W.cov, self ? (const u32*)nullptr : W.ncov, W.cnt,
+                       W.lo_first, ctx->d_meta);
+    GIQL_TRY(post_launch("disjoin count"));
+  }
+  GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, W.cnt, (u64)nt, W.off, W.bsums, W.total, &ctx->d_meta->n_out));
+  HIP_TRY(hipMemcpyAsync(ctx->h_meta, ctx->d_meta, sizeof(DevMeta), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (ctx->h_meta->aux0 & DJ_BAD_TARGET)
+    return set_err(GIQL_ERR_INVALID, "DISJOIN needs start <= end on every row: the target has a row with start > end");
+  if (ctx->h_meta->aux0 & DJ_BAD_REFERENCE)
+    return set_err(GIQL_ERR_INVALID, "DISJOIN needs start <= end on every row: the reference has a row with start > end");
+  GIQL_TRY(read_meta(ctx, st));
+  collect_spans(ctx);
+  DisjoinPlan& P = ctx->dj;
+  P.target = *t;
+  P.total = ctx->h_meta->n_out;
+  P.chrom_base = W.lb.chrom_base;
+  P.off = W.off;
+  P.lo_first = W.lo_first;
+  P.bp = W.bp;
+  P.n_bp = W.n_bp;
+  P.ncov = self ? nullptr : W.ncov;
+  P.cbp = self ? nullptr : W.cbp;
+  P.planned = true;
+  *n_out = (int64_t)P.total;
+  ctx->stats.n_out = (int64_t)P.total;
+  ctx->stats.span = (int64_t)ctx->h_meta->total_span;
+  return GIQL_OK;
+}
+
+int giql_hip_disjoin_plan_dev(giql_hip_ctx* ctx, const giql_side* target, const giql_side* reference, int32_t n_chrom,
+                              int64_t* n_out, void* stream) {
+  return with_order_fallback(ctx, [&] { return giql_hip_disjoin_plan_dev_impl(ctx, target, reference, n_chrom, n_out, stream); });
+}
+
+int giql_hip_disjoin_fill_dev(giql_hip_ctx* ctx, int32_t* parent_out, int32_t* start_out, int32_t* end_out,
+                              int64_t capacity, void* stream) {
+  if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
+  const DisjoinPlan& P = ctx->dj;
+  if (!P.planned) return set_err(GIQL_ERR_STATE, "disjoin_fill without a successful disjoin_plan");
+  if (P.total == 0) return GIQL_OK;
+  if (!parent_out || !start_out || !end_out) return set_err(GIQL_ERR_INVALID, "output buffer is NULL");
+  if (capacity < 0 || (u64)capacity < P.total)
+    return set_err(GIQL_ERR_CAPACITY, "capacity %lld < %llu rows", (long long)capacity, (unsigned long long)P.total);
+  const u64 n_tiles = (P.total + DJ_FILL_TILE - 1) / DJ_FILL_TILE;
+  if (n_tiles > 0x7FFFFFFFull) return set_err(GIQL_ERR_CAPACITY, "%llu output rows: more than one fill launch holds", (unsigned long long)P.total);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = (((uintptr_t)parent_out | (uintptr_t)start_out | (uintptr_t)end_out) & 15u) == 0 ? 1 : 0;
+  {
+    Phase ph(ctx, st, GIQL_PH_FILL, 1);
+    ctx->stats.phase_bytes[GIQL_PH_FILL] += (int64_t)12 * (int64_t)P.total;  // three int32 outputs per row
+    hipLaunchKernelGGL(k_dj_fill, dim3((u32)n_tiles), dim3(DJ_FILL_NT), 0, st, view_of(P.target), P.chrom_base, P.off,
+                       P.total, P.lo_first, P.bp, P.n_bp, P.ncov, P.cbp, vec, parent_out, start_out, end_out);
+    GIQL_TRY(post_launch("disjoin fill"));
+  }
+  return GIQL_OK;
 }
 
 // ------------------------------------------- distinct intervals + segment sums

@@ -665,6 +665,59 @@ class HipEngine:
                                                 ids.data_ptr() if s.n else None, self._stream()))
         return ids
 
+    # ---------------------------------------------------------------- DISJOIN
+    def disjoin(self, target: DeviceSide, reference: DeviceSide | None = None, n_chrom: int = 0):
+        """DISJOIN (``src/giql/expanders/disjoin.py:147-202``): every ``target`` row cut at the distinct starts and
+        ends of ``reference`` that fall strictly inside it; a piece is kept when a reference row covers its first
+        base.  ``reference=None`` is self mode (the reference is the target; every piece is kept).
+
+        Returns ``(parent, disjoin_start, disjoin_end)`` int32 device tensors: the target row a piece was cut from
+        and the piece in the TARGET's declared encoding.  Rows are ordered by parent row, then by start (the
+        reference promises no order).  The row count is exact and may pass 2^31 (count, then fill, like
+        :meth:`inner_plan` / :meth:`inner_fill`).  Both sides share one chromosome dictionary and need
+        ``start <= end`` on every row: a ``ValueError`` names the side that does not."""
+        torch = _torch()
+        self._check_sides(target, reference if reference is not None else target)
+        try:
+            return self._disjoin_once(target, reference, n_chrom)
+        except _lib.GiqlHipError as exc:
+            if exc.code != _lib.GIQL_ERR_SPAN:
+                raise
+        # a genome longer than the 32-bit axis: chromosome groups are independent units
+        parts = []
+        ref = reference if reference is not None else self._empty_side(target)
+        for st, rt, sr, _rr in self._groups(target, ref, n_chrom):
+            p, s, e = self._disjoin_once(st, sr if reference is not None else None, n_chrom)
+            parts.append((rt[p.long()], s, e))
+        if not parts:
+            z = torch.empty(0, dtype=torch.int32, device=self.device)
+            return z, z.clone(), z.clone()
+        parent = torch.cat([p[0] for p in parts])
+        order = torch.argsort(parent, stable=True)   # groups keep (parent, start) order inside; restore it across them
+        return (parent[order].to(torch.int32), torch.cat([p[1] for p in parts])[order],
+                torch.cat([p[2] for p in parts])[order])
+
+    def _disjoin_once(self, target: DeviceSide, reference, n_chrom: int):
+        torch = _torch()
+        n = ctypes.c_int64(0)
+        ct = target.c_struct()
+        cr = reference.c_struct() if reference is not None else None
+        try:
+            _lib.check(self._L.giql_hip_disjoin_plan_dev(
+                self._h, ctypes.byref(ct), ctypes.byref(cr) if cr is not None else None, int(n_chrom),
+                ctypes.byref(n), self._stream()))
+        except _lib.GiqlHipError as exc:
+            if exc.code == _lib.GIQL_ERR_INVALID and "start > end" in str(exc):
+                raise ValueError(str(exc)) from exc
+            raise
+        self._keepalive = (target, reference)
+        rows = int(n.value)
+        outs = [torch.empty(rows, dtype=torch.int32, device=self.device) for _ in range(3)]
+        if rows:
+            _lib.check(self._L.giql_hip_disjoin_fill_dev(self._h, outs[0].data_ptr(), outs[1].data_ptr(),
+                                                         outs[2].data_ptr(), rows, self._stream()))
+        return tuple(outs)
+
     def merge(self, s: DeviceSide, n_chrom: int, distance: int = 0, preds=None):
         """MERGE: ``(chrom, start, end, count)`` tensors of the merged regions ordered by
         (chrom, start) (``src/giql/expanders/merge.py:186-330``).  ``preds``: the ``predicate :=``

@@ -804,6 +804,57 @@ def _execute_filter(plan: JoinPlan, tables, eng: HipEngine, return_indices: bool
     return pa.Table.from_arrays(arrays, names=names)
 
 
+def _execute_disjoin(plan: JoinPlan, tables, eng: HipEngine, return_indices: bool):
+    """DISJOIN (src/giql/expanders/disjoin.py:102-202): both tables on the device under one chromosome dictionary
+    (uploaded or reused like a join's sides), ``HipEngine.disjoin``, then the target's projected columns gathered
+    by the parent row on the device, with ``disjoin_chrom`` (the parent's chromosome), ``disjoin_start`` and
+    ``disjoin_end`` (the target's declared encoding) appended.  Runs on one device."""
+    import pyarrow as pa
+
+    for side in (plan.left, plan.right):
+        if side is not None and side.table not in tables:
+            raise ValueError(f"table {side.table!r} was not provided")
+    tt = tables[plan.left.table]
+    rt = tables[plan.right.table] if plan.right is not None else None
+    t_chrom = _column(tt, plan.left.chrom_col)
+    if rt is None:
+        ia, ib, dictionary = encode_chroms(t_chrom, t_chrom)
+    else:
+        ia, ib, dictionary = encode_chroms(t_chrom, _column(rt, plan.right.chrom_col))
+    target = _device_side(tt, plan.left, ia, eng)
+    reference = _device_side(rt, plan.right, ib, eng) if rt is not None else None
+    try:
+        parent, ds, de = eng.disjoin(target, reference, len(dictionary))
+    except ValueError as exc:
+        bad = plan.left.table if "target" in str(exc) or plan.right is None else plan.right.table
+        raise ValueError(f"DISJOIN: table {bad!r} has a row with start > end ({exc})") from exc
+    if return_indices:
+        return parent.cpu().numpy(), ds.cpu().numpy(), de.cpu().numpy()
+    is_arrow = isinstance(tt, pa.Table)
+    all_cols = list(tt.column_names) if is_arrow else list(tt.keys() if isinstance(tt, dict) else tt.columns)
+    want = [c for p in plan.projection for c in (all_cols if p.side == "star" else [p.column] if p.side == "l" else [])]
+    if any(p.side == "star" or p.column == "disjoin_chrom" for p in plan.projection):
+        want.append(plan.left.chrom_col)
+    taken = {}
+    if want:
+        taken = (_device_take(tt, want, parent, eng) if is_arrow
+                 else {c: np.asarray(_column(tt, c))[parent.cpu().numpy()] for c in dict.fromkeys(want)})
+    appended = {"disjoin_chrom": lambda: taken[plan.left.chrom_col],
+                "disjoin_start": lambda: pa.array(ds.cpu().numpy(), type=pa.int32()),
+                "disjoin_end": lambda: pa.array(de.cpu().numpy(), type=pa.int32())}
+    names, cols = [], []
+    for p in plan.projection:
+        if p.side == "star":
+            items = [(c, c, None) for c in all_cols] + [(c, c, appended[c]) for c in appended]
+        else:
+            items = [(p.column, p.name, appended[p.column] if p.side == "disjoin" else None)]
+        for c, out_name, make in items:
+            names.append(out_name)
+            cols.append(make() if make is not None else taken[c])
+    arrays = [c if isinstance(c, (pa.Array, pa.ChunkedArray)) else pa.array(c) for c in cols]
+    return _finish_outer(pa.Table.from_arrays(arrays, names=names), plan)
+
+
 def _finish_count(plan, lt, rt, counts, n_chrom, eng, ia, return_indices, a_dev=None):
     """count_overlaps: COUNT(b.col) per distinct left key, zero-filled
     (src/giql/expanders/intersects_duckdb.py:806-854; oracle semantics of
@@ -1393,6 +1444,8 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
         return _execute_cluster_merge(plan, tables, eng, return_indices)
     if plan.kind == "FILTER":
         return _execute_filter(plan, tables, eng, return_indices)
+    if plan.kind == "DISJOIN":
+        return _execute_disjoin(plan, tables, eng, return_indices)
     for side in (plan.left, plan.right):
         if side.table not in tables:
             raise ValueError(f"table {side.table!r} was not provided")

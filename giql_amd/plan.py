@@ -13,7 +13,10 @@ from dataclasses import asdict, dataclass, field
 
 PLAN_PREFIX = "GIQL-HIP-PLAN/1 "
 
-KINDS = ("INNER", "SEMI", "ANTI", "NEAREST", "COUNT", "CLUSTER", "MERGE", "FILTER")
+KINDS = ("INNER", "SEMI", "ANTI", "NEAREST", "COUNT", "CLUSTER", "MERGE", "FILTER", "DISJOIN")
+
+#: the three columns DISJOIN appends to the target's row (src/giql/expanders/disjoin.py:191-198)
+DISJOIN_COLUMNS = ("disjoin_chrom", "disjoin_start", "disjoin_end")
 
 
 @dataclass(frozen=True)
@@ -37,7 +40,9 @@ class PlanSide:
 @dataclass(frozen=True)
 class Projection:
     side: str      # "l", "r", "distance" (NEAREST), "count" (COUNT aggregate); CLUSTER / MERGE:
-                   # "star" (every table column), "cluster" (the id), "count" (COUNT(*))
+                   # "star" (every table column), "cluster" (the id), "count" (COUNT(*)); DISJOIN: "l" (a
+                   # target column), "disjoin" (column = one of DISJOIN_COLUMNS), "star" (the target's
+                   # columns, then the three)
     column: str
     name: str      # output column name
 
@@ -93,7 +98,8 @@ class Having:
 class JoinPlan:
     kind: str
     left: PlanSide
-    right: PlanSide | None      # None for the single-table operators (CLUSTER / MERGE / FILTER)
+    right: PlanSide | None      # None for the single-table operators (CLUSTER / MERGE / FILTER) and for
+                                # DISJOIN in self mode (the reference defaults to the target)
     projection: tuple[Projection, ...] = field(default_factory=tuple)
     distinct: bool = False
     # NEAREST only (src/giql/expanders/nearest.py:240-252)
@@ -125,7 +131,8 @@ class JoinPlan:
         if self.kind not in KINDS:
             raise ValueError(f"unknown plan kind {self.kind!r}")
 
-    def to_string(self) -> str:
+    def to_dict(self) -> dict:
+        """The plan as plain JSON-able data (what :meth:`to_string` serialises)."""
         d = asdict(self)
         d["projection"] = [asdict(p) for p in self.projection]
         d["residuals"] = [asdict(r) for r in self.residuals]
@@ -133,13 +140,19 @@ class JoinPlan:
         d["aggregates"] = [asdict(a) for a in self.aggregates]
         d["having"] = [asdict(h) for h in self.having]
         d["order_by"] = [list(o) for o in self.order_by]
-        return PLAN_PREFIX + json.dumps(d, sort_keys=True, separators=(",", ":"))
+        return d
+
+    def to_string(self) -> str:
+        return PLAN_PREFIX + json.dumps(self.to_dict(), sort_keys=True, separators=(",", ":"))
 
     @classmethod
     def from_string(cls, text: str) -> "JoinPlan":
         if not isinstance(text, str) or not text.startswith(PLAN_PREFIX):
             raise ValueError("not a GIQL hip plan string")
-        d = json.loads(text[len(PLAN_PREFIX):])
+        return cls.from_dict(json.loads(text[len(PLAN_PREFIX):]))
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "JoinPlan":
         return cls(
             kind=d["kind"], left=PlanSide(**d["left"]),
             right=PlanSide(**d["right"]) if d.get("right") else None,

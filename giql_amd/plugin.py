@@ -47,8 +47,8 @@ import re
 from dataclasses import dataclass
 
 from .plan import PlanSide
-from .shape import (AGG_FUNCS, ColRef, HipDeclined, JoinShape, OrderKey, SelItem, TableRef, condition_terms, decline,
-                    lower_join_shape, norm)
+from .shape import (AGG_FUNCS, ColRef, DisjoinShape, HipDeclined, JoinShape, OrderKey, SelItem, TableRef, condition_terms,
+                    decline, lower_disjoin_shape, lower_join_shape, norm)
 
 SPATIAL_KEYS = ("intersects", "contains", "within", "spatialsetpredicate")
 SPATIAL_PREDICATE_META = "giql_spatial_predicate"   # what the generic spatial expanders stamp on their output
@@ -466,6 +466,102 @@ def lower_statement(root, node, ctx):
     return lower_join_shape(shape_from_ast(root, node, ctx), ctx.tables)
 
 
+# ------------------------------------------------------------------ DISJOIN
+DISJOIN_KEYS = ("giqldisjoin", "disjoin")
+
+
+def disjoin_shape_from_ast(root, node, ctx) -> DisjoinShape:
+    """The statement around a ``FROM DISJOIN(target [, reference := ref])`` node (``GIQLDisjoin``: ``this`` = the
+    target table, ``reference`` = the optional reference table) -> :class:`DisjoinShape`.  The operands' physical
+    columns and encodings come from ``ctx.resolution`` (slots ``this`` / ``reference``) when it carries them."""
+    if _arg(root, "with_", "with") is not None:
+        raise decline("DISJOIN over a CTE (top-level WITH)")
+    _only(root, _SELECT_ARGS, "SELECT")
+    from_node = _arg(root, "from_", "from")
+    holder = _arg(from_node, "this") if from_node is not None else None
+    fn_alias = None
+    if holder is not node:
+        # sqlglot wraps an aliased table function: Alias / Table(this=<function>, alias=...)
+        inner = _arg(holder, "this") if holder is not None else None
+        if inner is not node:
+            raise HipDeclined("table functions as join operands are not handled by dialect='hip'")
+        a = _arg(holder, "alias")
+        fn_alias = _ident(_arg(a, "this") if _key(a) == "tablealias" else a)[0] or None
+    if _arg(root, "joins"):
+        raise HipDeclined("table functions as join operands are not handled by dialect='hip'")
+
+    def operand(n, what):
+        if _key(n) in ("subquery", "select", "paren"):
+            raise decline("DISJOIN over a sub-query")
+        if _key(n) in ("column", "identifier"):   # a bare name parses as a column inside a function call
+            name, q = _ident(_arg(n, "this") if _key(n) == "column" else n)
+            return TableRef(name, name, q)
+        if _key(n) != "table":
+            raise decline(f"DISJOIN {what} that is not a base table")
+        return _tableref(n)
+
+    target = operand(_arg(node, "this"), "target")
+    ref_node = _arg(node, "reference")
+    reference = operand(ref_node, "reference") if ref_node is not None else None
+    distinct_node = _arg(root, "distinct")
+    if distinct_node is not None and _arg(distinct_node, "on") is not None:
+        raise decline("DISTINCT ON")
+    shape = DisjoinShape(items=[_select_item(e) for e in (_arg(root, "expressions") or [])], target=target,
+                         reference=reference, alias=fn_alias, distinct=distinct_node is not None,
+                         where=_arg(root, "where") is not None, group_by=_arg(root, "group") is not None,
+                         having=_arg(root, "having") is not None)
+    order = _arg(root, "order")
+    if order is not None:
+        _only(order, ("expressions",), "ORDER BY")
+        for o in _arg(order, "expressions") or []:
+            ordered = _key(o) == "ordered"
+            key = _arg(o, "this") if ordered else o
+            if _key(key) != "column":
+                raise decline("ORDER BY expression")
+            nf = _arg(o, "nulls_first") if ordered else None
+            shape.order_by.append(OrderKey(_colref(key), bool(_arg(o, "desc")) if ordered else False,
+                                           None if nf is None else bool(nf)))
+    for clause in ("limit", "offset"):
+        c = _arg(root, clause)
+        if c is not None:
+            _only(c, ("expression",), clause.upper())
+            v = _literal(_arg(c, "expression"))
+            if v is None or not isinstance(v[1], int):
+                raise decline(f"{clause.upper()} that is not an integer literal")
+            setattr(shape, clause, v[1])
+    res = getattr(ctx, "resolution", None)
+    rc_t = res.column("this") if res is not None else None
+    rc_r = res.column("reference") if res is not None and reference is not None else None
+    shape.sides = (side_from_resolution(rc_t, target, ctx.tables),
+                   side_from_resolution(rc_r, reference, ctx.tables) if reference is not None else None)
+    return shape
+
+
+def lower_disjoin_statement(root, node, ctx):
+    """The statement around a DISJOIN node -> :class:`JoinPlan` (or HipDeclined)."""
+    return lower_disjoin_shape(disjoin_shape_from_ast(root, node, ctx), ctx.tables)
+
+
+def make_disjoin_expander(fallback, make_command):
+    """The ``(HipTarget, GIQLDisjoin)`` expander: the plan as the statement's payload, else the generic CTE
+    expansion (``fallback``)."""
+
+    def expand_disjoin_hip(node, ctx):
+        root = _root(node)
+        if _key(root) == "select":
+            try:
+                plan = lower_disjoin_statement(root, node, ctx)
+            except HipDeclined:
+                plan = None
+            if plan is not None:
+                payload = plan.to_string()
+                ctx.add_statement_finalizer(lambda _root: make_command(payload))
+                return node
+        return fallback(node, ctx)
+
+    return expand_disjoin_hip
+
+
 def make_expander(fallback, make_command):
     """The ``(HipTarget, Intersects)`` expander with its two giql-side effects injected:
     ``fallback(node, ctx)`` = ``_expand_spatial_op(node, ctx, "intersects")`` and
@@ -513,3 +609,12 @@ if HAVE_GIQL:  # the registration itself needs the real package
     expand_intersects_hip = register(HipTarget, Intersects)(
         make_expander(lambda node, ctx: _expand_spatial_op(node, ctx, "intersects"),
                       lambda payload: exp.Command(this=payload)))
+
+    try:
+        from giql.expanders.disjoin import expand_disjoin as _expand_disjoin_generic
+        from giql.expressions import GIQLDisjoin
+
+        expand_disjoin_hip = register(HipTarget, GIQLDisjoin)(
+            make_disjoin_expander(_expand_disjoin_generic, lambda payload: exp.Command(this=payload)))
+    except ImportError:  # a giql without the DISJOIN operator
+        pass

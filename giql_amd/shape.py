@@ -30,7 +30,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field
 
-from .plan import Aggregate, Having, JoinPlan, Operand, PlanSide, Projection, Residual
+from .plan import DISJOIN_COLUMNS, Aggregate, Having, JoinPlan, Operand, PlanSide, Projection, Residual
 from .table import Table, Tables
 
 
@@ -695,3 +695,87 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
     return JoinPlan(kind, left, right, tuple(proj) + hidden, shape.distinct, residuals=residuals,
                     aggregates=aggs, group_by=groups, having=having, order_by=order,
                     limit=shape.limit, offset=shape.offset, output=output)
+
+
+# ------------------------------------------------------------------ DISJOIN
+DISJOIN_RESERVED_PREFIX = "__giql_dj_"   # the reference's CTE names (src/giql/constants.py DJ_PREFIX; disjoin.py:147-178)
+
+
+@dataclass
+class DisjoinShape:
+    """What either front end hands to :func:`lower_disjoin_shape`: ``SELECT ... FROM DISJOIN(target
+    [, reference := ref]) [alias]`` with the clauses of the outer SELECT."""
+
+    items: list[SelItem]
+    target: TableRef
+    reference: TableRef | None = None          # None: self mode
+    alias: str | None = None                   # the table function's alias (qualifies output columns)
+    distinct: bool = False
+    where: bool = False                        # clauses the lowering cannot express: seen, then declined
+    group_by: bool = False
+    having: bool = False
+    order_by: list[OrderKey] = field(default_factory=list)
+    limit: int | None = None
+    offset: int | None = None
+    sides: tuple[PlanSide, PlanSide | None] | None = None   # as resolved by the caller (the plugin), else from ``tables``
+
+
+def lower_disjoin_shape(shape: DisjoinShape, tables: Tables) -> JoinPlan:
+    """The gate of DISJOIN, shared by both front ends (src/giql/expanders/disjoin.py:102-202): projections over
+    the target's columns and the three ``disjoin_*`` columns, DISTINCT, ORDER BY output names, LIMIT / OFFSET.
+    WHERE, GROUP BY / aggregates and HAVING over the operator's rows decline."""
+    names = [shape.target.name] + ([shape.reference.name] if shape.reference is not None else [])
+    for n in names + ([shape.alias] if shape.alias else []):
+        if n.casefold().startswith(DISJOIN_RESERVED_PREFIX):
+            raise decline(f"the name {n!r} uses the reserved prefix {DISJOIN_RESERVED_PREFIX!r} of DISJOIN")
+    if shape.where:
+        raise decline("WHERE over the rows of DISJOIN")
+    if shape.group_by or any(it.func is not None or (it.ref is not None and it.ref.count) for it in shape.items):
+        raise decline("GROUP BY / aggregates over the rows of DISJOIN")
+    if shape.having:
+        raise decline("HAVING over the rows of DISJOIN")
+    if shape.sides is not None:
+        left, right = shape.sides
+    else:
+        left = table_side(shape.target, tables)
+        right = table_side(shape.reference, tables) if shape.reference is not None else None
+    qualifiers = {norm(shape.alias)} if shape.alias else {left.alias}
+
+    def own(ref: ColRef, where: str) -> str:
+        if ref.table is not None and norm(ref.table, ref.table_quoted) not in qualifiers:
+            raise ValueError(f"Unknown table qualifier {ref.table!r} in {where}")
+        return ref.column
+
+    proj, out_names = [], []
+    for it in shape.items:
+        ref = it.ref
+        if ref.star:
+            own(ref, "the SELECT list")
+            if it.alias:
+                raise decline("aliased star projection")
+            proj.append(Projection("star", "*", "*"))
+            out_names.append(None)
+            continue
+        column = own(ref, "the SELECT list")
+        if column.casefold().startswith(DISJOIN_RESERVED_PREFIX):
+            raise decline(f"the name {column!r} uses the reserved prefix {DISJOIN_RESERVED_PREFIX!r} of DISJOIN")
+        name = it.alias or column
+        proj.append(Projection("disjoin" if column in DISJOIN_COLUMNS else "l", column, name))
+        out_names.append(name)
+    if not proj:
+        raise decline("empty SELECT list")
+    has_star = any(p.side == "star" for p in proj)
+    order = []
+    for o in shape.order_by:
+        name = own(o.ref, "ORDER BY")
+        if name not in out_names and not has_star:
+            if shape.distinct:
+                raise ValueError("ORDER BY a column that DISTINCT does not keep")
+            # carried for the sort only, dropped from the result (the "__giql_" convention of the join plans)
+            hidden = f"__giql_o{len(order)}"
+            proj.append(Projection("disjoin" if name in DISJOIN_COLUMNS else "l", name, hidden))
+            name = hidden
+        nulls_first = o.nulls_first if o.nulls_first is not None else not o.desc
+        order.append((name, o.desc, nulls_first))
+    return JoinPlan("DISJOIN", left, right, tuple(proj), shape.distinct, order_by=tuple(order), limit=shape.limit,
+                    offset=shape.offset)

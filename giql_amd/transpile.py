@@ -43,7 +43,7 @@ from .shape import condition_terms as _condition_terms
 from .shape import operand_sides as _operand_sides
 from .shape import decline as _decline
 from .shape import genomic_col as _genomic_col
-from .shape import lower_join_shape, resolve_projection
+from .shape import DisjoinShape, lower_disjoin_shape, lower_join_shape, resolve_projection
 from .shape import norm as _norm
 from .shape import table_side as _table_side
 from .table import Table, Tables, build_tables, encoding_of
@@ -929,10 +929,115 @@ def _lower_cluster(p: _Parser, tbls: Tables) -> JoinPlan:
                     cluster_predicate=tuple(cluster_pred))
 
 
+def _disjoin_from(p: _Parser) -> int | None:
+    """Index of the ``DISJOIN`` token of a top-level ``FROM DISJOIN(`` (None: the FROM names something else)."""
+    depth = 0
+    for k, t in enumerate(p.toks):
+        if t.kind == "punct" and t.text in "()":
+            depth += 1 if t.text == "(" else -1
+        if t.kind == "kw" and t.text == "FROM" and depth == 0:
+            a, b = p.toks[k + 1], p.toks[min(k + 2, len(p.toks) - 1)]
+            if a.kind == "id" and not a.quoted and a.text.upper() == "DISJOIN" and b.kind == "punct" and b.text == "(":
+                return k + 1
+            return None
+    return None
+
+
+def _lower_disjoin(p: _Parser, tbls: Tables) -> JoinPlan:
+    """``SELECT [DISTINCT] <* | columns> FROM DISJOIN(target [, reference := ref]) [[AS] alias] [ORDER BY ...]
+    [LIMIT n] [OFFSET m]`` (docs/dialect/set-operators.rst, DISJOIN; src/giql/expanders/disjoin.py:102-202)."""
+    if p.at_kw("WITH"):
+        raise _decline("DISJOIN over a CTE (top-level WITH)")
+    p.expect_kw("SELECT")
+    shape = DisjoinShape(items=[], target=None)
+    if p.at_kw("DISTINCT"):
+        p.next()
+        if p.at_kw("ON"):
+            raise _decline("DISTINCT ON")
+        shape.distinct = True
+    shape.items = _parse_projection(p)
+    p.expect_kw("FROM")
+    p.next()                      # DISJOIN
+    p.expect_punct("(")
+
+    def table_arg() -> _TableRef:
+        if p.at_punct("(") or p.at_kw("SELECT", "WITH"):
+            raise _decline("DISJOIN over a sub-query")
+        t = p.ident()
+        if p.at_punct("."):
+            raise HipDeclined("catalog/schema-qualified tables are not handled by dialect='hip'")
+        if p.at_punct("("):
+            raise _decline("a table function as a DISJOIN argument")
+        return _TableRef(t.text, t.text, t.quoted)
+
+    shape.target = table_arg()
+    while p.at_punct(","):
+        p.next()
+        name = p.ident()
+        if p.peek().kind != "assign" or name.text.lower() != "reference" or shape.reference is not None:
+            raise _decline(f"DISJOIN argument {name.text!r}")
+        p.next()
+        shape.reference = table_arg()
+    p.expect_punct(")")
+    if p.at_kw("AS"):
+        p.next()
+        shape.alias = p.ident().text
+    elif p.peek().kind == "id":
+        shape.alias = p.next().text
+    if p.at_punct(",") or p.at_kw("JOIN", "INNER", "LEFT", "RIGHT", "FULL", "CROSS", "SEMI", "ANTI", "NATURAL"):
+        raise HipDeclined("table functions as join operands are not handled by dialect='hip'")
+    if p.at_kw("WHERE"):
+        shape.where = True
+    elif p.at_kw("GROUP"):
+        shape.group_by = True
+    elif p.at_kw("HAVING"):
+        shape.having = True
+    if not (shape.where or shape.group_by or shape.having):
+        if p.at_kw("ORDER"):
+            p.next()
+            p.expect_kw("BY")
+            while True:
+                if p.peek().kind != "id":
+                    raise _decline("ORDER BY expression")
+                ref = p.colref()
+                if p.at_punct("(") or (p.peek().kind == "punct" and p.peek().text in "+-/*"):
+                    raise _decline("ORDER BY expression")
+                desc = False
+                if p.peek().kind == "id" and not p.peek().quoted and p.peek().text.upper() in ("ASC", "DESC"):
+                    desc = p.next().text.upper() == "DESC"
+                nulls_first = None
+                if p.peek().kind == "id" and not p.peek().quoted and p.peek().text.upper() == "NULLS":
+                    p.next()
+                    t = p.next()
+                    if t.kind not in ("id", "kw") or t.text.upper() not in ("FIRST", "LAST"):
+                        raise ValueError("ORDER BY ... NULLS must be followed by FIRST or LAST")
+                    nulls_first = t.text.upper() == "FIRST"
+                shape.order_by.append(OrderKey(ref, desc, nulls_first))
+                if p.at_punct(","):
+                    p.next()
+                    continue
+                break
+        for _ in range(2):
+            for clause in ("LIMIT", "OFFSET"):
+                if p.at_kw(clause) and getattr(shape, clause.lower()) is None:
+                    p.next()
+                    t = p.next()
+                    if t.kind != "num" or "." in t.text:
+                        raise _decline(f"{clause} that is not an integer literal")
+                    setattr(shape, clause.lower(), int(t.text))
+        if p.peek().kind == "kw":
+            raise _decline(f"{p.peek().text} clause after DISJOIN")
+        if p.peek().kind != "end" and not p.at_punct(";"):
+            raise _decline(f"trailing input near {p.peek().text!r}")
+    return lower_disjoin_shape(shape, tbls)
+
+
 def build_plan(giql: str, tables=None) -> JoinPlan:
     """Parse *giql* and lower the INTERSECTS / NEAREST join (or a CLUSTER / MERGE
     query) to a :class:`JoinPlan`."""
     probe = _Parser(giql)
+    if _disjoin_from(probe) is not None:
+        return _lower_disjoin(probe, tables if isinstance(tables, Tables) else build_tables(tables))
     if probe.at_kw("SELECT") and _has_cluster_or_merge(probe):
         return _lower_cluster(probe, tables if isinstance(tables, Tables) else build_tables(tables))
     if probe.at_kw("SELECT") and _is_single_table_filter(probe):

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define GIQL_HIP_ABI_VERSION 2  /* 2: giql_hip_stats.phase_bytes, pinned host outputs, plan export */
+#define GIQL_HIP_ABI_VERSION 3  /* 2: giql_hip_stats.phase_bytes, pinned host outputs, plan export; 3: DISJOIN */
 
 enum {
   GIQL_OK = 0,
@@ -262,6 +262,26 @@ int giql_hip_merge_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom,
                        int64_t distance, int32_t* out_chrom, int32_t* out_start,
                        int32_t* out_end, int64_t* out_count, int64_t capacity,
                        int64_t* n_out, void* stream);
+
+/* DISJOIN(target [, reference := ref]): src/giql/expanders/disjoin.py:147-202 -- the five CTEs
+ * (breakpoints = DISTINCT reference starts UNION ends; cuts = breakpoints STRICTLY inside a target
+ * row; pieces = the LEAD gaps of {start} UNION cuts UNION {end}; the EXISTS coverage filter, skipped
+ * when the reference is the target, :189-202) in two calls, like the INNER pair:
+ *   plan: one sort of the reference's 2n event keys + scans + per-target counts; *n_out = the exact
+ *         number of output rows (int64: it may pass 2^31).  reference == NULL is self mode.
+ *   fill: parent_out[k] = the target row the piece was cut from, start_out[k] / end_out[k] = the piece
+ *         in the TARGET's declared encoding (disjoin.py:136-140), for k < n_out (capacity >= n_out),
+ *         ordered by parent row, then by start (the reference promises no order).
+ * Both sides share one chromosome dictionary; every row of both needs start <= end (checked on the
+ * device: GIQL_ERR_INVALID names the side); a zero-length target row yields nothing, a zero-length
+ * reference row cuts and never covers.  A reference has at most 2^29 rows.  The plan lives in the
+ * context's workspace under the rules of the INNER plan: any call that reuses the workspace makes
+ * fill return GIQL_ERR_STATE. */
+int giql_hip_disjoin_plan_dev(giql_hip_ctx* ctx, const giql_side* target,
+                              const giql_side* reference, int32_t n_chrom,
+                              int64_t* n_out, void* stream);
+int giql_hip_disjoin_fill_dev(giql_hip_ctx* ctx, int32_t* parent_out, int32_t* start_out,
+                              int32_t* end_out, int64_t capacity, void* stream);
 /* MERGE(..., predicate := ...): merge.py:201-210 hands the predicate to the CLUSTER it is built on, so a
  * merged region is a cluster of giql_hip_cluster_pred_dev; its MAX(end) is taken over the region's own
  * rows (a region may end while an earlier one still reaches further). */
