@@ -345,6 +345,65 @@ def test_group_rows_segment_sum(eng, name, enc):
     assert np.array_equal(sums, want)
 
 
+# -------------------------------------------------------------- DISJOIN
+def _disjoin_want(t, r=None):
+    """``brute_force_arrays`` (anchored row by row in tests/test_disjoin.py) on the canonical columns, the pieces
+    back in the target's encoding."""
+    from _disjoin_ref import brute_force_arrays
+
+    cols = [t.chrom.astype(np.int64), t.cs.astype(np.int64), t.ce.astype(np.int64)]
+    if r is not None:
+        cols += [r.chrom.astype(np.int64), r.cs.astype(np.int64), r.ce.astype(np.int64)]
+    want = brute_force_arrays(*cols)
+    want[:, 1] -= t.start_off
+    want[:, 2] -= t.end_off
+    return want
+
+
+@pytest.mark.parametrize("mode", ["self", "reference"])
+@pytest.mark.parametrize("enc", ENCODINGS, ids=lambda e: e[0])
+@pytest.mark.parametrize("name", JOIN_CLASSES)
+def test_disjoin(eng, name, enc, mode):
+    """``k_dj_events`` writes real keys with no sentinel: up to 0xFFFFFFFE at span 2^32 - 1, in the top bucket of
+    every sort form."""
+    t = make_side(name, enc, 2500, 18, zero_length=True)
+    r = make_side(name, enc, 4000, 19, zero_length=True) if mode == "reference" else None
+    dt, dr = dev(t), None if r is None else dev(r)
+    n = len(LAYOUTS[name])
+    want = _disjoin_want(t, r)
+    assert want.shape[0] > 2000
+    if name == "tight_top":      # events in the top 65,536 keys, one of them 0xFFFFFFFE
+        ref = r if r is not None else t
+        key = ref.ce[ref.chrom == 1].astype(np.int64) + 2**31 - 1
+        assert key.max() == TOP - 1 and (key >= TOP - 65536).sum() > 300
+    if name in FITS:
+        got = eng._disjoin_once(dt, dr, n)
+        st = eng.stats()
+        assert st["span"] == tight_span(name), (name, st["span"])
+        assert st["sort_local"] == (eng.kind != "default") and (eng.kind != "narrow" or st["bucket_bits"] == 13), st
+    else:
+        assert_span_error(lambda: eng._disjoin_once(dt, dr, n))
+        got = eng.disjoin(dt, dr, n)
+    got = np.stack([host(x) for x in got], 1).astype(np.int64)
+    assert got.shape == want.shape and np.array_equal(got, want)
+    assert not eng.stats()["sort_resorted"]
+
+
+@pytest.mark.parametrize("enc", ENCODINGS, ids=lambda e: e[0])
+def test_disjoin_one_chromosome_past_32_bits_is_a_clean_error(eng, enc):
+    from giql_amd import _lib
+
+    t = make_side("one_chrom_over", enc, 2000, 20)
+    r = make_side("one_chrom_over", enc, 2000, 21)
+    for dr in (None, dev(r)):
+        assert_span_error(lambda: eng._disjoin_once(dev(t), dr, 1))
+        with pytest.raises((ValueError, _lib.GiqlHipError)):
+            eng.disjoin(dev(t), dr, 1)
+    small = make_side("aligned_top", enc, 600, 22)      # the context answers afterwards
+    got = np.stack([host(x) for x in eng.disjoin(dev(small), None, 3)], 1).astype(np.int64)
+    assert np.array_equal(got, _disjoin_want(small))
+
+
 # ---------------------------------------------------------------- index
 @pytest.mark.parametrize("enc", ENCODINGS, ids=lambda e: e[0])
 @pytest.mark.parametrize("name", JOIN_CLASSES)

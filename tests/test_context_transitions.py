@@ -11,9 +11,11 @@ was found by a long random soak.  So here:
 * Walk 1: per operator family, one fresh context walks an Eulerian circuit of the complete directed graph over the
   input classes (self-loops included): every ordered pair (X, Y) is a call on Y right after the context's last call
   on X.  Each visit runs the family twice; the second run must reach the path its class names (``SIGNATURES``).
-* Walk 2: one context, all twelve operators in a shuffled order per visit, with ``select`` / ``take_utf8`` put
-  between some plans and their fill -- which must then refuse (``GIQL_ERR_STATE``): those calls reuse the workspace
-  the plan lives in.
+* Walk 2: one context, all twelve operators and DISJOIN's three in a shuffled order per visit, with ``select`` /
+  ``take_utf8`` / a plan of the other operator put between some plans and their fill -- which must then refuse
+  (``GIQL_ERR_STATE``): those calls reuse the workspace the plan lives in.
+* DISJOIN (self mode, reference mode, plan + fill through the raw ABI) walks the classes on which its path can
+  differ, against the brute force of ``tests/_disjoin_ref.py``; its plan lives in the same workspace (``ctx->dj``).
 * Leg 3: the sticky four-pass fallback after a bucket too large for the bucket stage, reached from every class.
 * Leg 4: production density on a default context: every ordered pair of bucket widths.
 
@@ -428,6 +430,77 @@ def op_index(eng, name, log, fam, rnd):
         index.close()
 
 
+# ---- DISJOIN: target = the class's A, reference = its B (self mode: A alone); truth = tests/_disjoin_ref.py's
+# vectorised brute force, anchored row by row in tests/test_disjoin.py
+DISJOIN_NAMES = ["general", "presorted", "irregular", "pileups", "many_chroms", "negative", "w16", "w13", "sparse"]
+
+
+@functools.lru_cache(maxsize=None)
+def want_disjoin(name, mode):
+    from _disjoin_ref import brute_force_arrays
+
+    a, b, _nch, _da, _db = resident(name)
+    i64 = lambda s: [s.chrom.astype(np.int64), s.cs.astype(np.int64), s.ce.astype(np.int64)]
+    out = brute_force_arrays(*i64(a)) if mode == "self" else brute_force_arrays(*i64(a), *i64(b))
+    out[:, 1] -= a.start_off
+    out[:, 2] -= a.end_off
+    return out
+
+
+def _pieces(parent, ds, de):
+    return np.stack([parent.cpu().numpy(), ds.cpu().numpy(), de.cpu().numpy()], 1).astype(np.int64)
+
+
+def _disjoin_call(eng, name, log, fam, rnd, mode):
+    _a, _b, nch, da, db = resident(name)
+    reference = None if mode == "self" else db
+    if name == "irregular":      # inverted rows in A: the error names the side that holds them
+        with pytest.raises(ValueError, match="the target has a row with start > end"):
+            eng.disjoin(da, reference, nch)
+        log.add(eng, fam, name, rnd, "disjoin_" + mode)
+        return
+    got = _pieces(*eng.disjoin(da, reference, nch))
+    log.add(eng, fam, name, rnd, "disjoin_" + mode)
+    w = want_disjoin(name, mode)
+    assert got.shape == w.shape and np.array_equal(got, w), (name, "disjoin", mode)
+
+
+def op_disjoin_self(eng, name, log, fam, rnd):
+    _disjoin_call(eng, name, log, fam, rnd, "self")
+
+
+def op_disjoin_ref(eng, name, log, fam, rnd):
+    _disjoin_call(eng, name, log, fam, rnd, "reference")
+
+
+def op_disjoin_plan_fill(eng, name, log, fam, rnd, intruder=None):
+    from _disjoin_ref import fill_raw, plan_raw
+    from giql_amd import _lib
+
+    _a, _b, nch, da, db = resident(name)
+    rc, n = plan_raw(eng, da, db, nch)
+    log.add(eng, fam, name, rnd, "disjoin_plan")
+    outs = [torch.full((max(n, 8),), -7, dtype=torch.int32, device="cuda:0") for _ in range(3)]
+    if name == "irregular":
+        assert rc == _lib.GIQL_ERR_INVALID and b"the target has a row" in eng._L.giql_hip_last_error(), (name, rc)
+        assert fill_raw(eng, outs, 8) == _lib.GIQL_ERR_STATE and all(int((o != -7).sum()) == 0 for o in outs)
+        return
+    w = want_disjoin(name, "reference")
+    assert (rc, n) == (0, w.shape[0]), (name, "disjoin plan", rc, n)
+    if intruder is not None:
+        intruder(eng, name)          # reuses the workspace the plan lives in: the plan is gone
+        assert fill_raw(eng, outs, n) == _lib.GIQL_ERR_STATE, (name, intruder.__name__)
+        assert b"without a successful disjoin_plan" in eng._L.giql_hip_last_error()
+        assert all(int((o != -7).sum()) == 0 for o in outs), (name, "a refused fill wrote")
+        assert plan_raw(eng, da, db, nch) == (0, n)
+    assert fill_raw(eng, outs, n) == 0
+    got = _pieces(*(o[:n] for o in outs))
+    assert np.array_equal(got, w), (name, "disjoin plan + fill")
+
+
+DISJOIN_OPS = [op_disjoin_self, op_disjoin_ref, op_disjoin_plan_fill]
+
+
 FAMILIES = {
     "inner": [op_inner_join, op_into_exact, op_into_short, op_into_ample, op_plan_fill],
     "row": [op_semi, op_anti, op_count],
@@ -490,6 +563,31 @@ def test_walk_every_ordered_pair_of_classes(monkeypatch, family):
         assert any(c[4]["bucket_join"] for c in log.calls if c[2] == 2), "no settled INNER call joined in the bucket stage"
 
 
+@pytest.mark.gpu
+def test_walk_disjoin_every_ordered_pair_of_its_classes(monkeypatch):
+    """The ``disjoin`` family: an Eulerian circuit over the classes on which DISJOIN's path can differ (82 visits).
+    On ``irregular`` every op must raise naming the target; the visit that follows must be right."""
+    eng = _density_engine(monkeypatch)
+    log = Log()
+    walk = eulerian_circuit(len(DISJOIN_NAMES))
+    assert len(walk) == 82
+    try:
+        for v in walk:
+            for rnd in (1, 2):
+                for op in DISJOIN_OPS:
+                    op(eng, DISJOIN_NAMES[v], log, "disjoin", rnd)
+    finally:
+        eng.close()
+    pairs = log.transitions("disjoin")
+    forms = sorted({(c[4]["sort_local"], c[4]["bucket_bits"]) for c in log.calls if c[1] != "irregular"})
+    print(f"\n[disjoin] ordered class pairs covered: {len(pairs)} of {len(DISJOIN_NAMES) ** 2}; "
+          f"(three-stage sort, bucket bits) seen: {forms}")
+    assert pairs == {(x, y) for x in DISJOIN_NAMES for y in DISJOIN_NAMES}
+    assert not any(c[4]["sort_resorted"] for c in log.calls)
+    after = [c for p, c in zip(log.calls, log.calls[1:]) if p[1] == "irregular" and c[1] != "irregular"]
+    assert len(after) == len(DISJOIN_NAMES) - 1         # every other class was visited right after the refusals
+
+
 # ---------------------------------------------------------------- Walk 2 (mixed operators, plans interrupted)
 def _intrude_select(eng, name):
     _a, _b, _nch, da, _db = resident(name)
@@ -508,6 +606,23 @@ def _intrude_take_utf8(eng, name):
     assert got == "".join(words[i] for i in idx) and o.cpu().numpy()[-1] == len(got), (name, "take_utf8")
 
 
+def _intrude_inner_plan(eng, name):
+    _a, _b, nch, da, db = resident(name)
+    assert eng.inner_plan(da, db, nch) == want(name, "pairs").shape[0], (name, "inner_plan between a plan and its fill")
+
+
+def _intrude_disjoin_plan(eng, name):
+    from _disjoin_ref import plan_raw
+
+    _a, _b, nch, da, db = resident("general")
+    assert plan_raw(eng, da, db, nch) == (0, want_disjoin("general", "reference").shape[0])
+
+
+INTRUDERS = {"select": _intrude_select, "take_utf8": _intrude_take_utf8, "inner_plan": _intrude_inner_plan,
+             "disjoin_plan": _intrude_disjoin_plan, None: None}
+MIXED_OPS = ALL_OPS + DISJOIN_OPS
+
+
 @pytest.mark.gpu
 def test_walk_mixed_operators_with_interrupted_plans(monkeypatch):
     eng = _density_engine(monkeypatch)
@@ -515,23 +630,38 @@ def test_walk_mixed_operators_with_interrupted_plans(monkeypatch):
     r = np.random.default_rng(2027)
     visits = list(r.permutation(len(NAMES))) + list(r.permutation(len(NAMES)))
     interrupted = {"select": 0, "take_utf8": 0}
+    dj_interrupted = {"select": 0, "take_utf8": 0, "inner_plan": 0}
+    inner_by_disjoin = 0
     try:
         for v in visits:
             name = NAMES[v]
-            for k in r.permutation(len(ALL_OPS)):
-                op = ALL_OPS[k]
+            for k in r.permutation(len(MIXED_OPS)):
+                op = MIXED_OPS[k]
                 if op is op_plan_fill:
-                    which = ("select", "take_utf8", None)[int(r.integers(0, 3))]
-                    intruder = {"select": _intrude_select, "take_utf8": _intrude_take_utf8, None: None}[which]
-                    op(eng, name, log, "mixed", 1, intruder=intruder)
-                    if which:
+                    which = ("select", "take_utf8", None, "disjoin_plan")[int(r.integers(0, 4))]
+                    op(eng, name, log, "mixed", 1, intruder=INTRUDERS[which])
+                    if which == "disjoin_plan":
+                        inner_by_disjoin += 1
+                    elif which:
                         interrupted[which] += 1
+                elif op is op_disjoin_plan_fill:
+                    which = ("select", "take_utf8", "inner_plan", None)[int(r.integers(0, 4))]
+                    op(eng, name, log, "mixed", 1, intruder=INTRUDERS[which])
+                    if which and name != "irregular":
+                        dj_interrupted[which] += 1
                 else:
                     op(eng, name, log, "mixed", 1)
     finally:
         eng.close()
-    print(f"\n[mixed] ordered class pairs covered: {len(log.transitions('mixed'))}; interrupted plans: {interrupted}")
+    dj = [c[4] for c in log.calls if c[3].startswith("disjoin") and c[1] != "irregular"]
+    forms = sorted({(st["sort_local"], st["bucket_bits"]) for st in dj})
+    print(f"\n[mixed] ordered class pairs covered: {len(log.transitions('mixed'))}; interrupted plans: {interrupted}; "
+          f"DISJOIN plans interrupted: {dj_interrupted}; INNER plans interrupted by a DISJOIN plan: {inner_by_disjoin}; "
+          f"DISJOIN (three-stage sort, bucket bits) seen: {forms}")
     assert interrupted["select"] > 0 and interrupted["take_utf8"] > 0
+    assert all(v > 0 for v in dj_interrupted.values()) and inner_by_disjoin > 0
+    # DISJOIN takes its bucket width from the span another operator left on the context: both sort forms were met
+    assert any(st["sort_local"] for st in dj) and any(not st["sort_local"] for st in dj)
 
 
 # ---------------------------------------------------------------- Leg 3: the sticky four-pass fallback

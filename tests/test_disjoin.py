@@ -1,5 +1,7 @@
-"""DISJOIN without a GPU: the front ends, the plan, the declines, the ABI, and the brute-force restatement
-against the golden fixture (tests/golden/disjoin.json, minted by tests/golden/make_disjoin.py)."""
+"""DISJOIN without a GPU: the front ends, the plan, the declines, the ABI, the brute-force restatement against the
+golden fixture (tests/golden/disjoin.json, minted by tests/golden/make_disjoin.py), the vectorised brute force
+against the row-by-row one, and the numpy mirror of the fill's tiles that shows which path each constructed case of
+tests/test_disjoin_paths.py reaches."""
 
 import os
 import re
@@ -8,6 +10,7 @@ import numpy as np
 import pytest
 
 import _ast_doubles as D
+import _disjoin_ref as R
 from _disjoin_ref import brute_force, brute_force_arrays, golden_cases, OFFSETS
 from giql_amd import _lib
 from giql_amd.plan import DISJOIN_COLUMNS, JoinPlan
@@ -142,3 +145,99 @@ def test_vectorised_brute_force_agrees_with_every_golden_case():
         got[:, 1] -= so
         got[:, 2] -= eo
         assert sorted(got.tolist()) == c["expected"], c["id"]
+
+
+# ---------------------------------------------------------------- the fast reference, anchored row by row
+def _same(case):
+    fast, slow = case.expected(), case.expected_row_by_row()
+    assert fast.shape == slow.shape and np.array_equal(fast, slow), case.id
+
+
+def test_vectorised_brute_force_equals_the_row_by_row_one_on_every_constructed_case():
+    """brute_force_arrays has the kernel's own shape (breakpoints, depth, two searchsorted); brute_force does not.
+    Only what passes here may serve the GPU tests as their truth (tests/test_disjoin_paths.py)."""
+    paths = R.path_cases()
+    for case, cnt in paths.values():
+        _same(case)
+        assert np.array_equal(case.counts(), cnt), case.id          # the builder gives the counts it was asked for
+    cover = R.coverage_cases()
+    assert len([c for c in cover if c.id.startswith("encodings-")]) == 16
+    for case in cover:
+        _same(case)
+    assert len(paths) + len(cover) == 50
+
+
+def test_vectorised_brute_force_equals_the_row_by_row_one_on_200_seeded_tables():
+    seen = {"self": 0, "reference": 0, "negative": 0, "zero_t": 0, "zero_r": 0, "dup": 0, "book": 0, "one_side": 0,
+            "rows": 0}
+    for seed in range(200):
+        case = R.seeded_small_case(seed)
+        tc, ts, te = case.t
+        assert 1 <= len(tc) <= 300 and (case.r is None or len(case.r[0]) <= 300)
+        _same(case)
+        rc, rs, re_ = case.r if case.r is not None else case.t
+        seen["self" if case.r is None else "reference"] += 1
+        seen["negative"] += int(ts.min() < 0 and (len(rs) == 0 or rs.min() < 0))
+        seen["zero_t"] += int((ts == te).any())
+        seen["zero_r"] += int((rs == re_).any())
+        seen["dup"] += int(len({*zip(rc.tolist(), rs.tolist(), re_.tolist())}) < len(rc))
+        seen["book"] += int(bool(set(zip(rc.tolist(), rs.tolist())) & set(zip(rc.tolist(), re_.tolist()))))
+        seen["one_side"] += int(case.r is not None and set(tc.tolist()) != set(rc.tolist()))
+        seen["rows"] += len(case.expected())
+    assert seen["self"] == seen["reference"] == 100
+    assert all(seen[k] >= 60 for k in ("negative", "zero_t", "zero_r", "dup", "book")) and seen["one_side"] >= 30, seen
+    assert seen["rows"] > 20_000
+
+
+# ---------------------------------------------------------------- every path case reaches the path it names
+def test_fill_mirror_on_hand_counted_tiles():
+    c = {"tile": 8, "items": 4, "off_cap": 3}
+    t = R.fill_mirror([0, 3, 0, 0, 6, 0, 2, 0], consts=c)           # offsets 0 0 3 3 3 9 9 11, total 11
+    assert [(x["k0"], x["k1"], x["r_lo"], x["nr"], x["staged"]) for x in t] == [(0, 8, 1, 4, False), (8, 11, 4, 3, True)]
+    assert [(x["vec_quads"], x["scalar_quads"], x["partial"], x["k0_in_row"]) for x in t] == [(2, 0, False, 0),
+                                                                                              (0, 1, True, 5)]
+    assert [(x["zero_rows"], x["zero_after"]) for x in t] == [(2, 1), (1, 1)]
+    assert all(x["vec_quads"] == 0 for x in R.fill_mirror([0, 3, 0, 0, 6, 0, 2, 0], align=(0, 4, 0), consts=c))
+    assert [R.tiles_of_row([0, 3, 0, 0, 6, 0, 2, 0], r, consts=c) for r in (0, 1, 4, 6)] == [0, 1, 2, 1]
+
+
+def test_every_path_case_reaches_its_path():
+    """A retuned DJ_FILL_TILE / DJ_FILL_ITEMS / DJ_OFF_CAP must fail here, not quietly empty a GPU case."""
+    k = R.fill_constants()
+    tile, items, cap = k["tile"], k["items"], k["off_cap"]
+    cases = R.path_cases()
+    m = {cid: R.fill_mirror(cnt) for cid, (_case, cnt) in cases.items()}
+    cnt = {cid: c for cid, (_case, c) in cases.items()}
+    # the unstaged branch and both sides of its cap
+    assert [(x["nr"], x["staged"]) for x in m["unstaged-5000"]] == [(5002, False)]
+    assert [(x["nr"], x["staged"]) for x in m["cap-exactly"]] == [(cap, True)]
+    assert [(x["nr"], x["staged"]) for x in m["cap-plus-one"]] == [(cap + 1, False)]
+    x, = m["unstaged-leading-trailing-zeros"]
+    assert not x["staged"] and x["r_lo"] == 9 and x["zero_after"] == 11 and cnt["unstaged-leading-trailing-zeros"][0] == 0
+    z = m["zero-rows-at-tile-edges"]
+    assert len(z) == 3 and all(x["staged"] and x["k0_in_row"] == 0 for x in z)
+    assert [x["zero_after"] for x in z] == [7, 3, 2]      # zero-piece rows between a tile's last slot and the next's first
+    assert z[1]["r_lo"] == 9 and z[2]["r_lo"] == 14       # ... skipped: the next tile opens on the row that owns its slot
+    u = m["unstaged-second-tile"]
+    assert [x["staged"] for x in u] == [True, False, True] and u[1]["k0_in_row"] == 0 and u[1]["zero_rows"] > cap
+    # tile edges
+    for total in (1, 3, 4, 5, tile - 1, tile, tile + 1, 4 * tile - 1, 4 * tile + 1):
+        t = m[f"total-{total}"]
+        assert len(t) == -(-total // tile) and t[-1]["k1"] == total
+        assert t[-1]["partial"] == (total % items != 0)
+        assert sum(x["vec_quads"] for x in t) == total // items
+        assert all(x["staged"] for x in t)
+    assert m["total-1"][0]["vec_quads"] == 0 and m["total-4"][0]["scalar_quads"] == 0
+    assert [x["k0_in_row"] for x in m["parent-starts-at-tile-boundary"]] == [0, 0]
+    assert m["parent-starts-at-tile-boundary"][1]["r_lo"] == 2
+    assert [x["k0_in_row"] for x in m["parent-straddles-two-tiles"]] == [0, 10]          # 10 of the row's 30 pieces lie in the first tile
+    assert R.tiles_of_row(cnt["parent-straddles-two-tiles"], 1) == 2
+    assert R.tiles_of_row(cnt["parent-straddles-five-tiles"], 1) == 5
+    assert [x["r_lo"] for x in m["parent-straddles-five-tiles"]] == [0, 1, 1, 1, 1]
+    for mod in (1, 2, 3):
+        t = m[f"total-mod-4-is-{mod}"]
+        assert t[-1]["k1"] % items == mod and t[-1]["partial"] and t[-1]["scalar_quads"] == 1
+    # unaligned outputs: no quad takes the 16-byte store, whichever of the three is off
+    for align in ((4, 0, 0), (0, 4, 0), (0, 0, 4), (4, 4, 4)):
+        t = R.fill_mirror(cnt["total-%d" % (4 * tile + 1)], align=align)
+        assert sum(x["vec_quads"] for x in t) == 0 and sum(x["scalar_quads"] for x in t) == tile + 1
