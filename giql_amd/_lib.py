@@ -41,6 +41,7 @@ SYMBOLS = [
     "giql_hip_nearest_k_dev", "giql_hip_stream_probe_dev", "giql_hip_host_pool_trim",
     "giql_hip_nearest32_dev", "giql_hip_index_create_dev", "giql_hip_index_destroy", "giql_hip_index_info",
     "giql_hip_inner_join_indexed_dev", "giql_hip_disjoin_plan_dev", "giql_hip_disjoin_fill_dev",
+    "giql_hip_contain_plan_dev", "giql_hip_contain_fill_dev",
 ]
 
 
@@ -193,6 +194,8 @@ def load() -> ctypes.CDLL:
     L.giql_hip_merge_pred_dev.argtypes = [vp, P(CSide), i32, i64, P(CPred), i32, vp, vp, vp, vp, i64, P(i64), vp]
     L.giql_hip_disjoin_plan_dev.argtypes = [vp, P(CSide), P(CSide), i32, P(i64), vp]
     L.giql_hip_disjoin_fill_dev.argtypes = [vp, vp, vp, vp, i64, vp]
+    L.giql_hip_contain_plan_dev.argtypes = [vp, P(CSide), P(CSide), i32, vp, P(i64)]
+    L.giql_hip_contain_fill_dev.argtypes = [vp, vp, vp, i64, vp]
     _lib = L
     return L
 

@@ -27,6 +27,7 @@
 #include "select_kernels.hip.h"
 #include "cluster_kernels.hip.h"
 #include "disjoin_kernels.hip.h"
+#include "contain_kernels.hip.h"
 #include "dev_common.hip.h"
 #include "join_kernels.hip.h"
 #include "onesweep.hip.h"
@@ -231,6 +232,26 @@ struct DisjoinPlan {
   u32* cbp = nullptr;        // indices of the covered breakpoints
 };
 
+// What contain_plan keeps for contain_fill (the per-row arrays inside the arena, the per-tile ones in ct_buf).  Dropped
+// by every call that claims the arena and by every call that reports stats (begin_call).
+struct ContainPlan {
+  bool planned = false;
+  giql_side outer, inner;
+  u32 n_o = 0, n_i = 0;
+  int form = 0;              // 0 general (candidate tiles), 1 uniform inner side (exact range + k_fill)
+  u64 n_cand = 0;            // T: candidates of the regular rows (general form)
+  u64 n_reg = 0, n_irr = 0;  // pairs of regular rows / pairs involving an irregular row
+  u32 n_tiles = 0;
+  SortBufs so, si;           // sorted (key, end, rid) of the outer / inner side in buffer 0
+  u32* lo = nullptr;         // first candidate per sorted outer row
+  u64* coff = nullptr;       // exclusive offsets of the rows' candidate counts (uniform form: of their pairs)
+  u32* ct_part = nullptr;    // first outer row per candidate tile
+  u64* tile_off = nullptr;   // exclusive pair offsets per candidate tile
+  u32* irr_o_list = nullptr;
+  u32* irr_i_list = nullptr;
+  u64* irr_off = nullptr;
+};
+
 struct giql_hip_ctx {
   explicit giql_hip_ctx(const Switches& s) : sw(s) {
     guess.local_sort = !s.no_local_sort;
@@ -242,6 +263,7 @@ struct giql_hip_ctx {
   CallState call;
   InnerPlan plan;
   DisjoinPlan dj;
+  ContainPlan ct;
 
   // device resources
   int device = 0;
@@ -256,6 +278,8 @@ struct giql_hip_ctx {
   size_t stage_out_cap = 0;
   char* xplan = nullptr;      // scratch of giql_hip_fill_from_plan_dev (offsets + scan partials), grown on demand
   size_t xplan_cap = 0;
+  char* ct_buf = nullptr;     // per-tile arrays of a CONTAINS plan (sized by its candidate total), grown on demand
+  size_t ct_buf_cap = 0;
   u64* d_scratch64 = nullptr;  // small device scratch (checksum)
   hipStream_t side_stream = nullptr;  // the second stream (SideChain)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -307,6 +331,7 @@ static int ensure_arena(giql_hip_ctx* ctx, size_t bytes, hipStream_t stream) {
   if (bytes <= ctx->arena_cap) return GIQL_OK;
   ctx->plan.planned = false;  // (giql_hip_reserve: a new arena holds no plan)
   ctx->dj.planned = false;
+  ctx->ct.planned = false;
   const size_t want = align_up(bytes + bytes / 8, (size_t)1 << 20);
   GIQL_TRY(grow_buffer((void**)&ctx->arena, &ctx->arena_cap, bytes, want, stream, "the workspace"));
   if (getenv("GIQL_HIP_DEBUG_ADDR")) fprintf(stderr, "[giql_hip] arena %p + %zu bytes\n", (void*)ctx->arena, want);
@@ -325,6 +350,7 @@ template <typename Carve>
 static int claim_arena(giql_hip_ctx* ctx, hipStream_t stream, Carve&& carve) {
   ctx->plan.planned = false;
   ctx->dj.planned = false;
+  ctx->ct.planned = false;
   GIQL_TRY(ensure_arena(ctx, carve(nullptr), stream));
   carve(ctx->arena);
   return GIQL_OK;
@@ -365,6 +391,7 @@ static void reset_stats(giql_hip_ctx* ctx) {
 
 static int begin_call(giql_hip_ctx* ctx) {
   HIP_TRY(hipSetDevice(ctx->device));
+  ctx->ct.planned = false;  // a CONTAINS plan does not outlive the next launching call
   reset_stats(ctx);
   return GIQL_OK;
 }
@@ -1269,6 +1296,7 @@ int giql_hip_destroy(giql_hip_ctx* ctx) {
   if (ctx->bucket_big) (void)hipFree(ctx->bucket_big);
   if (ctx->bucket_qwin) (void)hipFree(ctx->bucket_qwin);
   if (ctx->xplan) (void)hipFree(ctx->xplan);
+  if (ctx->ct_buf) (void)hipFree(ctx->ct_buf);
   if (ctx->h_meta) (void)hipHostFree(ctx->h_meta);
   delete ctx;
   return GIQL_OK;
@@ -3344,6 +3372,230 @@ int giql_hip_disjoin_fill_dev(giql_hip_ctx* ctx, int32_t* parent_out, int32_t* s
     hipLaunchKernelGGL(k_dj_fill, dim3((u32)n_tiles), dim3(DJ_FILL_NT), 0, st, view_of(P.target), P.chrom_base, P.off,
                        P.total, P.lo_first, P.bp, P.n_bp, P.ncov, P.cbp, vec, parent_out, start_out, end_out);
     GIQL_TRY(post_launch("disjoin fill"));
+  }
+  return GIQL_OK;
+}
+
+// ------------------------------------------------------- CONTAINS / WITHIN
+// contain(outer, inner): the pairs with the inner row inside the outer one (src/giql/expanders/intersects.py:155-166;
+// contain_kernels.hip.h).  Count-then-fill like the INNER pair.  Stages: spans of both sides on one axis -> ONE read of
+// the length ranges (the form) -> linearize + (key, end, rid) sort of both sides -> candidate range per sorted outer
+// row -> u64 offsets; then either the INNER join's k_partition + k_fill tail (uniform inner side: the range is exact)
+// or the candidate-tile count -> u64 scan of the tile totals, with the candidate-tile fill in contain_fill.
+struct ContainBufs {
+  LinBufs lb;
+  OsScratch os_o, os_i;
+  u32 *wlo = nullptr, *cand = nullptr, *irr_cnt = nullptr;
+  u64* bsums = nullptr;
+};
+
+static int giql_hip_contain_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* o, const giql_side* in, int32_t n_chrom,
+                                          void* stream, int64_t* n_pairs) {
+  if (!ctx || !n_pairs) return set_err(GIQL_ERR_INVALID, "ctx/n_pairs is NULL");
+  GIQL_TRY(check_side(o, "outer"));
+  GIQL_TRY(check_side(in, "inner"));
+  if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
+  GIQL_TRY(begin_call(ctx));
+  hipStream_t st = (hipStream_t)stream;
+  ctx->stats.n_a = o->n;
+  ctx->stats.n_b = in->n;
+  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the other plans too)
+  ctx->dj.planned = false;
+  ContainPlan& P = ctx->ct;
+  P = ContainPlan{};
+  P.outer = *o;
+  P.inner = *in;
+  P.n_o = (u32)o->n;
+  P.n_i = (u32)in->n;
+  *n_pairs = 0;
+  if (o->n == 0 || in->n == 0) {  // nothing to launch
+    P.planned = true;
+    return GIQL_OK;
+  }
+  if (n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
+  const size_t no = (size_t)o->n, ni = (size_t)in->n, nq = no + ni;
+  if (no > OS_MAX_ROWS || ni > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
+  constexpr u32 TQ = RC_NT * RC_ITEMS_C2;
+  const u32 nt = cdiv(no, TQ);
+  ContainBufs W;
+  auto carve = [&](char* base) {
+    Carver c{base};
+    common_sizes(c, n_chrom, W.lb);
+    sort_sizes(c, no, P.so, true);
+    sort_sizes(c, ni, P.si, true);
+    os_scratch_sizes(c, no, W.os_o);
+    os_scratch_sizes(c, ni, W.os_i);
+    P.irr_o_list = c.take<u32>(no);
+    P.irr_i_list = c.take<u32>(ni);
+    W.wlo = c.take<u32>((size_t)nt + 2);
+    P.lo = c.take<u32>(no);
+    W.cand = c.take<u32>(no);
+    P.coff = c.take<u64>(no + 1);
+    W.irr_cnt = c.take<u32>(nq);
+    P.irr_off = c.take<u64>(nq + 1);
+    W.bsums = c.take<u64>(cdiv(nq, SCAN_TILE) + 2);
+    return c.off;
+  };
+  GIQL_TRY(claim_arena(ctx, st, carve));
+  GIQL_TRY(run_spans(ctx, st, *o, *in, n_chrom, W.lb));
+  // the ONE read that decides the form (and reports a bad chromosome id or an axis past 32 bits before anything is
+  // sorted).  Uniform inner side: min == max canonical length > 0 over ALL its rows -- a single irregular row makes
+  // the minimum 0 (decide_form).
+  GIQL_TRY(read_meta(ctx, st));
+  ctx->guess.last_span = ctx->h_meta->total_span;  // known before anything is sorted: the sort form follows the real density
+  const i64 uni_len = ctx->sw.no_uniform ? 0 : uniform_len_b(*ctx->h_meta);
+  P.form = uni_len > 0 ? 1 : 0;
+  GIQL_TRY(run_linearize(ctx, st, *o, n_chrom, W.lb, P.so.key[0], P.so.end[0], P.irr_o_list, 0, 0, W.os_o.hist,
+                         W.os_o.gbase));
+  GIQL_TRY(run_sort_onesweep(ctx, st, P.so, (u32)no, W.os_o.gbase, W.os_o.status));
+  if (P.form == 1) {
+    // every inner row is regular and uni_len long: keys and row ids only, its `end` column is not read again
+    P.si.end[0] = P.si.end[1] = nullptr;
+    GIQL_TRY(run_linearize(ctx, st, *in, n_chrom, W.lb, P.si.key[0], nullptr, P.irr_i_list, 1, 0, W.os_i.hist,
+                           W.os_i.gbase, nullptr, nullptr, /*skip_end=*/true));
+  } else {
+    GIQL_TRY(run_linearize(ctx, st, *in, n_chrom, W.lb, P.si.key[0], P.si.end[0], P.irr_i_list, 1, 0, W.os_i.hist,
+                           W.os_i.gbase));
+  }
+  GIQL_TRY(run_sort_onesweep(ctx, st, P.si, (u32)ni, W.os_i.gbase, W.os_i.status));
+  const u32* irr_o = &ctx->d_meta->irr_a;
+  const u32* irr_i = &ctx->d_meta->irr_b;
+  {
+    // Candidates of a sorted outer row c: the inner keys in [c.key, c.endkey) -- the class-1 range, lo_off = 0 (uniform
+    // form: in [c.key, c.endkey - L + 1), which is exact).  The range cannot leak into the next chromosome:
+    // k_chrom_offsets gives each chromosome max - min + 1 positions over both sides, so an end key never reaches the
+    // next chromosome's base and every inner key below c.endkey lies on c's chromosome.
+    Phase ph(ctx, st, GIQL_PH_COUNT, 2);
+    ctx->stats.phase_bytes[GIQL_PH_COUNT] += (int64_t)16 * no + (int64_t)4 * ni;  // keys + ends read, lo + cand written; the inner keys
+    hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)nt + 1, 256)), dim3(256), 0, st, P.so.key[0], (u32)no, irr_o,
+                       P.si.key[0], (u32)ni, irr_i, (i64)0, TQ, nt, W.wlo);
+    if (P.form == 1)
+      hipLaunchKernelGGL((k_contain_range_count<RC_ITEMS_C2, RC_LDS_CAP>), dim3(nt), dim3(RC_NT), 0, st, P.so.key[0],
+                         P.so.end[0], (u32)no, irr_o, P.si.key[0], (u32)ni, irr_i, (i64)1 - uni_len, W.wlo, P.lo, W.cand);
+    else
+      hipLaunchKernelGGL((k_range_count<RC_ITEMS_C2, RC_LDS_CAP>), dim3(nt), dim3(RC_NT), 0, st, P.so.key[0],
+                         P.so.end[0], (u32)no, irr_o, P.si.key[0], (u32)ni, irr_i, (i64)0, W.wlo, P.lo, W.cand);
+    GIQL_TRY(post_launch("contain range count"));
+  }
+  // uniform form: the counts are the pairs (n_out); general form: the candidates (n_out_c1)
+  GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, W.cand, (u64)no, P.coff, W.bsums, P.coff + no,
+                         P.form == 1 ? &ctx->d_meta->n_out : &ctx->d_meta->n_out_c1));
+  GIQL_TRY(read_meta(ctx, st));
+  if (P.form == 1) {
+    P.n_reg = ctx->h_meta->n_out;
+  } else {
+    P.n_cand = ctx->h_meta->n_out_c1;
+    const u64 n_tiles = (P.n_cand + CT_TILE - 1) / CT_TILE;
+    if (n_tiles > 0x7FFFFFFFull)
+      return set_err(GIQL_ERR_CAPACITY, "%llu candidate pairs: more than one launch holds", (unsigned long long)P.n_cand);
+    P.n_tiles = (u32)n_tiles;
+    if (n_tiles > 0) {
+      u32* tile_cnt = nullptr;
+      u64* bsums_t = nullptr;
+      auto carve_t = [&](char* base) {
+        Carver c{base};
+        P.ct_part = c.take<u32>((size_t)n_tiles + 2);
+        tile_cnt = c.take<u32>((size_t)n_tiles);
+        P.tile_off = c.take<u64>((size_t)n_tiles + 1);
+        bsums_t = c.take<u64>(cdiv(n_tiles, SCAN_TILE) + 2);
+        return c.off;
+      };
+      const size_t need = carve_t(nullptr);
+      GIQL_TRY(grow_buffer((void**)&ctx->ct_buf, &ctx->ct_buf_cap, need, need + need / 4, st, "the candidate tiles"));
+      carve_t(ctx->ct_buf);
+      {
+        Phase ph(ctx, st, GIQL_PH_PARTITION);
+        hipLaunchKernelGGL(k_partition, dim3(cdiv(n_tiles + 1, 256)), dim3(256), 0, st, P.coff, (u32)no, (u64)0, CT_TILE,
+                           P.n_tiles, P.ct_part);
+      }
+      {
+        Phase ph(ctx, st, GIQL_PH_COUNT);
+        // every candidate's inner end read once; the tiles' row records {offset, lo, end}; one total per tile
+        ctx->stats.phase_bytes[GIQL_PH_COUNT] += (int64_t)4 * (int64_t)P.n_cand + (int64_t)16 * no + (int64_t)4 * (int64_t)n_tiles;
+        hipLaunchKernelGGL(k_ct_count, dim3(P.n_tiles), dim3(CT_NT), 0, st, P.coff, P.lo, P.so.end[0], (u32)no,
+                           P.si.end[0], P.ct_part, P.n_cand, tile_cnt);
+        GIQL_TRY(post_launch("contain tile count"));
+      }
+      GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, tile_cnt, n_tiles, P.tile_off, bsums_t, P.tile_off + n_tiles,
+                             &ctx->d_meta->n_out));
+      GIQL_TRY(read_meta(ctx, st));
+      P.n_reg = ctx->h_meta->n_out;
+    }
+  }
+  ctx->stats.n_irregular_a = ctx->h_meta->irr_a;
+  ctx->stats.n_irregular_b = ctx->h_meta->irr_b;
+  if (ctx->h_meta->irr_a + ctx->h_meta->irr_b > 0) {
+    {
+      Phase ph(ctx, st, GIQL_PH_IRREGULAR);
+      ctx->stats.phase_bytes[GIQL_PH_IRREGULAR] += (int64_t)16 * (int64_t)nq;  // three columns read, one count written (+ the listed rows)
+      hipLaunchKernelGGL(k_contain_irr_count, dim3(cdiv(nq, 256)), dim3(256), 0, st, view_of(*o), view_of(*in),
+                         P.irr_o_list, P.irr_i_list, ctx->d_meta, W.irr_cnt);
+      GIQL_TRY(post_launch("contain irregular count"));
+    }
+    GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_IRREGULAR, W.irr_cnt, (u64)nq, P.irr_off, W.bsums, P.irr_off + nq,
+                           &ctx->d_meta->n_out_irr));
+    GIQL_TRY(read_meta(ctx, st));
+    P.n_irr = ctx->h_meta->n_out_irr;
+  }
+  collect_spans(ctx);
+  ctx->stats.reserved = P.form;  // join_form: 0 general (candidate tiles), 1 uniform inner side
+  ctx->stats.n_out = (int64_t)(P.n_reg + P.n_irr);
+  ctx->stats.span = (int64_t)ctx->h_meta->total_span;
+  *n_pairs = (int64_t)(P.n_reg + P.n_irr);
+  P.planned = true;
+  return GIQL_OK;
+}
+
+int giql_hip_contain_plan_dev(giql_hip_ctx* ctx, const giql_side* outer, const giql_side* inner, int32_t n_chrom,
+                              void* stream, int64_t* n_pairs) {
+  return with_order_fallback(ctx, [&] { return giql_hip_contain_plan_dev_impl(ctx, outer, inner, n_chrom, stream, n_pairs); });
+}
+
+int giql_hip_contain_fill_dev(giql_hip_ctx* ctx, int32_t* row_outer, int32_t* row_inner, int64_t capacity,
+                              void* stream) {
+  if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
+  const ContainPlan& P = ctx->ct;
+  if (!P.planned) return set_err(GIQL_ERR_STATE, "contain_fill without a successful contain_plan");
+  const u64 total = P.n_reg + P.n_irr;
+  if (total == 0) return GIQL_OK;
+  if (!row_outer || !row_inner) return set_err(GIQL_ERR_INVALID, "row_outer/row_inner is NULL");
+  if (capacity < 0 || (u64)capacity < total)
+    return set_err(GIQL_ERR_CAPACITY, "capacity %lld < %llu pairs", (long long)capacity, (unsigned long long)total);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (P.n_reg > 0 && P.form == 1) {
+    constexpr u32 T2 = FILL_NT * FILL_ITEMS_C2;
+    const u64 nt64 = (P.n_reg + T2 - 1) / T2;
+    if (nt64 > 0x7FFFFFF0ull)
+      return set_err(GIQL_ERR_CAPACITY, "%llu pairs: more than one fill launch holds", (unsigned long long)P.n_reg);
+    const u32 ntf = (u32)nt64;
+    GIQL_TRY(grow_part(ctx, (size_t)ntf + 2, st));
+    {
+      Phase ph(ctx, st, GIQL_PH_PARTITION);
+      hipLaunchKernelGGL(k_partition, dim3(cdiv((u64)ntf + 1, 256)), dim3(256), 0, st, P.coff, P.n_o, (u64)0, T2, ntf,
+                         ctx->part);
+    }
+    Phase ph(ctx, st, GIQL_PH_FILL);
+    ctx->stats.phase_bytes[GIQL_PH_FILL] += (int64_t)12 * (int64_t)P.n_reg + (int64_t)16 * P.n_o;  // rid gather + two outputs; the row records
+    hipLaunchKernelGGL((k_fill<FILL_ITEMS_C2>), dim3(ntf), dim3(FILL_NT), 0, st, P.coff, P.lo, P.so.rid[0], P.n_o,
+                       P.si.rid[0], ctx->part, (u64)0, P.n_reg, row_outer, row_inner);
+    GIQL_TRY(post_launch("contain fill (uniform inner side)"));
+  } else if (P.n_reg > 0) {
+    Phase ph(ctx, st, GIQL_PH_FILL);
+    // the count pass's reads again + the tile offsets, a rid gather and two outputs per pair
+    ctx->stats.phase_bytes[GIQL_PH_FILL] += (int64_t)4 * (int64_t)P.n_cand + (int64_t)20 * P.n_o +
+                                            (int64_t)8 * P.n_tiles + (int64_t)12 * (int64_t)P.n_reg;
+    hipLaunchKernelGGL(k_ct_fill, dim3(P.n_tiles), dim3(CT_NT), 0, st, P.coff, P.lo, P.so.end[0], P.so.rid[0], P.n_o,
+                       P.si.end[0], P.si.rid[0], P.ct_part, P.n_cand, P.tile_off, row_outer, row_inner);
+    GIQL_TRY(post_launch("contain fill (candidate tiles)"));
+  }
+  if (P.n_irr > 0) {
+    Phase ph(ctx, st, GIQL_PH_IRREGULAR);
+    ctx->stats.phase_bytes[GIQL_PH_IRREGULAR] += (int64_t)8 * (int64_t)P.n_irr + (int64_t)20 * ((int64_t)P.n_o + P.n_i);
+    hipLaunchKernelGGL(k_contain_irr_fill, dim3(cdiv((u64)P.n_o + P.n_i, 256)), dim3(256), 0, st, view_of(P.outer),
+                       view_of(P.inner), P.irr_o_list, P.irr_i_list, ctx->d_meta, P.irr_off, row_outer + P.n_reg,
+                       row_inner + P.n_reg);
+    GIQL_TRY(post_launch("contain irregular fill"));
   }
   return GIQL_OK;
 }

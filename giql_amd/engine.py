@@ -718,6 +718,53 @@ class HipEngine:
                                                          outs[2].data_ptr(), rows, self._stream()))
         return tuple(outs)
 
+    # ------------------------------------------------------ CONTAINS / WITHIN
+    def contain_plan(self, outer: DeviceSide, inner: DeviceSide, n_chrom: int) -> int:
+        self._check_sides(outer, inner)
+        n = ctypes.c_int64(0)
+        co, ci = outer.c_struct(), inner.c_struct()
+        _lib.check(self._L.giql_hip_contain_plan_dev(self._h, ctypes.byref(co), ctypes.byref(ci), int(n_chrom),
+                                                     self._stream(), ctypes.byref(n)))
+        self._keepalive = (outer, inner)
+        return int(n.value)
+
+    def contain_fill(self, row_outer, row_inner) -> None:
+        torch = _torch()
+        cap = min(int(row_outer.shape[0]), int(row_inner.shape[0]))
+        _lib.check(self._L.giql_hip_contain_fill_dev(
+            self._h, self._dev_ptr(row_outer, "row_outer", torch.int32),
+            self._dev_ptr(row_inner, "row_inner", torch.int32), cap, self._stream()))
+
+    def contain_join(self, outer: DeviceSide, inner: DeviceSide, n_chrom: int):
+        """All ``(row_outer, row_inner)`` with ``outer CONTAINS inner`` -- same chromosome,
+        ``outer.start <= inner.start`` and ``outer.end >= inner.end`` on canonical coordinates
+        (``src/giql/expanders/intersects.py:155-166``); two int32 device tensors of the exact size, pairs in no
+        particular order.  ``x WITHIN y`` is ``contain_join(y, x)`` with the result columns exchanged.  Zero-length
+        and inverted rows follow the literal predicate.  ``stats()["join_form"]`` tells the path: ``"uniform_b"``
+        when every inner row has one length (the range of starts is exact), else ``"general"``."""
+        torch = _torch()
+        try:
+            return self._contain_once(outer, inner, n_chrom)
+        except _lib.GiqlHipError as exc:
+            if exc.code != _lib.GIQL_ERR_SPAN:
+                raise
+        # a genome longer than the 32-bit axis: chromosome groups are independent units
+        parts = [(ro[po.long()].to(torch.int32), ri[pi.long()].to(torch.int32)) for ro, ri, (po, pi) in
+                 self._retry_by_groups(lambda so, si: self._contain_once(so, si, n_chrom), outer, inner, n_chrom)]
+        if not parts:
+            z = torch.empty(0, dtype=torch.int32, device=self.device)
+            return z, z.clone()
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+    def _contain_once(self, outer: DeviceSide, inner: DeviceSide, n_chrom: int):
+        torch = _torch()
+        n = self.contain_plan(outer, inner, n_chrom)
+        row_outer = torch.empty(n, dtype=torch.int32, device=self.device)
+        row_inner = torch.empty(n, dtype=torch.int32, device=self.device)
+        if n:
+            self.contain_fill(row_outer, row_inner)
+        return row_outer, row_inner
+
     def merge(self, s: DeviceSide, n_chrom: int, distance: int = 0, preds=None):
         """MERGE: ``(chrom, start, end, count)`` tensors of the merged regions ordered by
         (chrom, start) (``src/giql/expanders/merge.py:186-330``).  ``preds``: the ``predicate :=``

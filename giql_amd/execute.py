@@ -642,6 +642,18 @@ def _subset(eng: HipEngine, side: DeviceSide, ids):
     return DeviceSide(c, s, e, side.start_off, side.end_off)
 
 
+def _spatial_join(plan: JoinPlan, a: DeviceSide, b: DeviceSide, n_chrom: int, eng: HipEngine):
+    """The pairs ``(row_left, row_right)`` of an INNER plan's spatial predicate: INTERSECTS, or CONTAINS / WITHIN
+    (src/giql/expanders/intersects.py:155-166) through the one containment path, ``contain_join(outer, inner)`` --
+    WITHIN with the sides exchanged and the result columns exchanged back."""
+    if plan.predicate == "contains":
+        return eng.contain_join(a, b, n_chrom)
+    if plan.predicate == "within":
+        rb, ra = eng.contain_join(b, a, n_chrom)
+        return ra, rb
+    return eng.inner_join(a, b, n_chrom)
+
+
 def _join_with_residuals(plan: JoinPlan, lt, rt, a: DeviceSide, b: DeviceSide, n_chrom: int, eng: HipEngine):
     """INNER / SEMI / ANTI with residual predicates; returns device row ids.
 
@@ -666,7 +678,7 @@ def _join_with_residuals(plan: JoinPlan, lt, rt, a: DeviceSide, b: DeviceSide, n
         return rows if ids is None else eng.take([ids], rows)[0]
 
     if not semi or both:
-        ra, rb = eng.inner_join(a_sub, b_sub, n_chrom)
+        ra, rb = _spatial_join(plan, a_sub, b_sub, n_chrom, eng)
         ra, rb = globalise(ra, ids_a), globalise(rb, ids_b)
         if both:
             ra, rb = eng.select(rb_.preds(both), idx_a=ra.contiguous(), idx_b=rb.contiguous(),
@@ -1261,7 +1273,7 @@ def _join_piece(plan: JoinPlan, lt, rt, ia: np.ndarray, ib: np.ndarray, n_chrom:
         if plan.residuals:
             ra, rb = _join_with_residuals(plan, lt, rt, a, b, n_chrom, eng)
         else:
-            ra, rb = eng.inner_join(a, b, n_chrom)
+            ra, rb = _spatial_join(plan, a, b, n_chrom, eng)
         if return_indices:
             return ra.cpu().numpy(), rb.cpu().numpy()
         idx = {"l": ra, "r": rb}
@@ -1451,7 +1463,11 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
             raise ValueError(f"table {side.table!r} was not provided")
     lt, rt = tables[plan.left.table], tables[plan.right.table]
     pins = {"l": pinned.get(plan.left.table), "r": pinned.get(plan.right.table)}
-    if (plan.kind == "INNER" and not plan.residuals and not (devices and len(devices) > 1)
+    if plan.predicate != "intersects" and devices is not None and len(devices) > 1:
+        # one device, like DISJOIN: the per-chromosome fan-out shards an INTERSECTS join
+        raise ValueError(f"{plan.predicate.upper()} joins run on one device; devices={devices!r} names {len(devices)}")
+    if (plan.kind == "INNER" and plan.predicate == "intersects" and not plan.residuals
+            and not (devices and len(devices) > 1)
             and any(p is not None and p.index for p in pins.values())):
         # a pinned table offers an index: the join reads it instead of spanning and sorting that table again
         got = _indexed_inner(plan, lt, rt, pins, eng)

@@ -15,6 +15,9 @@ PLAN_PREFIX = "GIQL-HIP-PLAN/1 "
 
 KINDS = ("INNER", "SEMI", "ANTI", "NEAREST", "COUNT", "CLUSTER", "MERGE", "FILTER", "DISJOIN")
 
+#: the spatial predicate of an INNER plan
+PREDICATES = ("intersects", "contains", "within")
+
 #: the three columns DISJOIN appends to the target's row (src/giql/expanders/disjoin.py:191-198)
 DISJOIN_COLUMNS = ("disjoin_chrom", "disjoin_start", "disjoin_end")
 
@@ -126,10 +129,18 @@ class JoinPlan:
     limit: int | None = None
     offset: int | None = None
     output: tuple[str, ...] = field(default_factory=tuple)         # final column names in SELECT order (grouped plans)
+    # INNER only: the join's spatial predicate, left <predicate> right (src/giql/expanders/intersects.py:149-166).
+    # "contains" / "within" run HipEngine.contain_join; plan strings written before the field existed load as
+    # "intersects"
+    predicate: str = "intersects"
 
     def __post_init__(self) -> None:
         if self.kind not in KINDS:
             raise ValueError(f"unknown plan kind {self.kind!r}")
+        if self.predicate not in PREDICATES:
+            raise ValueError(f"unknown join predicate {self.predicate!r}")
+        if self.predicate != "intersects" and self.kind != "INNER":
+            raise ValueError(f"predicate {self.predicate!r} needs an INNER plan, not {self.kind}")
 
     def to_dict(self) -> dict:
         """The plan as plain JSON-able data (what :meth:`to_string` serialises)."""
@@ -169,7 +180,8 @@ class JoinPlan:
                          for h in d.get("having", ())),
             group_by=tuple(d.get("group_by", ())),
             order_by=tuple((o[0], bool(o[1]), bool(o[2]) if len(o) > 2 else not bool(o[1])) for o in d.get("order_by", ())),
-            limit=d.get("limit"), offset=d.get("offset"), output=tuple(d.get("output", ())))
+            limit=d.get("limit"), offset=d.get("offset"), output=tuple(d.get("output", ())),
+            predicate=d.get("predicate", "intersects"))
 
 
 def is_plan_string(text) -> bool:

@@ -216,11 +216,11 @@ def _cond_tree(n, operand=None):
     if k == "paren":
         _only(n, ("this",), "parentheses")
         return _cond_tree(_arg(n, "this"), operand)
-    if k == "intersects":
+    if k in ("intersects", "contains", "within"):
         l, r = _arg(n, "this"), _arg(n, "expression")
         if _key(l) != "column" or _key(r) != "column":
-            raise decline("INTERSECTS operand that is not a column")
-        return ("leaf", ("intersects", _colref(l), _colref(r)))
+            raise decline(f"{k.upper()} operand that is not a column")
+        return ("leaf", (k, _colref(l), _colref(r)))
     if k in _CMP:
         return ("leaf", ("cmp", operand(_arg(n, "this")), _CMP[k], operand(_arg(n, "expression"))))
     if k == "between":
@@ -241,8 +241,6 @@ def _cond_tree(n, operand=None):
         if _key(_arg(n, "expression")) != "null" or x[0] == "lit":
             raise decline("IS predicate other than <column> IS [NOT] NULL")
         return ("leaf", ("cmp", x, "isnull", ("lit", 0)))
-    if k in ("contains", "within"):
-        raise decline(f"{k.upper()} predicate")
     raise decline(f"join condition of kind {k!r}")
 
 
@@ -331,10 +329,15 @@ def side_from_resolution(resolved, ref: TableRef, tables) -> PlanSide:
 
 
 # --------------------------------------------------------------- AST -> JoinShape -> plan
-def is_column_intersects(node) -> bool:
+def is_column_spatial(node, key: str = "intersects") -> bool:
+    """``<table>.<col> <key> <table>.<col>`` with ``key`` one of INTERSECTS / CONTAINS / WITHIN."""
     l, r = _arg(node, "this"), _arg(node, "expression")
-    return (_key(node) == "intersects" and _key(l) == "column" and _key(r) == "column"
+    return (_key(node) == key and _key(l) == "column" and _key(r) == "column"
             and _arg(l, "table") is not None and _arg(r, "table") is not None)
+
+
+def is_column_intersects(node) -> bool:
+    return is_column_spatial(node, "intersects")
 
 
 def has_sibling_spatial_predicate(node, root) -> bool:
@@ -562,13 +565,15 @@ def make_disjoin_expander(fallback, make_command):
     return expand_disjoin_hip
 
 
-def make_expander(fallback, make_command):
+def make_expander(fallback, make_command, key: str = "intersects"):
     """The ``(HipTarget, Intersects)`` expander with its two giql-side effects injected:
     ``fallback(node, ctx)`` = ``_expand_spatial_op(node, ctx, "intersects")`` and
-    ``make_command(payload)`` = ``exp.Command(this=payload)``."""
+    ``make_command(payload)`` = ``exp.Command(this=payload)``.  ``key`` = "contains" / "within": the same expander
+    for the ``Contains`` / ``Within`` nodes (a column-to-column join becomes an INNER plan with that predicate;
+    everything else falls back to the generic expansion, src/giql/expanders/intersects.py:155-166)."""
 
     def expand_intersects_hip(node, ctx):
-        if is_column_intersects(node):
+        if is_column_spatial(node, key):
             root = _root(node)
             if _key(root) == "select" and not has_sibling_spatial_predicate(node, root):
                 try:
@@ -609,6 +614,18 @@ if HAVE_GIQL:  # the registration itself needs the real package
     expand_intersects_hip = register(HipTarget, Intersects)(
         make_expander(lambda node, ctx: _expand_spatial_op(node, ctx, "intersects"),
                       lambda payload: exp.Command(this=payload)))
+
+    try:
+        from giql.expressions import Contains, Within
+
+        expand_contains_hip = register(HipTarget, Contains)(
+            make_expander(lambda node, ctx: _expand_spatial_op(node, ctx, "contains"),
+                          lambda payload: exp.Command(this=payload), "contains"))
+        expand_within_hip = register(HipTarget, Within)(
+            make_expander(lambda node, ctx: _expand_spatial_op(node, ctx, "within"),
+                          lambda payload: exp.Command(this=payload), "within"))
+    except ImportError:  # a giql without the two operators
+        pass
 
     try:
         from giql.expanders.disjoin import expand_disjoin as _expand_disjoin_generic

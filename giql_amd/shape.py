@@ -47,10 +47,15 @@ def decline(reason: str) -> HipDeclined:
 
 # ------------------------------------------------------- boolean conditions -> CNF
 # Both front ends hand a condition over as a tree -- ("leaf", term) | ("and", [nodes]) |
-# ("or", [nodes]) | ("not", node), a term being ("intersects", ...), ("intersects_lit", ...)
+# ("or", [nodes]) | ("not", node), a term being a spatial predicate (SPATIAL_TERMS: ("intersects", ...),
+# ("contains", ...), ("within", ...), or their literal-range forms ("intersects_lit", ...) ...)
 # or ("cmp", lhs, op, rhs) -- and get the terms of its conjunctive normal form back: the
 # select kernel evaluates an AND of ORs (include/giql_hip.h, giql_pred.group).  The
 # reference inlines such extras as SQL text (_classify_extras, intersects_duckdb.py:889-912).
+#: the column-to-column spatial predicates a join may carry (src/giql/expanders/intersects.py:149-166): a term
+#: (name, ColRef, ColRef) read "lhs <name> rhs"
+SPATIAL_TERMS = ("intersects", "contains", "within")
+_FLIPPED = {"intersects": "intersects", "contains": "within", "within": "contains"}
 NEGATED_OP = {"=": "!=", "!=": "=", "<": ">=", ">=": "<", ">": "<=", "<=": ">", "isnull": "notnull",
               "notnull": "isnull"}
 MAX_CONDITION_LEAVES = 12   # a select call takes 16 predicates; a literal-range filter adds three of its own
@@ -634,14 +639,21 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
     on_terms, where_terms = list(shape.on_terms), list(shape.where_terms)
     if not shape.on_seen and not shape.using and kind in ("SEMI", "ANTI"):
         raise decline("SEMI/ANTI join with its INTERSECTS outside ON")  # #201
-    n_int = sum(t[0] == "intersects" for t in on_terms + where_terms)
-    if n_int == 0:
+    spatial = [t for t in on_terms + where_terms if t[0] in SPATIAL_TERMS]
+    if not spatial:
         raise decline("join without an INTERSECTS predicate")
-    if n_int > 1:
-        raise decline("more than one INTERSECTS")
+    if len(spatial) > 1:
+        raise decline("more than one INTERSECTS" if all(t[0] == "intersects" for t in spatial)
+                      else "more than one spatial predicate in a join")
+    predicate, lhs, rhs = spatial[0]
+    if predicate != "intersects":
+        # CONTAINS / WITHIN run as the pair-producing join only (HipEngine.contain_join)
+        if kind in ("SEMI", "ANTI"):
+            raise decline(f"{kind} join over {predicate.upper()}")
+        if kind == "COUNT":
+            raise decline(f"count_overlaps over {predicate.upper()}")
     if kind in ("SEMI", "ANTI") and not any(t[0] == "intersects" for t in on_terms):
         raise decline("SEMI/ANTI join with its INTERSECTS outside ON")  # #201
-    _, lhs, rhs = [t for t in on_terms + where_terms if t[0] == "intersects"][0]
     cmp_terms = ([("on", t) for t in on_terms if t[0] in ("cmp", "or", "tree")]
                  + [("where", t) for t in where_terms if t[0] in ("cmp", "or", "tree")])
     if kind == "COUNT" and (cmp_terms or where_terms):
@@ -662,11 +674,12 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
         l_col, r_col = lhs.column, rhs.column
     elif ra == left.alias and la == right.alias:
         l_col, r_col = rhs.column, lhs.column
+        predicate = _FLIPPED[predicate]     # the plan states it as left <predicate> right
     else:
         raise decline("INTERSECTS operands that do not name the two joined tables")
     if l_col != genomic_col(left.table, tables) or r_col != genomic_col(right.table, tables):
         raise ValueError(
-            f"INTERSECTS operands must be the tables' genomic columns "
+            f"{spatial[0][0].upper()} operands must be the tables' genomic columns "
             f"({genomic_col(left.table, tables)!r} / {genomic_col(right.table, tables)!r})")
     if kind == "COUNT":
         if shape.distinct:
@@ -694,7 +707,7 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
     residuals = resolve_residuals(cmp_terms, left, right, kind)
     return JoinPlan(kind, left, right, tuple(proj) + hidden, shape.distinct, residuals=residuals,
                     aggregates=aggs, group_by=groups, having=having, order_by=order,
-                    limit=shape.limit, offset=shape.offset, output=output)
+                    limit=shape.limit, offset=shape.offset, output=output, predicate=predicate)
 
 
 # ------------------------------------------------------------------ DISJOIN

@@ -43,7 +43,7 @@ from .shape import condition_terms as _condition_terms
 from .shape import operand_sides as _operand_sides
 from .shape import decline as _decline
 from .shape import genomic_col as _genomic_col
-from .shape import DisjoinShape, lower_disjoin_shape, lower_join_shape, resolve_projection
+from .shape import SPATIAL_TERMS, DisjoinShape, lower_disjoin_shape, lower_join_shape, resolve_projection
 from .shape import norm as _norm
 from .shape import table_side as _table_side
 from .table import Table, Tables, build_tables, encoding_of
@@ -291,7 +291,18 @@ def _parse_predicate(p: _Parser, allow_literal: bool, operand=None):
             raise _decline("INTERSECTS operand that is not a column")
         return ("leaf", ("intersects", lhs[1], p.colref()))
     if p.at_kw("CONTAINS", "WITHIN"):
-        raise _decline(f"{p.peek().text} predicate")
+        word = p.next().text.upper()
+        if lhs[0] != "col":
+            raise _decline(f"{word} with a literal on the left")
+        if p.peek().kind == "str":
+            if not allow_literal:
+                raise _decline(f"literal-range {word} inside a join")
+            return ("leaf", (word.lower() + "_lit", lhs[1], p.next().text))
+        if p.at_kw("ANY", "ALL"):
+            raise _decline(f"{word} ANY/ALL")
+        if p.peek().kind != "id":
+            raise _decline(f"{word} operand that is not a column")
+        return ("leaf", (word.lower(), lhs[1], p.colref()))
     _no_arithmetic(p)
     negated = False
     if p.at_kw("NOT") and p.peek(1).kind == "kw" and p.peek(1).text in ("BETWEEN", "IN", "LIKE"):
@@ -601,6 +612,12 @@ def _literal_range_sql(p: _Parser, proj_text: str, from_ref: _TableRef, tables: 
             f"AND {q}\"{t.end_col}\" > {start})")
 
 
+# literal-range term -> (op on start, its bound, op on end, its bound)
+_LITERAL_TERMS = {"intersects_lit": ("<", "hi", ">", "lo"),
+                  "contains_lit": ("<=", "lo", ">=", "hi"),
+                  "within_lit": (">=", "lo", "<=", "hi")}
+
+
 def _is_single_table_filter(p: _Parser) -> bool:
     """``... FROM <one table> WHERE ...`` with a literal-range INTERSECTS and no join."""
     depth = 0
@@ -617,7 +634,7 @@ def _is_single_table_filter(p: _Parser) -> bool:
             elif seen_from and t.text in ("JOIN", "LATERAL"):
                 return False
             elif seen_from and t.text == "WHERE":
-                return any(a.kind == "kw" and a.text == "INTERSECTS" and b.kind == "str"
+                return any(a.kind == "kw" and a.text in ("INTERSECTS", "CONTAINS", "WITHIN") and b.kind == "str"
                            for a, b in zip(toks[k:], toks[k + 1:]))
         if depth == 0 and seen_from and t.kind == "punct" and t.text == ",":
             return False
@@ -663,8 +680,8 @@ def _lower_filter(p: _Parser, tbls: Tables) -> JoinPlan:
         raise _decline(f"trailing input near {p.peek().text!r}")
     side = _table_side(ref_t, tbls)
     table = tbls.get(ref_t.name) or Table(ref_t.name)
-    lits = [t for t in terms if t[0] == "intersects_lit"]
-    if len(lits) != 1 or any(t[0] == "intersects" for t in terms):
+    lits = [t for t in terms if t[0] in _LITERAL_TERMS]
+    if len(lits) != 1 or any(t[0] in SPATIAL_TERMS for t in terms):
         raise _decline("more than one spatial predicate")
 
     def own(refc: _ColRef) -> str:
@@ -672,7 +689,7 @@ def _lower_filter(p: _Parser, tbls: Tables) -> JoinPlan:
             raise ValueError(f"Unknown table qualifier {refc.table!r}; expected {side.alias!r}")
         return refc.column
 
-    _, col, text = lits[0]
+    lit_kind, col, text = lits[0]
     if own(col) != table.genomic_col:
         raise ValueError(f"{col.column!r} is not the genomic column of {ref_t.name}")
     m = re.match(r"^(?P<chr>[\w.]+):(?P<start>\d+)-(?P<end>\d+)$", text.strip())
@@ -683,9 +700,13 @@ def _lower_filter(p: _Parser, tbls: Tables) -> JoinPlan:
         raise ValueError(f"Start must be less than end: {lo} >= {hi}")
     if encoding_of(table) != ("0based", "half_open"):
         raise _decline("literal predicate over a non-canonical table")
+    # the three comparisons of _range_predicate (src/giql/expanders/intersects.py:101-129); its point-query form of
+    # CONTAINS (hi = lo + 1: end > lo) is end >= hi on integers
+    start_op, start_v, end_op, end_v = _LITERAL_TERMS[lit_kind]
+    bound = {"lo": lo, "hi": hi}
     residuals = [Residual("where", Operand("l", side.chrom_col), "=", Operand("str", m.group("chr"))),
-                 Residual("where", Operand("l", side.start_col), "<", Operand("int", hi)),
-                 Residual("where", Operand("l", side.end_col), ">", Operand("int", lo))]
+                 Residual("where", Operand("l", side.start_col), start_op, Operand("int", bound[start_v])),
+                 Residual("where", Operand("l", side.end_col), end_op, Operand("int", bound[end_v]))]
     residuals += _own_table_residuals([t for t in terms if t[0] in ("cmp", "or")], own)
     proj = []
     for refc, alias in items:

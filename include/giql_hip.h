@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define GIQL_HIP_ABI_VERSION 3  /* 2: giql_hip_stats.phase_bytes, pinned host outputs, plan export; 3: DISJOIN */
+#define GIQL_HIP_ABI_VERSION 4  /* 2: giql_hip_stats.phase_bytes, pinned host outputs, plan export; 3: DISJOIN; 4: CONTAINS / WITHIN */
 
 enum {
   GIQL_OK = 0,
@@ -282,6 +282,25 @@ int giql_hip_disjoin_plan_dev(giql_hip_ctx* ctx, const giql_side* target,
                               int64_t* n_out, void* stream);
 int giql_hip_disjoin_fill_dev(giql_hip_ctx* ctx, int32_t* parent_out, int32_t* start_out,
                               int32_t* end_out, int64_t capacity, void* stream);
+/* Column-to-column CONTAINS / WITHIN joins.  The reference lowers `x.interval CONTAINS y.interval` to the naive
+ * predicate  x.chrom = y.chrom AND x.start <= y.start AND x.end >= y.end  and WITHIN to the same with the operands
+ * exchanged (src/giql/expanders/intersects.py:155-166), on canonical 0-based half-open coordinates.  ONE device
+ * path, contain(outer, inner): the exact multiset of (outer row, inner row) pairs with the inner row inside the
+ * outer one, in unspecified order; WITHIN is the same call with the sides exchanged.  No row shape is excluded:
+ * zero-length and inverted rows (canonical end <= start) follow the literal predicate ([5,5) CONTAINS [5,5)).
+ *   plan: *n_pairs = the exact number of pairs (int64: it may pass 2^31).  giql_hip_stats.reserved bits 0-3 tell
+ *         the form: 0 = general (the candidates of every outer row -- the inner rows starting inside it -- are
+ *         filtered tile by tile), 1 = uniform inner side (every inner row regular and equally long: the range of
+ *         starts is exact and the INNER join's fill runs).  Empty sides give 0 pairs without a launch.
+ *   fill: row_outer[k] / row_inner[k] for k < n_pairs (capacity >= n_pairs, else GIQL_ERR_CAPACITY and the plan
+ *         stays valid).
+ * Both sides share one chromosome dictionary (GIQL_ERR_CHROM, GIQL_ERR_SPAN as for the INNER join).  The plan
+ * lives in the context: any other call that launches work drops it and fill returns GIQL_ERR_STATE; a contain
+ * plan likewise drops an INNER or DISJOIN plan (their fill and export entry points return GIQL_ERR_STATE). */
+int giql_hip_contain_plan_dev(giql_hip_ctx* ctx, const giql_side* outer, const giql_side* inner,
+                              int32_t n_chrom, void* stream, int64_t* n_pairs);
+int giql_hip_contain_fill_dev(giql_hip_ctx* ctx, int32_t* row_outer, int32_t* row_inner,
+                              int64_t capacity, void* stream);
 /* MERGE(..., predicate := ...): merge.py:201-210 hands the predicate to the CLUSTER it is built on, so a
  * merged region is a cluster of giql_hip_cluster_pred_dev; its MAX(end) is taken over the region's own
  * rows (a region may end while an earlier one still reaches further). */
