@@ -389,6 +389,51 @@ def test_disjoin(eng, name, enc, mode):
     assert not eng.stats()["sort_resorted"]
 
 
+# -------------------------------------------------------------- CONTAINS / WITHIN
+CONTAIN_LAYOUTS = ["tight_top", "one_chrom_max", "tight_over", "wide"]   # (tests/test_contain_gpu.py: the general form there)
+CONTAIN_L = 60
+
+
+def contain_sides(name, form):
+    """Outer rows with irregular ones among them; the inner side irregular rows too (general form) or every row
+    CONTAIN_L long.  ``make_side`` ends one row of each side exactly at the top of every chromosome: the inner one
+    ([hi - 100, hi), or [hi - CONTAIN_L, hi)) lies inside the outer one ([hi - 100, hi)) with equal ends."""
+    enc = ("1based", "closed")
+    a = make_side(name, enc, 1500, 21, irregular=60)
+    b = make_side(name, enc, 2500, 22, irregular=60) if form == "general" else make_side(name, enc, 2500, 22, uniform=CONTAIN_L)
+    return a, b
+
+
+@pytest.mark.parametrize("form", ["general", "uniform_b"])
+@pytest.mark.parametrize("name", CONTAIN_LAYOUTS)
+def test_contain(eng, name, form):
+    """Both forms of the containment join with keys up to 0xFFFFFFFE on every sort form: the general form's
+    ``inner end <= outer end`` and the uniform form's shifted upper key at the largest regular key."""
+    import _contain_ref as C
+
+    a, b = contain_sides(name, form)
+    da, db, n = dev(a), dev(b), len(LAYOUTS[name])
+    want = C.contain_pairs(a.chrom, a.cs, a.ce, b.chrom, b.cs, b.ce)
+    hi = LAYOUTS[name][n - 1][1]
+    top_o = np.nonzero((a.chrom == n - 1) & (a.ce == hi) & (a.cs < a.ce))[0]
+    top_i = np.nonzero((b.chrom == n - 1) & (b.ce == hi) & (b.cs < b.ce))[0]
+    assert want.shape[0] > 50 and (np.isin(want[:, 0], top_o) & np.isin(want[:, 1], top_i)).any()
+    if name in ("tight_top", "one_chrom_max"):      # both rows end at key 0xFFFFFFFE
+        base = sum(h - l + 1 for l, h in LAYOUTS[name][: n - 1]) - LAYOUTS[name][n - 1][0]
+        assert hi + base == TOP - 1
+    if name in FITS:
+        ro, ri = eng._contain_once(da, db, n)
+        st = eng.stats()
+        assert st["span"] == tight_span(name) and st["join_form"] == form, (name, st["span"], st["join_form"])
+        assert st["sort_local"] == (eng.kind != "default") and (eng.kind != "narrow" or st["bucket_bits"] == 13), st
+    else:
+        assert_span_error(lambda: eng.contain_plan(da, db, n))
+        ro, ri = eng.contain_join(da, db, n)
+    got = C.sort_pairs(np.stack([host(ro), host(ri)], 1))
+    assert eng.stats()["n_out"] > 0 and np.array_equal(got, want)
+    assert not eng.stats()["sort_resorted"]
+
+
 @pytest.mark.parametrize("enc", ENCODINGS, ids=lambda e: e[0])
 def test_disjoin_one_chromosome_past_32_bits_is_a_clean_error(eng, enc):
     from giql_amd import _lib

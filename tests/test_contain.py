@@ -225,50 +225,20 @@ def test_null_arguments_are_refused_before_any_device_work():
 
 
 # ------------------------------------------------------------------ the candidate tiles, mirrored in numpy
-def _mirror_general_form(outer, inner, tile, qcap):
-    """The general form's index arithmetic restated in numpy (contain_kernels.hip.h): candidate ranges of the sorted
-    outer rows, u64 offsets, ``k_partition``, then per tile the staged row records -- relative start clamped to
-    [0, tile_len], ``jbase = lo - (coff - tile base)`` modulo 2^32 -- the owner of candidate p as the LAST row with
-    rel <= p, the test ``inner_end[j] <= outer_end[q]``, and a slot = tile offset + rank among the tile's passing
-    candidates.  Returns the pairs in slot order and the number of tiles that took the search outside the stage."""
-    import numpy as np
-
-    (ok, oe_), (ik, ie_) = outer, inner
-    oo, io = np.argsort(ok, kind="stable"), np.argsort(ik, kind="stable")
-    qs, qe, ss, se = ok[oo], oe_[oo], ik[io], ie_[io]
-    lo = np.searchsorted(ss, qs, "left")
-    cand = np.searchsorted(ss, qe, "left") - lo
-    coff = np.concatenate([[0], np.cumsum(cand)]).astype(np.uint64)
-    total = int(coff[-1])
-    n_tiles = -(-total // tile)
-    part = [int(np.searchsorted(coff, np.uint64(t * tile), "right")) - 1 for t in range(n_tiles)] + [len(qs) - 1]
-    counts, tiles, unstaged = [], [], 0
-    for t in range(n_tiles):
-        start = t * tile
-        tile_len = min(tile, total - start)
-        qf, ql = part[t], min(part[t + 1], len(qs) - 1)
-        rows = np.arange(qf, ql + 1)
-        off = coff[rows].astype(np.int64)
-        rel = np.clip(off - start, 0, tile_len)
-        jbase = (lo[rows] - (off - start)) % 2**32
-        assert rel[0] == 0 and (rel[1:] >= 1).all()
-        unstaged += len(rows) > qcap
-        p = np.arange(tile_len)
-        k = np.searchsorted(rel, p, "right") - 1            # the last row with rel <= p
-        j = (jbase[k] + p) % 2**32
-        assert (j < len(ss)).all()
-        passing = se[j] <= qe[rows[k]]
-        counts.append(int(passing.sum()))
-        tiles.append(np.stack([oo[rows[k][passing]], io[j[passing]]], 1))
-    tile_off = np.concatenate([[0], np.cumsum(counts)])
-    out = np.zeros((int(tile_off[-1]), 2), np.int64)
-    for t, rows in enumerate(tiles):
-        out[tile_off[t]: tile_off[t] + len(rows)] = rows
-    return out, unstaged
+def _mirror_general_form(outer, inner, tile, qcap, n_waves, win):
+    """The general form's index arithmetic restated in numpy: ``_contain_ref.mirror_general_form`` (candidate ranges,
+    u64 offsets, ``k_partition``, the staged row records, the per-wave walk -- the first window's search, the ``k + 1``
+    test, the search from ``k + 2`` -- and the search of the offsets for a tile past the stage).  Returns the pairs in
+    slot order, the number of tiles that took the search outside the stage, and the per-tile records (row count,
+    staged or not, owners per window) the path tests assert reach with."""
+    pairs, info = R.mirror_general_form(outer, inner, tile, qcap, n_waves, win)
+    assert all(t["staged"] == (t["nqt"] <= qcap) and t["owners"].size == -(-t["tile_len"] // win) for t in info)
+    return pairs, sum(not t["staged"] for t in info), info
 
 
-@pytest.mark.parametrize("tile, qcap", [(64, 16), (7, 2), (16384, 4096)])
-def test_numpy_mirror_of_the_candidate_tiles_matches_the_brute_force(tile, qcap):
+@pytest.mark.parametrize("tile, qcap, n_waves, win", [(64, 16, 4, 4), (7, 2, 1, 1), (16384, 4096, 16, 64)],
+                         ids=["64-16", "7-2", "16384-4096"])
+def test_numpy_mirror_of_the_candidate_tiles_matches_the_brute_force(tile, qcap, n_waves, win):
     import numpy as np
 
     r = np.random.default_rng(tile)
@@ -279,8 +249,53 @@ def test_numpy_mirror_of_the_candidate_tiles_matches_the_brute_force(tile, qcap)
     oe[100:160] = os_[100:160] + 1
     is_ = r.integers(0, 5000, n_i)
     ie = is_ + r.integers(1, 200, n_i)
-    got, unstaged = _mirror_general_form((os_, oe), (is_, ie), tile, qcap)
+    got, unstaged, info = _mirror_general_form((os_, oe), (is_, ie), tile, qcap, n_waves, win)
     zeros = np.zeros
     want = R.contain_pairs(zeros(n_o, np.int64), os_, oe, zeros(n_i, np.int64), is_, ie)
     assert np.array_equal(R.sort_pairs(got), want) and want.shape[0] > 1000
     assert (unstaged > 0) == (qcap < 60)
+    # the walk met windows with one owner and windows in which the owner changes
+    owners = np.concatenate([t["owners"] for t in info if t["staged"]])
+    assert owners.min() == 1 and (owners.max() > 1 or win == 1)
+
+
+@pytest.mark.parametrize("cid", list(R.PATH_CASES))
+def test_every_path_case_reaches_its_path(cid):
+    """Each generator of tests/test_contain_paths.py, without a GPU: the mirror equals the brute force on it and shows
+    the path the case is named after (``_contain_ref.reach`` holds the assertions, the GPU tests call it too)."""
+    ev = R.reach(cid)
+    print(f"\n[{cid}] " + ", ".join(f"{k}={v}" for k, v in ev.items()))
+
+
+def test_sort_based_reference_equals_the_brute_force_on_seeded_tables():
+    """``contain_pairs_sorted`` (the truth of the cases the brute force would take minutes on) against
+    ``contain_pairs``: 240 seeded tables -- one to four chromosomes, zero-length and inverted rows on either side,
+    negative coordinates, duplicated rows -- and every fixture case, which covers the four encodings on both sides."""
+    import numpy as np
+
+    odd = 0
+    for seed in range(240):
+        r = np.random.default_rng(seed)
+        nch, n_o, n_i = 1 + seed % 4, int(r.integers(1, 250)), int(r.integers(1, 250))
+        lo = -500 if seed % 5 == 0 else 0
+        oc, ic = r.integers(0, nch, n_o), r.integers(0, nch, n_i)
+        os_, is_ = lo + r.integers(0, 1000, n_o), lo + r.integers(0, 1000, n_i)
+        oe, ie = os_ + r.integers(1, 300, n_o), is_ + r.integers(1, 80, n_i)
+        if seed % 3:                                     # irregular rows, and [p, p) inside [p, p)
+            for s, e in ((os_, oe), (is_, ie)):
+                bad = r.random(s.size) < 0.1
+                e[bad] = s[bad] - r.integers(0, 20, int(bad.sum()))
+            k = min(n_o, n_i, 5)
+            ic[:k], is_[:k], ie[:k] = oc[:k], os_[:k], np.minimum(oe[:k], os_[:k])
+            odd += int((oe <= os_).sum() > 0 and (ie <= is_).sum() > 0)
+        want = R.contain_pairs(oc, os_, oe, ic, is_, ie)
+        assert np.array_equal(R.contain_pairs_sorted(oc, os_, oe, ic, is_, ie), want), seed
+    assert odd >= 100
+    encodings = set()
+    for c in R.golden_cases():
+        ac, as_, ae, (aso, aeo), bc, bs, be, (bso, beo), _ = R.case_arrays(c)
+        a = (ac, as_.astype(np.int64) + aso, ae.astype(np.int64) + aeo)
+        b = (bc, bs.astype(np.int64) + bso, be.astype(np.int64) + beo)
+        assert R.contain_pairs_sorted(*a, *b).tolist() == c["contains"], c["id"]
+        encodings.add((tuple(c["enc_a"]), tuple(c["enc_b"])))
+    assert len(encodings) == 16

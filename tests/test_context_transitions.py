@@ -11,11 +11,14 @@ was found by a long random soak.  So here:
 * Walk 1: per operator family, one fresh context walks an Eulerian circuit of the complete directed graph over the
   input classes (self-loops included): every ordered pair (X, Y) is a call on Y right after the context's last call
   on X.  Each visit runs the family twice; the second run must reach the path its class names (``SIGNATURES``).
-* Walk 2: one context, all twelve operators and DISJOIN's three in a shuffled order per visit, with ``select`` /
-  ``take_utf8`` / a plan of the other operator put between some plans and their fill -- which must then refuse
-  (``GIQL_ERR_STATE``): those calls reuse the workspace the plan lives in.
+* Walk 2: one context, all twelve operators, DISJOIN's three and CONTAINS' three in a shuffled order per visit, with
+  ``select`` / ``take_utf8`` / a plan of another operator put between some plans and their fill -- which must then
+  refuse (``GIQL_ERR_STATE``): those calls reuse the workspace the plan lives in.
 * DISJOIN (self mode, reference mode, plan + fill through the raw ABI) walks the classes on which its path can
   differ, against the brute force of ``tests/_disjoin_ref.py``; its plan lives in the same workspace (``ctx->dj``).
+* CONTAINS / WITHIN (the join, the join with the sides exchanged, plan + fill through the raw ABI) walk the classes on
+  which its path can differ, against the brute force of ``tests/_contain_ref.py``; its plan is the third one kept on
+  the context (``ctx->ct``).
 * Leg 3: the sticky four-pass fallback after a bucket too large for the bucket stage, reached from every class.
 * Leg 4: production density on a default context: every ordered pair of bucket widths.
 
@@ -501,6 +504,77 @@ def op_disjoin_plan_fill(eng, name, log, fam, rnd, intruder=None):
 DISJOIN_OPS = [op_disjoin_self, op_disjoin_ref, op_disjoin_plan_fill]
 
 
+# ---- CONTAINS / WITHIN: outer = the class's A, inner = its B (WITHIN: the sides exchanged); truth = the brute force
+# of tests/_contain_ref.py, or its sort-based reference (anchored on the brute force in tests/test_contain.py) where
+# the brute force would take more than a few seconds
+CONTAIN_NAMES = ["general", "uniform_b", "irregular", "pileups", "many_chroms", "negative", "w15", "sparse"]
+CONTAIN_UNIFORM = {"contains": {"uniform_b", "long_rows", "w16", "sparse"}, "within": {"uniform_a"}}   # word -> classes whose inner side has one length
+CONTAIN_MAX_CELLS = 10**8
+
+
+@functools.lru_cache(maxsize=None)
+def want_contain(name, word):
+    import _contain_ref as C
+
+    a, b, _nch, _da, _db = resident(name)
+    i64 = lambda s: (s.chrom.astype(np.int64), s.cs.astype(np.int64), s.ce.astype(np.int64))
+    outer, inner = (i64(a), i64(b)) if word == "contains" else (i64(b), i64(a))
+    return C.truth(outer, inner, max_cells=CONTAIN_MAX_CELLS)
+
+
+def _contain_call(eng, name, log, fam, rnd, word):
+    _a, _b, nch, da, db = resident(name)
+    outer, inner = (da, db) if word == "contains" else (db, da)
+    ro, ri = eng.contain_join(outer, inner, nch)
+    log.add(eng, fam, name, rnd, word)
+    st = log.calls[-1][4]
+    w = want_contain(name, word)
+    assert st["n_out"] == w.shape[0] and np.array_equal(_pairs(ro, ri), w), (name, word)
+    # (the form is read back in every plan, never guessed: it holds on a first call after another class too)
+    assert st["join_form"] == ("uniform_b" if name in CONTAIN_UNIFORM[word] else "general"), (name, word, st["join_form"])
+
+
+def op_contain_join(eng, name, log, fam, rnd):
+    _contain_call(eng, name, log, fam, rnd, "contains")
+
+
+def op_contain_within(eng, name, log, fam, rnd):
+    _contain_call(eng, name, log, fam, rnd, "within")
+
+
+def _contain_plan_raw(eng, outer, inner, nch):
+    import ctypes
+
+    co, ci = outer.c_struct(), inner.c_struct()
+    n = ctypes.c_int64(-1)
+    rc = eng._L.giql_hip_contain_plan_dev(eng._h, ctypes.byref(co), ctypes.byref(ci), nch, eng._stream(), ctypes.byref(n))
+    return rc, n.value
+
+
+def op_contain_plan_fill(eng, name, log, fam, rnd, intruder=None):
+    from giql_amd import _lib
+
+    _a, _b, nch, da, db = resident(name)
+    w = want_contain(name, "contains")
+    rc, n = _contain_plan_raw(eng, da, db, nch)
+    log.add(eng, fam, name, rnd, "contain_plan")
+    assert (rc, n) == (0, w.shape[0]), (name, "contain plan", rc, n)
+    ro = torch.full((max(n, 8),), -7, dtype=torch.int32, device="cuda:0")
+    ri = torch.full((max(n, 8),), -7, dtype=torch.int32, device="cuda:0")
+    fill = lambda: eng._L.giql_hip_contain_fill_dev(eng._h, ro.data_ptr(), ri.data_ptr(), n, eng._stream())
+    if intruder is not None:
+        intruder(eng, name)          # reuses the workspace the plan lives in: the plan is gone
+        assert fill() == _lib.GIQL_ERR_STATE, (name, intruder.__name__)
+        assert b"without a successful contain_plan" in eng._L.giql_hip_last_error()
+        assert int((ro != -7).sum()) == 0 and int((ri != -7).sum()) == 0, (name, "a refused fill wrote")
+        assert _contain_plan_raw(eng, da, db, nch) == (0, n)
+    assert fill() == 0
+    assert np.array_equal(_pairs(ro[:n], ri[:n]), w), (name, "contain plan + fill")
+
+
+CONTAIN_OPS = [op_contain_join, op_contain_within, op_contain_plan_fill]
+
+
 FAMILIES = {
     "inner": [op_inner_join, op_into_exact, op_into_short, op_into_ample, op_plan_fill],
     "row": [op_semi, op_anti, op_count],
@@ -588,6 +662,38 @@ def test_walk_disjoin_every_ordered_pair_of_its_classes(monkeypatch):
     assert len(after) == len(DISJOIN_NAMES) - 1         # every other class was visited right after the refusals
 
 
+@pytest.mark.gpu
+def test_walk_contain_every_ordered_pair_of_its_classes(monkeypatch):
+    """The ``contain`` family: an Eulerian circuit over the classes on which CONTAINS' path can differ (65 visits) --
+    the general and the uniform form, irregular rows (part X and part Y of the literal predicate),
+    pile-ups of equal inner starts, many chromosomes, negative coordinates, one density that asks for narrow buckets
+    and one that asks for the four global passes.  contain_plan sets the density the next call's sort form follows
+    (``guess.last_span``) from its own spans, before it sorts: the settled call of a class takes the form of its own."""
+    eng = _density_engine(monkeypatch)
+    log = Log()
+    walk = eulerian_circuit(len(CONTAIN_NAMES))
+    assert len(walk) == 65
+    try:
+        for v in walk:
+            for rnd in (1, 2):
+                for op in CONTAIN_OPS:
+                    op(eng, CONTAIN_NAMES[v], log, "contain", rnd)
+    finally:
+        eng.close()
+    pairs = log.transitions("contain")
+    forms = sorted({(c[1], c[4]["sort_local"], c[4]["bucket_bits"] if c[4]["sort_local"] else None) for c in log.calls},
+                   key=str)
+    print(f"\n[contain] ordered class pairs covered: {len(pairs)} of {len(CONTAIN_NAMES) ** 2}; "
+          f"(class, three-stage sort, bucket bits) seen: {forms}")
+    assert pairs == {(x, y) for x in CONTAIN_NAMES for y in CONTAIN_NAMES}
+    assert not any(c[4]["sort_resorted"] for c in log.calls)
+    assert {c[4]["join_form"] for c in log.calls} == {"general", "uniform_b"}
+    assert all(c[4]["n_irregular_a"] + c[4]["n_irregular_b"] > 0 for c in log.calls if c[1] == "irregular")
+    settled = {c[1]: c[4] for c in log.calls if c[2] == 2 and c[3] == "contains"}
+    assert settled["w15"]["sort_local"] and settled["w15"]["bucket_bits"] == 15, settled["w15"]
+    assert not settled["sparse"]["sort_local"]
+
+
 # ---------------------------------------------------------------- Walk 2 (mixed operators, plans interrupted)
 def _intrude_select(eng, name):
     _a, _b, _nch, da, _db = resident(name)
@@ -618,9 +724,14 @@ def _intrude_disjoin_plan(eng, name):
     assert plan_raw(eng, da, db, nch) == (0, want_disjoin("general", "reference").shape[0])
 
 
+def _intrude_contain_plan(eng, name):
+    _a, _b, nch, da, db = resident("general")
+    assert _contain_plan_raw(eng, da, db, nch) == (0, want_contain("general", "contains").shape[0])
+
+
 INTRUDERS = {"select": _intrude_select, "take_utf8": _intrude_take_utf8, "inner_plan": _intrude_inner_plan,
-             "disjoin_plan": _intrude_disjoin_plan, None: None}
-MIXED_OPS = ALL_OPS + DISJOIN_OPS
+             "disjoin_plan": _intrude_disjoin_plan, "contain_plan": _intrude_contain_plan, None: None}
+MIXED_OPS = ALL_OPS + DISJOIN_OPS + CONTAIN_OPS
 
 
 @pytest.mark.gpu
@@ -630,25 +741,33 @@ def test_walk_mixed_operators_with_interrupted_plans(monkeypatch):
     r = np.random.default_rng(2027)
     visits = list(r.permutation(len(NAMES))) + list(r.permutation(len(NAMES)))
     interrupted = {"select": 0, "take_utf8": 0}
-    dj_interrupted = {"select": 0, "take_utf8": 0, "inner_plan": 0}
-    inner_by_disjoin = 0
+    dj_interrupted = {"select": 0, "take_utf8": 0, "inner_plan": 0, "contain_plan": 0}
+    ct_interrupted = {"select": 0, "take_utf8": 0, "inner_plan": 0, "disjoin_plan": 0}
+    inner_by_disjoin = inner_by_contain = 0
     try:
         for v in visits:
             name = NAMES[v]
             for k in r.permutation(len(MIXED_OPS)):
                 op = MIXED_OPS[k]
                 if op is op_plan_fill:
-                    which = ("select", "take_utf8", None, "disjoin_plan")[int(r.integers(0, 4))]
+                    which = ("select", "take_utf8", None, "disjoin_plan", "contain_plan")[int(r.integers(0, 5))]
                     op(eng, name, log, "mixed", 1, intruder=INTRUDERS[which])
                     if which == "disjoin_plan":
                         inner_by_disjoin += 1
+                    elif which == "contain_plan":
+                        inner_by_contain += 1
                     elif which:
                         interrupted[which] += 1
                 elif op is op_disjoin_plan_fill:
-                    which = ("select", "take_utf8", "inner_plan", None)[int(r.integers(0, 4))]
+                    which = ("select", "take_utf8", "inner_plan", None, "contain_plan")[int(r.integers(0, 5))]
                     op(eng, name, log, "mixed", 1, intruder=INTRUDERS[which])
                     if which and name != "irregular":
                         dj_interrupted[which] += 1
+                elif op is op_contain_plan_fill:
+                    which = ("select", "take_utf8", "inner_plan", "disjoin_plan", None)[int(r.integers(0, 5))]
+                    op(eng, name, log, "mixed", 1, intruder=INTRUDERS[which])
+                    if which:
+                        ct_interrupted[which] += 1
                 else:
                     op(eng, name, log, "mixed", 1)
     finally:
@@ -657,9 +776,11 @@ def test_walk_mixed_operators_with_interrupted_plans(monkeypatch):
     forms = sorted({(st["sort_local"], st["bucket_bits"]) for st in dj})
     print(f"\n[mixed] ordered class pairs covered: {len(log.transitions('mixed'))}; interrupted plans: {interrupted}; "
           f"DISJOIN plans interrupted: {dj_interrupted}; INNER plans interrupted by a DISJOIN plan: {inner_by_disjoin}; "
-          f"DISJOIN (three-stage sort, bucket bits) seen: {forms}")
+          f"DISJOIN (three-stage sort, bucket bits) seen: {forms}; CONTAINS plans interrupted: {ct_interrupted}; "
+          f"INNER plans interrupted by a CONTAINS plan: {inner_by_contain}")
     assert interrupted["select"] > 0 and interrupted["take_utf8"] > 0
     assert all(v > 0 for v in dj_interrupted.values()) and inner_by_disjoin > 0
+    assert all(v > 0 for v in ct_interrupted.values()) and inner_by_contain > 0
     # DISJOIN takes its bucket width from the span another operator left on the context: both sort forms were met
     assert any(st["sort_local"] for st in dj) and any(not st["sort_local"] for st in dj)
 
