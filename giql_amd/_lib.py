@@ -42,6 +42,7 @@ SYMBOLS = [
     "giql_hip_nearest32_dev", "giql_hip_index_create_dev", "giql_hip_index_destroy", "giql_hip_index_info",
     "giql_hip_inner_join_indexed_dev", "giql_hip_disjoin_plan_dev", "giql_hip_disjoin_fill_dev",
     "giql_hip_contain_plan_dev", "giql_hip_contain_fill_dev",
+    "giql_hip_window_plan_dev", "giql_hip_distance_dev",
 ]
 
 
@@ -196,6 +197,8 @@ def load() -> ctypes.CDLL:
     L.giql_hip_disjoin_fill_dev.argtypes = [vp, vp, vp, vp, i64, vp]
     L.giql_hip_contain_plan_dev.argtypes = [vp, P(CSide), P(CSide), i32, vp, P(i64)]
     L.giql_hip_contain_fill_dev.argtypes = [vp, vp, vp, i64, vp]
+    L.giql_hip_window_plan_dev.argtypes = [vp, P(CSide), P(CSide), i32, i64, vp, P(i64)]
+    L.giql_hip_distance_dev.argtypes = [vp, P(CSide), P(CSide), vp, vp, i64, vp, vp, i32, vp, vp, vp]
     _lib = L
     return L
 

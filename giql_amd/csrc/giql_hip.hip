@@ -28,6 +28,7 @@
 #include "cluster_kernels.hip.h"
 #include "disjoin_kernels.hip.h"
 #include "contain_kernels.hip.h"
+#include "distance_kernels.hip.h"
 #include "dev_common.hip.h"
 #include "join_kernels.hip.h"
 #include "onesweep.hip.h"
@@ -215,6 +216,7 @@ struct InnerPlan {
   u32* irr_a_list = nullptr;
   u32* irr_b_list = nullptr;
   u64* irr_off = nullptr;
+  i64 widen = -1;  // >= 0: a within-distance plan (giql_hip_window_plan_dev); its irregular pairs follow the widened predicate
 };
 
 // What disjoin_plan keeps for disjoin_fill (all inside the arena).  Dropped like the INNER plan by every call that
@@ -538,7 +540,7 @@ static inline bool sort_is_local(const giql_hip_ctx* ctx, size_t n) { return sor
 // also counts the digits of its aligned keys (k_chrom_minmax<true>) and the chromosome bases
 // are laid out 2^24-aligned when they fit (meta->aligned_ok).
 static int run_spans(giql_hip_ctx* ctx, hipStream_t st, const giql_side& a, const giql_side& b,
-                     int n_chrom, const LinBufs& lb, int hist_side = -1, u32* hist_partial = nullptr) {
+                     int n_chrom, const LinBufs& lb, int hist_side = -1, u32* hist_partial = nullptr, int pad = 0) {
   const bool hist = hist_side >= 0 && hist_partial && lb.abase && lb.top_partial &&
                     n_chrom <= MM_HIST_CHROMS && (hist_side ? b.n : a.n) > 0;
   // both sides count their digits (lb.hist_partial2 / top_partial2 for the other one; prezeroed plans only)
@@ -611,6 +613,10 @@ static int run_spans(giql_hip_ctx* ctx, hipStream_t st, const giql_side& a, cons
     if (offs[k] < omin) omin = offs[k];
     if (offs[k] > omax) omax = offs[k];
   }
+  // pad: positions every chromosome gets beyond its range on either end (the within-distance join: 1, for the
+  // clamped ends of its widened rows -- distance_kernels.hip.h)
+  omin -= pad;
+  omax += pad;
   hipLaunchKernelGGL(k_chrom_offsets, dim3(1), dim3(256), 0, st, lb.gmin, lb.gmax, n_chrom, omin,
                      omax, lb.chrom_base, lb.chrom_first, ctx->d_meta, lb.len_part, nblk[0], nblk[1],
                      hist ? 1 : 0, lb.abase);
@@ -1779,13 +1785,60 @@ static int plan_uniform(giql_hip_ctx* ctx, hipStream_t st, int n_chrom, PlanSide
 
 // ---- general form: two classes of pairs -- class 1: a.start in [b.start, b.end), counted per B row against the
 // sorted A starts; class 2: b.start in (a.start, a.end), counted per A row against the sorted B starts
+// The general two-class form's counts and scans over the sorted sides (buffer 0 of sa / sbb), shared by plan_general and
+// the within-distance plan: class 1 on `st1` (queries = sorted B over the sorted A starts), class 2 on `st` (queries =
+// sorted A over the sorted B starts); totals land in DevMeta::n_out_c1 / n_out.  Which class-1 kernels run follows
+// S.c1_fill / S.c1_items exactly as giql_hip_inner_fill_dev reads them back -- ONE copy, so the pairing cannot drift.
+static int run_class_counts(giql_hip_ctx* ctx, InnerState& S, InnerScratch& W, SortBufs& sa, SortBufs& sbb, size_t na,
+                            size_t nb, const u32* irr_a, const u32* irr_b, hipStream_t st1, hipStream_t st) {
+  constexpr u32 TQ2 = RC_NT * RC_ITEMS_C2;
+  {
+    Phase ph(ctx, st, GIQL_PH_COUNT, 4);
+    // class 1: queries = sorted B, points = sorted A starts, range [b.start, b.end);
+    // only one total per block is kept (see k_c1_count)
+    if (S.c1_fill) {
+      const u32 nt1r = cdiv(nb, TQ2);
+      hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)nt1r + 1, 256)), dim3(256), 0, st1,
+                         sbb.key[0], (u32)nb, irr_b, sa.key[0], (u32)na, irr_a, (i64)0, TQ2, nt1r, S.wlo1);
+      hipLaunchKernelGGL((k_range_count<RC_ITEMS_C2, RC_LDS_CAP>), dim3(nt1r), dim3(RC_NT), 0, st1,
+                         sbb.key[0], sbb.end[0], (u32)nb, irr_b, sa.key[0], (u32)na, irr_a, (i64)0, S.wlo1,
+                         S.lo1, S.cnt1);
+    } else {
+      const u32 c1_tq = (u32)(C1_NT * S.c1_items);  // class-1 rows per block
+      hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)S.nt1 + 1, 256)), dim3(256), 0, st1,
+                         sbb.key[0], (u32)nb, irr_b, sa.key[0], (u32)na, irr_a, (i64)0, c1_tq, S.nt1,
+                         S.wlo1);
+      if (S.c1_items == 2)
+        hipLaunchKernelGGL(k_c1_count<2>, dim3(S.nt1), dim3(C1_NT), 0, st1, sbb.key[0], sbb.end[0], (u32)nb,
+                           irr_b, sa.key[0], (u32)na, irr_a, S.wlo1, S.c1_base);
+      else
+        hipLaunchKernelGGL(k_c1_count<C1_ITEMS_MAX>, dim3(S.nt1), dim3(C1_NT), 0, st1, sbb.key[0], sbb.end[0], (u32)nb,
+                           irr_b, sa.key[0], (u32)na, irr_a, S.wlo1, S.c1_base);
+      // class-1 block totals -> block bases (one block, in place); total -> n_out_c1
+      hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, st1, S.c1_base, S.nt1,
+                         &ctx->d_meta->n_out_c1);
+    }
+    // class 2: queries = sorted A, points = sorted B starts, range (a.start, a.end)
+    hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)S.nt2 + 1, 256)), dim3(256), 0, st,
+                       sa.key[0], (u32)na, irr_a, sbb.key[0], (u32)nb, irr_b, (i64)1, TQ2, S.nt2, S.wlo2);
+    hipLaunchKernelGGL((k_range_count<RC_ITEMS_C2, RC_LDS_CAP>), dim3(S.nt2), dim3(RC_NT), 0, st,
+                       sa.key[0], sa.end[0], (u32)na, irr_a, sbb.key[0], (u32)nb, irr_b, (i64)1, S.wlo2,
+                       S.lo2, S.cnt2);
+    GIQL_TRY(post_launch("range count"));
+  }
+  if (S.c1_fill) {
+    GIQL_TRY(run_scan<u64>(ctx, st1, GIQL_PH_SCAN, S.cnt1, nb, S.off1, W.bsums1, S.off1 + nb, &ctx->d_meta->n_out_c1));
+  }
+  GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, S.cnt2, na, S.off2, W.bsums, S.off2 + na, &ctx->d_meta->n_out));
+  return GIQL_OK;
+}
+
 static int plan_general(giql_hip_ctx* ctx, hipStream_t st, int n_chrom, PlanSide& A, PlanSide& B, InnerScratch& W,
                         InnerAttempt& T) {
   InnerState& S = ctx->plan.inner;
   const LinBufs& lb = W.lb;
   SortBufs& sa = *A.sort;
   SortBufs& sbb = *B.sort;
-  constexpr u32 TQ2 = RC_NT * RC_ITEMS_C2;
   const size_t n_small = A.n < B.n ? A.n : B.n;
   bind_status(W, B, A);
   // The join itself in B's bucket stage (bucket_sort.hip.h, FUSE == 3): one-call form, on the context's guesses (the
@@ -1838,44 +1891,7 @@ static int plan_general(giql_hip_ctx* ctx, hipStream_t st, int n_chrom, PlanSide
   // class 1 (count + the scan of its block totals) runs beside class 2 when both sides are small
   SideChain sc1(ctx, st, T.onesweep ? n_small : 0);
   hipStream_t st1 = sc1.stream();
-  {
-    Phase ph(ctx, st, GIQL_PH_COUNT, 4);
-    // class 1: queries = sorted B, points = sorted A starts, range [b.start, b.end);
-    // only one total per block is kept (see k_c1_count)
-    if (S.c1_fill) {
-      const u32 nt1r = cdiv(B.n, TQ2);
-      hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)nt1r + 1, 256)), dim3(256), 0, st1,
-                         sbb.key[0], (u32)B.n, B.irr, sa.key[0], (u32)A.n, A.irr, (i64)0, TQ2, nt1r, S.wlo1);
-      hipLaunchKernelGGL((k_range_count<RC_ITEMS_C2, RC_LDS_CAP>), dim3(nt1r), dim3(RC_NT), 0, st1,
-                         sbb.key[0], sbb.end[0], (u32)B.n, B.irr, sa.key[0], (u32)A.n, A.irr, (i64)0, S.wlo1,
-                         S.lo1, S.cnt1);
-    } else {
-      const u32 c1_tq = (u32)(C1_NT * S.c1_items);  // class-1 rows per block
-      hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)S.nt1 + 1, 256)), dim3(256), 0, st1,
-                         sbb.key[0], (u32)B.n, B.irr, sa.key[0], (u32)A.n, A.irr, (i64)0, c1_tq, S.nt1,
-                         S.wlo1);
-      if (S.c1_items == 2)
-        hipLaunchKernelGGL(k_c1_count<2>, dim3(S.nt1), dim3(C1_NT), 0, st1, sbb.key[0], sbb.end[0], (u32)B.n,
-                           B.irr, sa.key[0], (u32)A.n, A.irr, S.wlo1, S.c1_base);
-      else
-        hipLaunchKernelGGL(k_c1_count<C1_ITEMS_MAX>, dim3(S.nt1), dim3(C1_NT), 0, st1, sbb.key[0], sbb.end[0], (u32)B.n,
-                           B.irr, sa.key[0], (u32)A.n, A.irr, S.wlo1, S.c1_base);
-      // class-1 block totals -> block bases (one block, in place); total -> n_out_c1
-      hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, st1, S.c1_base, S.nt1,
-                         &ctx->d_meta->n_out_c1);
-    }
-    // class 2: queries = sorted A, points = sorted B starts, range (a.start, a.end)
-    hipLaunchKernelGGL(k_count_partition, dim3(cdiv((u64)S.nt2 + 1, 256)), dim3(256), 0, st,
-                       sa.key[0], (u32)A.n, A.irr, sbb.key[0], (u32)B.n, B.irr, (i64)1, TQ2, S.nt2, S.wlo2);
-    hipLaunchKernelGGL((k_range_count<RC_ITEMS_C2, RC_LDS_CAP>), dim3(S.nt2), dim3(RC_NT), 0, st,
-                       sa.key[0], sa.end[0], (u32)A.n, A.irr, sbb.key[0], (u32)B.n, B.irr, (i64)1, S.wlo2,
-                       S.lo2, S.cnt2);
-    GIQL_TRY(post_launch("range count"));
-  }
-  if (S.c1_fill) {
-    GIQL_TRY(run_scan<u64>(ctx, st1, GIQL_PH_SCAN, S.cnt1, B.n, S.off1, W.bsums1, S.off1 + B.n, &ctx->d_meta->n_out_c1));
-  }
-  GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, S.cnt2, A.n, S.off2, W.bsums, S.off2 + A.n, &ctx->d_meta->n_out));
+  GIQL_TRY(run_class_counts(ctx, S, W, sa, sbb, A.n, B.n, A.irr, B.irr, st1, st));
   GIQL_TRY(sc1.join());
   GIQL_TRY(read_meta(ctx, st));
   ctx->plan.n_c1 = ctx->h_meta->n_out_c1;
@@ -1969,6 +1985,7 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
   ctx->plan.n_b = (u32)b->n;
   ctx->plan.n_chrom = n_chrom;
   ctx->plan.n_reg = ctx->plan.n_irr = ctx->plan.n_c1 = 0;
+  ctx->plan.widen = -1;
   *n_pairs = 0;
   if (a->n == 0 || b->n == 0 || n_chrom == 0) {  // empty result (tests :4173-4229)
     ctx->plan.planned = true;
@@ -2143,9 +2160,14 @@ int giql_hip_inner_fill_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, i
   }
   if (ctx->plan.n_irr > 0) {
     Phase ph(ctx, st, GIQL_PH_IRREGULAR);
-    hipLaunchKernelGGL(k_irr_fill, dim3(cdiv(nq, 256)), dim3(256), 0, st, view_of(ctx->plan.side_a),
-                       view_of(ctx->plan.side_b), ctx->plan.irr_a_list, ctx->plan.irr_b_list, ctx->d_meta,
-                       ctx->plan.irr_off, row_a + ctx->plan.n_reg, row_b + ctx->plan.n_reg);
+    if (ctx->plan.widen >= 0)
+      hipLaunchKernelGGL(k_window_irr_fill, dim3(cdiv(nq, 256)), dim3(256), 0, st, view_of(ctx->plan.side_a),
+                         view_of(ctx->plan.side_b), ctx->plan.irr_a_list, ctx->plan.irr_b_list, ctx->d_meta,
+                         ctx->plan.widen, ctx->plan.irr_off, row_a + ctx->plan.n_reg, row_b + ctx->plan.n_reg);
+    else
+      hipLaunchKernelGGL(k_irr_fill, dim3(cdiv(nq, 256)), dim3(256), 0, st, view_of(ctx->plan.side_a),
+                         view_of(ctx->plan.side_b), ctx->plan.irr_a_list, ctx->plan.irr_b_list, ctx->d_meta,
+                         ctx->plan.irr_off, row_a + ctx->plan.n_reg, row_b + ctx->plan.n_reg);
     GIQL_TRY(post_launch("irregular fill"));
   }
   return GIQL_OK;
@@ -2180,6 +2202,163 @@ int giql_hip_inner_join_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_si
   if (*n_pairs > capacity)
     return set_err(GIQL_ERR_CAPACITY, "capacity %lld < %lld pairs", (long long)capacity, (long long)*n_pairs);
   return giql_hip_inner_fill_dev(ctx, row_a, row_b, capacity, stream);
+}
+
+// ------------------------------------------------- within-distance join / DISTANCE
+// giql_hip_window_plan_dev: the pairs with DISTANCE(a, b) <= max_distance, as an INNER plan that giql_hip_inner_fill_dev
+// fills (distance_kernels.hip.h has the equivalence and the clamp).  ONE form is routed, the general two-class one, in
+// its plainest shape: span pass padded by one position per chromosome end -> ONE read-back (chrom ids, the 32-bit
+// axis, inverted rows) -> A widened and keyed by k_window_linearize, B by k_linearize -> both sorted -> the class-1 and
+// class-2 range counts and scans of plan_general -> the widened literal kernels for zero-length rows.  Nothing is
+// speculated and no INNER guess is read or written: the uniform-length form, the sorts from raw columns, the fused
+// count and the bucket-stage join are not reachable with a widening, and a plain INTERSECTS plan after this one
+// finds its guesses as it left them.
+static int giql_hip_window_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, int32_t n_chrom,
+                                         int64_t max_distance, void* stream, int64_t* n_pairs) {
+  if (!ctx || !n_pairs) return set_err(GIQL_ERR_INVALID, "ctx/n_pairs is NULL");
+  if (max_distance < 0) return set_err(GIQL_ERR_INVALID, "max_distance < 0");
+  GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
+  hipStream_t st = (hipStream_t)stream;
+  InnerPlan& P = ctx->plan;
+  P.planned = false;  // (the ways out before the arena is claimed drop the other plans too)
+  ctx->dj.planned = false;
+  P.swapped = false;
+  P.plan_is_join = false;
+  P.fuse_done = false;
+  P.side_a = *a;
+  P.side_b = *b;
+  P.n_a = (u32)a->n;
+  P.n_b = (u32)b->n;
+  P.n_chrom = n_chrom;
+  P.n_reg = P.n_irr = P.n_c1 = 0;
+  P.widen = -1;
+  *n_pairs = 0;
+  if (a->n == 0 || b->n == 0 || n_chrom == 0) {  // empty result, as the INNER plan's
+    P.planned = true;
+    return GIQL_OK;
+  }
+  const size_t na = (size_t)a->n, nb = (size_t)b->n, nq = na + nb;
+  if (na > OS_MAX_ROWS || nb > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
+  // coordinates of one chromosome are less than 2^32 + 2 apart: a larger N selects the same pairs, and the sums below
+  // stay far from the ends of int64
+  const i64 widen = max_distance > ((i64)1 << 33) ? ((i64)1 << 33) : (i64)max_distance;
+  InnerState& S = P.inner;
+  InnerScratch W;
+  constexpr u32 TQ2 = RC_NT * RC_ITEMS_C2;
+  S.uniform = 0;
+  S.c1_items = nb <= C1_SMALL_ROWS ? 2 : C1_ITEMS_MAX;
+  S.nt1 = cdiv(nb, (u32)(C1_NT * S.c1_items));
+  S.c1_fill = nb <= C1_SMALL_ROWS;
+  S.nt2 = cdiv(na, TQ2);
+  GIQL_TRY(claim_arena(ctx, st, [&](char* base) { return carve_inner(ctx, base, na, nb, n_chrom, true, W); }));
+  GIQL_TRY(run_spans(ctx, st, *a, *b, n_chrom, W.lb, -1, nullptr, /*pad=*/1));
+  GIQL_TRY(read_meta(ctx, st));
+  if (ctx->h_meta->inverted_a || ctx->h_meta->inverted_b) {
+    // which side: for callers in giql_hip_stats (n_irregular_a / n_irregular_b = -1), not only in the message
+    if (ctx->h_meta->inverted_a) ctx->stats.n_irregular_a = -1;
+    if (ctx->h_meta->inverted_b) ctx->stats.n_irregular_b = -1;
+    return set_err(GIQL_ERR_INVALID, "DISTANCE: side %s has a row with start > end",
+                   ctx->h_meta->inverted_a ? "a" : "b");
+  }
+  ctx->guess.last_span = ctx->h_meta->total_span;  // known before anything is sorted: the sort form follows the real density
+  SortBufs& sa = S.sa;
+  SortBufs& sbb = S.sb;
+  u32* const status_a = na <= nb ? W.os_status2 : W.os_status;
+  u32* const status_b = na <= nb ? W.os_status : W.os_status2;
+  {
+    int lo_pad = a->start_off, hi_pad = a->start_off;
+    const int offs[3] = {a->end_off, b->start_off, b->end_off};
+    for (int k = 0; k < 3; k++) {
+      if (offs[k] < lo_pad) lo_pad = offs[k];
+      if (offs[k] > hi_pad) hi_pad = offs[k];
+    }
+    lo_pad -= 1;  // run_spans(pad = 1) handed the same two numbers to k_chrom_offsets
+    hi_pad += 1;
+    HIP_TRY(hipMemsetAsync(W.hist[0], 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
+    Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
+    u32 grid = cdiv((u64)na, LIN_NT);
+    if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_window_linearize, dim3(grid), dim3(LIN_NT), 0, st, a->chrom, a->start, a->end, (u32)na,
+                       a->start_off, a->end_off, n_chrom, W.lb.chrom_base, W.lb.gmin, W.lb.gmax, lo_pad, hi_pad, widen,
+                       sa.key[0], sa.end[0], P.irr_a_list, ctx->d_meta, W.hist[0]);
+    hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, W.hist[0], (u32)LIN_HIST_REPLICAS, W.gbase[0]);
+    GIQL_TRY(post_launch("window linearize"));
+  }
+  GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, W.lb, sbb.key[0], sbb.end[0], P.irr_b_list, 1, 0, W.hist[1], W.gbase[1]));
+  GIQL_TRY(run_sort_onesweep(ctx, st, sa, (u32)na, W.gbase[0], status_a));
+  GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, W.gbase[1], status_b));
+  const u32* irr_a = &ctx->d_meta->irr_a;
+  const u32* irr_b = &ctx->d_meta->irr_b;
+  // the counts and scans of plan_general, over the widened A (class 1 and class 2 on the one stream)
+  GIQL_TRY(run_class_counts(ctx, S, W, sa, sbb, na, nb, irr_a, irr_b, st, st));
+  GIQL_TRY(read_meta(ctx, st));
+  P.n_c1 = ctx->h_meta->n_out_c1;
+  P.n_reg = ctx->h_meta->n_out + P.n_c1;
+  ctx->stats.n_irregular_a = ctx->h_meta->irr_a;
+  ctx->stats.n_irregular_b = ctx->h_meta->irr_b;
+  ctx->stats.span = (int64_t)ctx->h_meta->total_span;
+  if (ctx->h_meta->irr_a + ctx->h_meta->irr_b > 0) {
+    {
+      Phase ph(ctx, st, GIQL_PH_IRREGULAR);
+      hipLaunchKernelGGL(k_window_irr_count, dim3(cdiv(nq, 256)), dim3(256), 0, st, view_of(*a), view_of(*b),
+                         P.irr_a_list, P.irr_b_list, ctx->d_meta, widen, W.irr_cnt);
+      GIQL_TRY(post_launch("window irregular count"));
+    }
+    GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_IRREGULAR, W.irr_cnt, nq, P.irr_off, W.bsums, P.irr_off + nq,
+                           &ctx->d_meta->n_out_irr));
+    GIQL_TRY(read_meta(ctx, st));
+    P.n_irr = ctx->h_meta->n_out_irr;
+  }
+  collect_spans(ctx);
+  ctx->stats.reserved = 0;  // join_form: the general two-class form, the only one a widening reaches
+  ctx->stats.n_out = (int64_t)(P.n_reg + P.n_irr);
+  *n_pairs = (int64_t)(P.n_reg + P.n_irr);
+  P.widen = widen;
+  P.planned = true;
+  return GIQL_OK;
+}
+
+int giql_hip_window_plan_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, int32_t n_chrom,
+                             int64_t max_distance, void* stream, int64_t* n_pairs) {
+  return with_order_fallback(
+      ctx, [&] { return giql_hip_window_plan_dev_impl(ctx, a, b, n_chrom, max_distance, stream, n_pairs); });
+}
+
+// DISTANCE(a[row_a[i]], b[row_b[i]]) per pair (k_pair_distance).  No workspace: an INNER plan on the context stays.
+int giql_hip_distance_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, const int32_t* row_a,
+                          const int32_t* row_b, int64_t n, const int32_t* strand_a, const int32_t* strand_b,
+                          int32_t flags, int64_t* dist_out, uint8_t* valid_out, void* stream) {
+  if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
+  GIQL_TRY(check_side(a, "a"));
+  GIQL_TRY(check_side(b, "b"));
+  if (n < 0) return set_err(GIQL_ERR_INVALID, "n < 0");
+  if (flags & ~3) return set_err(GIQL_ERR_INVALID, "flags outside {1 = signed, 2 = stranded}");
+  if (n > 0 && (!row_a || !row_b || !dist_out || !valid_out))
+    return set_err(GIQL_ERR_INVALID, "row_a/row_b/dist_out/valid_out is NULL");
+  if ((flags & 2) && ((a->n > 0 && !strand_a) || (b->n > 0 && !strand_b)))
+    return set_err(GIQL_ERR_INVALID, "stranded DISTANCE without strand codes");
+  if (n == 0) return GIQL_OK;
+  GIQL_TRY(begin_call(ctx));
+  hipStream_t st = (hipStream_t)stream;
+  ctx->stats.n_a = a->n;
+  ctx->stats.n_b = b->n;
+  HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
+  u32 grid = cdiv((u64)n, DIST_NT * 4);
+  if (grid > GIQL_STREAM_GRID) grid = GIQL_STREAM_GRID;
+  {
+    Phase ph(ctx, st, GIQL_PH_AUX);
+    ctx->stats.phase_bytes[GIQL_PH_AUX] += (int64_t)33 * n;  // 8 B of ids, four 4 B coordinate gathers, 9 B written
+    hipLaunchKernelGGL(k_pair_distance, dim3(grid), dim3(DIST_NT), 0, st, view_of(*a), view_of(*b), row_a, row_b, (u64)n,
+                       strand_a, strand_b, (u32)flags, dist_out, valid_out, ctx->d_meta);
+    GIQL_TRY(post_launch("pair distance"));
+  }
+  if (read_meta(ctx, st) != GIQL_OK) {
+    if (ctx->h_meta->status == GIQL_ERR_INVALID) return set_err(GIQL_ERR_INVALID, "a row id is outside its table");
+    return ctx->h_meta->status ? ctx->h_meta->status : GIQL_ERR_HIP;
+  }
+  collect_spans(ctx);
+  ctx->stats.n_out = n;
+  return GIQL_OK;
 }
 
 // ------------------------------------------------------------- table index

@@ -117,6 +117,16 @@ class DeviceIndex:
             pass
 
 
+class InvertedRows(ValueError):
+    """A side of a within-distance join holds a row with ``start > end``.  ``sides``: which -- ``"a"``, ``"b"`` or
+    both -- as the library reports them in its stats (``n_irregular_a`` / ``n_irregular_b`` = -1), not read off the
+    wording of its message."""
+
+    def __init__(self, sides: tuple, message: str):
+        super().__init__(message)
+        self.sides = tuple(sides)
+
+
 class HipEngine:
     """One context (device arena + bookkeeping) on one GPU.  Not thread-safe."""
 
@@ -358,8 +368,9 @@ class HipEngine:
             self._h, a.c_struct(), b.c_struct(), int(n_chrom), spans.ctypes.data, self._stream()))
         return spans.tolist()
 
-    def _groups(self, a: DeviceSide, b: DeviceSide, n_chrom: int):
-        """Yield ``(sub_a, rows_a, sub_b, rows_b)`` per 32-bit chromosome group.
+    def _groups(self, a: DeviceSide, b: DeviceSide, n_chrom: int, pad: int = 0):
+        """Yield ``(sub_a, rows_a, sub_b, rows_b)`` per 32-bit chromosome group (``pad``: positions an operator
+        adds to every present chromosome's span -- the within-distance join: 2).
 
         The kernels place all chromosomes on one u32 axis; a genome whose spans sum
         past 2^32 is joined group by group (chromosomes are independent units).
@@ -367,7 +378,7 @@ class HipEngine:
         torch = _torch()
         from .shard import span_groups
 
-        groups = span_groups(self.chrom_spans(a, b, n_chrom))
+        groups = span_groups([s + pad if s else 0 for s in self.chrom_spans(a, b, n_chrom)])
         for g in groups:
             lut = torch.zeros(int(n_chrom), dtype=torch.bool, device=self.device)
             lut[torch.tensor(g, dtype=torch.long, device=self.device)] = True
@@ -394,9 +405,9 @@ class HipEngine:
             return z, z.clone()
         return torch.cat(outs_a), torch.cat(outs_b)
 
-    def _retry_by_groups(self, fn, a, b, n_chrom):
+    def _retry_by_groups(self, fn, a, b, n_chrom, pad: int = 0):
         """Run ``fn(sub_a, sub_b)`` per group after a GIQL_ERR_SPAN."""
-        return [(ra, rb, fn(sa, sb)) for sa, ra, sb, rb in self._groups(a, b, n_chrom)]
+        return [(ra, rb, fn(sa, sb)) for sa, ra, sb, rb in self._groups(a, b, n_chrom, pad)]
 
     # -------------------------------------------------------------- SEMI/ANTI
     def semi_anti(self, a: DeviceSide, b: DeviceSide, n_chrom: int, anti: bool):
@@ -764,6 +775,86 @@ class HipEngine:
         if n:
             self.contain_fill(row_outer, row_inner)
         return row_outer, row_inner
+
+    # --------------------------------------------------------------- DISTANCE
+    def window_join(self, a: DeviceSide, b: DeviceSide, n_chrom: int, max_distance: int):
+        """All ``(row_a, row_b)`` on one chromosome with ``DISTANCE(a, b) <= max_distance`` (an integer >= 0): the
+        reference's "all pairs within N bp" recipe (``docs/recipes/distance.rst:60-73``; the CASE is
+        ``src/giql/expanders/_distance.py:67-117``) as the INNER join over A widened by ``max_distance``
+        (``giql_hip_window_plan_dev``, filled by the INNER fill).  Overlapping rows have distance 0, book-ended
+        ones 1.  Two int32 device tensors of the exact size, pairs in no particular order;
+        ``stats()["join_form"]`` is always ``"general"``.  Every row of both sides needs ``start <= end``:
+        :class:`InvertedRows` (a ``ValueError``) tells in ``.sides`` which side does not."""
+        torch = _torch()
+        self._check_sides(a, b)
+        max_distance = int(max_distance)
+        if max_distance < 0:
+            raise ValueError("max_distance must be >= 0")
+        try:
+            return self._window_once(a, b, n_chrom, max_distance)
+        except _lib.GiqlHipError as exc:
+            if exc.code != _lib.GIQL_ERR_SPAN:
+                raise
+        # a genome longer than the 32-bit axis: chromosome groups are independent units
+        parts = [(ra[pa.long()].to(torch.int32), rb[pb.long()].to(torch.int32)) for ra, rb, (pa, pb) in
+                 self._retry_by_groups(lambda sa, sb: self._window_once(sa, sb, n_chrom, max_distance), a, b, n_chrom,
+                                       pad=2)]
+        if not parts:
+            z = torch.empty(0, dtype=torch.int32, device=self.device)
+            return z, z.clone()
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+    def _window_once(self, a: DeviceSide, b: DeviceSide, n_chrom: int, max_distance: int):
+        torch = _torch()
+        n = ctypes.c_int64(0)
+        ca, cb = a.c_struct(), b.c_struct()
+        try:
+            _lib.check(self._L.giql_hip_window_plan_dev(self._h, ctypes.byref(ca), ctypes.byref(cb), int(n_chrom),
+                                                        min(max_distance, (1 << 63) - 1), self._stream(),
+                                                        ctypes.byref(n)))
+        except _lib.GiqlHipError as exc:
+            if exc.code == _lib.GIQL_ERR_INVALID:
+                st = _lib.CStats()
+                _lib.check(self._L.giql_hip_get_stats(self._h, ctypes.byref(st)))
+                sides = tuple(s for s, v in (("a", st.n_irregular_a), ("b", st.n_irregular_b)) if int(v) == -1)
+                if sides:
+                    raise InvertedRows(sides, str(exc)) from exc
+            raise
+        self._keepalive = (a, b)
+        pairs = int(n.value)
+        row_a = torch.empty(pairs, dtype=torch.int32, device=self.device)
+        row_b = torch.empty(pairs, dtype=torch.int32, device=self.device)
+        if pairs:
+            self.inner_fill(row_a, row_b)
+        return row_a, row_b
+
+    def distance(self, a: DeviceSide, b: DeviceSide, row_a, row_b, signed: bool = False, stranded: bool = False,
+                 strand_a=None, strand_b=None):
+        """``DISTANCE(a[row_a[i]], b[row_b[i]])`` per pair: ``(distance int64, valid uint8)`` device tensors, the
+        four variants of ``src/giql/expanders/_distance.py:67-117``.  ``valid == 0`` is SQL NULL (the chromosomes
+        differ; stranded: a strand is NULL / ``.`` / ``?``).  ``strand_a`` / ``strand_b``: int32 device tensors,
+        one code per table row as ``execute._strand_codes`` makes them (0 ``+``, 1 ``-``, 2 ``.``, 3 ``?``, other =
+        NULL); required when ``stranded``.  Row ids outside their table raise ``GiqlHipError``."""
+        torch = _torch()
+        self._check_sides(a, b)
+        n = int(row_a.shape[0])
+        if int(row_b.shape[0]) != n:
+            raise ValueError("row_a and row_b must have one entry per pair")
+        flags = (1 if signed else 0) | (2 if stranded else 0)
+        if stranded:
+            for s, side, what in ((strand_a, a, "strand_a"), (strand_b, b, "strand_b")):
+                if s is None or int(s.shape[0]) != side.n:
+                    raise ValueError(f"stranded DISTANCE needs {what}: one int32 code per row of its table")
+        dist = torch.empty(n, dtype=torch.int64, device=self.device)
+        valid = torch.empty(n, dtype=torch.uint8, device=self.device)
+        ca, cb = a.c_struct(), b.c_struct()
+        _lib.check(self._L.giql_hip_distance_dev(
+            self._h, ctypes.byref(ca), ctypes.byref(cb), self._dev_ptr(row_a, "row_a", torch.int32),
+            self._dev_ptr(row_b, "row_b", torch.int32), n,
+            self._dev_ptr(strand_a, "strand_a", torch.int32) if stranded else None,
+            self._dev_ptr(strand_b, "strand_b", torch.int32) if stranded else None,
+            flags, dist.data_ptr() if n else None, valid.data_ptr() if n else None, self._stream()))
+        return dist, valid
 
     def merge(self, s: DeviceSide, n_chrom: int, distance: int = 0, preds=None):
         """MERGE: ``(chrom, start, end, count)`` tensors of the merged regions ordered by

@@ -16,7 +16,7 @@ import threading
 
 import numpy as np
 
-from .engine import ENCODING_OFFSETS, DeviceSide, HipEngine
+from .engine import ENCODING_OFFSETS, DeviceSide, HipEngine, InvertedRows
 from .plan import JoinPlan, PlanSide, Projection, is_plan_string
 from .shape import operand_sides
 from .transpile import build_plan
@@ -646,12 +646,49 @@ def _spatial_join(plan: JoinPlan, a: DeviceSide, b: DeviceSide, n_chrom: int, en
     """The pairs ``(row_left, row_right)`` of an INNER plan's spatial predicate: INTERSECTS, or CONTAINS / WITHIN
     (src/giql/expanders/intersects.py:155-166) through the one containment path, ``contain_join(outer, inner)`` --
     WITHIN with the sides exchanged and the result columns exchanged back."""
+    if plan.predicate == "within_distance":
+        # DISTANCE(left, right) <= max_distance: the INNER join over the widened left side (HipEngine.window_join)
+        if plan.max_distance < 0:       # written "< 0": a distance is never negative
+            import torch
+
+            z = torch.empty(0, dtype=torch.int32, device=eng.device)
+            return z, z.clone()
+        try:
+            return eng.window_join(a, b, n_chrom, plan.max_distance)
+        except InvertedRows as exc:
+            bad = " and ".join(repr((plan.left if s == "a" else plan.right).table) for s in exc.sides)
+            raise ValueError(f"DISTANCE needs start <= end on every row: table {bad} has a row with "
+                             f"start > end") from exc
     if plan.predicate == "contains":
         return eng.contain_join(a, b, n_chrom)
     if plan.predicate == "within":
         rb, ra = eng.contain_join(b, a, n_chrom)
         return ra, rb
     return eng.inner_join(a, b, n_chrom)
+
+
+def _pair_distances(plan: JoinPlan, lt, rt, a: DeviceSide, b: DeviceSide, ra, rb, eng: HipEngine) -> dict:
+    """The plan's "pair_distance" projections -> ``{code: masked int64 array}``: DISTANCE of every pair
+    ``(ra[i], rb[i])`` on the device (``HipEngine.distance``, the CASE of src/giql/expanders/_distance.py:67-117),
+    NULLs as mask entries.  ``code`` = "lr" | "rl" (which table is the CASE's A operand) + "+signed" / "+stranded"."""
+    import torch
+
+    out: dict = {}
+    codes = {p.column for p in plan.projection if p.side == "pair_distance"}
+    strands = None
+    for code in sorted(codes):
+        parts = code.split("+")
+        signed, stranded = "signed" in parts, "stranded" in parts
+        if stranded and strands is None:
+            ls, rs = (plan.strand_col or "strand,strand").split(",")
+            strands = tuple(torch.from_numpy(_strand_codes(_column(t, c), 4)).to(eng.device)
+                            for t, c in ((lt, ls), (rt, rs)))
+        first, second, rows_1, rows_2 = (a, b, ra, rb) if parts[0] == "lr" else (b, a, rb, ra)
+        s1, s2 = (strands if parts[0] == "lr" else strands[::-1]) if stranded else (None, None)
+        dist, valid = eng.distance(first, second, rows_1.contiguous(), rows_2.contiguous(), signed=signed,
+                                   stranded=stranded, strand_a=s1, strand_b=s2)
+        out[code] = np.ma.masked_array(dist.cpu().numpy(), mask=(valid == 0).cpu().numpy())
+    return out
 
 
 def _join_with_residuals(plan: JoinPlan, lt, rt, a: DeviceSide, b: DeviceSide, n_chrom: int, eng: HipEngine):
@@ -1277,6 +1314,8 @@ def _join_piece(plan: JoinPlan, lt, rt, ia: np.ndarray, ib: np.ndarray, n_chrom:
         if return_indices:
             return ra.cpu().numpy(), rb.cpu().numpy()
         idx = {"l": ra, "r": rb}
+        if any(p.side == "pair_distance" for p in plan.projection):
+            extra = {"pair_distance": _pair_distances(plan, lt, rt, a, b, ra, rb, eng)}
     elif plan.kind in ("SEMI", "ANTI"):
         if plan.residuals:
             rows = _join_with_residuals(plan, lt, rt, a, b, n_chrom, eng)
@@ -1317,6 +1356,8 @@ def _project(plan: JoinPlan, lt, rt, idx: dict, extra: dict, eng: HipEngine, dev
         names.append(p.name)
         if p.side == "distance":
             cols.append(extra["distance"])
+        elif p.side == "pair_distance":
+            cols.append(extra["pair_distance"][p.column])
         elif p.side in taken:
             cols.append(taken[p.side][p.column])
         else:
@@ -1466,7 +1507,10 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
     if plan.predicate != "intersects" and devices is not None and len(devices) > 1:
         # one device, like DISJOIN: the per-chromosome fan-out shards an INTERSECTS join
         raise ValueError(f"{plan.predicate.upper()} joins run on one device; devices={devices!r} names {len(devices)}")
-    if (plan.kind == "INNER" and plan.predicate == "intersects" and not plan.residuals
+    has_pair_distance = any(p.side == "pair_distance" for p in plan.projection)
+    if has_pair_distance and devices is not None and len(devices) > 1:
+        raise ValueError(f"a DISTANCE column is computed on one device; devices={devices!r} names {len(devices)}")
+    if (plan.kind == "INNER" and plan.predicate == "intersects" and not plan.residuals and not has_pair_distance
             and not (devices and len(devices) > 1)
             and any(p is not None and p.index for p in pins.values())):
         # a pinned table offers an index: the join reads it instead of spanning and sorting that table again

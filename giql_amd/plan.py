@@ -16,7 +16,7 @@ PLAN_PREFIX = "GIQL-HIP-PLAN/1 "
 KINDS = ("INNER", "SEMI", "ANTI", "NEAREST", "COUNT", "CLUSTER", "MERGE", "FILTER", "DISJOIN")
 
 #: the spatial predicate of an INNER plan
-PREDICATES = ("intersects", "contains", "within")
+PREDICATES = ("intersects", "contains", "within", "within_distance")
 
 #: the three columns DISJOIN appends to the target's row (src/giql/expanders/disjoin.py:191-198)
 DISJOIN_COLUMNS = ("disjoin_chrom", "disjoin_start", "disjoin_end")
@@ -42,7 +42,10 @@ class PlanSide:
 
 @dataclass(frozen=True)
 class Projection:
-    side: str      # "l", "r", "distance" (NEAREST), "count" (COUNT aggregate); CLUSTER / MERGE:
+    side: str      # "l", "r", "distance" (NEAREST), "count" (COUNT aggregate); "pair_distance" (INNER: the
+                   # DISTANCE of the pair as a nullable int64 column; column = "lr" | "rl" -- which table is the
+                   # CASE's A operand -- then "+signed" / "+stranded", src/giql/expanders/_distance.py:67-117);
+                   # CLUSTER / MERGE:
                    # "star" (every table column), "cluster" (the id), "count" (COUNT(*)); DISJOIN: "l" (a
                    # target column), "disjoin" (column = one of DISJOIN_COLUMNS), "star" (the target's
                    # columns, then the three)
@@ -131,7 +134,9 @@ class JoinPlan:
     output: tuple[str, ...] = field(default_factory=tuple)         # final column names in SELECT order (grouped plans)
     # INNER only: the join's spatial predicate, left <predicate> right (src/giql/expanders/intersects.py:149-166).
     # "contains" / "within" run HipEngine.contain_join; plan strings written before the field existed load as
-    # "intersects"
+    # "intersects".  "within_distance": DISTANCE(left, right) <= max_distance (HipEngine.window_join; -1 = nothing
+    # qualifies, the query compared with < 0).  A stranded "pair_distance" projection reads strand_col
+    # ("<left column>,<right column>", as stranded NEAREST does)
     predicate: str = "intersects"
 
     def __post_init__(self) -> None:
@@ -141,6 +146,8 @@ class JoinPlan:
             raise ValueError(f"unknown join predicate {self.predicate!r}")
         if self.predicate != "intersects" and self.kind != "INNER":
             raise ValueError(f"predicate {self.predicate!r} needs an INNER plan, not {self.kind}")
+        if self.predicate == "within_distance" and not isinstance(self.max_distance, int):
+            raise ValueError("predicate 'within_distance' needs an integer max_distance")
 
     def to_dict(self) -> dict:
         """The plan as plain JSON-able data (what :meth:`to_string` serialises)."""

@@ -47,8 +47,8 @@ import re
 from dataclasses import dataclass
 
 from .plan import PlanSide
-from .shape import (AGG_FUNCS, ColRef, DisjoinShape, HipDeclined, JoinShape, OrderKey, SelItem, TableRef, condition_terms,
-                    decline, lower_disjoin_shape, lower_join_shape, norm)
+from .shape import (AGG_FUNCS, ColRef, DisjoinShape, HipDeclined, JoinShape, OrderKey, SelItem, TableRef, comparison_leaf,
+                    condition_terms, decline, lower_disjoin_shape, lower_join_shape, norm)
 
 SPATIAL_KEYS = ("intersects", "contains", "within", "spatialsetpredicate")
 SPATIAL_PREDICATE_META = "giql_spatial_predicate"   # what the generic spatial expanders stamp on their output
@@ -167,6 +167,36 @@ def _literal(n):
 
 
 _ARITH = {"add": "+", "sub": "-", "mul": "*", "div": "/"}
+DISTANCE_KEYS = ("giqldistance", "distance")
+
+
+def _bool_param(n) -> bool:
+    """``stranded := true`` / ``signed := true`` as the node stores it: a Boolean node, a python bool or a literal
+    (``coerce_bool_param`` of the reference reads the same three)."""
+    if n is None:
+        return False
+    if isinstance(n, bool):
+        return n
+    if _key(n) == "boolean":
+        return bool(_arg(n, "this"))
+    if _key(n) == "literal":
+        return str(_arg(n, "this")).strip().lower() in ("true", "1")
+    raise decline("non-literal stranded / signed argument")
+
+
+def _distance_call(n):
+    """A ``GIQLDistance`` node (src/giql/expressions.py:288-323) -> ``("distfn", ColRef, ColRef, stranded, signed)``.
+    A literal range as an operand is the reference's own error (src/giql/expanders/distance.py:123)."""
+    _only(n, ("this", "expression", "stranded", "signed"), "DISTANCE")
+    refs = []
+    for arg, position in (("this", "first"), ("expression", "second")):
+        o = _arg(n, arg)
+        if _key(o) == "literal":
+            raise ValueError(f"Literal range as {position} argument not yet supported")
+        if _key(o) != "column":
+            raise decline("DISTANCE operand that is not a column")
+        refs.append(_colref(o))
+    return ("distfn", refs[0], refs[1], _bool_param(_arg(n, "stranded")), _bool_param(_arg(n, "signed")))
 
 
 def _operand(n):
@@ -181,6 +211,8 @@ def _operand(n):
         return ("col", _colref(n))
     if k == "boolean":
         raise decline("boolean literal in a join condition")
+    if k in DISTANCE_KEYS:
+        return _distance_call(n)
     if k in _ARITH:
         _only(n, ("this", "expression"), "arithmetic")     # (Div carries typed / safe flags when a dialect sets them)
         return ("fn", _ARITH[k], [_operand(_arg(n, "this")), _operand(_arg(n, "expression"))])
@@ -222,25 +254,27 @@ def _cond_tree(n, operand=None):
             raise decline(f"{k.upper()} operand that is not a column")
         return ("leaf", (k, _colref(l), _colref(r)))
     if k in _CMP:
-        return ("leaf", ("cmp", operand(_arg(n, "this")), _CMP[k], operand(_arg(n, "expression"))))
+        return comparison_leaf(operand(_arg(n, "this")), _CMP[k], operand(_arg(n, "expression")))
+    if k in ("between", "in") and any(_key(x) in DISTANCE_KEYS for x in _walk(n)):
+        raise decline("BETWEEN / IN over a DISTANCE")      # as the tested value, as a bound, inside a bound's arithmetic
     if k == "between":
         _only(n, ("this", "low", "high"), "BETWEEN")
         x = operand(_arg(n, "this"))
-        return ("and", [("leaf", ("cmp", x, ">=", operand(_arg(n, "low")))),
-                        ("leaf", ("cmp", x, "<=", operand(_arg(n, "high"))))])
+        return ("and", [comparison_leaf(x, ">=", operand(_arg(n, "low"))),
+                        comparison_leaf(x, "<=", operand(_arg(n, "high")))])
     if k == "in":
         _only(n, ("this", "expressions"), "IN")      # IN (sub-query) / IN UNNEST(...) carry other args
         x = operand(_arg(n, "this"))
         values = [_literal(v) for v in (_arg(n, "expressions") or [])]
         if not values or any(v is None for v in values):
             raise decline("IN list with a non-literal member")
-        return ("or", [("leaf", ("cmp", x, "=", v)) for v in values])
+        return ("or", [comparison_leaf(x, "=", v) for v in values])
     if k == "is":
         _only(n, ("this", "expression"), "IS")
         x = operand(_arg(n, "this"))
         if _key(_arg(n, "expression")) != "null" or x[0] == "lit":
             raise decline("IS predicate other than <column> IS [NOT] NULL")
-        return ("leaf", ("cmp", x, "isnull", ("lit", 0)))
+        return comparison_leaf(x, "isnull", ("lit", 0))
     raise decline(f"join condition of kind {k!r}")
 
 
@@ -258,8 +292,12 @@ def _select_item(n) -> SelItem:
         return SelItem(_colref(n), alias)
     if k == "star":
         return SelItem(ColRef(None, False, "*", star=True), alias)
+    if k in DISTANCE_KEYS:
+        return SelItem(None, alias, distance=_distance_call(n)[1:])
     if k.upper() in AGG_FUNCS:
         arg = _arg(n, "this")
+        if any(_key(x) in DISTANCE_KEYS for x in _walk(arg)):
+            raise decline("DISTANCE inside an aggregate")
         distinct = False
         if _key(arg) == "distinct":
             exprs = _arg(arg, "expressions") or []
@@ -407,6 +445,8 @@ def shape_from_ast(root, node, ctx) -> JoinShape:
     if group is not None:
         _only(group, ("expressions",), "GROUP BY")   # ROLLUP / CUBE / GROUPING SETS / ALL / WITH TOTALS
         for g in _arg(group, "expressions") or []:
+            if _key(g) in DISTANCE_KEYS:
+                raise decline("DISTANCE in GROUP BY")
             if _key(g) != "column":
                 raise decline("GROUP BY expression")
             shape.group_by.append(_colref(g))
@@ -423,6 +463,8 @@ def shape_from_ast(root, node, ctx) -> JoinShape:
                 return ("agg", it)
             if _key(n) in ("subquery", "select", "paren"):
                 raise decline("parenthesised / sub-query HAVING condition")
+            if any(_key(x) in DISTANCE_KEYS for x in _walk(n)):
+                raise decline("DISTANCE in HAVING")
             return _operand(n)
 
         shape.having = condition_terms(_cond_tree(_arg(having, "this"), having_operand))
@@ -589,6 +631,30 @@ def make_expander(fallback, make_command, key: str = "intersects"):
     return expand_intersects_hip
 
 
+def make_distance_expander(fallback, make_command):
+    """The ``(HipTarget, GIQLDistance)`` expander.  Registered so that the generic CASE expander
+    (src/giql/expanders/distance.py:296-331) does not fire first: a DISTANCE node in a statement this target runs --
+    the ``DISTANCE(x, y) <= N`` join predicate, or the value in the SELECT list of such a join or of an
+    INTERSECTS / CONTAINS / WITHIN join -- stays as it is and the statement's plan becomes the payload; every
+    other statement gets the CASE (``fallback``).  The statement's sides come from THIS node's resolution
+    (slots ``this`` / ``expression``, like a spatial operator's)."""
+
+    def expand_distance_hip(node, ctx):
+        root = _root(node)
+        if _key(root) == "select":
+            try:
+                plan = lower_statement(root, node, ctx)
+            except HipDeclined:
+                plan = None
+            if plan is not None:
+                payload = plan.to_string()
+                ctx.add_statement_finalizer(lambda _root: make_command(payload))
+                return node
+        return fallback(node, ctx)
+
+    return expand_distance_hip
+
+
 try:
     from giql.expander import register
     from giql.expanders.intersects import _expand_spatial_op
@@ -625,6 +691,15 @@ if HAVE_GIQL:  # the registration itself needs the real package
             make_expander(lambda node, ctx: _expand_spatial_op(node, ctx, "within"),
                           lambda payload: exp.Command(this=payload), "within"))
     except ImportError:  # a giql without the two operators
+        pass
+
+    try:
+        from giql.expanders.distance import expand_distance as _expand_distance_generic
+        from giql.expressions import GIQLDistance
+
+        expand_distance_hip = register(HipTarget, GIQLDistance)(
+            make_distance_expander(_expand_distance_generic, lambda payload: exp.Command(this=payload)))
+    except ImportError:  # a giql without the DISTANCE operator
         pass
 
     try:

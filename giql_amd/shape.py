@@ -55,10 +55,52 @@ def decline(reason: str) -> HipDeclined:
 #: the column-to-column spatial predicates a join may carry (src/giql/expanders/intersects.py:149-166): a term
 #: (name, ColRef, ColRef) read "lhs <name> rhs"
 SPATIAL_TERMS = ("intersects", "contains", "within")
-_FLIPPED = {"intersects": "intersects", "contains": "within", "within": "contains"}
+#: DISTANCE(x.interval, y.interval) <= N as a join predicate (docs/recipes/distance.rst:60-73): a term
+#: ("within_distance", ColRef, ColRef, N) with N already the inclusive bound (-1: nothing qualifies)
+DISTANCE_TERM = "within_distance"
+JOIN_TERMS = SPATIAL_TERMS + (DISTANCE_TERM,)
+_FLIPPED = {"intersects": "intersects", "contains": "within", "within": "contains", DISTANCE_TERM: DISTANCE_TERM}
 NEGATED_OP = {"=": "!=", "!=": "=", "<": ">=", ">=": "<", ">": "<=", "<=": ">", "isnull": "notnull",
               "notnull": "isnull"}
 MAX_CONDITION_LEAVES = 12   # a select call takes 16 predicates; a literal-range filter adds three of its own
+
+
+_MIRRORED_OP = {"<": ">", "<=": ">=", ">": "<", ">=": "<=", "=": "=", "!=": "!="}
+INT64_MAX = (1 << 63) - 1
+
+
+def holds_distance(o) -> bool:
+    """Does an operand term hold a DISTANCE call -- ``("distfn", ColRef, ColRef, stranded, signed)`` -- anywhere?"""
+    if o[0] == "distfn":
+        return True
+    return o[0] == "fn" and any(holds_distance(c) for c in o[2])
+
+
+def comparison_leaf(lhs, op, rhs):
+    """The condition-tree leaf of ``lhs op rhs``.  Both front ends build every comparison through here, so a
+    DISTANCE call among the operands is met in ONE place: ``DISTANCE(x.interval, y.interval) <= N`` / ``< N``
+    (N an integer literal; also written ``N >= DISTANCE(...)``) becomes the join predicate
+    ``("within_distance", x, y, bound)``; every other use of the value in a condition declines -- the reference
+    evaluates its CASE row by row over a cartesian product there (docs/dialect/distance-operators.rst:68-78)."""
+    if not (holds_distance(lhs) or holds_distance(rhs)):
+        return ("leaf", ("cmp", lhs, op, rhs))
+    if lhs[0] != "distfn" and rhs[0] == "distfn":
+        lhs, rhs, op = rhs, lhs, _MIRRORED_OP.get(op, op)
+    if lhs[0] != "distfn":
+        raise decline("DISTANCE inside an arithmetic expression of a condition")
+    if op in ("isnull", "notnull"):
+        raise decline("IS [NOT] NULL over a DISTANCE")
+    if op not in ("<", "<="):
+        raise decline(f"DISTANCE compared with {op} (only DISTANCE(...) <= N and < N run as a join)")
+    if rhs[0] != "lit" or isinstance(rhs[1], bool) or not isinstance(rhs[1], int):
+        raise decline("DISTANCE bound that is not an integer literal")
+    _, a, b, stranded, signed = lhs
+    if stranded or signed:
+        raise decline("signed / stranded DISTANCE in a join condition")
+    bound = rhs[1] - (1 if op == "<" else 0)
+    if bound > INT64_MAX:
+        raise decline("DISTANCE bound that does not fit int64")
+    return ("leaf", (DISTANCE_TERM, a, b, max(bound, -1)))
 
 
 def _nnf(node, neg: bool = False):
@@ -186,6 +228,9 @@ class SelItem:
     alias: str | None = None
     func: str | None = None      # None = plain column
     distinct: bool = False
+    # DISTANCE(x.interval, y.interval [, stranded := b] [, signed := b]) as an output column: (ColRef x, ColRef y,
+    # stranded, signed); ``ref`` is None then
+    distance: tuple | None = None
 
 
 @dataclass
@@ -250,11 +295,50 @@ def _side_of(ref: ColRef, left: PlanSide, right: PlanSide, where: str) -> str:
     raise ValueError(f"Unknown table qualifier {ref.table!r} in {where}")
 
 
+def distance_projection(it: SelItem, left: PlanSide, right: PlanSide, tables: Tables) -> tuple:
+    """A DISTANCE select item -> ``(Projection("pair_distance", code, name), strand columns | None)``.  ``code``
+    says which table is the CASE's A operand -- "lr": the left one, "rl": the right one (the sign and the strand
+    flip follow A, src/giql/expanders/_distance.py:88-117) -- followed by "+signed" / "+stranded" as asked."""
+    x, y, stranded, signed = it.distance
+    for ref in (x, y):
+        if ref.star or ref.table is None:
+            raise decline("DISTANCE operand that is not a table-qualified column")
+    sx, sy = _side_of(x, left, right, "DISTANCE"), _side_of(y, left, right, "DISTANCE")
+    if sx == sy:
+        raise decline("DISTANCE between two columns of one table")
+    for ref, sd in ((x, sx), (y, sy)):
+        table = left.table if sd == "l" else right.table
+        if ref.column != genomic_col(table, tables):
+            raise ValueError(f"DISTANCE operands must be the tables' genomic columns "
+                             f"({genomic_col(left.table, tables)!r} / {genomic_col(right.table, tables)!r})")
+    strands = None
+    if stranded:
+        cols = []
+        for side in (left, right):
+            t = tables.get(side.table)
+            cols.append(t.strand_col if t is not None else "strand")
+        if not all(cols):
+            raise decline("stranded DISTANCE over a table without a strand column")
+        strands = ",".join(cols)
+    code = ("lr" if sx == "l" else "rl") + ("+signed" if signed else "") + ("+stranded" if stranded else "")
+    return Projection("pair_distance", code, it.alias or "distance"), strands
+
+
 def resolve_projection(items, left: PlanSide, right: PlanSide, left_only: bool,
-                       distance_alias: str | None = None) -> tuple[Projection, ...]:
+                       distance_alias: str | None = None, tables: Tables | None = None,
+                       strands_out: list | None = None) -> tuple[Projection, ...]:
+    """``strands_out`` (a list) receives the "<left>,<right>" strand columns of every stranded DISTANCE item."""
     out = []
     for it in items:
         ref = it.ref
+        if it.distance is not None:
+            if tables is None:      # (NEAREST: its own ``distance`` column is the one it offers)
+                raise decline("DISTANCE in the SELECT list of a NEAREST join")
+            proj, strands = distance_projection(it, left, right, tables)
+            out.append(proj)
+            if strands and strands_out is not None:
+                strands_out.append(strands)
+            continue
         if it.func is not None or ref.count:
             raise decline("COUNT(...) outside the count_overlaps LEFT JOIN ... GROUP BY shape")
         if ref.star:
@@ -282,6 +366,10 @@ def bind_expression(o, bind_leaf) -> Operand:
     """An operand term -- ``("lit", v)`` / a column term / ``("fn", op, [terms])`` -- as a plan operand; columns and
     literals through ``bind_leaf``.  Arithmetic becomes ``Operand("expr", ["fn", op, [children]])`` whose leaves
     are ``[kind, value]`` pairs (lists throughout: the plan's JSON form gives lists back)."""
+    if holds_distance(o):
+        # (comparison_leaf turns the one accepted use into a join predicate before any operand is bound; whatever still
+        # carries a call here came past it, and a "distfn" term must never be read as a column term)
+        raise decline("DISTANCE as an operand of a condition (only DISTANCE(...) <= N and < N run, as a join)")
     if o[0] != "fn":
         return bind_leaf(o)
 
@@ -620,6 +708,12 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
         left = table_side(shape.from_ref, tables)
         right = table_side(shape.join_ref, tables)
     has_count_item = any((it.func == "COUNT" and it.ref is not None and not it.distinct) for it in items)
+    dist_items = [it for it in items if it.distance is not None]
+    if dist_items and kind != "INNER":
+        # the value is defined per PAIR: SEMI / ANTI keep left rows, count_overlaps counts them
+        raise decline(f"{'count_overlaps / outer' if kind == 'LEFT' else kind} join with a DISTANCE in the SELECT list")
+    if dist_items and (shape.group_by or shape.having or any(it.func is not None for it in items)):
+        raise decline("DISTANCE in the SELECT list beside GROUP BY / HAVING / aggregates")
     if kind == "LEFT":
         # count_overlaps: LEFT [OUTER] JOIN ... COUNT(b.col) ... GROUP BY left keys
         # (_match_count_overlaps, intersects_duckdb.py:432-548); every other outer join declines (:661-662)
@@ -639,19 +733,21 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
     on_terms, where_terms = list(shape.on_terms), list(shape.where_terms)
     if not shape.on_seen and not shape.using and kind in ("SEMI", "ANTI"):
         raise decline("SEMI/ANTI join with its INTERSECTS outside ON")  # #201
-    spatial = [t for t in on_terms + where_terms if t[0] in SPATIAL_TERMS]
+    spatial = [t for t in on_terms + where_terms if t[0] in JOIN_TERMS]
     if not spatial:
         raise decline("join without an INTERSECTS predicate")
     if len(spatial) > 1:
         raise decline("more than one INTERSECTS" if all(t[0] == "intersects" for t in spatial)
                       else "more than one spatial predicate in a join")
-    predicate, lhs, rhs = spatial[0]
+    predicate, lhs, rhs = spatial[0][:3]
+    max_distance = spatial[0][3] if predicate == DISTANCE_TERM else None
+    label = "DISTANCE" if predicate == DISTANCE_TERM else predicate.upper()
     if predicate != "intersects":
-        # CONTAINS / WITHIN run as the pair-producing join only (HipEngine.contain_join)
+        # CONTAINS / WITHIN / DISTANCE <= N run as the pair-producing join only (HipEngine.contain_join / window_join)
         if kind in ("SEMI", "ANTI"):
-            raise decline(f"{kind} join over {predicate.upper()}")
+            raise decline(f"{kind} join over {label}")
         if kind == "COUNT":
-            raise decline(f"count_overlaps over {predicate.upper()}")
+            raise decline(f"count_overlaps over {label}")
     if kind in ("SEMI", "ANTI") and not any(t[0] == "intersects" for t in on_terms):
         raise decline("SEMI/ANTI join with its INTERSECTS outside ON")  # #201
     cmp_terms = ([("on", t) for t in on_terms if t[0] in ("cmp", "or", "tree")]
@@ -679,7 +775,7 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
         raise decline("INTERSECTS operands that do not name the two joined tables")
     if l_col != genomic_col(left.table, tables) or r_col != genomic_col(right.table, tables):
         raise ValueError(
-            f"{spatial[0][0].upper()} operands must be the tables' genomic columns "
+            f"{'DISTANCE' if spatial[0][0] == DISTANCE_TERM else spatial[0][0].upper()} operands must be the tables' genomic columns "
             f"({genomic_col(left.table, tables)!r} / {genomic_col(right.table, tables)!r})")
     if kind == "COUNT":
         if shape.distinct:
@@ -692,6 +788,7 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
     grouped = bool(shape.group_by) or any(it.func is not None for it in items) or bool(shape.having)
     output: tuple[str, ...] = ()
     having: tuple[Having, ...] = ()
+    strands: list = []          # strand columns of the stranded DISTANCE select items (all alike: one pair of tables)
     if grouped:
         proj, aggs, groups, output = _resolve_grouped(shape, left, right, left_only)
         visible_aggs = aggs
@@ -701,13 +798,35 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
             # columns it projects are neither grouped nor aggregated
             raise ValueError("a projected column must appear in GROUP BY or inside an aggregate")
     else:
-        proj, aggs, groups = resolve_projection(items, left, right, left_only), (), ()
+        proj, aggs, groups = resolve_projection(items, left, right, left_only, tables=tables, strands_out=strands), (), ()
         visible_aggs = ()
     hidden, order = _resolve_order(shape, proj, visible_aggs, left, right, left_only, grouped)
+    if predicate == DISTANCE_TERM:
+        # x.chrom = y.chrom beside the predicate (the documented recipe writes it): a NULL distance already drops
+        # pairs across chromosomes, the join IS per chromosome -- absorbed, not run as a string comparison per pair
+        cmp_terms = [(c, t) for c, t in cmp_terms if not _is_chrom_equality(t, left, right)]
     residuals = resolve_residuals(cmp_terms, left, right, kind)
-    return JoinPlan(kind, left, right, tuple(proj) + hidden, shape.distinct, residuals=residuals,
+    strand_col = strands[0] if strands else None
+    return JoinPlan(kind, left, right, tuple(proj) + hidden, shape.distinct, max_distance=max_distance,
+                    residuals=residuals, strand_col=strand_col,
                     aggregates=aggs, group_by=groups, having=having, order_by=order,
                     limit=shape.limit, offset=shape.offset, output=output, predicate=predicate)
+
+
+def _is_chrom_equality(term, left: PlanSide, right: PlanSide) -> bool:
+    """``<left alias>.<its chrom column> = <right alias>.<its chrom column>`` (either way round)."""
+    if term[0] != "cmp" or term[2] != "=" or term[1][0] != "col" or term[3][0] != "col":
+        return False
+    got = set()
+    for o in (term[1], term[3]):
+        ref: ColRef = o[1]
+        if ref.table is None or ref.star:
+            return False
+        q = norm(ref.table, ref.table_quoted)
+        for tag, side in (("l", left), ("r", right)):
+            if q == side.alias and ref.column == side.chrom_col:
+                got.add(tag)
+    return got == {"l", "r"}
 
 
 # ------------------------------------------------------------------ DISJOIN

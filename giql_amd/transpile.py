@@ -44,6 +44,8 @@ from .shape import operand_sides as _operand_sides
 from .shape import decline as _decline
 from .shape import genomic_col as _genomic_col
 from .shape import SPATIAL_TERMS, DisjoinShape, lower_disjoin_shape, lower_join_shape, resolve_projection
+from .shape import comparison_leaf as _comparison_leaf
+from .shape import holds_distance as _holds_distance
 from .shape import norm as _norm
 from .shape import table_side as _table_side
 from .table import Table, Tables, build_tables, encoding_of
@@ -187,6 +189,41 @@ _CLAUSE_END = ("WHERE", "GROUP", "ORDER", "HAVING", "LIMIT", "OFFSET", "UNION", 
 _ARITH_FUNCS = {"LEAST": "least", "GREATEST": "greatest", "ABS": "abs"}
 
 
+def _at_distance_call(p: _Parser) -> bool:
+    t = p.peek()
+    return t.kind == "id" and not t.quoted and t.text.upper() == "DISTANCE" and p.peek(1).kind == "punct" \
+        and p.peek(1).text == "("
+
+
+def _parse_distance_call(p: _Parser):
+    """``DISTANCE(x.interval, y.interval [, stranded := <bool>] [, signed := <bool>])`` at the cursor ->
+    ``("distfn", ColRef x, ColRef y, stranded, signed)`` (src/giql/expressions.py:288-323).  A literal range as an
+    operand is the reference's own error (src/giql/expanders/distance.py:123)."""
+    p.next()
+    p.expect_punct("(")
+    refs = []
+    for position in ("first", "second"):
+        if p.peek().kind == "str":
+            raise ValueError(f"Literal range as {position} argument not yet supported")
+        if p.peek().kind != "id":
+            raise _decline("DISTANCE operand that is not a column")
+        refs.append(p.colref())
+        if position == "first":
+            p.expect_punct(",")
+    flags = {"stranded": False, "signed": False}
+    while p.at_punct(","):
+        p.next()
+        name = p.next()
+        if name.kind != "id" or name.text.lower() not in flags or p.peek().kind != "assign":
+            raise _decline("DISTANCE argument other than stranded := / signed :=")
+        p.next()
+        if not p.at_kw("TRUE", "FALSE"):
+            raise _decline(f"non-literal {name.text.lower()} argument")
+        flags[name.text.lower()] = p.next().text == "TRUE"
+    p.expect_punct(")")
+    return ("distfn", refs[0], refs[1], flags["stranded"], flags["signed"])
+
+
 def _parse_atom(p: _Parser, expr=None):
     """A residual operand without arithmetic: [-]number, 'string', a column reference, or -- when ``expr`` (the
     parser of a full expression) is given -- ``LEAST / GREATEST / ABS ( ... )``."""
@@ -206,6 +243,8 @@ def _parse_atom(p: _Parser, expr=None):
         raise _decline("boolean literal in a join condition")
     if t.kind != "id":
         raise _decline(f"join condition operand near {t.text!r}")
+    if expr is not None and _at_distance_call(p):
+        return _parse_distance_call(p)
     if expr is not None and not t.quoted and t.text.upper() in _ARITH_FUNCS and p.peek(1).kind == "punct" \
             and p.peek(1).text == "(":
         name = _ARITH_FUNCS[p.next().text.upper()]
@@ -310,6 +349,8 @@ def _parse_predicate(p: _Parser, allow_literal: bool, operand=None):
         negated = True
     if p.at_kw("LIKE"):
         raise _decline("LIKE predicate")
+    if _holds_distance(lhs) and (p.at_kw("BETWEEN", "IN") or negated):
+        raise _decline("BETWEEN / IN over a DISTANCE")
     if p.at_kw("BETWEEN"):
         p.next()
         lo = operand(p)
@@ -317,7 +358,9 @@ def _parse_predicate(p: _Parser, allow_literal: bool, operand=None):
         p.expect_kw("AND")
         hi = operand(p)
         _no_arithmetic(p)
-        node = ("and", [("leaf", ("cmp", lhs, ">=", lo)), ("leaf", ("cmp", lhs, "<=", hi))])
+        if _holds_distance(lo) or _holds_distance(hi):
+            raise _decline("BETWEEN / IN over a DISTANCE")
+        node = ("and", [_comparison_leaf(lhs, ">=", lo), _comparison_leaf(lhs, "<=", hi)])
     elif p.at_kw("IN"):
         p.next()
         p.expect_punct("(")
@@ -334,7 +377,7 @@ def _parse_predicate(p: _Parser, allow_literal: bool, operand=None):
                 continue
             break
         p.expect_punct(")")
-        node = ("or", [("leaf", ("cmp", lhs, "=", v)) for v in values])
+        node = ("or", [_comparison_leaf(lhs, "=", v) for v in values])
     elif p.at_kw("IS"):
         p.next()
         is_not = False
@@ -346,14 +389,14 @@ def _parse_predicate(p: _Parser, allow_literal: bool, operand=None):
         p.next()
         if lhs[0] == "lit":
             raise _decline("IS NULL over a literal")
-        return ("leaf", ("cmp", lhs, "notnull" if is_not else "isnull", ("lit", 0)))
+        return _comparison_leaf(lhs, "notnull" if is_not else "isnull", ("lit", 0))
     else:
         op = _parse_comparison_op(p)
         if op is None:
             raise _decline("join condition other than INTERSECTS / simple comparisons")
         rhs = operand(p)
         _no_arithmetic(p)
-        return ("leaf", ("cmp", lhs, op, rhs))
+        return _comparison_leaf(lhs, op, rhs)
     return ("not", node) if negated else node
 
 
@@ -442,6 +485,8 @@ _UNSUPPORTED_TAIL = ("GROUP", "ORDER", "HAVING", "LIMIT", "OFFSET", "UNION")
 def _parse_aggregate_call(p: _Parser, where: str):
     """``FUNC([DISTINCT] <col> | *)`` at the cursor -> (func, distinct, ColRef | None)."""
     func = p.peek().text.upper()
+    if func == "DISTANCE":
+        raise _decline(f"DISTANCE in {where}")
     if func not in AGG_FUNCS:
         raise _decline(f"function call in {where}")
     p.next()
@@ -450,6 +495,8 @@ def _parse_aggregate_call(p: _Parser, where: str):
     if p.at_kw("DISTINCT"):
         p.next()
         distinct = True
+    if _at_distance_call(p):
+        raise _decline("DISTANCE inside an aggregate")
     if p.at_punct("*"):
         p.next()
         ref = None
@@ -504,7 +551,10 @@ def _parse_projection(p: _Parser) -> list[SelItem]:
         is_call = t.kind == "id" and not t.quoted and p.peek(1).kind == "punct" and p.peek(1).text == "("
         func = None
         distinct = False
-        if is_call:
+        distance = None
+        if _at_distance_call(p):
+            ref, distance = None, _parse_distance_call(p)[1:]
+        elif is_call:
             func, distinct, ref = _parse_aggregate_call(p, "the SELECT list")
             if ref is not None and func == "COUNT" and not distinct:
                 ref.count = True
@@ -520,7 +570,7 @@ def _parse_projection(p: _Parser) -> list[SelItem]:
             alias = p.next().text
         elif p.peek().kind == "id":
             alias = p.next().text
-        items.append(SelItem(ref, alias, func, distinct))
+        items.append(SelItem(ref, alias, func, distinct, distance))
         if p.at_punct(","):
             p.next()
             continue
@@ -1186,6 +1236,8 @@ def _lower(giql: str, tables, want_sql: bool):
         p.next()
         p.expect_kw("BY")
         while True:
+            if _at_distance_call(p):
+                raise _decline("DISTANCE in GROUP BY")
             if p.peek().kind != "id":
                 raise _decline("GROUP BY expression")
             shape.group_by.append(p.colref())

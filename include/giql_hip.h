@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define GIQL_HIP_ABI_VERSION 4  /* 2: giql_hip_stats.phase_bytes, pinned host outputs, plan export; 3: DISJOIN; 4: CONTAINS / WITHIN */
+#define GIQL_HIP_ABI_VERSION 4  /* 2: giql_hip_stats.phase_bytes, pinned host outputs, plan export; 3: DISJOIN; 4: CONTAINS / WITHIN (DISTANCE added two symbols, no change) */
 
 enum {
   GIQL_OK = 0,
@@ -301,6 +301,33 @@ int giql_hip_contain_plan_dev(giql_hip_ctx* ctx, const giql_side* outer, const g
                               int32_t n_chrom, void* stream, int64_t* n_pairs);
 int giql_hip_contain_fill_dev(giql_hip_ctx* ctx, int32_t* row_outer, int32_t* row_inner,
                               int64_t capacity, void* stream);
+/* DISTANCE (src/giql/expanders/_distance.py:67-117, the CASE; src/giql/expanders/distance.py:297-331, which of its
+ * four variants runs): 0 for overlapping rows, gap + 1 otherwise (book-ended rows: 1), NULL across chromosomes.
+ *
+ * giql_hip_window_plan_dev -- the documented "all pairs within N bp" recipe (docs/dialect/distance-operators.rst:68-78,
+ * docs/recipes/distance.rst:60-73: a per-chromosome cartesian product filtered by the CASE) as a range join: *n_pairs =
+ * the exact number of (row_a, row_b) with equal chrom and DISTANCE(a, b) <= max_distance (>= 0) on canonical
+ * coordinates.  For rows with start <= end that is the overlap predicate with A widened by max_distance,
+ *   a.start - N < b.end AND a.end + N > b.start,
+ * so the plan is an INNER plan in the general two-class form (stats.reserved bits 0-3 = 0, always) and
+ * giql_hip_inner_fill_dev fills it, under the INNER plan's rules; giql_hip_inner_plan_export_dev returns GIQL_ERR_STATE
+ * after it (a window plan WITHOUT PAIRS exports as an INNER plan without pairs does: GIQL_OK with zero counts).  The widening is this parameter alone (giql_side's offsets keep their meaning and their checks); it happens
+ * in 64 bits while the keys are made, clamped to one position beyond the chromosome's coordinate range over both
+ * sides, so the linear axis grows by 2 positions per chromosome whatever max_distance is.  Zero-length rows (and A rows
+ * that stay zero-length at max_distance = 0) follow the literal predicate, a thread per row against their list.
+ * GIQL_ERR_INVALID: max_distance < 0, or a row of either side has canonical end < start (the message names the
+ * side, and giql_hip_get_stats reports n_irregular_a / n_irregular_b = -1 for every side that holds such a row); GIQL_ERR_CHROM / GIQL_ERR_SPAN as for the INNER join. */
+int giql_hip_window_plan_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, int32_t n_chrom,
+                             int64_t max_distance, void* stream, int64_t* n_pairs);
+/* dist_out[i] / valid_out[i] = DISTANCE(a row row_a[i], b row row_b[i]) for i < n: an int64 value and a validity
+ * byte (0 = SQL NULL, the value is 0 then), computed in 64 bits.  flags: bit 0 = signed (negative when B lies
+ * upstream), bit 1 = stranded (NULL unless both strands are '+' / '-'; the sign flips on A's '-' strand); the + 1 is
+ * applied to the gap before any sign.  strand_a / strand_b: one int32 code per ROW of the table (0 '+', 1 '-', 2 '.',
+ * 3 '?', anything else NULL), read only when stranded (NULL otherwise).  All DEVICE pointers.  A row id outside
+ * [0, side n) is GIQL_ERR_INVALID and nothing is read through it.  Uses no workspace: a plan on the context stays. */
+int giql_hip_distance_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, const int32_t* row_a,
+                          const int32_t* row_b, int64_t n, const int32_t* strand_a, const int32_t* strand_b,
+                          int32_t flags, int64_t* dist_out, uint8_t* valid_out, void* stream);
 /* MERGE(..., predicate := ...): merge.py:201-210 hands the predicate to the CLUSTER it is built on, so a
  * merged region is a cluster of giql_hip_cluster_pred_dev; its MAX(end) is taken over the region's own
  * rows (a region may end while an earlier one still reaches further). */
