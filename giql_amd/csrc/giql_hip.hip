@@ -36,6 +36,7 @@
 #include "radix_sort.hip.h"
 #include "scan.hip.h"
 #include "probe_kernels.hip.h"
+#include "index_rows_kernels.hip.h"
 
 using namespace giql;
 
@@ -2382,6 +2383,11 @@ struct giql_hip_index {
   u32 *key = nullptr, *end = nullptr, *rid = nullptr;   // [n] sorted by key (every bucket sorted in place)
   u32* small = nullptr;    // the sort's digit offsets gbase[4][256] | first[n_chrom + 1]: chromosome c owns keys [first[c], first[c + 1])
   size_t bytes = 0;
+  // what the per-row operators read (giql_hip_index_prepare_rows_dev: built on their first call, never at creation)
+  bool rows_ready = false;
+  u32* bnd_key = nullptr;     // [2^(32 - wbits) + 1] directory over key: first row with key >= v << wbits
+  u32* end_sorted = nullptr;  // general form: [n] the end keys alone, sorted ...
+  u32* bnd_end = nullptr;     // ... and their directory
 };
 
 int giql_hip_index_destroy(giql_hip_index* idx) {
@@ -2391,6 +2397,9 @@ int giql_hip_index_destroy(giql_hip_index* idx) {
   if (idx->end) (void)hipFree(idx->end);
   if (idx->rid) (void)hipFree(idx->rid);
   if (idx->small) (void)hipFree(idx->small);
+  if (idx->bnd_key) (void)hipFree(idx->bnd_key);
+  if (idx->end_sorted) (void)hipFree(idx->end_sorted);
+  if (idx->bnd_end) (void)hipFree(idx->bnd_end);
   delete idx;
   return GIQL_OK;
 }
@@ -2617,6 +2626,223 @@ int giql_hip_inner_join_indexed_dev(giql_hip_ctx* ctx, const giql_hip_index* idx
   ctx->stats.phase_bytes[GIQL_PH_SORT_LOCAL] += (int64_t)8 * (int64_t)total;
   if (total > (u64)capacity)
     return set_err(GIQL_ERR_CAPACITY, "capacity %lld < %llu pairs", (long long)capacity, (unsigned long long)total);
+  return GIQL_OK;
+}
+
+// ------------------------------------------- per-row operators against an index
+// What COUNT / SEMI / ANTI read of an index beyond its sorted start keys (index_rows_kernels.hip.h): a directory of
+// bucket boundaries over them and, in the general form, the end keys alone, sorted, with a directory of their own.
+// Built once per index, on the first row-operator call (or by giql_hip_index_prepare_rows_dev), into buffers of the
+// index's own; key / end / rid are only read.  The caller has run begin_call; the arena is claimed here and free
+// again on return.
+static int index_prepare_rows_core(giql_hip_ctx* ctx, giql_hip_index* idx, hipStream_t st) {
+  const size_t n = idx->n;
+  const u32 wbits = (u32)idx->wbits;
+  const size_t n_cells = (size_t)bs_n_buckets(wbits) + 1;
+  struct Built {  // released on every early way out
+    u32 *bnd_key = nullptr, *end_sorted = nullptr, *bnd_end = nullptr;
+    ~Built() {
+      if (bnd_key) (void)hipFree(bnd_key);
+      if (end_sorted) (void)hipFree(end_sorted);
+      if (bnd_end) (void)hipFree(bnd_end);
+    }
+  } w;
+  size_t added = n_cells * sizeof(u32);
+  HIP_TRY(hipMalloc((void**)&w.bnd_key, n_cells * sizeof(u32)));
+  // a directory: every cell written once, behind a search of ~log2(rows per top digit) keys
+  const int64_t dir_bytes = (int64_t)n_cells * (4 + 4 * 24);
+  {
+    Phase ph(ctx, st, GIQL_PH_AUX);
+    ctx->stats.phase_bytes[GIQL_PH_AUX] += dir_bytes;
+    hipLaunchKernelGGL(k_bucket_bounds, dim3(cdiv(n_cells, 256)), dim3(256), 0, st, idx->key, (u32)n,
+                       idx->small + 3 * OS_BINS, w.bnd_key, wbits);
+    GIQL_TRY(post_launch("start directory (index)"));
+  }
+  if (idx->general) {
+    HIP_TRY(hipMalloc((void**)&w.end_sorted, n * sizeof(u32)));
+    HIP_TRY(hipMalloc((void**)&w.bnd_end, n_cells * sizeof(u32)));
+    added += n * sizeof(u32) + n_cells * sizeof(u32);
+    SortBufs se;  // a keys-only sort: buffer 0 = the index's new array, buffer 1 in the arena
+    u32 *hist = nullptr, *gbase = nullptr, *status = nullptr;
+    auto carve = [&](char* base) {
+      Carver c{base};
+      se.key[1] = c.take<u32>(n);
+      hist = c.take<u32>((size_t)LIN_HIST_REPLICAS * 1024);
+      gbase = c.take<u32>(1024);
+      status = c.take<u32>(4 * os_pass_words(n));
+      return c.off;
+    };
+    GIQL_TRY(claim_arena(ctx, st, carve));
+    se.key[0] = w.end_sorted;
+    se.end[0] = se.end[1] = se.rid[0] = se.rid[1] = nullptr;
+    HIP_TRY(hipMemsetAsync(hist, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
+    {
+      Phase ph(ctx, st, GIQL_PH_AUX);  // the copy of the end keys the sort starts from: read once, written once
+      ctx->stats.phase_bytes[GIQL_PH_AUX] += (int64_t)8 * n;
+      HIP_TRY(hipMemcpyAsync(w.end_sorted, idx->end, n * sizeof(u32), hipMemcpyDeviceToDevice, st));
+    }
+    {
+      Phase ph(ctx, st, GIQL_PH_SORT_HIST, 3);  // the end keys' digit histogram: every key read once
+      ctx->stats.phase_bytes[GIQL_PH_SORT_HIST] += (int64_t)4 * n;
+      hipLaunchKernelGGL(k_init_minmax, dim3(1), dim3(256), 0, st, (int*)nullptr, (int*)nullptr, 0, ctx->d_meta);
+      u32 grid = cdiv(n, IR_NT);
+      if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
+      hipLaunchKernelGGL(k_hist_u32, dim3(grid), dim3(IR_NT), 0, st, idx->end, (u32)n, hist, (u32)LIN_HIST_REPLICAS);
+      hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, hist, (u32)LIN_HIST_REPLICAS, gbase);
+      GIQL_TRY(post_launch("end-key digits (index)"));
+    }
+    {
+      ForceLocal global_only{ctx, -1};  // four global passes: the result is back in buffer 0
+      GIQL_TRY(run_sort_onesweep(ctx, st, se, (u32)n, gbase, status));
+    }
+    if (se.key[0] != w.end_sorted) return set_err(GIQL_ERR_HIP, "internal: the sort did not end in the index's buffer");
+    {
+      Phase ph(ctx, st, GIQL_PH_AUX);
+      ctx->stats.phase_bytes[GIQL_PH_AUX] += dir_bytes;
+      hipLaunchKernelGGL(k_bucket_bounds, dim3(cdiv(n_cells, 256)), dim3(256), 0, st, w.end_sorted, (u32)n,
+                         gbase + 3 * OS_BINS, w.bnd_end, wbits);
+      GIQL_TRY(post_launch("end directory (index)"));
+    }
+    GIQL_TRY(read_meta(ctx, st));  // (a look-back timeout of the sort; synchronises the stream)
+  } else {
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  idx->bnd_key = w.bnd_key, idx->end_sorted = w.end_sorted, idx->bnd_end = w.bnd_end;
+  w.bnd_key = w.end_sorted = w.bnd_end = nullptr;
+  idx->bytes += added;
+  idx->rows_ready = true;
+  return GIQL_OK;
+}
+
+static int index_prepare_rows(giql_hip_ctx* ctx, giql_hip_index* idx, hipStream_t st) {
+  if (idx->rows_ready) return GIQL_OK;
+  return with_order_fallback(ctx, [&] { return index_prepare_rows_core(ctx, idx, st); });
+}
+
+static int check_index_call(giql_hip_ctx* ctx, const giql_hip_index* idx) {
+  if (!ctx || !idx) return set_err(GIQL_ERR_INVALID, "ctx/index is NULL");
+  if (idx->device != ctx->device)
+    return set_err(GIQL_ERR_INVALID, "the index lives on device %d, the context on %d", idx->device, ctx->device);
+  return GIQL_OK;
+}
+
+int giql_hip_index_prepare_rows_dev(giql_hip_ctx* ctx, giql_hip_index* idx, void* stream) {
+  GIQL_TRY(check_index_call(ctx, idx));
+  if (idx->rows_ready) return GIQL_OK;
+  GIQL_TRY(begin_call(ctx));
+  ctx->plan.planned = false;
+  ctx->stats.n_b = idx->n;
+  GIQL_TRY(index_prepare_rows(ctx, idx, (hipStream_t)stream));
+  collect_spans(ctx);
+  ctx->stats.span = (int64_t)idx->span;
+  return GIQL_OK;
+}
+
+static IndexRowsView rows_view_of(const giql_hip_index* idx) {
+  IndexRowsView v;
+  v.first = idx->small + 1024;
+  v.key = idx->key;
+  v.bnd_key = idx->bnd_key;
+  v.end_key = idx->general ? idx->end_sorted : nullptr;
+  v.bnd_end = idx->general ? idx->bnd_end : nullptr;
+  v.n = idx->n;
+  v.n_chrom = idx->n_chrom;
+  v.wbits = (u32)idx->wbits;
+  v.uni_len = idx->uni_len;
+  return v;
+}
+
+// bytes of the row kernel: the row's three columns, two directory cells per search and one key per step of a search
+// inside an average bucket
+static int64_t index_rows_bytes(const giql_hip_index* idx, size_t na, int out_bytes) {
+  const double per_bucket = (double)idx->n / (double)bs_n_buckets((u32)idx->wbits);
+  int steps = 1;
+  while ((double)(1u << steps) < per_bucket + 1.0 && steps < 31) steps++;
+  return (int64_t)na * (12 + out_bytes + 2 * (8 + 4 * steps));
+}
+
+// The prologue the two row operators share: checks, begin_call, the sizes, the index's row arrays.
+static int begin_index_rows_call(giql_hip_ctx* ctx, giql_hip_index* idx, const giql_side* a, hipStream_t st) {
+  GIQL_TRY(check_index_call(ctx, idx));
+  GIQL_TRY(check_side(a, "a"));
+  GIQL_TRY(begin_call(ctx));
+  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
+  ctx->stats.n_a = a->n;
+  ctx->stats.n_b = idx->n;
+  if (a->n == 0) return GIQL_OK;
+  return index_prepare_rows(ctx, idx, st);
+}
+
+static int finish_index_rows_call(giql_hip_ctx* ctx, const giql_hip_index* idx, hipStream_t st) {
+  GIQL_TRY(read_meta(ctx, st));
+  collect_spans(ctx);
+  ctx->stats.span = (int64_t)idx->span;
+  ctx->stats.reserved = idx->general ? 0 : 1;
+  if (ctx->h_meta->aux0)
+    return set_err(GIQL_ERR_STATE, "the query table holds irregular rows (canonical end <= start): use the ordinary operator");
+  return GIQL_OK;
+}
+
+int giql_hip_count_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const giql_side* a, int64_t* counts_out,
+                               void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  GIQL_TRY(begin_index_rows_call(ctx, idx, a, st));
+  if (a->n == 0) return GIQL_OK;
+  if (!counts_out) return set_err(GIQL_ERR_INVALID, "counts_out is NULL");
+  const size_t na = (size_t)a->n;
+  GIQL_TRY(claim_arena(ctx, st, [](char*) { return (size_t)0; }));
+  HIP_TRY(hipMemsetAsync(ctx->d_meta, 0, sizeof(DevMeta), st));
+  {
+    Phase ph(ctx, st, GIQL_PH_COUNT);
+    ctx->stats.phase_bytes[GIQL_PH_COUNT] += index_rows_bytes(idx, na, 8);
+    hipLaunchKernelGGL(k_index_rows<false>, dim3(cdiv(na, IR_NT)), dim3(IR_NT), 0, st, a->chrom, a->start, a->end, (u32)na,
+                       a->start_off, a->end_off, rows_view_of(idx), 0, counts_out, (u32*)nullptr, &ctx->d_meta->aux0);
+    GIQL_TRY(post_launch("count rows (index)"));
+  }
+  GIQL_TRY(finish_index_rows_call(ctx, idx, st));
+  ctx->stats.n_out = a->n;
+  return GIQL_OK;
+}
+
+int giql_hip_semi_anti_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const giql_side* a, int anti,
+                                   int32_t* rows_out, int64_t* n_out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (ctx && idx && !n_out) return set_err(GIQL_ERR_INVALID, "n_out is NULL");
+  GIQL_TRY(begin_index_rows_call(ctx, idx, a, st));
+  *n_out = 0;
+  if (a->n == 0) return GIQL_OK;
+  if (!rows_out) return set_err(GIQL_ERR_INVALID, "rows_out is NULL");
+  const size_t na = (size_t)a->n;
+  u32* flag = nullptr;
+  u64* bsums = nullptr;
+  auto carve = [&](char* base) {
+    Carver c{base};
+    flag = c.take<u32>(na);
+    bsums = c.take<u64>(cdiv(na, SCAN_TILE) + 2);
+    return c.off;
+  };
+  GIQL_TRY(claim_arena(ctx, st, carve));
+  HIP_TRY(hipMemsetAsync(ctx->d_meta, 0, sizeof(DevMeta), st));
+  {
+    Phase ph(ctx, st, GIQL_PH_COUNT);
+    ctx->stats.phase_bytes[GIQL_PH_COUNT] += index_rows_bytes(idx, na, 4);
+    hipLaunchKernelGGL(k_index_rows<true>, dim3(cdiv(na, IR_NT)), dim3(IR_NT), 0, st, a->chrom, a->start, a->end, (u32)na,
+                       a->start_off, a->end_off, rows_view_of(idx), anti, (i64*)nullptr, flag, &ctx->d_meta->aux0);
+    GIQL_TRY(post_launch("semi flags (index)"));
+  }
+  {
+    // the scan of the flags with the compaction in its down-sweep, as giql_hip_semi_anti_dev runs it
+    const u32 nbk = cdiv(na, SCAN_TILE);
+    Phase ph(ctx, st, GIQL_PH_SCAN, 3);
+    hipLaunchKernelGGL(k_scan_reduce, dim3(nbk), dim3(SCAN_NT), 0, st, flag, (u64)na, bsums);
+    hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, st, bsums, nbk, bsums + nbk + 1, &ctx->d_meta->n_out);
+    hipLaunchKernelGGL(k_scan_down_compact, dim3(nbk), dim3(SCAN_NT), 0, st, flag, (u64)na, bsums, rows_out);
+    GIQL_TRY(post_launch("scan + compact (index)"));
+  }
+  GIQL_TRY(finish_index_rows_call(ctx, idx, st));
+  *n_out = (int64_t)ctx->h_meta->n_out;
+  ctx->stats.n_out = *n_out;
+  ctx->stats.phase_bytes[GIQL_PH_SCAN] += (int64_t)8 * (int64_t)na + (int64_t)4 * *n_out;
   return GIQL_OK;
 }
 

@@ -97,13 +97,33 @@ class DeviceSide:
 class DeviceIndex:
     """A table index in HBM (``giql_hip_index``): what the reference's users get from ``CREATE INDEX ... (chrom,
     start, "end")`` (``docs/transpilation/performance.rst:111-130``).  Built by :meth:`HipEngine.index_create`,
-    used by :meth:`HipEngine.inner_join_indexed`; released by :meth:`close` / garbage collection."""
+    used by :meth:`HipEngine.inner_join_indexed`, :meth:`HipEngine.count_overlaps_indexed` and
+    :meth:`HipEngine.semi_anti_indexed`; released by :meth:`close` / garbage collection."""
 
     def __init__(self, engine: "HipEngine", handle, n_chrom: int):
         self.engine, self._h, self.n_chrom, self.last_pairs = engine, handle, n_chrom, 0
+        self._rows_prepared = False     # the row operators' arrays exist and ``nbytes`` counts them
+        self._refresh_info()
+
+    def _refresh_info(self) -> None:
         n, b, g, sp = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
-        _lib.check(engine._L.giql_hip_index_info(handle, ctypes.byref(n), ctypes.byref(b), ctypes.byref(g), ctypes.byref(sp)))
+        _lib.check(self.engine._L.giql_hip_index_info(self._h, ctypes.byref(n), ctypes.byref(b), ctypes.byref(g), ctypes.byref(sp)))
         self.n, self.nbytes, self.general, self.span = int(n.value), int(b.value), bool(g.value), int(sp.value)
+
+    def _note_rows_prepared(self) -> None:
+        if not self._rows_prepared:     # (a row operator that succeeded has prepared the index on the way)
+            self._rows_prepared = True
+            self._refresh_info()
+
+    def prepare_rows(self) -> None:
+        """Build what the per-row operators read of the index (``giql_hip_index_prepare_rows_dev``: a directory of
+        bucket boundaries; for a table of variable length its sorted end keys too, 4 B per row).  Once per index
+        -- a second call does nothing -- and done by the first ``count_overlaps_indexed`` / ``semi_anti_indexed``
+        call otherwise; ``nbytes`` is refreshed."""
+        eng = self.engine
+        _lib.check(eng._L.giql_hip_index_prepare_rows_dev(eng._h, self._h, eng._stream()))
+        self._rows_prepared = True
+        self._refresh_info()
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -356,6 +376,43 @@ class HipEngine:
         _lib.check(rc)
         index.last_pairs = int(n.value)
         return int(n.value)
+
+    def _check_indexed(self, a: DeviceSide, index: "DeviceIndex") -> None:
+        if index.engine is not self:
+            raise ValueError("the index was built on another engine")
+        if a.n and a.device != self.device:
+            raise ValueError(f"side lives on {a.device}, engine on {self.device}")
+
+    def count_overlaps_indexed(self, a: DeviceSide, index: "DeviceIndex"):
+        """int64 device tensor: the number of overlapping rows of the indexed table per row of ``a``, in ``a``'s
+        order (``giql_hip_count_indexed_dev``: what :meth:`count_overlaps` returns, without sorting either side).
+        ``a.chrom`` speaks the indexed table's dictionary.  ``GIQL_ERR_STATE`` when ``a`` holds irregular rows."""
+        torch = _torch()
+        self._check_indexed(a, index)
+        counts = torch.zeros(a.n, dtype=torch.int64, device=self.device)
+        ca = a.c_struct()
+        rc = self._L.giql_hip_count_indexed_dev(self._h, index._h, ctypes.byref(ca),
+                                                counts.data_ptr() if a.n else None, self._stream())
+        _lib.check(rc)
+        if a.n:                         # (an empty query returns before the index is prepared)
+            index._note_rows_prepared()
+        return counts
+
+    def semi_anti_indexed(self, a: DeviceSide, index: "DeviceIndex", anti: bool):
+        """Ascending int32 row ids of ``a`` with (SEMI) / without (ANTI) an overlapping row of the indexed table
+        (``giql_hip_semi_anti_indexed_dev``: what :meth:`semi_anti` returns).  ``GIQL_ERR_STATE`` when ``a`` holds
+        irregular rows."""
+        torch = _torch()
+        self._check_indexed(a, index)
+        rows = torch.empty(a.n, dtype=torch.int32, device=self.device)
+        n = ctypes.c_int64(0)
+        ca = a.c_struct()
+        rc = self._L.giql_hip_semi_anti_indexed_dev(self._h, index._h, ctypes.byref(ca), int(bool(anti)),
+                                                    rows.data_ptr() if a.n else None, ctypes.byref(n), self._stream())
+        _lib.check(rc)
+        if a.n:                         # (an empty query returns before the index is prepared)
+            index._note_rows_prepared()
+        return rows[: int(n.value)]
 
     # ------------------------------------------------ genomes longer than 2^32
     def chrom_spans(self, a: DeviceSide, b: DeviceSide, n_chrom: int):

@@ -216,9 +216,10 @@ class PinnedTable:
 
 
 def pin(table, index: bool = False) -> PinnedTable:
-    """See :class:`PinnedTable`.  ``index=True``: INNER joins against this table go through a table index in HBM,
-    built on first use (``giql_hip_index_create_dev``: the table's span pass and global sort passes are then not
-    repeated per query) -- the counterpart of ``CREATE INDEX ... (chrom, start, "end")``."""
+    """See :class:`PinnedTable`.  ``index=True``: INNER, SEMI, ANTI and count_overlaps joins against this table go
+    through a table index in HBM, built on first use (``giql_hip_index_create_dev``: the table's span pass and global
+    sort passes are then not repeated per query; SEMI / ANTI / count_overlaps with the table on the RIGHT sort
+    neither side) -- the counterpart of ``CREATE INDEX ... (chrom, start, "end")``."""
     return PinnedTable(table, index=index)
 
 
@@ -962,6 +963,12 @@ def _finish_count(plan, lt, rt, counts, n_chrom, eng, ia, return_indices, a_dev=
 
 
 _PINNED_MIN_BYTES = 64 << 20
+# plan kinds execute() answers from a pinned right table's index without sorting either side, and the index forms it
+# does so for.  Both forms are on because both measured faster than the ordinary operators for all three kinds
+# (tools/index_rows_timing.py, profiles/index_rows_timing.json.log: 1M x 10M, 2.1-2.3x fixed-length, 1.35-1.9x general;
+# DESIGN.md "Row operators against an index"); a form that loses is switched off here and falls to the ordinary path.
+_INDEXED_ROW_KINDS = ("COUNT", "SEMI", "ANTI")
+_INDEXED_ROW_FORMS = {"fixed_length": True, "general": True}
 
 
 def _to_host(t) -> np.ndarray:
@@ -1184,6 +1191,47 @@ def _chrom_lookup(index_values, query_values) -> np.ndarray:
                        count=len(query_values))
 
 
+def _pinned_index(pin_, it, iside: PlanSide, eng: HipEngine):
+    """``(DeviceIndex | None, dictionary)`` of a table pinned with ``index=True``: built on first use, ONE per
+    (device, interval columns, encoding) -- the INNER join and the per-row operators share it.  ``None``: the
+    table does not take the indexed form (remembered: it is not tried again)."""
+    from . import _lib
+
+    key = (str(eng.device), iside.chrom_col, iside.start_col, iside.end_col, iside.encoding)
+    if key not in pin_._indexes:
+        codes, dictionary = _chrom_values(_column(it, iside.chrom_col))
+        try:
+            dev = DeviceSide.from_numpy(codes, _int32_column(_column(it, iside.start_col), iside.start_col),
+                                        _int32_column(_column(it, iside.end_col), iside.end_col), iside.encoding,
+                                        device=eng.device)
+            pin_._indexes[key] = (eng.index_create(dev, len(dictionary)), dictionary)
+            del dev            # (the index holds its own arrays: the columns' device copy is not kept)
+        except _lib.GiqlHipError as exc:
+            if exc.code != _lib.GIQL_ERR_STATE:
+                raise
+            pin_._indexes[key] = (None, dictionary)    # this table does not take the indexed form
+    return pin_._indexes[key]
+
+
+def _index_query_side(qt, qside: PlanSide, dictionary, eng: HipEngine, own: bool = False):
+    """A query table on the device with its chrom ids in an index's dictionary (the index speaks its OWN
+    dictionary: it outlives the pairing of one query; chromosomes it lacks all get the id ``len(dictionary)`` and
+    match nothing).  ``own=True`` also returns the same rows with ids from the query table's own dictionary and
+    that dictionary's size -- what a GROUP BY over the query rows needs: the looked-up ids merge every chromosome
+    the index lacks into one."""
+    qcodes, qvalues = _chrom_values(_column(qt, qside.chrom_col))
+    lut = _chrom_lookup(dictionary, qvalues)
+    q = DeviceSide.from_numpy(lut[qcodes] if len(qvalues) else qcodes,
+                              _int32_column(_column(qt, qside.start_col), qside.start_col),
+                              _int32_column(_column(qt, qside.end_col), qside.end_col), qside.encoding, device=eng.device)
+    if not own:
+        return q
+    import torch
+
+    own_ids = torch.from_numpy(np.ascontiguousarray(qcodes, dtype=np.int32)).to(eng.device)
+    return q, DeviceSide(own_ids, q.start, q.end, q.start_off, q.end_off), qcodes, len(qvalues)
+
+
 def _indexed_inner(plan: JoinPlan, lt, rt, pins, eng: HipEngine):
     """INNER join through a pinned table's index, or None when no side offers one / the tables do not take the
     indexed form (the ordinary join follows).  The index speaks its OWN chromosome dictionary (it outlives the
@@ -1196,27 +1244,10 @@ def _indexed_inner(plan: JoinPlan, lt, rt, pins, eng: HipEngine):
             continue
         it, iside = (rt, plan.right) if which == "r" else (lt, plan.left)
         qt, qside = (lt, plan.left) if which == "r" else (rt, plan.right)
-        key = (str(eng.device), iside.chrom_col, iside.start_col, iside.end_col, iside.encoding)
-        if key not in pin_._indexes:
-            codes, dictionary = _chrom_values(_column(it, iside.chrom_col))
-            try:
-                dev = DeviceSide.from_numpy(codes, _int32_column(_column(it, iside.start_col), iside.start_col),
-                                            _int32_column(_column(it, iside.end_col), iside.end_col), iside.encoding,
-                                            device=eng.device)
-                pin_._indexes[key] = (eng.index_create(dev, len(dictionary)), dictionary)
-                del dev            # (the index holds its own arrays: the columns' device copy is not kept)
-            except _lib.GiqlHipError as exc:
-                if exc.code != _lib.GIQL_ERR_STATE:
-                    raise
-                pin_._indexes[key] = (None, dictionary)    # this table does not take the indexed form
-        index, dictionary = pin_._indexes[key]
+        index, dictionary = _pinned_index(pin_, it, iside, eng)
         if index is None:
             continue
-        qcodes, qvalues = _chrom_values(_column(qt, qside.chrom_col))
-        lut = _chrom_lookup(dictionary, qvalues)
-        q = DeviceSide.from_numpy(lut[qcodes] if len(qvalues) else qcodes,
-                                  _int32_column(_column(qt, qside.start_col), qside.start_col),
-                                  _int32_column(_column(qt, qside.end_col), qside.end_col), qside.encoding, device=eng.device)
+        q = _index_query_side(qt, qside, dictionary, eng)
         try:
             rq, ri = eng.inner_join_indexed(q, index)
         except _lib.GiqlHipError as exc:
@@ -1225,6 +1256,29 @@ def _indexed_inner(plan: JoinPlan, lt, rt, pins, eng: HipEngine):
             continue               # e.g. irregular query rows: the ordinary join answers them
         return (rq, ri) if which == "r" else (ri, rq)
     return None
+
+
+def _indexed_rows(plan: JoinPlan, lt, rt, pin_, eng: HipEngine):
+    """COUNT / SEMI / ANTI of the left table over the RIGHT table's index (the table pinned with ``index=True``), or
+    None when the table does not take the indexed form or the left table holds irregular rows (the ordinary
+    operator follows).  The right table's columns are not uploaded.  COUNT: ``(counts, left side, left ids,
+    n_chrom)`` -- the per-left-row counts and the left side under its own dictionary, for ``_finish_count``; SEMI /
+    ANTI: the ascending left row ids."""
+    from . import _lib
+
+    index, dictionary = _pinned_index(pin_, rt, plan.right, eng)
+    if index is None or not _INDEXED_ROW_FORMS["general" if index.general else "fixed_length"]:
+        return None
+    try:
+        if plan.kind == "COUNT":
+            q, a_own, ia, n_chrom = _index_query_side(lt, plan.left, dictionary, eng, own=True)
+            return eng.count_overlaps_indexed(q, index), a_own, ia, n_chrom
+        q = _index_query_side(lt, plan.left, dictionary, eng)
+        return eng.semi_anti_indexed(q, index, plan.kind == "ANTI")
+    except _lib.GiqlHipError as exc:
+        if exc.code != _lib.GIQL_ERR_STATE:
+            raise
+        return None                # irregular left rows: the ordinary operator answers them
 
 
 def _join_piece(plan: JoinPlan, lt, rt, ia: np.ndarray, ib: np.ndarray, n_chrom: int, eng: HipEngine,
@@ -1520,6 +1574,18 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
             if return_indices:
                 return ra.cpu().numpy(), rb.cpu().numpy()
             return _finish_outer(_project(plan, lt, rt, {"l": ra, "r": rb}, {}, eng, device_projection), plan)
+    if (plan.kind in _INDEXED_ROW_KINDS and plan.predicate == "intersects" and not plan.residuals
+            and not (devices and len(devices) > 1) and pins["r"] is not None and pins["r"].index):
+        # the per-row operators read the RIGHT table's index (a pinned left table is of no use to them): neither
+        # side is sorted, the pinned table's columns are not uploaded
+        got = _indexed_rows(plan, lt, rt, pins["r"], eng)
+        if got is not None and plan.kind == "COUNT":
+            counts, a_own, ia, n_chrom = got
+            return _finish_count(plan, lt, rt, counts, n_chrom, eng, ia, return_indices, a_dev=a_own)
+        if got is not None:
+            if return_indices:
+                return got.cpu().numpy()
+            return _finish_outer(_project(plan, lt, rt, {"l": got}, {}, eng, device_projection), plan)
     ia, ib, dictionary = encode_chroms(_column(lt, plan.left.chrom_col), _column(rt, plan.right.chrom_col))
     n_chrom = len(dictionary)
     dev_sides: dict = {}

@@ -578,6 +578,38 @@ int giql_hip_inner_join_indexed_dev(giql_hip_ctx* ctx, const giql_hip_index* idx
                                     const giql_side* a, int32_t* row_a,
                                     int32_t* row_idx, int64_t capacity,
                                     void* stream, int64_t* n_pairs);
+/* The per-row operators against an indexed table: count_overlaps (bedtools -c),
+ * SEMI (-u) and ANTI (-v) of `a` over the index, with the results of
+ * giql_hip_count_dev / giql_hip_semi_anti_dev on the same tables.  Neither side
+ * is sorted per call: one thread per row of `a`, in input order, ranks the row's
+ * start and end among the index's sorted keys -- through a directory of bucket
+ * boundaries and a short search inside the bucket -- and writes at the row's own
+ * index; SEMI / ANTI then compact their flags into ascending row ids.
+ *
+ * What they read beyond the index's sorted start keys -- the directory and, for a
+ * table of variable length, its end keys alone, sorted, with a directory of their
+ * own (4 more bytes per row) -- is built ONCE per index by
+ * giql_hip_index_prepare_rows_dev, never at creation: giql_hip_index_info reports
+ * the larger size afterwards.  The call is idempotent, and the two operators make
+ * it themselves when it has not run; so the FIRST row-operator call on an index
+ * (or the prepare call) must not run concurrently with any other call on that
+ * index -- the single-owner rule of a context, once, for the index.  Later calls
+ * only read the index.
+ *
+ * `a`'s chrom ids speak the INDEXED table's dictionary; ids >= its n_chrom match
+ * nothing (count 0, kept by ANTI, dropped by SEMI).  a->n == 0 is GIQL_OK with
+ * nothing written; an index on another device is GIQL_ERR_INVALID.  GIQL_ERR_STATE
+ * when `a` holds an irregular row (canonical end <= start) on an indexed
+ * chromosome: use the ordinary operator (the outputs are then unspecified, the
+ * context stays usable).  Query rows may be of any length: the 32768-position cap
+ * of giql_hip_inner_join_indexed_dev belongs to the bucket stage, which these
+ * calls do not use.  counts_out: [a->n] int64; rows_out: room for a->n int32. */
+int giql_hip_index_prepare_rows_dev(giql_hip_ctx* ctx, giql_hip_index* idx, void* stream);
+int giql_hip_count_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const giql_side* a,
+                               int64_t* counts_out, void* stream);
+int giql_hip_semi_anti_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx,
+                                   const giql_side* a, int anti, int32_t* rows_out,
+                                   int64_t* n_out, void* stream);
 
 /* What this device reads / writes / copies per second, by access shape (round 4:
  * the measured ceiling the kernels are held against; SURVEY.md section 8d "verify
