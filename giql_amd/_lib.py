@@ -44,6 +44,7 @@ SYMBOLS = [
     "giql_hip_contain_plan_dev", "giql_hip_contain_fill_dev",
     "giql_hip_window_plan_dev", "giql_hip_distance_dev",
     "giql_hip_index_prepare_rows_dev", "giql_hip_count_indexed_dev", "giql_hip_semi_anti_indexed_dev",
+    "giql_hip_index_prepare_nearest_dev", "giql_hip_nearest_indexed_dev",
 ]
 
 
@@ -170,6 +171,8 @@ def load() -> ctypes.CDLL:
     L.giql_hip_index_prepare_rows_dev.argtypes = [vp, vp, vp]
     L.giql_hip_count_indexed_dev.argtypes = [vp, vp, P(CSide), vp, vp]
     L.giql_hip_semi_anti_indexed_dev.argtypes = [vp, vp, P(CSide), ctypes.c_int, vp, P(i64), vp]
+    L.giql_hip_index_prepare_nearest_dev.argtypes = [vp, vp, vp]
+    L.giql_hip_nearest_indexed_dev.argtypes = [vp, vp, P(CSide), ctypes.c_int, i64, vp, vp, vp]
     L.giql_hip_nearest32_dev.argtypes = [vp, P(CSide), P(CSide), i32, ctypes.c_int, i64, vp, vp]
     L.giql_hip_nearest_k_dev.argtypes = [vp, P(CSide), P(CSide), i32, i32, ctypes.c_int, i64, vp, vp, vp]
     L.giql_hip_chrom_spans_dev.argtypes = [vp, P(CSide), P(CSide), i32, vp, vp]

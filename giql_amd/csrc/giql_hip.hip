@@ -37,6 +37,7 @@
 #include "scan.hip.h"
 #include "probe_kernels.hip.h"
 #include "index_rows_kernels.hip.h"
+#include "index_nearest_kernels.hip.h"
 
 using namespace giql;
 
@@ -2388,6 +2389,12 @@ struct giql_hip_index {
   u32* bnd_key = nullptr;     // [2^(32 - wbits) + 1] directory over key: first row with key >= v << wbits
   u32* end_sorted = nullptr;  // general form: [n] the end keys alone, sorted ...
   u32* bnd_end = nullptr;     // ... and their directory
+  // what NEAREST reads (giql_hip_index_prepare_nearest_dev: on its first call, never at creation) beside bnd_key,
+  // which either preparation builds and the other finds here
+  int nearest_state = 0;      // 0: not prepared; 1: ready; -1: the table does not take the NEAREST form (remembered)
+  u32* chrom_lo = nullptr;    // [n_chrom + 1] rank of first[c] among the keys
+  u32* nr_rid = nullptr;      // general form: [n] the row ids in (start, end) order ...
+  u32* nr_pmax = nullptr;     // ... and the prefix max of the end keys in that order
 };
 
 int giql_hip_index_destroy(giql_hip_index* idx) {
@@ -2400,6 +2407,9 @@ int giql_hip_index_destroy(giql_hip_index* idx) {
   if (idx->bnd_key) (void)hipFree(idx->bnd_key);
   if (idx->end_sorted) (void)hipFree(idx->end_sorted);
   if (idx->bnd_end) (void)hipFree(idx->bnd_end);
+  if (idx->chrom_lo) (void)hipFree(idx->chrom_lo);
+  if (idx->nr_rid) (void)hipFree(idx->nr_rid);
+  if (idx->nr_pmax) (void)hipFree(idx->nr_pmax);
   delete idx;
   return GIQL_OK;
 }
@@ -2635,29 +2645,48 @@ int giql_hip_inner_join_indexed_dev(giql_hip_ctx* ctx, const giql_hip_index* idx
 // Built once per index, on the first row-operator call (or by giql_hip_index_prepare_rows_dev), into buffers of the
 // index's own; key / end / rid are only read.  The caller has run begin_call; the arena is claimed here and free
 // again on return.
+// bytes of building a directory: every cell written once, behind a search of ~log2(rows per top digit) keys
+static int64_t index_directory_bytes(const giql_hip_index* idx) {
+  return (int64_t)((size_t)bs_n_buckets((u32)idx->wbits) + 1) * (4 + 4 * 24);
+}
+
+// The directory over the index's start keys, which the row operators and NEAREST both read: built by whichever
+// preparation runs first (stream-ordered: later kernels on `st` see it), found there by the other.
+static int index_ensure_key_directory(giql_hip_ctx* ctx, giql_hip_index* idx, hipStream_t st) {
+  if (idx->bnd_key) return GIQL_OK;
+  const size_t n_cells = (size_t)bs_n_buckets((u32)idx->wbits) + 1;
+  u32* bnd = nullptr;
+  HIP_TRY(hipMalloc((void**)&bnd, n_cells * sizeof(u32)));
+  {
+    Phase ph(ctx, st, GIQL_PH_AUX);
+    ctx->stats.phase_bytes[GIQL_PH_AUX] += index_directory_bytes(idx);
+    hipLaunchKernelGGL(k_bucket_bounds, dim3(cdiv(n_cells, 256)), dim3(256), 0, st, idx->key, idx->n,
+                       idx->small + 3 * OS_BINS, bnd, (u32)idx->wbits);
+    const int rc = post_launch("start directory (index)");
+    if (rc != GIQL_OK) {
+      (void)hipFree(bnd);
+      return rc;
+    }
+  }
+  idx->bnd_key = bnd;
+  idx->bytes += n_cells * sizeof(u32);
+  return GIQL_OK;
+}
+
 static int index_prepare_rows_core(giql_hip_ctx* ctx, giql_hip_index* idx, hipStream_t st) {
   const size_t n = idx->n;
   const u32 wbits = (u32)idx->wbits;
   const size_t n_cells = (size_t)bs_n_buckets(wbits) + 1;
   struct Built {  // released on every early way out
-    u32 *bnd_key = nullptr, *end_sorted = nullptr, *bnd_end = nullptr;
+    u32 *end_sorted = nullptr, *bnd_end = nullptr;
     ~Built() {
-      if (bnd_key) (void)hipFree(bnd_key);
       if (end_sorted) (void)hipFree(end_sorted);
       if (bnd_end) (void)hipFree(bnd_end);
     }
   } w;
-  size_t added = n_cells * sizeof(u32);
-  HIP_TRY(hipMalloc((void**)&w.bnd_key, n_cells * sizeof(u32)));
-  // a directory: every cell written once, behind a search of ~log2(rows per top digit) keys
-  const int64_t dir_bytes = (int64_t)n_cells * (4 + 4 * 24);
-  {
-    Phase ph(ctx, st, GIQL_PH_AUX);
-    ctx->stats.phase_bytes[GIQL_PH_AUX] += dir_bytes;
-    hipLaunchKernelGGL(k_bucket_bounds, dim3(cdiv(n_cells, 256)), dim3(256), 0, st, idx->key, (u32)n,
-                       idx->small + 3 * OS_BINS, w.bnd_key, wbits);
-    GIQL_TRY(post_launch("start directory (index)"));
-  }
+  size_t added = 0;
+  GIQL_TRY(index_ensure_key_directory(ctx, idx, st));
+  const int64_t dir_bytes = index_directory_bytes(idx);
   if (idx->general) {
     HIP_TRY(hipMalloc((void**)&w.end_sorted, n * sizeof(u32)));
     HIP_TRY(hipMalloc((void**)&w.bnd_end, n_cells * sizeof(u32)));
@@ -2707,8 +2736,8 @@ static int index_prepare_rows_core(giql_hip_ctx* ctx, giql_hip_index* idx, hipSt
   } else {
     HIP_TRY(hipStreamSynchronize(st));
   }
-  idx->bnd_key = w.bnd_key, idx->end_sorted = w.end_sorted, idx->bnd_end = w.bnd_end;
-  w.bnd_key = w.end_sorted = w.bnd_end = nullptr;
+  idx->end_sorted = w.end_sorted, idx->bnd_end = w.bnd_end;
+  w.end_sorted = w.bnd_end = nullptr;
   idx->bytes += added;
   idx->rows_ready = true;
   return GIQL_OK;
@@ -2843,6 +2872,142 @@ int giql_hip_semi_anti_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const
   *n_out = (int64_t)ctx->h_meta->n_out;
   ctx->stats.n_out = *n_out;
   ctx->stats.phase_bytes[GIQL_PH_SCAN] += (int64_t)8 * (int64_t)na + (int64_t)4 * *n_out;
+  return GIQL_OK;
+}
+
+// ------------------------------------------------------ NEAREST against an index
+// What NEAREST (k = 1) reads of an index beyond its sorted start keys (index_nearest_kernels.hip.h): the directory
+// over them (shared with the row operators), chrom_lo[] and, in the general form, a (start, end)-ordered VIEW in
+// arrays of its own -- the row ids and the prefix max of the end keys in that order, 8 bytes per row.  The index's
+// key / end / rid are only read (the indexed INNER join of another context may be reading them): the short runs of
+// equal start are ordered by end on COPIES (k_fix_start_ties), the end copy lives in the arena and is dropped.  A run
+// longer than NEAREST_TIE_MAX (a pile-up table) declines: the index remembers it, keeps no NEAREST array and every
+// NEAREST call on it returns GIQL_ERR_STATE; the other indexed operators are unaffected.  The caller has run
+// begin_call; the arena is claimed here and free again on return.
+static int index_nearest_declined() {
+  return set_err(GIQL_ERR_STATE, "the indexed table holds a run of more than %u rows on one start: it does not take the "
+                 "NEAREST form of an index; use the ordinary operator", NEAREST_TIE_MAX);
+}
+
+static int index_prepare_nearest(giql_hip_ctx* ctx, giql_hip_index* idx, hipStream_t st) {
+  if (idx->nearest_state > 0) return GIQL_OK;
+  if (idx->nearest_state < 0) return index_nearest_declined();
+  const size_t n = idx->n;
+  struct Built {  // released on every early way out
+    u32 *chrom_lo = nullptr, *nr_rid = nullptr, *nr_pmax = nullptr;
+    ~Built() {
+      if (chrom_lo) (void)hipFree(chrom_lo);
+      if (nr_rid) (void)hipFree(nr_rid);
+      if (nr_pmax) (void)hipFree(nr_pmax);
+    }
+  } w;
+  size_t added = 0;
+  if (idx->general) {
+    u32 *ends = nullptr, *bmax = nullptr;
+    auto carve = [&](char* base) {
+      Carver c{base};
+      ends = c.take<u32>(n);
+      bmax = c.take<u32>(cdiv(n, PM_TILE) + 1);
+      return c.off;
+    };
+    GIQL_TRY(claim_arena(ctx, st, carve));
+    HIP_TRY(hipMalloc((void**)&w.nr_rid, n * sizeof(u32)));
+    HIP_TRY(hipMalloc((void**)&w.nr_pmax, n * sizeof(u32)));
+    added += 2 * n * sizeof(u32);
+    HIP_TRY(hipMemsetAsync(ctx->d_meta, 0, sizeof(DevMeta), st));
+    {
+      Phase ph(ctx, st, GIQL_PH_AUX);  // the copies the tie fix works on (read once, written once), the run heads' pass
+      ctx->stats.phase_bytes[GIQL_PH_AUX] += (int64_t)(16 + 4) * n;
+      HIP_TRY(hipMemcpyAsync(ends, idx->end, n * sizeof(u32), hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(w.nr_rid, idx->rid, n * sizeof(u32), hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL(k_fix_start_ties, dim3(cdiv(n, 256)), dim3(256), 0, st, idx->key, ends, w.nr_rid, (u32)n,
+                         ctx->d_meta);
+      GIQL_TRY(post_launch("start ties (index)"));
+    }
+    ctx->stats.phase_bytes[GIQL_PH_AUX] += (int64_t)12 * n;  // the prefix max: read twice, written once
+    GIQL_TRY(run_pmax(ctx, st, ends, (u32)n, w.nr_pmax, bmax));
+    GIQL_TRY(read_meta(ctx, st));
+    if (ctx->h_meta->aux0 != 0) {
+      idx->nearest_state = -1;  // (w's arrays are released: the index keeps nothing of the attempt)
+      return index_nearest_declined();
+    }
+  }
+  GIQL_TRY(index_ensure_key_directory(ctx, idx, st));
+  HIP_TRY(hipMalloc((void**)&w.chrom_lo, ((size_t)idx->n_chrom + 1) * sizeof(u32)));
+  added += ((size_t)idx->n_chrom + 1) * sizeof(u32);
+  {
+    Phase ph(ctx, st, GIQL_PH_AUX);
+    hipLaunchKernelGGL(k_chrom_bounds, dim3(cdiv((u64)idx->n_chrom + 1, 256)), dim3(256), 0, st, idx->small + 1024,
+                       idx->n_chrom, idx->key, (u32)n, w.chrom_lo);
+    GIQL_TRY(post_launch("chromosome ranks (index)"));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  idx->chrom_lo = w.chrom_lo, idx->nr_rid = w.nr_rid, idx->nr_pmax = w.nr_pmax;
+  w.chrom_lo = w.nr_rid = w.nr_pmax = nullptr;
+  idx->bytes += added;
+  idx->nearest_state = 1;
+  return GIQL_OK;
+}
+
+int giql_hip_index_prepare_nearest_dev(giql_hip_ctx* ctx, giql_hip_index* idx, void* stream) {
+  GIQL_TRY(check_index_call(ctx, idx));
+  if (idx->nearest_state > 0) return GIQL_OK;
+  if (idx->nearest_state < 0) return index_nearest_declined();
+  GIQL_TRY(begin_call(ctx));
+  ctx->plan.planned = false;
+  ctx->stats.n_b = idx->n;
+  GIQL_TRY(index_prepare_nearest(ctx, idx, (hipStream_t)stream));
+  collect_spans(ctx);
+  ctx->stats.span = (int64_t)idx->span;
+  return GIQL_OK;
+}
+
+// NEAREST k = 1 of `a` over an indexed table with the results of giql_hip_nearest_dev on the same two tables:
+// neither side is sorted, nothing is scattered (k_index_nearest).
+int giql_hip_nearest_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const giql_side* a, int is_signed,
+                                 int64_t max_distance, int32_t* idx_b_out, int64_t* dist_out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!ctx || !idx) return set_err(GIQL_ERR_INVALID, "ctx/index is NULL");
+  if (!idx_b_out || !dist_out) return set_err(GIQL_ERR_INVALID, "idx_b_out/dist_out is NULL");
+  GIQL_TRY(check_index_call(ctx, idx));
+  GIQL_TRY(check_side(a, "a"));
+  if ((size_t)a->n > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
+  GIQL_TRY(begin_call(ctx));
+  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
+  ctx->stats.n_a = a->n;
+  ctx->stats.n_b = idx->n;
+  if (a->n == 0) return GIQL_OK;
+  GIQL_TRY(index_prepare_nearest(ctx, idx, st));
+  const size_t na = (size_t)a->n;
+  GIQL_TRY(claim_arena(ctx, st, [](char*) { return (size_t)0; }));
+  HIP_TRY(hipMemsetAsync(ctx->d_meta, 0, sizeof(DevMeta), st));
+  IndexNearestView v;
+  v.rows = rows_view_of(idx);
+  v.rows.end_key = v.rows.bnd_end = nullptr;  // (the row operators' arrays: not read here, possibly not built)
+  v.chrom_lo = idx->chrom_lo;
+  v.rid = idx->rid;
+  v.nr_pmax = idx->nr_pmax;
+  v.nr_rid = idx->nr_rid;
+  {
+    Phase ph(ctx, st, GIQL_PH_COUNT);
+    // the searches of index_rows_bytes + the candidates' keys / prefix maxima (~4 loads) and the matched row id
+    ctx->stats.phase_bytes[GIQL_PH_COUNT] += index_rows_bytes(idx, na, 12) + (int64_t)na * 20;
+    if (idx->general)
+      hipLaunchKernelGGL(k_index_nearest<true>, dim3(cdiv(na, IR_NT)), dim3(IR_NT), 0, st, a->chrom, a->start, a->end,
+                         (u32)na, a->start_off, a->end_off, v, is_signed, (i64)max_distance, idx_b_out, (i64*)dist_out,
+                         &ctx->d_meta->aux1);
+    else
+      hipLaunchKernelGGL(k_index_nearest<false>, dim3(cdiv(na, IR_NT)), dim3(IR_NT), 0, st, a->chrom, a->start, a->end,
+                         (u32)na, a->start_off, a->end_off, v, is_signed, (i64)max_distance, idx_b_out, (i64*)dist_out,
+                         &ctx->d_meta->aux1);
+    GIQL_TRY(post_launch("nearest (index)"));
+  }
+  GIQL_TRY(read_meta(ctx, st));
+  collect_spans(ctx);
+  ctx->stats.span = (int64_t)idx->span;
+  ctx->stats.reserved = idx->general ? 0 : 1;
+  if (ctx->h_meta->aux1) return set_err(GIQL_ERR_INVALID, "NEAREST: a query row has end < start");
+  ctx->stats.n_out = a->n;
   return GIQL_OK;
 }
 

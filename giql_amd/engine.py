@@ -97,12 +97,14 @@ class DeviceSide:
 class DeviceIndex:
     """A table index in HBM (``giql_hip_index``): what the reference's users get from ``CREATE INDEX ... (chrom,
     start, "end")`` (``docs/transpilation/performance.rst:111-130``).  Built by :meth:`HipEngine.index_create`,
-    used by :meth:`HipEngine.inner_join_indexed`, :meth:`HipEngine.count_overlaps_indexed` and
-    :meth:`HipEngine.semi_anti_indexed`; released by :meth:`close` / garbage collection."""
+    used by :meth:`HipEngine.inner_join_indexed`, :meth:`HipEngine.count_overlaps_indexed`,
+    :meth:`HipEngine.semi_anti_indexed` and :meth:`HipEngine.nearest_indexed`; released by :meth:`close` / garbage
+    collection."""
 
     def __init__(self, engine: "HipEngine", handle, n_chrom: int):
         self.engine, self._h, self.n_chrom, self.last_pairs = engine, handle, n_chrom, 0
         self._rows_prepared = False     # the row operators' arrays exist and ``nbytes`` counts them
+        self._nearest_prepared = False  # ... and NEAREST's
         self._refresh_info()
 
     def _refresh_info(self) -> None:
@@ -123,6 +125,23 @@ class DeviceIndex:
         eng = self.engine
         _lib.check(eng._L.giql_hip_index_prepare_rows_dev(eng._h, self._h, eng._stream()))
         self._rows_prepared = True
+        self._refresh_info()
+
+    def _note_nearest_prepared(self) -> None:
+        if not self._nearest_prepared:  # (a NEAREST call that succeeded has prepared the index on the way)
+            self._nearest_prepared = True
+            self._refresh_info()
+
+    def prepare_nearest(self) -> None:
+        """Build what :meth:`HipEngine.nearest_indexed` reads of the index (``giql_hip_index_prepare_nearest_dev``:
+        the directory of bucket boundaries it shares with the row operators, a rank per chromosome; for a table of
+        variable length the row ids and the prefix max of the ends in (start, end) order too, 8 B per row).  Once
+        per index -- a second call does nothing -- and done by the first ``nearest_indexed`` call otherwise;
+        ``nbytes`` is refreshed.  ``GIQL_ERR_STATE`` (now and on every later NEAREST call) when a table of variable
+        length holds a long run of rows on one start: the ordinary operator answers such a table."""
+        eng = self.engine
+        _lib.check(eng._L.giql_hip_index_prepare_nearest_dev(eng._h, self._h, eng._stream()))
+        self._nearest_prepared = True
         self._refresh_info()
 
     def close(self) -> None:
@@ -413,6 +432,25 @@ class HipEngine:
         if a.n:                         # (an empty query returns before the index is prepared)
             index._note_rows_prepared()
         return rows[: int(n.value)]
+
+    def nearest_indexed(self, a: DeviceSide, index: "DeviceIndex", signed: bool = False, max_distance=None):
+        """NEAREST k=1 of ``a`` over the indexed table: ``(idx_b int32, distance int64)`` per row of ``a``, in
+        ``a``'s order; idx_b = -1 = none (``giql_hip_nearest_indexed_dev``: what :meth:`nearest` returns, without
+        sorting either side).  ``a.chrom`` speaks the indexed table's dictionary.  ``GIQL_ERR_INVALID`` for a row
+        with end < start; ``GIQL_ERR_STATE`` when the index does not take the NEAREST form
+        (:meth:`DeviceIndex.prepare_nearest`)."""
+        torch = _torch()
+        self._check_indexed(a, index)
+        # (the library writes every slot; one spare element keeps the pointers non-NULL for an empty query)
+        idx = torch.empty(max(a.n, 1), dtype=torch.int32, device=self.device)
+        dist = torch.empty(max(a.n, 1), dtype=torch.int64, device=self.device)
+        md = -1 if max_distance is None else int(max_distance)
+        ca = a.c_struct()
+        _lib.check(self._L.giql_hip_nearest_indexed_dev(self._h, index._h, ctypes.byref(ca), int(bool(signed)), md,
+                                                        idx.data_ptr(), dist.data_ptr(), self._stream()))
+        if a.n:                         # (an empty query returns before the index is prepared)
+            index._note_nearest_prepared()
+        return idx[: a.n], dist[: a.n]
 
     # ------------------------------------------------ genomes longer than 2^32
     def chrom_spans(self, a: DeviceSide, b: DeviceSide, n_chrom: int):

@@ -219,7 +219,8 @@ def pin(table, index: bool = False) -> PinnedTable:
     """See :class:`PinnedTable`.  ``index=True``: INNER, SEMI, ANTI and count_overlaps joins against this table go
     through a table index in HBM, built on first use (``giql_hip_index_create_dev``: the table's span pass and global
     sort passes are then not repeated per query; SEMI / ANTI / count_overlaps with the table on the RIGHT sort
-    neither side) -- the counterpart of ``CREATE INDEX ... (chrom, start, "end")``."""
+    neither side) -- the counterpart of ``CREATE INDEX ... (chrom, start, "end")``.  NEAREST (k = 1, unstranded) with
+    the table as its target reads the same index for the index forms ``_INDEXED_NEAREST_FORMS`` switches on."""
     return PinnedTable(table, index=index)
 
 
@@ -969,6 +970,12 @@ _PINNED_MIN_BYTES = 64 << 20
 # DESIGN.md "Row operators against an index"); a form that loses is switched off here and falls to the ordinary path.
 _INDEXED_ROW_KINDS = ("COUNT", "SEMI", "ANTI")
 _INDEXED_ROW_FORMS = {"fixed_length": True, "general": True}
+# NEAREST (k = 1, unstranded) against a pinned right table's index, per index form: a form is on only where the
+# indexed call measured faster than the ordinary one at BOTH sizes of tools/index_nearest_timing.py (1M x 10M and
+# 10M x 10M) by more than the spread of its repetitions (profiles/index_nearest_timing.json.log; DESIGN.md "NEAREST
+# against an index").  Measured: 3.4x (fixed-length) and 2.1x (general) at 1M x 10M, but 0.91x and 0.51x at 10M x 10M,
+# so both forms are off.  A form that is off stays available through HipEngine.nearest_indexed.
+_INDEXED_NEAREST_FORMS = {"fixed_length": False, "general": False}
 
 
 def _to_host(t) -> np.ndarray:
@@ -1281,6 +1288,37 @@ def _indexed_rows(plan: JoinPlan, lt, rt, pin_, eng: HipEngine):
         return None                # irregular left rows: the ordinary operator answers them
 
 
+def _routes_indexed_nearest(plan: JoinPlan, pins: dict, devices) -> bool:
+    """Whether a plan is a candidate for ``_indexed_nearest``: NEAREST with k = 1, not stranded, on one device, its
+    TARGET (right) table pinned with ``index=True`` (a pinned left table is of no use to it)."""
+    return (plan.kind == "NEAREST" and plan.k == 1 and not plan.stranded and not plan.residuals
+            and not (devices and len(devices) > 1) and pins.get("r") is not None and bool(pins["r"].index))
+
+
+def _indexed_nearest(plan: JoinPlan, lt, rt, pin_, eng: HipEngine):
+    """NEAREST k = 1 of the left table over the RIGHT table's index (the table pinned with ``index=True``): the
+    ``(keep, ib_keep, distance)`` triple of ``_nearest_rows``, or None when the table does not take the indexed form,
+    its index form is switched off (``_INDEXED_NEAREST_FORMS``) or the index declines NEAREST (a long run of rows on
+    one start) -- the ordinary operator follows.  The right table's columns are not uploaded."""
+    from . import _lib
+
+    index, dictionary = _pinned_index(pin_, rt, plan.right, eng)
+    if index is None or not _INDEXED_NEAREST_FORMS["general" if index.general else "fixed_length"]:
+        return None
+    try:
+        index.prepare_nearest()    # (once per index; a declined index answers at once, before the left table is uploaded)
+        q = _index_query_side(lt, plan.left, dictionary, eng)
+        ib_dev, dist = eng.nearest_indexed(q, index, signed=plan.signed, max_distance=plan.max_distance)
+    except _lib.GiqlHipError as exc:
+        if exc.code != _lib.GIQL_ERR_STATE:
+            raise
+        return None
+    import torch
+
+    keep = torch.nonzero(ib_dev >= 0).flatten().to(torch.int32)
+    return keep, ib_dev[keep.long()].contiguous(), dist[keep.long()].cpu().numpy()
+
+
 def _join_piece(plan: JoinPlan, lt, rt, ia: np.ndarray, ib: np.ndarray, n_chrom: int, eng: HipEngine,
                 return_indices: bool, device_projection: bool, sides_out: dict | None = None):
     """The join of ``lt`` x ``rt`` (chrom ids ``ia`` / ``ib`` from one shared dictionary) on ONE engine,
@@ -1586,6 +1624,15 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
             if return_indices:
                 return got.cpu().numpy()
             return _finish_outer(_project(plan, lt, rt, {"l": got}, {}, eng, device_projection), plan)
+    if _routes_indexed_nearest(plan, pins, devices):
+        # NEAREST k = 1 reads the RIGHT table's index: neither side is sorted, the pinned table's columns are not uploaded
+        got = _indexed_nearest(plan, lt, rt, pins["r"], eng)
+        if got is not None:
+            keep, ib_keep, dn = got
+            if return_indices:
+                return keep.cpu().numpy(), ib_keep.cpu().numpy(), dn
+            return _finish_outer(_project(plan, lt, rt, {"l": keep, "r": ib_keep}, {"distance": dn}, eng,
+                                          device_projection), plan)
     ia, ib, dictionary = encode_chroms(_column(lt, plan.left.chrom_col), _column(rt, plan.right.chrom_col))
     n_chrom = len(dictionary)
     dev_sides: dict = {}

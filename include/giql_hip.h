@@ -610,6 +610,55 @@ int giql_hip_count_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const giq
 int giql_hip_semi_anti_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx,
                                    const giql_side* a, int anti, int32_t* rows_out,
                                    int64_t* n_out, void* stream);
+/* NEAREST (k = 1, unstranded) of `a` against an indexed table, with the results
+ * of giql_hip_nearest_dev on the same two tables (the reference's lateral
+ * NEAREST, src/giql/expanders/nearest.py:336-397, with the distance CASE of
+ * _distance.py:67-87): per row of `a` the row of the indexed table with the
+ * smallest (ABS(distance), start, end), idx_b_out[i] = its row id (-1: none) and
+ * dist_out[i] = the distance (0 with none; negative for an upstream target when
+ * is_signed).  max_distance >= 0 drops a result with ABS(distance) beyond it;
+ * negative: no limit.  Neither side is sorted per call: one thread per row of
+ * `a`, in input order, ranks the row's end (and, for a table of fixed length,
+ * its start) among the index's sorted keys through the directory of bucket
+ * boundaries and writes at the row's own index.  Distances come from the row's
+ * unclamped 64-bit coordinates: a row below 0, beyond the indexed range or
+ * reaching over either end still gets its nearest target on the chromosome.
+ *
+ * What it reads beyond the index's sorted start keys -- the directory (shared
+ * with the row operators), a rank per chromosome and, for a table of variable
+ * length, a (start, end)-ordered view: row ids and the prefix max of the ends,
+ * 8 more bytes per row -- is built ONCE per index by
+ * giql_hip_index_prepare_nearest_dev, never at creation; giql_hip_index_info
+ * reports the larger size afterwards.  The call is idempotent and
+ * giql_hip_nearest_indexed_dev makes it itself when it has not run, under the
+ * single-owner rule of giql_hip_index_prepare_rows_dev: the FIRST of these calls
+ * on an index must not run concurrently with any other call on it; later calls
+ * only read the index.  The index's own key / end / rid arrays are never
+ * reordered.
+ *
+ * `a`'s chrom ids speak the INDEXED table's dictionary; an id outside
+ * [0, its n_chrom) or a chromosome without an indexed row gives (-1, 0).
+ *   a->n == 0                          GIQL_OK, nothing written
+ *   ctx / idx / an output is NULL      GIQL_ERR_INVALID, before a device is touched
+ *                                      (the outputs also with a->n == 0)
+ *   the index is on another device     GIQL_ERR_INVALID
+ *   a row of `a` has end < start       GIQL_ERR_INVALID (canonical coordinates;
+ *                                      a zero-length row is legal and answered)
+ *   the table holds a run of more than 32 rows on one start (variable length
+ *   only: the short-run tie fix of giql_hip_nearest_dev does not cover it)
+ *                                      GIQL_ERR_STATE from the prepare call and
+ *                                      from this and every later NEAREST call on
+ *                                      the index, which remembers it and keeps no
+ *                                      NEAREST array: use the ordinary operator.
+ *                                      The context stays usable; INNER / COUNT /
+ *                                      SEMI / ANTI on the index are unaffected.
+ * Several targets tied on (distance, start, end): any one of them may come back,
+ * as upstream.  idx_b_out: [a->n] int32; dist_out: [a->n] int64.  The context's
+ * stats report n_a, n_b and n_out = a->n; a plan held by the context is dropped. */
+int giql_hip_index_prepare_nearest_dev(giql_hip_ctx* ctx, giql_hip_index* idx, void* stream);
+int giql_hip_nearest_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const giql_side* a,
+                                 int is_signed, int64_t max_distance,
+                                 int32_t* idx_b_out, int64_t* dist_out, void* stream);
 
 /* What this device reads / writes / copies per second, by access shape (round 4:
  * the measured ceiling the kernels are held against; SURVEY.md section 8d "verify
