@@ -45,6 +45,7 @@ SYMBOLS = [
     "giql_hip_window_plan_dev", "giql_hip_distance_dev",
     "giql_hip_index_prepare_rows_dev", "giql_hip_count_indexed_dev", "giql_hip_semi_anti_indexed_dev",
     "giql_hip_index_prepare_nearest_dev", "giql_hip_nearest_indexed_dev",
+    "giql_hip_left_pad_dev",
 ]
 
 
@@ -189,6 +190,7 @@ def load() -> ctypes.CDLL:
     L.giql_hip_select_dev.argtypes = [vp, P(CPred), i32, vp, i64, vp, i64, i64, vp, vp, P(i64), vp]
     L.giql_hip_select_expr_dev.argtypes = [vp, P(CPred), i32, P(COperand), i32, vp, i64, vp, i64, i64, vp, vp, P(i64), vp]
     L.giql_hip_mark_dev.argtypes = [vp, vp, i64, vp, i64, vp]
+    L.giql_hip_left_pad_dev.argtypes = [vp, vp, vp, i64, i64, i64, vp, P(i64)]
     L.giql_hip_group_rows_dev.argtypes = [vp, P(CSide), i32, vp, vp, P(i64), vp]
     L.giql_hip_segment_sum_dev.argtypes = [vp, vp, vp, i64, vp, i64, vp]
     L.giql_hip_cluster_dev.argtypes = [vp, P(CSide), i32, i64, vp, vp]

@@ -25,6 +25,7 @@
 #include "aux_kernels.hip.h"
 #include "take_kernels.hip.h"
 #include "select_kernels.hip.h"
+#include "outer_kernels.hip.h"
 #include "cluster_kernels.hip.h"
 #include "disjoin_kernels.hip.h"
 #include "contain_kernels.hip.h"
@@ -4767,6 +4768,76 @@ int giql_hip_mark_dev(giql_hip_ctx* ctx, const int32_t* idx, int64_t n, uint8_t*
     GIQL_TRY(post_launch("mark"));
   }
   GIQL_TRY(read_meta(ctx, st));
+  collect_spans(ctx);
+  return GIQL_OK;
+}
+
+// --------------------------------------------------------- LEFT OUTER: the pad
+// Mark, count and fill over a flag byte and a bit per left row in the arena (outer_kernels.hip.h); one read-back
+// between the count and the fill yields the status and the number of unmatched rows.
+int giql_hip_left_pad_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, int64_t n_pairs,
+                          int64_t capacity, int64_t n_rows_a, void* stream, int64_t* n_total) {
+  if (!ctx || !n_total || n_pairs < 0 || capacity < n_pairs || n_rows_a < 0 || n_rows_a > 0x7FFFFFFFll ||
+      (capacity > 0 && !row_a))
+    return set_err(GIQL_ERR_INVALID, "bad arguments (0 <= n_pairs <= capacity, n_rows_a < 2^31)");
+  *n_total = n_pairs;
+  ctx->plan.planned = false;  // (the way out with nothing to do drops the plan too)
+  if (n_pairs == 0 && n_rows_a == 0) return GIQL_OK;
+  GIQL_TRY(begin_call(ctx));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n_words = ((size_t)n_rows_a + 63) / 64;
+  const u32 nb = cdiv((u64)n_rows_a, LP_BLOCK_ROWS);
+  u64 *bits = nullptr, *bsums = nullptr;
+  uint8_t* flags = nullptr;
+  GIQL_TRY(claim_arena(ctx, st, [&](char* base) {
+    Carver c{base};
+    flags = c.take<uint8_t>((size_t)n_rows_a + 1);
+    bits = c.take<u64>(n_words + 1);
+    bsums = c.take<u64>((size_t)nb + 1);
+    return c.off;
+  }));
+  HIP_TRY(hipMemsetAsync(ctx->d_meta, 0, sizeof(DevMeta), st));
+  if (n_rows_a) HIP_TRY(hipMemsetAsync(flags, 0, (size_t)n_rows_a, st));
+  if (n_pairs > 0) {
+    u32 grid = cdiv((u64)n_pairs, LP_NT * 8);
+    if (grid > GIQL_STREAM_GRID) grid = GIQL_STREAM_GRID;
+    Phase ph(ctx, st, GIQL_PH_AUX);
+    hipLaunchKernelGGL(k_left_mark, dim3(grid), dim3(LP_NT), 0, st, (const int*)row_a, (u64)n_pairs, (u32)n_rows_a,
+                       flags, ctx->d_meta);
+    GIQL_TRY(post_launch("left_mark"));
+  }
+  if (nb) {
+    {
+      Phase ph(ctx, st, GIQL_PH_COUNT);
+      hipLaunchKernelGGL(k_left_count, dim3(nb), dim3(LP_NT), 0, st, (const uint8_t*)flags, (u32)n_rows_a, bits, bsums);
+      GIQL_TRY(post_launch("left_count"));
+    }
+    Phase ph(ctx, st, GIQL_PH_SCAN);
+    hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, st, bsums, nb, (u64*)nullptr, &ctx->d_meta->n_out);
+    GIQL_TRY(post_launch("left_pad scan"));
+  }
+  const int rc = read_meta(ctx, st);
+  if (rc == GIQL_ERR_INVALID)
+    return set_err(GIQL_ERR_INVALID, "row_a holds an id outside [0, n_rows_a = %lld)", (long long)n_rows_a);
+  GIQL_TRY(rc);
+  const u64 n_pad = ctx->h_meta->n_out;
+  *n_total = n_pairs + (int64_t)n_pad;
+  ctx->stats.n_out = *n_total;
+  if (capacity < *n_total) {
+    collect_spans(ctx);
+    return set_err(GIQL_ERR_CAPACITY, "left_pad: %lld entries offered, %lld needed", (long long)capacity,
+                   (long long)*n_total);
+  }
+  if (n_pad) {
+    {
+      Phase ph(ctx, st, GIQL_PH_FILL);
+      hipLaunchKernelGGL(k_left_fill, dim3(nb), dim3(LP_NT), 0, st, (const u64*)bits, (u32)n_rows_a, (const u64*)bsums,
+                         (u64)n_pairs, row_a, row_b);
+      GIQL_TRY(post_launch("left_fill"));
+    }
+    // (the fill stays in flight, like giql_hip_inner_fill_dev's: the total is on the host already)
+    if (ctx->profiling) HIP_TRY(hipStreamSynchronize(st));
+  }
   collect_spans(ctx);
   return GIQL_OK;
 }

@@ -166,6 +166,10 @@ class InvertedRows(ValueError):
         self.sides = tuple(sides)
 
 
+#: left rows one block of the LEFT OUTER pad's count / fill kernels covers (csrc/outer_kernels.hip.h, LP_BLOCK_ROWS)
+LEFT_PAD_BLOCK_ROWS = 32768
+
+
 class HipEngine:
     """One context (device arena + bookkeeping) on one GPU.  Not thread-safe."""
 
@@ -287,7 +291,16 @@ class HipEngine:
 
     def inner_join(self, a: DeviceSide, b: DeviceSide, n_chrom: int, out=None):
         """All ``(row_a, row_b)`` with ``a INTERSECTS b``; two int32 device tensors."""
+        row_a, row_b, n = self._join_into_buffers(a, b, n_chrom, out=out)
+        return row_a[:n], row_b[:n]
+
+    def _join_into_buffers(self, a: DeviceSide, b: DeviceSide, n_chrom: int, out=None, extra_room: int = 0):
+        """The INNER join's pairs at the front of two int32 device buffers: ``(row_a, row_b, n_pairs)``.  The buffers
+        hold at least ``n_pairs + extra_room`` entries (what a caller appends behind the pairs: :meth:`left_join`),
+        and the join itself is never offered the extra room -- except after a ``GIQL_ERR_SPAN``, when the pairs of
+        the chromosome groups come back in tensors of exactly their length."""
         torch = _torch()
+        extra = int(extra_room)
         # A context that has joined before gets ONE call (giql_hip_inner_join_dev): buffers sized from its previous
         # result -- for large tables the pairs are then written by the sort's last stage itself, with no count /
         # scan / fill kernels and no read-back in between.  A result that does not fit comes back as
@@ -301,50 +314,54 @@ class HipEngine:
             guess = int(guess * (a.n / max(g_na, 1)) * (b.n / max(g_nb, 1))) + 1
         guess = min(guess, a.n * b.n)
         row_a = row_b = None
+        cap = 0
         if out is None and guess > 0 and a.n and b.n:
             cap = min(int(guess * 1.05) + 4096, a.n * b.n)
             try:
                 free = int(torch.cuda.mem_get_info(self.device)[0])
-                cap = min(cap, max(free // 24, 4096))     # two int32 arrays within a third of what is free
+                cap = min(cap, max(free // 24 - extra, 4096))     # two int32 arrays within a third of what is free
             except Exception:  # pragma: no cover
                 pass
             try:   # (a guess left over from a much larger join must not be what runs the device out of memory)
-                row_a = torch.empty(cap, dtype=torch.int32, device=self.device)
-                row_b = torch.empty(cap, dtype=torch.int32, device=self.device)
+                row_a = torch.empty(cap + extra, dtype=torch.int32, device=self.device)
+                row_b = torch.empty(cap + extra, dtype=torch.int32, device=self.device)
             except RuntimeError:
                 row_a = row_b = None
                 self._pairs_guess = 0
         if row_a is not None and row_b is not None:
             try:
-                n = self.inner_join_into(a, b, n_chrom, row_a, row_b)
+                # (the join sees `cap` entries only: pairs past the guess must not spend the caller's extra room)
+                n = self.inner_join_into(a, b, n_chrom, row_a[:cap], row_b[:cap])
                 self._pairs_guess, self._pairs_guess_rows = n, (a.n, b.n)
-                return row_a[:n], row_b[:n]
+                return row_a, row_b, n
             except _lib.GiqlHipError as exc:
                 if exc.code == _lib.GIQL_ERR_SPAN:
-                    return self._inner_by_groups(a, b, n_chrom)
+                    ra, rb = self._inner_by_groups(a, b, n_chrom)
+                    return ra, rb, int(ra.shape[0])
                 if exc.code != _lib.GIQL_ERR_CAPACITY:
                     raise
                 n = int(self.last_pairs)
                 del row_a, row_b
-                row_a = torch.empty(n, dtype=torch.int32, device=self.device)
-                row_b = torch.empty(n, dtype=torch.int32, device=self.device)
+                row_a = torch.empty(n + extra, dtype=torch.int32, device=self.device)
+                row_b = torch.empty(n + extra, dtype=torch.int32, device=self.device)
                 self.inner_fill(row_a, row_b)
                 self._pairs_guess, self._pairs_guess_rows = n, (a.n, b.n)
-                return row_a, row_b
+                return row_a, row_b, n
         try:
             n = self.inner_plan(a, b, n_chrom)
         except _lib.GiqlHipError as exc:
             if exc.code != _lib.GIQL_ERR_SPAN:
                 raise
-            return self._inner_by_groups(a, b, n_chrom)
+            ra, rb = self._inner_by_groups(a, b, n_chrom)
+            return ra, rb, int(ra.shape[0])
         self._pairs_guess, self._pairs_guess_rows = n, (a.n, b.n)
-        if out is not None and out[0].shape[0] >= n:
-            row_a, row_b = out[0][:n], out[1][:n]
+        if out is not None and min(int(out[0].shape[0]), int(out[1].shape[0])) >= n + extra:
+            row_a, row_b = out[0], out[1]
         else:
-            row_a = torch.empty(n, dtype=torch.int32, device=self.device)
-            row_b = torch.empty(n, dtype=torch.int32, device=self.device)
-        self.inner_fill(row_a, row_b)
-        return row_a, row_b
+            row_a = torch.empty(n + extra, dtype=torch.int32, device=self.device)
+            row_b = torch.empty(n + extra, dtype=torch.int32, device=self.device)
+        self.inner_fill(row_a[:n], row_b[:n])
+        return row_a, row_b, n
 
     # ------------------------------------------------------------- table index
     def index_create(self, side: DeviceSide, n_chrom: int) -> "DeviceIndex":
@@ -1224,6 +1241,50 @@ class HipEngine:
             _lib.check(self._L.giql_hip_mark_dev(self._h, idx.data_ptr(), n, flags.data_ptr(), int(n_rows),
                                                  self._stream()))
         return flags
+
+    # ------------------------------------------------------------- LEFT OUTER
+    def left_pad(self, row_a, row_b, n_pairs: int, n_rows_a: int) -> int:
+        """The unmatched-row pass of a LEFT OUTER join (``giql_hip_left_pad_dev``): behind the ``n_pairs`` pairs
+        held at the front of ``row_a`` / ``row_b`` (int32 device tensors with room to spare; ``row_b`` may be
+        ``None``), append ``(r, -1)`` for every ``r`` in ``[0, n_rows_a)`` that ``row_a[:n_pairs]`` does not hold,
+        ascending.  Returns the new length.  Too little room raises ``GiqlHipError`` with ``GIQL_ERR_CAPACITY``
+        and writes nothing; the length needed is then in :attr:`last_total`."""
+        torch = _torch()
+        cap = int(row_a.shape[0]) if row_b is None else min(int(row_a.shape[0]), int(row_b.shape[0]))
+        if not 0 <= int(n_pairs) <= cap:
+            raise ValueError(f"n_pairs = {n_pairs} outside [0, {cap}], the buffers' length")
+        total = ctypes.c_int64(0)
+        self.last_total = None
+        rc = self._L.giql_hip_left_pad_dev(
+            self._h, self._dev_ptr(row_a, "row_a", torch.int32), self._dev_ptr(row_b, "row_b", torch.int32),
+            int(n_pairs), cap, int(n_rows_a), self._stream(), ctypes.byref(total))
+        self.last_total = int(total.value)
+        _lib.check(rc)
+        return int(total.value)
+
+    def left_join(self, a: DeviceSide, b: DeviceSide, n_chrom: int):
+        """``a LEFT JOIN b ON a INTERSECTS b`` as row ids: the INNER join's pairs, then ``(r, -1)`` for every left
+        row without a pair (ascending).  The pair buffers are allocated with room for ``a.n`` more entries that the
+        join itself is never offered (:meth:`_join_into_buffers`), so the pad appends in place whatever the pair
+        count turns out to be; the result is two views of them."""
+        self._check_sides(a, b)
+        row_a, row_b, n = self._join_into_buffers(a, b, n_chrom, extra_room=a.n)
+        if min(int(row_a.shape[0]), int(row_b.shape[0])) < n + a.n:   # (joined group by group: exactly sized)
+            return self.left_pad_pairs(row_a[:n], row_b[:n], a.n)
+        total = self.left_pad(row_a, row_b, n, a.n)
+        return row_a[:total], row_b[:total]
+
+    def left_pad_pairs(self, ra, rb, n_rows_a: int):
+        """:meth:`left_pad` for pairs that arrive in tensors of their own length (a join with residuals, CONTAINS,
+        a within-distance join): they are copied once into buffers with room for ``n_rows_a`` more entries."""
+        torch = _torch()
+        n = int(ra.shape[0])
+        row_a = torch.empty(n + int(n_rows_a), dtype=torch.int32, device=self.device)
+        row_b = torch.empty(n + int(n_rows_a), dtype=torch.int32, device=self.device)
+        row_a[:n] = ra
+        row_b[:n] = rb
+        total = self.left_pad(row_a, row_b, n, n_rows_a)
+        return row_a[:total], row_b[:total]
 
     # --------------------------------------------------------------- checksum
     def pairs_checksum(self, row_a, row_b) -> int:

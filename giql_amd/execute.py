@@ -429,16 +429,23 @@ def _device_side(table, side: PlanSide, chrom_ids: np.ndarray, engine: HipEngine
     return dev
 
 
-def _take(table, name: str, idx: np.ndarray):
+def _take(table, name: str, idx: np.ndarray, pad_null: bool = False):
+    """``pad_null`` (the right side of a LEFT plan): a row id of -1 yields NULL."""
     col = _column(table, name)
+    pad = (idx < 0) if pad_null else None
     try:
         import pyarrow as pa
 
         if isinstance(col, (pa.ChunkedArray, pa.Array)):
-            return col.take(pa.array(idx, type=pa.int64()))
+            return col.take(pa.array(idx, type=pa.int64(), mask=pad))
     except ImportError:  # pragma: no cover
         pass
-    return np.asarray(col)[idx]
+    if pad is None:
+        return np.asarray(col)[idx]
+    vals = np.asarray(col)
+    if not vals.shape[0]:       # (an empty right table: every row is padded)
+        vals = np.zeros(1, vals.dtype)
+    return np.ma.masked_array(vals[np.where(pad, 0, idx)], mask=pad)
 
 
 class _Residuals:
@@ -730,6 +737,56 @@ def _join_with_residuals(plan: JoinPlan, lt, rt, a: DeviceSide, b: DeviceSide, n
     flags = eng.mark(matched.contiguous(), a.n)
     final = [(("a", flags), "=", ("lit", 0 if plan.kind == "ANTI" else 1))] + rb_.preds(outer)
     return eng.select(final, n=a.n, n_rows_a=a.n, want=("a",))[0]
+
+
+def _null_right(spec, device):
+    """A predicate of ``_Residuals.preds`` with every right-table column replaced by a one-row, all-NULL stand-in
+    (same dtype, validity byte 0): what a padded row of a LEFT join offers the WHERE clause."""
+    import torch
+
+    if not isinstance(spec, tuple):
+        return spec
+    if len(spec) >= 2 and spec[0] == "b" and torch.is_tensor(spec[1]):
+        return ("b", torch.zeros(1, dtype=spec[1].dtype, device=device), torch.zeros(1, dtype=torch.uint8, device=device))
+    return tuple(_null_right(x, device) for x in spec)
+
+
+def _left_join_rows(plan: JoinPlan, lt, rt, a: DeviceSide, b: DeviceSide, n_chrom: int, eng: HipEngine):
+    """A LEFT plan's row ids ``(ra, rb)``, ``rb == -1`` on a padded row.
+
+    The ON residuals take part in matching only, exactly as an INNER join's do (left-only ones restrict which left
+    rows CAN match, right-only ones shrink the right table, two-sided ones filter the pairs); ``left_pad``
+    then appends every one of the ``a.n`` left rows that kept no pair (measured faster than composing the same rows
+    from ``mark``, ``select`` and a concatenation: DESIGN.md, "LEFT OUTER joins").  The WHERE residuals filter that result under
+    three-valued logic: the matched pairs through ``select`` as they are, the padded rows through the SAME
+    ``select`` against a one-row all-NULL right table."""
+    import torch
+    from dataclasses import replace
+
+    on = tuple(r for r in plan.residuals if r.clause == "on")
+    where = tuple(r for r in plan.residuals if r.clause != "on")
+    inner = replace(plan, kind="INNER", residuals=on)
+    if on:
+        ra, rb = eng.left_pad_pairs(*_join_with_residuals(inner, lt, rt, a, b, n_chrom, eng), a.n)
+    elif plan.predicate == "intersects":
+        ra, rb = eng.left_join(a, b, n_chrom)      # (the pairs land in buffers with room for the pad)
+    else:
+        ra, rb = eng.left_pad_pairs(*_spatial_join(inner, a, b, n_chrom, eng), a.n)
+    if not where:
+        return ra, rb
+    n_matched = int((rb >= 0).sum())      # (the padded rows are the tail)
+    res = _Residuals(plan, lt, rt, eng, dev_sides={"l": a, "r": b})
+    preds = res.preds(res.clauses(where))
+    ka, kb = ra[:0], rb[:0]
+    if n_matched:
+        ka, kb = eng.select(preds, idx_a=ra[:n_matched], idx_b=rb[:n_matched], n_rows_a=a.n, n_rows_b=b.n)
+    n_pad = int(ra.shape[0]) - n_matched
+    if not n_pad:
+        return ka, kb
+    stand_in = [_null_right(p, eng.device) for p in preds]
+    kp = eng.select(stand_in, idx_a=ra[n_matched:], idx_b=torch.zeros(n_pad, dtype=torch.int32, device=eng.device),
+                    n_rows_a=a.n, n_rows_b=1, want=("a",))[0]
+    return torch.cat([ka, kp]), torch.cat([kb, torch.full_like(kp, -1)])
 
 
 def _execute_cluster_merge(plan: JoinPlan, tables, eng: HipEngine, return_indices: bool):
@@ -1029,13 +1086,15 @@ def _utf8_lengths(off_dev, idx_dev):
     import torch
 
     n_rows = int(off_dev.shape[0]) - 1
+    if n_rows <= 0:     # (an empty column has one offset: nothing to index, every id is a padded row's -1 or refused)
+        return torch.zeros(idx_dev.shape[0], dtype=torch.int64, device=idx_dev.device)
     ok = (idx_dev >= 0) & (idx_dev < n_rows)
     ix = torch.where(ok, idx_dev, 0).long()
     lens = off_dev[ix + 1].long() - off_dev[ix].long()
     return torch.where(ok, lens, 0)
 
 
-def _device_take(table, names, idx_dev, eng: HipEngine):
+def _device_take(table, names, idx_dev, eng: HipEngine, pad_null: bool = False):
     """Gather the projected columns ``names`` of ``table`` by the device-resident
     row ids ``idx_dev`` ON THE GPU (``giql_hip_take_dev`` / ``giql_hip_take_utf8_*``;
     the reference's outer SELECT, ``intersects_duckdb.py:1402-1644``).
@@ -1047,6 +1106,9 @@ def _device_take(table, names, idx_dev, eng: HipEngine):
     ``pyarrow.ChunkedArray`` of the column's own type (``plan_utf8_slices``).  Column types the
     kernels do not cover (nested, dictionary, large_*) use ``pyarrow.take`` on
     the host ids -- boundary plumbing, no join arithmetic.
+
+    ``pad_null`` (the right side of a LEFT plan): a row id of -1 yields NULL in every column, whether or not the
+    source column has NULLs of its own (the take kernels write zero bytes / an empty string there).
     """
     import pyarrow as pa
     import torch
@@ -1080,6 +1142,10 @@ def _device_take(table, names, idx_dev, eng: HipEngine):
     cols_dev += [torch.from_numpy(masks[m]).to(dev) for m in mask_names]
     taken = eng.take(cols_dev, idx_dev) if cols_dev else []
     valid = {m: taken[len(fixed) + i].cpu().numpy().astype(bool) for i, m in enumerate(mask_names)}
+    pad = (idx_dev < 0).cpu().numpy() if pad_null and n else None
+    if pad is not None and pad.any():
+        for name in [f[0] for f in fixed] + [s_[0] for s_ in strings]:
+            valid[name] = (valid[name] & ~pad) if name in valid else ~pad
     for (name, t, v), tk in zip(fixed, taken):
         arr = _to_host(tk)
         out[name] = pa.array(arr, type=t, mask=(~valid[name]) if name in valid else None)
@@ -1109,7 +1175,8 @@ def _device_take(table, names, idx_dev, eng: HipEngine):
             del o_dev, d_dev
         out[name] = chunks[0] if len(chunks) == 1 else pa.chunked_array(chunks, type=t)
     if host:
-        idx_h = pa.array(idx_dev.cpu().numpy(), type=pa.int64())
+        idx_np = idx_dev.cpu().numpy()
+        idx_h = pa.array(idx_np, type=pa.int64(), mask=(idx_np < 0) if pad_null else None)
         for name in host:
             out[name] = _column(table, name).take(idx_h)
     return out
@@ -1408,6 +1475,11 @@ def _join_piece(plan: JoinPlan, lt, rt, ia: np.ndarray, ib: np.ndarray, n_chrom:
         idx = {"l": ra, "r": rb}
         if any(p.side == "pair_distance" for p in plan.projection):
             extra = {"pair_distance": _pair_distances(plan, lt, rt, a, b, ra, rb, eng)}
+    elif plan.kind == "LEFT":
+        ra, rb = _left_join_rows(plan, lt, rt, a, b, n_chrom, eng)
+        if return_indices:
+            return ra.cpu().numpy(), rb.cpu().numpy()
+        idx = {"l": ra, "r": rb}
     elif plan.kind in ("SEMI", "ANTI"):
         if plan.residuals:
             rows = _join_with_residuals(plan, lt, rt, a, b, n_chrom, eng)
@@ -1440,7 +1512,7 @@ def _project(plan: JoinPlan, lt, rt, idx: dict, extra: dict, eng: HipEngine, dev
         for s, tbl in (("l", lt), ("r", rt)):
             want = [p.column for p in wanted if p.side == s]
             if want and s in idx:
-                taken[s] = _device_take(tbl, want, idx[s], eng)
+                taken[s] = _device_take(tbl, want, idx[s], eng, pad_null=(s == "r" and plan.kind == "LEFT"))
     idx_h = {s: v.cpu().numpy() for s, v in idx.items() if s not in taken}
 
     names, cols = [], []
@@ -1453,7 +1525,8 @@ def _project(plan: JoinPlan, lt, rt, idx: dict, extra: dict, eng: HipEngine, dev
         elif p.side in taken:
             cols.append(taken[p.side][p.column])
         else:
-            cols.append(_take(lt if p.side == "l" else rt, p.column, idx_h[p.side]))
+            cols.append(_take(lt if p.side == "l" else rt, p.column, idx_h[p.side],
+                              pad_null=(p.side == "r" and plan.kind == "LEFT")))
     if pa is None:  # pragma: no cover
         return dict(zip(names, cols))
     def as_arrow(c):
@@ -1553,14 +1626,15 @@ def _execute_sharded(plan: JoinPlan, lt, rt, ia, ib, n_chrom, devices, return_in
 
 
 def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, return_indices=False,
-            device_projection: bool = True, devices=None):
-    """Run *plan* (a :class:`JoinPlan`, its string form, or a GIQL query string)
-    against ``tables`` (``{name: pyarrow.Table | dict of arrays}``).
+            device_projection: bool = True, devices=None, outer_joins: bool = False):
+    """Run *plan* (a :class:`JoinPlan`, its string form, or a GIQL query string; ``outer_joins`` as in
+    :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
+    (``{name: pyarrow.Table | dict of arrays}``).
 
     Returns a ``pyarrow.Table`` with the plan's projected columns (bag semantics,
     unspecified row order, as upstream), or ``{column: array}`` when pyarrow is
     absent.  ``return_indices=True`` returns the raw row indices instead:
-    ``(row_a, row_b)`` for INNER, ``rows_a`` for SEMI/ANTI,
+    ``(row_a, row_b)`` for INNER and LEFT (``row_b == -1`` on a left row without a match), ``rows_a`` for SEMI/ANTI,
     ``(rows_a, idx_b, distance)`` for NEAREST (``distance`` a numpy masked array when
     ``stranded := true`` met '.' / '?' strands: those rows' distance is NULL) and the
     per-left-row counts for count_overlaps.  ``device_projection`` (default) gathers the projected columns
@@ -1574,7 +1648,7 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
     first one.
     """
     if isinstance(plan, str):
-        plan = JoinPlan.from_string(plan) if is_plan_string(plan) else build_plan(plan, giql_tables)
+        plan = JoinPlan.from_string(plan) if is_plan_string(plan) else build_plan(plan, giql_tables, outer_joins=outer_joins)
     if not isinstance(plan, JoinPlan):
         raise ValueError("plan must be a JoinPlan, a plan string or a GIQL query")
     devices = [int(d) for d in devices] if devices is not None else None
@@ -1596,6 +1670,9 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
             raise ValueError(f"table {side.table!r} was not provided")
     lt, rt = tables[plan.left.table], tables[plan.right.table]
     pins = {"l": pinned.get(plan.left.table), "r": pinned.get(plan.right.table)}
+    if plan.kind == "LEFT" and devices is not None and len(devices) > 1:
+        raise NotImplementedError(f"a LEFT OUTER join runs on one device; devices={devices!r} names {len(devices)} "
+                                  "(the per-chromosome fan-out does not pad unmatched rows yet)")
     if plan.predicate != "intersects" and devices is not None and len(devices) > 1:
         # one device, like DISJOIN: the per-chromosome fan-out shards an INTERSECTS join
         raise ValueError(f"{plan.predicate.upper()} joins run on one device; devices={devices!r} names {len(devices)}")

@@ -13,7 +13,11 @@ from dataclasses import asdict, dataclass, field
 
 PLAN_PREFIX = "GIQL-HIP-PLAN/1 "
 
-KINDS = ("INNER", "SEMI", "ANTI", "NEAREST", "COUNT", "CLUSTER", "MERGE", "FILTER", "DISJOIN")
+KINDS = ("INNER", "SEMI", "ANTI", "NEAREST", "COUNT", "CLUSTER", "MERGE", "FILTER", "DISJOIN", "LEFT")
+
+#: the kinds that produce pairs through a spatial predicate: INNER, and LEFT = INNER's pairs + one (left row, NULL)
+#: row per left row that keeps none (its ON residuals take part in matching, its WHERE residuals filter the result)
+PAIR_KINDS = ("INNER", "LEFT")
 
 #: the spatial predicate of an INNER plan
 PREDICATES = ("intersects", "contains", "within", "within_distance")
@@ -132,7 +136,7 @@ class JoinPlan:
     limit: int | None = None
     offset: int | None = None
     output: tuple[str, ...] = field(default_factory=tuple)         # final column names in SELECT order (grouped plans)
-    # INNER only: the join's spatial predicate, left <predicate> right (src/giql/expanders/intersects.py:149-166).
+    # INNER / LEFT only: the join's spatial predicate, left <predicate> right (src/giql/expanders/intersects.py:149-166).
     # "contains" / "within" run HipEngine.contain_join; plan strings written before the field existed load as
     # "intersects".  "within_distance": DISTANCE(left, right) <= max_distance (HipEngine.window_join; -1 = nothing
     # qualifies, the query compared with < 0).  A stranded "pair_distance" projection reads strand_col
@@ -144,7 +148,7 @@ class JoinPlan:
             raise ValueError(f"unknown plan kind {self.kind!r}")
         if self.predicate not in PREDICATES:
             raise ValueError(f"unknown join predicate {self.predicate!r}")
-        if self.predicate != "intersects" and self.kind != "INNER":
+        if self.predicate != "intersects" and self.kind not in PAIR_KINDS:
             raise ValueError(f"predicate {self.predicate!r} needs an INNER plan, not {self.kind}")
         if self.predicate == "within_distance" and not isinstance(self.max_distance, int):
             raise ValueError("predicate 'within_distance' needs an integer max_distance")

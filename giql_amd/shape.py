@@ -263,6 +263,8 @@ class JoinShape:
     # the two operands as resolved by the caller (the plugin reads them from
     # ``ctx.resolution.column(...)``); None = derive them from ``tables`` by table name
     sides: tuple[PlanSide, PlanSide] | None = None
+    # opt-in: a LEFT [OUTER] JOIN outside the count_overlaps shape lowers to a LEFT plan instead of declining
+    outer_joins: bool = False
 
 
 # ------------------------------------------------------------------ helpers
@@ -441,6 +443,8 @@ def check_expression_sizes(residuals, kind: str) -> None:
             nodes += n
         sides = frozenset(operand_sides(r.lhs) | operand_sides(r.rhs))
         call = ("where" if kind in ("SEMI", "ANTI") and r.clause == "where" else "on", sides)
+        if kind == "LEFT" and r.clause == "where":
+            call = ("where", None)      # the WHERE of a LEFT plan filters the padded result in one call per half
         per_call[call] = per_call.get(call, 0) + nodes
         if per_call[call] > MAX_EXPR_NODES:
             raise decline(f"expressions too large for one select call ({per_call[call]} nodes, at most {MAX_EXPR_NODES})")
@@ -717,9 +721,11 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
     if kind == "LEFT":
         # count_overlaps: LEFT [OUTER] JOIN ... COUNT(b.col) ... GROUP BY left keys
         # (_match_count_overlaps, intersects_duckdb.py:432-548); every other outer join declines (:661-662)
-        if not has_count_item:
+        # unless the caller opted in (JoinShape.outer_joins): then it is a LEFT plan
+        if has_count_item:
+            kind = "COUNT"
+        elif not shape.outer_joins:
             raise decline("LEFT outer join")
-        kind = "COUNT"
     if kind == "COUNT" and not shape.on_seen:
         raise decline("count_overlaps without an ON clause")
     if shape.using:
@@ -739,8 +745,17 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
     if len(spatial) > 1:
         raise decline("more than one INTERSECTS" if all(t[0] == "intersects" for t in spatial)
                       else "more than one spatial predicate in a join")
+    if kind == "LEFT" and not any(t[0] in JOIN_TERMS for t in on_terms):
+        # in WHERE the predicate would filter the padded rows away again: an INNER join written the long way
+        raise decline("LEFT join with its spatial predicate outside ON")
     predicate, lhs, rhs = spatial[0][:3]
     max_distance = spatial[0][3] if predicate == DISTANCE_TERM else None
+    if kind == "LEFT" and predicate == "intersects":
+        # bedtools -v: LEFT JOIN ... WHERE b.<chrom | start | end> IS NULL with no other use of the right table is
+        # the ANTI join (a matched row's right key columns are never NULL) -- semi_anti, not pairs thrown away
+        rest = _anti_shortcut(shape, where_terms, right)
+        if rest is not None:
+            kind, where_terms = "ANTI", rest
     label = "DISTANCE" if predicate == DISTANCE_TERM else predicate.upper()
     if predicate != "intersects":
         # CONTAINS / WITHIN / DISTANCE <= N run as the pair-producing join only (HipEngine.contain_join / window_join)
@@ -804,13 +819,48 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
     if predicate == DISTANCE_TERM:
         # x.chrom = y.chrom beside the predicate (the documented recipe writes it): a NULL distance already drops
         # pairs across chromosomes, the join IS per chromosome -- absorbed, not run as a string comparison per pair
-        cmp_terms = [(c, t) for c, t in cmp_terms if not _is_chrom_equality(t, left, right)]
+        # (in the WHERE of a LEFT join the equality is a filter of its own: it drops the padded rows)
+        cmp_terms = [(c, t) for c, t in cmp_terms
+                     if (kind == "LEFT" and c == "where") or not _is_chrom_equality(t, left, right)]
     residuals = resolve_residuals(cmp_terms, left, right, kind)
     strand_col = strands[0] if strands else None
     return JoinPlan(kind, left, right, tuple(proj) + hidden, shape.distinct, max_distance=max_distance,
                     residuals=residuals, strand_col=strand_col,
                     aggregates=aggs, group_by=groups, having=having, order_by=order,
                     limit=shape.limit, offset=shape.offset, output=output, predicate=predicate)
+
+
+def _col_refs(x):
+    """Every :class:`ColRef` inside a term, an operand, a select item or a list of them."""
+    if isinstance(x, ColRef):
+        yield x
+    elif isinstance(x, SelItem):
+        yield from _col_refs(x.ref)
+        yield from _col_refs(x.distance)
+    elif isinstance(x, OrderKey):
+        yield from _col_refs(x.ref)
+    elif isinstance(x, (tuple, list)):
+        for y in x:
+            yield from _col_refs(y)
+
+
+def _anti_shortcut(shape: JoinShape, where_terms: list, right: PlanSide):
+    """The WHERE terms left over when a LEFT join is an ANTI join in disguise, else None: one conjunct is
+    ``<right>.<chrom | start | end column> IS NULL`` and nothing else in the statement -- the SELECT list, the other
+    WHERE conjuncts, GROUP BY, HAVING, ORDER BY -- reads the right table (a star counts as reading it)."""
+    def reads_right(x) -> bool:
+        return any(r.star or (r.table is not None and norm(r.table, r.table_quoted) == right.alias)
+                   for r in _col_refs(x))
+
+    keys = (right.chrom_col, right.start_col, right.end_col)
+    for i, t in enumerate(where_terms):
+        if (t[0] == "cmp" and t[2] == "isnull" and t[1][0] == "col" and isinstance(t[1][1], ColRef)
+                and not t[1][1].star and t[1][1].column in keys and reads_right(t[1])):
+            rest = where_terms[:i] + where_terms[i + 1:]
+            if not reads_right([shape.items, rest, shape.group_by, shape.having, shape.order_by]):
+                return rest
+            return None
+    return None
 
 
 def _is_chrom_equality(term, left: PlanSide, right: PlanSide) -> bool:

@@ -1103,9 +1103,12 @@ def _lower_disjoin(p: _Parser, tbls: Tables) -> JoinPlan:
     return lower_disjoin_shape(shape, tbls)
 
 
-def build_plan(giql: str, tables=None) -> JoinPlan:
+def build_plan(giql: str, tables=None, *, outer_joins: bool = False) -> JoinPlan:
     """Parse *giql* and lower the INTERSECTS / NEAREST join (or a CLUSTER / MERGE
-    query) to a :class:`JoinPlan`."""
+    query) to a :class:`JoinPlan`.
+
+    ``outer_joins=True`` opts in to LEFT [OUTER] JOIN: outside the count_overlaps shape it lowers to a plan of
+    kind ``LEFT`` (or ``ANTI``, for the ``WHERE b.<key> IS NULL`` recipe) instead of declining."""
     probe = _Parser(giql)
     if _disjoin_from(probe) is not None:
         return _lower_disjoin(probe, tables if isinstance(tables, Tables) else build_tables(tables))
@@ -1113,12 +1116,12 @@ def build_plan(giql: str, tables=None) -> JoinPlan:
         return _lower_cluster(probe, tables if isinstance(tables, Tables) else build_tables(tables))
     if probe.at_kw("SELECT") and _is_single_table_filter(probe):
         return _lower_filter(probe, tables if isinstance(tables, Tables) else build_tables(tables))
-    plan = _lower(giql, tables, want_sql=False)
+    plan = _lower(giql, tables, want_sql=False, outer_joins=outer_joins)
     assert isinstance(plan, JoinPlan)
     return plan
 
 
-def _lower(giql: str, tables, want_sql: bool):
+def _lower(giql: str, tables, want_sql: bool, outer_joins: bool = False):
     tbls = tables if isinstance(tables, Tables) else build_tables(tables)
     p = _Parser(giql)
     if p.at_kw("WITH"):
@@ -1222,7 +1225,7 @@ def _lower(giql: str, tables, want_sql: bool):
                         stranded=nearest[3], strand_col=strand_col)
 
     shape = JoinShape(items=items, from_ref=from_ref, join_ref=join_ref, kind=kind, on_seen=on_seen, using=using,
-                      distinct=distinct)
+                      distinct=distinct, outer_joins=bool(outer_joins))
     if on_seen:
         if p.peek().kind not in ("id", "num", "str") and not p.at_punct("-") and not p.at_punct("(") \
                 and not p.at_kw("NOT"):
@@ -1306,16 +1309,17 @@ def _render(toks: list[Tok]) -> str:
     return out
 
 
-def transpile(giql: str, tables=None, *, dialect: str | None = None) -> str:
+def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins: bool = False) -> str:
     """Mirror of ``giql.transpile`` for this backend's path.
 
     ``dialect="hip"``: returns the plan string of the INTERSECTS / NEAREST join
-    (hand it to :func:`giql_amd.execute`).  ``dialect=None``: returns SQL for the
+    (hand it to :func:`giql_amd.execute`); ``outer_joins=True`` lets a LEFT [OUTER] JOIN lower too
+    (:func:`build_plan`).  ``dialect=None``: returns SQL for the
     literal-range predicate (plumbing, BASELINE config 1).  Other dialects belong to
     the reference package.
     """
     if dialect == "hip":
-        return build_plan(giql, tables).to_string()
+        return build_plan(giql, tables, outer_joins=outer_joins).to_string()
     if dialect is None:
         return _lower(giql, tables, want_sql=True)
     raise ValueError(

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define GIQL_HIP_ABI_VERSION 4  /* 2: giql_hip_stats.phase_bytes, pinned host outputs, plan export; 3: DISJOIN; 4: CONTAINS / WITHIN (DISTANCE added two symbols, no change) */
+#define GIQL_HIP_ABI_VERSION 4  /* 2: giql_hip_stats.phase_bytes, pinned host outputs, plan export; 3: DISJOIN; 4: CONTAINS / WITHIN (DISTANCE added two symbols, left_pad one: no change) */
 
 enum {
   GIQL_OK = 0,
@@ -165,7 +165,7 @@ int giql_hip_get_stats(giql_hip_ctx* ctx, giql_hip_stats* out);
  * The plan lives in the context's workspace.  It is consumed by fill and by
  * giql_hip_inner_plan_export_dev (each as often as wanted) only until the next call
  * on the context that launches work and is neither: the operators, the index entry
- * points, chrom_spans, select and take_utf8_plan reuse that workspace and make fill /
+ * points, chrom_spans, select, left_pad and take_utf8_plan reuse that workspace and make fill /
  * export return GIQL_ERR_STATE; after any other such call a fill is not supported.
  * Calls that launch nothing -- get_stats, set_profiling, last_error -- keep the plan. */
 int giql_hip_inner_plan_dev(giql_hip_ctx* ctx, const giql_side* a,
@@ -464,6 +464,18 @@ int giql_hip_select_expr_dev(giql_hip_ctx* ctx, const giql_pred* preds, int32_t 
  * residuals (src/giql/expanders/intersects_duckdb.py:1254-1282). */
 int giql_hip_mark_dev(giql_hip_ctx* ctx, const int32_t* idx, int64_t n,
                       uint8_t* flags, int64_t n_rows, void* stream);
+/* The unmatched-row pass of a LEFT OUTER join over the pairs of an INNER join (any of the pair-producing
+ * operators; residual filters applied first).
+ * Appends, in place, one (row, -1) entry for every r in [0, n_rows_a) that does not occur in
+ * row_a[0 .. n_pairs): row_a[n_pairs + j] = j-th such r in ascending order, row_b[n_pairs + j] = -1.
+ * *n_total = n_pairs + number appended.  capacity < *n_total: GIQL_ERR_CAPACITY, *n_total set, nothing
+ * written at or past n_pairs.  An id in row_a outside [0, n_rows_a): GIQL_ERR_INVALID, nothing appended.
+ * row_b may be NULL (ids only).  n_rows_a <= 0x7FFFFFFF; n_pairs is 64-bit.
+ * The call keeps a flag byte and a bit per left row in the context's workspace, like the other operators: an INNER
+ * plan held there is gone afterwards (giql_hip_inner_fill_dev / giql_hip_inner_plan_export_dev return
+ * GIQL_ERR_STATE), so fill the pairs first and pad them second. */
+int giql_hip_left_pad_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, int64_t n_pairs,
+                          int64_t capacity, int64_t n_rows_a, void* stream, int64_t* n_total);
 
 /* ---- host-buffer entry points (Arrow buffers in host memory) ------------
  * giql_hip_inner: columns of both tables in host memory in, the pairs out in host arrays the library
