@@ -15,7 +15,7 @@ from __future__ import annotations
 import ctypes
 from dataclasses import dataclass
 
-from . import _lib
+from . import _lib, wide
 
 #: (coordinate_system, interval_type) -> (start_off, end_off)
 #: src/giql/canonical.py:16-52
@@ -31,6 +31,11 @@ def _torch():
     import torch
 
     return torch
+
+
+def _c_max_distance(max_distance) -> int:
+    """``max_distance`` as the C ABI takes it: -1 = no limit."""
+    return -1 if max_distance is None else int(max_distance)
 
 
 @dataclass
@@ -297,10 +302,28 @@ class HipEngine:
     def _join_into_buffers(self, a: DeviceSide, b: DeviceSide, n_chrom: int, out=None, extra_room: int = 0):
         """The INNER join's pairs at the front of two int32 device buffers: ``(row_a, row_b, n_pairs)``.  The buffers
         hold at least ``n_pairs + extra_room`` entries (what a caller appends behind the pairs: :meth:`left_join`),
-        and the join itself is never offered the extra room -- except after a ``GIQL_ERR_SPAN``, when the pairs of
-        the chromosome groups come back in tensors of exactly their length."""
+        and the join itself is never offered the extra room -- except on a genome wider than the 32-bit axis, when
+        the pairs of the chromosome groups come back in tensors of exactly their length (:meth:`_wide`).  A group's
+        join is planned and filled into exactly sized buffers and leaves ``_pairs_guess`` / ``_pairs_guess_rows``
+        alone: a sub-join must not overwrite the guess of the whole."""
         torch = _torch()
-        extra = int(extra_room)
+
+        def once(sa, sb, rows):
+            if rows is None:
+                return self._join_once(sa, sb, n_chrom, out, int(extra_room))
+            n = self.inner_plan(sa, sb, n_chrom)
+            pairs = [torch.empty(n, dtype=torch.int32, device=self.device) for _ in range(2)]
+            self.inner_fill(*pairs)
+            return pairs
+
+        def combine(parts):
+            ra, rb = wide.pairs(parts, self.device)
+            return ra, rb, int(ra.shape[0])
+
+        return self._wide(once, combine, a, b, n_chrom)
+
+    def _join_once(self, a: DeviceSide, b: DeviceSide, n_chrom: int, out, extra: int):
+        torch = _torch()
         # A context that has joined before gets ONE call (giql_hip_inner_join_dev): buffers sized from its previous
         # result -- for large tables the pairs are then written by the sort's last stage itself, with no count /
         # scan / fill kernels and no read-back in between.  A result that does not fit comes back as
@@ -335,9 +358,6 @@ class HipEngine:
                 self._pairs_guess, self._pairs_guess_rows = n, (a.n, b.n)
                 return row_a, row_b, n
             except _lib.GiqlHipError as exc:
-                if exc.code == _lib.GIQL_ERR_SPAN:
-                    ra, rb = self._inner_by_groups(a, b, n_chrom)
-                    return ra, rb, int(ra.shape[0])
                 if exc.code != _lib.GIQL_ERR_CAPACITY:
                     raise
                 n = int(self.last_pairs)
@@ -347,13 +367,7 @@ class HipEngine:
                 self.inner_fill(row_a, row_b)
                 self._pairs_guess, self._pairs_guess_rows = n, (a.n, b.n)
                 return row_a, row_b, n
-        try:
-            n = self.inner_plan(a, b, n_chrom)
-        except _lib.GiqlHipError as exc:
-            if exc.code != _lib.GIQL_ERR_SPAN:
-                raise
-            ra, rb = self._inner_by_groups(a, b, n_chrom)
-            return ra, rb, int(ra.shape[0])
+        n = self.inner_plan(a, b, n_chrom)
         self._pairs_guess, self._pairs_guess_rows = n, (a.n, b.n)
         if out is not None and min(int(out[0].shape[0]), int(out[1].shape[0])) >= n + extra:
             row_a, row_b = out[0], out[1]
@@ -379,10 +393,7 @@ class HipEngine:
         (``giql_hip_inner_join_indexed_dev``).  ``a.chrom`` speaks the indexed table's dictionary.  The buffers
         are sized from the index's previous result (``cap`` overrides); a short buffer costs one more call."""
         torch = _torch()
-        if index.engine is not self:
-            raise ValueError("the index was built on another engine")
-        if a.n and a.device != self.device:
-            raise ValueError(f"side lives on {a.device}, engine on {self.device}")
+        self._check_indexed(a, index)
         cap = int(cap) if cap is not None else (int(index.last_pairs * 1.05) + 4096 if index.last_pairs else max(a.n, 1 << 20))
         for _attempt in range(3):
             row_a = torch.empty(cap, dtype=torch.int32, device=self.device)
@@ -461,7 +472,7 @@ class HipEngine:
         # (the library writes every slot; one spare element keeps the pointers non-NULL for an empty query)
         idx = torch.empty(max(a.n, 1), dtype=torch.int32, device=self.device)
         dist = torch.empty(max(a.n, 1), dtype=torch.int64, device=self.device)
-        md = -1 if max_distance is None else int(max_distance)
+        md = _c_max_distance(max_distance)
         ca = a.c_struct()
         _lib.check(self._L.giql_hip_nearest_indexed_dev(self._h, index._h, ctypes.byref(ca), int(bool(signed)), md,
                                                         idx.data_ptr(), dist.data_ptr(), self._stream()))
@@ -502,40 +513,32 @@ class HipEngine:
                             b.start_off, b.end_off)
             yield sa, ra, sb, rb
 
-    def _inner_by_groups(self, a, b, n_chrom):
+    def _empty_side(self) -> DeviceSide:
         torch = _torch()
-        outs_a, outs_b = [], []
-        for sa, ra, sb, rb in self._groups(a, b, n_chrom):
-            n = self.inner_plan(sa, sb, n_chrom)
-            la = torch.empty(n, dtype=torch.int32, device=self.device)
-            lb = torch.empty(n, dtype=torch.int32, device=self.device)
-            self.inner_fill(la, lb)
-            outs_a.append(ra[la.long()].to(torch.int32))
-            outs_b.append(rb[lb.long()].to(torch.int32))
-        if not outs_a:
-            z = torch.empty(0, dtype=torch.int32, device=self.device)
-            return z, z.clone()
-        return torch.cat(outs_a), torch.cat(outs_b)
+        z = torch.empty(0, dtype=torch.int32, device=self.device)
+        return DeviceSide(z, z.clone(), z.clone(), 0, 0)
 
-    def _retry_by_groups(self, fn, a, b, n_chrom, pad: int = 0):
-        """Run ``fn(sub_a, sub_b)`` per group after a GIQL_ERR_SPAN."""
-        return [(ra, rb, fn(sa, sb)) for sa, ra, sb, rb in self._groups(a, b, n_chrom, pad)]
+    def _wide(self, once, combine, a: DeviceSide, b, n_chrom: int, pad: int = 0):
+        """Every operator's answer to a genome wider than the 32-bit axis.  ``once(a, b, None)`` on the whole sides
+        is the result; when the library refuses them with ``GIQL_ERR_SPAN``, ``once(sub_a, sub_b, rows_a)`` runs per
+        group of :meth:`_groups`, in its order, and ``combine`` (a function of :mod:`giql_amd.wide`) turns the list
+        of ``(rows_a, rows_b, result)`` into the result for the whole sides.  ``b=None`` (a one-table operator,
+        DISJOIN's self mode): an empty side stands in for the grouping and ``once`` gets ``None`` every time.  Any
+        other error is the caller's."""
+        try:
+            return once(a, b, None)
+        except _lib.GiqlHipError as exc:
+            if exc.code != _lib.GIQL_ERR_SPAN:
+                raise
+        groups = self._groups(a, b if b is not None else self._empty_side(), n_chrom, pad)
+        return combine([(ra, rb, once(sa, sb if b is not None else None, ra)) for sa, ra, sb, rb in groups])
 
     # -------------------------------------------------------------- SEMI/ANTI
     def semi_anti(self, a: DeviceSide, b: DeviceSide, n_chrom: int, anti: bool):
         """Ascending A row ids with (SEMI) / without (ANTI) an overlapping B row."""
-        torch = _torch()
         self._check_sides(a, b)
-        try:
-            return self._semi_anti_once(a, b, n_chrom, anti)
-        except _lib.GiqlHipError as exc:
-            if exc.code != _lib.GIQL_ERR_SPAN:
-                raise
-        parts = [ra[rows.long()] for ra, _rb, rows in
-                 self._retry_by_groups(lambda sa, sb: self._semi_anti_once(sa, sb, n_chrom, anti), a, b, n_chrom)]
-        if not parts:
-            return torch.empty(0, dtype=torch.int32, device=self.device)
-        return torch.sort(torch.cat(parts)).values.to(torch.int32)
+        return self._wide(lambda sa, sb, _rows: self._semi_anti_once(sa, sb, n_chrom, anti),
+                          lambda parts: wide.row_ids(parts, self.device), a, b, n_chrom)
 
     def _semi_anti_once(self, a: DeviceSide, b: DeviceSide, n_chrom: int, anti: bool):
         torch = _torch()
@@ -555,17 +558,9 @@ class HipEngine:
     # ------------------------------------------------------------------ COUNT
     def count_overlaps(self, a: DeviceSide, b: DeviceSide, n_chrom: int):
         """int64 tensor: number of overlapping B rows per A row (original order)."""
-        torch = _torch()
         self._check_sides(a, b)
-        try:
-            return self._count_once(a, b, n_chrom)
-        except _lib.GiqlHipError as exc:
-            if exc.code != _lib.GIQL_ERR_SPAN:
-                raise
-        counts = torch.zeros(a.n, dtype=torch.int64, device=self.device)
-        for ra, _rb, c in self._retry_by_groups(lambda sa, sb: self._count_once(sa, sb, n_chrom), a, b, n_chrom):
-            counts[ra] = c
-        return counts
+        return self._wide(lambda sa, sb, _rows: self._count_once(sa, sb, n_chrom),
+                          lambda parts: wide.per_row(parts, a.n, self.device), a, b, n_chrom)
 
     def _count_once(self, a: DeviceSide, b: DeviceSide, n_chrom: int):
         torch = _torch()
@@ -579,24 +574,9 @@ class HipEngine:
     def nearest(self, a: DeviceSide, b: DeviceSide, n_chrom: int, signed: bool = False,
                 max_distance=None):
         """NEAREST k=1: ``(idx_b int32, distance int64)`` per A row; idx_b=-1 = none."""
-        torch = _torch()
         self._check_sides(a, b)
-        try:
-            return self._nearest_once(a, b, n_chrom, signed, max_distance)
-        except _lib.GiqlHipError as exc:
-            if exc.code != _lib.GIQL_ERR_SPAN:
-                raise
-        idx = torch.full((a.n,), -1, dtype=torch.int32, device=self.device)
-        dist = torch.zeros(a.n, dtype=torch.int64, device=self.device)
-        for ra, rb, (gi, gd) in self._retry_by_groups(
-                lambda sa, sb: self._nearest_once(sa, sb, n_chrom, signed, max_distance), a, b, n_chrom):
-            hit = gi >= 0
-            mapped = torch.full_like(gi, -1)
-            if rb.numel():
-                mapped[hit] = rb[gi[hit].long()].to(torch.int32)
-            idx[ra] = mapped
-            dist[ra] = gd
-        return idx, dist
+        return self._wide(lambda sa, sb, _rows: self._nearest_once(sa, sb, n_chrom, signed, max_distance),
+                          lambda parts: wide.nearest(parts, (a.n,), self.device), a, b, n_chrom)
 
     def _nearest_once(self, a: DeviceSide, b: DeviceSide, n_chrom: int, signed: bool = False,
                       max_distance=None):
@@ -604,7 +584,7 @@ class HipEngine:
         # (no pre-fill: the library writes every slot -- k_nearest_unpack, or its own memsets for an empty B)
         idx = torch.empty((a.n,), dtype=torch.int32, device=self.device)
         dist = torch.empty(a.n, dtype=torch.int64, device=self.device)
-        md = -1 if max_distance is None else int(max_distance)
+        md = _c_max_distance(max_distance)
         _lib.check(self._L.giql_hip_nearest_dev(
             self._h, a.c_struct(), b.c_struct(), int(n_chrom), int(bool(signed)), md,
             idx.data_ptr() if a.n else None, dist.data_ptr() if a.n else None, self._stream()))
@@ -618,7 +598,7 @@ class HipEngine:
         torch = _torch()
         self._check_sides(a, b)
         out = torch.empty((a.n, 2), dtype=torch.int32, device=self.device)
-        md = -1 if max_distance is None else int(max_distance)
+        md = _c_max_distance(max_distance)
         _lib.check(self._L.giql_hip_nearest32_dev(
             self._h, a.c_struct(), b.c_struct(), int(n_chrom), int(bool(signed)), md,
             out.data_ptr() if a.n else None, self._stream()))
@@ -627,25 +607,10 @@ class HipEngine:
     def nearest_k(self, a: DeviceSide, b: DeviceSide, n_chrom: int, k: int, signed: bool = False, max_distance=None):
         """NEAREST k >= 1: ``(idx_b [n_a, k] int32, distance [n_a, k] int64)`` per A row in the reference's
         order ABS(distance), start, end; unused slots idx_b = -1 (``giql_hip_nearest_k_dev``)."""
-        torch = _torch()
         self._check_sides(a, b)
         k = int(k)
-        try:
-            return self._nearest_k_once(a, b, n_chrom, k, signed, max_distance)
-        except _lib.GiqlHipError as exc:
-            if exc.code != _lib.GIQL_ERR_SPAN:
-                raise
-        idx = torch.full((a.n, k), -1, dtype=torch.int32, device=self.device)
-        dist = torch.zeros((a.n, k), dtype=torch.int64, device=self.device)
-        for ra, rb, (gi, gd) in self._retry_by_groups(
-                lambda sa, sb: self._nearest_k_once(sa, sb, n_chrom, k, signed, max_distance), a, b, n_chrom):
-            hit = gi >= 0
-            mapped = torch.full_like(gi, -1)
-            if rb.numel():
-                mapped[hit] = rb[gi[hit].long()].to(torch.int32)
-            idx[ra] = mapped
-            dist[ra] = gd
-        return idx, dist
+        return self._wide(lambda sa, sb, _rows: self._nearest_k_once(sa, sb, n_chrom, k, signed, max_distance),
+                          lambda parts: wide.nearest(parts, (a.n, k), self.device), a, b, n_chrom)
 
     def _nearest_k_once(self, a: DeviceSide, b: DeviceSide, n_chrom: int, k: int, signed: bool = False,
                         max_distance=None):
@@ -653,7 +618,7 @@ class HipEngine:
         # (no pre-fill: the library writes every slot, unused ones as idx -1 / distance 0)
         idx = torch.empty((a.n, k), dtype=torch.int32, device=self.device)
         dist = torch.empty((a.n, k), dtype=torch.int64, device=self.device)
-        md = -1 if max_distance is None else int(max_distance)
+        md = _c_max_distance(max_distance)
         _lib.check(self._L.giql_hip_nearest_k_dev(
             self._h, a.c_struct(), b.c_struct(), int(n_chrom), k, int(bool(signed)), md,
             idx.data_ptr() if a.n else None, dist.data_ptr() if a.n else None, self._stream()))
@@ -666,32 +631,10 @@ class HipEngine:
         count_overlaps (``intersects_duckdb.py:806-854``).  Group ids ascend with
         (chrom, start, end), the order of the linear axis, also when a genome wider
         than 32 bits is grouped by chromosomes."""
-        torch = _torch()
-        try:
-            return self._group_rows_once(s, n_chrom)
-        except _lib.GiqlHipError as exc:
-            if exc.code != _lib.GIQL_ERR_SPAN:
-                raise
-        raw = DeviceSide(s.chrom, s.start, s.end, 0, 0)  # the kernel groups RAW coordinates: so are the spans taken
-        parts = []
-        for sub, rows, _sb, _rb in self._groups(raw, self._empty_side(raw), n_chrom):
-            gid, rep = self._group_rows_once(sub, n_chrom)
-            parts.append((rows, gid, rows[rep.long()]))
-        gid = torch.empty(s.n, dtype=torch.int32, device=self.device)
-        if not parts:
-            return gid, gid.clone()
-        # each group numbers its groups along its own axis: renumber them in (chrom, start, end) order
-        rep = torch.cat([p[2] for p in parts])
-        order = torch.argsort(s.end[rep], stable=True)
-        order = order[torch.argsort(s.start[rep][order], stable=True)]
-        order = order[torch.argsort(s.chrom[rep][order], stable=True)]
-        rank = torch.empty_like(order)
-        rank[order] = torch.arange(order.numel(), dtype=order.dtype, device=self.device)
-        first = 0
-        for rows, g, r in parts:
-            gid[rows] = rank[first + g.long()].to(torch.int32)
-            first += int(r.numel())
-        return gid, rep[order].to(torch.int32)
+        # the kernel groups RAW coordinates (the library drops the offsets itself): so are the groups' spans taken
+        raw = DeviceSide(s.chrom, s.start, s.end, 0, 0)
+        return self._wide(lambda sub, _b, _rows: self._group_rows_once(sub, n_chrom),
+                          lambda parts: wide.group_rows(parts, s.chrom, s.start, s.end), raw, None, n_chrom)
 
     def _group_rows_once(self, s: DeviceSide, n_chrom: int):
         torch = _torch()
@@ -716,29 +659,16 @@ class HipEngine:
         return sums
 
     # --------------------------------------------------------- CLUSTER / MERGE
-    def _empty_side(self, like: DeviceSide) -> DeviceSide:
-        torch = _torch()
-        z = torch.empty(0, dtype=torch.int32, device=self.device)
-        return DeviceSide(z, z.clone(), z.clone(), 0, 0)
-
     def cluster(self, s: DeviceSide, n_chrom: int, distance: int = 0, preds=None):
         """CLUSTER ids per row (int64, 1-based within each partition ``s.chrom``):
         ``src/giql/expanders/cluster.py:210-300``.  Raw coordinates (offsets must be 0).
         ``preds`` (``predicate := ... PREV(col)``, cluster.py:281-296): ``[(lhs, op, rhs)]`` as for
         :meth:`select`, operand ``("a", column)`` = the current row's value, ``("b", column)`` = its sorted
         predecessor's; columns are device tensors of ``s.n`` rows."""
-        torch = _torch()
         if preds:
             return self._cluster_pred(s, n_chrom, distance, preds)
-        try:
-            return self._cluster_once(s, n_chrom, distance)
-        except _lib.GiqlHipError as exc:
-            if exc.code != _lib.GIQL_ERR_SPAN:
-                raise
-        ids = torch.zeros(s.n, dtype=torch.int64, device=self.device)
-        for sub, rows, _sb, _rb in self._groups(s, self._empty_side(s), n_chrom):
-            ids[rows] = self._cluster_once(sub, n_chrom, distance)
-        return ids
+        return self._wide(lambda sub, _b, _rows: self._cluster_once(sub, n_chrom, distance),
+                          lambda parts: wide.per_row(parts, s.n, self.device), s, None, n_chrom)
 
     @staticmethod
     def _check_pred_rows(s: DeviceSide, preds) -> None:
@@ -750,7 +680,11 @@ class HipEngine:
     @staticmethod
     def _preds_of_rows(preds, rows):
         """CLUSTER / MERGE predicates over the rows ``rows`` of their table (one chromosome group): every
-        column operand and its validity mask indexed by ``rows``; literals as they are."""
+        column operand and its validity mask indexed by ``rows``; literals as they are.  ``rows=None`` is the whole
+        table and no predicate stays none."""
+        if not preds or rows is None:
+            return preds
+
         def operand(o):
             if o[0] not in ("a", "b"):
                 return o
@@ -759,17 +693,10 @@ class HipEngine:
         return [(operand(p[0]), p[1], operand(p[2])) + tuple(p[3:]) for p in preds]
 
     def _cluster_pred(self, s: DeviceSide, n_chrom: int, distance: int, preds):
-        torch = _torch()
         self._check_pred_rows(s, preds)
-        try:
-            return self._cluster_pred_once(s, n_chrom, distance, preds)
-        except _lib.GiqlHipError as exc:
-            if exc.code != _lib.GIQL_ERR_SPAN:
-                raise
-        ids = torch.zeros(s.n, dtype=torch.int64, device=self.device)
-        for sub, rows, _sb, _rb in self._groups(s, self._empty_side(s), n_chrom):
-            ids[rows] = self._cluster_pred_once(sub, n_chrom, distance, self._preds_of_rows(preds, rows))
-        return ids
+        return self._wide(
+            lambda sub, _b, rows: self._cluster_pred_once(sub, n_chrom, distance, self._preds_of_rows(preds, rows)),
+            lambda parts: wide.per_row(parts, s.n, self.device), s, None, n_chrom)
 
     def _cluster_pred_once(self, s: DeviceSide, n_chrom: int, distance: int, preds):
         torch = _torch()
@@ -799,26 +726,9 @@ class HipEngine:
         reference promises no order).  The row count is exact and may pass 2^31 (count, then fill, like
         :meth:`inner_plan` / :meth:`inner_fill`).  Both sides share one chromosome dictionary and need
         ``start <= end`` on every row: a ``ValueError`` names the side that does not."""
-        torch = _torch()
         self._check_sides(target, reference if reference is not None else target)
-        try:
-            return self._disjoin_once(target, reference, n_chrom)
-        except _lib.GiqlHipError as exc:
-            if exc.code != _lib.GIQL_ERR_SPAN:
-                raise
-        # a genome longer than the 32-bit axis: chromosome groups are independent units
-        parts = []
-        ref = reference if reference is not None else self._empty_side(target)
-        for st, rt, sr, _rr in self._groups(target, ref, n_chrom):
-            p, s, e = self._disjoin_once(st, sr if reference is not None else None, n_chrom)
-            parts.append((rt[p.long()], s, e))
-        if not parts:
-            z = torch.empty(0, dtype=torch.int32, device=self.device)
-            return z, z.clone(), z.clone()
-        parent = torch.cat([p[0] for p in parts])
-        order = torch.argsort(parent, stable=True)   # groups keep (parent, start) order inside; restore it across them
-        return (parent[order].to(torch.int32), torch.cat([p[1] for p in parts])[order],
-                torch.cat([p[2] for p in parts])[order])
+        return self._wide(lambda st, sr, _rows: self._disjoin_once(st, sr, n_chrom),
+                          lambda parts: wide.disjoin(parts, self.device), target, reference, n_chrom)
 
     def _disjoin_once(self, target: DeviceSide, reference, n_chrom: int):
         torch = _torch()
@@ -865,19 +775,8 @@ class HipEngine:
         particular order.  ``x WITHIN y`` is ``contain_join(y, x)`` with the result columns exchanged.  Zero-length
         and inverted rows follow the literal predicate.  ``stats()["join_form"]`` tells the path: ``"uniform_b"``
         when every inner row has one length (the range of starts is exact), else ``"general"``."""
-        torch = _torch()
-        try:
-            return self._contain_once(outer, inner, n_chrom)
-        except _lib.GiqlHipError as exc:
-            if exc.code != _lib.GIQL_ERR_SPAN:
-                raise
-        # a genome longer than the 32-bit axis: chromosome groups are independent units
-        parts = [(ro[po.long()].to(torch.int32), ri[pi.long()].to(torch.int32)) for ro, ri, (po, pi) in
-                 self._retry_by_groups(lambda so, si: self._contain_once(so, si, n_chrom), outer, inner, n_chrom)]
-        if not parts:
-            z = torch.empty(0, dtype=torch.int32, device=self.device)
-            return z, z.clone()
-        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+        return self._wide(lambda so, si, _rows: self._contain_once(so, si, n_chrom),
+                          lambda parts: wide.pairs(parts, self.device), outer, inner, n_chrom)
 
     def _contain_once(self, outer: DeviceSide, inner: DeviceSide, n_chrom: int):
         torch = _torch()
@@ -897,24 +796,12 @@ class HipEngine:
         ones 1.  Two int32 device tensors of the exact size, pairs in no particular order;
         ``stats()["join_form"]`` is always ``"general"``.  Every row of both sides needs ``start <= end``:
         :class:`InvertedRows` (a ``ValueError``) tells in ``.sides`` which side does not."""
-        torch = _torch()
         self._check_sides(a, b)
         max_distance = int(max_distance)
         if max_distance < 0:
             raise ValueError("max_distance must be >= 0")
-        try:
-            return self._window_once(a, b, n_chrom, max_distance)
-        except _lib.GiqlHipError as exc:
-            if exc.code != _lib.GIQL_ERR_SPAN:
-                raise
-        # a genome longer than the 32-bit axis: chromosome groups are independent units
-        parts = [(ra[pa.long()].to(torch.int32), rb[pb.long()].to(torch.int32)) for ra, rb, (pa, pb) in
-                 self._retry_by_groups(lambda sa, sb: self._window_once(sa, sb, n_chrom, max_distance), a, b, n_chrom,
-                                       pad=2)]
-        if not parts:
-            z = torch.empty(0, dtype=torch.int32, device=self.device)
-            return z, z.clone()
-        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+        return self._wide(lambda sa, sb, _rows: self._window_once(sa, sb, n_chrom, max_distance),
+                          lambda parts: wide.pairs(parts, self.device), a, b, n_chrom, pad=2)
 
     def _window_once(self, a: DeviceSide, b: DeviceSide, n_chrom: int, max_distance: int):
         torch = _torch()
@@ -972,21 +859,11 @@ class HipEngine:
         """MERGE: ``(chrom, start, end, count)`` tensors of the merged regions ordered by
         (chrom, start) (``src/giql/expanders/merge.py:186-330``).  ``preds``: the ``predicate :=``
         argument, as for :meth:`cluster` (merge.py:201-210 hands it to the CLUSTER underneath)."""
-        torch = _torch()
         if preds:
             self._check_pred_rows(s, preds)
-        try:
-            return self._merge_once(s, n_chrom, distance, preds)
-        except _lib.GiqlHipError as exc:
-            if exc.code != _lib.GIQL_ERR_SPAN:
-                raise
-        parts = [self._merge_once(sub, n_chrom, distance, self._preds_of_rows(preds, rows) if preds else None)
-                 for sub, rows, _sb, _rb in self._groups(s, self._empty_side(s), n_chrom)]
-        if not parts:
-            return self._merge_once(self._empty_side(s), n_chrom, distance)
-        c, st, en, cnt = (torch.cat([p[k] for p in parts]) for k in range(4))
-        order = torch.argsort(c.long() * (1 << 32) + (st.long() + (1 << 31)), stable=True)
-        return c[order], st[order], en[order], cnt[order]
+        return self._wide(
+            lambda sub, _b, rows: self._merge_once(sub, n_chrom, distance, self._preds_of_rows(preds, rows)),
+            lambda parts: wide.merge(parts, self.device), s, None, n_chrom)
 
     def _merge_once(self, s: DeviceSide, n_chrom: int, distance: int, preds=None):
         torch = _torch()

@@ -3,9 +3,10 @@
 All chromosomes share one linear u32 axis (``k_chrom_offsets``, join_kernels.hip.h): key = base[c] + canonical
 coordinate.  Spans summing to at most 2^32 - 1 run on one axis, the sentinel key of irregular rows one past the
 last real key; past that a call returns GIQL_ERR_SPAN and the engine runs it chromosome group by group
-(``HipEngine._groups``).  Each axis class below is built from small seeded tables whose COORDINATES sit at those
-edges, and every test first shows that its class was reached (the span a call reports, or GIQL_ERR_SPAN from the
-C ABI), so a later change of layout cannot quietly turn it into a test of something easier.
+(``HipEngine._wide`` over ``HipEngine._groups``; the groups' results are put together by ``giql_amd/wide.py``, whose
+functions tests/test_wide_combine.py checks without a GPU).  Each axis class below is built from small seeded tables
+whose COORDINATES sit at those edges, and every test first shows that its class was reached (the span a call reports,
+or GIQL_ERR_SPAN from the C ABI), so a later change of layout cannot quietly turn it into a test of something easier.
 
 Classes (canonical [lo, hi] per chromosome; span = hi - lo + 1):
   tight_top       [0, 2^31-1] + [1, 2^31-1]: exactly 2^32 - 1, real keys up to 0xFFFFFFFE next to the sentinel
@@ -197,6 +198,22 @@ def test_inner_uniform_form(eng, name, enc):
         assert eng.stats()["join_form"] in ("uniform_a", "uniform_b")
     want = ora.sort_pairs(*ora.c_inner(a, b))
     assert want.shape[0] > 500 and np.array_equal(ora.sort_pairs(host(ra), host(rb)), want)
+
+
+# ------------------------------------------------------------ LEFT OUTER
+@pytest.mark.parametrize("enc", ENCODINGS, ids=lambda e: e[0])
+@pytest.mark.parametrize("name", sorted(GROUPED))
+def test_left_join_by_chromosome_groups(eng, name, enc):
+    """The groups' pairs come back in tensors of exactly their length: ``left_join`` pads a copy with room."""
+    import _left_ref as R
+
+    a = make_side(name, enc, 2500, 23, irregular=150)
+    b = make_side(name, enc, 4000, 24, irregular=150)
+    da, db, n = reach(eng, name, a, b)
+    ra, rb = eng.left_join(da, db, n)
+    want = R.left_rows(a, b)
+    assert (want[:, 1] >= 0).sum() > 1000 and (want[:, 1] < 0).sum() > 100
+    assert ra.dtype == rb.dtype == torch.int32 and np.array_equal(R.sort_rows(host(ra), host(rb)), want)
 
 
 # -------------------------------------------------------------- NEAREST
