@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <atomic>
+#include <memory>
 #include <sys/mman.h>
 #include <utility>
 #if defined(__SSE2__)
@@ -66,6 +67,8 @@ static int set_err(int code, const char* fmt, ...) {
     int _rc = (expr);       \
     if (_rc != GIQL_OK) return _rc; \
   } while (0)
+
+#include "owned_memory.h"  // (after set_err / HIP_TRY: its buffers report through them)
 
 // tile shapes per class: class 1 = many queries with ~0.5 match each (B rows as
 // queries), class 2 = fewer queries with tens of matches each (A rows)
@@ -273,24 +276,19 @@ struct giql_hip_ctx {
   // device resources
   int device = 0;
   int n_cu = 256;             // compute units of the device
-  char* arena = nullptr;
-  size_t arena_cap = 0;
-  DevMeta* d_meta = nullptr;
-  DevMeta* h_meta = nullptr;  // pinned
-  u32* part = nullptr;        // fill partition (grown on demand)
-  size_t part_cap = 0;        // (bytes)
-  void* stage_out = nullptr;  // device staging of the host-buffer entry points' outputs (grown on demand)
-  size_t stage_out_cap = 0;
-  char* xplan = nullptr;      // scratch of giql_hip_fill_from_plan_dev (offsets + scan partials), grown on demand
-  size_t xplan_cap = 0;
-  char* ct_buf = nullptr;     // per-tile arrays of a CONTAINS plan (sized by its candidate total), grown on demand
-  size_t ct_buf_cap = 0;
-  u64* d_scratch64 = nullptr;  // small device scratch (checksum)
+  DevArray<char> arena;       // the workspace (grown on demand; its bytes() are stats.workspace_bytes)
+  DevArray<DevMeta> d_meta;
+  DevMeta* h_meta = nullptr;  // pinned (released by giql_hip_destroy)
+  DevArray<u32> part;         // fill partition (grown on demand)
+  DevBuf stage_out;           // device staging of the host-buffer entry points' outputs (grown on demand)
+  DevArray<char> xplan;       // scratch of giql_hip_fill_from_plan_dev (offsets + scan partials), grown on demand
+  DevArray<char> ct_buf;      // per-tile arrays of a CONTAINS plan (sized by its candidate total), grown on demand
+  DevArray<u64> d_scratch64;  // small device scratch (checksum)
   hipStream_t side_stream = nullptr;  // the second stream (SideChain)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  u32* bucket_qwin = nullptr;  // [2 * BS_MAX_BUCKETS] query window per bucket
-  u32* bucket_bnd = nullptr;   // [BS_MAX_BUCKETS + 1] bucket boundaries of the sort in flight
-  u32* bucket_big = nullptr;   // [1 + BS_MAX_BUCKETS] buckets too large for LDS, queued for k_bucket_sort_big ([0] = count)
+  DevArray<u32> bucket_qwin;  // [2 * BS_MAX_BUCKETS] query window per bucket
+  DevArray<u32> bucket_bnd;   // [BS_MAX_BUCKETS + 1] bucket boundaries of the sort in flight
+  DevArray<u32> bucket_big;   // [1 + BS_MAX_BUCKETS] buckets too large for LDS, queued for k_bucket_sort_big ([0] = count)
 
   // profiling
   int profiling = 0;          // 0 off, 1 every phase, 2 only profile_phase (the dominant kernel's)
@@ -317,36 +315,20 @@ struct Carver {
   }
 };
 
-// A device buffer grown on demand: at least `need` bytes, `want` of them when it has to grow (the buffer's slack).
-// The old one may still be read by work on `stream`; it is freed after that work.
-static int grow_buffer(void** buf, size_t* cap, size_t need, size_t want, hipStream_t stream, const char* what) {
-  if (need <= *cap) return GIQL_OK;
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (*buf) HIP_TRY(hipFree(*buf));
-  *buf = nullptr;
-  *cap = 0;
-  const hipError_t e = hipMalloc(buf, want);
-  if (e != hipSuccess)
-    return set_err(GIQL_ERR_NOMEM, "hipMalloc(%zu bytes) for %s failed: %s", want, what, hipGetErrorString(e));
-  *cap = want;
-  return GIQL_OK;
-}
-
 static int ensure_arena(giql_hip_ctx* ctx, size_t bytes, hipStream_t stream) {
-  if (bytes <= ctx->arena_cap) return GIQL_OK;
+  if (bytes <= ctx->arena.bytes()) return GIQL_OK;
   ctx->plan.planned = false;  // (giql_hip_reserve: a new arena holds no plan)
   ctx->dj.planned = false;
   ctx->ct.planned = false;
   const size_t want = align_up(bytes + bytes / 8, (size_t)1 << 20);
-  GIQL_TRY(grow_buffer((void**)&ctx->arena, &ctx->arena_cap, bytes, want, stream, "the workspace"));
-  if (getenv("GIQL_HIP_DEBUG_ADDR")) fprintf(stderr, "[giql_hip] arena %p + %zu bytes\n", (void*)ctx->arena, want);
+  GIQL_TRY(ctx->arena.grow(bytes, want, stream, "the workspace"));
+  if (getenv("GIQL_HIP_DEBUG_ADDR")) fprintf(stderr, "[giql_hip] arena %p + %zu bytes\n", ctx->arena.get(), want);
   return GIQL_OK;
 }
 
 // the fill's merge-path partition: at least `words` entries
 static int grow_part(giql_hip_ctx* ctx, size_t words, hipStream_t stream) {
-  return grow_buffer((void**)&ctx->part, &ctx->part_cap, words * sizeof(u32), (words + words / 4) * sizeof(u32), stream,
-                     "the fill partition");
+  return ctx->part.grow(words * sizeof(u32), (words + words / 4) * sizeof(u32), stream, "the fill partition");
 }
 
 // The workspace of a call: `carve` lays its buffers out from a base (nullptr: a dry run that returns the size), once
@@ -495,6 +477,18 @@ static int run_scan(giql_hip_ctx* ctx, hipStream_t st, int phase, const u32* in,
   hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, st, bsums, nb, total_out, total_out2);
   hipLaunchKernelGGL((k_scan_down<TOut>), dim3(nb), dim3(SCAN_NT), 0, st, in, n, bsums, out);
   return post_launch("scan");
+}
+
+// The scan of 0/1 flags with the compaction in its down-sweep (SEMI / ANTI): the ids of the set flags, ascending, into
+// rows_out; their number into DevMeta::n_out.  `spine_out`: where the spine leaves its exclusive block offsets.
+static int run_scan_compact(giql_hip_ctx* ctx, hipStream_t st, const u32* flag, size_t n, u64* bsums, u64* spine_out,
+                            int32_t* rows_out, const char* what) {
+  const u32 nbk = cdiv(n, SCAN_TILE);
+  Phase ph(ctx, st, GIQL_PH_SCAN, 3);
+  hipLaunchKernelGGL(k_scan_reduce, dim3(nbk), dim3(SCAN_NT), 0, st, flag, (u64)n, bsums);
+  hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, st, bsums, nbk, spine_out, &ctx->d_meta->n_out);
+  hipLaunchKernelGGL(k_scan_down_compact, dim3(nbk), dim3(SCAN_NT), 0, st, flag, (u64)n, bsums, rows_out);
+  return post_launch(what);
 }
 
 // The same over counts given as two bounds per row (cnt = hi - lo below the regular prefix, 0 past it):
@@ -1269,18 +1263,19 @@ int giql_hip_create(int device, giql_hip_ctx** out) {
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
       ctx->n_cu = prop.multiProcessorCount;
   }
-  hipError_t e = hipMalloc((void**)&ctx->d_meta, sizeof(DevMeta));
-  if (e == hipSuccess) e = hipHostMalloc((void**)&ctx->h_meta, sizeof(DevMeta), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_scratch64, 64);
-  if (e == hipSuccess &&
+  bool ok = ctx->d_meta.alloc(sizeof(DevMeta)) == GIQL_OK &&
+            hipHostMalloc((void**)&ctx->h_meta, sizeof(DevMeta), hipHostMallocDefault) == hipSuccess &&
+            ctx->d_scratch64.alloc(64) == GIQL_OK;
+  if (ok &&
       (hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking) != hipSuccess ||
        hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
        hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess))
     ctx->side_stream = nullptr;  // no second stream: everything stays on the caller's
-  if (e == hipSuccess) e = hipMalloc((void**)&ctx->bucket_bnd, ((size_t)BS_MAX_BUCKETS + 16) * sizeof(u32));
-  if (e == hipSuccess) e = hipMalloc((void**)&ctx->bucket_big, ((size_t)BS_MAX_BUCKETS + 16) * sizeof(u32));
-  if (e == hipSuccess) e = hipMalloc((void**)&ctx->bucket_qwin, ((size_t)2 * BS_MAX_BUCKETS + 16) * sizeof(u32));
-  if (e != hipSuccess) {
+  ok = ok && ctx->bucket_bnd.alloc(((size_t)BS_MAX_BUCKETS + 16) * sizeof(u32)) == GIQL_OK &&
+       ctx->bucket_big.alloc(((size_t)BS_MAX_BUCKETS + 16) * sizeof(u32)) == GIQL_OK &&
+       ctx->bucket_qwin.alloc(((size_t)2 * BS_MAX_BUCKETS + 16) * sizeof(u32)) == GIQL_OK;
+  if (!ok) {
+    const hipError_t e = hipGetLastError();  // (of the allocation that failed: nothing was called after it)
     giql_hip_destroy(ctx);
     return set_err(GIQL_ERR_HIP, "context allocation failed: %s", hipGetErrorString(e));
   }
@@ -1293,21 +1288,11 @@ int giql_hip_destroy(giql_hip_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)hipDeviceSynchronize();
   for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
-  if (ctx->arena) (void)hipFree(ctx->arena);
-  if (ctx->part) (void)hipFree(ctx->part);
-  if (ctx->stage_out) (void)hipFree(ctx->stage_out);
-  if (ctx->d_meta) (void)hipFree(ctx->d_meta);
-  if (ctx->d_scratch64) (void)hipFree(ctx->d_scratch64);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
-  if (ctx->bucket_bnd) (void)hipFree(ctx->bucket_bnd);
-  if (ctx->bucket_big) (void)hipFree(ctx->bucket_big);
-  if (ctx->bucket_qwin) (void)hipFree(ctx->bucket_qwin);
-  if (ctx->xplan) (void)hipFree(ctx->xplan);
-  if (ctx->ct_buf) (void)hipFree(ctx->ct_buf);
   if (ctx->h_meta) (void)hipHostFree(ctx->h_meta);
-  delete ctx;
+  delete ctx;  // (the device buffers go with it)
   return GIQL_OK;
 }
 
@@ -1336,7 +1321,7 @@ int giql_hip_get_stats(giql_hip_ctx* ctx, giql_hip_stats* out) {
     HIP_TRY(hipEventSynchronize(ctx->spans.back().b));
     collect_spans(ctx);
   }
-  ctx->stats.workspace_bytes = (int64_t)ctx->arena_cap;
+  ctx->stats.workspace_bytes = (int64_t)ctx->arena.bytes();
   *out = ctx->stats;
   // byte 0: join form (+ bit 5: a side was sorted in three stages, bit 6: this context fell back to
   // the four-pass sort for good); byte 1: sort tile order in force; bits 16-26: order fallbacks so far; bits 27-28:
@@ -1714,7 +1699,7 @@ static int plan_uniform(giql_hip_ctx* ctx, hipStream_t st, int n_chrom, PlanSide
   static_assert((T2 & (T2 - 1)) == 0, "fill tiles are a power of two (k_scan_chain_diff shifts)");
   const u64 nt_cap64 = (ctx->plan.fuse_cap + T2 - 1) / T2;
   const bool offered = Q.out_row && T.no_irr && ctx->plan.fuse_cap > 0;
-  T.early_fill = offered && nt_cap64 <= 0x7FFFFFF0ull && ((size_t)nt_cap64 + 2) * sizeof(u32) <= ctx->part_cap;
+  T.early_fill = offered && nt_cap64 <= 0x7FFFFFF0ull && ((size_t)nt_cap64 + 2) * sizeof(u32) <= ctx->part.bytes();
   // ... and, when the other side's bucket stage answers the bounds anyway, the pairs are written right there
   // (bucket_sort.hip.h, FUSE == 2) -- as long as the query windows stay well inside what a block holds in
   // registers: a window covers the query buckets (coarsely grouped: whole 65536-key buckets) that a bucket's
@@ -2382,35 +2367,32 @@ struct giql_hip_index {
   u64 span = 0;
   u32 sentinel = 0;        // one past the largest key of the axis
   int wbits = 16;          // key bits of a bucket (16; 15 / 14 / 13 for tables past ~2,800 rows per 65,536 positions)
-  u32 *key = nullptr, *end = nullptr, *rid = nullptr;   // [n] sorted by key (every bucket sorted in place)
-  u32* small = nullptr;    // the sort's digit offsets gbase[4][256] | first[n_chrom + 1]: chromosome c owns keys [first[c], first[c + 1])
-  size_t bytes = 0;
+  DevArray<u32> key, end, rid;  // [n] sorted by key (every bucket sorted in place)
+  DevArray<u32> small;     // the sort's digit offsets gbase[4][256] | first[n_chrom + 1]: chromosome c owns keys [first[c], first[c + 1])
   // what the per-row operators read (giql_hip_index_prepare_rows_dev: built on their first call, never at creation)
   bool rows_ready = false;
-  u32* bnd_key = nullptr;     // [2^(32 - wbits) + 1] directory over key: first row with key >= v << wbits
-  u32* end_sorted = nullptr;  // general form: [n] the end keys alone, sorted ...
-  u32* bnd_end = nullptr;     // ... and their directory
+  DevArray<u32> bnd_key;      // [2^(32 - wbits) + 1] directory over key: first row with key >= v << wbits
+  DevArray<u32> end_sorted;   // general form: [n] the end keys alone, sorted ...
+  DevArray<u32> bnd_end;      // ... and their directory
   // what NEAREST reads (giql_hip_index_prepare_nearest_dev: on its first call, never at creation) beside bnd_key,
   // which either preparation builds and the other finds here
   int nearest_state = 0;      // 0: not prepared; 1: ready; -1: the table does not take the NEAREST form (remembered)
-  u32* chrom_lo = nullptr;    // [n_chrom + 1] rank of first[c] among the keys
-  u32* nr_rid = nullptr;      // general form: [n] the row ids in (start, end) order ...
-  u32* nr_pmax = nullptr;     // ... and the prefix max of the end keys in that order
+  DevArray<u32> chrom_lo;     // [n_chrom + 1] rank of first[c] among the keys
+  DevArray<u32> nr_rid;       // general form: [n] the row ids in (start, end) order ...
+  DevArray<u32> nr_pmax;      // ... and the prefix max of the end keys in that order
+  // what giql_hip_index_info reports: the arrays the index owns at this moment (a preparation moves its arrays in as
+  // its last step, so one that declined or failed has added nothing)
+  size_t bytes() const {
+    size_t sum = 0;
+    for (const DevArray<u32>* b : {&key, &end, &rid, &small, &bnd_key, &end_sorted, &bnd_end, &chrom_lo, &nr_rid, &nr_pmax})
+      sum += b->bytes();
+    return sum;
+  }
 };
 
 int giql_hip_index_destroy(giql_hip_index* idx) {
   if (!idx) return GIQL_OK;
   (void)hipSetDevice(idx->device);
-  if (idx->key) (void)hipFree(idx->key);
-  if (idx->end) (void)hipFree(idx->end);
-  if (idx->rid) (void)hipFree(idx->rid);
-  if (idx->small) (void)hipFree(idx->small);
-  if (idx->bnd_key) (void)hipFree(idx->bnd_key);
-  if (idx->end_sorted) (void)hipFree(idx->end_sorted);
-  if (idx->bnd_end) (void)hipFree(idx->bnd_end);
-  if (idx->chrom_lo) (void)hipFree(idx->chrom_lo);
-  if (idx->nr_rid) (void)hipFree(idx->nr_rid);
-  if (idx->nr_pmax) (void)hipFree(idx->nr_pmax);
   delete idx;
   return GIQL_OK;
 }
@@ -2418,7 +2400,7 @@ int giql_hip_index_destroy(giql_hip_index* idx) {
 int giql_hip_index_info(const giql_hip_index* idx, int64_t* n_rows, int64_t* bytes, int32_t* general, int64_t* span) {
   if (!idx) return set_err(GIQL_ERR_INVALID, "index is NULL");
   if (n_rows) *n_rows = idx->n;
-  if (bytes) *bytes = (int64_t)idx->bytes;
+  if (bytes) *bytes = (int64_t)idx->bytes();
   if (general) *general = idx->general ? 1 : 0;
   if (span) *span = (int64_t)idx->span;
   return GIQL_OK;
@@ -2459,14 +2441,8 @@ int giql_hip_index_create_dev(giql_hip_ctx* ctx, const giql_side* side, int32_t 
     return c.off;
   };
   GIQL_TRY(claim_arena(ctx, st, carve));
-  giql_hip_index* idx = new (std::nothrow) giql_hip_index();
+  std::unique_ptr<giql_hip_index> idx(new (std::nothrow) giql_hip_index());  // released on every early way out
   if (!idx) return set_err(GIQL_ERR_NOMEM, "out of host memory");
-  struct Fail {  // released on every early way out
-    giql_hip_index* p;
-    ~Fail() {
-      if (p) giql_hip_index_destroy(p);
-    }
-  } guard{idx};
   PrezeroGuard prezero_guard{ctx};
   idx->device = ctx->device;
   idx->n = (u32)n;
@@ -2499,11 +2475,10 @@ int giql_hip_index_create_dev(giql_hip_ctx* ctx, const giql_side* side, int32_t 
   idx->len_max = m.len_max_b;
   idx->span = m.total_span;
   idx->sentinel = m.sentinel;
-  HIP_TRY(hipMalloc((void**)&idx->key, n * sizeof(u32)));
-  HIP_TRY(hipMalloc((void**)&idx->rid, n * sizeof(u32)));
-  if (idx->general) HIP_TRY(hipMalloc((void**)&idx->end, n * sizeof(u32)));
-  HIP_TRY(hipMalloc((void**)&idx->small, (1024 + (size_t)n_chrom + 1) * sizeof(u32)));
-  idx->bytes = n * sizeof(u32) * (idx->general ? 3 : 2) + (1024 + (size_t)n_chrom + 1) * sizeof(u32);
+  GIQL_TRY(idx->key.alloc(n * sizeof(u32)));
+  GIQL_TRY(idx->rid.alloc(n * sizeof(u32)));
+  if (idx->general) GIQL_TRY(idx->end.alloc(n * sizeof(u32)));
+  GIQL_TRY(idx->small.alloc((1024 + (size_t)n_chrom + 1) * sizeof(u32)));
   GIQL_TRY(span_digit_offsets(ctx, st, lb, hist, gbase, nullptr, nullptr, "digit offsets (index)"));
   SortBufs sb = scratch;
   sb.key[0] = idx->key;
@@ -2532,8 +2507,7 @@ int giql_hip_index_create_dev(giql_hip_ctx* ctx, const giql_side* side, int32_t 
   collect_spans(ctx);
   ctx->stats.n_b = side->n;
   ctx->stats.span = (int64_t)idx->span;
-  guard.p = nullptr;
-  *out = idx;
+  *out = idx.release();
   return GIQL_OK;
 }
 
@@ -2656,21 +2630,16 @@ static int64_t index_directory_bytes(const giql_hip_index* idx) {
 static int index_ensure_key_directory(giql_hip_ctx* ctx, giql_hip_index* idx, hipStream_t st) {
   if (idx->bnd_key) return GIQL_OK;
   const size_t n_cells = (size_t)bs_n_buckets((u32)idx->wbits) + 1;
-  u32* bnd = nullptr;
-  HIP_TRY(hipMalloc((void**)&bnd, n_cells * sizeof(u32)));
+  DevArray<u32> bnd;
+  GIQL_TRY(bnd.alloc(n_cells * sizeof(u32)));
   {
     Phase ph(ctx, st, GIQL_PH_AUX);
     ctx->stats.phase_bytes[GIQL_PH_AUX] += index_directory_bytes(idx);
     hipLaunchKernelGGL(k_bucket_bounds, dim3(cdiv(n_cells, 256)), dim3(256), 0, st, idx->key, idx->n,
                        idx->small + 3 * OS_BINS, bnd, (u32)idx->wbits);
-    const int rc = post_launch("start directory (index)");
-    if (rc != GIQL_OK) {
-      (void)hipFree(bnd);
-      return rc;
-    }
+    GIQL_TRY(post_launch("start directory (index)"));
   }
-  idx->bnd_key = bnd;
-  idx->bytes += n_cells * sizeof(u32);
+  idx->bnd_key = std::move(bnd);
   return GIQL_OK;
 }
 
@@ -2678,20 +2647,12 @@ static int index_prepare_rows_core(giql_hip_ctx* ctx, giql_hip_index* idx, hipSt
   const size_t n = idx->n;
   const u32 wbits = (u32)idx->wbits;
   const size_t n_cells = (size_t)bs_n_buckets(wbits) + 1;
-  struct Built {  // released on every early way out
-    u32 *end_sorted = nullptr, *bnd_end = nullptr;
-    ~Built() {
-      if (end_sorted) (void)hipFree(end_sorted);
-      if (bnd_end) (void)hipFree(bnd_end);
-    }
-  } w;
-  size_t added = 0;
+  DevArray<u32> end_sorted, bnd_end;  // built here (released on every early way out), moved into the index last
   GIQL_TRY(index_ensure_key_directory(ctx, idx, st));
   const int64_t dir_bytes = index_directory_bytes(idx);
   if (idx->general) {
-    HIP_TRY(hipMalloc((void**)&w.end_sorted, n * sizeof(u32)));
-    HIP_TRY(hipMalloc((void**)&w.bnd_end, n_cells * sizeof(u32)));
-    added += n * sizeof(u32) + n_cells * sizeof(u32);
+    GIQL_TRY(end_sorted.alloc(n * sizeof(u32)));
+    GIQL_TRY(bnd_end.alloc(n_cells * sizeof(u32)));
     SortBufs se;  // a keys-only sort: buffer 0 = the index's new array, buffer 1 in the arena
     u32 *hist = nullptr, *gbase = nullptr, *status = nullptr;
     auto carve = [&](char* base) {
@@ -2703,13 +2664,13 @@ static int index_prepare_rows_core(giql_hip_ctx* ctx, giql_hip_index* idx, hipSt
       return c.off;
     };
     GIQL_TRY(claim_arena(ctx, st, carve));
-    se.key[0] = w.end_sorted;
+    se.key[0] = end_sorted;
     se.end[0] = se.end[1] = se.rid[0] = se.rid[1] = nullptr;
     HIP_TRY(hipMemsetAsync(hist, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
     {
       Phase ph(ctx, st, GIQL_PH_AUX);  // the copy of the end keys the sort starts from: read once, written once
       ctx->stats.phase_bytes[GIQL_PH_AUX] += (int64_t)8 * n;
-      HIP_TRY(hipMemcpyAsync(w.end_sorted, idx->end, n * sizeof(u32), hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(end_sorted, idx->end, n * sizeof(u32), hipMemcpyDeviceToDevice, st));
     }
     {
       Phase ph(ctx, st, GIQL_PH_SORT_HIST, 3);  // the end keys' digit histogram: every key read once
@@ -2725,21 +2686,19 @@ static int index_prepare_rows_core(giql_hip_ctx* ctx, giql_hip_index* idx, hipSt
       ForceLocal global_only{ctx, -1};  // four global passes: the result is back in buffer 0
       GIQL_TRY(run_sort_onesweep(ctx, st, se, (u32)n, gbase, status));
     }
-    if (se.key[0] != w.end_sorted) return set_err(GIQL_ERR_HIP, "internal: the sort did not end in the index's buffer");
+    if (se.key[0] != end_sorted) return set_err(GIQL_ERR_HIP, "internal: the sort did not end in the index's buffer");
     {
       Phase ph(ctx, st, GIQL_PH_AUX);
       ctx->stats.phase_bytes[GIQL_PH_AUX] += dir_bytes;
-      hipLaunchKernelGGL(k_bucket_bounds, dim3(cdiv(n_cells, 256)), dim3(256), 0, st, w.end_sorted, (u32)n,
-                         gbase + 3 * OS_BINS, w.bnd_end, wbits);
+      hipLaunchKernelGGL(k_bucket_bounds, dim3(cdiv(n_cells, 256)), dim3(256), 0, st, end_sorted, (u32)n,
+                         gbase + 3 * OS_BINS, bnd_end, wbits);
       GIQL_TRY(post_launch("end directory (index)"));
     }
     GIQL_TRY(read_meta(ctx, st));  // (a look-back timeout of the sort; synchronises the stream)
   } else {
     HIP_TRY(hipStreamSynchronize(st));
   }
-  idx->end_sorted = w.end_sorted, idx->bnd_end = w.bnd_end;
-  w.end_sorted = w.bnd_end = nullptr;
-  idx->bytes += added;
+  idx->end_sorted = std::move(end_sorted), idx->bnd_end = std::move(bnd_end);
   idx->rows_ready = true;
   return GIQL_OK;
 }
@@ -2791,16 +2750,20 @@ static int64_t index_rows_bytes(const giql_hip_index* idx, size_t na, int out_by
   return (int64_t)na * (12 + out_bytes + 2 * (8 + 4 * steps));
 }
 
-// The prologue the two row operators share: checks, begin_call, the sizes, the index's row arrays.
-static int begin_index_rows_call(giql_hip_ctx* ctx, giql_hip_index* idx, const giql_side* a, hipStream_t st) {
+// The prologue COUNT / SEMI / ANTI / NEAREST against an index share: checks, begin_call, the sizes, then `prepare`
+// (index_prepare_rows / index_prepare_nearest: what the operator reads of the index) unless the query is empty.
+static int index_prepare_nearest(giql_hip_ctx* ctx, giql_hip_index* idx, hipStream_t st);
+static int begin_indexed_call(giql_hip_ctx* ctx, giql_hip_index* idx, const giql_side* a, hipStream_t st,
+                              int (*prepare)(giql_hip_ctx*, giql_hip_index*, hipStream_t), size_t max_rows = SIZE_MAX) {
   GIQL_TRY(check_index_call(ctx, idx));
   GIQL_TRY(check_side(a, "a"));
+  if ((size_t)a->n > max_rows) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
   GIQL_TRY(begin_call(ctx));
   ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   ctx->stats.n_a = a->n;
   ctx->stats.n_b = idx->n;
   if (a->n == 0) return GIQL_OK;
-  return index_prepare_rows(ctx, idx, st);
+  return prepare(ctx, idx, st);
 }
 
 static int finish_index_rows_call(giql_hip_ctx* ctx, const giql_hip_index* idx, hipStream_t st) {
@@ -2816,7 +2779,7 @@ static int finish_index_rows_call(giql_hip_ctx* ctx, const giql_hip_index* idx, 
 int giql_hip_count_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const giql_side* a, int64_t* counts_out,
                                void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  GIQL_TRY(begin_index_rows_call(ctx, idx, a, st));
+  GIQL_TRY(begin_indexed_call(ctx, idx, a, st, index_prepare_rows));
   if (a->n == 0) return GIQL_OK;
   if (!counts_out) return set_err(GIQL_ERR_INVALID, "counts_out is NULL");
   const size_t na = (size_t)a->n;
@@ -2838,7 +2801,7 @@ int giql_hip_semi_anti_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const
                                    int32_t* rows_out, int64_t* n_out, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (ctx && idx && !n_out) return set_err(GIQL_ERR_INVALID, "n_out is NULL");
-  GIQL_TRY(begin_index_rows_call(ctx, idx, a, st));
+  GIQL_TRY(begin_indexed_call(ctx, idx, a, st, index_prepare_rows));
   *n_out = 0;
   if (a->n == 0) return GIQL_OK;
   if (!rows_out) return set_err(GIQL_ERR_INVALID, "rows_out is NULL");
@@ -2860,15 +2823,8 @@ int giql_hip_semi_anti_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const
                        a->start_off, a->end_off, rows_view_of(idx), anti, (i64*)nullptr, flag, &ctx->d_meta->aux0);
     GIQL_TRY(post_launch("semi flags (index)"));
   }
-  {
-    // the scan of the flags with the compaction in its down-sweep, as giql_hip_semi_anti_dev runs it
-    const u32 nbk = cdiv(na, SCAN_TILE);
-    Phase ph(ctx, st, GIQL_PH_SCAN, 3);
-    hipLaunchKernelGGL(k_scan_reduce, dim3(nbk), dim3(SCAN_NT), 0, st, flag, (u64)na, bsums);
-    hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, st, bsums, nbk, bsums + nbk + 1, &ctx->d_meta->n_out);
-    hipLaunchKernelGGL(k_scan_down_compact, dim3(nbk), dim3(SCAN_NT), 0, st, flag, (u64)na, bsums, rows_out);
-    GIQL_TRY(post_launch("scan + compact (index)"));
-  }
+  // as giql_hip_semi_anti_dev runs it
+  GIQL_TRY(run_scan_compact(ctx, st, flag, na, bsums, bsums + cdiv(na, SCAN_TILE) + 1, rows_out, "scan + compact (index)"));
   GIQL_TRY(finish_index_rows_call(ctx, idx, st));
   *n_out = (int64_t)ctx->h_meta->n_out;
   ctx->stats.n_out = *n_out;
@@ -2894,15 +2850,7 @@ static int index_prepare_nearest(giql_hip_ctx* ctx, giql_hip_index* idx, hipStre
   if (idx->nearest_state > 0) return GIQL_OK;
   if (idx->nearest_state < 0) return index_nearest_declined();
   const size_t n = idx->n;
-  struct Built {  // released on every early way out
-    u32 *chrom_lo = nullptr, *nr_rid = nullptr, *nr_pmax = nullptr;
-    ~Built() {
-      if (chrom_lo) (void)hipFree(chrom_lo);
-      if (nr_rid) (void)hipFree(nr_rid);
-      if (nr_pmax) (void)hipFree(nr_pmax);
-    }
-  } w;
-  size_t added = 0;
+  DevArray<u32> chrom_lo, nr_rid, nr_pmax;  // built here (released on every early way out), moved into the index last
   if (idx->general) {
     u32 *ends = nullptr, *bmax = nullptr;
     auto carve = [&](char* base) {
@@ -2912,40 +2860,36 @@ static int index_prepare_nearest(giql_hip_ctx* ctx, giql_hip_index* idx, hipStre
       return c.off;
     };
     GIQL_TRY(claim_arena(ctx, st, carve));
-    HIP_TRY(hipMalloc((void**)&w.nr_rid, n * sizeof(u32)));
-    HIP_TRY(hipMalloc((void**)&w.nr_pmax, n * sizeof(u32)));
-    added += 2 * n * sizeof(u32);
+    GIQL_TRY(nr_rid.alloc(n * sizeof(u32)));
+    GIQL_TRY(nr_pmax.alloc(n * sizeof(u32)));
     HIP_TRY(hipMemsetAsync(ctx->d_meta, 0, sizeof(DevMeta), st));
     {
       Phase ph(ctx, st, GIQL_PH_AUX);  // the copies the tie fix works on (read once, written once), the run heads' pass
       ctx->stats.phase_bytes[GIQL_PH_AUX] += (int64_t)(16 + 4) * n;
       HIP_TRY(hipMemcpyAsync(ends, idx->end, n * sizeof(u32), hipMemcpyDeviceToDevice, st));
-      HIP_TRY(hipMemcpyAsync(w.nr_rid, idx->rid, n * sizeof(u32), hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(k_fix_start_ties, dim3(cdiv(n, 256)), dim3(256), 0, st, idx->key, ends, w.nr_rid, (u32)n,
+      HIP_TRY(hipMemcpyAsync(nr_rid, idx->rid, n * sizeof(u32), hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL(k_fix_start_ties, dim3(cdiv(n, 256)), dim3(256), 0, st, idx->key, ends, nr_rid, (u32)n,
                          ctx->d_meta);
       GIQL_TRY(post_launch("start ties (index)"));
     }
     ctx->stats.phase_bytes[GIQL_PH_AUX] += (int64_t)12 * n;  // the prefix max: read twice, written once
-    GIQL_TRY(run_pmax(ctx, st, ends, (u32)n, w.nr_pmax, bmax));
+    GIQL_TRY(run_pmax(ctx, st, ends, (u32)n, nr_pmax, bmax));
     GIQL_TRY(read_meta(ctx, st));
     if (ctx->h_meta->aux0 != 0) {
-      idx->nearest_state = -1;  // (w's arrays are released: the index keeps nothing of the attempt)
+      idx->nearest_state = -1;  // (the arrays built so far are released: the index keeps nothing of the attempt)
       return index_nearest_declined();
     }
   }
   GIQL_TRY(index_ensure_key_directory(ctx, idx, st));
-  HIP_TRY(hipMalloc((void**)&w.chrom_lo, ((size_t)idx->n_chrom + 1) * sizeof(u32)));
-  added += ((size_t)idx->n_chrom + 1) * sizeof(u32);
+  GIQL_TRY(chrom_lo.alloc(((size_t)idx->n_chrom + 1) * sizeof(u32)));
   {
     Phase ph(ctx, st, GIQL_PH_AUX);
     hipLaunchKernelGGL(k_chrom_bounds, dim3(cdiv((u64)idx->n_chrom + 1, 256)), dim3(256), 0, st, idx->small + 1024,
-                       idx->n_chrom, idx->key, (u32)n, w.chrom_lo);
+                       idx->n_chrom, idx->key, (u32)n, chrom_lo);
     GIQL_TRY(post_launch("chromosome ranks (index)"));
   }
   HIP_TRY(hipStreamSynchronize(st));
-  idx->chrom_lo = w.chrom_lo, idx->nr_rid = w.nr_rid, idx->nr_pmax = w.nr_pmax;
-  w.chrom_lo = w.nr_rid = w.nr_pmax = nullptr;
-  idx->bytes += added;
+  idx->chrom_lo = std::move(chrom_lo), idx->nr_rid = std::move(nr_rid), idx->nr_pmax = std::move(nr_pmax);
   idx->nearest_state = 1;
   return GIQL_OK;
 }
@@ -2970,15 +2914,8 @@ int giql_hip_nearest_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const g
   hipStream_t st = (hipStream_t)stream;
   if (!ctx || !idx) return set_err(GIQL_ERR_INVALID, "ctx/index is NULL");
   if (!idx_b_out || !dist_out) return set_err(GIQL_ERR_INVALID, "idx_b_out/dist_out is NULL");
-  GIQL_TRY(check_index_call(ctx, idx));
-  GIQL_TRY(check_side(a, "a"));
-  if ((size_t)a->n > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
-  GIQL_TRY(begin_call(ctx));
-  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
-  ctx->stats.n_a = a->n;
-  ctx->stats.n_b = idx->n;
+  GIQL_TRY(begin_indexed_call(ctx, idx, a, st, index_prepare_nearest, OS_MAX_ROWS));
   if (a->n == 0) return GIQL_OK;
-  GIQL_TRY(index_prepare_nearest(ctx, idx, st));
   const size_t na = (size_t)a->n;
   GIQL_TRY(claim_arena(ctx, st, [](char*) { return (size_t)0; }));
   HIP_TRY(hipMemsetAsync(ctx->d_meta, 0, sizeof(DevMeta), st));
@@ -3129,16 +3066,9 @@ static int giql_hip_semi_anti_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
                          sa.rid[0], (u32)na, ctx->d_meta, sbb.key[0], pmax, (u32)nb, anti, flag);
     GIQL_TRY(post_launch("semi flags"));
   }
-  {
-    // scan of the flags with the compaction in its down-sweep, the count straight into DevMeta::n_out
-    // (three launches; were five: scan x 3, a device-to-device copy of the total, compact)
-    const u32 nbk = cdiv(na, SCAN_TILE);
-    Phase ph(ctx, st, GIQL_PH_SCAN, 3);
-    hipLaunchKernelGGL(k_scan_reduce, dim3(nbk), dim3(SCAN_NT), 0, st, flag, (u64)na, bsums);
-    hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, st, bsums, nbk, off + na, &ctx->d_meta->n_out);
-    hipLaunchKernelGGL(k_scan_down_compact, dim3(nbk), dim3(SCAN_NT), 0, st, flag, (u64)na, bsums, rows_out);
-    GIQL_TRY(post_launch("scan + compact"));
-  }
+  // the count straight into DevMeta::n_out (three launches; were five: scan x 3, a device-to-device copy of the
+  // total, compact)
+  GIQL_TRY(run_scan_compact(ctx, st, flag, na, bsums, off + na, rows_out, "scan + compact"));
   GIQL_TRY(read_meta(ctx, st));
   if (nb > 0 && !row_form_settled(ctx, uni_len, speculated))  // B is not fixed-length after all
     return GIQL_STATUS_GUESS_MISSED;
@@ -4072,7 +4002,7 @@ static int giql_hip_contain_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* o,
         return c.off;
       };
       const size_t need = carve_t(nullptr);
-      GIQL_TRY(grow_buffer((void**)&ctx->ct_buf, &ctx->ct_buf_cap, need, need + need / 4, st, "the candidate tiles"));
+      GIQL_TRY(ctx->ct_buf.grow(need, need + need / 4, st, "the candidate tiles"));
       carve_t(ctx->ct_buf);
       {
         Phase ph(ctx, st, GIQL_PH_PARTITION);
@@ -4435,8 +4365,7 @@ int giql_hip_fill_from_plan_dev(giql_hip_ctx* ctx, const int32_t* q_rid, const u
     return c.off;
   };
   const size_t need = carve(nullptr);
-  GIQL_TRY(grow_buffer((void**)&ctx->xplan, &ctx->xplan_cap, need, align_up(need + need / 8, (size_t)1 << 20), st,
-                       "the plan scratch"));
+  GIQL_TRY(ctx->xplan.grow(need, align_up(need + need / 8, (size_t)1 << 20), st, "the plan scratch"));
   carve(ctx->xplan);
   GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, cnt, (u64)n_q, off, bsums, off + n_q));
   u64 total = 0;
@@ -4845,10 +4774,7 @@ int giql_hip_left_pad_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, int
 // ----------------------------------------------------- host-buffer variants
 struct DevSide {
   giql_side s;
-  int32_t* buf = nullptr;
-  ~DevSide() {
-    if (buf) (void)hipFree(buf);
-  }
+  DevArray<int32_t> buf;  // the three columns, uploaded
 };
 
 static int upload_side(const giql_side* h, DevSide& d) {
@@ -4858,7 +4784,7 @@ static int upload_side(const giql_side* h, DevSide& d) {
     return GIQL_OK;
   }
   const size_t n = (size_t)h->n;
-  HIP_TRY(hipMalloc((void**)&d.buf, 3 * n * sizeof(int32_t)));
+  GIQL_TRY(d.buf.alloc(3 * n * sizeof(int32_t)));
   HIP_TRY(hipMemcpy(d.buf, h->chrom, n * sizeof(int32_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d.buf + n, h->start, n * sizeof(int32_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d.buf + 2 * n, h->end, n * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -4982,13 +4908,6 @@ int giql_hip_host_pool_trim(int64_t keep_bytes, int64_t* released) {
   return GIQL_OK;
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 // ---- the host-buffer INNER join, pipelined over row blocks of the larger table (round 3) ----
 // One shot, the call is a chain on the PCIe link: 1.3 GB of columns in (23 ms), the join (2.4 ms), 3.2 GB of
 // pairs out (57 ms).  The link is full duplex and an INNER join is a union over row blocks of one side --
@@ -5007,22 +4926,18 @@ __global__ __launch_bounds__(256) void k_add_i32(int32_t* __restrict__ v, u64 n,
 struct E2eResources {  // released on every path out of inner_host_pipelined
   hipStream_t cs = nullptr;
   hipEvent_t filled[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
-  int32_t* in[2] = {nullptr, nullptr};
-  int32_t* out[2] = {nullptr, nullptr};
-  size_t out_cap[2] = {0, 0};  // pairs per array
-  int32_t *ha = nullptr, *hb = nullptr;
+  DevArray<int32_t> in[2];
+  DevArray<int32_t> out[2];  // row_a | row_b of a block, half of the buffer each
+  HostPtr<int32_t> ha, hb;
   size_t h_cap = 0;
+  // the copy stream has drained before the members above, which it reads and writes, are released (after this body)
   ~E2eResources() {
     if (cs) (void)hipStreamSynchronize(cs);
     for (int k = 0; k < 2; k++) {
-      if (in[k]) (void)hipFree(in[k]);
-      if (out[k]) (void)hipFree(out[k]);
       if (filled[k]) (void)hipEventDestroy(filled[k]);
       if (copied[k]) (void)hipEventDestroy(copied[k]);
     }
     if (cs) (void)hipStreamDestroy(cs);
-    giql_hip_free_host(ha);
-    giql_hip_free_host(hb);
   }
 };
 
@@ -5039,7 +4954,7 @@ static int inner_host_pipelined(giql_hip_ctx* ctx, const giql_side* a, const giq
   for (int k = 0; k < 2; k++) {
     HIP_TRY(hipEventCreateWithFlags(&R.filled[k], hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&R.copied[k], hipEventDisableTiming));
-    HIP_TRY(hipMalloc((void**)&R.in[k], 3 * block_rows * sizeof(int32_t)));
+    GIQL_TRY(R.in[k].alloc(3 * block_rows * sizeof(int32_t)));
   }
   const size_t n_big = (size_t)big->n;
   size_t total = 0;
@@ -5067,17 +4982,13 @@ static int inner_host_pipelined(giql_hip_ctx* ctx, const giql_side* a, const giq
     HIP_TRY(hipEventSynchronize(R.copied[slot]));  // the slot's previous pairs have left the device
     if (nj > 0) {
       const size_t stride = align_up((size_t)nj, (size_t)1 << 19);  // each row on a 2 MiB boundary (the fill's stores)
-      if (stride > R.out_cap[slot]) {
-        if (R.out[slot]) HIP_TRY(hipFree(R.out[slot]));
-        R.out[slot] = nullptr;
-        R.out_cap[slot] = 0;
-        const size_t want = stride + stride / 8;
-        if (hipMalloc((void**)&R.out[slot], 2 * want * sizeof(int32_t)) != hipSuccess)
-          return set_err(GIQL_ERR_NOMEM, "hipMalloc for %lld pairs failed", (long long)nj);
-        R.out_cap[slot] = want;
+      {
+        const int rc = R.out[slot].grow(2 * stride * sizeof(int32_t), 2 * (stride + stride / 8) * sizeof(int32_t), nullptr, "the pairs");
+        if (rc == GIQL_ERR_NOMEM) return set_err(GIQL_ERR_NOMEM, "hipMalloc for %lld pairs failed", (long long)nj);
+        GIQL_TRY(rc);
       }
       int32_t* oa = R.out[slot];
-      int32_t* ob = oa + R.out_cap[slot];
+      int32_t* ob = oa + R.out[slot].bytes() / (2 * sizeof(int32_t));
       GIQL_TRY(giql_hip_inner_fill_dev(ctx, oa, ob, nj, nullptr));
       if (j0 > 0) {
         u32 grid = cdiv((u64)nj, 256 * 8);
@@ -5091,21 +5002,14 @@ static int inner_host_pipelined(giql_hip_ctx* ctx, const giql_side* a, const giq
         const double per_row = (double)(total + (size_t)nj) / (double)(j0 + nblk);
         size_t want = (size_t)(per_row * (double)n_big * 1.08) + (1u << 20);
         if (want < total + (size_t)nj) want = total + (size_t)nj;
-        int32_t* na_ = (int32_t*)host_alloc(want * sizeof(int32_t));
-        int32_t* nb_ = (int32_t*)host_alloc(want * sizeof(int32_t));
-        if (!na_ || !nb_) {
-          giql_hip_free_host(na_);
-          giql_hip_free_host(nb_);
-          return set_err(GIQL_ERR_NOMEM, "out of host memory for %zu pairs", want);
-        }
+        HostPtr<int32_t> na_(host_alloc(want * sizeof(int32_t))), nb_(host_alloc(want * sizeof(int32_t)));
+        if (!na_ || !nb_) return set_err(GIQL_ERR_NOMEM, "out of host memory for %zu pairs", want);
         if (total) {
           memcpy(na_, R.ha, total * sizeof(int32_t));
           memcpy(nb_, R.hb, total * sizeof(int32_t));
         }
-        giql_hip_free_host(R.ha);
-        giql_hip_free_host(R.hb);
-        R.ha = na_;
-        R.hb = nb_;
+        R.ha = std::move(na_);  // (the arrays they replace go back to the pool)
+        R.hb = std::move(nb_);
         R.h_cap = want;
       }
       HIP_TRY(hipEventRecord(R.filled[slot], nullptr));
@@ -5118,14 +5022,13 @@ static int inner_host_pipelined(giql_hip_ctx* ctx, const giql_side* a, const giq
   }
   HIP_TRY(hipStreamSynchronize(R.cs));
   if (!R.ha) {  // no pair at all: the caller still gets arrays to free
-    R.ha = (int32_t*)host_alloc(sizeof(int32_t));
-    R.hb = (int32_t*)host_alloc(sizeof(int32_t));
+    R.ha = HostPtr<int32_t>(host_alloc(sizeof(int32_t)));
+    R.hb = HostPtr<int32_t>(host_alloc(sizeof(int32_t)));
     if (!R.ha || !R.hb) return set_err(GIQL_ERR_NOMEM, "out of host memory");
   }
   *n_pairs = (int64_t)total;
-  *row_a = R.ha;
-  *row_b = R.hb;
-  R.ha = R.hb = nullptr;  // handed over
+  *row_a = R.ha.release();  // handed over
+  *row_b = R.hb.release();
   return GIQL_OK;
 }
 
@@ -5139,15 +5042,9 @@ static int inner_host_pipelined(giql_hip_ctx* ctx, const giql_side* a, const giq
 // come out in the plan's query order.  Only the single-range form (fixed-length side, no irregular rows) has a compact
 // plan: any other plan is filled and downloaded as before.  GIQL_HIP_E2E_THREADS: expansion threads (default 32: tools/e2e_threads.py -- 16: 45.8 ms, 32: 39.9, 64: 40.0 at the headline sizes).
 struct CompactHost {  // page-locked staging of the plan, back to the pool on every path out
-  int32_t* q_rid = nullptr;
-  u32 *lo = nullptr, *cnt = nullptr;
-  int32_t* s_rid = nullptr;
-  ~CompactHost() {
-    giql_hip_free_host(q_rid);
-    giql_hip_free_host(lo);
-    giql_hip_free_host(cnt);
-    giql_hip_free_host(s_rid);
-  }
+  HostPtr<int32_t> q_rid;
+  HostPtr<u32> lo, cnt;
+  HostPtr<int32_t> s_rid;
 };
 
 // returns GIQL_OK with *done = false when the plan has no compact form (the caller fills and downloads)
@@ -5160,8 +5057,8 @@ static int inner_host_compact_tail(giql_hip_ctx* ctx, int64_t n, int32_t* ha, in
   if (nq == 0 || ns == 0) return GIQL_OK;
   // device staging: the context's output staging buffer (3 nq + ns words)
   const size_t need = (3 * nq + ns + 64) * sizeof(u32);
-  GIQL_TRY(grow_buffer(&ctx->stage_out, &ctx->stage_out_cap, need, need + need / 16, nullptr, "the compact plan"));
-  int32_t* d_qrid = (int32_t*)ctx->stage_out;
+  GIQL_TRY(ctx->stage_out.grow(need, need + need / 16, nullptr, "the compact plan"));
+  int32_t* d_qrid = (int32_t*)ctx->stage_out.get();
   u32* d_lo = (u32*)d_qrid + nq;
   u32* d_cnt = d_lo + nq;
   int32_t* d_srid = (int32_t*)(d_cnt + nq);
@@ -5172,11 +5069,8 @@ static int inner_host_compact_tail(giql_hip_ctx* ctx, int64_t n, int32_t* ha, in
   if (rc_x == GIQL_ERR_STATE) return GIQL_OK;
   GIQL_TRY(rc_x);
   if ((size_t)xq != nq || (size_t)xs != ns) return set_err(GIQL_ERR_STATE, "plan export sizes changed under the call");
-  CompactHost H;
-  H.q_rid = (int32_t*)host_alloc(nq * 4);
-  H.lo = (u32*)host_alloc(nq * 4);
-  H.cnt = (u32*)host_alloc(nq * 4);
-  H.s_rid = (int32_t*)host_alloc(ns * 4);
+  CompactHost H{HostPtr<int32_t>(host_alloc(nq * 4)), HostPtr<u32>(host_alloc(nq * 4)), HostPtr<u32>(host_alloc(nq * 4)),
+                HostPtr<int32_t>(host_alloc(ns * 4))};
   if (!H.q_rid || !H.lo || !H.cnt || !H.s_rid) return set_err(GIQL_ERR_NOMEM, "out of host memory for the compact plan");
   constexpr size_t CHUNK = (size_t)16 << 20;   // sorted ids per download chunk (64 MB: ~1.1 ms on the link)
   constexpr size_t QBLK = (size_t)1 << 16;     // queries per expansion block
@@ -5403,33 +5297,22 @@ int giql_hip_inner(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, in
   // bounce buffer) -- unless host threads write them (compact plan): plain memory then, nothing to page-lock (3.2 GB:
   // ~200 ms on a first call); giql_hip_free_host releases either kind
   const size_t out_bytes = (size_t)(n > 0 ? n : 1) * sizeof(int32_t);
-  int32_t* ha = (int32_t*)(compact ? host_alloc_plain(out_bytes) : host_alloc(out_bytes));
-  int32_t* hb = (int32_t*)(compact ? host_alloc_plain(out_bytes) : host_alloc(out_bytes));
-  if (!ha || !hb) {
-    giql_hip_free_host(ha);
-    giql_hip_free_host(hb);
-    return set_err(GIQL_ERR_NOMEM, "out of host memory for %lld pairs", (long long)n);
-  }
+  HostPtr<int32_t> ha(compact ? host_alloc_plain(out_bytes) : host_alloc(out_bytes));
+  HostPtr<int32_t> hb(compact ? host_alloc_plain(out_bytes) : host_alloc(out_bytes));
+  if (!ha || !hb) return set_err(GIQL_ERR_NOMEM, "out of host memory for %lld pairs", (long long)n);
   const double ms_pin = ms_since(t0);
   t0 = now();
   double ms_fill = 0, ms_d2h = 0;
   bool compact_done = false;
-  if (compact && n > 0) {
-    const int rc = inner_host_compact_tail(ctx, n, ha, hb, &compact_done);
-    if (rc != GIQL_OK) {
-      giql_hip_free_host(ha);
-      giql_hip_free_host(hb);
-      return rc;
-    }
-  }
+  if (compact && n > 0) GIQL_TRY(inner_host_compact_tail(ctx, n, ha, hb, &compact_done));
   if (n > 0 && !compact_done) {
     // row_b starts on a 2 MiB boundary of its own: a row that begins in the middle of a cache
     // line makes every 256-byte wave store of the fill touch three lines instead of two
     const size_t stride = align_up((size_t)n, (size_t)1 << 19);
     // the device staging of the pairs is kept by the context (a fresh 3.2 GB hipMalloc costs ~160 ms)
     const size_t need = 2 * stride * sizeof(int32_t);
-    int rc = grow_buffer(&ctx->stage_out, &ctx->stage_out_cap, need, need + need / 16, nullptr, "the pairs");
-    int32_t* d_a = (int32_t*)ctx->stage_out;
+    int rc = ctx->stage_out.grow(need, need + need / 16, nullptr, "the pairs");
+    int32_t* d_a = (int32_t*)ctx->stage_out.get();
     int32_t* d_b = d_a + stride;
     if (rc == GIQL_OK) rc = giql_hip_inner_fill_dev(ctx, d_a, d_b, n, nullptr);
     if (dbg) {
@@ -5441,18 +5324,14 @@ int giql_hip_inner(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, in
       rc = set_err(GIQL_ERR_HIP, "D2H copy of row_a failed");
     if (rc == GIQL_OK && hipMemcpy(hb, d_b, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
       rc = set_err(GIQL_ERR_HIP, "D2H copy of row_b failed");
-    if (rc != GIQL_OK) {
-      giql_hip_free_host(ha);
-      giql_hip_free_host(hb);
-      return rc;
-    }
+    GIQL_TRY(rc);
   }
   ms_d2h = ms_since(t0);
   if (dbg)
     fprintf(stderr, "[giql_hip_inner] H2D %.1f ms, plan %.1f, pinned alloc %.1f, output alloc + fill %.1f, %s %.1f (%lld pairs)\n",
             ms_h2d, ms_plan, ms_pin, ms_fill, compact_done ? "compact plan D2H + host expansion" : "D2H", ms_d2h, (long long)n);
-  *row_a = ha;
-  *row_b = hb;
+  *row_a = ha.release();
+  *row_b = hb.release();
   return GIQL_OK;
 }
 
@@ -5466,19 +5345,17 @@ int giql_hip_semi_anti(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b
   DevSide da, db;
   GIQL_TRY(upload_side(a, da));
   GIQL_TRY(upload_side(b, db));
-  DevBuf out;
+  DevArray<int32_t> out;
   const size_t na = (size_t)a->n;
-  HIP_TRY(hipMalloc(&out.p, (na ? na : 1) * sizeof(int32_t)));
+  GIQL_TRY(out.alloc((na ? na : 1) * sizeof(int32_t)));
   int64_t n = 0;
-  GIQL_TRY(giql_hip_semi_anti_dev(ctx, &da.s, &db.s, n_chrom, anti, (int32_t*)out.p, &n, nullptr));
-  int32_t* h = (int32_t*)host_alloc((size_t)(n > 0 ? n : 1) * sizeof(int32_t));
+  GIQL_TRY(giql_hip_semi_anti_dev(ctx, &da.s, &db.s, n_chrom, anti, out, &n, nullptr));
+  HostPtr<int32_t> h(host_alloc((size_t)(n > 0 ? n : 1) * sizeof(int32_t)));
   if (!h) return set_err(GIQL_ERR_NOMEM, "out of host memory");
-  if (n > 0 && hipMemcpy(h, out.p, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-    giql_hip_free_host(h);
+  if (n > 0 && hipMemcpy(h, out, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
     return set_err(GIQL_ERR_HIP, "D2H copy failed");
-  }
   *n_out = n;
-  *rows_a = h;
+  *rows_a = h.release();
   return GIQL_OK;
 }
 
@@ -5493,10 +5370,10 @@ int giql_hip_count(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, in
   DevSide da, db;
   GIQL_TRY(upload_side(a, da));
   GIQL_TRY(upload_side(b, db));
-  DevBuf out;
-  HIP_TRY(hipMalloc(&out.p, (size_t)a->n * sizeof(int64_t)));
-  GIQL_TRY(giql_hip_count_dev(ctx, &da.s, &db.s, n_chrom, (int64_t*)out.p, nullptr));
-  HIP_TRY(hipMemcpy(counts_out, out.p, (size_t)a->n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  DevArray<int64_t> out;
+  GIQL_TRY(out.alloc((size_t)a->n * sizeof(int64_t)));
+  GIQL_TRY(giql_hip_count_dev(ctx, &da.s, &db.s, n_chrom, out, nullptr));
+  HIP_TRY(hipMemcpy(counts_out, out, (size_t)a->n * sizeof(int64_t), hipMemcpyDeviceToHost));
   return GIQL_OK;
 }
 
@@ -5511,13 +5388,13 @@ int giql_hip_nearest(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, 
   DevSide da, db;
   GIQL_TRY(upload_side(a, da));
   GIQL_TRY(upload_side(b, db));
-  DevBuf oi, od;
-  HIP_TRY(hipMalloc(&oi.p, (size_t)a->n * sizeof(int32_t)));
-  HIP_TRY(hipMalloc(&od.p, (size_t)a->n * sizeof(int64_t)));
-  GIQL_TRY(giql_hip_nearest_dev(ctx, &da.s, &db.s, n_chrom, is_signed, max_distance,
-                                (int32_t*)oi.p, (int64_t*)od.p, nullptr));
-  HIP_TRY(hipMemcpy(idx_b_out, oi.p, (size_t)a->n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(dist_out, od.p, (size_t)a->n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  DevArray<int32_t> oi;
+  DevArray<int64_t> od;
+  GIQL_TRY(oi.alloc((size_t)a->n * sizeof(int32_t)));
+  GIQL_TRY(od.alloc((size_t)a->n * sizeof(int64_t)));
+  GIQL_TRY(giql_hip_nearest_dev(ctx, &da.s, &db.s, n_chrom, is_signed, max_distance, oi, od, nullptr));
+  HIP_TRY(hipMemcpy(idx_b_out, oi, (size_t)a->n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(dist_out, od, (size_t)a->n * sizeof(int64_t), hipMemcpyDeviceToHost));
   return GIQL_OK;
 }
 

@@ -108,46 +108,39 @@ class DeviceIndex:
 
     def __init__(self, engine: "HipEngine", handle, n_chrom: int):
         self.engine, self._h, self.n_chrom, self.last_pairs = engine, handle, n_chrom, 0
-        self._rows_prepared = False     # the row operators' arrays exist and ``nbytes`` counts them
-        self._nearest_prepared = False  # ... and NEAREST's
         self._refresh_info()
 
-    def _refresh_info(self) -> None:
+    def _info(self):
         n, b, g, sp = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
         _lib.check(self.engine._L.giql_hip_index_info(self._h, ctypes.byref(n), ctypes.byref(b), ctypes.byref(g), ctypes.byref(sp)))
-        self.n, self.nbytes, self.general, self.span = int(n.value), int(b.value), bool(g.value), int(sp.value)
+        return int(n.value), int(b.value), bool(g.value), int(sp.value)
 
-    def _note_rows_prepared(self) -> None:
-        if not self._rows_prepared:     # (a row operator that succeeded has prepared the index on the way)
-            self._rows_prepared = True
-            self._refresh_info()
+    def _refresh_info(self) -> None:
+        self.n, _, self.general, self.span = self._info()   # fixed at creation
+
+    @property
+    def nbytes(self) -> int:
+        """HBM bytes of the arrays the index owns now (``giql_hip_index_info``): grows when a preparation adds its
+        arrays, whoever ran it."""
+        return self._info()[1]
 
     def prepare_rows(self) -> None:
         """Build what the per-row operators read of the index (``giql_hip_index_prepare_rows_dev``: a directory of
         bucket boundaries; for a table of variable length its sorted end keys too, 4 B per row).  Once per index
         -- a second call does nothing -- and done by the first ``count_overlaps_indexed`` / ``semi_anti_indexed``
-        call otherwise; ``nbytes`` is refreshed."""
+        call otherwise."""
         eng = self.engine
         _lib.check(eng._L.giql_hip_index_prepare_rows_dev(eng._h, self._h, eng._stream()))
-        self._rows_prepared = True
-        self._refresh_info()
-
-    def _note_nearest_prepared(self) -> None:
-        if not self._nearest_prepared:  # (a NEAREST call that succeeded has prepared the index on the way)
-            self._nearest_prepared = True
-            self._refresh_info()
 
     def prepare_nearest(self) -> None:
         """Build what :meth:`HipEngine.nearest_indexed` reads of the index (``giql_hip_index_prepare_nearest_dev``:
         the directory of bucket boundaries it shares with the row operators, a rank per chromosome; for a table of
         variable length the row ids and the prefix max of the ends in (start, end) order too, 8 B per row).  Once
-        per index -- a second call does nothing -- and done by the first ``nearest_indexed`` call otherwise;
-        ``nbytes`` is refreshed.  ``GIQL_ERR_STATE`` (now and on every later NEAREST call) when a table of variable
+        per index -- a second call does nothing -- and done by the first ``nearest_indexed`` call otherwise.
+        ``GIQL_ERR_STATE`` (now and on every later NEAREST call) when a table of variable
         length holds a long run of rows on one start: the ordinary operator answers such a table."""
         eng = self.engine
         _lib.check(eng._L.giql_hip_index_prepare_nearest_dev(eng._h, self._h, eng._stream()))
-        self._nearest_prepared = True
-        self._refresh_info()
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -441,8 +434,6 @@ class HipEngine:
         rc = self._L.giql_hip_count_indexed_dev(self._h, index._h, ctypes.byref(ca),
                                                 counts.data_ptr() if a.n else None, self._stream())
         _lib.check(rc)
-        if a.n:                         # (an empty query returns before the index is prepared)
-            index._note_rows_prepared()
         return counts
 
     def semi_anti_indexed(self, a: DeviceSide, index: "DeviceIndex", anti: bool):
@@ -457,8 +448,6 @@ class HipEngine:
         rc = self._L.giql_hip_semi_anti_indexed_dev(self._h, index._h, ctypes.byref(ca), int(bool(anti)),
                                                     rows.data_ptr() if a.n else None, ctypes.byref(n), self._stream())
         _lib.check(rc)
-        if a.n:                         # (an empty query returns before the index is prepared)
-            index._note_rows_prepared()
         return rows[: int(n.value)]
 
     def nearest_indexed(self, a: DeviceSide, index: "DeviceIndex", signed: bool = False, max_distance=None):
@@ -476,8 +465,6 @@ class HipEngine:
         ca = a.c_struct()
         _lib.check(self._L.giql_hip_nearest_indexed_dev(self._h, index._h, ctypes.byref(ca), int(bool(signed)), md,
                                                         idx.data_ptr(), dist.data_ptr(), self._stream()))
-        if a.n:                         # (an empty query returns before the index is prepared)
-            index._note_nearest_prepared()
         return idx[: a.n], dist[: a.n]
 
     # ------------------------------------------------ genomes longer than 2^32
