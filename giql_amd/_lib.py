@@ -20,6 +20,11 @@ GIQL_ERR_SPAN = -5
 GIQL_ERR_CAPACITY = -6
 GIQL_ERR_STATE = -7
 
+#: ``GIQL_ROWPRED_*`` (include/giql_hip.h)
+ROWPRED_CONTAINS = 1
+ROWPRED_WITHIN = 2
+ROWPRED_DISTANCE = 3
+
 PHASES = [
     "span", "linearize", "sort_hist", "sort_scan", "sort_scatter", "count", "scan",
     "partition", "fill", "irregular", "aux", "sort_local",
@@ -46,6 +51,7 @@ SYMBOLS = [
     "giql_hip_index_prepare_rows_dev", "giql_hip_count_indexed_dev", "giql_hip_semi_anti_indexed_dev",
     "giql_hip_index_prepare_nearest_dev", "giql_hip_nearest_indexed_dev",
     "giql_hip_left_pad_dev",
+    "giql_hip_semi_anti_pred_dev", "giql_hip_count_pred_dev",
 ]
 
 
@@ -164,6 +170,8 @@ def load() -> ctypes.CDLL:
     L.giql_hip_inner_join_dev.argtypes = [vp, P(CSide), P(CSide), i32, vp, vp, i64, vp, P(i64)]
     L.giql_hip_semi_anti_dev.argtypes = [vp, P(CSide), P(CSide), i32, ctypes.c_int, vp, P(i64), vp]
     L.giql_hip_count_dev.argtypes = [vp, P(CSide), P(CSide), i32, vp, vp]
+    L.giql_hip_semi_anti_pred_dev.argtypes = [vp, P(CSide), P(CSide), i32, i32, i64, ctypes.c_int, vp, P(i64), vp]
+    L.giql_hip_count_pred_dev.argtypes = [vp, P(CSide), P(CSide), i32, i32, i64, vp, vp]
     L.giql_hip_nearest_dev.argtypes = [vp, P(CSide), P(CSide), i32, ctypes.c_int, i64, vp, vp, vp]
     L.giql_hip_index_create_dev.argtypes = [vp, P(CSide), i32, vp, P(vp)]
     L.giql_hip_index_destroy.argtypes = [vp]

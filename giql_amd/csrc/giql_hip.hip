@@ -31,6 +31,7 @@
 #include "disjoin_kernels.hip.h"
 #include "contain_kernels.hip.h"
 #include "distance_kernels.hip.h"
+#include "row_pred_kernels.hip.h"
 #include "dev_common.hip.h"
 #include "join_kernels.hip.h"
 #include "onesweep.hip.h"
@@ -3886,39 +3887,22 @@ int giql_hip_disjoin_fill_dev(giql_hip_ctx* ctx, int32_t* parent_out, int32_t* s
 struct ContainBufs {
   LinBufs lb;
   OsScratch os_o, os_i;
-  u32 *wlo = nullptr, *cand = nullptr, *irr_cnt = nullptr;
+  u32 *wlo = nullptr, *cand = nullptr, *irr_cnt = nullptr, *extra = nullptr;
   u64* bsums = nullptr;
 };
 
-static int giql_hip_contain_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* o, const giql_side* in, int32_t n_chrom,
-                                          void* stream, int64_t* n_pairs) {
-  if (!ctx || !n_pairs) return set_err(GIQL_ERR_INVALID, "ctx/n_pairs is NULL");
-  GIQL_TRY(check_side(o, "outer"));
-  GIQL_TRY(check_side(in, "inner"));
-  if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
-  GIQL_TRY(begin_call(ctx));
-  hipStream_t st = (hipStream_t)stream;
-  ctx->stats.n_a = o->n;
-  ctx->stats.n_b = in->n;
-  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the other plans too)
-  ctx->dj.planned = false;
-  ContainPlan& P = ctx->ct;
-  P = ContainPlan{};
-  P.outer = *o;
-  P.inner = *in;
-  P.n_o = (u32)o->n;
-  P.n_i = (u32)in->n;
-  *n_pairs = 0;
-  if (o->n == 0 || in->n == 0) {  // nothing to launch
-    P.planned = true;
-    return GIQL_OK;
-  }
-  if (n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
+// The candidate stage shared by the CONTAINS plan and the per-row containment counts: workspace, spans, the form,
+// both sorts, the candidate range {P.lo, W.cand} of every sorted outer row and their u64 offsets P.coff, with the
+// total read back (uniform form: the pairs, DevMeta::n_out; general form: the candidates, DevMeta::n_out_c1).
+// extra_words: u32 words carved for the caller behind the stage's own buffers (W.extra); force_general: take the
+// candidate-tile form whatever the inner side's lengths are.
+static int contain_candidates(giql_hip_ctx* ctx, hipStream_t st, const giql_side* o, const giql_side* in,
+                              int32_t n_chrom, ContainPlan& P, ContainBufs& W, size_t extra_words,
+                              bool force_general) {
   const size_t no = (size_t)o->n, ni = (size_t)in->n, nq = no + ni;
   if (no > OS_MAX_ROWS || ni > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
   constexpr u32 TQ = RC_NT * RC_ITEMS_C2;
   const u32 nt = cdiv(no, TQ);
-  ContainBufs W;
   auto carve = [&](char* base) {
     Carver c{base};
     common_sizes(c, n_chrom, W.lb);
@@ -3935,6 +3919,7 @@ static int giql_hip_contain_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* o,
     W.irr_cnt = c.take<u32>(nq);
     P.irr_off = c.take<u64>(nq + 1);
     W.bsums = c.take<u64>(cdiv(nq, SCAN_TILE) + 2);
+    W.extra = c.take<u32>(extra_words);
     return c.off;
   };
   GIQL_TRY(claim_arena(ctx, st, carve));
@@ -3944,7 +3929,7 @@ static int giql_hip_contain_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* o,
   // the minimum 0 (decide_form).
   GIQL_TRY(read_meta(ctx, st));
   ctx->guess.last_span = ctx->h_meta->total_span;  // known before anything is sorted: the sort form follows the real density
-  const i64 uni_len = ctx->sw.no_uniform ? 0 : uniform_len_b(*ctx->h_meta);
+  const i64 uni_len = (ctx->sw.no_uniform || force_general) ? 0 : uniform_len_b(*ctx->h_meta);
   P.form = uni_len > 0 ? 1 : 0;
   GIQL_TRY(run_linearize(ctx, st, *o, n_chrom, W.lb, P.so.key[0], P.so.end[0], P.irr_o_list, 0, 0, W.os_o.hist,
                          W.os_o.gbase));
@@ -3982,6 +3967,36 @@ static int giql_hip_contain_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* o,
   GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, W.cand, (u64)no, P.coff, W.bsums, P.coff + no,
                          P.form == 1 ? &ctx->d_meta->n_out : &ctx->d_meta->n_out_c1));
   GIQL_TRY(read_meta(ctx, st));
+  return GIQL_OK;
+}
+
+static int giql_hip_contain_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* o, const giql_side* in, int32_t n_chrom,
+                                          void* stream, int64_t* n_pairs) {
+  if (!ctx || !n_pairs) return set_err(GIQL_ERR_INVALID, "ctx/n_pairs is NULL");
+  GIQL_TRY(check_side(o, "outer"));
+  GIQL_TRY(check_side(in, "inner"));
+  if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
+  GIQL_TRY(begin_call(ctx));
+  hipStream_t st = (hipStream_t)stream;
+  ctx->stats.n_a = o->n;
+  ctx->stats.n_b = in->n;
+  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the other plans too)
+  ctx->dj.planned = false;
+  ContainPlan& P = ctx->ct;
+  P = ContainPlan{};
+  P.outer = *o;
+  P.inner = *in;
+  P.n_o = (u32)o->n;
+  P.n_i = (u32)in->n;
+  *n_pairs = 0;
+  if (o->n == 0 || in->n == 0) {  // nothing to launch
+    P.planned = true;
+    return GIQL_OK;
+  }
+  if (n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
+  const size_t no = (size_t)o->n, ni = (size_t)in->n, nq = no + ni;
+  ContainBufs W;
+  GIQL_TRY(contain_candidates(ctx, st, o, in, n_chrom, P, W, 0, false));
   if (P.form == 1) {
     P.n_reg = ctx->h_meta->n_out;
   } else {
@@ -4099,6 +4114,354 @@ int giql_hip_contain_fill_dev(giql_hip_ctx* ctx, int32_t* row_outer, int32_t* ro
     GIQL_TRY(post_launch("contain irregular fill"));
   }
   return GIQL_OK;
+}
+
+// ------------------------------------- SEMI / ANTI / COUNT over CONTAINS, WITHIN, DISTANCE
+// The per-row forms of the three pair predicates that are not INTERSECTS (row_pred_kernels.hip.h).  Nothing is
+// speculated: every call reads the span pass back once (chrom ids, the 32-bit axis, inverted rows under DISTANCE)
+// before it sorts.
+static int check_rowpred(int32_t pred, int64_t max_distance) {
+  if (pred != GIQL_ROWPRED_CONTAINS && pred != GIQL_ROWPRED_WITHIN && pred != GIQL_ROWPRED_DISTANCE)
+    return set_err(GIQL_ERR_INVALID, "pred %d is none of GIQL_ROWPRED_*", (int)pred);
+  if (pred == GIQL_ROWPRED_DISTANCE && max_distance < -1) return set_err(GIQL_ERR_INVALID, "max_distance < -1");
+  return GIQL_OK;
+}
+
+// DISTANCE needs start <= end on every row of both sides, reported as giql_hip_window_plan_dev reports it.
+static int reject_inverted(giql_hip_ctx* ctx) {
+  if (!ctx->h_meta->inverted_a && !ctx->h_meta->inverted_b) return GIQL_OK;
+  if (ctx->h_meta->inverted_a) ctx->stats.n_irregular_a = -1;
+  if (ctx->h_meta->inverted_b) ctx->stats.n_irregular_b = -1;
+  return set_err(GIQL_ERR_INVALID, "DISTANCE: side %s has a row with start > end", ctx->h_meta->inverted_a ? "a" : "b");
+}
+
+// the clamp range of the widened rows: what run_spans(pad = 1) handed to k_chrom_offsets
+static void window_pads(const giql_side& a, const giql_side& b, int& lo_pad, int& hi_pad) {
+  lo_pad = hi_pad = a.start_off;
+  const int offs[3] = {a.end_off, b.start_off, b.end_off};
+  for (int k = 0; k < 3; k++) {
+    if (offs[k] < lo_pad) lo_pad = offs[k];
+    if (offs[k] > hi_pad) hi_pad = offs[k];
+  }
+  lo_pad -= 1;
+  hi_pad += 1;
+}
+
+static inline i64 clamp_widen(int64_t max_distance) {  // (giql_hip_window_plan_dev: a larger N selects the same pairs)
+  return max_distance > ((i64)1 << 33) ? ((i64)1 << 33) : (i64)max_distance;
+}
+
+static int giql_hip_semi_anti_pred_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, int32_t n_chrom,
+                                            int32_t pred, int64_t max_distance, int anti, int32_t* rows_out,
+                                            int64_t* n_out, void* stream) {
+  if (!ctx || !n_out) return set_err(GIQL_ERR_INVALID, "ctx/n_out is NULL");
+  GIQL_TRY(check_rowpred(pred, max_distance));
+  GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
+  hipStream_t st = (hipStream_t)stream;
+  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plans too)
+  ctx->dj.planned = false;
+  *n_out = 0;
+  if (a->n == 0) return GIQL_OK;
+  if (!rows_out) return set_err(GIQL_ERR_INVALID, "rows_out is NULL");
+  const size_t na = (size_t)a->n, nb = (size_t)b->n;
+  if (na > OS_MAX_ROWS || nb > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
+  if (nb > 0 && n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
+  const bool dist = pred == GIQL_ROWPRED_DISTANCE;
+  const int nch = n_chrom;
+  if (nb == 0) {  // no right row: nothing for SEMI, every row for ANTI
+    if (anti) {
+      hipLaunchKernelGGL(k_rp_iota, dim3(cdiv(na, 256)), dim3(256), 0, st, rows_out, (u32)na);
+      GIQL_TRY(post_launch("anti (empty right side)"));
+      *n_out = a->n;
+    }
+    ctx->stats.n_out = *n_out;
+    return GIQL_OK;
+  }
+
+  LinBufs lb;
+  SortBufs sa, sbb;
+  OsScratch os, os_a;
+  u32 *flag = nullptr, *pmax = nullptr, *bmax = nullptr, *dummy_irr = nullptr;
+  u64 *bsums = nullptr, *off = nullptr;
+  auto carve = [&](char* base) {
+    Carver c{base};
+    common_sizes(c, nch, lb);
+    sort_sizes(c, na, sa, true);
+    for (int k = 0; k < 2; k++) {  // B: (sort key, the other key as payload), no row ids
+      sbb.key[k] = c.take<u32>(nb);
+      sbb.end[k] = c.take<u32>(nb);
+      sbb.rid[k] = nullptr;
+    }
+    os_scratch_sizes(c, na, os_a);
+    os_scratch_sizes(c, nb, os);
+    bsums = c.take<u64>(cdiv(na, SCAN_TILE) + 2);
+    flag = c.take<u32>(na);
+    off = c.take<u64>(na + 1);
+    pmax = c.take<u32>(nb);
+    bmax = c.take<u32>(cdiv(nb, PM_TILE) + 1);
+    dummy_irr = c.take<u32>(16);
+    return c.off;
+  };
+  GIQL_TRY(claim_arena(ctx, st, carve));
+  GIQL_TRY(run_spans(ctx, st, *a, *b, nch, lb, -1, nullptr, /*pad=*/dist ? 1 : 0));
+  GIQL_TRY(read_meta(ctx, st));
+  if (dist) GIQL_TRY(reject_inverted(ctx));
+  ctx->stats.span = (int64_t)ctx->h_meta->total_span;
+  ctx->guess.last_span = ctx->h_meta->total_span;
+  if (dist && max_distance < 0) {  // `< 0`: no pair, after the rows have been checked
+    if (anti) {
+      hipLaunchKernelGGL(k_rp_iota, dim3(cdiv(na, 256)), dim3(256), 0, st, rows_out, (u32)na);
+      GIQL_TRY(post_launch("anti (no pair possible)"));
+      *n_out = a->n;
+    }
+    ctx->stats.n_out = *n_out;
+    return GIQL_OK;
+  }
+  const i64 widen = dist ? clamp_widen(max_distance) : 0;
+  // A: every row on its real key, sorted coarsely (its order only serves locality)
+  if (dist) {
+    int lo_pad, hi_pad;
+    window_pads(*a, *b, lo_pad, hi_pad);
+    HIP_TRY(hipMemsetAsync(os_a.hist, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
+    Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
+    u32 grid = cdiv((u64)na, LIN_NT);
+    if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_rp_window_keys, dim3(grid), dim3(LIN_NT), 0, st, a->chrom, a->start, a->end, (u32)na,
+                       a->start_off, a->end_off, nch, lb.chrom_base, lb.gmin, lb.gmax, lo_pad, hi_pad, widen, sa.key[0],
+                       sa.end[0], ctx->d_meta, os_a.hist);
+    hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, os_a.hist, (u32)LIN_HIST_REPLICAS, os_a.gbase);
+    GIQL_TRY(post_launch("row predicate window keys"));
+  } else {
+    GIQL_TRY(run_linearize(ctx, st, *a, nch, lb, sa.key[0], sa.end[0], dummy_irr + 8, 0, 1, os_a.hist, os_a.gbase));
+  }
+  GIQL_TRY(run_sort_onesweep(ctx, st, sa, (u32)na, os_a.gbase, os_a.status, false, nullptr, nullptr,
+                             /*skip_digits=*/row_skip(ctx, nb)));
+  // B: every row on its real key.  WITHIN and DISTANCE sort it by start with the end keys as payload; CONTAINS sorts
+  // it by END with the start keys as payload -- a SortBufs is only pointers, and the linearize pass counts the end
+  // keys' digits on the way (os.hist_e / os.gbase_e, as the COUNT path's second sort does).
+  if (pred == GIQL_ROWPRED_CONTAINS) {
+    GIQL_TRY(run_linearize(ctx, st, *b, nch, lb, sbb.end[0], sbb.key[0], dummy_irr, 1, 1, os.hist, os.gbase, os.hist_e,
+                           os.gbase_e));
+    GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase_e, os.status));
+  } else {
+    GIQL_TRY(run_linearize(ctx, st, *b, nch, lb, sbb.key[0], sbb.end[0], dummy_irr, 1, 1, os.hist, os.gbase));
+    GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase, os.status));
+  }
+  GIQL_TRY(run_pmax(ctx, st, sbb.end[0], (u32)nb, pmax, bmax));
+  {
+    Phase ph(ctx, st, GIQL_PH_COUNT);
+    if (dist)
+      hipLaunchKernelGGL(k_semi_flags, dim3(cdiv(na, 256)), dim3(256), 0, st, sa.key[0], sa.end[0], sa.rid[0], (u32)na,
+                         ctx->d_meta, sbb.key[0], pmax, (u32)nb, anti, flag);
+    else
+      hipLaunchKernelGGL(k_rp_semi_flags, dim3(cdiv(na, 256)), dim3(256), 0, st, sa.key[0], sa.end[0], sa.rid[0],
+                         (u32)na, ctx->d_meta, sbb.key[0], pmax, (u32)nb, pred == GIQL_ROWPRED_WITHIN ? 1 : 0, anti,
+                         flag);
+    GIQL_TRY(post_launch("row predicate flags"));
+  }
+  GIQL_TRY(run_scan_compact(ctx, st, flag, na, bsums, off + na, rows_out, "scan + compact"));
+  GIQL_TRY(read_meta(ctx, st));
+  collect_spans(ctx);
+  ctx->stats.reserved = 0;  // form: general, the only one
+  *n_out = (int64_t)ctx->h_meta->n_out;
+  ctx->stats.n_out = *n_out;
+  return GIQL_OK;
+}
+
+int giql_hip_semi_anti_pred_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, int32_t n_chrom,
+                                int32_t pred, int64_t max_distance, int anti, int32_t* rows_out, int64_t* n_out,
+                                void* stream) {
+  return with_order_fallback(ctx, [&] {
+    return giql_hip_semi_anti_pred_dev_impl(ctx, a, b, n_chrom, pred, max_distance, anti, rows_out, n_out, stream);
+  });
+}
+
+// COUNT over DISTANCE: the rank difference of giql_hip_count_dev over the widened A (general form only).
+static int count_window(giql_hip_ctx* ctx, hipStream_t st, const giql_side* a, const giql_side* b, int32_t n_chrom,
+                        int64_t max_distance, int64_t* counts_out) {
+  const size_t na = (size_t)a->n, nb = (size_t)b->n;
+  LinBufs lb;
+  SortBufs sa, sstart, send;
+  OsScratch os, os_a;
+  u32 *irr_a_list = nullptr, *irr_b_list = nullptr;
+  auto carve = [&](char* base) {
+    Carver c{base};
+    common_sizes(c, n_chrom, lb);
+    sort_sizes(c, na, sa, true);
+    for (int k = 0; k < 2; k++) {  // two keys-only sorts of B: starts and ends
+      sstart.key[k] = c.take<u32>(nb);
+      sstart.end[k] = sstart.rid[k] = nullptr;
+      send.key[k] = c.take<u32>(nb);
+      send.end[k] = send.rid[k] = nullptr;
+    }
+    os_scratch_sizes(c, na, os_a);
+    os_scratch_sizes(c, nb, os);
+    irr_a_list = c.take<u32>(na);
+    irr_b_list = c.take<u32>(nb);
+    return c.off;
+  };
+  GIQL_TRY(claim_arena(ctx, st, carve));
+  GIQL_TRY(run_spans(ctx, st, *a, *b, n_chrom, lb, -1, nullptr, /*pad=*/1));
+  GIQL_TRY(read_meta(ctx, st));
+  GIQL_TRY(reject_inverted(ctx));
+  ctx->stats.span = (int64_t)ctx->h_meta->total_span;
+  ctx->guess.last_span = ctx->h_meta->total_span;
+  if (max_distance < 0) {  // `< 0`: no pair, after the rows have been checked
+    HIP_TRY(hipMemsetAsync(counts_out, 0, na * sizeof(int64_t), st));
+    ctx->stats.n_out = a->n;
+    return GIQL_OK;
+  }
+  const i64 widen = clamp_widen(max_distance);
+  {
+    int lo_pad, hi_pad;
+    window_pads(*a, *b, lo_pad, hi_pad);
+    HIP_TRY(hipMemsetAsync(os_a.hist, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
+    Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
+    u32 grid = cdiv((u64)na, LIN_NT);
+    if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_window_linearize, dim3(grid), dim3(LIN_NT), 0, st, a->chrom, a->start, a->end, (u32)na,
+                       a->start_off, a->end_off, n_chrom, lb.chrom_base, lb.gmin, lb.gmax, lo_pad, hi_pad, widen,
+                       sa.key[0], sa.end[0], irr_a_list, ctx->d_meta, os_a.hist);
+    hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, os_a.hist, (u32)LIN_HIST_REPLICAS, os_a.gbase);
+    GIQL_TRY(post_launch("window linearize"));
+  }
+  GIQL_TRY(run_sort_onesweep(ctx, st, sa, (u32)na, os_a.gbase, os_a.status, false, nullptr, nullptr,
+                             /*skip_digits=*/row_skip(ctx, nb)));  // locality only: the kernel tells listed rows by their key
+  GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, sstart.key[0], send.key[0], irr_b_list, 1, 0, os.hist, os.gbase,
+                         os.hist_e, os.gbase_e));
+  GIQL_TRY(run_sort_onesweep(ctx, st, sstart, (u32)nb, os.gbase, os.status));
+  GIQL_TRY(run_sort_onesweep(ctx, st, send, (u32)nb, os.gbase_e, os.status));
+  {
+    Phase ph(ctx, st, GIQL_PH_COUNT);
+    hipLaunchKernelGGL(k_rp_count_window_rows, dim3(cdiv(na, 256)), dim3(256), 0, st, sa.key[0], sa.end[0], sa.rid[0],
+                       (u32)na, view_of(*a), view_of(*b), sstart.key[0], send.key[0], (u32)nb, irr_b_list, ctx->d_meta,
+                       widen, counts_out);
+    GIQL_TRY(post_launch("count rows (distance)"));
+  }
+  GIQL_TRY(read_meta(ctx, st));
+  ctx->stats.n_irregular_a = ctx->h_meta->irr_a;
+  ctx->stats.n_irregular_b = ctx->h_meta->irr_b;
+  if (ctx->h_meta->irr_a > 0) {
+    Phase ph(ctx, st, GIQL_PH_IRREGULAR);
+    hipLaunchKernelGGL(k_rp_count_irregular, dim3(ctx->h_meta->irr_a), dim3(256), 0, st, view_of(*a), view_of(*b),
+                       irr_a_list, (int)GIQL_ROWPRED_DISTANCE, widen, counts_out);
+    GIQL_TRY(post_launch("count irregular (distance)"));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  collect_spans(ctx);
+  ctx->stats.reserved = 0;
+  ctx->stats.n_out = a->n;
+  return GIQL_OK;
+}
+
+// COUNT over CONTAINS / WITHIN: the CONTAINS plan's candidate stage, then the per-row tile walk (k_ct_rows) or, with a
+// uniform inner side under CONTAINS, the exact range counts scattered by row id.  a CONTAINS b: a is the outer side;
+// a WITHIN b: a is the inner side, and the general form is taken whatever a's lengths are.
+static int count_contain(giql_hip_ctx* ctx, hipStream_t st, const giql_side* a, const giql_side* b, int32_t n_chrom,
+                         int32_t pred, int64_t* counts_out) {
+  const bool per_inner = pred == GIQL_ROWPRED_WITHIN;
+  const giql_side* o = per_inner ? b : a;
+  const giql_side* in = per_inner ? a : b;
+  const size_t no = (size_t)o->n, ni = (size_t)in->n, na = (size_t)a->n;
+  ContainPlan P;  // a call's own: the context holds no plan afterwards
+  ContainBufs W;
+  P.n_o = (u32)no;
+  P.n_i = (u32)ni;
+  GIQL_TRY(contain_candidates(ctx, st, o, in, n_chrom, P, W, per_inner ? ni : 0, per_inner));
+  // (listed rows: the outer side was linearised as side 0, the inner one as side 1)
+  const u32 irr_o = ctx->h_meta->irr_a, irr_i = ctx->h_meta->irr_b;
+  ctx->stats.n_irregular_a = per_inner ? irr_i : irr_o;
+  ctx->stats.n_irregular_b = per_inner ? irr_o : irr_i;
+  ctx->stats.span = (int64_t)ctx->h_meta->total_span;
+  if (P.form == 1) {
+    Phase ph(ctx, st, GIQL_PH_FILL);
+    hipLaunchKernelGGL(k_rp_scatter_counts, dim3(cdiv(no, 256)), dim3(256), 0, st, W.cand, P.so.rid[0], (u32)no,
+                       counts_out);
+    GIQL_TRY(post_launch("count scatter (uniform inner side)"));
+  } else {
+    P.n_cand = ctx->h_meta->n_out_c1;
+    const u64 n_tiles = (P.n_cand + CT_TILE - 1) / CT_TILE;
+    if (n_tiles > 0x7FFFFFFFull)
+      return set_err(GIQL_ERR_CAPACITY, "%llu candidate pairs: more than one launch holds", (unsigned long long)P.n_cand);
+    if (per_inner)
+      HIP_TRY(hipMemsetAsync(W.extra, 0, ni * sizeof(u32), st));
+    else
+      HIP_TRY(hipMemsetAsync(counts_out, 0, na * sizeof(int64_t), st));
+    if (n_tiles > 0) {
+      const size_t need = ((size_t)n_tiles + 2) * sizeof(u32);
+      GIQL_TRY(ctx->ct_buf.grow(need, need + need / 4, st, "the candidate tiles"));
+      P.ct_part = reinterpret_cast<u32*>((char*)ctx->ct_buf);
+      {
+        Phase ph(ctx, st, GIQL_PH_PARTITION);
+        hipLaunchKernelGGL(k_partition, dim3(cdiv(n_tiles + 1, 256)), dim3(256), 0, st, P.coff, (u32)no, (u64)0, CT_TILE,
+                           (u32)n_tiles, P.ct_part);
+      }
+      Phase ph(ctx, st, GIQL_PH_COUNT);
+      ctx->stats.phase_bytes[GIQL_PH_COUNT] += (int64_t)4 * (int64_t)P.n_cand + (int64_t)20 * no;
+      if (per_inner)
+        hipLaunchKernelGGL(k_ct_rows<true>, dim3((u32)n_tiles), dim3(CT_NT), 0, st, P.coff, P.lo, P.so.end[0],
+                           P.so.rid[0], (u32)no, P.si.end[0], P.ct_part, P.n_cand, (unsigned long long*)nullptr, W.extra);
+      else
+        hipLaunchKernelGGL(k_ct_rows<false>, dim3((u32)n_tiles), dim3(CT_NT), 0, st, P.coff, P.lo, P.so.end[0],
+                           P.so.rid[0], (u32)no, P.si.end[0], P.ct_part, P.n_cand,
+                           reinterpret_cast<unsigned long long*>(counts_out), (u32*)nullptr);
+      GIQL_TRY(post_launch("contain row counts"));
+    }
+    if (per_inner) {
+      Phase ph(ctx, st, GIQL_PH_FILL);
+      hipLaunchKernelGGL(k_rp_scatter_counts, dim3(cdiv(ni, 256)), dim3(256), 0, st, W.extra, P.si.rid[0], (u32)ni,
+                         counts_out);
+      GIQL_TRY(post_launch("count scatter (per inner row)"));
+    }
+  }
+  // rows the sorted prefixes leave out, by the literal predicate: (listed a) x (every b), (regular a) x (listed b)
+  const u32 irr_x = per_inner ? irr_i : irr_o, irr_y = per_inner ? irr_o : irr_i;
+  const u32* list_x = per_inner ? P.irr_i_list : P.irr_o_list;
+  const u32* list_y = per_inner ? P.irr_o_list : P.irr_i_list;
+  if (irr_x + irr_y > 0) {
+    Phase ph(ctx, st, GIQL_PH_IRREGULAR, 2);
+    if (irr_y > 0)
+      hipLaunchKernelGGL(k_rp_count_vs_irregular, dim3(cdiv(na, 256)), dim3(256), 0, st, view_of(*a), view_of(*b),
+                         list_y, per_inner ? &ctx->d_meta->irr_a : &ctx->d_meta->irr_b, (int)pred, counts_out);
+    if (irr_x > 0)
+      hipLaunchKernelGGL(k_rp_count_irregular, dim3(irr_x), dim3(256), 0, st, view_of(*a), view_of(*b), list_x,
+                         (int)pred, (i64)0, counts_out);
+    GIQL_TRY(post_launch("count irregular (containment)"));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  collect_spans(ctx);
+  ctx->stats.reserved = P.form;  // form: 0 general (candidate tiles), 1 uniform inner side
+  ctx->stats.n_out = a->n;
+  return GIQL_OK;
+}
+
+static int giql_hip_count_pred_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, int32_t n_chrom,
+                                        int32_t pred, int64_t max_distance, int64_t* counts_out, void* stream) {
+  if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
+  GIQL_TRY(check_rowpred(pred, max_distance));
+  GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
+  hipStream_t st = (hipStream_t)stream;
+  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plans too)
+  ctx->dj.planned = false;
+  if (a->n == 0) return GIQL_OK;
+  if (!counts_out) return set_err(GIQL_ERR_INVALID, "counts_out is NULL");
+  const size_t na = (size_t)a->n, nb = (size_t)b->n;
+  if (na > OS_MAX_ROWS || nb > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
+  if (nb > 0 && n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
+  if (nb == 0) {
+    HIP_TRY(hipMemsetAsync(counts_out, 0, na * sizeof(int64_t), st));
+    ctx->stats.n_out = a->n;
+    return GIQL_OK;
+  }
+  if (pred == GIQL_ROWPRED_DISTANCE) return count_window(ctx, st, a, b, n_chrom, max_distance, counts_out);
+  return count_contain(ctx, st, a, b, n_chrom, pred, counts_out);
+}
+
+int giql_hip_count_pred_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, int32_t n_chrom, int32_t pred,
+                            int64_t max_distance, int64_t* counts_out, void* stream) {
+  return with_order_fallback(ctx, [&] {
+    return giql_hip_count_pred_dev_impl(ctx, a, b, n_chrom, pred, max_distance, counts_out, stream);
+  });
 }
 
 // ------------------------------------------- distinct intervals + segment sums

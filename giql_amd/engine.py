@@ -814,6 +814,78 @@ class HipEngine:
             self.inner_fill(row_a, row_b)
         return row_a, row_b
 
+    # ------------------------- SEMI / ANTI / COUNT over CONTAINS, WITHIN, DISTANCE
+    _ROW_PREDICATES = {"contains": _lib.ROWPRED_CONTAINS, "within": _lib.ROWPRED_WITHIN,
+                       "within_distance": _lib.ROWPRED_DISTANCE}
+
+    def _row_predicate(self, predicate: str, max_distance):
+        """``(GIQL_ROWPRED_* code, max_distance for the C call, the pad of :meth:`_groups`)``."""
+        if predicate not in self._ROW_PREDICATES:
+            raise ValueError(f"predicate must be one of {sorted(self._ROW_PREDICATES)}, not {predicate!r}")
+        if predicate != "within_distance":
+            return self._ROW_PREDICATES[predicate], 0, 0
+        if max_distance is None:
+            raise ValueError("within_distance needs max_distance")
+        max_distance = int(max_distance)
+        if max_distance < -1:
+            raise ValueError("max_distance must be >= -1 (-1: `< 0`, no pair)")
+        return self._ROW_PREDICATES[predicate], min(max_distance, (1 << 63) - 1), 2
+
+    def _check_row_pred(self, rc: int) -> None:
+        """:func:`_lib.check` with an inverted row under DISTANCE reported as :meth:`_window_once` reports it."""
+        try:
+            _lib.check(rc)
+        except _lib.GiqlHipError as exc:
+            if exc.code == _lib.GIQL_ERR_INVALID:
+                st = _lib.CStats()
+                _lib.check(self._L.giql_hip_get_stats(self._h, ctypes.byref(st)))
+                sides = tuple(s for s, v in (("a", st.n_irregular_a), ("b", st.n_irregular_b)) if int(v) == -1)
+                if sides:
+                    raise InvertedRows(sides, str(exc)) from exc
+            raise
+
+    def semi_anti_pred(self, a: DeviceSide, b: DeviceSide, n_chrom: int, predicate: str, anti: bool,
+                       max_distance=None):
+        """Ascending int32 ids of the ``a`` rows with (SEMI) / without (ANTI) a ``b`` row satisfying ``predicate``:
+        ``"contains"`` (a CONTAINS b), ``"within"`` (a WITHIN b) or ``"within_distance"`` (``DISTANCE(a, b) <=
+        max_distance``; -1 stands for ``< 0`` and selects no pair).  Exactly the left rows of :meth:`contain_join` /
+        :meth:`window_join` (``giql_hip_semi_anti_pred_dev``: one sort of ``b``, one prefix maximum, one binary
+        search per row -- no pair is written).  Zero-length rows follow the literal predicate, inverted rows too
+        under containment; DISTANCE raises :class:`InvertedRows` for them."""
+        self._check_sides(a, b)
+        code, md, pad = self._row_predicate(predicate, max_distance)
+        return self._wide(lambda sa, sb, _rows: self._semi_anti_pred_once(sa, sb, n_chrom, code, md, anti),
+                          lambda parts: wide.row_ids(parts, self.device), a, b, n_chrom, pad=pad)
+
+    def _semi_anti_pred_once(self, a: DeviceSide, b: DeviceSide, n_chrom: int, code: int, md: int, anti: bool):
+        torch = _torch()
+        rows = torch.empty(a.n, dtype=torch.int32, device=self.device)
+        n = ctypes.c_int64(0)
+        self._check_row_pred(self._L.giql_hip_semi_anti_pred_dev(
+            self._h, a.c_struct(), b.c_struct(), int(n_chrom), code, md, int(bool(anti)),
+            rows.data_ptr() if a.n else None, ctypes.byref(n), self._stream()))
+        return rows[: int(n.value)]
+
+    def count_pred(self, a: DeviceSide, b: DeviceSide, n_chrom: int, predicate: str, max_distance=None):
+        """int64 tensor: the number of ``b`` rows satisfying ``predicate`` per ``a`` row, in ``a``'s order (the
+        predicates of :meth:`semi_anti_pred`; ``giql_hip_count_pred_dev``).  DISTANCE is a rank difference over two
+        sorts of ``b``; containment walks the CONTAINS plan's candidate tiles and adds per row --
+        ``stats()["join_form"]`` is ``"uniform_b"`` when ``b`` has one length under ``"contains"`` (its range counts
+        are exact), else ``"general"``."""
+        self._check_sides(a, b)
+        code, md, pad = self._row_predicate(predicate, max_distance)
+        return self._wide(lambda sa, sb, _rows: self._count_pred_once(sa, sb, n_chrom, code, md),
+                          lambda parts: wide.per_row(parts, a.n, self.device), a, b, n_chrom, pad=pad)
+
+    def _count_pred_once(self, a: DeviceSide, b: DeviceSide, n_chrom: int, code: int, md: int):
+        torch = _torch()
+        # (no pre-fill: the library writes every slot -- its own memset where the tile walk adds into the counts)
+        counts = torch.empty(a.n, dtype=torch.int64, device=self.device)
+        self._check_row_pred(self._L.giql_hip_count_pred_dev(
+            self._h, a.c_struct(), b.c_struct(), int(n_chrom), code, md,
+            counts.data_ptr() if a.n else None, self._stream()))
+        return counts
+
     def distance(self, a: DeviceSide, b: DeviceSide, row_a, row_b, signed: bool = False, stranded: bool = False,
                  strand_a=None, strand_b=None):
         """``DISTANCE(a[row_a[i]], b[row_b[i]])`` per pair: ``(distance int64, valid uint8)`` device tensors, the

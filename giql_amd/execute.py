@@ -665,15 +665,63 @@ def _spatial_join(plan: JoinPlan, a: DeviceSide, b: DeviceSide, n_chrom: int, en
         try:
             return eng.window_join(a, b, n_chrom, plan.max_distance)
         except InvertedRows as exc:
-            bad = " and ".join(repr((plan.left if s == "a" else plan.right).table) for s in exc.sides)
-            raise ValueError(f"DISTANCE needs start <= end on every row: table {bad} has a row with "
-                             f"start > end") from exc
+            raise _inverted_rows_error(plan, exc) from exc
     if plan.predicate == "contains":
         return eng.contain_join(a, b, n_chrom)
     if plan.predicate == "within":
         rb, ra = eng.contain_join(b, a, n_chrom)
         return ra, rb
     return eng.inner_join(a, b, n_chrom)
+
+
+# SEMI / ANTI ("exists") and count_overlaps ("count") over CONTAINS / WITHIN / DISTANCE <= N, per form: True = execute()
+# calls HipEngine.semi_anti_pred / count_pred, False = it composes what existed before them (the pair join, then mark
+# + select, or a bincount of the left ids).  A form is on only where the new call's median lay below the
+# composition's whole spread at BOTH sizes of tools/row_predicates_timing.py (the rule of _INDEXED_NEAREST_FORMS);
+# a form that is off stays reachable through the engine method.  Measured (profiles/row_predicates_timing.json.log;
+# new ms against composed [min, max] ms at 1M x 10M, then at 100M x 10M; DESIGN.md "Row predicates" has the table):
+#   exists / contains          0.494 vs [0.622, 0.735]   6.74 vs [5.20, 5.47]    -> off (loses where no pair exists)
+#   exists / within            0.456 vs [0.827, 0.850]   7.07 vs [7.69, 7.91]    -> on
+#   exists / within_distance   0.461 vs [0.721, 0.733]   7.08 vs [23.3, 23.7]    -> on
+#   count  / contains          0.458 vs [0.746, 0.878]   5.43 vs [4.81, 4.92]    -> off (loses where no pair exists)
+#   count  / within            0.763 vs [0.769, 0.783]   8.09 vs [18.2, 18.3]    -> on (the small size by 0.006 ms)
+#   count  / within_distance   0.595 vs [1.227, 1.242]   7.48 vs [67.2, 67.8]    -> on
+_ROW_PREDICATE_FORMS = {
+    ("exists", "contains"): False, ("exists", "within"): True, ("exists", "within_distance"): True,
+    ("count", "contains"): False, ("count", "within"): True, ("count", "within_distance"): True,
+}
+
+
+def _inverted_rows_error(plan: JoinPlan, exc: InvertedRows) -> ValueError:
+    bad = " and ".join(repr((plan.left if s == "a" else plan.right).table) for s in exc.sides)
+    return ValueError(f"DISTANCE needs start <= end on every row: table {bad} has a row with start > end")
+
+
+def _row_pred_matched(plan: JoinPlan, a: DeviceSide, b: DeviceSide, n_chrom: int, eng: HipEngine, anti: bool):
+    """Ascending ids of the ``a`` rows with / without a ``b`` row under the plan's CONTAINS / WITHIN / DISTANCE
+    predicate: the engine's per-row call, or the pair join reduced by mark + select where that measured no slower
+    (``_ROW_PREDICATE_FORMS``)."""
+    if _ROW_PREDICATE_FORMS[("exists", plan.predicate)]:
+        try:
+            return eng.semi_anti_pred(a, b, n_chrom, plan.predicate, anti, plan.max_distance)
+        except InvertedRows as exc:
+            raise _inverted_rows_error(plan, exc) from exc
+    ra, _rb = _spatial_join(plan, a, b, n_chrom, eng)
+    flags = eng.mark(ra.contiguous(), a.n)
+    return eng.select([(("a", flags), "=", ("lit", 0 if anti else 1))], n=a.n, n_rows_a=a.n, want=("a",))[0]
+
+
+def _row_pred_counts(plan: JoinPlan, a: DeviceSide, b: DeviceSide, n_chrom: int, eng: HipEngine):
+    """int64 device tensor: the ``b`` rows under the plan's predicate per ``a`` row (``_row_pred_matched``'s twin)."""
+    if _ROW_PREDICATE_FORMS[("count", plan.predicate)]:
+        try:
+            return eng.count_pred(a, b, n_chrom, plan.predicate, plan.max_distance)
+        except InvertedRows as exc:
+            raise _inverted_rows_error(plan, exc) from exc
+    import torch
+
+    ra, _rb = _spatial_join(plan, a, b, n_chrom, eng)
+    return torch.bincount(ra.long(), minlength=a.n)   # (plumbing: the pair ids are already reduced to one column)
 
 
 def _pair_distances(plan: JoinPlan, lt, rt, a: DeviceSide, b: DeviceSide, ra, rb, eng: HipEngine) -> dict:
@@ -732,6 +780,8 @@ def _join_with_residuals(plan: JoinPlan, lt, rt, a: DeviceSide, b: DeviceSide, n
         if not semi:
             return ra, rb
         matched = ra
+    elif plan.predicate != "intersects":
+        matched = globalise(_row_pred_matched(plan, a_sub, b_sub, n_chrom, eng, False), ids_a)
     else:
         matched = globalise(eng.semi_anti(a_sub, b_sub, n_chrom, False), ids_a)
     flags = eng.mark(matched.contiguous(), a.n)
@@ -1463,6 +1513,8 @@ def _join_piece(plan: JoinPlan, lt, rt, ia: np.ndarray, ib: np.ndarray, n_chrom:
     if sides_out is not None:     # (what the caller goes on with: COUNT's GROUP BY reads the left side again)
         sides_out["l"], sides_out["r"] = a, b
     if plan.kind == "COUNT":
+        if plan.predicate != "intersects":
+            return _row_pred_counts(plan, a, b, n_chrom, eng)
         return eng.count_overlaps(a, b, n_chrom)   # device int64, one per left row
     extra = {}
     if plan.kind == "INNER":
@@ -1483,6 +1535,8 @@ def _join_piece(plan: JoinPlan, lt, rt, ia: np.ndarray, ib: np.ndarray, n_chrom:
     elif plan.kind in ("SEMI", "ANTI"):
         if plan.residuals:
             rows = _join_with_residuals(plan, lt, rt, a, b, n_chrom, eng)
+        elif plan.predicate != "intersects":
+            rows = _row_pred_matched(plan, a, b, n_chrom, eng, plan.kind == "ANTI")
         else:
             rows = eng.semi_anti(a, b, n_chrom, plan.kind == "ANTI")
         if return_indices:
@@ -1626,9 +1680,9 @@ def _execute_sharded(plan: JoinPlan, lt, rt, ia, ib, n_chrom, devices, return_in
 
 
 def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, return_indices=False,
-            device_projection: bool = True, devices=None, outer_joins: bool = False):
-    """Run *plan* (a :class:`JoinPlan`, its string form, or a GIQL query string; ``outer_joins`` as in
-    :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
+            device_projection: bool = True, devices=None, outer_joins: bool = False, row_predicates: bool = False):
+    """Run *plan* (a :class:`JoinPlan`, its string form, or a GIQL query string; ``outer_joins`` and
+    ``row_predicates`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
     (``{name: pyarrow.Table | dict of arrays}``).
 
     Returns a ``pyarrow.Table`` with the plan's projected columns (bag semantics,
@@ -1648,7 +1702,8 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
     first one.
     """
     if isinstance(plan, str):
-        plan = JoinPlan.from_string(plan) if is_plan_string(plan) else build_plan(plan, giql_tables, outer_joins=outer_joins)
+        plan = JoinPlan.from_string(plan) if is_plan_string(plan) else build_plan(
+            plan, giql_tables, outer_joins=outer_joins, row_predicates=row_predicates)
     if not isinstance(plan, JoinPlan):
         raise ValueError("plan must be a JoinPlan, a plan string or a GIQL query")
     devices = [int(d) for d in devices] if devices is not None else None
@@ -1673,6 +1728,9 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
     if plan.kind == "LEFT" and devices is not None and len(devices) > 1:
         raise NotImplementedError(f"a LEFT OUTER join runs on one device; devices={devices!r} names {len(devices)} "
                                   "(the per-chromosome fan-out does not pad unmatched rows yet)")
+    if plan.row_predicates and devices is not None and len(devices) > 1:
+        raise NotImplementedError(f"SEMI / ANTI / COUNT over {plan.predicate.upper()} run on one device; "
+                                  f"devices={devices!r} names {len(devices)}")
     if plan.predicate != "intersects" and devices is not None and len(devices) > 1:
         # one device, like DISJOIN: the per-chromosome fan-out shards an INTERSECTS join
         raise ValueError(f"{plan.predicate.upper()} joins run on one device; devices={devices!r} names {len(devices)}")

@@ -19,6 +19,9 @@ KINDS = ("INNER", "SEMI", "ANTI", "NEAREST", "COUNT", "CLUSTER", "MERGE", "FILTE
 #: row per left row that keeps none (its ON residuals take part in matching, its WHERE residuals filter the result)
 PAIR_KINDS = ("INNER", "LEFT")
 
+#: the kinds that keep one flag or one integer per left row
+ROW_KINDS = ("SEMI", "ANTI", "COUNT")
+
 #: the spatial predicate of an INNER plan
 PREDICATES = ("intersects", "contains", "within", "within_distance")
 
@@ -142,13 +145,18 @@ class JoinPlan:
     # qualifies, the query compared with < 0).  A stranded "pair_distance" projection reads strand_col
     # ("<left column>,<right column>", as stranded NEAREST does)
     predicate: str = "intersects"
+    # SEMI / ANTI / COUNT over "contains" / "within" / "within_distance" (HipEngine.semi_anti_pred / count_pred):
+    # only plans lowered with the ``row_predicates`` opt-in carry such a predicate, and they say so here
+    row_predicates: bool = False
 
     def __post_init__(self) -> None:
         if self.kind not in KINDS:
             raise ValueError(f"unknown plan kind {self.kind!r}")
         if self.predicate not in PREDICATES:
             raise ValueError(f"unknown join predicate {self.predicate!r}")
-        if self.predicate != "intersects" and self.kind not in PAIR_KINDS:
+        if self.row_predicates and (self.kind not in ROW_KINDS or self.predicate == "intersects"):
+            raise ValueError("row_predicates marks a SEMI / ANTI / COUNT plan over CONTAINS / WITHIN / DISTANCE only")
+        if self.predicate != "intersects" and self.kind not in PAIR_KINDS and not self.row_predicates:
             raise ValueError(f"predicate {self.predicate!r} needs an INNER plan, not {self.kind}")
         if self.predicate == "within_distance" and not isinstance(self.max_distance, int):
             raise ValueError("predicate 'within_distance' needs an integer max_distance")
@@ -192,7 +200,7 @@ class JoinPlan:
             group_by=tuple(d.get("group_by", ())),
             order_by=tuple((o[0], bool(o[1]), bool(o[2]) if len(o) > 2 else not bool(o[1])) for o in d.get("order_by", ())),
             limit=d.get("limit"), offset=d.get("offset"), output=tuple(d.get("output", ())),
-            predicate=d.get("predicate", "intersects"))
+            predicate=d.get("predicate", "intersects"), row_predicates=d.get("row_predicates", False))
 
 
 def is_plan_string(text) -> bool:

@@ -265,6 +265,9 @@ class JoinShape:
     sides: tuple[PlanSide, PlanSide] | None = None
     # opt-in: a LEFT [OUTER] JOIN outside the count_overlaps shape lowers to a LEFT plan instead of declining
     outer_joins: bool = False
+    # opt-in: SEMI / ANTI joins and the count_overlaps shape over CONTAINS / WITHIN / DISTANCE <= N lower to SEMI /
+    # ANTI / COUNT plans carrying that predicate instead of declining
+    row_predicates: bool = False
 
 
 # ------------------------------------------------------------------ helpers
@@ -750,20 +753,22 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
         raise decline("LEFT join with its spatial predicate outside ON")
     predicate, lhs, rhs = spatial[0][:3]
     max_distance = spatial[0][3] if predicate == DISTANCE_TERM else None
-    if kind == "LEFT" and predicate == "intersects":
+    if kind == "LEFT" and (predicate == "intersects" or shape.row_predicates):
         # bedtools -v: LEFT JOIN ... WHERE b.<chrom | start | end> IS NULL with no other use of the right table is
         # the ANTI join (a matched row's right key columns are never NULL) -- semi_anti, not pairs thrown away
         rest = _anti_shortcut(shape, where_terms, right)
         if rest is not None:
             kind, where_terms = "ANTI", rest
     label = "DISTANCE" if predicate == DISTANCE_TERM else predicate.upper()
-    if predicate != "intersects":
+    row_pred = predicate != "intersects" and shape.row_predicates and kind in ("SEMI", "ANTI", "COUNT")
+    if predicate != "intersects" and not shape.row_predicates:
         # CONTAINS / WITHIN / DISTANCE <= N run as the pair-producing join only (HipEngine.contain_join / window_join)
+        # unless the caller opted in (JoinShape.row_predicates): HipEngine.semi_anti_pred / count_pred
         if kind in ("SEMI", "ANTI"):
             raise decline(f"{kind} join over {label}")
         if kind == "COUNT":
             raise decline(f"count_overlaps over {label}")
-    if kind in ("SEMI", "ANTI") and not any(t[0] == "intersects" for t in on_terms):
+    if kind in ("SEMI", "ANTI") and not any(t[0] == "intersects" or (row_pred and t[0] in JOIN_TERMS) for t in on_terms):
         raise decline("SEMI/ANTI join with its INTERSECTS outside ON")  # #201
     cmp_terms = ([("on", t) for t in on_terms if t[0] in ("cmp", "or", "tree")]
                  + [("where", t) for t in where_terms if t[0] in ("cmp", "or", "tree")])
@@ -797,7 +802,8 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
             raise decline("DISTINCT with count_overlaps")
         if shape.order_by or shape.limit is not None or shape.offset is not None or shape.having:
             raise decline("HAVING / ORDER BY / LIMIT over count_overlaps")
-        return JoinPlan("COUNT", left, right, resolve_count_projection(items, shape.group_by, left, right))
+        return JoinPlan("COUNT", left, right, resolve_count_projection(items, shape.group_by, left, right),
+                        max_distance=max_distance if row_pred else None, predicate=predicate, row_predicates=row_pred)
 
     left_only = kind in ("SEMI", "ANTI")
     grouped = bool(shape.group_by) or any(it.func is not None for it in items) or bool(shape.having)
@@ -827,7 +833,8 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
     return JoinPlan(kind, left, right, tuple(proj) + hidden, shape.distinct, max_distance=max_distance,
                     residuals=residuals, strand_col=strand_col,
                     aggregates=aggs, group_by=groups, having=having, order_by=order,
-                    limit=shape.limit, offset=shape.offset, output=output, predicate=predicate)
+                    limit=shape.limit, offset=shape.offset, output=output, predicate=predicate,
+                    row_predicates=row_pred)
 
 
 def _col_refs(x):

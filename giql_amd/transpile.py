@@ -1103,12 +1103,14 @@ def _lower_disjoin(p: _Parser, tbls: Tables) -> JoinPlan:
     return lower_disjoin_shape(shape, tbls)
 
 
-def build_plan(giql: str, tables=None, *, outer_joins: bool = False) -> JoinPlan:
+def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predicates: bool = False) -> JoinPlan:
     """Parse *giql* and lower the INTERSECTS / NEAREST join (or a CLUSTER / MERGE
     query) to a :class:`JoinPlan`.
 
     ``outer_joins=True`` opts in to LEFT [OUTER] JOIN: outside the count_overlaps shape it lowers to a plan of
-    kind ``LEFT`` (or ``ANTI``, for the ``WHERE b.<key> IS NULL`` recipe) instead of declining."""
+    kind ``LEFT`` (or ``ANTI``, for the ``WHERE b.<key> IS NULL`` recipe) instead of declining.
+    ``row_predicates=True`` opts in to SEMI / ANTI joins and the count_overlaps shape over CONTAINS, WITHIN and
+    ``DISTANCE(...) <= N``: they lower to SEMI / ANTI / COUNT plans carrying that predicate instead of declining."""
     probe = _Parser(giql)
     if _disjoin_from(probe) is not None:
         return _lower_disjoin(probe, tables if isinstance(tables, Tables) else build_tables(tables))
@@ -1116,12 +1118,12 @@ def build_plan(giql: str, tables=None, *, outer_joins: bool = False) -> JoinPlan
         return _lower_cluster(probe, tables if isinstance(tables, Tables) else build_tables(tables))
     if probe.at_kw("SELECT") and _is_single_table_filter(probe):
         return _lower_filter(probe, tables if isinstance(tables, Tables) else build_tables(tables))
-    plan = _lower(giql, tables, want_sql=False, outer_joins=outer_joins)
+    plan = _lower(giql, tables, want_sql=False, outer_joins=outer_joins, row_predicates=row_predicates)
     assert isinstance(plan, JoinPlan)
     return plan
 
 
-def _lower(giql: str, tables, want_sql: bool, outer_joins: bool = False):
+def _lower(giql: str, tables, want_sql: bool, outer_joins: bool = False, row_predicates: bool = False):
     tbls = tables if isinstance(tables, Tables) else build_tables(tables)
     p = _Parser(giql)
     if p.at_kw("WITH"):
@@ -1225,7 +1227,7 @@ def _lower(giql: str, tables, want_sql: bool, outer_joins: bool = False):
                         stranded=nearest[3], strand_col=strand_col)
 
     shape = JoinShape(items=items, from_ref=from_ref, join_ref=join_ref, kind=kind, on_seen=on_seen, using=using,
-                      distinct=distinct, outer_joins=bool(outer_joins))
+                      distinct=distinct, outer_joins=bool(outer_joins), row_predicates=bool(row_predicates))
     if on_seen:
         if p.peek().kind not in ("id", "num", "str") and not p.at_punct("-") and not p.at_punct("(") \
                 and not p.at_kw("NOT"):
@@ -1309,17 +1311,18 @@ def _render(toks: list[Tok]) -> str:
     return out
 
 
-def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins: bool = False) -> str:
+def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins: bool = False,
+              row_predicates: bool = False) -> str:
     """Mirror of ``giql.transpile`` for this backend's path.
 
     ``dialect="hip"``: returns the plan string of the INTERSECTS / NEAREST join
     (hand it to :func:`giql_amd.execute`); ``outer_joins=True`` lets a LEFT [OUTER] JOIN lower too
-    (:func:`build_plan`).  ``dialect=None``: returns SQL for the
+    and ``row_predicates=True`` the per-row joins over CONTAINS / WITHIN / DISTANCE (:func:`build_plan`).  ``dialect=None``: returns SQL for the
     literal-range predicate (plumbing, BASELINE config 1).  Other dialects belong to
     the reference package.
     """
     if dialect == "hip":
-        return build_plan(giql, tables, outer_joins=outer_joins).to_string()
+        return build_plan(giql, tables, outer_joins=outer_joins, row_predicates=row_predicates).to_string()
     if dialect is None:
         return _lower(giql, tables, want_sql=True)
     raise ValueError(

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define GIQL_HIP_ABI_VERSION 4  /* 2: giql_hip_stats.phase_bytes, pinned host outputs, plan export; 3: DISJOIN; 4: CONTAINS / WITHIN (DISTANCE added two symbols, left_pad one: no change) */
+#define GIQL_HIP_ABI_VERSION 4  /* 2: giql_hip_stats.phase_bytes, pinned host outputs, plan export; 3: DISJOIN; 4: CONTAINS / WITHIN (DISTANCE added two symbols, left_pad one, the row predicates two: no change) */
 
 enum {
   GIQL_OK = 0,
@@ -328,6 +328,31 @@ int giql_hip_window_plan_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_s
 int giql_hip_distance_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, const int32_t* row_a,
                           const int32_t* row_b, int64_t n, const int32_t* strand_a, const int32_t* strand_b,
                           int32_t flags, int64_t* dist_out, uint8_t* valid_out, void* stream);
+/* The per-row forms of the three pair predicates that are not INTERSECTS, on canonical coordinates:
+ *   GIQL_ROWPRED_CONTAINS  a.chrom = b.chrom AND a.start <= b.start AND a.end >= b.end
+ *   GIQL_ROWPRED_WITHIN    the same with the operands exchanged
+ *   GIQL_ROWPRED_DISTANCE  DISTANCE(a, b) <= max_distance (giql_hip_window_plan_dev's predicate)
+ * giql_hip_semi_anti_pred_dev: rows_out = the ids of the A rows with at least one (anti = 0) / no (anti != 0) B row
+ * satisfying the predicate, ascending, *n_out of them (rows_out holds a->n ids).  giql_hip_count_pred_dev:
+ * counts_out[i] = the number of B rows satisfying it with A row i.  Both equal exactly what giql_hip_contain_plan_dev /
+ * giql_hip_window_plan_dev give when their pairs are reduced per A row, for every row shape those accept: zero-length
+ * rows follow the literal predicate, and so do inverted rows under CONTAINS / WITHIN; DISTANCE needs start <= end on
+ * every row of both sides (GIQL_ERR_INVALID names the side, n_irregular_a / n_irregular_b = -1, as the window plan).
+ * max_distance is read for GIQL_ROWPRED_DISTANCE only; -1 (`< 0`) selects no pair: an empty SEMI, every row for ANTI,
+ * all-zero counts.  An empty B is answered without spanning or sorting anything.  Existence is one sort of B, one prefix maximum and one binary
+ * search per A row; the DISTANCE count is a rank difference over two sorts of B; the containment count walks the
+ * CONTAINS plan's candidate tiles (stats.reserved bits 0-3: 0 general, 1 uniform B under CONTAINS, whose range counts
+ * are exact).  stats.n_irregular_a / n_irregular_b: the rows settled by the literal predicate (counts only).
+ * GIQL_ERR_CHROM / GIQL_ERR_SPAN as for the INNER join.  Like every call that launches work, both drop an INNER,
+ * contain or DISJOIN plan held in the context: its fill returns GIQL_ERR_STATE. */
+#define GIQL_ROWPRED_CONTAINS 1   /* a CONTAINS b */
+#define GIQL_ROWPRED_WITHIN   2   /* a WITHIN b   */
+#define GIQL_ROWPRED_DISTANCE 3   /* DISTANCE(a, b) <= max_distance; max_distance is read for this one only */
+int giql_hip_semi_anti_pred_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, int32_t n_chrom,
+                                int32_t pred, int64_t max_distance, int anti, int32_t* rows_out, int64_t* n_out,
+                                void* stream);
+int giql_hip_count_pred_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, int32_t n_chrom, int32_t pred,
+                            int64_t max_distance, int64_t* counts_out, void* stream);
 /* MERGE(..., predicate := ...): merge.py:201-210 hands the predicate to the CLUSTER it is built on, so a
  * merged region is a cluster of giql_hip_cluster_pred_dev; its MAX(end) is taken over the region's own
  * rows (a region may end while an earlier one still reaches further). */
