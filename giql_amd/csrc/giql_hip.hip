@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <atomic>
+#include <initializer_list>
 #include <memory>
 #include <sys/mman.h>
 #include <utility>
@@ -396,6 +397,12 @@ static int begin_pair_call(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
   return GIQL_OK;
 }
 
+// the onesweep sort's status words count rows in 30 bits
+static int check_rows_fit(size_t na, size_t nb) {
+  if (na > OS_MAX_ROWS || nb > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
+  return GIQL_OK;
+}
+
 // Clears the prezeroed state (and the unstable first pass that goes with the INNER plan's) when a call's frame ends:
 // the sort helpers zero their own histograms and status words again.
 struct PrezeroGuard {
@@ -429,6 +436,12 @@ static void collect_spans(giql_hip_ctx* ctx) {
   for (int i = 0; i < GIQL_PH_N; i++) t += ctx->stats.phase_ms[i];
   ctx->stats.total_ms = t;
   ctx->stats.profiled = 1;
+}
+
+// The axis the last read-back saw: reported, and the density the next call's sort form follows.
+static void note_span(giql_hip_ctx* ctx) {
+  ctx->stats.span = (int64_t)ctx->h_meta->total_span;
+  ctx->guess.last_span = ctx->h_meta->total_span;
 }
 
 // ------------------------------------------------------------ small helpers
@@ -534,6 +547,21 @@ struct LinBufs {
 static inline int sort_local_bits(const giql_hip_ctx* ctx, size_t n);
 static inline bool sort_is_local(const giql_hip_ctx* ctx, size_t n) { return sort_local_bits(ctx, n) != 0; }
 
+// The range of the two sides' canonical offsets, widened by `pad`: the positions every chromosome gets beyond its
+// rows' range on either end (the within-distance forms: 1, for the clamped ends of their widened rows --
+// distance_kernels.hip.h).  run_spans hands the two numbers to k_chrom_offsets and key_widened_side clamps to them:
+// both take them from here.
+static void window_pads(const giql_side& a, const giql_side& b, int pad, int& lo_pad, int& hi_pad) {
+  lo_pad = hi_pad = a.start_off;
+  const int offs[3] = {a.end_off, b.start_off, b.end_off};
+  for (int k = 0; k < 3; k++) {
+    if (offs[k] < lo_pad) lo_pad = offs[k];
+    if (offs[k] > hi_pad) hi_pad = offs[k];
+  }
+  lo_pad -= pad;
+  hi_pad += pad;
+}
+
 // hist_side = 0 / 1 (with hist_partial and lb.abase / lb.top_partial): that side's span pass
 // also counts the digits of its aligned keys (k_chrom_minmax<true>) and the chromosome bases
 // are laid out 2^24-aligned when they fit (meta->aligned_ok).
@@ -605,16 +633,8 @@ static int run_spans(giql_hip_ctx* ctx, hipStream_t st, const giql_side& a, cons
                          (i64)s.n, n_chrom, lb.gmin, lb.gmax, ctx->d_meta, s.end_off - s.start_off, k,
                          lb.len_part, 0, (u32*)nullptr, (u32*)nullptr);
   }
-  int omin = a.start_off, omax = a.start_off;
-  const int offs[3] = {a.end_off, b.start_off, b.end_off};
-  for (int k = 0; k < 3; k++) {
-    if (offs[k] < omin) omin = offs[k];
-    if (offs[k] > omax) omax = offs[k];
-  }
-  // pad: positions every chromosome gets beyond its range on either end (the within-distance join: 1, for the
-  // clamped ends of its widened rows -- distance_kernels.hip.h)
-  omin -= pad;
-  omax += pad;
+  int omin, omax;
+  window_pads(a, b, pad, omin, omax);
   hipLaunchKernelGGL(k_chrom_offsets, dim3(1), dim3(256), 0, st, lb.gmin, lb.gmax, n_chrom, omin,
                      omax, lb.chrom_base, lb.chrom_first, ctx->d_meta, lb.len_part, nblk[0], nblk[1],
                      hist ? 1 : 0, lb.abase);
@@ -955,17 +975,28 @@ static int run_sort_onesweep(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u3
   return post_launch("onesweep sort");
 }
 
-// A two-key sort's FIRST sort runs on a view of the buffers with key and end exchanged.  run_sort_onesweep leaves its
-// result in what it then CALLS buffer 0 -- after an odd number of passes (three: a query side sorted without its lowest
-// digit, a side with buckets narrower than 2^16 keys) that is the other physical buffer, and it says so by exchanging the
-// view's pointers.  The owner of the buffers has to follow, or its second sort starts from the unsorted copy (round 4:
-// found by the soak on a context forced to 8,192-key buckets -- ties among equal starts came out in input order).
-static inline void adopt_by_end(SortBufs& owner, const SortBufs& by_end) {
+// The stable two-key sort: (key, end) lexicographic order = stable sort by end, then stable sort by key (which keeps the
+// row ids the first sort left).  gbase_key / gbase_end: the digit bases of the two columns; both sorts go through the
+// one set of status words.
+// The FIRST sort runs on a view of the buffers with key and end exchanged.  run_sort_onesweep leaves its result in what
+// it then CALLS buffer 0 -- after an odd number of passes (three: a query side sorted without its lowest digit, a side
+// with buckets narrower than 2^16 keys) that is the other physical buffer, and it says so by exchanging the view's
+// pointers.  The owner of the buffers has to follow, or its second sort starts from the unsorted copy (round 4: found
+// by the soak on a context forced to 8,192-key buckets -- ties among equal starts came out in input order).
+static int run_sort_two_keys(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u32 n, const u32* gbase_key,
+                             const u32* gbase_end, u32* status) {
+  SortBufs by_end = sb;
   for (int k = 0; k < 2; k++) {
-    owner.end[k] = by_end.key[k];
-    owner.key[k] = by_end.end[k];
-    owner.rid[k] = by_end.rid[k];
+    by_end.key[k] = sb.end[k];
+    by_end.end[k] = sb.key[k];
   }
+  GIQL_TRY(run_sort_onesweep(ctx, st, by_end, n, gbase_end, status));
+  for (int k = 0; k < 2; k++) {
+    sb.end[k] = by_end.key[k];
+    sb.key[k] = by_end.end[k];
+    sb.rid[k] = by_end.rid[k];
+  }
+  return run_sort_onesweep(ctx, st, sb, n, gbase_key, status, /*keep_rids=*/true);
 }
 
 // Stable LSD radix sort; input in buffer 0, result in buffer 0 (4 passes).
@@ -1045,6 +1076,25 @@ static void sort_sizes(Carver& c, size_t n, SortBufs& sb, bool payload) {
     sb.key[k] = c.take<u32>(n);
     sb.end[k] = payload ? c.take<u32>(n) : nullptr;
     sb.rid[k] = payload ? c.take<u32>(n) : nullptr;
+  }
+}
+
+// (sort key, one payload column), no row ids: B of SEMI / ANTI and of their predicate form
+static void sort_sizes_key_payload(Carver& c, size_t n, SortBufs& sb) {
+  for (int k = 0; k < 2; k++) {
+    sb.key[k] = c.take<u32>(n);
+    sb.end[k] = c.take<u32>(n);
+    sb.rid[k] = nullptr;
+  }
+}
+
+// two keys-only sorts of one side, its starts and its ends: B of COUNT and of COUNT over DISTANCE
+static void sort_sizes_starts_ends(Carver& c, size_t n, SortBufs& sstart, SortBufs& send) {
+  for (int k = 0; k < 2; k++) {
+    sstart.key[k] = c.take<u32>(n);
+    sstart.end[k] = sstart.rid[k] = nullptr;
+    send.key[k] = c.take<u32>(n);
+    send.end[k] = send.rid[k] = nullptr;
   }
 }
 
@@ -2194,6 +2244,44 @@ int giql_hip_inner_join_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_si
 }
 
 // ------------------------------------------------- within-distance join / DISTANCE
+// DISTANCE needs start <= end on every row of both sides; which side does not: for callers in giql_hip_stats
+// (n_irregular_a / n_irregular_b = -1), not only in the message.
+static int reject_inverted(giql_hip_ctx* ctx) {
+  if (!ctx->h_meta->inverted_a && !ctx->h_meta->inverted_b) return GIQL_OK;
+  if (ctx->h_meta->inverted_a) ctx->stats.n_irregular_a = -1;
+  if (ctx->h_meta->inverted_b) ctx->stats.n_irregular_b = -1;
+  return set_err(GIQL_ERR_INVALID, "DISTANCE: side %s has a row with start > end", ctx->h_meta->inverted_a ? "a" : "b");
+}
+
+// coordinates of one chromosome are less than 2^32 + 2 apart: a larger N selects the same pairs, and the sums of the
+// widened rows stay far from the ends of int64
+static inline i64 clamp_widen(int64_t max_distance) {
+  return max_distance > ((i64)1 << 33) ? ((i64)1 << 33) : (i64)max_distance;
+}
+
+// A widened by `widen` on both ends and keyed on the axis run_spans(pad = 1) laid out over the sides a and b, its
+// ends clamped to that padding; with the digit histogram and bases of its sort.  irr_list: rows left zero-length get
+// the sentinel key and a place in the list (k_window_linearize); nullptr: every row keeps its key (k_rp_window_keys).
+static int key_widened_side(giql_hip_ctx* ctx, hipStream_t st, const giql_side& a, const giql_side& b, int n_chrom,
+                            const LinBufs& lb, i64 widen, SortBufs& sa, u32* irr_list, u32* hist, u32* gbase) {
+  int lo_pad, hi_pad;
+  window_pads(a, b, /*pad=*/1, lo_pad, hi_pad);
+  HIP_TRY(hipMemsetAsync(hist, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
+  Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
+  u32 grid = cdiv((u64)a.n, LIN_NT);
+  if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
+  if (irr_list)
+    hipLaunchKernelGGL(k_window_linearize, dim3(grid), dim3(LIN_NT), 0, st, a.chrom, a.start, a.end, (u32)a.n,
+                       a.start_off, a.end_off, n_chrom, lb.chrom_base, lb.gmin, lb.gmax, lo_pad, hi_pad, widen,
+                       sa.key[0], sa.end[0], irr_list, ctx->d_meta, hist);
+  else
+    hipLaunchKernelGGL(k_rp_window_keys, dim3(grid), dim3(LIN_NT), 0, st, a.chrom, a.start, a.end, (u32)a.n,
+                       a.start_off, a.end_off, n_chrom, lb.chrom_base, lb.gmin, lb.gmax, lo_pad, hi_pad, widen,
+                       sa.key[0], sa.end[0], ctx->d_meta, hist);
+  hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, hist, (u32)LIN_HIST_REPLICAS, gbase);
+  return post_launch(irr_list ? "window linearize" : "row predicate window keys");
+}
+
 // giql_hip_window_plan_dev: the pairs with DISTANCE(a, b) <= max_distance, as an INNER plan that giql_hip_inner_fill_dev
 // fills (distance_kernels.hip.h has the equivalence and the clamp).  ONE form is routed, the general two-class one, in
 // its plainest shape: span pass padded by one position per chromosome end -> ONE read-back (chrom ids, the 32-bit
@@ -2227,10 +2315,8 @@ static int giql_hip_window_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* a, 
     return GIQL_OK;
   }
   const size_t na = (size_t)a->n, nb = (size_t)b->n, nq = na + nb;
-  if (na > OS_MAX_ROWS || nb > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
-  // coordinates of one chromosome are less than 2^32 + 2 apart: a larger N selects the same pairs, and the sums below
-  // stay far from the ends of int64
-  const i64 widen = max_distance > ((i64)1 << 33) ? ((i64)1 << 33) : (i64)max_distance;
+  GIQL_TRY(check_rows_fit(na, nb));
+  const i64 widen = clamp_widen(max_distance);
   InnerState& S = P.inner;
   InnerScratch W;
   constexpr u32 TQ2 = RC_NT * RC_ITEMS_C2;
@@ -2242,37 +2328,13 @@ static int giql_hip_window_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* a, 
   GIQL_TRY(claim_arena(ctx, st, [&](char* base) { return carve_inner(ctx, base, na, nb, n_chrom, true, W); }));
   GIQL_TRY(run_spans(ctx, st, *a, *b, n_chrom, W.lb, -1, nullptr, /*pad=*/1));
   GIQL_TRY(read_meta(ctx, st));
-  if (ctx->h_meta->inverted_a || ctx->h_meta->inverted_b) {
-    // which side: for callers in giql_hip_stats (n_irregular_a / n_irregular_b = -1), not only in the message
-    if (ctx->h_meta->inverted_a) ctx->stats.n_irregular_a = -1;
-    if (ctx->h_meta->inverted_b) ctx->stats.n_irregular_b = -1;
-    return set_err(GIQL_ERR_INVALID, "DISTANCE: side %s has a row with start > end",
-                   ctx->h_meta->inverted_a ? "a" : "b");
-  }
+  GIQL_TRY(reject_inverted(ctx));
   ctx->guess.last_span = ctx->h_meta->total_span;  // known before anything is sorted: the sort form follows the real density
   SortBufs& sa = S.sa;
   SortBufs& sbb = S.sb;
   u32* const status_a = na <= nb ? W.os_status2 : W.os_status;
   u32* const status_b = na <= nb ? W.os_status : W.os_status2;
-  {
-    int lo_pad = a->start_off, hi_pad = a->start_off;
-    const int offs[3] = {a->end_off, b->start_off, b->end_off};
-    for (int k = 0; k < 3; k++) {
-      if (offs[k] < lo_pad) lo_pad = offs[k];
-      if (offs[k] > hi_pad) hi_pad = offs[k];
-    }
-    lo_pad -= 1;  // run_spans(pad = 1) handed the same two numbers to k_chrom_offsets
-    hi_pad += 1;
-    HIP_TRY(hipMemsetAsync(W.hist[0], 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
-    Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
-    u32 grid = cdiv((u64)na, LIN_NT);
-    if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
-    hipLaunchKernelGGL(k_window_linearize, dim3(grid), dim3(LIN_NT), 0, st, a->chrom, a->start, a->end, (u32)na,
-                       a->start_off, a->end_off, n_chrom, W.lb.chrom_base, W.lb.gmin, W.lb.gmax, lo_pad, hi_pad, widen,
-                       sa.key[0], sa.end[0], P.irr_a_list, ctx->d_meta, W.hist[0]);
-    hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, W.hist[0], (u32)LIN_HIST_REPLICAS, W.gbase[0]);
-    GIQL_TRY(post_launch("window linearize"));
-  }
+  GIQL_TRY(key_widened_side(ctx, st, *a, *b, n_chrom, W.lb, widen, sa, P.irr_a_list, W.hist[0], W.gbase[0]));
   GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, W.lb, sbb.key[0], sbb.end[0], P.irr_b_list, 1, 0, W.hist[1], W.gbase[1]));
   GIQL_TRY(run_sort_onesweep(ctx, st, sa, (u32)na, W.gbase[0], status_a));
   GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, W.gbase[1], status_b));
@@ -2957,26 +3019,50 @@ struct OsScratch {
   u32* status = nullptr;
 };
 
-// ONE memset for everything two sides' histograms and sort passes need at zero, instead of one per histogram and per
-// sort (four launches of ~5 us on a path of ~60): `first` is carved right before `second`, so the range runs from
-// first's histograms to the end of second's four passes of status words.  Only for calls that sort each side ONCE (a
-// second sort through the same status words must zero them again: ctx->call.prezeroed makes the helpers skip theirs).
-static int prezero_row_scratch(giql_hip_ctx* ctx, hipStream_t st, const OsScratch& first, const OsScratch& second,
-                               size_t n_second) {
-  char* const lo = reinterpret_cast<char*>(first.hist);
-  char* const hi = reinterpret_cast<char*>(second.status + 4 * os_pass_stride(ctx, n_second));
-  if (!first.hist || hi <= lo) return GIQL_OK;
-  HIP_TRY(hipMemsetAsync(lo, 0, (size_t)(hi - lo), st));
-  ctx->call.prezeroed = true;
-  return GIQL_OK;
-}
-
 static void os_scratch_sizes(Carver& c, size_t n_max, OsScratch& o) {
   o.hist = c.take<u32>((size_t)LIN_HIST_REPLICAS * 1024);
   o.hist_e = c.take<u32>((size_t)LIN_HIST_REPLICAS * 1024);
   o.gbase = c.take<u32>(1024);
   o.gbase_e = c.take<u32>(1024);
   o.status = c.take<u32>(4 * os_pass_words(n_max));
+}
+
+// The scratch of an operator that sorts both sides: A's own (its chain may run beside B's: SideChain), then B's, one
+// range of the workspace that only os_pair_sizes lays out.
+struct OsScratchPair {
+  OsScratch a, b;
+  // ONE memset for everything the two sides' histograms and sort passes need at zero, instead of one per histogram and
+  // per sort (four launches of ~5 us on a path of ~60): from a's histograms to the end of b's four passes of status
+  // words for n_b rows.  Only for calls that sort each side ONCE (a second sort through the same status words must
+  // zero them again: ctx->call.prezeroed makes the helpers skip theirs).
+  int prezero(giql_hip_ctx* ctx, hipStream_t st, size_t n_b) const {
+    char* const lo = reinterpret_cast<char*>(a.hist);
+    char* const hi = reinterpret_cast<char*>(b.status + 4 * os_pass_stride(ctx, n_b));
+    if (!a.hist || hi <= lo) return GIQL_OK;
+    HIP_TRY(hipMemsetAsync(lo, 0, (size_t)(hi - lo), st));
+    ctx->call.prezeroed = true;
+    return GIQL_OK;
+  }
+};
+
+// `inside`: words of the caller's that prezero() is to zero with the rest (NEAREST's digit counts of the span pass),
+// carved between the two sides' scratch.
+struct ExtraWords {
+  u32** at;
+  size_t n;
+};
+static void os_pair_sizes(Carver& c, size_t na, size_t nb, OsScratchPair& o, std::initializer_list<ExtraWords> inside = {}) {
+  os_scratch_sizes(c, na, o.a);
+  for (const ExtraWords& x : inside) *x.at = c.take<u32>(x.n);
+  os_scratch_sizes(c, nb, o.b);
+}
+
+// The tail of SEMI / ANTI: the flags compacted to ascending row ids with the count straight into DevMeta::n_out (three
+// launches; were five: scan x 3, a device-to-device copy of the total, compact), then the call's last read-back.
+static int finish_semi(giql_hip_ctx* ctx, hipStream_t st, const u32* flag, size_t na, u64* bsums, u64* spine_out,
+                       int32_t* rows_out) {
+  GIQL_TRY(run_scan_compact(ctx, st, flag, na, bsums, spine_out, rows_out, "scan + compact"));
+  return read_meta(ctx, st);
 }
 
 // -------------------------------------------------------------- SEMI / ANTI
@@ -2991,25 +3077,21 @@ static int giql_hip_semi_anti_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
   if (a->n == 0) return GIQL_OK;
   if (!rows_out) return set_err(GIQL_ERR_INVALID, "rows_out is NULL");
   const size_t na = (size_t)a->n, nb = (size_t)b->n;
-  if (na > OS_MAX_ROWS || nb > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
+  GIQL_TRY(check_rows_fit(na, nb));
   const int nch = n_chrom > 0 ? n_chrom : 1;
 
   LinBufs lb;
   SortBufs sa, sbb;
-  OsScratch os, os_a;
+  OsScratchPair osp;
+  OsScratch &os_a = osp.a, &os = osp.b;
   u32 *flag = nullptr, *pmax = nullptr, *bmax = nullptr, *dummy_irr = nullptr;
   u64 *bsums = nullptr, *off = nullptr;
   auto carve = [&](char* base) {
     Carver c{base};
     common_sizes(c, nch, lb);
     sort_sizes(c, na, sa, true);
-    for (int k = 0; k < 2; k++) {  // B: (key, end), no row ids
-      sbb.key[k] = c.take<u32>(nb ? nb : 1);
-      sbb.end[k] = c.take<u32>(nb ? nb : 1);
-      sbb.rid[k] = nullptr;
-    }
-    os_scratch_sizes(c, na, os_a);   // A's own histogram / status words: its chain may run beside B's
-    os_scratch_sizes(c, nb ? nb : 1, os);  // (right behind A's: prezero_row_scratch)
+    sort_sizes_key_payload(c, nb ? nb : 1, sbb);  // B: (key, end)
+    os_pair_sizes(c, na, nb ? nb : 1, osp);
     bsums = c.take<u64>(cdiv(na, SCAN_TILE) + 2);
     flag = c.take<u32>(na);
     off = c.take<u64>(na + 1);
@@ -3020,7 +3102,7 @@ static int giql_hip_semi_anti_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
   };
   GIQL_TRY(claim_arena(ctx, st, carve));
   PrezeroGuard prezero_guard{ctx};
-  GIQL_TRY(prezero_row_scratch(ctx, st, os_a, os, nb ? nb : 1));  // each side is sorted once, in either form
+  GIQL_TRY(osp.prezero(ctx, st, nb ? nb : 1));  // each side is sorted once, in either form
 
   GIQL_TRY(run_spans(ctx, st, *a, *b, nch, lb));
   i64 uni_len = 0;
@@ -3033,25 +3115,25 @@ static int giql_hip_semi_anti_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
     GIQL_TRY(run_linearize(ctx, sc.stream(), *a, nch, lb, sa.key[0], sa.end[0], dummy_irr + 8, 0, 1, os_a.hist, os_a.gbase));
     GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sa, (u32)na, os_a.gbase, os_a.status, false, nullptr, nullptr,
                                /*skip_digits=*/row_skip(ctx, nb)));  // the query side's order only serves locality; every row keeps its real key here
-  if (nb > 0 && uni_len > 0) {
-    // fixed-length B: keys only (its `end` column is not read again), no prefix max
-    sbb.end[0] = sbb.end[1] = nullptr;
-    GIQL_TRY(run_linearize(ctx, st, *b, nch, lb, sbb.key[0], nullptr, dummy_irr, 1, 1, os.hist, os.gbase,
-                           nullptr, nullptr, /*skip_end=*/true));
-    GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase, os.status, false, nullptr, nullptr,
-                               /*skip_digits=*/coarse_b ? 1 : 0));
-  } else if (nb > 0) {
-    // every B row keeps its real key: the prefix-max test is exact for any row
-    GIQL_TRY(run_linearize(ctx, st, *b, nch, lb, sbb.key[0], sbb.end[0], dummy_irr, 1, 1, os.hist,
-                           os.gbase));
+    if (nb > 0 && uni_len > 0) {
+      // fixed-length B: keys only (its `end` column is not read again), no prefix max
+      sbb.end[0] = sbb.end[1] = nullptr;
+      GIQL_TRY(run_linearize(ctx, st, *b, nch, lb, sbb.key[0], nullptr, dummy_irr, 1, 1, os.hist, os.gbase,
+                             nullptr, nullptr, /*skip_end=*/true));
+      GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase, os.status, false, nullptr, nullptr,
+                                 /*skip_digits=*/coarse_b ? 1 : 0));
+    } else if (nb > 0) {
+      // every B row keeps its real key: the prefix-max test is exact for any row
+      GIQL_TRY(run_linearize(ctx, st, *b, nch, lb, sbb.key[0], sbb.end[0], dummy_irr, 1, 1, os.hist,
+                             os.gbase));
 #if defined(GIQL_LIN_ABLATE)  // timing-only builds stop here: their keys / histograms are not valid
-    GIQL_TRY(read_meta(ctx, st));
-    collect_spans(ctx);
-    return GIQL_OK;
+      GIQL_TRY(read_meta(ctx, st));
+      collect_spans(ctx);
+      return GIQL_OK;
 #endif
-    GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase, os.status));
-    GIQL_TRY(run_pmax(ctx, st, sbb.end[0], (u32)nb, pmax, bmax));
-  }
+      GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase, os.status));
+      GIQL_TRY(run_pmax(ctx, st, sbb.end[0], (u32)nb, pmax, bmax));
+    }
     GIQL_TRY(sc.join());
   }
   {
@@ -3067,18 +3149,14 @@ static int giql_hip_semi_anti_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
                          sa.rid[0], (u32)na, ctx->d_meta, sbb.key[0], pmax, (u32)nb, anti, flag);
     GIQL_TRY(post_launch("semi flags"));
   }
-  // the count straight into DevMeta::n_out (three launches; were five: scan x 3, a device-to-device copy of the
-  // total, compact)
-  GIQL_TRY(run_scan_compact(ctx, st, flag, na, bsums, off + na, rows_out, "scan + compact"));
-  GIQL_TRY(read_meta(ctx, st));
+  GIQL_TRY(finish_semi(ctx, st, flag, na, bsums, off + na, rows_out));
   if (nb > 0 && !row_form_settled(ctx, uni_len, speculated))  // B is not fixed-length after all
     return GIQL_STATUS_GUESS_MISSED;
   collect_spans(ctx);
   ctx->stats.reserved = (uni_len > 0 ? 1 : 0) | (coarse_b ? 0x10 : 0);  // form: fixed-length B or general; bit 4: B sorted coarsely (without its lowest digit)
   *n_out = (int64_t)ctx->h_meta->n_out;
   ctx->stats.n_out = *n_out;
-  ctx->stats.span = (int64_t)ctx->h_meta->total_span;
-  ctx->guess.last_span = ctx->h_meta->total_span;
+  note_span(ctx);
   return GIQL_OK;
 }
 
@@ -3097,27 +3175,22 @@ static int giql_hip_count_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const 
   if (a->n == 0) return GIQL_OK;
   if (!counts_out) return set_err(GIQL_ERR_INVALID, "counts_out is NULL");
   const size_t na = (size_t)a->n, nb = (size_t)b->n;
-  if (na > OS_MAX_ROWS || nb > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
+  GIQL_TRY(check_rows_fit(na, nb));
   if (nb == 0 || n_chrom == 0) {
     HIP_TRY(hipMemsetAsync(counts_out, 0, na * sizeof(int64_t), st));
     return GIQL_OK;
   }
   LinBufs lb;
   SortBufs sa, sstart, send;
-  OsScratch os, os_a;
+  OsScratchPair osp;
+  OsScratch &os_a = osp.a, &os = osp.b;
   u32 *irr_a_list = nullptr, *irr_b_list = nullptr;
   auto carve = [&](char* base) {
     Carver c{base};
     common_sizes(c, n_chrom, lb);
     sort_sizes(c, na, sa, true);
-    for (int k = 0; k < 2; k++) {  // two keys-only sorts of B: starts and ends
-      sstart.key[k] = c.take<u32>(nb);
-      sstart.end[k] = sstart.rid[k] = nullptr;
-      send.key[k] = c.take<u32>(nb);
-      send.end[k] = send.rid[k] = nullptr;
-    }
-    os_scratch_sizes(c, na, os_a);   // A's chain may run beside B's (SideChain)
-    os_scratch_sizes(c, nb, os);     // (right behind A's: prezero_row_scratch)
+    sort_sizes_starts_ends(c, nb, sstart, send);
+    os_pair_sizes(c, na, nb, osp);
     irr_a_list = c.take<u32>(na);
     irr_b_list = c.take<u32>(nb);
     return c.off;
@@ -3130,26 +3203,26 @@ static int giql_hip_count_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const 
   GIQL_TRY(row_form_guess(ctx, st, uni_len, speculated));
   const bool coarse_b = uni_len > 0 && coarse_b_ok(ctx, nb);
   PrezeroGuard prezero_guard{ctx};
-  if (uni_len > 0) GIQL_TRY(prezero_row_scratch(ctx, st, os_a, os, nb));  // (the general form sorts B twice through one set of status words)
+  if (uni_len > 0) GIQL_TRY(osp.prezero(ctx, st, nb));  // (the general form sorts B twice through one set of status words)
   {
-  SideChain sc(ctx, st, na);
-  GIQL_TRY(run_linearize(ctx, sc.stream(), *a, n_chrom, lb, sa.key[0], sa.end[0], irr_a_list, 0, 0, os_a.hist,
-                         os_a.gbase));
-  GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sa, (u32)na, os_a.gbase, os_a.status, false, nullptr, nullptr,
-                             /*skip_digits=*/row_skip(ctx, nb)));  // locality only: k_count_rows tells irregular rows by their key
-  if (uni_len > 0) {
-    // fixed-length B: one sorted array (its sorted ends are its sorted starts + L)
-    GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, sstart.key[0], nullptr, irr_b_list, 1, 0, os.hist,
-                           os.gbase, nullptr, nullptr, /*skip_end=*/true));
-    GIQL_TRY(run_sort_onesweep(ctx, st, sstart, (u32)nb, os.gbase, os.status, false, nullptr, nullptr,
-                               /*skip_digits=*/coarse_b ? 1 : 0));
-  } else {
-    GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, sstart.key[0], send.key[0], irr_b_list, 1, 0,
-                           os.hist, os.gbase, os.hist_e, os.gbase_e));
-    GIQL_TRY(run_sort_onesweep(ctx, st, sstart, (u32)nb, os.gbase, os.status));
-    GIQL_TRY(run_sort_onesweep(ctx, st, send, (u32)nb, os.gbase_e, os.status));
-  }
-  GIQL_TRY(sc.join());
+    SideChain sc(ctx, st, na);
+    GIQL_TRY(run_linearize(ctx, sc.stream(), *a, n_chrom, lb, sa.key[0], sa.end[0], irr_a_list, 0, 0, os_a.hist,
+                           os_a.gbase));
+    GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sa, (u32)na, os_a.gbase, os_a.status, false, nullptr, nullptr,
+                               /*skip_digits=*/row_skip(ctx, nb)));  // locality only: k_count_rows tells irregular rows by their key
+    if (uni_len > 0) {
+      // fixed-length B: one sorted array (its sorted ends are its sorted starts + L)
+      GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, sstart.key[0], nullptr, irr_b_list, 1, 0, os.hist,
+                             os.gbase, nullptr, nullptr, /*skip_end=*/true));
+      GIQL_TRY(run_sort_onesweep(ctx, st, sstart, (u32)nb, os.gbase, os.status, false, nullptr, nullptr,
+                                 /*skip_digits=*/coarse_b ? 1 : 0));
+    } else {
+      GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, sstart.key[0], send.key[0], irr_b_list, 1, 0,
+                             os.hist, os.gbase, os.hist_e, os.gbase_e));
+      GIQL_TRY(run_sort_onesweep(ctx, st, sstart, (u32)nb, os.gbase, os.status));
+      GIQL_TRY(run_sort_onesweep(ctx, st, send, (u32)nb, os.gbase_e, os.status));
+    }
+    GIQL_TRY(sc.join());
   }
   {
     Phase ph(ctx, st, GIQL_PH_COUNT);
@@ -3173,8 +3246,7 @@ static int giql_hip_count_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const 
   }
   collect_spans(ctx);
   ctx->stats.n_out = a->n;
-  ctx->stats.span = (int64_t)ctx->h_meta->total_span;
-  ctx->guess.last_span = ctx->h_meta->total_span;
+  note_span(ctx);
   return GIQL_OK;
 }
 
@@ -3196,7 +3268,7 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
   if (!out32 && (!idx_b_out || !dist_out)) return set_err(GIQL_ERR_INVALID, "idx_b_out/dist_out is NULL");
   if (out32 && ((uintptr_t)out32 & 7)) return set_err(GIQL_ERR_INVALID, "idx_dist_out must be 8-byte aligned");
   const size_t na = (size_t)a->n, nb = (size_t)b->n;
-  if (na > OS_MAX_ROWS || nb > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
+  GIQL_TRY(check_rows_fit(na, nb));
   if (nb == 0 || n_chrom == 0) {
     if (out32) {
       hipLaunchKernelGGL(k_nearest32_none, dim3(cdiv(na, 256)), dim3(256), 0, st, reinterpret_cast<int2*>(out32), (u32)na);
@@ -3208,7 +3280,8 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
   }
   LinBufs lb;
   SortBufs sa, sbb;
-  OsScratch os, os_a;
+  OsScratchPair osp;
+  OsScratch &os_a = osp.a, &os = osp.b;
   u32 *pmax = nullptr, *bmax = nullptr, *dummy_irr = nullptr, *chrom_lo = nullptr;
   NearestRec* recs = nullptr;
   auto carve = [&](char* base) {
@@ -3216,11 +3289,9 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
     common_sizes(c, n_chrom, lb);
     sort_sizes(c, na, sa, true);
     sort_sizes(c, nb, sbb, true);
-    os_scratch_sizes(c, na, os_a);   // A's chain may run beside B's (SideChain)
-    lb.top_partial = c.take<u32>((size_t)LIN_HIST_REPLICAS * MM_TOP_WORDS);   // (inside the range prezero_row_scratch zeroes)
-    lb.top_partial2 = c.take<u32>((size_t)LIN_HIST_REPLICAS * MM_TOP_WORDS);
-    lb.abase = c.take<u32>(MM_HIST_CHROMS);
-    os_scratch_sizes(c, nb, os);     // (right behind A's: prezero_row_scratch)
+    const size_t top_words = (size_t)LIN_HIST_REPLICAS * MM_TOP_WORDS;  // the span pass's digit counts: zeroed with the rest
+    os_pair_sizes(c, na, nb, osp,
+                  {{&lb.top_partial, top_words}, {&lb.top_partial2, top_words}, {&lb.abase, (size_t)MM_HIST_CHROMS}});
     recs = c.take<NearestRec>(out32 ? 0 : na);   // (the 32-bit form scatters its records straight into the output)
     pmax = c.take<u32>(nb);
     bmax = c.take<u32>(cdiv(nb, PM_TILE) + 1);
@@ -3232,7 +3303,7 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
 
   const bool two_sorts = ctx->guess.nearest_two_sorts;
   PrezeroGuard prezero_guard{ctx};
-  if (!two_sorts) GIQL_TRY(prezero_row_scratch(ctx, st, os_a, os, nb));  // (the two-sort plan reuses B's status words)
+  if (!two_sorts) GIQL_TRY(osp.prezero(ctx, st, nb));  // (the two-sort plan reuses B's status words)
   // Both sides sorted from their raw columns (round 3): with every chromosome base a multiple of 2^24 the span pass
   // counts the digits of the keys itself (k_chrom_minmax<1>, "Histogram in the span pass"), and the first sort pass
   // of each side builds key and end key from (chrom, start, end) -- no linearize pass (2 x 49 us at 10M x 10M against
@@ -3265,15 +3336,7 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
                            os.gbase, two_sorts ? os.hist_e : nullptr, two_sorts ? os.gbase_e : nullptr));
   // (an inverted B row -- NEAREST needs start <= end on both sides -- is reported by the span pass: DevMeta::inverted_b)
   if (two_sorts) {
-    // (start, end) lexicographic order = stable sort by end, then stable sort by start
-    SortBufs by_end = sbb;
-    for (int k = 0; k < 2; k++) {
-      by_end.key[k] = sbb.end[k];
-      by_end.end[k] = sbb.key[k];
-    }
-    GIQL_TRY(run_sort_onesweep(ctx, st, by_end, (u32)nb, os.gbase_e, os.status));
-    adopt_by_end(sbb, by_end);
-    GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase, os.status, /*keep_rids=*/true));
+    GIQL_TRY(run_sort_two_keys(ctx, st, sbb, (u32)nb, os.gbase, os.gbase_e, os.status));  // (start, end) order
   } else {
     // one sort by start; the (short) runs of equal starts are ordered by end in place
     GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase, os.status, false, keygen ? b : nullptr, lb.abase));
@@ -3317,8 +3380,7 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
     return set_err(GIQL_ERR_INVALID, "NEAREST: a distance does not fit int32; use giql_hip_nearest_dev (int64 distances)");
   collect_spans(ctx);
   ctx->stats.n_out = a->n;
-  ctx->stats.span = (int64_t)ctx->h_meta->total_span;
-  ctx->guess.last_span = ctx->h_meta->total_span;
+  note_span(ctx);
   return GIQL_OK;
 }
 
@@ -3347,7 +3409,7 @@ static int giql_hip_nearest_k_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
   if (a->n == 0) return GIQL_OK;
   if (!idx_b_out || !dist_out) return set_err(GIQL_ERR_INVALID, "idx_b_out/dist_out is NULL");
   const size_t na = (size_t)a->n, nb = (size_t)b->n;
-  if (na > OS_MAX_ROWS || nb > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
+  GIQL_TRY(check_rows_fit(na, nb));
   if (na * (size_t)k > 0x7FFFFFF0ull) return set_err(GIQL_ERR_INVALID, "n_a * k does not fit 31 bits");
   if (nb == 0 || n_chrom == 0) {
     HIP_TRY(hipMemsetAsync(idx_b_out, 0xFF, na * k * sizeof(int32_t), st));
@@ -3385,16 +3447,7 @@ static int giql_hip_nearest_k_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
   if (two_sorts) {
     // tables with long runs of equal starts or ends: stable two-key sorts -- (start, end) = by end, then stably by
     // start; (end, start) = that order stably re-sorted by end
-    {
-      SortBufs by_end = sbb;
-      for (int i = 0; i < 2; i++) {
-        by_end.key[i] = sbb.end[i];
-        by_end.end[i] = sbb.key[i];
-      }
-      GIQL_TRY(run_sort_onesweep(ctx, st, by_end, (u32)nb, os.gbase_e, os.status));
-      adopt_by_end(sbb, by_end);
-      GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase, os.status, /*keep_rids=*/true));
-    }
+    GIQL_TRY(run_sort_two_keys(ctx, st, sbb, (u32)nb, os.gbase, os.gbase_e, os.status));
     HIP_TRY(hipMemcpyAsync(se.key[0], sbb.end[0], nb * sizeof(u32), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(se.end[0], sbb.key[0], nb * sizeof(u32), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(se.rid[0], sbb.rid[0], nb * sizeof(u32), hipMemcpyDeviceToDevice, st));
@@ -3448,8 +3501,7 @@ static int giql_hip_nearest_k_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
   if (ctx->h_meta->inverted_b) return set_err(GIQL_ERR_INVALID, "NEAREST: a target row has end < start");
   collect_spans(ctx);
   ctx->stats.n_out = a->n * (int64_t)k;
-  ctx->stats.span = (int64_t)ctx->h_meta->total_span;
-  ctx->guess.last_span = ctx->h_meta->total_span;
+  note_span(ctx);
   return GIQL_OK;
 }
 
@@ -4127,28 +4179,16 @@ static int check_rowpred(int32_t pred, int64_t max_distance) {
   return GIQL_OK;
 }
 
-// DISTANCE needs start <= end on every row of both sides, reported as giql_hip_window_plan_dev reports it.
-static int reject_inverted(giql_hip_ctx* ctx) {
-  if (!ctx->h_meta->inverted_a && !ctx->h_meta->inverted_b) return GIQL_OK;
-  if (ctx->h_meta->inverted_a) ctx->stats.n_irregular_a = -1;
-  if (ctx->h_meta->inverted_b) ctx->stats.n_irregular_b = -1;
-  return set_err(GIQL_ERR_INVALID, "DISTANCE: side %s has a row with start > end", ctx->h_meta->inverted_a ? "a" : "b");
-}
-
-// the clamp range of the widened rows: what run_spans(pad = 1) handed to k_chrom_offsets
-static void window_pads(const giql_side& a, const giql_side& b, int& lo_pad, int& hi_pad) {
-  lo_pad = hi_pad = a.start_off;
-  const int offs[3] = {a.end_off, b.start_off, b.end_off};
-  for (int k = 0; k < 3; k++) {
-    if (offs[k] < lo_pad) lo_pad = offs[k];
-    if (offs[k] > hi_pad) hi_pad = offs[k];
+// The exit of a call whose right side can pair with no left row: nothing for SEMI, every row for ANTI.
+static int every_row_for_anti(giql_hip_ctx* ctx, hipStream_t st, size_t na, int anti, int32_t* rows_out, int64_t* n_out,
+                              const char* what) {
+  if (anti) {
+    hipLaunchKernelGGL(k_rp_iota, dim3(cdiv(na, 256)), dim3(256), 0, st, rows_out, (u32)na);
+    GIQL_TRY(post_launch(what));
+    *n_out = (int64_t)na;
   }
-  lo_pad -= 1;
-  hi_pad += 1;
-}
-
-static inline i64 clamp_widen(int64_t max_distance) {  // (giql_hip_window_plan_dev: a larger N selects the same pairs)
-  return max_distance > ((i64)1 << 33) ? ((i64)1 << 33) : (i64)max_distance;
+  ctx->stats.n_out = *n_out;
+  return GIQL_OK;
 }
 
 static int giql_hip_semi_anti_pred_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, int32_t n_chrom,
@@ -4164,36 +4204,24 @@ static int giql_hip_semi_anti_pred_dev_impl(giql_hip_ctx* ctx, const giql_side* 
   if (a->n == 0) return GIQL_OK;
   if (!rows_out) return set_err(GIQL_ERR_INVALID, "rows_out is NULL");
   const size_t na = (size_t)a->n, nb = (size_t)b->n;
-  if (na > OS_MAX_ROWS || nb > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
+  GIQL_TRY(check_rows_fit(na, nb));
   if (nb > 0 && n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
   const bool dist = pred == GIQL_ROWPRED_DISTANCE;
   const int nch = n_chrom;
-  if (nb == 0) {  // no right row: nothing for SEMI, every row for ANTI
-    if (anti) {
-      hipLaunchKernelGGL(k_rp_iota, dim3(cdiv(na, 256)), dim3(256), 0, st, rows_out, (u32)na);
-      GIQL_TRY(post_launch("anti (empty right side)"));
-      *n_out = a->n;
-    }
-    ctx->stats.n_out = *n_out;
-    return GIQL_OK;
-  }
+  if (nb == 0) return every_row_for_anti(ctx, st, na, anti, rows_out, n_out, "anti (empty right side)");
 
   LinBufs lb;
   SortBufs sa, sbb;
-  OsScratch os, os_a;
+  OsScratchPair osp;
+  OsScratch &os_a = osp.a, &os = osp.b;
   u32 *flag = nullptr, *pmax = nullptr, *bmax = nullptr, *dummy_irr = nullptr;
   u64 *bsums = nullptr, *off = nullptr;
   auto carve = [&](char* base) {
     Carver c{base};
     common_sizes(c, nch, lb);
     sort_sizes(c, na, sa, true);
-    for (int k = 0; k < 2; k++) {  // B: (sort key, the other key as payload), no row ids
-      sbb.key[k] = c.take<u32>(nb);
-      sbb.end[k] = c.take<u32>(nb);
-      sbb.rid[k] = nullptr;
-    }
-    os_scratch_sizes(c, na, os_a);
-    os_scratch_sizes(c, nb, os);
+    sort_sizes_key_payload(c, nb, sbb);  // B: (sort key, the other key as payload)
+    os_pair_sizes(c, na, nb, osp);
     bsums = c.take<u64>(cdiv(na, SCAN_TILE) + 2);
     flag = c.take<u32>(na);
     off = c.take<u64>(na + 1);
@@ -4206,31 +4234,12 @@ static int giql_hip_semi_anti_pred_dev_impl(giql_hip_ctx* ctx, const giql_side* 
   GIQL_TRY(run_spans(ctx, st, *a, *b, nch, lb, -1, nullptr, /*pad=*/dist ? 1 : 0));
   GIQL_TRY(read_meta(ctx, st));
   if (dist) GIQL_TRY(reject_inverted(ctx));
-  ctx->stats.span = (int64_t)ctx->h_meta->total_span;
-  ctx->guess.last_span = ctx->h_meta->total_span;
-  if (dist && max_distance < 0) {  // `< 0`: no pair, after the rows have been checked
-    if (anti) {
-      hipLaunchKernelGGL(k_rp_iota, dim3(cdiv(na, 256)), dim3(256), 0, st, rows_out, (u32)na);
-      GIQL_TRY(post_launch("anti (no pair possible)"));
-      *n_out = a->n;
-    }
-    ctx->stats.n_out = *n_out;
-    return GIQL_OK;
-  }
-  const i64 widen = dist ? clamp_widen(max_distance) : 0;
+  note_span(ctx);
+  if (dist && max_distance < 0)  // `< 0`: no pair, after the rows have been checked
+    return every_row_for_anti(ctx, st, na, anti, rows_out, n_out, "anti (no pair possible)");
   // A: every row on its real key, sorted coarsely (its order only serves locality)
   if (dist) {
-    int lo_pad, hi_pad;
-    window_pads(*a, *b, lo_pad, hi_pad);
-    HIP_TRY(hipMemsetAsync(os_a.hist, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
-    Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
-    u32 grid = cdiv((u64)na, LIN_NT);
-    if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
-    hipLaunchKernelGGL(k_rp_window_keys, dim3(grid), dim3(LIN_NT), 0, st, a->chrom, a->start, a->end, (u32)na,
-                       a->start_off, a->end_off, nch, lb.chrom_base, lb.gmin, lb.gmax, lo_pad, hi_pad, widen, sa.key[0],
-                       sa.end[0], ctx->d_meta, os_a.hist);
-    hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, os_a.hist, (u32)LIN_HIST_REPLICAS, os_a.gbase);
-    GIQL_TRY(post_launch("row predicate window keys"));
+    GIQL_TRY(key_widened_side(ctx, st, *a, *b, nch, lb, clamp_widen(max_distance), sa, nullptr, os_a.hist, os_a.gbase));
   } else {
     GIQL_TRY(run_linearize(ctx, st, *a, nch, lb, sa.key[0], sa.end[0], dummy_irr + 8, 0, 1, os_a.hist, os_a.gbase));
   }
@@ -4259,8 +4268,7 @@ static int giql_hip_semi_anti_pred_dev_impl(giql_hip_ctx* ctx, const giql_side* 
                          flag);
     GIQL_TRY(post_launch("row predicate flags"));
   }
-  GIQL_TRY(run_scan_compact(ctx, st, flag, na, bsums, off + na, rows_out, "scan + compact"));
-  GIQL_TRY(read_meta(ctx, st));
+  GIQL_TRY(finish_semi(ctx, st, flag, na, bsums, off + na, rows_out));
   collect_spans(ctx);
   ctx->stats.reserved = 0;  // form: general, the only one
   *n_out = (int64_t)ctx->h_meta->n_out;
@@ -4282,20 +4290,15 @@ static int count_window(giql_hip_ctx* ctx, hipStream_t st, const giql_side* a, c
   const size_t na = (size_t)a->n, nb = (size_t)b->n;
   LinBufs lb;
   SortBufs sa, sstart, send;
-  OsScratch os, os_a;
+  OsScratchPair osp;
+  OsScratch &os_a = osp.a, &os = osp.b;
   u32 *irr_a_list = nullptr, *irr_b_list = nullptr;
   auto carve = [&](char* base) {
     Carver c{base};
     common_sizes(c, n_chrom, lb);
     sort_sizes(c, na, sa, true);
-    for (int k = 0; k < 2; k++) {  // two keys-only sorts of B: starts and ends
-      sstart.key[k] = c.take<u32>(nb);
-      sstart.end[k] = sstart.rid[k] = nullptr;
-      send.key[k] = c.take<u32>(nb);
-      send.end[k] = send.rid[k] = nullptr;
-    }
-    os_scratch_sizes(c, na, os_a);
-    os_scratch_sizes(c, nb, os);
+    sort_sizes_starts_ends(c, nb, sstart, send);
+    os_pair_sizes(c, na, nb, osp);
     irr_a_list = c.take<u32>(na);
     irr_b_list = c.take<u32>(nb);
     return c.off;
@@ -4304,27 +4307,14 @@ static int count_window(giql_hip_ctx* ctx, hipStream_t st, const giql_side* a, c
   GIQL_TRY(run_spans(ctx, st, *a, *b, n_chrom, lb, -1, nullptr, /*pad=*/1));
   GIQL_TRY(read_meta(ctx, st));
   GIQL_TRY(reject_inverted(ctx));
-  ctx->stats.span = (int64_t)ctx->h_meta->total_span;
-  ctx->guess.last_span = ctx->h_meta->total_span;
+  note_span(ctx);
   if (max_distance < 0) {  // `< 0`: no pair, after the rows have been checked
     HIP_TRY(hipMemsetAsync(counts_out, 0, na * sizeof(int64_t), st));
     ctx->stats.n_out = a->n;
     return GIQL_OK;
   }
   const i64 widen = clamp_widen(max_distance);
-  {
-    int lo_pad, hi_pad;
-    window_pads(*a, *b, lo_pad, hi_pad);
-    HIP_TRY(hipMemsetAsync(os_a.hist, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
-    Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
-    u32 grid = cdiv((u64)na, LIN_NT);
-    if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
-    hipLaunchKernelGGL(k_window_linearize, dim3(grid), dim3(LIN_NT), 0, st, a->chrom, a->start, a->end, (u32)na,
-                       a->start_off, a->end_off, n_chrom, lb.chrom_base, lb.gmin, lb.gmax, lo_pad, hi_pad, widen,
-                       sa.key[0], sa.end[0], irr_a_list, ctx->d_meta, os_a.hist);
-    hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, os_a.hist, (u32)LIN_HIST_REPLICAS, os_a.gbase);
-    GIQL_TRY(post_launch("window linearize"));
-  }
+  GIQL_TRY(key_widened_side(ctx, st, *a, *b, n_chrom, lb, widen, sa, irr_a_list, os_a.hist, os_a.gbase));
   GIQL_TRY(run_sort_onesweep(ctx, st, sa, (u32)na, os_a.gbase, os_a.status, false, nullptr, nullptr,
                              /*skip_digits=*/row_skip(ctx, nb)));  // locality only: the kernel tells listed rows by their key
   GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, sstart.key[0], send.key[0], irr_b_list, 1, 0, os.hist, os.gbase,
@@ -4446,7 +4436,7 @@ static int giql_hip_count_pred_dev_impl(giql_hip_ctx* ctx, const giql_side* a, c
   if (a->n == 0) return GIQL_OK;
   if (!counts_out) return set_err(GIQL_ERR_INVALID, "counts_out is NULL");
   const size_t na = (size_t)a->n, nb = (size_t)b->n;
-  if (na > OS_MAX_ROWS || nb > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
+  GIQL_TRY(check_rows_fit(na, nb));
   if (nb > 0 && n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
   if (nb == 0) {
     HIP_TRY(hipMemsetAsync(counts_out, 0, na * sizeof(int64_t), st));
@@ -4473,7 +4463,7 @@ static int giql_hip_group_rows_dev_impl(giql_hip_ctx* ctx, const giql_side* s, i
   if (!ctx || !n_groups) return set_err(GIQL_ERR_INVALID, "ctx/n_groups is NULL");
   GIQL_TRY(check_side(s, "s"));
   if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
-  if ((size_t)s->n > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
+  GIQL_TRY(check_rows_fit((size_t)s->n, 0));
   GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
   ctx->stats.n_a = s->n;
@@ -4509,15 +4499,8 @@ static int giql_hip_group_rows_dev_impl(giql_hip_ctx* ctx, const giql_side* s, i
   GIQL_TRY(run_spans(ctx, st, raw, none, n_chrom, lb));
   GIQL_TRY(run_linearize(ctx, st, raw, n_chrom, lb, sb.key[0], sb.end[0], dummy_irr, 0, 1, os.hist,
                          os.gbase, two_sorts ? os.hist_e : nullptr, two_sorts ? os.gbase_e : nullptr));
-  if (two_sorts) {  // (start, end) order = stable sort by end, then stable sort by start
-    SortBufs by_end = sb;
-    for (int k = 0; k < 2; k++) {
-      by_end.key[k] = sb.end[k];
-      by_end.end[k] = sb.key[k];
-    }
-    GIQL_TRY(run_sort_onesweep(ctx, st, by_end, (u32)n, os.gbase_e, os.status));
-    adopt_by_end(sb, by_end);
-    GIQL_TRY(run_sort_onesweep(ctx, st, sb, (u32)n, os.gbase, os.status, /*keep_rids=*/true));
+  if (two_sorts) {
+    GIQL_TRY(run_sort_two_keys(ctx, st, sb, (u32)n, os.gbase, os.gbase_e, os.status));  // (start, end) order
   } else {
     GIQL_TRY(run_sort_onesweep(ctx, st, sb, (u32)n, os.gbase, os.status));
     Phase ph(ctx, st, GIQL_PH_AUX);

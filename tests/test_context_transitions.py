@@ -11,6 +11,7 @@ was found by a long random soak.  So here:
 * Walk 1: per operator family, one fresh context walks an Eulerian circuit of the complete directed graph over the
   input classes (self-loops included): every ordered pair (X, Y) is a call on Y right after the context's last call
   on X.  Each visit runs the family twice; the second run must reach the path its class names (``SIGNATURES``).
+  The ``row_pred`` family is SEMI / ANTI / COUNT over CONTAINS, WITHIN and DISTANCE and the within-distance join.
 * Walk 2: one context, all twelve operators, DISJOIN's three and CONTAINS' three in a shuffled order per visit, with
   ``select`` / ``take_utf8`` / a plan of another operator put between some plans and their fill -- which must then
   refuse (``GIQL_ERR_STATE``): those calls reuse the workspace the plan lives in.
@@ -162,6 +163,10 @@ INDEX_DECLINES = {"many_chroms": "chromosomes", "negative": "aligned axis"}   # 
 INDEX_QUERY_DECLINES = {"irregular", "long_rows"}   # query sides the indexed join may refuse (the ordinary join answers)
 WIDTHS = {"w16": 16, "w15": 15, "w14": 14, "w13": 13}
 WIDTH_FAMILIES = ("row", "nearest")   # sorts on the tight span: every settled call takes the width of its density
+# (the ``row_pred`` family sorts on the tight span of its own call too -- each form reads its spans back and sets the
+# density before it sorts -- but the statistics name the side sorted LAST, and COUNT over WITHIN sorts the small left
+# table last (it is the inner side of the CONTAINS plan): its settled calls report A's form, not the width B's density
+# asks for, so the family is not one of these)
 
 
 @functools.lru_cache(maxsize=None)
@@ -575,14 +580,96 @@ def op_contain_plan_fill(eng, name, log, fam, rnd, intruder=None):
 CONTAIN_OPS = [op_contain_join, op_contain_within, op_contain_plan_fill]
 
 
+# ---- SEMI / ANTI / COUNT over CONTAINS, WITHIN and DISTANCE, and the within-distance join: they read and write the
+# density the next call's sort follows (``guess.last_span``) like the INTERSECTS forms.  One predicate per visit, in
+# turn: its first round runs on what the previous visit's predicate and class left, its second on its own (the walk's
+# time is the brute-force references', many times the ``row`` family's: one predicate a visit, not all three).
+# Truth = the pair references of the contain family reduced per left row (tests/_rows_ref.py) and the chunked brute
+# force of the window predicate.
+ROW_PREDS = (("contains", None), ("within", None), ("within_distance", 1000))
+ROW_PRED_CALLS = 2 * 4      # log entries of one visit: two rounds of SEMI, ANTI, COUNT, the join
+
+
+def _round_pred(log, fam):
+    return ROW_PREDS[(sum(c[0] == fam for c in log.calls) // ROW_PRED_CALLS) % len(ROW_PREDS)]
+
+
+@functools.lru_cache(maxsize=None)
+def want_row_pred(name, predicate, n):
+    """(semi ids, anti ids, counts) per row of the class's A."""
+    import _rows_ref as R
+
+    a, b, _nch, _da, _db = resident(name)
+    if predicate == "contains":
+        return R.reduce_pairs(want_contain(name, "contains"), a.n)
+    if predicate == "within":
+        return R.reduce_pairs(R.transpose(want_contain(name, "within")), a.n)
+    counts = R.window_counts(a.chrom, a.cs, a.ce, b.chrom, b.cs, b.ce, n)
+    ids = np.arange(a.n, dtype=np.int64)
+    return ids[counts > 0], ids[counts == 0], counts
+
+
+def _distance_refused(eng, name, predicate, call):
+    """DISTANCE refuses the class with inverted rows, naming the side (the walk goes on on the same context)."""
+    from giql_amd.engine import InvertedRows
+
+    if not (predicate == "within_distance" and name == "irregular"):
+        return False
+    with pytest.raises(InvertedRows) as exc:
+        call()
+    assert exc.value.sides == ("a",), (name, exc.value.sides)
+    return True
+
+
+def op_semi_pred(eng, name, log, fam, rnd):
+    _a, _b, nch, da, db = resident(name)
+    predicate, n = _round_pred(log, fam)
+    for anti in (False, True):
+        what = "anti_pred" if anti else "semi_pred"
+        if _distance_refused(eng, name, predicate, lambda: eng.semi_anti_pred(da, db, nch, predicate, anti, n)):
+            log.add(eng, fam, name, rnd, what)
+            continue
+        got = eng.semi_anti_pred(da, db, nch, predicate, anti, n).cpu().numpy()
+        log.add(eng, fam, name, rnd, what)
+        assert np.array_equal(got, want_row_pred(name, predicate, n)[1 if anti else 0]), (name, what, predicate)
+
+
+def op_count_pred(eng, name, log, fam, rnd):
+    _a, _b, nch, da, db = resident(name)
+    predicate, n = _round_pred(log, fam)
+    if _distance_refused(eng, name, predicate, lambda: eng.count_pred(da, db, nch, predicate, n)):
+        log.add(eng, fam, name, rnd, "count_pred")
+        return
+    got = eng.count_pred(da, db, nch, predicate, n).cpu().numpy()
+    log.add(eng, fam, name, rnd, "count_pred")
+    assert np.array_equal(got, want_row_pred(name, predicate, n)[2]), (name, "count_pred", predicate)
+
+
+def op_window_join(eng, name, log, fam, rnd):
+    """The within-distance join (N = 1000 whatever the round's predicate: the plan is DISTANCE's own).  Its pairs are
+    the reference's exactly when each is one of them, none comes twice and every left row has its count of them."""
+    a, b, nch, da, db = resident(name)
+    n = 1000
+    if _distance_refused(eng, name, "within_distance", lambda: eng.window_join(da, db, nch, n)):
+        log.add(eng, fam, name, rnd, "window_join")
+        return
+    ra, rb = (t.cpu().numpy().astype(np.int64) for t in eng.window_join(da, db, nch, n))
+    log.add(eng, fam, name, rnd, "window_join")
+    counts = want_row_pred(name, "within_distance", n)[2]
+    assert np.array_equal(np.bincount(ra, minlength=a.n), counts), (name, "window_join counts")
+    assert np.unique(ra * b.n + rb).size == ra.size, (name, "window_join: a pair twice")
+    assert np.all((a.chrom[ra] == b.chrom[rb]) & (a.cs[ra] - n < b.ce[rb]) & (a.ce[ra] + n > b.cs[rb])), (name, "window_join")
+
+
 FAMILIES = {
     "inner": [op_inner_join, op_into_exact, op_into_short, op_into_ample, op_plan_fill],
     "row": [op_semi, op_anti, op_count],
     "nearest": [op_nearest, op_nearest_k],
     "group_rows": [op_group_rows],
     "index": [op_index],
+    "row_pred": [op_semi_pred, op_count_pred, op_window_join],
 }
-ALL_OPS = [op for ops in FAMILIES.values() for op in ops]
+ALL_OPS = [op for fam, ops in FAMILIES.items() if fam != "row_pred" for op in ops]   # (Walk 2 and Leg 3: the twelve)
 
 
 def _check_signature(log, name):
