@@ -52,6 +52,7 @@ SYMBOLS = [
     "giql_hip_index_prepare_nearest_dev", "giql_hip_nearest_indexed_dev",
     "giql_hip_left_pad_dev",
     "giql_hip_semi_anti_pred_dev", "giql_hip_count_pred_dev",
+    "giql_hip_eval_expr_dev",
 ]
 
 
@@ -125,9 +126,24 @@ class CPred(ctypes.Structure):
     _fields_ = [("lhs", COperand), ("rhs", COperand), ("op", ctypes.c_int32), ("group", ctypes.c_int32)]
 
 
+class CExprOut(ctypes.Structure):
+    """``giql_expr_out`` (include/giql_hip.h)."""
+
+    _fields_ = [
+        ("first", ctypes.c_int32),
+        ("count", ctypes.c_int32),
+        ("type", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("data", ctypes.c_void_p),
+        ("valid", ctypes.c_void_p),
+    ]
+
+
 OPS = {"=": 0, "==": 0, "!=": 1, "<>": 1, "<": 2, "<=": 3, ">": 4, ">=": 5, "isnull": 6, "notnull": 7, "istrue": 8}
 SIDE_A, SIDE_B, SIDE_LIT, SIDE_EXPR = 0, 1, 2, 3
 T_I32, T_I64, T_F32, T_F64, T_U8 = range(5)
+#: ``GIQL_X_IF`` / ``GIQL_X_NULL``: the node kinds of a searched CASE
+X_IF, X_NULL = 35, 36
 
 _lib = None
 
@@ -216,6 +232,7 @@ def load() -> ctypes.CDLL:
     L.giql_hip_contain_fill_dev.argtypes = [vp, vp, vp, i64, vp]
     L.giql_hip_window_plan_dev.argtypes = [vp, P(CSide), P(CSide), i32, i64, vp, P(i64)]
     L.giql_hip_distance_dev.argtypes = [vp, P(CSide), P(CSide), vp, vp, i64, vp, vp, i32, vp, vp, vp]
+    L.giql_hip_eval_expr_dev.argtypes = [vp, P(COperand), i32, P(CExprOut), i32, vp, i64, vp, i64, i64, P(i64), vp]
     _lib = L
     return L
 

@@ -27,6 +27,7 @@
 #include "aux_kernels.hip.h"
 #include "take_kernels.hip.h"
 #include "select_kernels.hip.h"
+#include "eval_kernels.hip.h"
 #include "outer_kernels.hip.h"
 #include "cluster_kernels.hip.h"
 #include "disjoin_kernels.hip.h"
@@ -3631,35 +3632,49 @@ int giql_hip_cluster_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom,
   return with_order_fallback(ctx, [&] { return giql_hip_cluster_dev_impl(ctx, s, n_chrom, distance, cluster_id_out, stream); });
 }
 
-static int check_operand(const giql_operand& o, int k, const char* which);
+static int check_operand(const giql_operand& o, int k, const char* which, const char* owner = "predicate");
 
 // giql_pred[] -> the by-value kernel argument; uses[side] = a column of that side is read
 // A well-formed postfix program: every operator finds its arguments, one value is left, the stack stays within
-// SEL_X_STACK.  uses[side] as in convert_preds.
+// SEL_X_STACK.  uses[side] as in convert_preds.  `owner` k `which` names the program in a message ("predicate 2 lhs",
+// "output 0 program").
+// can_float (giql_hip_eval_expr_dev): the static type of the result -- per stack slot, can the value be a float?  A
+// float leaf is an F32 / F64 column or a float literal, `/` yields a float, arithmetic / NEG / ABS / LEAST / GREATEST
+// the OR of their arguments, IF `then OR else`; comparisons, IS [NOT] NULL, AND / OR / NOT and NULL are integers.
 static int check_program(const giql_operand* nodes, int32_t n_nodes, int first, int count, int k, const char* which,
-                         bool* uses) {
-  if (!nodes || first < 0 || count < 1 || first + count > n_nodes)
-    return set_err(GIQL_ERR_INVALID, "predicate %d %s: expression nodes [%d, %d) outside the %d given", k, which, first,
-                   first + count, n_nodes);
+                         bool* uses, const char* owner = "predicate", bool* can_float = nullptr) {
+  if (!nodes || first < 0 || count < 1 || first > n_nodes - count)
+    return set_err(GIQL_ERR_INVALID, "%s %d %s: expression nodes [%d, %lld) outside the %d given", owner, k, which, first,
+                   (long long)first + count, n_nodes);
   int sp = 0;
+  bool fl[SEL_X_STACK + 1];
   for (int t = first; t < first + count; t++) {
     const giql_operand& nd = nodes[t];
-    if (nd.side == GIQL_SIDE_A || nd.side == GIQL_SIDE_B || nd.side == GIQL_SIDE_LIT) {
-      GIQL_TRY(check_operand(nd, k, which));
-      if (uses && nd.side != GIQL_SIDE_LIT) uses[nd.side] = true;
-      if (++sp > SEL_X_STACK) return set_err(GIQL_ERR_INVALID, "predicate %d %s: expression deeper than %d", k, which, SEL_X_STACK);
+    if (nd.side == GIQL_SIDE_A || nd.side == GIQL_SIDE_B || nd.side == GIQL_SIDE_LIT || nd.side == GIQL_X_NULL) {
+      if (nd.side != GIQL_X_NULL) GIQL_TRY(check_operand(nd, k, which, owner));
+      if (uses && (nd.side == GIQL_SIDE_A || nd.side == GIQL_SIDE_B)) uses[nd.side] = true;
+      if (++sp > SEL_X_STACK) return set_err(GIQL_ERR_INVALID, "%s %d %s: expression deeper than %d", owner, k, which, SEL_X_STACK);
+      fl[sp - 1] = nd.side == GIQL_SIDE_LIT ? nd.lit_is_float != 0
+                                            : (nd.side != GIQL_X_NULL && (nd.type == GIQL_T_F32 || nd.type == GIQL_T_F64));
     } else if (nd.side == GIQL_X_NEG || nd.side == GIQL_X_ABS || nd.side == GIQL_X_ISNULL || nd.side == GIQL_X_NOTNULL ||
                nd.side == GIQL_X_NOT) {
-      if (sp < 1) return set_err(GIQL_ERR_INVALID, "predicate %d %s: malformed expression", k, which);
+      if (sp < 1) return set_err(GIQL_ERR_INVALID, "%s %d %s: malformed expression", owner, k, which);
+      if (nd.side != GIQL_X_NEG && nd.side != GIQL_X_ABS) fl[sp - 1] = false;
     } else if ((nd.side >= GIQL_X_ADD && nd.side <= GIQL_X_GREATEST) || (nd.side >= GIQL_X_EQ && nd.side <= GIQL_X_GE) ||
                nd.side == GIQL_X_AND || nd.side == GIQL_X_OR) {
-      if (sp < 2) return set_err(GIQL_ERR_INVALID, "predicate %d %s: malformed expression", k, which);
+      if (sp < 2) return set_err(GIQL_ERR_INVALID, "%s %d %s: malformed expression", owner, k, which);
       sp--;
+      fl[sp - 1] = nd.side == GIQL_X_DIV || (nd.side <= GIQL_X_GREATEST && (fl[sp - 1] || fl[sp]));
+    } else if (nd.side == GIQL_X_IF) {
+      if (sp < 3) return set_err(GIQL_ERR_INVALID, "%s %d %s: malformed expression (IF needs three values)", owner, k, which);
+      sp -= 2;
+      fl[sp - 1] = fl[sp] || fl[sp + 1];
     } else {
-      return set_err(GIQL_ERR_INVALID, "predicate %d %s: expression node kind %d", k, which, nd.side);
+      return set_err(GIQL_ERR_INVALID, "%s %d %s: expression node kind %d", owner, k, which, nd.side);
     }
   }
-  if (sp != 1) return set_err(GIQL_ERR_INVALID, "predicate %d %s: malformed expression", k, which);
+  if (sp != 1) return set_err(GIQL_ERR_INVALID, "%s %d %s: malformed expression", owner, k, which);
+  if (can_float) *can_float = fl[0];
   return GIQL_OK;
 }
 
@@ -4942,13 +4957,13 @@ int giql_hip_take_utf8_fill_dev(giql_hip_ctx* ctx, const int32_t* offsets, const
 }
 
 // ------------------------------------------------ residual predicates (select)
-static int check_operand(const giql_operand& o, int k, const char* which) {
+static int check_operand(const giql_operand& o, int k, const char* which, const char* owner) {
   if (o.side == GIQL_SIDE_LIT) return GIQL_OK;
   if (o.side != GIQL_SIDE_A && o.side != GIQL_SIDE_B)
-    return set_err(GIQL_ERR_INVALID, "predicate %d %s: side %d", k, which, o.side);
+    return set_err(GIQL_ERR_INVALID, "%s %d %s: side %d", owner, k, which, o.side);
   if (o.type < GIQL_T_I32 || o.type > GIQL_T_U8)
-    return set_err(GIQL_ERR_INVALID, "predicate %d %s: type %d", k, which, o.type);
-  if (!o.data) return set_err(GIQL_ERR_INVALID, "predicate %d %s: NULL column", k, which);
+    return set_err(GIQL_ERR_INVALID, "%s %d %s: type %d", owner, k, which, o.type);
+  if (!o.data) return set_err(GIQL_ERR_INVALID, "%s %d %s: NULL column", owner, k, which);
   return GIQL_OK;
 }
 
@@ -4971,7 +4986,9 @@ int giql_hip_select_expr_dev(giql_hip_ctx* ctx, const giql_pred* preds, int32_t 
     return set_err(GIQL_ERR_INVALID, "bad arguments (at most %d predicates and %d expression nodes, n < 2^31)",
                    SEL_MAX_PREDS, SEL_MAX_NODES);
   static_assert(GIQL_SIDE_EXPR == SEL_SIDE_EXPR && GIQL_X_ADD == SEL_X_ADD && GIQL_X_GREATEST == SEL_X_GREATEST &&
-                GIQL_X_NEG == SEL_X_NEG && GIQL_X_ABS == SEL_X_ABS && GIQL_X_DIV == SEL_X_DIV, "expression node kinds");
+                GIQL_X_NEG == SEL_X_NEG && GIQL_X_ABS == SEL_X_ABS && GIQL_X_DIV == SEL_X_DIV &&
+                GIQL_X_EQ == SEL_X_EQ && GIQL_X_NOT == SEL_X_NOT && GIQL_X_IF == SEL_X_IF && GIQL_X_NULL == SEL_X_NULL,
+                "expression node kinds");
   DevPreds ps;
   bool uses[2] = {false, false};
   bool any_expr = false;
@@ -5024,6 +5041,77 @@ int giql_hip_select_expr_dev(giql_hip_ctx* ctx, const giql_pred* preds, int32_t 
   collect_spans(ctx);
   *n_kept = (int64_t)h_total;
   ctx->stats.n_out = (int64_t)h_total;
+  return GIQL_OK;
+}
+
+// ------------------------------------------------ computed columns (eval)
+// The value of up to EV_MAX_OUTS programs per candidate, in one pass (eval_kernels.hip.h).  The programs are checked
+// and statically typed on the host before anything is launched; the nodes are staged in the arena like select's.
+int giql_hip_eval_expr_dev(giql_hip_ctx* ctx, const giql_operand* nodes, int32_t n_nodes, const giql_expr_out* outs,
+                           int32_t n_outs, const int32_t* idx_a, int64_t n_rows_a, const int32_t* idx_b,
+                           int64_t n_rows_b, int64_t n, int64_t* n_null, void* stream) {
+  if (!ctx || n < 0 || n > 0x7FFFFFF0ll || n_rows_a < 0 || n_rows_b < 0 || n_rows_a > 0x7FFFFFFFll ||
+      n_rows_b > 0x7FFFFFFFll || n_nodes < 0 || n_nodes > SEL_MAX_NODES || (n_nodes && !nodes))
+    return set_err(GIQL_ERR_INVALID, "bad arguments (at most %d expression nodes, n < 2^31)", SEL_MAX_NODES);
+  if (n_outs < 1 || n_outs > EV_MAX_OUTS || !outs)
+    return set_err(GIQL_ERR_INVALID, "n_outs = %d outside [1, %d]", n_outs, EV_MAX_OUTS);
+  static_assert(sizeof(giql_expr_out) == sizeof(DevExprOut), "giql_expr_out layout");
+  DevExprOuts d;
+  memset(&d, 0, sizeof(d));
+  d.n = n_outs;
+  bool uses[2] = {false, false};
+  for (int k = 0; k < n_outs; k++) {
+    if (outs[k].type != GIQL_T_I64 && outs[k].type != GIQL_T_F64)
+      return set_err(GIQL_ERR_INVALID, "output %d: type %d (GIQL_T_I64 or GIQL_T_F64)", k, outs[k].type);
+    if (n > 0 && !outs[k].data) return set_err(GIQL_ERR_INVALID, "output %d: data is NULL", k);
+    bool can_float = false;
+    GIQL_TRY(check_program(nodes, n_nodes, outs[k].first, outs[k].count, k, "program", uses, "output", &can_float));
+    if (can_float && outs[k].type == GIQL_T_I64)
+      return set_err(GIQL_ERR_INVALID, "output %d: the program can yield a float, its output is GIQL_T_I64", k);
+    memcpy(&d.o[k], &outs[k], sizeof(DevExprOut));
+  }
+  // a side given neither ids nor a row count is addressed by the candidate index
+  if (!idx_a && n_rows_a == 0 && !uses[0]) n_rows_a = n;
+  if (!idx_b && n_rows_b == 0 && !uses[1]) n_rows_b = n;
+  // the nodes and the NULL counts are carved from the start of the arena, where the plans keep their arrays
+  ctx->plan.planned = false;  // (so the way out with no candidates drops the plans too)
+  ctx->dj.planned = false;
+  ctx->ct.planned = false;
+  if (n_null) memset(n_null, 0, (size_t)n_outs * sizeof(int64_t));
+  if (n == 0) return GIQL_OK;
+  GIQL_TRY(begin_call(ctx));
+  hipStream_t st = (hipStream_t)stream;
+  DevOperand* prog = nullptr;
+  u64* nulls = nullptr;
+  GIQL_TRY(claim_arena(ctx, st, [&](char* base) {
+    Carver c{base};
+    prog = c.take<DevOperand>(SEL_MAX_NODES);
+    nulls = c.take<u64>(EV_MAX_OUTS);
+    return c.off;
+  }));
+  HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
+  HIP_TRY(hipMemsetAsync(nulls, 0, EV_MAX_OUTS * sizeof(u64), st));
+  // (pageable source: staged by the runtime before the call returns)
+  HIP_TRY(hipMemcpyAsync(prog, nodes, (size_t)n_nodes * sizeof(DevOperand), hipMemcpyHostToDevice, st));
+  const u32 n_tiles = cdiv((u64)n, SEL_TILE);
+  {
+    Phase ph(ctx, st, GIQL_PH_AUX);
+    ctx->stats.phase_bytes[GIQL_PH_AUX] += (int64_t)(8 + 9 * n_outs) * n;  // ids read, 8 B + 1 B per output (+ the gathers)
+    hipLaunchKernelGGL(k_eval_expr, dim3(n_tiles < GIQL_STREAM_GRID ? n_tiles : GIQL_STREAM_GRID), dim3(SEL_NT), 0, st, d,
+                       (const DevOperand*)prog, idx_a, (u32)n_rows_a, idx_b, (u32)n_rows_b, (u64)n, n_tiles, nulls,
+                       ctx->d_meta);
+    GIQL_TRY(post_launch("eval_expr"));
+  }
+  u64 h_nulls[EV_MAX_OUTS] = {0};
+  HIP_TRY(hipMemcpyAsync(h_nulls, nulls, sizeof(h_nulls), hipMemcpyDeviceToHost, st));
+  if (read_meta(ctx, st) != GIQL_OK) {
+    if (ctx->h_meta->status == GIQL_ERR_INVALID) return set_err(GIQL_ERR_INVALID, "a row id is outside its table");
+    return ctx->h_meta->status ? ctx->h_meta->status : GIQL_ERR_HIP;
+  }
+  collect_spans(ctx);
+  if (n_null)
+    for (int k = 0; k < n_outs; k++) n_null[k] = (int64_t)h_nulls[k];
+  ctx->stats.n_out = n;
   return GIQL_OK;
 }
 

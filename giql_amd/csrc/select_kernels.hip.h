@@ -59,10 +59,14 @@ __device__ __forceinline__ SelValue sel_load(const DevOperand& o, int ia, int ib
     return v;
   }
   const int r = o.side == 0 ? ia : ib;
-  if (o.valid && !o.valid[r]) v.null = true;
   v.is_float = o.type == 2 || o.type == 3;
   v.i = 0;
   v.f = 0.0;
+  if (r < 0) {  // the NULL row of its side (k_eval_expr: a LEFT join's padded row); the select kernels never pass one
+    v.null = true;
+    return v;
+  }
+  if (o.valid && !o.valid[r]) v.null = true;
   switch (o.type) {
     case 0: v.i = reinterpret_cast<const int*>(o.data)[r]; break;
     case 1: v.i = reinterpret_cast<const i64*>(o.data)[r]; break;
@@ -102,6 +106,10 @@ constexpr int SEL_X_ADD = 16, SEL_X_SUB = 17, SEL_X_MUL = 18, SEL_X_DIV = 19, SE
 // normal form of an OR of ANDs outgrows every cap.  The predicate that holds such a program has op SEL_OP_IS_TRUE.
 constexpr int SEL_X_EQ = 24, SEL_X_NE = 25, SEL_X_LT = 26, SEL_X_LE = 27, SEL_X_GT = 28, SEL_X_GE = 29,
               SEL_X_ISNULL = 30, SEL_X_NOTNULL = 31, SEL_X_AND = 32, SEL_X_OR = 33, SEL_X_NOT = 34;
+// A searched CASE (eval_kernels.hip.h; legal in a filter's programs too): IF pops else, then, cond and pushes `then`
+// when cond is TRUE, `else` when it is FALSE or NULL -- both branches are evaluated, which is exact because nothing
+// in the interpreter can raise; NULL pushes an integer NULL (a CASE without ELSE).
+constexpr int SEL_X_IF = 35, SEL_X_NULL = 36;
 constexpr int SEL_OP_IS_TRUE = 8;
 constexpr int SEL_X_STACK = 12;
 constexpr int SEL_MAX_NODES = 256;
@@ -116,6 +124,21 @@ __device__ __noinline__ SelValue sel_eval_prog(const DevOperand* __restrict__ pr
     const DevOperand nd = prog[t];
     if (nd.side <= 2) {
       st[sp++] = sel_load(nd, ia, ib);
+      continue;
+    }
+    if (nd.side == SEL_X_NULL) {
+      SelValue& v = st[sp++];
+      v.i = 0;
+      v.f = 0.0;
+      v.is_float = false;
+      v.null = true;
+      continue;
+    }
+    if (nd.side == SEL_X_IF) {
+      sp -= 2;
+      const SelValue& c = st[sp - 1];
+      const bool t = !c.null && (c.is_float ? c.f != 0.0 : c.i != 0);
+      st[sp - 1] = t ? st[sp] : st[sp + 1];
       continue;
     }
     if (nd.side == SEL_X_NEG || nd.side == SEL_X_ABS) {

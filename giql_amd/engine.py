@@ -33,6 +33,28 @@ def _torch():
     return torch
 
 
+def expr_can_float(tree) -> bool:
+    """The static type of an expression tree as :meth:`HipEngine.eval_exprs` takes it: can its value be a float?
+    The rule ``giql_hip_eval_expr_dev`` checks on the host (include/giql_hip.h): a float32 / float64 column or a
+    float literal is, the result of ``/`` is, arithmetic / ``neg`` / ``abs`` / ``least`` / ``greatest`` are when an
+    argument is, ``if`` when its ``then`` or ``else`` is; comparisons, IS [NOT] NULL, AND / OR / NOT and ``null``
+    are integers.  A float-typed expression needs a float64 output, every other one is int64."""
+    kind = tree[0]
+    if kind == "expr":
+        return expr_can_float(tree[1])
+    if kind == "lit":
+        return isinstance(tree[1], float)
+    if kind in ("a", "b"):
+        return bool(tree[1].dtype.is_floating_point)
+    if kind == "/":
+        return True
+    if kind == "if":
+        return expr_can_float(tree[2]) or expr_can_float(tree[3])
+    if kind in ("+", "-", "*", "neg", "abs", "least", "greatest"):
+        return any(expr_can_float(c) for c in tree[1:])
+    return False
+
+
 def _c_max_distance(max_distance) -> int:
     """``max_distance`` as the C ABI takes it: -1 = no limit."""
     return -1 if max_distance is None else int(max_distance)
@@ -1020,12 +1042,23 @@ class HipEngine:
 
     def _flatten_expr(self, tree, nodes, keep_alive) -> None:
         """Append the postfix form of ``tree`` -- ``("a" | "b", column[, valid])``, ``("lit", v)`` or
-        ``(op, child, ...)`` with op one of ``+ - * / neg abs least greatest`` -- to ``nodes``."""
+        ``(op, child, ...)`` with op one of ``+ - * / neg abs least greatest``, a comparison, ``isnull`` /
+        ``notnull``, ``and`` / ``or`` / ``not``; ``("if", cond, then, else)`` and ``("null",)`` (a searched CASE and
+        its missing ELSE: GIQL_X_IF / GIQL_X_NULL) -- to ``nodes``."""
         kind = tree[0]
         if kind in ("a", "b", "lit"):
             o, ka = self._c_operand(tree)
             nodes.append(o)
             keep_alive.append(ka)
+            return
+        if kind in ("if", "null"):
+            if len(tree) != (4 if kind == "if" else 1):
+                raise ValueError(f"{kind!r} with {len(tree) - 1} argument(s)")
+            for child in tree[1:]:
+                self._flatten_expr(child, nodes, keep_alive)
+            nd = _lib.COperand()
+            nd.side = _lib.X_IF if kind == "if" else _lib.X_NULL
+            nodes.append(nd)
             return
         if kind not in self._XOPS:
             raise ValueError(f"expression operator {kind!r}")
@@ -1167,6 +1200,82 @@ class HipEngine:
                 out_b[m:].data_ptr() if out_b is not None and hi > lo else None, ctypes.byref(kept), self._stream()))
             m += int(kept.value)
         return (out_a[:m] if out_a is not None else None, out_b[:m] if out_b is not None else None)
+
+    #: programs per ``giql_hip_eval_expr_dev`` call
+    EVAL_OUTS = 8
+
+    def eval_exprs(self, trees, idx_a=None, idx_b=None, n=None, n_rows_a=0, n_rows_b=0):
+        """The VALUE of every expression tree per candidate -- computed SELECT-list columns such as bedtools' -wo /
+        -wao ``overlap_bp`` (``giql_hip_eval_expr_dev``): a list of ``(values, valid)`` device tensors, one per tree.
+
+        ``trees`` are what :meth:`select` takes under ``("expr", tree)`` (with or without that wrapper), plus
+        ``("if", cond, then, else)`` and ``("null",)``.  Candidates are the pairs ``(idx_a[i], idx_b[i])``; a missing
+        id array means "the candidate index"; a NEGATIVE id is the NULL row of its side (every column of that side
+        reads as NULL: the padded row of :meth:`left_pad`).  ``values`` is float64 where :func:`expr_can_float` says
+        the tree can yield a float, else int64 (0 where NULL); ``valid`` is a uint8 tensor (0 = SQL NULL), or ``None``
+        when the output holds no NULL.
+
+        Any ``n`` is accepted: candidates go in slices of :attr:`SELECT_SLICE` as in :meth:`select`; more than
+        :attr:`EVAL_OUTS` trees (or more than 256 nodes) go in several calls."""
+        torch = _torch()
+        if n is None:
+            n = int((idx_a if idx_a is not None else idx_b).shape[0])
+        n = int(n)
+        for t in (idx_a, idx_b):
+            if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or int(t.shape[0]) != n):
+                raise ValueError("id arrays must be contiguous int32 tensors of n rows")
+        trees = [t[1] if t[0] == "expr" else t for t in trees]
+        flat = []
+        for tree in trees:
+            nodes, keep_alive = [], []
+            self._flatten_expr(tree, nodes, keep_alive)
+            if len(nodes) > 256:
+                raise ValueError("at most 256 expression nodes per program")
+            flat.append((nodes, keep_alive, expr_can_float(tree)))
+        batches, cur, used = [], [], 0
+        for k, (nodes, _ka, _fl) in enumerate(flat):
+            if cur and (len(cur) == self.EVAL_OUTS or used + len(nodes) > 256):
+                batches.append(cur)
+                cur, used = [], 0
+            cur.append(k)
+            used += len(nodes)
+        if cur:
+            batches.append(cur)
+        values = [torch.empty(n, dtype=torch.float64 if fl else torch.int64, device=self.device) for _n, _ka, fl in flat]
+        valid = [torch.empty(n, dtype=torch.uint8, device=self.device) for _ in flat]
+        n_null = [0] * len(flat)
+        for batch in batches:
+            nodes = [nd for k in batch for nd in flat[k][0]]
+            c_nodes = (_lib.COperand * len(nodes))(*nodes)
+            c_outs = (_lib.CExprOut * len(batch))()
+            first = 0
+            for j, k in enumerate(batch):
+                c_outs[j].first, c_outs[j].count = first, len(flat[k][0])
+                c_outs[j].type = _lib.T_F64 if flat[k][2] else _lib.T_I64
+                first += len(flat[k][0])
+            for lo in range(0, max(n, 1), self.SELECT_SLICE):
+                hi = min(n, lo + self.SELECT_SLICE)
+                ids, rows = [], []
+                for t, n_rows in ((idx_a, int(n_rows_a)), (idx_b, int(n_rows_b))):
+                    if t is not None:
+                        t = t[lo:hi]
+                    elif lo:    # (as in select: the candidate index stays global past the first slice)
+                        t = torch.arange(lo, hi, dtype=torch.int32, device=self.device)
+                        n_rows = n_rows or n
+                    ids.append(t)
+                    rows.append(n_rows)
+                for j, k in enumerate(batch):
+                    c_outs[j].data = values[k][lo:].data_ptr() if hi > lo else None
+                    c_outs[j].valid = valid[k][lo:].data_ptr() if hi > lo else None
+                nulls = (ctypes.c_int64 * len(batch))()
+                _lib.check(self._L.giql_hip_eval_expr_dev(
+                    self._h, c_nodes, len(nodes), c_outs, len(batch),
+                    ids[0].data_ptr() if ids[0] is not None and hi > lo else None, rows[0],
+                    ids[1].data_ptr() if ids[1] is not None and hi > lo else None, rows[1], hi - lo,
+                    nulls, self._stream()))
+                for j, k in enumerate(batch):
+                    n_null[k] += int(nulls[j])
+        return [(values[k], valid[k] if n_null[k] else None) for k in range(len(flat))]
 
     def mark(self, idx, n_rows: int):
         """``flags[idx] = 1`` over ``n_rows`` zero-initialised bytes (which left rows keep a pair)."""

@@ -598,10 +598,11 @@ class _Residuals:
                               self._valid(col)))
         return specs
 
-    def _spec(self, o):
+    def _spec(self, o, where: str = "predicate"):
         """An operand as :meth:`HipEngine.select` takes it: a column, a literal, or ``("expr", tree)`` -- arithmetic,
         or (round 4) a whole boolean condition: comparisons, IS [NOT] NULL, AND / OR / NOT
-        (``giql_hip_select_expr_dev``)."""
+        (``giql_hip_select_expr_dev``); a computed column's searched CASE comes out as ``("if", cond, then, else)`` /
+        ``("null",)`` for :meth:`HipEngine.eval_exprs`.  ``where`` names the operand's place in an error."""
         import torch
 
         eside = {"l": "a", "r": "b"}
@@ -612,7 +613,7 @@ class _Residuals:
             nv = self._numeric(kind, value)
             if nv is None:
                 raise ValueError(f"column {value!r}: type {self._arrow(kind, value).type} is not supported "
-                                 "in a dialect='hip' predicate" + (" expression" if o.kind == "expr" else ""))
+                                 f"in a dialect='hip' {where}" + (" expression" if o.kind == "expr" else ""))
             return (eside[kind], nv[0], nv[1])
 
         def is_str(t):
@@ -746,6 +747,24 @@ def _pair_distances(plan: JoinPlan, lt, rt, a: DeviceSide, b: DeviceSide, ra, rb
                                    stranded=stranded, strand_a=s1, strand_b=s2)
         out[code] = np.ma.masked_array(dist.cpu().numpy(), mask=(valid == 0).cpu().numpy())
     return out
+
+
+def _computed_columns(plan: JoinPlan, lt, rt, a: DeviceSide, b: DeviceSide, ra, rb, eng: HipEngine) -> list:
+    """The plan's computed columns (``JoinPlan.expressions``: bedtools -wo / -wao's ``overlap_bp``) for the final row
+    ids ``(ra[i], rb[i])`` -- after the residual filters and after the pad of a LEFT join, whose rows carry
+    ``rb == -1``: the kernel reads that as the right table's NULL row -- as int64 / float64 arrays, masked where the
+    value is NULL.  All of them go through ``HipEngine.eval_exprs`` on the device; the raw ``start`` / ``end`` are
+    there already, every other column is uploaded once (``_Residuals``)."""
+    from .engine import expr_can_float
+
+    res = _Residuals(plan, lt, rt, eng, dev_sides={"l": a, "r": b})
+    trees = [res._spec(e, where="computed column") for e in plan.expressions]
+    outs = eng.eval_exprs(trees, idx_a=ra.contiguous(), idx_b=rb.contiguous(), n_rows_a=a.n, n_rows_b=b.n)
+    cols = []
+    for tree, (vals, valid) in zip(trees, outs):
+        v = vals.cpu().numpy().astype(np.float64 if expr_can_float(tree) else np.int64, copy=False)
+        cols.append(v if valid is None else np.ma.masked_array(v, mask=(valid == 0).cpu().numpy()))
+    return cols
 
 
 def _join_with_residuals(plan: JoinPlan, lt, rt, a: DeviceSide, b: DeviceSide, n_chrom: int, eng: HipEngine):
@@ -1527,11 +1546,15 @@ def _join_piece(plan: JoinPlan, lt, rt, ia: np.ndarray, ib: np.ndarray, n_chrom:
         idx = {"l": ra, "r": rb}
         if any(p.side == "pair_distance" for p in plan.projection):
             extra = {"pair_distance": _pair_distances(plan, lt, rt, a, b, ra, rb, eng)}
+        if plan.expressions:
+            extra["expr"] = _computed_columns(plan, lt, rt, a, b, ra, rb, eng)
     elif plan.kind == "LEFT":
         ra, rb = _left_join_rows(plan, lt, rt, a, b, n_chrom, eng)
         if return_indices:
             return ra.cpu().numpy(), rb.cpu().numpy()
         idx = {"l": ra, "r": rb}
+        if plan.expressions:     # the padded rows go through the same call: their -1 is the right table's NULL row
+            extra["expr"] = _computed_columns(plan, lt, rt, a, b, ra, rb, eng)
     elif plan.kind in ("SEMI", "ANTI"):
         if plan.residuals:
             rows = _join_with_residuals(plan, lt, rt, a, b, n_chrom, eng)
@@ -1560,8 +1583,14 @@ def _project(plan: JoinPlan, lt, rt, idx: dict, extra: dict, eng: HipEngine, dev
     except ImportError:  # pragma: no cover
         pa = None
     taken: dict = {}
-    wanted = list(plan.projection) + [Projection(a.side, a.column, f"__giql_a{i}")
-                                      for i, a in enumerate(plan.aggregates) if a.side in ("l", "r")]
+    wanted = []
+    for p in plan.projection:      # a.* / b.* beside a computed column: the table's columns, in its order
+        if p.side in ("l", "r") and p.column == "*":
+            tbl = lt if p.side == "l" else rt
+            wanted += [Projection(p.side, c, c) for c in (tbl.column_names if hasattr(tbl, "column_names") else list(tbl))]
+        else:
+            wanted.append(p)
+    wanted += [Projection(a.side, a.column, f"__giql_a{i}") for i, a in enumerate(plan.aggregates) if a.side in ("l", "r")]
     if pa is not None and device_projection and all(isinstance(t, pa.Table) for t in (lt, rt)):
         for s, tbl in (("l", lt), ("r", rt)):
             want = [p.column for p in wanted if p.side == s]
@@ -1576,6 +1605,8 @@ def _project(plan: JoinPlan, lt, rt, idx: dict, extra: dict, eng: HipEngine, dev
             cols.append(extra["distance"])
         elif p.side == "pair_distance":
             cols.append(extra["pair_distance"][p.column])
+        elif p.side == "expr":
+            cols.append(extra["expr"][int(p.column)])
         elif p.side in taken:
             cols.append(taken[p.side][p.column])
         else:
@@ -1680,9 +1711,10 @@ def _execute_sharded(plan: JoinPlan, lt, rt, ia, ib, n_chrom, devices, return_in
 
 
 def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, return_indices=False,
-            device_projection: bool = True, devices=None, outer_joins: bool = False, row_predicates: bool = False):
-    """Run *plan* (a :class:`JoinPlan`, its string form, or a GIQL query string; ``outer_joins`` and
-    ``row_predicates`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
+            device_projection: bool = True, devices=None, outer_joins: bool = False, row_predicates: bool = False,
+            select_expressions: bool = False):
+    """Run *plan* (a :class:`JoinPlan`, its string form, or a GIQL query string; ``outer_joins``,
+    ``row_predicates`` and ``select_expressions`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
     (``{name: pyarrow.Table | dict of arrays}``).
 
     Returns a ``pyarrow.Table`` with the plan's projected columns (bag semantics,
@@ -1703,7 +1735,8 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
     """
     if isinstance(plan, str):
         plan = JoinPlan.from_string(plan) if is_plan_string(plan) else build_plan(
-            plan, giql_tables, outer_joins=outer_joins, row_predicates=row_predicates)
+            plan, giql_tables, outer_joins=outer_joins, row_predicates=row_predicates,
+            select_expressions=select_expressions)
     if not isinstance(plan, JoinPlan):
         raise ValueError("plan must be a JoinPlan, a plan string or a GIQL query")
     devices = [int(d) for d in devices] if devices is not None else None
@@ -1725,6 +1758,8 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
             raise ValueError(f"table {side.table!r} was not provided")
     lt, rt = tables[plan.left.table], tables[plan.right.table]
     pins = {"l": pinned.get(plan.left.table), "r": pinned.get(plan.right.table)}
+    if plan.expressions and devices is not None and len(devices) > 1:
+        raise ValueError(f"a computed column is evaluated on one device; devices={devices!r} names {len(devices)}")
     if plan.kind == "LEFT" and devices is not None and len(devices) > 1:
         raise NotImplementedError(f"a LEFT OUTER join runs on one device; devices={devices!r} names {len(devices)} "
                                   "(the per-chromosome fan-out does not pad unmatched rows yet)")
@@ -1738,7 +1773,7 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
     if has_pair_distance and devices is not None and len(devices) > 1:
         raise ValueError(f"a DISTANCE column is computed on one device; devices={devices!r} names {len(devices)}")
     if (plan.kind == "INNER" and plan.predicate == "intersects" and not plan.residuals and not has_pair_distance
-            and not (devices and len(devices) > 1)
+            and not plan.expressions and not (devices and len(devices) > 1)
             and any(p is not None and p.index for p in pins.values())):
         # a pinned table offers an index: the join reads it instead of spanning and sorting that table again
         got = _indexed_inner(plan, lt, rt, pins, eng)
@@ -1857,4 +1892,5 @@ def _finish_outer(out, plan: JoinPlan):
     if plan.offset is not None or plan.limit is not None:
         start = plan.offset or 0
         out = out.slice(start, plan.limit) if plan.limit is not None else out.slice(start)
-    return out.select([n for n in out.column_names if not n.startswith("__giql_")])
+    # (by position: a.* and b.* beside a computed column may carry one name twice)
+    return out.select([i for i, n in enumerate(out.column_names) if not n.startswith("__giql_")])

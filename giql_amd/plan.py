@@ -52,6 +52,8 @@ class Projection:
     side: str      # "l", "r", "distance" (NEAREST), "count" (COUNT aggregate); "pair_distance" (INNER: the
                    # DISTANCE of the pair as a nullable int64 column; column = "lr" | "rl" -- which table is the
                    # CASE's A operand -- then "+signed" / "+stranded", src/giql/expanders/_distance.py:67-117);
+                   # "expr" (INNER / LEFT: a computed column, column = the index into JoinPlan.expressions as text);
+                   # "l" / "r" with column "*" (beside a computed column only): every column of that table, by name;
                    # CLUSTER / MERGE:
                    # "star" (every table column), "cluster" (the id), "count" (COUNT(*)); DISJOIN: "l" (a
                    # target column), "disjoin" (column = one of DISJOIN_COLUMNS), "star" (the target's
@@ -148,6 +150,12 @@ class JoinPlan:
     # SEMI / ANTI / COUNT over "contains" / "within" / "within_distance" (HipEngine.semi_anti_pred / count_pred):
     # only plans lowered with the ``row_predicates`` opt-in carry such a predicate, and they say so here
     row_predicates: bool = False
+    # INNER / LEFT only: the computed columns of the SELECT list (bedtools -wo / -wao: "LEAST(a.end, b.end) -
+    # GREATEST(a.start, b.start) AS overlap_bp"), each an Operand("expr", tree) in the serialised form the residuals
+    # use -- a searched CASE is ["fn", "if", [cond, then, else]], a missing ELSE ["fn", "null", []] -- evaluated per
+    # result row by HipEngine.eval_exprs; a Projection("expr", "<index>", name) refers to one.  Only plans lowered with
+    # the ``select_expressions`` opt-in carry any; plan strings written before the field existed load with none
+    expressions: tuple[Operand, ...] = field(default_factory=tuple)
 
     def __post_init__(self) -> None:
         if self.kind not in KINDS:
@@ -160,6 +168,11 @@ class JoinPlan:
             raise ValueError(f"predicate {self.predicate!r} needs an INNER plan, not {self.kind}")
         if self.predicate == "within_distance" and not isinstance(self.max_distance, int):
             raise ValueError("predicate 'within_distance' needs an integer max_distance")
+        if self.expressions and self.kind not in PAIR_KINDS:
+            raise ValueError(f"computed columns need an INNER or LEFT plan, not {self.kind}")
+        for p in self.projection:
+            if p.side == "expr" and not (p.column.isdigit() and int(p.column) < len(self.expressions)):
+                raise ValueError(f"projection {p.name!r} names expression {p.column!r} of {len(self.expressions)}")
 
     def to_dict(self) -> dict:
         """The plan as plain JSON-able data (what :meth:`to_string` serialises)."""
@@ -170,6 +183,7 @@ class JoinPlan:
         d["aggregates"] = [asdict(a) for a in self.aggregates]
         d["having"] = [asdict(h) for h in self.having]
         d["order_by"] = [list(o) for o in self.order_by]
+        d["expressions"] = [asdict(e) for e in self.expressions]
         return d
 
     def to_string(self) -> str:
@@ -200,7 +214,8 @@ class JoinPlan:
             group_by=tuple(d.get("group_by", ())),
             order_by=tuple((o[0], bool(o[1]), bool(o[2]) if len(o) > 2 else not bool(o[1])) for o in d.get("order_by", ())),
             limit=d.get("limit"), offset=d.get("offset"), output=tuple(d.get("output", ())),
-            predicate=d.get("predicate", "intersects"), row_predicates=d.get("row_predicates", False))
+            predicate=d.get("predicate", "intersects"), row_predicates=d.get("row_predicates", False),
+            expressions=tuple(Operand(**e) for e in d.get("expressions", ())))
 
 
 def is_plan_string(text) -> bool:

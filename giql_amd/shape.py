@@ -231,6 +231,10 @@ class SelItem:
     # DISTANCE(x.interval, y.interval [, stranded := b] [, signed := b]) as an output column: (ColRef x, ColRef y,
     # stranded, signed); ``ref`` is None then
     distance: tuple | None = None
+    # a computed column (``select_expressions``): an operand term as the residuals' operands are -- ("col", ColRef) /
+    # ("lit", v) / ("fn", op, [terms]), a searched CASE as ("fn", "if", [condition, then, else]) over a condition
+    # term (``case_term``), a missing ELSE as ("fn", "null", []); ``ref`` is None then and ``alias`` is set
+    expr: tuple | None = None
 
 
 @dataclass
@@ -268,6 +272,9 @@ class JoinShape:
     # opt-in: SEMI / ANTI joins and the count_overlaps shape over CONTAINS / WITHIN / DISTANCE <= N lower to SEMI /
     # ANTI / COUNT plans carrying that predicate instead of declining
     row_predicates: bool = False
+    # opt-in: arithmetic / searched-CASE items of the SELECT list (SelItem.expr) lower to computed columns of an INNER
+    # or LEFT plan; a front end that does not parse them never sets SelItem.expr
+    select_expressions: bool = False
 
 
 # ------------------------------------------------------------------ helpers
@@ -331,8 +338,11 @@ def distance_projection(it: SelItem, left: PlanSide, right: PlanSide, tables: Ta
 
 def resolve_projection(items, left: PlanSide, right: PlanSide, left_only: bool,
                        distance_alias: str | None = None, tables: Tables | None = None,
-                       strands_out: list | None = None) -> tuple[Projection, ...]:
-    """``strands_out`` (a list) receives the "<left>,<right>" strand columns of every stranded DISTANCE item."""
+                       strands_out: list | None = None, exprs_out: list | None = None,
+                       stars: bool = False) -> tuple[Projection, ...]:
+    """``strands_out`` (a list) receives the "<left>,<right>" strand columns of every stranded DISTANCE item,
+    ``exprs_out`` the bound expression of every computed column, in the order their projections number them.
+    ``stars``: a qualified star lowers to ``Projection(side, "*", "*")`` instead of declining."""
     out = []
     for it in items:
         ref = it.ref
@@ -344,8 +354,19 @@ def resolve_projection(items, left: PlanSide, right: PlanSide, left_only: bool,
             if strands and strands_out is not None:
                 strands_out.append(strands)
             continue
+        if it.expr is not None:
+            if exprs_out is None:
+                raise decline("expression in the SELECT list of a NEAREST join")
+            out.append(Projection("expr", str(len(exprs_out)), it.alias))
+            exprs_out.append(expression_operand(it, left, right))
+            continue
         if it.func is not None or ref.count:
             raise decline("COUNT(...) outside the count_overlaps LEFT JOIN ... GROUP BY shape")
+        if ref.star and stars and ref.table is not None and not it.alias:
+            # a.* / b.* beside a computed column (the -wo / -wao recipes, ``select_expressions``): execute() has the
+            # table and enumerates its columns there, so nothing is narrowed
+            out.append(Projection(_side_of(ref, left, right, "the SELECT list"), "*", "*"))
+            continue
         if ref.star:
             # schema-less star enumeration would narrow the result (#202)
             raise decline("star projection")
@@ -424,11 +445,76 @@ def expression_cost(o: Operand) -> tuple:
         kids = [walk(c) for c in t[2]]
         if not kids:
             return (1, 1)
+        if t[1] == "if":    # cond, then, else, IF: the condition and `then` stay live while `else` is evaluated
+            return (sum(k[0] for k in kids) + 1, max(k[1] + i for i, k in enumerate(kids)))
         nodes = sum(k[0] for k in kids) + max(len(kids) - 1, 1)
         depth = max([kids[0][1]] + [1 + k[1] for k in kids[1:]])
         return (nodes, depth)
 
     return walk(o.value)
+
+
+def case_term(whens, otherwise):
+    """A searched CASE -- ``[(condition tree, value term), ...]`` and the ELSE term or None -- as the operand term
+    ``("fn", "if", [condition, then, else])``, nested WHEN by WHEN; a missing ELSE is ``("fn", "null", [])``.  A
+    condition is what ``condition_terms`` takes, except a spatial predicate: NOT is pushed into the comparisons
+    (exact: ``if`` takes ``then`` only where the condition is TRUE, as a filter keeps only TRUE) and the rest becomes
+    a boolean term of the select kernel's programs."""
+    out = otherwise if otherwise is not None else ("fn", "null", [])
+    for cond, value in reversed(whens):
+        for leaf in _leaves(cond):
+            if leaf[0] == DISTANCE_TERM:
+                raise decline("DISTANCE inside an expression of the SELECT list")
+            if leaf[0] != "cmp":
+                raise decline("spatial predicate in a CASE condition")
+        out = ("fn", "if", [_bool_term(_nnf(cond)), value, out])
+    return out
+
+
+def _leaves(node):
+    if node[0] == "leaf":
+        yield node[1]
+    elif node[0] == "not":
+        yield from _leaves(node[1])
+    else:
+        for c in node[1]:
+            yield from _leaves(c)
+
+
+def _string_valued(t, under_cmp: bool = False) -> bool:
+    """Does a string literal stand anywhere but directly under a comparison?"""
+    if t[0] == "lit":
+        return isinstance(t[1], str) and not under_cmp
+    if t[0] != "fn":
+        return False
+    return any(_string_valued(c, t[1] in COMPARISONS) for c in t[2])
+
+
+def expression_operand(it: SelItem, left: PlanSide, right: PlanSide) -> Operand:
+    """A computed column's term bound to the two sides: ``Operand("expr", tree)``, the form residual operands have."""
+    if holds_distance(it.expr):
+        raise decline("DISTANCE inside an expression of the SELECT list")
+    if _string_valued(it.expr):
+        raise decline("string-valued expression in the SELECT list")
+
+    def bind(o) -> Operand:
+        if o[0] == "lit":
+            v = o[1]
+            return Operand("str" if isinstance(v, str) else ("float" if isinstance(v, float) else "int"), v)
+        ref: ColRef = o[1]
+        if ref.star:
+            raise decline("star in an expression of the SELECT list")
+        return Operand(_side_of(ref, left, right, "the SELECT list"), ref.column)
+
+    op = bind_expression(it.expr, bind)
+    if not operand_sides(op):
+        raise decline("constant expression in the SELECT list")
+    nodes, depth = expression_cost(op)
+    if depth > MAX_EXPR_DEPTH:
+        raise decline(f"expression too deep for the eval kernel ({depth} values live, at most {MAX_EXPR_DEPTH})")
+    if nodes > MAX_EXPR_NODES:
+        raise decline(f"expression too large for one eval call ({nodes} nodes, at most {MAX_EXPR_NODES})")
+    return op
 
 
 def check_expression_sizes(residuals, kind: str) -> None:
@@ -721,6 +807,9 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
         raise decline(f"{'count_overlaps / outer' if kind == 'LEFT' else kind} join with a DISTANCE in the SELECT list")
     if dist_items and (shape.group_by or shape.having or any(it.func is not None for it in items)):
         raise decline("DISTANCE in the SELECT list beside GROUP BY / HAVING / aggregates")
+    expr_items = [it for it in items if it.expr is not None]
+    if expr_items and (shape.group_by or shape.having or any(it.func is not None for it in items)):
+        raise decline("expression in the SELECT list beside GROUP BY / HAVING / aggregates")
     if kind == "LEFT":
         # count_overlaps: LEFT [OUTER] JOIN ... COUNT(b.col) ... GROUP BY left keys
         # (_match_count_overlaps, intersects_duckdb.py:432-548); every other outer join declines (:661-662)
@@ -759,6 +848,9 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
         rest = _anti_shortcut(shape, where_terms, right)
         if rest is not None:
             kind, where_terms = "ANTI", rest
+    if expr_items and kind not in ("INNER", "LEFT"):
+        # the value is defined per PAIR (or padded row): SEMI / ANTI keep left rows
+        raise decline(f"{kind} join with an expression in the SELECT list")
     label = "DISTANCE" if predicate == DISTANCE_TERM else predicate.upper()
     row_pred = predicate != "intersects" and shape.row_predicates and kind in ("SEMI", "ANTI", "COUNT")
     if predicate != "intersects" and not shape.row_predicates:
@@ -810,6 +902,10 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
     output: tuple[str, ...] = ()
     having: tuple[Having, ...] = ()
     strands: list = []          # strand columns of the stranded DISTANCE select items (all alike: one pair of tables)
+    exprs: list = []            # the computed columns, as their projections number them
+    # a.* / b.* lower only beside a computed column of an opted-in pair plan, and not under DISTINCT (the two tables'
+    # columns may share names, which a DISTINCT by output name cannot tell apart)
+    stars = bool(expr_items) and kind in ("INNER", "LEFT") and not shape.distinct
     if grouped:
         proj, aggs, groups, output = _resolve_grouped(shape, left, right, left_only)
         visible_aggs = aggs
@@ -819,7 +915,8 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
             # columns it projects are neither grouped nor aggregated
             raise ValueError("a projected column must appear in GROUP BY or inside an aggregate")
     else:
-        proj, aggs, groups = resolve_projection(items, left, right, left_only, tables=tables, strands_out=strands), (), ()
+        proj, aggs, groups = resolve_projection(items, left, right, left_only, tables=tables, strands_out=strands,
+                                                exprs_out=exprs, stars=stars), (), ()
         visible_aggs = ()
     hidden, order = _resolve_order(shape, proj, visible_aggs, left, right, left_only, grouped)
     if predicate == DISTANCE_TERM:
@@ -834,7 +931,7 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
                     residuals=residuals, strand_col=strand_col,
                     aggregates=aggs, group_by=groups, having=having, order_by=order,
                     limit=shape.limit, offset=shape.offset, output=output, predicate=predicate,
-                    row_predicates=row_pred)
+                    row_predicates=row_pred, expressions=tuple(exprs))
 
 
 def _col_refs(x):
@@ -844,6 +941,7 @@ def _col_refs(x):
     elif isinstance(x, SelItem):
         yield from _col_refs(x.ref)
         yield from _col_refs(x.distance)
+        yield from _col_refs(x.expr)
     elif isinstance(x, OrderKey):
         yield from _col_refs(x.ref)
     elif isinstance(x, (tuple, list)):

@@ -44,6 +44,7 @@ from .shape import operand_sides as _operand_sides
 from .shape import decline as _decline
 from .shape import genomic_col as _genomic_col
 from .shape import SPATIAL_TERMS, DisjoinShape, lower_disjoin_shape, lower_join_shape, resolve_projection
+from .shape import case_term as _case_term
 from .shape import comparison_leaf as _comparison_leaf
 from .shape import holds_distance as _holds_distance
 from .shape import norm as _norm
@@ -245,6 +246,9 @@ def _parse_atom(p: _Parser, expr=None):
         raise _decline(f"join condition operand near {t.text!r}")
     if expr is not None and _at_distance_call(p):
         return _parse_distance_call(p)
+    if expr is not None and getattr(p, "case_ok", False) and _at_word(p, "CASE") and not (
+            p.peek(1).kind == "punct" and p.peek(1).text in ".("):
+        return _parse_case(p)
     if expr is not None and not t.quoted and t.text.upper() in _ARITH_FUNCS and p.peek(1).kind == "punct" \
             and p.peek(1).text == "(":
         name = _ARITH_FUNCS[p.next().text.upper()]
@@ -261,6 +265,117 @@ def _parse_atom(p: _Parser, expr=None):
     if p.at_punct("("):
         raise _decline("function call in a join condition")
     return ("col", ref)
+
+
+def _at_word(p: _Parser, word: str, k: int = 0) -> bool:
+    """An unquoted identifier spelling ``word`` (CASE / WHEN / THEN / ELSE / END are no keywords of the tokenizer: a
+    column may carry such a name, ``a.end`` does)."""
+    t = p.peek(k)
+    return t.kind == "id" and not t.quoted and t.text.upper() == word
+
+
+_BOOL_WORDS = ("AND", "OR", "NOT", "IS", "BETWEEN", "IN", "LIKE", "INTERSECTS", "CONTAINS", "WITHIN")
+
+
+def _no_boolean_value(p: _Parser) -> None:
+    """After a value of the SELECT list: a comparison or a boolean operator here would make the value a condition."""
+    t = p.peek()
+    if (t.kind == "punct" and t.text in "=<>!") or (t.kind == "kw" and t.text in _BOOL_WORDS):
+        raise _decline("comparison or boolean as the value of a SELECT item")
+
+
+def _parse_case(p: _Parser):
+    """A searched ``CASE WHEN <condition> THEN <expr> [WHEN ...] [ELSE <expr>] END`` at the cursor -> the operand
+    term of ``shape.case_term``.  A condition is what a residual may be, except a spatial predicate; ``a.end`` is a
+    column (a keyword is a name after a dot), a bare END closes the CASE."""
+    p.next()
+    if not _at_word(p, "WHEN"):
+        raise _decline("simple CASE (CASE <value> WHEN ...) in the SELECT list")
+    whens = []
+    while _at_word(p, "WHEN"):
+        p.next()
+        cond = _parse_bool(p, False)
+        if not _at_word(p, "THEN"):
+            raise ValueError(f"Parse error: expected THEN near {p.peek().text!r}")
+        p.next()
+        value = _parse_operand(p)
+        _no_boolean_value(p)
+        whens.append((cond, value))
+    otherwise = None
+    if _at_word(p, "ELSE"):
+        p.next()
+        otherwise = _parse_operand(p)
+        _no_boolean_value(p)
+    if not _at_word(p, "END"):
+        raise ValueError(f"Parse error: expected END near {p.peek().text!r}")
+    p.next()
+    return _case_term(whens, otherwise)
+
+
+def _at_expression_item(p: _Parser) -> bool:
+    """Does a computed column start at the cursor (``select_expressions``)?  A number, a string, a sign or a
+    parenthesis; a CASE; LEAST / GREATEST / ABS; a column or a call followed by an operator."""
+    t = p.peek()
+    if t.kind in ("num", "str") or p.at_punct("(") or p.at_punct("-") or p.at_kw("NOT"):
+        return True
+    if t.kind != "id":
+        return False
+    nxt = p.peek(1)
+    if _at_word(p, "CASE") and not (nxt.kind == "punct" and nxt.text in ".,") and not (nxt.kind == "kw" and nxt.text in ("FROM", "AS")):
+        return True
+    k = 1
+    if nxt.kind == "punct" and nxt.text == "(":
+        if not t.quoted and t.text.upper() in _ARITH_FUNCS:
+            return True
+        depth = 0
+        while p.peek(k).kind != "end":      # the call's closing parenthesis
+            depth += (p.peek(k).kind == "punct") * ((p.peek(k).text == "(") - (p.peek(k).text == ")"))
+            k += 1
+            if depth == 0:
+                break
+    elif nxt.kind == "punct" and nxt.text == ".":
+        if p.peek(2).kind == "punct":       # a.*
+            return False
+        k = 3
+    after = p.peek(k)
+    return (after.kind == "punct" and after.text in "+-/*=<>!%") or (after.kind == "kw" and after.text in _BOOL_WORDS)
+
+
+def _parse_expression_item(p: _Parser) -> SelItem:
+    """One computed column of the SELECT list: ``<expression> [AS] alias``."""
+    if p.at_kw("NOT"):
+        raise _decline("comparison or boolean as the value of a SELECT item")
+    p.case_ok = True
+    try:
+        try:
+            term = _parse_operand(p)
+        except HipDeclined as exc:
+            if str(exc).startswith("function call in a join condition:"):    # (the operand parser's wording)
+                raise _decline("function call in an expression of the SELECT list") from None
+            raise
+        except ValueError:
+            _no_boolean_value(p)    # "(a.x > 1) AS hi": the operand parser met a comparison where it wanted ")"
+            raise
+        _no_boolean_value(p)
+    finally:
+        p.case_ok = False
+    if p.peek().kind == "punct" and p.peek().text in "%|&^":
+        raise _decline(f"operator {p.peek().text!r} in an expression of the SELECT list")
+    alias = None
+    if p.at_kw("AS"):
+        p.next()
+        alias = p.next().text
+    elif p.peek().kind == "id":
+        alias = p.next().text
+    if term[0] == "col":                    # a parenthesised plain column
+        return SelItem(term[1], alias)
+    if term[0] == "distfn":
+        return SelItem(None, alias, distance=term[1:])
+    if term[0] == "lit":
+        raise _decline("constant expression in the SELECT list")
+    if alias is None:
+        raise _decline("expression without an alias in the SELECT list")
+    return SelItem(None, alias, expr=term)
 
 
 def _parse_operand(p: _Parser, level: int = 0):
@@ -537,12 +652,20 @@ def _parse_having(p: _Parser):
     return terms
 
 
-def _parse_projection(p: _Parser) -> list[SelItem]:
+def _parse_projection(p: _Parser, select_expressions: bool = False) -> list[SelItem]:
     """SELECT list: qualified columns and plain aggregates ``FUNC([DISTINCT] <col>)`` / ``COUNT(*)``
     (the projections ``_resolve_projections`` can rebuild, intersects_duckdb.py:1402-1644); every
-    other expression declines (#204, #205)."""
+    other expression declines (#204, #205) -- unless ``select_expressions`` opts in to computed columns:
+    arithmetic over columns and literals, LEAST / GREATEST / ABS and a searched CASE, each with an alias
+    (docs/recipes/bedtools-migration.rst, -wo / -wao)."""
     items: list[SelItem] = []
     while True:
+        if select_expressions and _at_expression_item(p):
+            items.append(_parse_expression_item(p))
+            if p.at_punct(","):
+                p.next()
+                continue
+            break
         if p.peek().kind == "kw" and not p.at_kw("FROM"):
             raise _decline(f"projection starting with {p.peek().text}")
         if p.peek().kind in ("num", "str") or p.at_punct("("):
@@ -1103,27 +1226,41 @@ def _lower_disjoin(p: _Parser, tbls: Tables) -> JoinPlan:
     return lower_disjoin_shape(shape, tbls)
 
 
-def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predicates: bool = False) -> JoinPlan:
+def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predicates: bool = False,
+               select_expressions: bool = False) -> JoinPlan:
     """Parse *giql* and lower the INTERSECTS / NEAREST join (or a CLUSTER / MERGE
     query) to a :class:`JoinPlan`.
 
     ``outer_joins=True`` opts in to LEFT [OUTER] JOIN: outside the count_overlaps shape it lowers to a plan of
     kind ``LEFT`` (or ``ANTI``, for the ``WHERE b.<key> IS NULL`` recipe) instead of declining.
     ``row_predicates=True`` opts in to SEMI / ANTI joins and the count_overlaps shape over CONTAINS, WITHIN and
-    ``DISTANCE(...) <= N``: they lower to SEMI / ANTI / COUNT plans carrying that predicate instead of declining."""
+    ``DISTANCE(...) <= N``: they lower to SEMI / ANTI / COUNT plans carrying that predicate instead of declining.
+    ``select_expressions=True`` opts in to computed columns in the SELECT list of an INNER or LEFT join -- arithmetic
+    over columns and literals, LEAST / GREATEST / ABS, a searched CASE, each with an alias (bedtools -wo / -wao:
+    ``LEAST(a.end, b.end) - GREATEST(a.start, b.start) AS overlap_bp``) -- instead of declining them."""
     probe = _Parser(giql)
-    if _disjoin_from(probe) is not None:
-        return _lower_disjoin(probe, tables if isinstance(tables, Tables) else build_tables(tables))
-    if probe.at_kw("SELECT") and _has_cluster_or_merge(probe):
-        return _lower_cluster(probe, tables if isinstance(tables, Tables) else build_tables(tables))
-    if probe.at_kw("SELECT") and _is_single_table_filter(probe):
-        return _lower_filter(probe, tables if isinstance(tables, Tables) else build_tables(tables))
-    plan = _lower(giql, tables, want_sql=False, outer_joins=outer_joins, row_predicates=row_predicates)
+    tbls = tables if isinstance(tables, Tables) else build_tables(tables)
+    for routed, lower, what in ((_disjoin_from(probe) is not None, _lower_disjoin, "DISJOIN"),
+                                (probe.at_kw("SELECT") and _has_cluster_or_merge(probe), _lower_cluster, "CLUSTER / MERGE"),
+                                (probe.at_kw("SELECT") and _is_single_table_filter(probe), _lower_filter,
+                                 "a literal-range filter")):
+        if not routed:
+            continue
+        try:
+            return lower(probe, tbls)
+        except HipDeclined as exc:
+            # these operators compute no column: with the opt-in the decline names the operator
+            if select_expressions and str(exc).startswith("expression in the SELECT list:"):
+                raise _decline(f"expression in the SELECT list of {what}") from None
+            raise
+    plan = _lower(giql, tables, want_sql=False, outer_joins=outer_joins, row_predicates=row_predicates,
+                  select_expressions=select_expressions)
     assert isinstance(plan, JoinPlan)
     return plan
 
 
-def _lower(giql: str, tables, want_sql: bool, outer_joins: bool = False, row_predicates: bool = False):
+def _lower(giql: str, tables, want_sql: bool, outer_joins: bool = False, row_predicates: bool = False,
+           select_expressions: bool = False):
     tbls = tables if isinstance(tables, Tables) else build_tables(tables)
     p = _Parser(giql)
     if p.at_kw("WITH"):
@@ -1145,7 +1282,7 @@ def _lower(giql: str, tables, want_sql: bool, outer_joins: bool = False, row_pre
         proj_text = _render(p.toks[proj_start:p.i])
         items = None
     else:
-        items = _parse_projection(p)
+        items = _parse_projection(p, select_expressions=bool(select_expressions))
         proj_text = ""
     p.expect_kw("FROM")
     from_ref = p.table_ref()
@@ -1227,7 +1364,8 @@ def _lower(giql: str, tables, want_sql: bool, outer_joins: bool = False, row_pre
                         stranded=nearest[3], strand_col=strand_col)
 
     shape = JoinShape(items=items, from_ref=from_ref, join_ref=join_ref, kind=kind, on_seen=on_seen, using=using,
-                      distinct=distinct, outer_joins=bool(outer_joins), row_predicates=bool(row_predicates))
+                      distinct=distinct, outer_joins=bool(outer_joins), row_predicates=bool(row_predicates),
+                      select_expressions=bool(select_expressions))
     if on_seen:
         if p.peek().kind not in ("id", "num", "str") and not p.at_punct("-") and not p.at_punct("(") \
                 and not p.at_kw("NOT"):
@@ -1312,17 +1450,19 @@ def _render(toks: list[Tok]) -> str:
 
 
 def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins: bool = False,
-              row_predicates: bool = False) -> str:
+              row_predicates: bool = False, select_expressions: bool = False) -> str:
     """Mirror of ``giql.transpile`` for this backend's path.
 
     ``dialect="hip"``: returns the plan string of the INTERSECTS / NEAREST join
     (hand it to :func:`giql_amd.execute`); ``outer_joins=True`` lets a LEFT [OUTER] JOIN lower too
-    and ``row_predicates=True`` the per-row joins over CONTAINS / WITHIN / DISTANCE (:func:`build_plan`).  ``dialect=None``: returns SQL for the
+    and ``row_predicates=True`` the per-row joins over CONTAINS / WITHIN / DISTANCE, ``select_expressions=True``
+    computed columns such as ``overlap_bp`` in the SELECT list (:func:`build_plan`).  ``dialect=None``: returns SQL for the
     literal-range predicate (plumbing, BASELINE config 1).  Other dialects belong to
     the reference package.
     """
     if dialect == "hip":
-        return build_plan(giql, tables, outer_joins=outer_joins, row_predicates=row_predicates).to_string()
+        return build_plan(giql, tables, outer_joins=outer_joins, row_predicates=row_predicates,
+                          select_expressions=select_expressions).to_string()
     if dialect is None:
         return _lower(giql, tables, want_sql=True)
     raise ValueError(

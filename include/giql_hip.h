@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define GIQL_HIP_ABI_VERSION 4  /* 2: giql_hip_stats.phase_bytes, pinned host outputs, plan export; 3: DISJOIN; 4: CONTAINS / WITHIN (DISTANCE added two symbols, left_pad one, the row predicates two: no change) */
+#define GIQL_HIP_ABI_VERSION 4  /* 2: giql_hip_stats.phase_bytes, pinned host outputs, plan export; 3: DISJOIN; 4: CONTAINS / WITHIN (DISTANCE added two symbols, left_pad one, the row predicates two, eval_expr one: no change) */
 
 enum {
   GIQL_OK = 0,
@@ -426,6 +426,9 @@ enum { GIQL_X_ADD = 16, GIQL_X_SUB = 17, GIQL_X_MUL = 18, GIQL_X_DIV = 19, GIQL_
         * reference inlines it as text (src/giql/expanders/intersects_duckdb.py:889-957) -- no normal form */
        GIQL_X_EQ = 24, GIQL_X_NE = 25, GIQL_X_LT = 26, GIQL_X_LE = 27, GIQL_X_GT = 28, GIQL_X_GE = 29,
        GIQL_X_ISNULL = 30, GIQL_X_NOTNULL = 31, GIQL_X_AND = 32, GIQL_X_OR = 33, GIQL_X_NOT = 34 };
+/* a searched CASE (giql_hip_eval_expr_dev; legal in giql_hip_select_expr_dev programs as well) */
+#define GIQL_X_IF   35  /* pops else, then, cond; pushes `then` when cond is TRUE, `else` when it is FALSE or NULL */
+#define GIQL_X_NULL 36  /* pushes an integer NULL (a CASE without ELSE) */
 
 typedef struct giql_operand {
   int32_t side;          /* GIQL_SIDE_*                                          */
@@ -477,13 +480,51 @@ int giql_hip_select_dev(giql_hip_ctx* ctx, const giql_pred* preds, int32_t n_pre
  * most 12 values are live.  Semantics are those of the reference's execution target (DuckDB): integer + - *
  * stay 64-bit integers, `/` is a floating division and NULL on a zero divisor, NULL propagates through
  * arithmetic, LEAST / GREATEST skip NULL arguments; comparisons and AND / OR / NOT are three-valued (a boolean
- * program is the lhs of a predicate with op GIQL_OP_IS_TRUE: the candidate is kept when it is TRUE). */
+ * program is the lhs of a predicate with op GIQL_OP_IS_TRUE: the candidate is kept when it is TRUE).  GIQL_X_IF /
+ * GIQL_X_NULL (a searched CASE, see giql_hip_eval_expr_dev) are legal here too; a negative row id stays
+ * GIQL_ERR_INVALID in both select calls. */
 int giql_hip_select_expr_dev(giql_hip_ctx* ctx, const giql_pred* preds, int32_t n_preds,
                              const giql_operand* nodes, int32_t n_nodes,
                              const int32_t* idx_a, int64_t n_rows_a,
                              const int32_t* idx_b, int64_t n_rows_b, int64_t n,
                              int32_t* out_a, int32_t* out_b, int64_t* n_kept,
                              void* stream);
+/* Computed SELECT-list columns: the VALUE of an expression per candidate instead of a keep bit -- bedtools' -wo /
+ * -wao of docs/recipes/bedtools-migration.rst and docs/recipes/intersect.rst, "(LEAST(a.end, b.end) -
+ * GREATEST(a.start, b.start)) AS overlap_bp", under a LEFT JOIN inside "CASE WHEN b.chrom IS NULL THEN 0 ELSE ... END".
+ * outs[k].data[i] / .valid[i] = the value of program k for candidate i (idx_a[i], idx_b[i]), i < n.
+ * 1 <= n_outs <= 8 programs share one pass over the candidates; nodes / outs are HOST arrays.
+ * Programs and semantics are those of giql_hip_select_expr_dev: at most 256 nodes in all, at most 12 live values;
+ * integers stay 64-bit and wrap, `/` is a binary64 division and NULL on a zero divisor, NULL propagates, LEAST /
+ * GREATEST skip NULLs, booleans are Kleene's with TRUE / FALSE as 1 / 0.  GIQL_X_IF evaluates both branches: nothing
+ * in the evaluator can raise, so that is exact.
+ * A NEGATIVE row id is the NULL row of its side -- the padded row of giql_hip_left_pad_dev: every column leaf of
+ * that side reads as NULL whatever its validity pointer, and nothing is read through the id.  An id >= n_rows of its
+ * side is GIQL_ERR_INVALID, as in select (giql_hip_select_* keep rejecting negative ids too).  A missing id array
+ * means "the candidate index".
+ * Static typing, on the host, before anything is launched: a value can be a float when it is an F32 / F64 column or a
+ * float literal, the result of `/`, or arithmetic / NEG / ABS / LEAST / GREATEST / IF (then, else) over such a
+ * value; comparisons, IS [NOT] NULL, AND / OR / NOT and GIQL_X_NULL are integers.  A program that can yield a float
+ * needs a GIQL_T_F64 output (GIQL_ERR_INVALID otherwise); a GIQL_T_F64 output converts an integer value with one
+ * round-to-nearest (double).
+ * n <= 0x7FFFFFF0 (a caller with more slices them: HipEngine.eval_exprs); n == 0 is GIQL_OK with nothing launched.
+ * n_outs outside 1..8, a NULL data, a type other than GIQL_T_I64 / GIQL_T_F64 or a malformed program:
+ * GIQL_ERR_INVALID, the message names the output.  n_null[k] = the number of NULL results of output k (read back
+ * with the status: no extra synchronisation).
+ * Like select, the call stages its nodes in the context's workspace: an INNER / CONTAINS / DISJOIN plan held there
+ * is gone afterwards (giql_hip_inner_fill_dev and its kin return GIQL_ERR_STATE). */
+typedef struct giql_expr_out {
+  int32_t first, count;   /* the program: nodes[first .. first + count) */
+  int32_t type;           /* GIQL_T_I64 or GIQL_T_F64: element type of data */
+  int32_t reserved;
+  void* data;             /* device, n elements of 8 bytes */
+  uint8_t* valid;         /* device, n bytes: 1 = value, 0 = SQL NULL (data is 0 then); may be NULL */
+} giql_expr_out;
+int giql_hip_eval_expr_dev(giql_hip_ctx* ctx, const giql_operand* nodes, int32_t n_nodes,
+                           const giql_expr_out* outs, int32_t n_outs,
+                           const int32_t* idx_a, int64_t n_rows_a,
+                           const int32_t* idx_b, int64_t n_rows_b, int64_t n,
+                           int64_t* n_null /* host, n_outs entries, may be NULL */, void* stream);
 /* flags[idx[i]] = 1 for i < n (flags: device, n_rows bytes, caller-initialised):
  * the left rows that keep at least one pair, for SEMI / ANTI with two-sided
  * residuals (src/giql/expanders/intersects_duckdb.py:1254-1282). */
