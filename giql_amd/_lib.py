@@ -53,6 +53,7 @@ SYMBOLS = [
     "giql_hip_left_pad_dev",
     "giql_hip_semi_anti_pred_dev", "giql_hip_count_pred_dev",
     "giql_hip_eval_expr_dev",
+    "giql_hip_merge_agg_dev",
 ]
 
 
@@ -138,6 +139,22 @@ class CExprOut(ctypes.Structure):
         ("valid", ctypes.c_void_p),
     ]
 
+
+class CAgg(ctypes.Structure):
+    """``giql_agg`` (include/giql_hip.h)."""
+
+    _fields_ = [
+        ("func", ctypes.c_int32),
+        ("type", ctypes.c_int32),
+        ("data", ctypes.c_void_p),
+        ("valid", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("out_nn", ctypes.c_void_p),
+    ]
+
+
+#: ``GIQL_AGG_*``: the kernel's functions (AVG is SUM / non-NULL count, divided by the engine)
+AGG_FUNCS = {"COUNT": 0, "SUM": 1, "MIN": 2, "MAX": 3}
 
 OPS = {"=": 0, "==": 0, "!=": 1, "<>": 1, "<": 2, "<=": 3, ">": 4, ">=": 5, "isnull": 6, "notnull": 7, "istrue": 8}
 SIDE_A, SIDE_B, SIDE_LIT, SIDE_EXPR = 0, 1, 2, 3
@@ -233,6 +250,8 @@ def load() -> ctypes.CDLL:
     L.giql_hip_window_plan_dev.argtypes = [vp, P(CSide), P(CSide), i32, i64, vp, P(i64)]
     L.giql_hip_distance_dev.argtypes = [vp, P(CSide), P(CSide), vp, vp, i64, vp, vp, i32, vp, vp, vp]
     L.giql_hip_eval_expr_dev.argtypes = [vp, P(COperand), i32, P(CExprOut), i32, vp, i64, vp, i64, i64, P(i64), vp]
+    L.giql_hip_merge_agg_dev.argtypes = [vp, P(CSide), i32, i64, P(CPred), i32, P(CAgg), i32, vp, vp, vp, vp, i64,
+                                         P(i64), vp]
     _lib = L
     return L
 

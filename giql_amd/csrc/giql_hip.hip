@@ -30,6 +30,7 @@
 #include "eval_kernels.hip.h"
 #include "outer_kernels.hip.h"
 #include "cluster_kernels.hip.h"
+#include "merge_agg_kernels.hip.h"
 #include "disjoin_kernels.hip.h"
 #include "contain_kernels.hip.h"
 #include "distance_kernels.hip.h"
@@ -3524,6 +3525,8 @@ struct ClusterBufs {
   u64 *bsums = nullptr, *total = nullptr;
   u32* head_pos = nullptr;
   u32* seg_end = nullptr;  // MERGE under a predicate: MAX(end) per region
+  int n_aggs = 0;          // MERGE with aggregates: set before cluster_front
+  u64* agg_ws = nullptr;   //   per aggregate the four per-tile carry arrays (merge_agg_kernels.hip.h)
 };
 
 static int cluster_front(giql_hip_ctx* ctx, hipStream_t st, const giql_side* s, int32_t n_chrom,
@@ -3549,6 +3552,7 @@ static int cluster_front(giql_hip_ctx* ctx, hipStream_t st, const giql_side* s, 
     cb.dummy_irr = c.take<u32>(16);
     cb.head_pos = want_heads ? c.take<u32>(n + 1) : nullptr;
     cb.seg_end = want_heads && preds && preds->n > 0 ? c.take<u32>(n + 1) : nullptr;
+    cb.agg_ws = cb.n_aggs ? c.take<u64>((size_t)cb.n_aggs * 4 * cdiv(n, (size_t)MAGG_TILE)) : nullptr;
     return c.off;
   };
   GIQL_TRY(claim_arena(ctx, st, carve));
@@ -3720,7 +3724,7 @@ int giql_hip_cluster_pred_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_c
 static int giql_hip_merge_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom, int64_t distance,
                        int32_t* out_chrom, int32_t* out_start, int32_t* out_end,
                        int64_t* out_count, int64_t capacity, int64_t* n_out, void* stream,
-                       const DevPreds* preds = nullptr) {
+                       const DevPreds* preds = nullptr, MaggArgs* aggs = nullptr) {
   GIQL_TRY(check_cluster_args(ctx, s, n_chrom));
   if (!n_out) return set_err(GIQL_ERR_INVALID, "n_out is NULL");
   GIQL_TRY(begin_call(ctx));
@@ -3733,7 +3737,8 @@ static int giql_hip_merge_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int32_
   if (n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
   ClusterBufs cb;
   const bool pred = preds && preds->n > 0;
-  GIQL_TRY(cluster_front(ctx, st, s, n_chrom, distance, pred, true, cb, preds));
+  cb.n_aggs = aggs ? aggs->n_aggs : 0;
+  GIQL_TRY(cluster_front(ctx, st, s, n_chrom, distance, pred || aggs, true, cb, preds));
   u64 h_total = 0;
   HIP_TRY(hipMemcpyAsync(&h_total, cb.total, sizeof(u64), hipMemcpyDeviceToHost, st));
   GIQL_TRY(cluster_status(ctx, st));
@@ -3741,7 +3746,7 @@ static int giql_hip_merge_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int32_
     return set_err(GIQL_ERR_CAPACITY, "%llu merged regions, capacity %lld",
                    (unsigned long long)h_total, (long long)capacity);
   {
-    Phase ph(ctx, st, GIQL_PH_FILL, pred ? 3 : 2);
+    Phase ph(ctx, st, GIQL_PH_FILL, (pred ? 3 : 2) + (aggs ? 2 : 0));
     hipLaunchKernelGGL(k_merge_heads, dim3(cdiv((u64)s->n, 256)), dim3(256), 0, st, cb.flags, cb.excl,
                        (u32)s->n, cb.head_pos);
     if (pred && h_total) {
@@ -3753,6 +3758,19 @@ static int giql_hip_merge_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int32_
       hipLaunchKernelGGL(k_merge_rows, dim3(cdiv(h_total, 256)), dim3(256), 0, st, cb.head_pos,
                          (u32)h_total, (u32)s->n, cb.sb.key[0], cb.pmax, pred ? cb.seg_end : (u32*)nullptr, cb.lb.chrom_first,
                          cb.lb.chrom_base, n_chrom, out_chrom, out_start, out_end, (i64*)out_count);
+    if (aggs && h_total) {  // one segmented reduction over the sorted order; every region gets exactly one writer
+      const u32 n_tiles = cdiv((u64)s->n, MAGG_TILE);
+      for (int a = 0; a < aggs->n_aggs; a++) {
+        u64* w = cb.agg_ws + (size_t)a * 4 * n_tiles;
+        aggs->aggs[a].first_v = w, aggs->aggs[a].last_v = w + n_tiles;
+        aggs->aggs[a].first_c = (i64*)(w + 2 * (size_t)n_tiles), aggs->aggs[a].last_c = (i64*)(w + 3 * (size_t)n_tiles);
+      }
+      hipLaunchKernelGGL(k_magg_tiles, dim3(n_tiles), dim3(MAGG_TILE), 0, st, cb.sb.rid[0], cb.excl, cb.flags,
+                         (u32)s->n, *aggs);
+      if (n_tiles > 1)
+        hipLaunchKernelGGL(k_magg_fold, dim3(cdiv((u64)n_tiles - 1, 256 / WAVE)), dim3(256), 0, st, cb.excl, cb.flags,
+                           (u32)s->n, n_tiles, *aggs);
+    }
     GIQL_TRY(post_launch("merge rows"));
   }
   HIP_TRY(hipStreamSynchronize(st));
@@ -3777,6 +3795,39 @@ int giql_hip_merge_pred_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chr
   DevPreds ps;
   GIQL_TRY(convert_preds(preds, n_preds, ps, nullptr));
   return with_order_fallback(ctx, [&] { return giql_hip_merge_dev_impl(ctx, s, n_chrom, distance, out_chrom, out_start, out_end, out_count, capacity, n_out, stream, &ps); });
+}
+
+// MERGE with aggregates: the host array of giql_agg -> the by-value kernel argument.  Aggregates that read the same
+// (data, valid, type) share one column, i.e. one gather; the kernel walks the aggregates column by column.
+int giql_hip_merge_agg_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom, int64_t distance,
+                           const giql_pred* preds, int32_t n_preds, const giql_agg* aggs, int32_t n_aggs,
+                           int32_t* out_chrom, int32_t* out_start, int32_t* out_end, int64_t* out_count,
+                           int64_t capacity, int64_t* n_out, void* stream) {
+  if (n_preds < 0 || n_preds > SEL_MAX_PREDS || (n_preds && !preds))
+    return set_err(GIQL_ERR_INVALID, "bad predicates (at most %d)", SEL_MAX_PREDS);
+  if (n_aggs < 1 || n_aggs > MAGG_MAX || !aggs)
+    return set_err(GIQL_ERR_INVALID, "%d aggregates: MERGE takes 1 to %d", n_aggs, MAGG_MAX);
+  MaggArgs ma;
+  memset(&ma, 0, sizeof(ma));
+  ma.n_aggs = n_aggs;
+  for (int k = 0; k < n_aggs; k++) {
+    const giql_agg& g = aggs[k];
+    if (g.func < GIQL_AGG_COUNT || g.func > GIQL_AGG_MAX)
+      return set_err(GIQL_ERR_INVALID, "aggregate %d: function %d", k, g.func);
+    if (g.type < GIQL_T_I32 || g.type > GIQL_T_F64)
+      return set_err(GIQL_ERR_INVALID, "aggregate %d: column type %d (int32, int64, float32 or float64)", k, g.type);
+    if (!g.data || !g.out) return set_err(GIQL_ERR_INVALID, "aggregate %d: data or out is NULL", k);
+    int c = 0;
+    while (c < ma.n_cols && !(ma.cols[c].data == g.data && ma.cols[c].valid == g.valid && ma.cols[c].type == g.type)) c++;
+    if (c == ma.n_cols) ma.cols[ma.n_cols++] = MaggCol{g.data, g.valid, g.type};
+    ma.aggs[k].func = g.func;
+    ma.aggs[k].col = c;
+    ma.aggs[k].out = (u64*)g.out;
+    ma.aggs[k].out_nn = (i64*)g.out_nn;
+  }
+  DevPreds ps;
+  GIQL_TRY(convert_preds(preds, n_preds, ps, nullptr));
+  return with_order_fallback(ctx, [&] { return giql_hip_merge_dev_impl(ctx, s, n_chrom, distance, out_chrom, out_start, out_end, out_count, capacity, n_out, stream, &ps, &ma); });
 }
 
 // ----------------------------------------------------------------- DISJOIN

@@ -967,6 +967,102 @@ class HipEngine:
         k = int(m.value)
         return c[:k], st[:k], en[:k], cnt[:k]
 
+    #: aggregates per :meth:`merge_agg` call, as asked for (the C ABI takes 8 kernel aggregates)
+    MERGE_AGG_MAX = 8
+
+    def merge_agg(self, s: DeviceSide, n_chrom: int, distance: int, aggs, preds=None):
+        """MERGE with aggregates per merged region (``src/giql/expanders/merge.py:317-390``): the four tensors of
+        :meth:`merge` plus, per entry of ``aggs``, ``(values, valid)``.  An entry is ``(func, values_tensor,
+        valid_tensor_or_None)``, ``func`` in COUNT, SUM, MIN, MAX, AVG; the tensors are contiguous int32 / int64 /
+        float32 / float64 (validity: uint8 / bool) device tensors of ``s.n`` rows.  ``valid`` is "the region has a
+        non-NULL input" (COUNT: always).  SUM / MIN / MAX of an integer column are int64, of a float column float64;
+        AVG is ``double(sum) / double(non-NULL count)`` computed on the device from the kernel's SUM, which a SUM
+        over the same column shares.  Float sums use no atomics: the same call returns the same bits."""
+        torch = _torch()
+        aggs = [(str(a[0]).upper(), a[1], a[2] if len(a) > 2 else None) for a in aggs]
+        if not 1 <= len(aggs) <= self.MERGE_AGG_MAX:
+            raise ValueError(f"MERGE takes 1 to {self.MERGE_AGG_MAX} aggregates, got {len(aggs)}")
+        ok = (torch.int32, torch.int64, torch.float32, torch.float64)
+        for func, t, valid in aggs:
+            if func not in ("COUNT", "SUM", "MIN", "MAX", "AVG"):
+                raise ValueError(f"aggregate function {func!r}")
+            if t.dtype not in ok or t.dim() != 1 or not t.is_contiguous() or int(t.shape[0]) != s.n:
+                raise ValueError("an aggregate column must be a contiguous 1-D int32/int64/float32/float64 tensor "
+                                 "with one value per row of the table")
+            if valid is not None and (valid.dtype not in (torch.uint8, torch.bool) or valid.shape != t.shape
+                                      or not valid.is_contiguous()):
+                raise ValueError("validity must be a contiguous uint8/bool tensor of the column's length")
+        if preds:
+            self._check_pred_rows(s, preds)
+        dtypes = [torch.int64 if f == "COUNT" else torch.float64 if f == "AVG" or t.is_floating_point() else torch.int64
+                  for f, t, _v in aggs]
+
+        def of_rows(rows):
+            if rows is None:
+                return aggs
+            taken = {}  # one copy per tensor: aggregates over one column keep sharing it
+
+            def take(t):
+                if t is not None and t.data_ptr() not in taken:
+                    taken[t.data_ptr()] = t[rows].contiguous()
+                return None if t is None else taken[t.data_ptr()]
+
+            return [(f, take(t), take(v)) for f, t, v in aggs]
+
+        return self._wide(
+            lambda sub, _b, rows: self._merge_agg_once(sub, n_chrom, distance, of_rows(rows),
+                                                       self._preds_of_rows(preds, rows)),
+            lambda parts: wide.merge_agg(parts, self.device, dtypes), s, None, n_chrom)
+
+    def _merge_agg_once(self, s: DeviceSide, n_chrom: int, distance: int, aggs, preds=None):
+        torch = _torch()
+        n = s.n
+        types = {torch.int32: _lib.T_I32, torch.int64: _lib.T_I64, torch.float32: _lib.T_F32,
+                 torch.float64: _lib.T_F64}
+        # the kernel's aggregates: AVG asks for SUM, and a SUM and an AVG over one column share it
+        kernel, slot = [], []
+        for func, t, valid in aggs:
+            key = ("SUM" if func == "AVG" else func, t.data_ptr(), None if valid is None else valid.data_ptr(), t.dtype)
+            if key not in [k[0] for k in kernel]:
+                flt = t.is_floating_point() and key[0] != "COUNT"
+                kernel.append((key, t, valid, torch.empty(n, dtype=torch.float64 if flt else torch.int64,
+                                                          device=self.device),
+                               torch.empty(n, dtype=torch.int64, device=self.device)))
+            slot.append([k[0] for k in kernel].index(key))
+        c_aggs = (_lib.CAgg * len(kernel))()
+        for j, (key, t, valid, out, nn) in enumerate(kernel):
+            c_aggs[j].func, c_aggs[j].type = _lib.AGG_FUNCS[key[0]], types[t.dtype]
+            c_aggs[j].data = t.data_ptr() if n else 1  # never dereferenced when empty
+            c_aggs[j].valid = valid.data_ptr() if valid is not None and n else None
+            c_aggs[j].out = out.data_ptr() if n else 1
+            c_aggs[j].out_nn = nn.data_ptr() if n else None
+        c = torch.empty(n, dtype=torch.int32, device=self.device)
+        st = torch.empty(n, dtype=torch.int32, device=self.device)
+        en = torch.empty(n, dtype=torch.int32, device=self.device)
+        cnt = torch.empty(n, dtype=torch.int64, device=self.device)
+        m = ctypes.c_int64(0)
+        c_preds, k = None, 0
+        if preds:
+            c_preds, k, _keep_alive, _nodes, n_nodes = self._c_preds(preds)
+            if n_nodes:
+                raise ValueError("arithmetic in a CLUSTER / MERGE predicate is not supported")
+        _lib.check(self._L.giql_hip_merge_agg_dev(
+            self._h, s.c_struct(), int(n_chrom), int(distance), c_preds, k, c_aggs, len(kernel),
+            c.data_ptr() if n else None, st.data_ptr() if n else None, en.data_ptr() if n else None,
+            cnt.data_ptr() if n else None, n, ctypes.byref(m), self._stream()))
+        r = int(m.value)
+        res = []
+        for (func, _t, _v), j in zip(aggs, slot):
+            out, nn = kernel[j][3][:r], kernel[j][4][:r]
+            if func == "COUNT":
+                res.append((out, torch.ones(r, dtype=torch.bool, device=self.device)))
+                continue
+            valid = nn > 0
+            if func == "AVG":
+                out = out.double() / nn.double()
+            res.append((torch.where(valid, out, torch.zeros_like(out)), valid))
+        return (c[:r], st[:r], en[:r], cnt[:r]) + tuple(res)
+
     # ------------------------------------------------------------- projection
     def take(self, cols, idx, outs=None):
         """Arrow ``take`` of fixed-width device columns by int32 row ids ``idx``

@@ -858,6 +858,47 @@ def _left_join_rows(plan: JoinPlan, lt, rt, a: DeviceSide, b: DeviceSide, n_chro
     return torch.cat([ka, kp]), torch.cat([kb, torch.full_like(kp, -1)])
 
 
+def _check_int_sum(column: str, col) -> None:
+    """SUM / AVG over the integer Arrow column ``col`` accumulate in int64 on the device, where DuckDB sums into a
+    128-bit integer: refuse the column when ``n_rows * max(|min|, |max|)`` could reach 2^63 instead of wrapping."""
+    import pyarrow.compute as pc
+
+    mm = pc.min_max(col)
+    lo, hi = mm["min"].as_py(), mm["max"].as_py()
+    if lo is None:
+        return
+    if len(col) * max(abs(lo), abs(hi)) >= 2**63:
+        raise ValueError(f"SUM / AVG over column {column!r}: {len(col)} rows of magnitude up to {max(abs(lo), abs(hi))} "
+                         "can overflow the int64 sum; cast the column to a float type")
+
+
+def _merge_aggregate_inputs(plan: JoinPlan, tbl, keep, eng: HipEngine):
+    """The value columns of a MERGE plan's aggregates on the device, ``[(func, values, valid)]`` in the plan's order,
+    and each column's Arrow type.  Columns go up once (``_Residuals._numeric``: types and validity bytes); when the
+    WHERE kept a subset they are taken by ``keep`` there, so the merge's row ids and the values stay aligned."""
+    import pyarrow as pa
+
+    res = _Residuals(plan, tbl, None, eng)
+    inputs, types, taken = [], [], {}
+    for ag in plan.aggregates:
+        col = res._arrow("l", ag.column)
+        t = col.type
+        if not (pa.types.is_integer(t) or pa.types.is_floating(t)):
+            raise ValueError(f"{ag.func}({ag.column}): column {ag.column!r} has type {t}; MERGE aggregates take "
+                             "integer and floating-point columns")
+        if ag.func in ("SUM", "AVG") and pa.types.is_integer(t):
+            _check_int_sum(ag.column, col)
+        if ag.column not in taken:
+            vals, valid = res._numeric("l", ag.column)
+            if keep is not None:
+                vals = vals[keep.long()].contiguous()
+                valid = None if valid is None else valid[keep.long()].contiguous()
+            taken[ag.column] = (vals, valid)
+        inputs.append((ag.func,) + taken[ag.column])
+        types.append(t)
+    return inputs, types
+
+
 def _execute_cluster_merge(plan: JoinPlan, tables, eng: HipEngine, return_indices: bool):
     """CLUSTER / MERGE over one table (src/giql/expanders/cluster.py:81-300,
     src/giql/expanders/merge.py:62-330): partition ids = dictionary-encoded chrom
@@ -870,6 +911,8 @@ def _execute_cluster_merge(plan: JoinPlan, tables, eng: HipEngine, return_indice
     if side.table not in tables:
         raise ValueError(f"table {side.table!r} was not provided")
     tbl = tables[side.table]
+    if plan.aggregates and return_indices:
+        raise ValueError("return_indices=True has no place for a MERGE plan's aggregates; ask for the table")
     def sorted_codes(name: str):
         """(sorted dictionary as a numpy array, codes): Arrow's hash for string columns, numpy.unique otherwise."""
         what = f"{side.table}.{name}"
@@ -930,7 +973,14 @@ def _execute_cluster_merge(plan: JoinPlan, tables, eng: HipEngine, return_indice
         arrays = [c if isinstance(c, (pa.Array, pa.ChunkedArray)) else pa.array(c) for c in cols]
         return pa.Table.from_arrays(arrays, names=names)
 
-    c, s, e, cnt = (t.cpu().numpy() for t in eng.merge(dev_side, n_part, plan.distance, preds=preds))
+    agg_out = ()
+    if plan.aggregates:
+        agg_in, agg_types = _merge_aggregate_inputs(plan, tbl, keep, eng)
+        merged = eng.merge_agg(dev_side, n_part, plan.distance, agg_in, preds=preds)
+        agg_out = merged[4:]
+    else:
+        merged = eng.merge(dev_side, n_part, plan.distance, preds=preds)
+    c, s, e, cnt = (t.cpu().numpy() for t in merged[:4])
     def named(dictionary, codes):
         """The dictionary's values at ``codes`` as an Arrow column (a take on the Arrow side: a Python list of
         millions of strings took longer than the merge)."""
@@ -946,6 +996,12 @@ def _execute_cluster_merge(plan: JoinPlan, tables, eng: HipEngine, return_indice
     for p in plan.projection:
         if p.side == "count":
             cols[p.name] = pa.array(cnt, type=pa.int64())
+        elif p.side == "agg":
+            ag, (vals, valid) = plan.aggregates[int(p.column)], agg_out[int(p.column)]
+            arr = pa.array(vals.cpu().numpy(), mask=~valid.cpu().numpy())
+            if ag.func in ("MIN", "MAX"):  # the column's own type (the device holds int64 / float64: exact)
+                arr = arr.cast(agg_types[int(p.column)])
+            cols[p.name] = arr
     out = pa.table(cols)
     if plan.stranded and out.num_rows:  # kernel order is (chrom, strand, start); SQL: ORDER BY chrom, start
         out = out.sort_by([(side.chrom_col, "ascending"), (side.start_col, "ascending")])
@@ -1712,9 +1768,9 @@ def _execute_sharded(plan: JoinPlan, lt, rt, ia, ib, n_chrom, devices, return_in
 
 def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, return_indices=False,
             device_projection: bool = True, devices=None, outer_joins: bool = False, row_predicates: bool = False,
-            select_expressions: bool = False):
+            select_expressions: bool = False, merge_aggregates: bool = False):
     """Run *plan* (a :class:`JoinPlan`, its string form, or a GIQL query string; ``outer_joins``,
-    ``row_predicates`` and ``select_expressions`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
+    ``row_predicates``, ``select_expressions`` and ``merge_aggregates`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
     (``{name: pyarrow.Table | dict of arrays}``).
 
     Returns a ``pyarrow.Table`` with the plan's projected columns (bag semantics,
@@ -1736,7 +1792,7 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
     if isinstance(plan, str):
         plan = JoinPlan.from_string(plan) if is_plan_string(plan) else build_plan(
             plan, giql_tables, outer_joins=outer_joins, row_predicates=row_predicates,
-            select_expressions=select_expressions)
+            select_expressions=select_expressions, merge_aggregates=merge_aggregates)
     if not isinstance(plan, JoinPlan):
         raise ValueError("plan must be a JoinPlan, a plan string or a GIQL query")
     devices = [int(d) for d in devices] if devices is not None else None

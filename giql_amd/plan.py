@@ -55,7 +55,8 @@ class Projection:
                    # "expr" (INNER / LEFT: a computed column, column = the index into JoinPlan.expressions as text);
                    # "l" / "r" with column "*" (beside a computed column only): every column of that table, by name;
                    # CLUSTER / MERGE:
-                   # "star" (every table column), "cluster" (the id), "count" (COUNT(*)); DISJOIN: "l" (a
+                   # "star" (every table column), "cluster" (the id), "count" (COUNT(*)), "agg" (MERGE: an
+                   # aggregate of a value column, column = the index into JoinPlan.aggregates as text); DISJOIN: "l" (a
                    # target column), "disjoin" (column = one of DISJOIN_COLUMNS), "star" (the target's
                    # columns, then the three)
     column: str
@@ -131,6 +132,8 @@ class JoinPlan:
     cluster_predicate: tuple[Residual, ...] = field(default_factory=tuple)
     # the clauses that ride on the reference's outer SELECT wrapper (intersects_duckdb.py:1336-1400),
     # finished on the projected table: projection columns named "__giql_*" are carried for them only
+    # (a MERGE plan lowered with the ``merge_aggregates`` opt-in: the aggregates of value columns per merged region,
+    # side "l", computed by HipEngine.merge_agg; a Projection("agg", "<index>", name) places each in the SELECT list)
     aggregates: tuple[Aggregate, ...] = field(default_factory=tuple)
     group_by: tuple[str, ...] = field(default_factory=tuple)       # output names of the key columns
     having: tuple[Having, ...] = field(default_factory=tuple)      # conjuncts over the grouped result
@@ -171,6 +174,9 @@ class JoinPlan:
         if self.expressions and self.kind not in PAIR_KINDS:
             raise ValueError(f"computed columns need an INNER or LEFT plan, not {self.kind}")
         for p in self.projection:
+            if p.side == "agg" and not (self.kind == "MERGE" and p.column.isdigit()
+                                        and int(p.column) < len(self.aggregates)):
+                raise ValueError(f"projection {p.name!r} names aggregate {p.column!r} of {len(self.aggregates)}")
             if p.side == "expr" and not (p.column.isdigit() and int(p.column) < len(self.expressions)):
                 raise ValueError(f"projection {p.name!r} names expression {p.column!r} of {len(self.expressions)}")
 

@@ -36,7 +36,7 @@ from __future__ import annotations
 import re
 from dataclasses import dataclass
 
-from .plan import JoinPlan, Operand, PlanSide, Projection, Residual
+from .plan import Aggregate, JoinPlan, Operand, PlanSide, Projection, Residual
 from .shape import AGG_FUNCS, ColRef as _ColRef, HipDeclined, JoinShape, OrderKey, SelItem, TableRef as _TableRef
 from .shape import bind_expression as _bind_expression
 from .shape import condition_terms as _condition_terms
@@ -988,12 +988,19 @@ def _parse_cluster_call(p: _Parser):
     return this, distance, stranded, predicate
 
 
-def _lower_cluster(p: _Parser, tbls: Tables) -> JoinPlan:
+#: the aggregates ``merge_aggregates`` lowers beside MERGE (merge.py:317-390 keeps any plain aggregate there)
+MERGE_AGG_FUNCS = ("COUNT", "SUM", "AVG", "MIN", "MAX")
+MERGE_AGG_MAX = 8
+
+
+def _lower_cluster(p: _Parser, tbls: Tables, merge_aggregates: bool = False) -> JoinPlan:
     """``SELECT <cols | *>, CLUSTER(interval[, d][, stranded := b]) AS id FROM t [WHERE ...]`` and
     ``SELECT MERGE(interval[, d][, stranded := b]) [, COUNT(*) AS n] FROM t [WHERE ...]``
     (src/giql/expanders/cluster.py:81-205, src/giql/expanders/merge.py:62-183).  A WHERE
     of simple comparisons filters the rows before clustering, as in the reference, where
-    it lands inside the inner ``__giql_lag_calc`` subquery (cluster.py:404-420)."""
+    it lands inside the inner ``__giql_lag_calc`` subquery (cluster.py:404-420).
+    ``merge_aggregates``: ``COUNT(col)``, ``SUM(col)``, ``AVG(col)``, ``MIN(col)``, ``MAX(col)`` over a column of the
+    table, each with an alias, lower beside MERGE too (merge.py:317-390) instead of declining."""
     p.expect_kw("SELECT")
     if p.at_kw("DISTINCT"):
         raise _decline("DISTINCT with CLUSTER / MERGE")
@@ -1008,11 +1015,21 @@ def _lower_cluster(p: _Parser, tbls: Tables) -> JoinPlan:
                 and p.peek(1).text == "(":
             p.next()
             p.next()
-            if not p.at_punct("*"):
+            if p.at_punct("*"):
+                p.next()
+                p.expect_punct(")")
+                items.append(("COUNT", None))
+            elif not merge_aggregates:
                 raise _decline("aggregate other than COUNT(*) beside MERGE")
+            else:
+                items.append(("AGG", ("COUNT", _parse_merge_agg_arg(p, "COUNT"))))
+        elif merge_aggregates and t.kind == "id" and not t.quoted and p.peek(1).kind == "punct" \
+                and p.peek(1).text == "(" and t.text.upper() in MERGE_AGG_FUNCS + ("STRING_AGG",):
+            func = p.next().text.upper()
             p.next()
-            p.expect_punct(")")
-            items.append(("COUNT", None))
+            if func == "STRING_AGG":
+                raise _decline("STRING_AGG beside MERGE (-o collapse)")
+            items.append(("AGG", (func, _parse_merge_agg_arg(p, func))))
         elif t.kind in ("num", "str") or p.at_punct("("):
             raise _decline("expression in the SELECT list")
         else:
@@ -1067,7 +1084,7 @@ def _lower_cluster(p: _Parser, tbls: Tables) -> JoinPlan:
             raise ValueError(f"Unknown table qualifier {refc.table!r}; expected {side.alias!r}")
         return refc.column
 
-    proj = []
+    proj, aggregates = [], []
     if op == "CLUSTER":
         if not op_alias:
             raise _decline("CLUSTER without an alias")
@@ -1077,7 +1094,7 @@ def _lower_cluster(p: _Parser, tbls: Tables) -> JoinPlan:
         for kind, payload, alias in items:
             if kind == "CLUSTER":
                 proj.append(Projection("cluster", "", op_alias))
-            elif kind == "COUNT":
+            elif kind in ("COUNT", "AGG"):
                 raise _decline("aggregate beside CLUSTER")
             elif payload.star:
                 own(payload) if payload.table else None
@@ -1092,6 +1109,14 @@ def _lower_cluster(p: _Parser, tbls: Tables) -> JoinPlan:
                 if not alias:
                     raise _decline("COUNT(*) without an alias beside MERGE")
                 proj.append(Projection("count", "*", alias))
+            elif kind == "AGG":
+                func, refc = payload
+                if not alias:
+                    raise _decline(f"{func}({refc.column}) without an alias beside MERGE")
+                if len(aggregates) == MERGE_AGG_MAX:
+                    raise _decline(f"more than {MERGE_AGG_MAX} aggregates beside MERGE")
+                proj.append(Projection("agg", str(len(aggregates)), alias))
+                aggregates.append(Aggregate(func, "l", own(refc), alias))
             elif payload.star:
                 raise ValueError("MERGE cannot be combined with a star projection (e.g. SELECT *, MERGE(...))")  # merge.py:96-133
             else:
@@ -1120,7 +1145,22 @@ def _lower_cluster(p: _Parser, tbls: Tables) -> JoinPlan:
             cluster_pred.append(Residual("predicate", pbind(lhs), cmp_op, pbind(rhs), g))
     return JoinPlan(op, side, None, tuple(proj), residuals=tuple(residuals), distance=distance,
                     stranded=stranded, strand_col=table.strand_col if stranded else None,
-                    cluster_predicate=tuple(cluster_pred))
+                    cluster_predicate=tuple(cluster_pred), aggregates=tuple(aggregates))
+
+
+def _parse_merge_agg_arg(p: _Parser, func: str) -> _ColRef:
+    """The argument of an aggregate beside MERGE, after its ``(``, through the ``)``: one column of the table."""
+    if p.at_kw("DISTINCT"):
+        raise _decline(f"DISTINCT inside {func}() beside MERGE")
+    if p.at_punct("*"):
+        raise ValueError(f"{func}(*) is not an aggregate; only COUNT takes *")
+    if p.peek().kind != "id":
+        raise _decline(f"expression argument of {func}() beside MERGE")
+    ref = p.colref()
+    if ref.star or not p.at_punct(")"):
+        raise _decline(f"expression argument of {func}() beside MERGE")
+    p.expect_punct(")")
+    return ref
 
 
 def _disjoin_from(p: _Parser) -> int | None:
@@ -1227,7 +1267,7 @@ def _lower_disjoin(p: _Parser, tbls: Tables) -> JoinPlan:
 
 
 def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predicates: bool = False,
-               select_expressions: bool = False) -> JoinPlan:
+               select_expressions: bool = False, merge_aggregates: bool = False) -> JoinPlan:
     """Parse *giql* and lower the INTERSECTS / NEAREST join (or a CLUSTER / MERGE
     query) to a :class:`JoinPlan`.
 
@@ -1237,7 +1277,9 @@ def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predica
     ``DISTANCE(...) <= N``: they lower to SEMI / ANTI / COUNT plans carrying that predicate instead of declining.
     ``select_expressions=True`` opts in to computed columns in the SELECT list of an INNER or LEFT join -- arithmetic
     over columns and literals, LEAST / GREATEST / ABS, a searched CASE, each with an alias (bedtools -wo / -wao:
-    ``LEAST(a.end, b.end) - GREATEST(a.start, b.start) AS overlap_bp``) -- instead of declining them."""
+    ``LEAST(a.end, b.end) - GREATEST(a.start, b.start) AS overlap_bp``) -- instead of declining them.
+    ``merge_aggregates=True`` opts in to ``COUNT(col)`` / ``SUM`` / ``AVG`` / ``MIN`` / ``MAX`` of a table column
+    beside MERGE, each with an alias (bedtools ``merge -c 5 -o mean``: ``MERGE(interval), AVG(score) AS avg_score``)."""
     probe = _Parser(giql)
     tbls = tables if isinstance(tables, Tables) else build_tables(tables)
     for routed, lower, what in ((_disjoin_from(probe) is not None, _lower_disjoin, "DISJOIN"),
@@ -1247,6 +1289,8 @@ def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predica
         if not routed:
             continue
         try:
+            if lower is _lower_cluster:
+                return lower(probe, tbls, merge_aggregates=bool(merge_aggregates))
             return lower(probe, tbls)
         except HipDeclined as exc:
             # these operators compute no column: with the opt-in the decline names the operator
@@ -1450,19 +1494,21 @@ def _render(toks: list[Tok]) -> str:
 
 
 def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins: bool = False,
-              row_predicates: bool = False, select_expressions: bool = False) -> str:
+              row_predicates: bool = False, select_expressions: bool = False,
+              merge_aggregates: bool = False) -> str:
     """Mirror of ``giql.transpile`` for this backend's path.
 
     ``dialect="hip"``: returns the plan string of the INTERSECTS / NEAREST join
     (hand it to :func:`giql_amd.execute`); ``outer_joins=True`` lets a LEFT [OUTER] JOIN lower too
     and ``row_predicates=True`` the per-row joins over CONTAINS / WITHIN / DISTANCE, ``select_expressions=True``
-    computed columns such as ``overlap_bp`` in the SELECT list (:func:`build_plan`).  ``dialect=None``: returns SQL for the
+    computed columns such as ``overlap_bp`` in the SELECT list, ``merge_aggregates=True`` SUM / AVG / MIN / MAX /
+    COUNT(col) beside MERGE (:func:`build_plan`).  ``dialect=None``: returns SQL for the
     literal-range predicate (plumbing, BASELINE config 1).  Other dialects belong to
     the reference package.
     """
     if dialect == "hip":
         return build_plan(giql, tables, outer_joins=outer_joins, row_predicates=row_predicates,
-                          select_expressions=select_expressions).to_string()
+                          select_expressions=select_expressions, merge_aggregates=merge_aggregates).to_string()
     if dialect is None:
         return _lower(giql, tables, want_sql=True)
     raise ValueError(

@@ -94,11 +94,30 @@ def disjoin(parts, device):
             _cat([p[2] for _rt, _rr, p in parts], torch.int32, device)[order])
 
 
-def merge(parts, device):
-    """MERGE, result ``(chrom, start, end, count)`` of the group's regions: all regions ordered by (chrom, start)."""
+def _merge_columns(parts, device):
+    """The groups' ``(chrom, start, end, count)`` one after the other, and the permutation that orders the regions by
+    (chrom, start)."""
     import torch
 
     c, st, en = (_cat([p[k] for _rows, _rb, p in parts], torch.int32, device) for k in range(3))
     cnt = _cat([p[3] for _rows, _rb, p in parts], torch.int64, device)
-    order = torch.argsort(c.long() * (1 << 32) + (st.long() + (1 << 31)), stable=True)
-    return c[order], st[order], en[order], cnt[order]
+    return (c, st, en, cnt), torch.argsort(c.long() * (1 << 32) + (st.long() + (1 << 31)), stable=True)
+
+
+def merge(parts, device):
+    """MERGE, result ``(chrom, start, end, count)`` of the group's regions: all regions ordered by (chrom, start)."""
+    cols, order = _merge_columns(parts, device)
+    return tuple(t[order] for t in cols)
+
+
+def merge_agg(parts, device, dtypes):
+    """MERGE with aggregates, result ``(chrom, start, end, count, (values, valid), ...)``: a region never spans two
+    groups, so the groups' regions are concatenated and every column takes :func:`merge`'s order.  ``dtypes``: the
+    value dtype per aggregate (what no group at all returns)."""
+    import torch
+
+    cols, order = _merge_columns(parts, device)
+    aggs = tuple((_cat([p[4 + j][0] for _rows, _rb, p in parts], dt, device)[order],
+                  _cat([p[4 + j][1] for _rows, _rb, p in parts], torch.bool, device)[order])
+                 for j, dt in enumerate(dtypes))
+    return tuple(t[order] for t in cols) + aggs

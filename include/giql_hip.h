@@ -361,6 +361,30 @@ int giql_hip_merge_pred_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chr
                             int32_t* out_chrom, int32_t* out_start, int32_t* out_end,
                             int64_t* out_count, int64_t capacity, int64_t* n_out, void* stream);
 
+/* MERGE with aggregates (merge.py:317-390 keeps any plain aggregate beside MERGE under the per-cluster GROUP BY):
+ * giql_hip_merge_pred_dev (n_preds = 0: plain MERGE) plus, per merged region, up to 8 aggregates of value columns
+ * addressed by row id.  One segmented reduction over the sorted order serves them all; aggregates that read the same
+ * (data, valid, type) share one gather.  Integer columns accumulate as int64 (no overflow check: the caller bounds
+ * n x max|value|), float columns are widened to binary64 on load.  No atomics: a float SUM is bitwise the same on
+ * every run over the same input.  NaN is greater than every number: MAX of a region with a NaN is NaN, MIN skips NaNs
+ * unless every non-NULL value is one, SUM propagates.  GIQL_ERR_INVALID names the aggregate, before anything is
+ * launched: n_aggs outside 1..8, a NULL data / out, an unknown func / type. */
+enum { GIQL_AGG_COUNT = 0 /* non-NULL inputs */, GIQL_AGG_SUM = 1, GIQL_AGG_MIN = 2, GIQL_AGG_MAX = 3 };
+typedef struct giql_agg {
+  int32_t func, type;      /* GIQL_AGG_*, GIQL_T_I32 / I64 / F32 / F64 of data          */
+  const void* data;        /* device column, s->n rows, addressed by row id             */
+  const uint8_t* valid;    /* device byte-per-row validity, NULL = all valid            */
+  void* out;               /* device, capacity x 8 bytes: int64 (COUNT; SUM/MIN/MAX of  */
+                           /* an integer column) or binary64 (SUM/MIN/MAX of a float)   */
+  int64_t* out_nn;         /* device, capacity: non-NULL inputs of the region; a region */
+                           /* with 0 has a NULL result (out = 0).  May be NULL for COUNT */
+} giql_agg;
+int giql_hip_merge_agg_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom, int64_t distance,
+                           const struct giql_pred* preds, int32_t n_preds, /* 0: plain MERGE */
+                           const giql_agg* aggs, int32_t n_aggs,           /* host array, 1..8 */
+                           int32_t* out_chrom, int32_t* out_start, int32_t* out_end, int64_t* out_count,
+                           int64_t capacity, int64_t* n_out, void* stream);
+
 /* ---- the aggregate half of count_overlaps --------------------------------
  * GROUP BY the left interval + SUM of the per-row counts
  * (src/giql/expanders/intersects_duckdb.py:806-854; a key held by k duplicate left
