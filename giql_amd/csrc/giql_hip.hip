@@ -6,15 +6,9 @@
 // HIP device every entry point fails with GIQL_ERR_HIP.
 #include <hip/hip_runtime.h>
 #include <chrono>
-#include <atomic>
 #include <initializer_list>
 #include <memory>
-#include <sys/mman.h>
 #include <utility>
-#if defined(__SSE2__)
-#include <emmintrin.h>
-#endif
-#include <mutex>
 #include <thread>
 #include <stdarg.h>
 #include <stdio.h>
@@ -44,6 +38,8 @@
 #include "probe_kernels.hip.h"
 #include "index_rows_kernels.hip.h"
 #include "index_nearest_kernels.hip.h"
+#include "host_pool.h"
+#include "plan_expand.h"
 
 using namespace giql;
 
@@ -5279,116 +5275,30 @@ static int upload_side(const giql_side* h, DevSide& d) {
   return GIQL_OK;
 }
 
-// Pinned host memory for library-owned outputs (released by giql_hip_free_host).  Page-locking is the
-// expensive part of the PCIe-inclusive calls -- 3.2 GB of pairs: 203 ms to pin, 57 ms to copy
-// (GIQL_HIP_DEBUG_E2E=1) -- so released buffers are kept for the next call: a small process-wide pool,
-// best fit, at most GIQL_HIP_HOST_POOL_MB (default 8192; 0 = none) of idle memory.
-struct HostPool {
-  struct Buf {
-    void* p;
-    size_t bytes;
-    bool idle;
-    bool pinned;  // page-locked (hipHostMalloc) or plain memory (the compact-plan path's outputs: written by host threads)
-  };
-  static void release(void* p, bool pinned) {
-    if (pinned)
-      (void)hipHostFree(p);
-    else
-      free(p);
-  }
-  std::mutex mu;
-  std::vector<Buf> bufs;
-  size_t idle_limit;
-  HostPool() {
-    const char* e = getenv("GIQL_HIP_HOST_POOL_MB");
-    idle_limit = (size_t)(e ? strtoull(e, nullptr, 10) : 8192ull) << 20;
-  }
-  void* get(size_t bytes, bool pinned = true) {
-    {
-      std::lock_guard<std::mutex> g(mu);
-      Buf* best = nullptr;
-      for (auto& b : bufs)  // (a page-locked buffer serves a plain request as well)
-        if (b.idle && b.bytes >= bytes && (b.pinned || !pinned) && (!best || b.bytes < best->bytes)) best = &b;
-      if (best && best->bytes <= 2 * bytes + (1u << 20)) {  // not a 3 GB buffer for a 4-byte result
-        best->idle = false;
-        return best->p;
-      }
-    }
-    void* p = nullptr;
-    size_t cap = bytes + bytes / 16;  // a little head-room: the next result of a similar call fits too
-    if (pinned) {
-      if (hipHostMalloc(&p, cap, hipHostMallocDefault) != hipSuccess) return nullptr;
-    } else {
-      // plain memory on 2 MiB boundaries, huge pages asked for: the expansion threads touch it for the first time
-      // (4 KB pages: ~800,000 faults for 3.2 GB of pairs)
-      cap = align_up(cap, (size_t)2 << 20);
-      p = aligned_alloc((size_t)2 << 20, cap);
-      if (!p) return nullptr;
-#if defined(MADV_HUGEPAGE)
-      (void)madvise(p, cap, MADV_HUGEPAGE);
-#endif
-    }
-    std::lock_guard<std::mutex> g(mu);
-    bufs.push_back({p, cap, false, pinned});
-    return p;
-  }
-  void put(void* p) {
-    std::vector<std::pair<void*, bool>> drop;
-    {
-      std::lock_guard<std::mutex> g(mu);
-      bool known = false;
-      for (auto& b : bufs)
-        if (b.p == p) {
-          b.idle = true;
-          known = true;
-        }
-      if (!known) drop.push_back({p, true});
-      // over the limit: release the smallest idle buffers first (the big ones are the ones worth keeping)
-      size_t idle = 0;
-      for (auto& b : bufs)
-        if (b.idle) idle += b.bytes;
-      while (idle > idle_limit) {
-        size_t k = bufs.size();
-        for (size_t i = 0; i < bufs.size(); i++)
-          if (bufs[i].idle && (k == bufs.size() || bufs[i].bytes < bufs[k].bytes)) k = i;
-        if (k == bufs.size()) break;
-        idle -= bufs[k].bytes;
-        drop.push_back({bufs[k].p, bufs[k].pinned});
-        bufs.erase(bufs.begin() + (long)k);
-      }
-    }
-    for (auto& d : drop) release(d.first, d.second);
-  }
-};
+// the per-row host calls (SEMI / ANTI, COUNT, NEAREST), once their arguments are checked: both sides onto the context's device
+static int upload_sides(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, DevSide& da, DevSide& db) {
+  HIP_TRY(hipSetDevice(ctx->device));
+  GIQL_TRY(upload_side(a, da));
+  return upload_side(b, db);
+}
+
+// library-owned host outputs (released by giql_hip_free_host): one process-wide pool (host_pool.h), at most GIQL_HIP_HOST_POOL_MB (default 8192; 0 = none) idle
+static void* pinned_alloc(size_t bytes) {
+  void* p = nullptr;
+  return hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+}
+static void pinned_free(void* p) { (void)hipHostFree(p); }
 static HostPool& host_pool() {
-  static HostPool* pool = new HostPool();  // never destroyed: no HIP calls at process exit
+  static const char* e = getenv("GIQL_HIP_HOST_POOL_MB");
+  // never destroyed: no HIP calls at process exit
+  static HostPool* pool = new HostPool((size_t)(e ? strtoull(e, nullptr, 10) : 8192ull) << 20, pinned_alloc, pinned_free);
   return *pool;
 }
-static void* host_alloc(size_t bytes) { return host_pool().get(bytes ? bytes : 1); }
-static void* host_alloc_plain(size_t bytes) { return host_pool().get(bytes ? bytes : 1, false); }
+static void* host_alloc(size_t bytes, bool pinned = true) { return host_pool().get(bytes, pinned); }
 
 int giql_hip_host_pool_trim(int64_t keep_bytes, int64_t* released) {
   if (keep_bytes < 0) return set_err(GIQL_ERR_INVALID, "keep_bytes < 0");
-  HostPool& hp = host_pool();
-  std::vector<std::pair<void*, bool>> drop;
-  size_t freed = 0;
-  {
-    std::lock_guard<std::mutex> g(hp.mu);
-    size_t idle = 0;
-    for (auto& b : hp.bufs)
-      if (b.idle) idle += b.bytes;
-    while (idle > (size_t)keep_bytes) {  // the largest first: they are what a trim is called for
-      size_t k = hp.bufs.size();
-      for (size_t i = 0; i < hp.bufs.size(); i++)
-        if (hp.bufs[i].idle && (k == hp.bufs.size() || hp.bufs[i].bytes > hp.bufs[k].bytes)) k = i;
-      if (k == hp.bufs.size()) break;
-      idle -= hp.bufs[k].bytes;
-      freed += hp.bufs[k].bytes;
-      drop.push_back({hp.bufs[k].p, hp.bufs[k].pinned});
-      hp.bufs.erase(hp.bufs.begin() + (long)k);
-    }
-  }
-  for (auto& d : drop) HostPool::release(d.first, d.second);
+  const size_t freed = host_pool().release_idle((size_t)keep_bytes, true);  // the largest first: they are what a trim is called for
   if (released) *released = (int64_t)freed;
   return GIQL_OK;
 }
@@ -5523,21 +5433,18 @@ static int inner_host_pipelined(giql_hip_ctx* ctx, const giql_side* a, const giq
 // sizes (9 ms), and host threads expand it at the host's memory rate (tools/probes/host_expand_probe.cpp: 150 GB/s
 // of pairs with 16 threads on the GPU box = 21 ms for 3.2 GB).  So: columns up, plan, export, the three per-query
 // arrays down, then the sorted ids in chunks while the threads already expand the queries whose ranges have arrived
-// (blocks of 65,536 queries handed out in order; a block waits for the chunk that holds its last id).  The pairs
+// (plan_expand.h: blocks of 65,536 queries handed out in order; a block waits for the chunk that holds its furthest id).  The pairs
 // come out in the plan's query order.  Only the single-range form (fixed-length side, no irregular rows) has a compact
 // plan: any other plan is filled and downloaded as before.  GIQL_HIP_E2E_THREADS: expansion threads (default 32: tools/e2e_threads.py -- 16: 45.8 ms, 32: 39.9, 64: 40.0 at the headline sizes).
-struct CompactHost {  // page-locked staging of the plan, back to the pool on every path out
-  HostPtr<int32_t> q_rid;
-  HostPtr<u32> lo, cnt;
-  HostPtr<int32_t> s_rid;
-};
+static bool plan_has_compact_form(const giql_hip_ctx* ctx) {
+  return ctx->plan.inner.uniform != 0 && ctx->plan.n_irr == 0 && ctx->plan.n_c1 == 0 && !ctx->plan.plan_is_join;
+}
 
 // returns GIQL_OK with *done = false when the plan has no compact form (the caller fills and downloads)
 static int inner_host_compact_tail(giql_hip_ctx* ctx, int64_t n, int32_t* ha, int32_t* hb, bool* done) {
   *done = false;
-  InnerState& S = ctx->plan.inner;
-  if (n <= 0 || S.uniform == 0 || ctx->plan.n_irr != 0 || ctx->plan.n_c1 != 0 || ctx->plan.plan_is_join) return GIQL_OK;
-  const bool q_is_a_plan = S.uniform != 2;
+  if (n <= 0 || !plan_has_compact_form(ctx)) return GIQL_OK;
+  const bool q_is_a_plan = ctx->plan.inner.uniform != 2;
   const size_t nq = (size_t)(q_is_a_plan ? ctx->plan.n_a : ctx->plan.n_b), ns = (size_t)(q_is_a_plan ? ctx->plan.n_b : ctx->plan.n_a);
   if (nq == 0 || ns == 0) return GIQL_OK;
   // device staging: the context's output staging buffer (3 nq + ns words)
@@ -5554,12 +5461,14 @@ static int inner_host_compact_tail(giql_hip_ctx* ctx, int64_t n, int32_t* ha, in
   if (rc_x == GIQL_ERR_STATE) return GIQL_OK;
   GIQL_TRY(rc_x);
   if ((size_t)xq != nq || (size_t)xs != ns) return set_err(GIQL_ERR_STATE, "plan export sizes changed under the call");
-  CompactHost H{HostPtr<int32_t>(host_alloc(nq * 4)), HostPtr<u32>(host_alloc(nq * 4)), HostPtr<u32>(host_alloc(nq * 4)),
-                HostPtr<int32_t>(host_alloc(ns * 4))};
-  if (!H.q_rid || !H.lo || !H.cnt || !H.s_rid) return set_err(GIQL_ERR_NOMEM, "out of host memory for the compact plan");
+  // page-locked staging of the plan, back to the pool on every path out
+  HostPtr<int32_t> h_qrid(host_alloc(nq * 4));
+  HostPtr<u32> h_lo(host_alloc(nq * 4)), h_cnt(host_alloc(nq * 4));
+  HostPtr<int32_t> h_srid(host_alloc(ns * 4));
+  if (!h_qrid || !h_lo || !h_cnt || !h_srid) return set_err(GIQL_ERR_NOMEM, "out of host memory for the compact plan");
   constexpr size_t CHUNK = (size_t)16 << 20;   // sorted ids per download chunk (64 MB: ~1.1 ms on the link)
   constexpr size_t QBLK = (size_t)1 << 16;     // queries per expansion block
-  const size_t n_chunks = (ns + CHUNK - 1) / CHUNK, n_blk = (nq + QBLK - 1) / QBLK;
+  const size_t n_chunks = (ns + CHUNK - 1) / CHUNK;
   std::vector<hipEvent_t> ev(n_chunks + 1, nullptr);
   struct EvGuard {
     std::vector<hipEvent_t>& e;
@@ -5570,13 +5479,13 @@ static int inner_host_compact_tail(giql_hip_ctx* ctx, int64_t n, int32_t* ha, in
   } ev_guard{ev};
   for (auto& e : ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   hipStream_t st = nullptr;  // the export kernel ran on the null stream: the copies follow it there
-  HIP_TRY(hipMemcpyAsync(H.cnt, d_cnt, nq * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(H.lo, d_lo, nq * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(H.q_rid, d_qrid, nq * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, nq * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_lo, d_lo, nq * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_qrid, d_qrid, nq * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipEventRecord(ev[0], st));
   for (size_t c = 0; c < n_chunks; c++) {
     const size_t c0 = c * CHUNK, cn = ns - c0 < CHUNK ? ns - c0 : CHUNK;
-    HIP_TRY(hipMemcpyAsync(H.s_rid + c0, d_srid + c0, cn * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_srid + c0, d_srid + c0, cn * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(ev[c + 1], st));
   }
   HIP_TRY(hipEventSynchronize(ev[0]));  // the per-query arrays are here
@@ -5584,149 +5493,11 @@ static int inner_host_compact_tail(giql_hip_ctx* ctx, int64_t n, int32_t* ha, in
   if (const char* e = getenv("GIQL_HIP_E2E_THREADS")) n_thr = atoi(e);
   const int hw = (int)std::thread::hardware_concurrency();
   if (hw > 0 && n_thr > hw) n_thr = hw;
-  if (n_thr < 1) n_thr = 1;
-  if ((size_t)n_thr > n_blk) n_thr = (int)n_blk;
   bool stream_stores = true;  // GIQL_HIP_E2E_NT=0: plain stores
   if (const char* e = getenv("GIQL_HIP_E2E_NT")) stream_stores = atoi(e) != 0;
-  (void)stream_stores;
-  // block offsets: per-block sums in parallel, a serial scan over the (few hundred) blocks
-  std::vector<u64> blk_off(n_blk + 1, 0);
-  std::vector<u32> blk_need(n_blk, 0);  // one past the last sorted id a block reads
-  std::atomic<size_t> next{0};
-  std::atomic<size_t> chunks_here{0};
-  std::atomic<int> bad{0};
-  const u32* const lo = H.lo;
-  const u32* const cnt = H.cnt;
-  auto sums = [&] {
-    for (;;) {
-      const size_t bk = next.fetch_add(1);
-      if (bk >= n_blk) return;
-      const size_t q0 = bk * QBLK, q1 = q0 + QBLK < nq ? q0 + QBLK : nq;
-      u64 t = 0;
-      u32 need_s = 0;
-      for (size_t q = q0; q < q1; q++) {
-        t += cnt[q];
-        const u64 e = (u64)lo[q] + cnt[q];
-        if (cnt[q] && e > need_s) need_s = e > (u64)ns ? 0xFFFFFFFFu : (u32)e;
-      }
-      blk_off[bk + 1] = t;
-      blk_need[bk] = need_s;
-    }
-  };
-  {
-    std::vector<std::thread> th;
-    try {
-      for (int t = 1; t < n_thr; t++) th.emplace_back(sums);
-    } catch (...) {  // no more threads to be had: the ones that started (and this one) do the work
-    }
-    sums();
-    for (auto& t : th) t.join();
-  }
-  for (size_t bk = 0; bk < n_blk; bk++) {
-    if (blk_need[bk] == 0xFFFFFFFFu) return set_err(GIQL_ERR_STATE, "compact plan: a range past the sorted ids");
-    blk_off[bk + 1] += blk_off[bk];
-  }
-  if (blk_off[n_blk] != (u64)n) return set_err(GIQL_ERR_STATE, "compact plan: %llu pairs, the plan counted %lld",
-                                               (unsigned long long)blk_off[n_blk], (long long)n);
-  int32_t* const out_q = query_is_a ? ha : hb;
-  int32_t* const out_s = query_is_a ? hb : ha;
-  const int32_t* const q_rid = H.q_rid;
-  const int32_t* const s_rid = H.s_rid;
-  next.store(0);
-  auto expand = [&] {
-    for (;;) {
-      const size_t bk = next.fetch_add(1);
-      if (bk >= n_blk) return;
-      const size_t want = ((size_t)blk_need[bk] + CHUNK - 1) / CHUNK;  // chunks that must have arrived
-      while (chunks_here.load(std::memory_order_acquire) < want) {
-        if (bad.load()) return;
-        std::this_thread::yield();
-      }
-      const size_t q0 = bk * QBLK, q1 = q0 + QBLK < nq ? q0 + QBLK : nq;
-      u64 o = blk_off[bk];
-#if defined(__SSE2__)
-      if (stream_stores) {
-        // The pairs are staged in two 4 KB buffers (L1) and leave in aligned 16-byte NON-TEMPORAL stores: a plain store
-        // makes the core read every output line before writing it, i.e. 6.4 GB of memory traffic for 3.2 GB of pairs.
-        // Both arrays come page-aligned from the pool and share the offset, so one alignment serves both.
-        constexpr u32 BUF = 1024;
-        alignas(64) int32_t bq[BUF], bs[BUF];
-        const u64 o_end = blk_off[bk + 1];
-        size_t q = q0;
-        u32 k = 0;  // next pair of query q
-        auto next_pair = [&](int32_t& vq, int32_t& vs) {  // (the block holds o_end - o more pairs: never runs past q1)
-          while (k >= cnt[q]) {
-            q++;
-            k = 0;
-          }
-          vq = q_rid[q];
-          vs = s_rid[lo[q] + k];
-          k++;
-        };
-        while (o < o_end && (o & 15u)) {  // up to the first 64-byte boundary: plain stores
-          next_pair(out_q[o], out_s[o]);
-          o++;
-        }
-        while (o_end - o >= BUF) {
-          u32 f = 0;
-          while (f < BUF) {  // whole runs of one query at a time
-            while (k >= cnt[q]) {
-              q++;
-              k = 0;
-            }
-            const u32 c = cnt[q] - k < BUF - f ? cnt[q] - k : BUF - f;
-            const int32_t id = q_rid[q];
-            const int32_t* src = s_rid + lo[q] + k;
-            for (u32 j = 0; j < c; j++) {
-              bq[f + j] = id;
-              bs[f + j] = src[j];
-            }
-            f += c;
-            k += c;
-          }
-          for (u32 j = 0; j < BUF; j += 4) {
-            _mm_stream_si128(reinterpret_cast<__m128i*>(out_q + o + j), _mm_load_si128(reinterpret_cast<const __m128i*>(bq + j)));
-            _mm_stream_si128(reinterpret_cast<__m128i*>(out_s + o + j), _mm_load_si128(reinterpret_cast<const __m128i*>(bs + j)));
-          }
-          o += BUF;
-        }
-        while (o < o_end) {
-          next_pair(out_q[o], out_s[o]);
-          o++;
-        }
-        _mm_sfence();
-        continue;
-      }
-#endif
-      for (size_t q = q0; q < q1; q++) {
-        const u32 c = cnt[q];
-        const int32_t id = q_rid[q];
-        const int32_t* src = s_rid + lo[q];
-        for (u32 k = 0; k < c; k++) {
-          out_q[o + k] = id;
-          out_s[o + k] = src[k];
-        }
-        o += c;
-      }
-    }
-  };
-  std::vector<std::thread> th;
-  try {
-    for (int t = 0; t < n_thr; t++) th.emplace_back(expand);
-  } catch (...) {  // (as above; this thread expands too once every chunk has arrived)
-  }
-  int rc = GIQL_OK;
-  for (size_t c = 0; c < n_chunks; c++) {  // this thread follows the link and publishes what has arrived
-    if (hipEventSynchronize(ev[c + 1]) != hipSuccess) {
-      rc = set_err(GIQL_ERR_HIP, "D2H copy of the compact plan failed");
-      bad.store(1);
-      break;
-    }
-    chunks_here.store(c + 1, std::memory_order_release);
-  }
-  if (rc == GIQL_OK) expand();  // whatever blocks are left (all of them when no helper thread could be started)
-  for (auto& t : th) t.join();
-  GIQL_TRY(rc);
+  // (both output arrays come page-aligned from the pool: expand_plan's precondition)
+  GIQL_TRY(expand_plan(CompactPlan{h_qrid, h_lo, h_cnt, h_srid, nq, ns}, (uint64_t)n, query_is_a ? ha : hb, query_is_a ? hb : ha,
+                       n_thr, stream_stores, CHUNK, QBLK, [&](size_t c) { return hipEventSynchronize(ev[c + 1]) != hipSuccess; }, set_err));
   *done = true;
   return GIQL_OK;
 }
@@ -5771,7 +5542,7 @@ int giql_hip_inner(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, in
   *n_pairs = n;
   // The compact plan pays when it is smaller than the pairs (and the result is worth a team of threads)
   bool compact = false;
-  if (try_compact && n > 0 && ctx->plan.inner.uniform != 0 && ctx->plan.n_irr == 0 && ctx->plan.n_c1 == 0 && !ctx->plan.plan_is_join) {
+  if (try_compact && n > 0 && plan_has_compact_form(ctx)) {
     const bool q_is_a_plan = ctx->plan.inner.uniform != 2;
     const int64_t nq = q_is_a_plan ? ctx->plan.n_a : ctx->plan.n_b, ns = q_is_a_plan ? ctx->plan.n_b : ctx->plan.n_a;
     // ... on a host with the cores to expand it: 16 threads write ~150 GB/s of pairs, 4 would lose against the link
@@ -5782,8 +5553,8 @@ int giql_hip_inner(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, in
   // bounce buffer) -- unless host threads write them (compact plan): plain memory then, nothing to page-lock (3.2 GB:
   // ~200 ms on a first call); giql_hip_free_host releases either kind
   const size_t out_bytes = (size_t)(n > 0 ? n : 1) * sizeof(int32_t);
-  HostPtr<int32_t> ha(compact ? host_alloc_plain(out_bytes) : host_alloc(out_bytes));
-  HostPtr<int32_t> hb(compact ? host_alloc_plain(out_bytes) : host_alloc(out_bytes));
+  HostPtr<int32_t> ha(host_alloc(out_bytes, !compact));
+  HostPtr<int32_t> hb(host_alloc(out_bytes, !compact));
   if (!ha || !hb) return set_err(GIQL_ERR_NOMEM, "out of host memory for %lld pairs", (long long)n);
   const double ms_pin = ms_since(t0);
   t0 = now();
@@ -5825,11 +5596,9 @@ int giql_hip_semi_anti(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b
   if (!ctx || !n_out || !rows_a) return set_err(GIQL_ERR_INVALID, "NULL argument");
   GIQL_TRY(check_side(a, "a"));
   GIQL_TRY(check_side(b, "b"));
-  HIP_TRY(hipSetDevice(ctx->device));
   *rows_a = nullptr;
   DevSide da, db;
-  GIQL_TRY(upload_side(a, da));
-  GIQL_TRY(upload_side(b, db));
+  GIQL_TRY(upload_sides(ctx, a, b, da, db));
   DevArray<int32_t> out;
   const size_t na = (size_t)a->n;
   GIQL_TRY(out.alloc((na ? na : 1) * sizeof(int32_t)));
@@ -5851,10 +5620,8 @@ int giql_hip_count(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, in
   GIQL_TRY(check_side(b, "b"));
   if (a->n == 0) return GIQL_OK;
   if (!counts_out) return set_err(GIQL_ERR_INVALID, "counts_out is NULL");
-  HIP_TRY(hipSetDevice(ctx->device));
   DevSide da, db;
-  GIQL_TRY(upload_side(a, da));
-  GIQL_TRY(upload_side(b, db));
+  GIQL_TRY(upload_sides(ctx, a, b, da, db));
   DevArray<int64_t> out;
   GIQL_TRY(out.alloc((size_t)a->n * sizeof(int64_t)));
   GIQL_TRY(giql_hip_count_dev(ctx, &da.s, &db.s, n_chrom, out, nullptr));
@@ -5869,10 +5636,8 @@ int giql_hip_nearest(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, 
   GIQL_TRY(check_side(b, "b"));
   if (a->n == 0) return GIQL_OK;
   if (!idx_b_out || !dist_out) return set_err(GIQL_ERR_INVALID, "output is NULL");
-  HIP_TRY(hipSetDevice(ctx->device));
   DevSide da, db;
-  GIQL_TRY(upload_side(a, da));
-  GIQL_TRY(upload_side(b, db));
+  GIQL_TRY(upload_sides(ctx, a, b, da, db));
   DevArray<int32_t> oi;
   DevArray<int64_t> od;
   GIQL_TRY(oi.alloc((size_t)a->n * sizeof(int32_t)));

@@ -1,5 +1,5 @@
 // giql_amd/csrc/owned_memory.h -- the two owners of the memory giql_hip.hip allocates: a device buffer (hipMalloc /
-// hipFree) and a pointer from the pinned-host pool (host_alloc / giql_hip_free_host).  Both are move-only and release
+// hipFree) and a pointer from the pinned-host pool (host_pool.h, through host_alloc / giql_hip_free_host).  Both are move-only and release
 // what they hold when they go out of scope, so an early return needs no clean-up of its own.  Included by
 // giql_hip.hip after set_err / HIP_TRY, which it reports through.
 #pragma once
@@ -69,7 +69,7 @@ struct DevArray : DevBuf {
   T* operator->() const { return static_cast<T*>(get()); }
 };
 
-// A pointer from the host pool (host_alloc / host_alloc_plain), back to the pool when its owner goes.
+// A pointer from the host pool (host_alloc), back to the pool when its owner goes.
 template <typename T>
 class HostPtr {
  public:
