@@ -202,10 +202,18 @@ struct CallState {
   bool bucket_join = false;
 };
 
-// What inner_plan keeps for inner_fill / export (all inside the arena).  Dropped (planned = false) by every call that
-// claims the arena (claim_arena); written by inner_plan_core.
+// Which plan the context keeps between two calls: at most one, so one tag.  A plan is pointers into the workspace and
+// is only as good as the record of who has touched that workspace since; the record is kept in three places and no
+// operator writes it.  A plan entry point sets its tag as its last step (also on its way out with an empty result);
+// begin_call drops whatever is kept, at the start of every call that resets the call state; claim_arena and
+// ensure_arena drop it where the workspace is carved or replaced without a begin_call (giql_hip_reserve,
+// giql_hip_chrom_spans_dev).  The fill and export entry points only test it.  (giql_hip_inner alone drops it once
+// more, on return: its plans read columns staged for that call.)
+enum class Plan { NONE, INNER, DISJOIN, CONTAINS };
+
+// What inner_plan keeps for inner_fill / export (all inside the arena); written by inner_plan_core and by
+// giql_hip_window_plan_dev.  Live while ctx->kept == Plan::INNER.
 struct InnerPlan {
-  bool planned = false;
   bool plan_is_join = false;  // the pairs left from the bucket stage: no plan arrays (fill / export need a plan of their own)
   bool swapped = false;       // planned with the sides exchanged (giql_hip_inner_plan_dev_impl)
   // one-call join (giql_hip_inner_join_dev): the caller's outputs offered to the plan for a fill launched before the
@@ -225,10 +233,8 @@ struct InnerPlan {
   i64 widen = -1;  // >= 0: a within-distance plan (giql_hip_window_plan_dev); its irregular pairs follow the widened predicate
 };
 
-// What disjoin_plan keeps for disjoin_fill (all inside the arena).  Dropped like the INNER plan by every call that
-// claims the arena.
+// What disjoin_plan keeps for disjoin_fill (all inside the arena).  Live while ctx->kept == Plan::DISJOIN.
 struct DisjoinPlan {
-  bool planned = false;
   giql_side target;
   u64 total = 0;
   i64* chrom_base = nullptr;
@@ -240,10 +246,9 @@ struct DisjoinPlan {
   u32* cbp = nullptr;        // indices of the covered breakpoints
 };
 
-// What contain_plan keeps for contain_fill (the per-row arrays inside the arena, the per-tile ones in ct_buf).  Dropped
-// by every call that claims the arena and by every call that reports stats (begin_call).
+// What contain_plan keeps for contain_fill (the per-row arrays inside the arena, the per-tile ones in ct_buf).  Live
+// while ctx->kept == Plan::CONTAINS.
 struct ContainPlan {
-  bool planned = false;
   giql_side outer, inner;
   u32 n_o = 0, n_i = 0;
   int form = 0;              // 0 general (candidate tiles), 1 uniform inner side (exact range + k_fill)
@@ -269,6 +274,7 @@ struct giql_hip_ctx {
   const Switches sw;
   Guesses guess;
   CallState call;
+  Plan kept = Plan::NONE;     // which of the three below is live
   InnerPlan plan;
   DisjoinPlan dj;
   ContainPlan ct;
@@ -317,9 +323,7 @@ struct Carver {
 
 static int ensure_arena(giql_hip_ctx* ctx, size_t bytes, hipStream_t stream) {
   if (bytes <= ctx->arena.bytes()) return GIQL_OK;
-  ctx->plan.planned = false;  // (giql_hip_reserve: a new arena holds no plan)
-  ctx->dj.planned = false;
-  ctx->ct.planned = false;
+  ctx->kept = Plan::NONE;  // (giql_hip_reserve: a new arena holds no plan)
   const size_t want = align_up(bytes + bytes / 8, (size_t)1 << 20);
   GIQL_TRY(ctx->arena.grow(bytes, want, stream, "the workspace"));
   if (getenv("GIQL_HIP_DEBUG_ADDR")) fprintf(stderr, "[giql_hip] arena %p + %zu bytes\n", ctx->arena.get(), want);
@@ -332,12 +336,11 @@ static int grow_part(giql_hip_ctx* ctx, size_t words, hipStream_t stream) {
 }
 
 // The workspace of a call: `carve` lays its buffers out from a base (nullptr: a dry run that returns the size), once
-// to size the arena and once for real.  The call reuses what an INNER plan keeps there: the plan is dropped.
+// to size the arena and once for real.  The call reuses what a plan keeps there: the plan is dropped, before the dry
+// run (the INNER plan's carve writes the plan's own pointers).
 template <typename Carve>
 static int claim_arena(giql_hip_ctx* ctx, hipStream_t stream, Carve&& carve) {
-  ctx->plan.planned = false;
-  ctx->dj.planned = false;
-  ctx->ct.planned = false;
+  ctx->kept = Plan::NONE;
   GIQL_TRY(ensure_arena(ctx, carve(nullptr), stream));
   carve(ctx->arena);
   return GIQL_OK;
@@ -376,23 +379,35 @@ static void reset_stats(giql_hip_ctx* ctx) {
   ctx->ev_used = 0;
 }
 
-static int begin_call(giql_hip_ctx* ctx) {
+// The start of every call that resets the call state, and the one rule of a plan's lifetime: the plan the context
+// keeps is dropped here, whatever the call goes on to do -- also when it returns at once because a side is empty.
+// (A check that fails before this point leaves the context as it was.)  n_a / n_b: the sizes the call reports.
+static int begin_call(giql_hip_ctx* ctx, int64_t n_a = 0, int64_t n_b = 0, bool keep_join_plan = false) {
   HIP_TRY(hipSetDevice(ctx->device));
-  ctx->ct.planned = false;  // a CONTAINS plan does not outlive the next launching call
+  if (!keep_join_plan || ctx->kept == Plan::CONTAINS) ctx->kept = Plan::NONE;
   reset_stats(ctx);
+  ctx->stats.n_a = n_a;
+  ctx->stats.n_b = n_b;
   return GIQL_OK;
 }
 
-// The prologue of the operators on two sides: the checks, then begin_call and the sides' sizes.
+// begin_call for the five calls that touch no workspace and are made while a plan is still wanted --
+//   giql_hip_distance_dev   the within-distance join fills its plan, then asks for the pairs' distances;
+//   giql_hip_take_dev, giql_hip_take_utf8_fill_dev, giql_hip_mark_dev, giql_hip_segment_sum_dev
+//                           projections and reductions over row ids the caller holds, run between a plan and its fill.
+// They keep an INNER or DISJOIN plan.  A CONTAINS plan goes all the same: its per-tile arrays (ct_buf) and the
+// statistics its fill adds to belong to the call that made it.
+static int begin_call_beside_plan(giql_hip_ctx* ctx, int64_t n_a = 0, int64_t n_b = 0) {
+  return begin_call(ctx, n_a, n_b, true);
+}
+
+// The prologue of the operators on two sides: the checks, then begin_call with the sides' sizes.
 static int check_side(const giql_side* s, const char* name);
 static int begin_pair_call(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, int32_t n_chrom) {
   GIQL_TRY(check_side(a, "a"));
   GIQL_TRY(check_side(b, "b"));
   if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
-  GIQL_TRY(begin_call(ctx));
-  ctx->stats.n_a = a->n;
-  ctx->stats.n_b = b->n;
-  return GIQL_OK;
+  return begin_call(ctx, a->n, b->n);
 }
 
 // the onesweep sort's status words count rows in 30 bits
@@ -2025,7 +2040,7 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
   ctx->plan.widen = -1;
   *n_pairs = 0;
   if (a->n == 0 || b->n == 0 || n_chrom == 0) {  // empty result (tests :4173-4229)
-    ctx->plan.planned = true;
+    ctx->kept = Plan::INNER;
     ctx->plan.plan_is_join = false;
     return GIQL_OK;
   }
@@ -2084,7 +2099,7 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
   ctx->stats.reserved = S.uniform | ((T.keygen_u || T.keygen_g) ? 0x10 : 0);
   ctx->stats.n_out = (int64_t)(ctx->plan.n_reg + ctx->plan.n_irr);
   *n_pairs = (int64_t)(ctx->plan.n_reg + ctx->plan.n_irr);
-  ctx->plan.planned = true;
+  ctx->kept = Plan::INNER;
   ctx->plan.plan_is_join = T.bucket_join();
   return GIQL_OK;
 }
@@ -2125,7 +2140,7 @@ int giql_hip_inner_plan_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_si
 int giql_hip_inner_fill_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, int64_t capacity,
                             void* stream) {
   if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
-  if (!ctx->plan.planned) return set_err(GIQL_ERR_STATE, "inner_fill without a successful inner_plan");
+  if (ctx->kept != Plan::INNER) return set_err(GIQL_ERR_STATE, "inner_fill without a successful inner_plan");
   const u64 total = ctx->plan.n_reg + ctx->plan.n_irr;
   if (total == 0) return GIQL_OK;
   if (ctx->plan.plan_is_join)
@@ -2295,8 +2310,6 @@ static int giql_hip_window_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* a, 
   GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
   hipStream_t st = (hipStream_t)stream;
   InnerPlan& P = ctx->plan;
-  P.planned = false;  // (the ways out before the arena is claimed drop the other plans too)
-  ctx->dj.planned = false;
   P.swapped = false;
   P.plan_is_join = false;
   P.fuse_done = false;
@@ -2309,7 +2322,7 @@ static int giql_hip_window_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* a, 
   P.widen = -1;
   *n_pairs = 0;
   if (a->n == 0 || b->n == 0 || n_chrom == 0) {  // empty result, as the INNER plan's
-    P.planned = true;
+    ctx->kept = Plan::INNER;
     return GIQL_OK;
   }
   const size_t na = (size_t)a->n, nb = (size_t)b->n, nq = na + nb;
@@ -2363,7 +2376,7 @@ static int giql_hip_window_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* a, 
   ctx->stats.n_out = (int64_t)(P.n_reg + P.n_irr);
   *n_pairs = (int64_t)(P.n_reg + P.n_irr);
   P.widen = widen;
-  P.planned = true;
+  ctx->kept = Plan::INNER;
   return GIQL_OK;
 }
 
@@ -2373,7 +2386,7 @@ int giql_hip_window_plan_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_s
       ctx, [&] { return giql_hip_window_plan_dev_impl(ctx, a, b, n_chrom, max_distance, stream, n_pairs); });
 }
 
-// DISTANCE(a[row_a[i]], b[row_b[i]]) per pair (k_pair_distance).  No workspace: an INNER plan on the context stays.
+// DISTANCE(a[row_a[i]], b[row_b[i]]) per pair (k_pair_distance).  No workspace: begin_call_beside_plan.
 int giql_hip_distance_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, const int32_t* row_a,
                           const int32_t* row_b, int64_t n, const int32_t* strand_a, const int32_t* strand_b,
                           int32_t flags, int64_t* dist_out, uint8_t* valid_out, void* stream) {
@@ -2387,10 +2400,8 @@ int giql_hip_distance_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_side
   if ((flags & 2) && ((a->n > 0 && !strand_a) || (b->n > 0 && !strand_b)))
     return set_err(GIQL_ERR_INVALID, "stranded DISTANCE without strand codes");
   if (n == 0) return GIQL_OK;
-  GIQL_TRY(begin_call(ctx));
+  GIQL_TRY(begin_call_beside_plan(ctx, a->n, b->n));
   hipStream_t st = (hipStream_t)stream;
-  ctx->stats.n_a = a->n;
-  ctx->stats.n_b = b->n;
   HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
   u32 grid = cdiv((u64)n, DIST_NT * 4);
   if (grid > GIQL_STREAM_GRID) grid = GIQL_STREAM_GRID;
@@ -2585,12 +2596,9 @@ int giql_hip_inner_join_indexed_dev(giql_hip_ctx* ctx, const giql_hip_index* idx
   if (idx->device != ctx->device) return set_err(GIQL_ERR_INVALID, "the index lives on device %d, the context on %d", idx->device, ctx->device);
   if (capacity < 0 || (capacity > 0 && (!row_a || !row_idx))) return set_err(GIQL_ERR_INVALID, "bad output buffers");
   *n_pairs = 0;
-  GIQL_TRY(begin_call(ctx));
+  GIQL_TRY(begin_call(ctx, a->n, idx->n));
   hipStream_t st = (hipStream_t)stream;
   ctx->plan.fuse_done = false;
-  ctx->stats.n_a = a->n;
-  ctx->stats.n_b = idx->n;
-  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   if (a->n == 0) return GIQL_OK;
   const size_t na = (size_t)a->n, nb = (size_t)idx->n;
   if (na > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
@@ -2779,9 +2787,7 @@ static int check_index_call(giql_hip_ctx* ctx, const giql_hip_index* idx) {
 int giql_hip_index_prepare_rows_dev(giql_hip_ctx* ctx, giql_hip_index* idx, void* stream) {
   GIQL_TRY(check_index_call(ctx, idx));
   if (idx->rows_ready) return GIQL_OK;
-  GIQL_TRY(begin_call(ctx));
-  ctx->plan.planned = false;
-  ctx->stats.n_b = idx->n;
+  GIQL_TRY(begin_call(ctx, 0, idx->n));
   GIQL_TRY(index_prepare_rows(ctx, idx, (hipStream_t)stream));
   collect_spans(ctx);
   ctx->stats.span = (int64_t)idx->span;
@@ -2819,10 +2825,7 @@ static int begin_indexed_call(giql_hip_ctx* ctx, giql_hip_index* idx, const giql
   GIQL_TRY(check_index_call(ctx, idx));
   GIQL_TRY(check_side(a, "a"));
   if ((size_t)a->n > max_rows) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
-  GIQL_TRY(begin_call(ctx));
-  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
-  ctx->stats.n_a = a->n;
-  ctx->stats.n_b = idx->n;
+  GIQL_TRY(begin_call(ctx, a->n, idx->n));
   if (a->n == 0) return GIQL_OK;
   return prepare(ctx, idx, st);
 }
@@ -2844,7 +2847,6 @@ int giql_hip_count_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const giq
   if (a->n == 0) return GIQL_OK;
   if (!counts_out) return set_err(GIQL_ERR_INVALID, "counts_out is NULL");
   const size_t na = (size_t)a->n;
-  GIQL_TRY(claim_arena(ctx, st, [](char*) { return (size_t)0; }));
   HIP_TRY(hipMemsetAsync(ctx->d_meta, 0, sizeof(DevMeta), st));
   {
     Phase ph(ctx, st, GIQL_PH_COUNT);
@@ -2959,9 +2961,7 @@ int giql_hip_index_prepare_nearest_dev(giql_hip_ctx* ctx, giql_hip_index* idx, v
   GIQL_TRY(check_index_call(ctx, idx));
   if (idx->nearest_state > 0) return GIQL_OK;
   if (idx->nearest_state < 0) return index_nearest_declined();
-  GIQL_TRY(begin_call(ctx));
-  ctx->plan.planned = false;
-  ctx->stats.n_b = idx->n;
+  GIQL_TRY(begin_call(ctx, 0, idx->n));
   GIQL_TRY(index_prepare_nearest(ctx, idx, (hipStream_t)stream));
   collect_spans(ctx);
   ctx->stats.span = (int64_t)idx->span;
@@ -2978,7 +2978,6 @@ int giql_hip_nearest_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const g
   GIQL_TRY(begin_indexed_call(ctx, idx, a, st, index_prepare_nearest, OS_MAX_ROWS));
   if (a->n == 0) return GIQL_OK;
   const size_t na = (size_t)a->n;
-  GIQL_TRY(claim_arena(ctx, st, [](char*) { return (size_t)0; }));
   HIP_TRY(hipMemsetAsync(ctx->d_meta, 0, sizeof(DevMeta), st));
   IndexNearestView v;
   v.rows = rows_view_of(idx);
@@ -3070,7 +3069,6 @@ static int giql_hip_semi_anti_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
   if (!ctx || !n_out) return set_err(GIQL_ERR_INVALID, "ctx/n_out is NULL");
   GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
   hipStream_t st = (hipStream_t)stream;
-  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   *n_out = 0;
   if (a->n == 0) return GIQL_OK;
   if (!rows_out) return set_err(GIQL_ERR_INVALID, "rows_out is NULL");
@@ -3169,7 +3167,6 @@ static int giql_hip_count_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const 
   if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
   GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
   hipStream_t st = (hipStream_t)stream;
-  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   if (a->n == 0) return GIQL_OK;
   if (!counts_out) return set_err(GIQL_ERR_INVALID, "counts_out is NULL");
   const size_t na = (size_t)a->n, nb = (size_t)b->n;
@@ -3261,7 +3258,6 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
   if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
   GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
   hipStream_t st = (hipStream_t)stream;
-  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   if (a->n == 0) return GIQL_OK;
   if (!out32 && (!idx_b_out || !dist_out)) return set_err(GIQL_ERR_INVALID, "idx_b_out/dist_out is NULL");
   if (out32 && ((uintptr_t)out32 & 7)) return set_err(GIQL_ERR_INVALID, "idx_dist_out must be 8-byte aligned");
@@ -3403,7 +3399,6 @@ static int giql_hip_nearest_k_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
   if (k < 1 || k > NEAREST_K_MAX) return set_err(GIQL_ERR_INVALID, "k=%d outside [1, %d]", k, NEAREST_K_MAX);
   GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
   hipStream_t st = (hipStream_t)stream;
-  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   if (a->n == 0) return GIQL_OK;
   if (!idx_b_out || !dist_out) return set_err(GIQL_ERR_INVALID, "idx_b_out/dist_out is NULL");
   const size_t na = (size_t)a->n, nb = (size_t)b->n;
@@ -3604,10 +3599,8 @@ static int cluster_status(giql_hip_ctx* ctx, hipStream_t st) {
 static int giql_hip_cluster_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom, int64_t distance,
                          int64_t* cluster_id_out, void* stream, const DevPreds* preds = nullptr) {
   GIQL_TRY(check_cluster_args(ctx, s, n_chrom));
-  GIQL_TRY(begin_call(ctx));
+  GIQL_TRY(begin_call(ctx, s->n));
   hipStream_t st = (hipStream_t)stream;
-  ctx->stats.n_a = s->n;
-  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   if (s->n == 0) return GIQL_OK;
   if (!cluster_id_out) return set_err(GIQL_ERR_INVALID, "cluster_id_out is NULL");
   if (n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
@@ -3723,10 +3716,8 @@ static int giql_hip_merge_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int32_
                        const DevPreds* preds = nullptr, MaggArgs* aggs = nullptr) {
   GIQL_TRY(check_cluster_args(ctx, s, n_chrom));
   if (!n_out) return set_err(GIQL_ERR_INVALID, "n_out is NULL");
-  GIQL_TRY(begin_call(ctx));
+  GIQL_TRY(begin_call(ctx, s->n));
   hipStream_t st = (hipStream_t)stream;
-  ctx->stats.n_a = s->n;
-  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   *n_out = 0;
   if (s->n == 0) return GIQL_OK;
   if (!out_chrom || !out_start || !out_end) return set_err(GIQL_ERR_INVALID, "output buffer is NULL");
@@ -3848,12 +3839,8 @@ static int giql_hip_disjoin_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* t,
   const bool self = r == nullptr;  // the reference defaults to the target: every piece is covered by its parent
   const giql_side* ref = self ? t : r;
   if ((u64)ref->n * 2 > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "DISJOIN reference larger than 2^29 rows");
-  GIQL_TRY(begin_call(ctx));
+  GIQL_TRY(begin_call(ctx, t->n, ref->n));
   hipStream_t st = (hipStream_t)stream;
-  ctx->stats.n_a = t->n;
-  ctx->stats.n_b = ref->n;
-  ctx->plan.planned = false;
-  ctx->dj.planned = false;
   *n_out = 0;
   if (t->n == 0) return GIQL_OK;
   if (n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
@@ -3956,7 +3943,7 @@ static int giql_hip_disjoin_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* t,
   P.n_bp = W.n_bp;
   P.ncov = self ? nullptr : W.ncov;
   P.cbp = self ? nullptr : W.cbp;
-  P.planned = true;
+  ctx->kept = Plan::DISJOIN;
   *n_out = (int64_t)P.total;
   ctx->stats.n_out = (int64_t)P.total;
   ctx->stats.span = (int64_t)ctx->h_meta->total_span;
@@ -3972,7 +3959,7 @@ int giql_hip_disjoin_fill_dev(giql_hip_ctx* ctx, int32_t* parent_out, int32_t* s
                               int64_t capacity, void* stream) {
   if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
   const DisjoinPlan& P = ctx->dj;
-  if (!P.planned) return set_err(GIQL_ERR_STATE, "disjoin_fill without a successful disjoin_plan");
+  if (ctx->kept != Plan::DISJOIN) return set_err(GIQL_ERR_STATE, "disjoin_fill without a successful disjoin_plan");
   if (P.total == 0) return GIQL_OK;
   if (!parent_out || !start_out || !end_out) return set_err(GIQL_ERR_INVALID, "output buffer is NULL");
   if (capacity < 0 || (u64)capacity < P.total)
@@ -4090,12 +4077,8 @@ static int giql_hip_contain_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* o,
   GIQL_TRY(check_side(o, "outer"));
   GIQL_TRY(check_side(in, "inner"));
   if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
-  GIQL_TRY(begin_call(ctx));
+  GIQL_TRY(begin_call(ctx, o->n, in->n));
   hipStream_t st = (hipStream_t)stream;
-  ctx->stats.n_a = o->n;
-  ctx->stats.n_b = in->n;
-  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the other plans too)
-  ctx->dj.planned = false;
   ContainPlan& P = ctx->ct;
   P = ContainPlan{};
   P.outer = *o;
@@ -4104,7 +4087,7 @@ static int giql_hip_contain_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* o,
   P.n_i = (u32)in->n;
   *n_pairs = 0;
   if (o->n == 0 || in->n == 0) {  // nothing to launch
-    P.planned = true;
+    ctx->kept = Plan::CONTAINS;
     return GIQL_OK;
   }
   if (n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
@@ -4172,7 +4155,7 @@ static int giql_hip_contain_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* o,
   ctx->stats.n_out = (int64_t)(P.n_reg + P.n_irr);
   ctx->stats.span = (int64_t)ctx->h_meta->total_span;
   *n_pairs = (int64_t)(P.n_reg + P.n_irr);
-  P.planned = true;
+  ctx->kept = Plan::CONTAINS;
   return GIQL_OK;
 }
 
@@ -4185,7 +4168,7 @@ int giql_hip_contain_fill_dev(giql_hip_ctx* ctx, int32_t* row_outer, int32_t* ro
                               void* stream) {
   if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
   const ContainPlan& P = ctx->ct;
-  if (!P.planned) return set_err(GIQL_ERR_STATE, "contain_fill without a successful contain_plan");
+  if (ctx->kept != Plan::CONTAINS) return set_err(GIQL_ERR_STATE, "contain_fill without a successful contain_plan");
   const u64 total = P.n_reg + P.n_irr;
   if (total == 0) return GIQL_OK;
   if (!row_outer || !row_inner) return set_err(GIQL_ERR_INVALID, "row_outer/row_inner is NULL");
@@ -4260,8 +4243,6 @@ static int giql_hip_semi_anti_pred_dev_impl(giql_hip_ctx* ctx, const giql_side* 
   GIQL_TRY(check_rowpred(pred, max_distance));
   GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
   hipStream_t st = (hipStream_t)stream;
-  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plans too)
-  ctx->dj.planned = false;
   *n_out = 0;
   if (a->n == 0) return GIQL_OK;
   if (!rows_out) return set_err(GIQL_ERR_INVALID, "rows_out is NULL");
@@ -4493,8 +4474,6 @@ static int giql_hip_count_pred_dev_impl(giql_hip_ctx* ctx, const giql_side* a, c
   GIQL_TRY(check_rowpred(pred, max_distance));
   GIQL_TRY(begin_pair_call(ctx, a, b, n_chrom));
   hipStream_t st = (hipStream_t)stream;
-  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plans too)
-  ctx->dj.planned = false;
   if (a->n == 0) return GIQL_OK;
   if (!counts_out) return set_err(GIQL_ERR_INVALID, "counts_out is NULL");
   const size_t na = (size_t)a->n, nb = (size_t)b->n;
@@ -4526,10 +4505,8 @@ static int giql_hip_group_rows_dev_impl(giql_hip_ctx* ctx, const giql_side* s, i
   GIQL_TRY(check_side(s, "s"));
   if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
   GIQL_TRY(check_rows_fit((size_t)s->n, 0));
-  GIQL_TRY(begin_call(ctx));
+  GIQL_TRY(begin_call(ctx, s->n));
   hipStream_t st = (hipStream_t)stream;
-  ctx->stats.n_a = s->n;
-  ctx->plan.planned = false;  // (the ways out before the arena is claimed drop the plan too)
   *n_groups = 0;
   if (s->n == 0) return GIQL_OK;
   if (!group_of_row || !rep_row) return set_err(GIQL_ERR_INVALID, "output buffer is NULL");
@@ -4607,7 +4584,7 @@ int giql_hip_segment_sum_dev(giql_hip_ctx* ctx, const int64_t* values, const int
   if (!ctx || n < 0 || n_groups < 0 || n_groups > 0x7FFFFFFFll) return set_err(GIQL_ERR_INVALID, "bad arguments");
   if ((n > 0 && (!values || !group_of_row)) || (n_groups > 0 && !sums))
     return set_err(GIQL_ERR_INVALID, "NULL buffer");
-  GIQL_TRY(begin_call(ctx));
+  GIQL_TRY(begin_call_beside_plan(ctx));
   hipStream_t st = (hipStream_t)stream;
   if (n_groups > 0) HIP_TRY(hipMemsetAsync(sums, 0, (size_t)n_groups * sizeof(int64_t), st));
   if (n == 0) return GIQL_OK;
@@ -4712,7 +4689,7 @@ int giql_hip_inner_plan_export_dev(giql_hip_ctx* ctx, int32_t* q_rid_out, uint32
                                    int32_t rid_add_a, int32_t rid_add_b, int32_t* query_is_a, int64_t* n_q,
                                    int64_t* n_s, void* stream) {
   if (!ctx || !query_is_a || !n_q || !n_s) return set_err(GIQL_ERR_INVALID, "NULL argument");
-  if (!ctx->plan.planned) return set_err(GIQL_ERR_STATE, "plan export without a successful inner_plan");
+  if (ctx->kept != Plan::INNER) return set_err(GIQL_ERR_STATE, "plan export without a successful inner_plan");
   if (ctx->plan.plan_is_join && ctx->plan.n_reg + ctx->plan.n_irr != 0)
     return set_err(GIQL_ERR_STATE, "the last giql_hip_inner_join_dev wrote its pairs itself and kept no plan: "
                                    "call giql_hip_inner_plan_dev first");
@@ -4907,7 +4884,7 @@ int giql_hip_take_dev(giql_hip_ctx* ctx, const void* const* cols, const int32_t*
       return set_err(GIQL_ERR_INVALID, "column %d: buffer not aligned to its element size", c);
   }
   if (n == 0 || n_cols == 0) return GIQL_OK;
-  GIQL_TRY(begin_call(ctx));
+  GIQL_TRY(begin_call_beside_plan(ctx));
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
   u32 grid = cdiv((u64)n, (u64)TK_NT * 4 * 4);
@@ -4943,8 +4920,6 @@ int giql_hip_take_utf8_plan_dev(giql_hip_ctx* ctx, const int32_t* offsets, int64
   GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
   *n_bytes = 0;
-  // its scan partials are carved from the start of the arena, where an INNER plan keeps its arrays
-  ctx->plan.planned = false;  // (so the way out with no rows drops the plan too)
   if (n == 0) {
     HIP_TRY(hipMemsetAsync(out_offsets, 0, sizeof(int32_t), st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -4987,7 +4962,7 @@ int giql_hip_take_utf8_fill_dev(giql_hip_ctx* ctx, const int32_t* offsets, const
   if (!ctx || n < 0 || n_rows < 0 || n_rows > 0x7FFFFFFFll) return set_err(GIQL_ERR_INVALID, "bad arguments");
   if (n == 0) return GIQL_OK;
   if (!idx || !out_offsets || (n_rows > 0 && !offsets)) return set_err(GIQL_ERR_INVALID, "NULL buffer");
-  GIQL_TRY(begin_call(ctx));
+  GIQL_TRY(begin_call_beside_plan(ctx));
   hipStream_t st = (hipStream_t)stream;
   u32 grid = cdiv((u64)n, (u64)TK_NT * 2);
   if (grid > 2u * GIQL_STREAM_GRID) grid = 2u * GIQL_STREAM_GRID;
@@ -5043,11 +5018,9 @@ int giql_hip_select_expr_dev(giql_hip_ctx* ctx, const giql_pred* preds, int32_t 
   // a side given neither ids nor a row count is addressed by the candidate index
   if (!idx_a && n_rows_a == 0 && !uses[0]) n_rows_a = n;
   if (!idx_b && n_rows_b == 0 && !uses[1]) n_rows_b = n;
-  // the mask and scan partials are carved from the start of the arena, where an INNER plan keeps its arrays
-  ctx->plan.planned = false;  // (so the way out with no candidates drops the plan too)
   *n_kept = 0;
+  GIQL_TRY(begin_call(ctx));  // (before the way out with no candidates: that one drops a plan too)
   if (n == 0) return GIQL_OK;
-  GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
   const u32 nb = cdiv((u64)n, SEL_TILE);
   DevOperand* prog = nullptr;
@@ -5120,13 +5093,9 @@ int giql_hip_eval_expr_dev(giql_hip_ctx* ctx, const giql_operand* nodes, int32_t
   // a side given neither ids nor a row count is addressed by the candidate index
   if (!idx_a && n_rows_a == 0 && !uses[0]) n_rows_a = n;
   if (!idx_b && n_rows_b == 0 && !uses[1]) n_rows_b = n;
-  // the nodes and the NULL counts are carved from the start of the arena, where the plans keep their arrays
-  ctx->plan.planned = false;  // (so the way out with no candidates drops the plans too)
-  ctx->dj.planned = false;
-  ctx->ct.planned = false;
   if (n_null) memset(n_null, 0, (size_t)n_outs * sizeof(int64_t));
+  GIQL_TRY(begin_call(ctx));  // (before the way out with no candidates: that one drops a plan too)
   if (n == 0) return GIQL_OK;
-  GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
   DevOperand* prog = nullptr;
   u64* nulls = nullptr;
@@ -5167,7 +5136,7 @@ int giql_hip_mark_dev(giql_hip_ctx* ctx, const int32_t* idx, int64_t n, uint8_t*
   if (!ctx || n < 0 || n_rows < 0 || n_rows > 0x7FFFFFFFll || (n > 0 && (!idx || !flags)))
     return set_err(GIQL_ERR_INVALID, "bad arguments");
   if (n == 0) return GIQL_OK;
-  GIQL_TRY(begin_call(ctx));
+  GIQL_TRY(begin_call_beside_plan(ctx));
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
   u32 grid = cdiv((u64)n, 256 * 8);
@@ -5191,9 +5160,8 @@ int giql_hip_left_pad_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, int
       (capacity > 0 && !row_a))
     return set_err(GIQL_ERR_INVALID, "bad arguments (0 <= n_pairs <= capacity, n_rows_a < 2^31)");
   *n_total = n_pairs;
-  ctx->plan.planned = false;  // (the way out with nothing to do drops the plan too)
+  GIQL_TRY(begin_call(ctx));  // (before the way out with nothing to do: that one drops a plan too)
   if (n_pairs == 0 && n_rows_a == 0) return GIQL_OK;
-  GIQL_TRY(begin_call(ctx));
   hipStream_t st = (hipStream_t)stream;
   const size_t n_words = ((size_t)n_rows_a + 63) / 64;
   const u32 nb = cdiv((u64)n_rows_a, LP_BLOCK_ROWS);
@@ -5509,6 +5477,12 @@ int giql_hip_inner(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, in
   GIQL_TRY(check_side(b, "b"));
   HIP_TRY(hipSetDevice(ctx->device));
   *row_a = *row_b = nullptr;
+  // The plans made below read sides staged on the device for this call only: none outlives it.  (The one write of
+  // the tag outside the plan entry points, begin_call and the arena: a plan must not point at released columns.)
+  struct DropPlan {
+    giql_hip_ctx* c;
+    ~DropPlan() { c->kept = Plan::NONE; }
+  } drop_plan{ctx};
   // GIQL_HIP_E2E_COMPACT: 1 = compact-plan download whenever the plan has that form, 0 = never (round 3: pairs
   // downloaded, the larger table uploaded block by block); unset = compact unless this context's last plan says the
   // tables do not take the single-range form (then the block pipeline, which hides most of the upload, is the better bet)

@@ -162,12 +162,23 @@ int giql_hip_get_stats(giql_hip_ctx* ctx, giql_hip_stats* out);
 /* INNER join in two calls so the caller owns the output:
  *   plan: sort + count + scan; returns the exact number of pairs;
  *   fill: writes row_a[i], row_b[i] for i < n_pairs (capacity >= n_pairs).
- * The plan lives in the context's workspace.  It is consumed by fill and by
- * giql_hip_inner_plan_export_dev (each as often as wanted) only until the next call
- * on the context that launches work and is neither: the operators, the index entry
- * points, chrom_spans, select, left_pad and take_utf8_plan reuse that workspace and make fill /
- * export return GIQL_ERR_STATE; after any other such call a fill is not supported.
- * Calls that launch nothing -- get_stats, set_profiling, last_error -- keep the plan. */
+ *
+ * THE LIFETIME OF A PLAN -- one rule for the INNER plan (giql_hip_window_plan_dev's is one), the DISJOIN plan and
+ * the CONTAINS plan.  A plan lives in the context's workspace, and a context keeps at most one: a successful plan
+ * call replaces whatever was kept.  The plan
+ * is consumed by its own fill and export entry points, each as often as wanted, until the next call on the context
+ * that begins a call: every operator, plan, index, select / eval_expr / left_pad / take_utf8_plan and chrom_spans
+ * entry point, the host-buffer entry points (which keep no plan of their own: theirs read columns staged for that
+ * call alone), and giql_hip_reserve when it grows the workspace.  Such a call drops
+ * the plan whatever it goes on to do -- with an empty side or nothing to do as well -- and the fill and export
+ * entry points return GIQL_ERR_STATE afterwards.  Two exceptions:
+ *   - giql_hip_distance_dev, giql_hip_take_dev, giql_hip_take_utf8_fill_dev, giql_hip_mark_dev and
+ *     giql_hip_segment_sum_dev use no workspace and keep an INNER or DISJOIN plan (distances and projections of
+ *     the pairs filled so far); a CONTAINS plan does not survive them.
+ *   - calls that launch nothing keep every plan: get_stats, set_profiling, last_error, reserve within the current
+ *     size, and a prepare call on an index that is already prepared.  So do the fill and export entry points
+ *     themselves, giql_hip_fill_from_plan_dev, giql_hip_pairs_checksum_dev and the copy / stream probes.  (A
+ *     call that rejects its arguments has dropped the plan only if it had begun: do not rely on either.) */
 int giql_hip_inner_plan_dev(giql_hip_ctx* ctx, const giql_side* a,
                             const giql_side* b, int32_t n_chrom, void* stream,
                             int64_t* n_pairs);
@@ -275,8 +286,8 @@ int giql_hip_merge_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom,
  * Both sides share one chromosome dictionary; every row of both needs start <= end (checked on the
  * device: GIQL_ERR_INVALID names the side); a zero-length target row yields nothing, a zero-length
  * reference row cuts and never covers.  A reference has at most 2^29 rows.  The plan lives in the
- * context's workspace under the rules of the INNER plan: any call that reuses the workspace makes
- * fill return GIQL_ERR_STATE. */
+ * context's workspace: THE LIFETIME OF A PLAN (giql_hip_inner_plan_dev) says until when.  An empty target
+ * gives *n_out = 0 and keeps no plan. */
 int giql_hip_disjoin_plan_dev(giql_hip_ctx* ctx, const giql_side* target,
                               const giql_side* reference, int32_t n_chrom,
                               int64_t* n_out, void* stream);
@@ -295,8 +306,8 @@ int giql_hip_disjoin_fill_dev(giql_hip_ctx* ctx, int32_t* parent_out, int32_t* s
  *   fill: row_outer[k] / row_inner[k] for k < n_pairs (capacity >= n_pairs, else GIQL_ERR_CAPACITY and the plan
  *         stays valid).
  * Both sides share one chromosome dictionary (GIQL_ERR_CHROM, GIQL_ERR_SPAN as for the INNER join).  The plan
- * lives in the context: any other call that launches work drops it and fill returns GIQL_ERR_STATE; a contain
- * plan likewise drops an INNER or DISJOIN plan (their fill and export entry points return GIQL_ERR_STATE). */
+ * lives in the context (per-row arrays in the workspace, per-tile arrays beside it) under THE LIFETIME OF A PLAN
+ * (giql_hip_inner_plan_dev); it is the one plan that giql_hip_distance_dev, take, mark and segment_sum drop too. */
 int giql_hip_contain_plan_dev(giql_hip_ctx* ctx, const giql_side* outer, const giql_side* inner,
                               int32_t n_chrom, void* stream, int64_t* n_pairs);
 int giql_hip_contain_fill_dev(giql_hip_ctx* ctx, int32_t* row_outer, int32_t* row_inner,
@@ -324,7 +335,8 @@ int giql_hip_window_plan_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_s
  * upstream), bit 1 = stranded (NULL unless both strands are '+' / '-'; the sign flips on A's '-' strand); the + 1 is
  * applied to the gap before any sign.  strand_a / strand_b: one int32 code per ROW of the table (0 '+', 1 '-', 2 '.',
  * 3 '?', anything else NULL), read only when stranded (NULL otherwise).  All DEVICE pointers.  A row id outside
- * [0, side n) is GIQL_ERR_INVALID and nothing is read through it.  Uses no workspace: a plan on the context stays. */
+ * [0, side n) is GIQL_ERR_INVALID and nothing is read through it.  Uses no workspace: an INNER or DISJOIN plan on the
+ * context stays (THE LIFETIME OF A PLAN, giql_hip_inner_plan_dev). */
 int giql_hip_distance_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_side* b, const int32_t* row_a,
                           const int32_t* row_b, int64_t n, const int32_t* strand_a, const int32_t* strand_b,
                           int32_t flags, int64_t* dist_out, uint8_t* valid_out, void* stream);
@@ -343,8 +355,8 @@ int giql_hip_distance_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_side
  * search per A row; the DISTANCE count is a rank difference over two sorts of B; the containment count walks the
  * CONTAINS plan's candidate tiles (stats.reserved bits 0-3: 0 general, 1 uniform B under CONTAINS, whose range counts
  * are exact).  stats.n_irregular_a / n_irregular_b: the rows settled by the literal predicate (counts only).
- * GIQL_ERR_CHROM / GIQL_ERR_SPAN as for the INNER join.  Like every call that launches work, both drop an INNER,
- * contain or DISJOIN plan held in the context: its fill returns GIQL_ERR_STATE. */
+ * GIQL_ERR_CHROM / GIQL_ERR_SPAN as for the INNER join.  Both begin a call: a plan held in the context is dropped
+ * (THE LIFETIME OF A PLAN, giql_hip_inner_plan_dev). */
 #define GIQL_ROWPRED_CONTAINS 1   /* a CONTAINS b */
 #define GIQL_ROWPRED_WITHIN   2   /* a WITHIN b   */
 #define GIQL_ROWPRED_DISTANCE 3   /* DISTANCE(a, b) <= max_distance; max_distance is read for this one only */
@@ -535,8 +547,8 @@ int giql_hip_select_expr_dev(giql_hip_ctx* ctx, const giql_pred* preds, int32_t 
  * n_outs outside 1..8, a NULL data, a type other than GIQL_T_I64 / GIQL_T_F64 or a malformed program:
  * GIQL_ERR_INVALID, the message names the output.  n_null[k] = the number of NULL results of output k (read back
  * with the status: no extra synchronisation).
- * Like select, the call stages its nodes in the context's workspace: an INNER / CONTAINS / DISJOIN plan held there
- * is gone afterwards (giql_hip_inner_fill_dev and its kin return GIQL_ERR_STATE). */
+ * Like select, the call begins a call on the context (it stages its nodes in the workspace): a plan held there is
+ * dropped, with n == 0 as well (THE LIFETIME OF A PLAN, giql_hip_inner_plan_dev). */
 typedef struct giql_expr_out {
   int32_t first, count;   /* the program: nodes[first .. first + count) */
   int32_t type;           /* GIQL_T_I64 or GIQL_T_F64: element type of data */
@@ -561,9 +573,9 @@ int giql_hip_mark_dev(giql_hip_ctx* ctx, const int32_t* idx, int64_t n,
  * *n_total = n_pairs + number appended.  capacity < *n_total: GIQL_ERR_CAPACITY, *n_total set, nothing
  * written at or past n_pairs.  An id in row_a outside [0, n_rows_a): GIQL_ERR_INVALID, nothing appended.
  * row_b may be NULL (ids only).  n_rows_a <= 0x7FFFFFFF; n_pairs is 64-bit.
- * The call keeps a flag byte and a bit per left row in the context's workspace, like the other operators: an INNER
- * plan held there is gone afterwards (giql_hip_inner_fill_dev / giql_hip_inner_plan_export_dev return
- * GIQL_ERR_STATE), so fill the pairs first and pad them second. */
+ * The call keeps a flag byte and a bit per left row in the context's workspace, like the other operators: a plan
+ * held there is dropped (THE LIFETIME OF A PLAN, giql_hip_inner_plan_dev), so fill the pairs first and pad them
+ * second. */
 int giql_hip_left_pad_dev(giql_hip_ctx* ctx, int32_t* row_a, int32_t* row_b, int64_t n_pairs,
                           int64_t capacity, int64_t n_rows_a, void* stream, int64_t* n_total);
 
@@ -756,7 +768,8 @@ int giql_hip_semi_anti_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx,
  *                                      SEMI / ANTI on the index are unaffected.
  * Several targets tied on (distance, start, end): any one of them may come back,
  * as upstream.  idx_b_out: [a->n] int32; dist_out: [a->n] int64.  The context's
- * stats report n_a, n_b and n_out = a->n; a plan held by the context is dropped. */
+ * stats report n_a, n_b and n_out = a->n; a plan held by the context is dropped
+ * (THE LIFETIME OF A PLAN, giql_hip_inner_plan_dev). */
 int giql_hip_index_prepare_nearest_dev(giql_hip_ctx* ctx, giql_hip_index* idx, void* stream);
 int giql_hip_nearest_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const giql_side* a,
                                  int is_signed, int64_t max_distance,

@@ -16,10 +16,11 @@ was found by a long random soak.  So here:
   ``select`` / ``take_utf8`` / a plan of another operator put between some plans and their fill -- which must then
   refuse (``GIQL_ERR_STATE``): those calls reuse the workspace the plan lives in.
 * DISJOIN (self mode, reference mode, plan + fill through the raw ABI) walks the classes on which its path can
-  differ, against the brute force of ``tests/_disjoin_ref.py``; its plan lives in the same workspace (``ctx->dj``).
+  differ, against the brute force of ``tests/_disjoin_ref.py``; its plan lives in the same workspace, and the
+  context keeps one plan at a time (``ctx->kept``; ``tests/test_plan_lifetime_gpu.py`` has the rule cell by cell).
 * CONTAINS / WITHIN (the join, the join with the sides exchanged, plan + fill through the raw ABI) walk the classes on
-  which its path can differ, against the brute force of ``tests/_contain_ref.py``; its plan is the third one kept on
-  the context (``ctx->ct``).
+  which its path can differ, against the brute force of ``tests/_contain_ref.py``; its plan is the third kind the
+  context can keep.
 * Leg 3: the sticky four-pass fallback after a bucket too large for the bucket stage, reached from every class.
 * Leg 4: production density on a default context: every ordered pair of bucket widths.
 
