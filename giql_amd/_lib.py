@@ -56,6 +56,9 @@ SYMBOLS = [
     "giql_hip_merge_agg_dev",
 ]
 
+#: every symbol include/giql_hip_range_sets.h declares (the extension header beside giql_hip.h)
+RANGE_SET_SYMBOLS = ["giql_hip_range_set_any_dev"]
+
 
 class GiqlHipUnavailable(RuntimeError):
     """libgiql_hip.so could not be loaded (not built, or no ROCm runtime)."""
@@ -152,6 +155,24 @@ class CAgg(ctypes.Structure):
         ("out_nn", ctypes.c_void_p),
     ]
 
+
+class CRangeSet(ctypes.Structure):
+    """``giql_range_set`` (include/giql_hip_range_sets.h)."""
+
+    _fields_ = [
+        ("op", ctypes.c_int32),
+        ("n_ranges", ctypes.c_int32),
+        ("chrom", ctypes.c_void_p),
+        ("on_start", ctypes.c_void_p),
+        ("on_end", ctypes.c_void_p),
+        ("out_value", ctypes.c_void_p),
+        ("out_valid", ctypes.c_void_p),
+    ]
+
+
+#: ``GIQL_RANGE_*``: the operator of a literal range set, and the caps of one call
+RANGE_OPS = {"intersects": 0, "contains": 1, "within": 2}
+RANGE_MAX_SETS, RANGE_MAX_RANGES = 8, 1024
 
 #: ``GIQL_AGG_*``: the kernel's functions (AVG is SUM / non-NULL count, divided by the engine)
 AGG_FUNCS = {"COUNT": 0, "SUM": 1, "MIN": 2, "MAX": 3}
@@ -252,6 +273,7 @@ def load() -> ctypes.CDLL:
     L.giql_hip_eval_expr_dev.argtypes = [vp, P(COperand), i32, P(CExprOut), i32, vp, i64, vp, i64, i64, P(i64), vp]
     L.giql_hip_merge_agg_dev.argtypes = [vp, P(CSide), i32, i64, P(CPred), i32, P(CAgg), i32, vp, vp, vp, vp, i64,
                                          P(i64), vp]
+    L.giql_hip_range_set_any_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, P(CRangeSet), i32, vp]
     _lib = L
     return L
 

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/giql_hip.h"
+#include "../../include/giql_hip_range_sets.h"
 #include "aux_kernels.hip.h"
 #include "take_kernels.hip.h"
 #include "select_kernels.hip.h"
@@ -25,6 +26,7 @@
 #include "outer_kernels.hip.h"
 #include "cluster_kernels.hip.h"
 #include "merge_agg_kernels.hip.h"
+#include "range_set_kernels.hip.h"
 #include "disjoin_kernels.hip.h"
 #include "contain_kernels.hip.h"
 #include "distance_kernels.hip.h"
@@ -5148,6 +5150,94 @@ int giql_hip_mark_dev(giql_hip_ctx* ctx, const int32_t* idx, int64_t n, uint8_t*
   }
   GIQL_TRY(read_meta(ctx, st));
   collect_spans(ctx);
+  return GIQL_OK;
+}
+
+// ------------------------------------------------- literal range sets (ANY)
+// The sets' tables are prepared on the host (range_set_prepare.h), laid out in one block of the arena and copied in
+// one transfer; one launch answers every set (grid.y = set).
+int giql_hip_range_set_any_dev(giql_hip_ctx* ctx, const int32_t* chrom, const int32_t* start, const int32_t* end,
+                               const uint8_t* valid_chrom, const uint8_t* valid_start, const uint8_t* valid_end,
+                               int64_t n, const giql_range_set* sets, int32_t n_sets, void* stream) {
+  static_assert(GIQL_RANGE_INTERSECTS == RSET_INTERSECTS && GIQL_RANGE_CONTAINS == RSET_CONTAINS &&
+                GIQL_RANGE_WITHIN == RSET_WITHIN && GIQL_RANGE_MAX_SETS == RSET_MAX_SETS &&
+                GIQL_RANGE_MAX_RANGES == RSET_MAX_RANGES, "range set constants");
+  if (!ctx || n < 0 || n > 0x7FFFFFF0ll || !sets || n_sets < 1 || n_sets > RSET_MAX_SETS ||
+      (n > 0 && (!chrom || !start || !end)))
+    return set_err(GIQL_ERR_INVALID, "bad arguments (1..%d sets, n in [0, 2^31-16], no NULL column)", RSET_MAX_SETS);
+  for (int k = 0; k < n_sets; k++) {
+    const giql_range_set& s = sets[k];
+    if (s.op < RSET_INTERSECTS || s.op > RSET_WITHIN) return set_err(GIQL_ERR_INVALID, "range set %d: op %d", k, s.op);
+    if (s.n_ranges < 1 || s.n_ranges > RSET_MAX_RANGES)
+      return set_err(GIQL_ERR_INVALID, "range set %d: %d ranges outside [1, %d]", k, s.n_ranges, RSET_MAX_RANGES);
+    if (!s.chrom || !s.on_start || !s.on_end || (n > 0 && (!s.out_value || !s.out_valid)))
+      return set_err(GIQL_ERR_INVALID, "range set %d: NULL array", k);
+  }
+  GIQL_TRY(begin_call(ctx, n));  // (before the way out with no rows: that one drops a plan too)
+  if (n == 0) return GIQL_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // the block: per set chrom[k] (int32), then key / other / agg (int64), every array 16-byte aligned
+  std::vector<char> blob;
+  size_t off[RSET_MAX_SETS][4];
+  size_t total = 0;
+  for (int k = 0; k < n_sets; k++) {
+    const size_t nr = (size_t)sets[k].n_ranges;
+    off[k][0] = total;
+    total = align_up(total + nr * sizeof(int32_t), 16);
+    for (int a = 1; a < 4; a++) {
+      off[k][a] = total;
+      total = align_up(total + nr * sizeof(i64), 16);
+    }
+  }
+  blob.resize(total);
+  RangeSetTable t;
+  for (int k = 0; k < n_sets; k++) {
+    const giql_range_set& s = sets[k];
+    if (!range_set_prepare(s.op, s.chrom, s.on_start, s.on_end, s.n_ranges, t))
+      return set_err(GIQL_ERR_INVALID, "range set %d could not be prepared", k);
+    const size_t nr = (size_t)s.n_ranges;
+    memcpy(blob.data() + off[k][0], t.chrom.data(), nr * sizeof(int32_t));
+    memcpy(blob.data() + off[k][1], t.key.data(), nr * sizeof(i64));
+    memcpy(blob.data() + off[k][2], t.other.data(), nr * sizeof(i64));
+    memcpy(blob.data() + off[k][3], t.agg.data(), nr * sizeof(i64));
+  }
+  char* d_blob = nullptr;
+  GIQL_TRY(claim_arena(ctx, st, [&](char* base) {
+    Carver c{base};
+    d_blob = c.take<char>(total);
+    return c.off;
+  }));
+  HIP_TRY(hipMemcpyAsync(d_blob, blob.data(), total, hipMemcpyHostToDevice, st));
+  RsArgs args;
+  memset(&args, 0, sizeof(args));
+  uintptr_t a16 = (uintptr_t)chrom | (uintptr_t)start | (uintptr_t)end;
+  uintptr_t a4 = (uintptr_t)valid_chrom | (uintptr_t)valid_start | (uintptr_t)valid_end;
+  for (int k = 0; k < n_sets; k++) {
+    RsSetDev& d = args.set[k];
+    d.chrom = reinterpret_cast<const int32_t*>(d_blob + off[k][0]);
+    d.key = reinterpret_cast<const i64*>(d_blob + off[k][1]);
+    d.other = reinterpret_cast<const i64*>(d_blob + off[k][2]);
+    d.agg = reinterpret_cast<const i64*>(d_blob + off[k][3]);
+    d.k = sets[k].n_ranges;
+    d.op = sets[k].op;
+    d.value = sets[k].out_value;
+    d.valid = sets[k].out_valid;
+    a4 |= (uintptr_t)d.value | (uintptr_t)d.valid;
+  }
+  const int vec_ok = (a16 & 15) == 0 && (a4 & 3) == 0;
+  const u64 n_tiles = ((u64)n + RSET_TILE - 1) / RSET_TILE;
+  // the 28 KB of LDS let five blocks share a compute unit: one resident wave of blocks walks the tiles
+  u64 grid = (u64)ctx->n_cu * 5;
+  if (grid > n_tiles) grid = n_tiles;
+  {
+    Phase ph(ctx, st, GIQL_PH_AUX);
+    hipLaunchKernelGGL(k_range_set_any, dim3((u32)grid, (u32)n_sets), dim3(RSET_NT), 0, st, chrom, start, end, valid_chrom,
+                       valid_start, valid_end, (u64)n, args, vec_ok);
+    GIQL_TRY(post_launch("range_set_any"));
+  }
+  HIP_TRY(hipStreamSynchronize(st));  // (the host block is read by the copy until here)
+  collect_spans(ctx);
+  ctx->stats.n_out = n;
   return GIQL_OK;
 }
 

@@ -1373,6 +1373,60 @@ class HipEngine:
                     n_null[k] += int(nulls[j])
         return [(values[k], valid[k] if n_null[k] else None) for k in range(len(flat))]
 
+    def range_set_any(self, chrom, start, end, sets, valid=(None, None, None)):
+        """``interval <op> ANY(ranges)`` per row of one table, for up to 8 sets of up to 1024 literal ranges
+        (``giql_hip_range_set_any_dev``): a list of ``(value, valid)`` uint8 device tensors, one pair per set --
+        the predicate's three-valued result, ``valid`` 0 where it is SQL NULL -- ready to stand as a uint8 operand
+        with its validity in :meth:`select`.
+
+        ``chrom`` / ``start`` / ``end``: int32 device tensors of one length, the chromosome codes and the RAW
+        coordinate columns; ``valid``: their uint8 validity tensors (``None`` = no NULLs).  A set is
+        ``(op, chrom_codes, on_start, on_end)`` with ``op`` "intersects" / "contains" / "within" and three host
+        sequences of one length: per range its chromosome code and the int64 bounds ``start`` and ``end`` are
+        compared with (``start < on_start AND end > on_end`` for INTERSECTS, ``<=`` / ``>=`` for CONTAINS, ``>=`` /
+        ``<=`` for WITHIN) -- the caller has moved the table's coordinate encoding onto them.  Any order, duplicates
+        allowed."""
+        import numpy as np
+
+        torch = _torch()
+        n = int(chrom.shape[0])
+        cols = []
+        for t, what in ((chrom, "chrom"), (start, "start"), (end, "end")):
+            if t.dim() != 1 or int(t.shape[0]) != n:
+                raise ValueError(f"{what} must be a 1-D tensor of {n} rows")
+            cols.append(self._dev_ptr(t, what, torch.int32))
+        valids = []
+        for v, what in zip(valid, ("chrom", "start", "end")):
+            if v is not None and (v.dtype not in (torch.uint8, torch.bool) or v.dim() != 1 or int(v.shape[0]) != n):
+                raise ValueError(f"validity of {what} must be a uint8 tensor of {n} rows")
+            valids.append(self._dev_ptr(v, f"validity of {what}"))
+        if not 1 <= len(sets) <= _lib.RANGE_MAX_SETS:
+            raise ValueError(f"between 1 and {_lib.RANGE_MAX_SETS} range sets per call, got {len(sets)}")
+        c_sets = (_lib.CRangeSet * len(sets))()
+        keep_alive, outs = [], []
+        for j, (op, codes, on_start, on_end) in enumerate(sets):
+            if op not in _lib.RANGE_OPS:
+                raise ValueError(f"range set operator {op!r}")
+            codes = np.ascontiguousarray(codes, dtype=np.int32)
+            on_start = np.ascontiguousarray(on_start, dtype=np.int64)
+            on_end = np.ascontiguousarray(on_end, dtype=np.int64)
+            k = int(codes.shape[0])
+            if codes.ndim != 1 or on_start.shape != codes.shape or on_end.shape != codes.shape:
+                raise ValueError("a range set is three sequences of one length")
+            if not 1 <= k <= _lib.RANGE_MAX_RANGES:
+                raise ValueError(f"between 1 and {_lib.RANGE_MAX_RANGES} ranges per set, got {k}")
+            value = torch.empty(n, dtype=torch.uint8, device=self.device)
+            ok = torch.empty(n, dtype=torch.uint8, device=self.device)
+            c_sets[j].op, c_sets[j].n_ranges = _lib.RANGE_OPS[op], k
+            c_sets[j].chrom, c_sets[j].on_start, c_sets[j].on_end = codes.ctypes.data, on_start.ctypes.data, on_end.ctypes.data
+            c_sets[j].out_value = value.data_ptr() if n else None
+            c_sets[j].out_valid = ok.data_ptr() if n else None
+            keep_alive.append((codes, on_start, on_end))
+            outs.append((value, ok))
+        _lib.check(self._L.giql_hip_range_set_any_dev(self._h, cols[0], cols[1], cols[2], valids[0], valids[1], valids[2],
+                                                      n, c_sets, len(sets), self._stream()))
+        return outs
+
     def mark(self, idx, n_rows: int):
         """``flags[idx] = 1`` over ``n_rows`` zero-initialised bytes (which left rows keep a pair)."""
         torch = _torch()

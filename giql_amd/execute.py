@@ -1010,6 +1010,66 @@ def _execute_cluster_merge(plan: JoinPlan, tables, eng: HipEngine, return_indice
     return out
 
 
+def _filter_chrom_codes(col, what: str):
+    """A filter table's chromosome column as ``(int32 codes, the values the codes index, validity bytes or None)``.
+    An Arrow string column keeps the codes of its own dictionary -- the array ``_arrow_codes`` caches for a pinned
+    or immutable table, so that ``_device_side`` finds the table's device copy again -- with NULL rows encoded as
+    ``""`` and flagged in the validity beside."""
+    fast = _arrow_codes(col, what, nulls_as="")
+    if fast is not None:
+        import pyarrow as pa
+
+        codes, values = fast
+        arr = col.combine_chunks() if isinstance(col, pa.ChunkedArray) else col
+        valid = None
+        if arr.null_count:
+            valid = np.ascontiguousarray(arr.is_valid().to_numpy(zero_copy_only=False).astype(np.uint8))
+        if codes.flags.writeable:
+            codes.setflags(write=False)   # (shared by every later query over this table)
+        return codes, list(values), valid
+    raw = _to_numpy_obj(col)
+    null = np.fromiter((v is None or (isinstance(v, float) and v != v) for v in raw), dtype=bool, count=raw.size)
+    values, codes = np.unique(np.where(null, "", raw).astype(str), return_inverse=True)
+    return (np.ascontiguousarray(codes, dtype=np.int32), values.tolist(),
+            np.ascontiguousarray(~null, dtype=np.uint8) if null.any() else None)
+
+
+def _range_set_answers(plan: JoinPlan, tbl, eng: HipEngine) -> list:
+    """``HipEngine.range_set_any`` over a FILTER plan's table: the chromosome column is encoded once, the chromosomes
+    the plan's ranges name join its dictionary (one no row carries gets a code past the table's own), the bounds take
+    the table's coordinate encoding (``range_sets.bounds``) and the raw int32 columns go up as they are."""
+    import pyarrow as pa
+    import torch
+
+    from .range_sets import bounds
+
+    side = plan.left
+    codes, values, chrom_valid = _filter_chrom_codes(_column(tbl, side.chrom_col), f"{side.table}.{side.chrom_col}")
+    code_of = {v: i for i, v in enumerate(values)}
+    for rs in plan.range_sets:
+        for c, _lo, _hi in rs.ranges:
+            code_of.setdefault(c, len(code_of))
+    valid = [chrom_valid, None, None]
+    cols = []
+    for k, name in ((1, side.start_col), (2, side.end_col)):
+        col = _column(tbl, name)
+        if isinstance(col, (pa.Array, pa.ChunkedArray)) and col.null_count:
+            valid[k] = np.ascontiguousarray(col.is_valid().to_numpy(zero_copy_only=False).astype(np.uint8))
+            col = col.fill_null(0)
+        cols.append(col)
+    if valid[1] is None and valid[2] is None:
+        dev = _device_side(tbl, side, codes, eng)     # (a pinned table's device copy is found again here)
+    else:
+        dev = DeviceSide.from_numpy(codes, _int32_column(cols[0], f"{side.table}.{side.start_col}"),
+                                    _int32_column(cols[1], f"{side.table}.{side.end_col}"), side.encoding, device=eng.device)
+    sets = []
+    for rs in plan.range_sets:
+        on_start, on_end = zip(*[bounds(rs.op, r, side.encoding) for r in rs.ranges])
+        sets.append((rs.op, [code_of[c] for c, _lo, _hi in rs.ranges], on_start, on_end))
+    valid_dev = [None if v is None else torch.from_numpy(v).to(eng.device) for v in valid]
+    return eng.range_set_any(dev.chrom, dev.start, dev.end, sets, valid=valid_dev)
+
+
 def _execute_filter(plan: JoinPlan, tables, eng: HipEngine, return_indices: bool):
     """Literal-range filter of one table (BASELINE config 1): the plan's comparisons run
     in the select kernel, the projected columns are gathered on the device."""
@@ -1020,7 +1080,14 @@ def _execute_filter(plan: JoinPlan, tables, eng: HipEngine, return_indices: bool
         raise ValueError(f"table {side.table!r} was not provided")
     tbl = tables[side.table]
     n = _n_rows(tbl)
-    keep = eng.select(_Residuals(plan, tbl, None, eng).preds(plan.residuals), n=n, n_rows_a=n, want=("a",))[0]
+    preds = _Residuals(plan, tbl, None, eng).preds(plan.residuals)
+    if plan.range_sets:
+        # each set is one more predicate: the kernel's three-valued answer as a uint8 operand with its validity,
+        # kept where it is TRUE (``= 1``) or, under NOT, where it is FALSE (``= 0``); a NULL answer fails both
+        answers = _range_set_answers(plan, tbl, eng)
+        preds += [(("a", value, valid), "=", ("lit", 0 if rs.negated else 1), 0)
+                  for rs, (value, valid) in zip(plan.range_sets, answers)]
+    keep = eng.select(preds, n=n, n_rows_a=n, want=("a",))[0]
     if return_indices:
         return keep.cpu().numpy()
     is_arrow = isinstance(tbl, pa.Table)
@@ -1768,9 +1835,9 @@ def _execute_sharded(plan: JoinPlan, lt, rt, ia, ib, n_chrom, devices, return_in
 
 def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, return_indices=False,
             device_projection: bool = True, devices=None, outer_joins: bool = False, row_predicates: bool = False,
-            select_expressions: bool = False, merge_aggregates: bool = False):
+            select_expressions: bool = False, merge_aggregates: bool = False, range_sets: bool = False):
     """Run *plan* (a :class:`JoinPlan`, its string form, or a GIQL query string; ``outer_joins``,
-    ``row_predicates``, ``select_expressions`` and ``merge_aggregates`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
+    ``row_predicates``, ``select_expressions``, ``merge_aggregates`` and ``range_sets`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
     (``{name: pyarrow.Table | dict of arrays}``).
 
     Returns a ``pyarrow.Table`` with the plan's projected columns (bag semantics,
@@ -1792,7 +1859,7 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
     if isinstance(plan, str):
         plan = JoinPlan.from_string(plan) if is_plan_string(plan) else build_plan(
             plan, giql_tables, outer_joins=outer_joins, row_predicates=row_predicates,
-            select_expressions=select_expressions, merge_aggregates=merge_aggregates)
+            select_expressions=select_expressions, merge_aggregates=merge_aggregates, range_sets=range_sets)
     if not isinstance(plan, JoinPlan):
         raise ValueError("plan must be a JoinPlan, a plan string or a GIQL query")
     devices = [int(d) for d in devices] if devices is not None else None

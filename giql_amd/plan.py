@@ -110,6 +110,23 @@ class Having:
     group: int = 0  # conjuncts sharing a non-zero group are OR-ed (one clause of the normal form)
 
 
+#: the operators and quantifiers of a literal range set
+RANGE_OPS = ("intersects", "contains", "within")
+RANGE_QUANTIFIERS = ("any", "all")
+
+
+@dataclass(frozen=True)
+class RangeSet:
+    """``<genomic column> <op> ANY | ALL ('chr:lo-hi', ...)`` over a FILTER plan's table, or its negation
+    (docs/dialect/quantifiers.rst; src/giql/expanders/intersects.py:243-270): one term ``chrom = c AND <cmp on start>
+    AND <cmp on end>`` per range, OR-ed for ANY and AND-ed for ALL, in three-valued logic.  SOME is ANY."""
+
+    op: str                    # intersects | contains | within
+    quantifier: str            # any | all
+    negated: bool
+    ranges: tuple              # (chrom, start, end) per range, canonical 0-based half-open
+
+
 @dataclass(frozen=True)
 class JoinPlan:
     kind: str
@@ -159,6 +176,11 @@ class JoinPlan:
     # result row by HipEngine.eval_exprs; a Projection("expr", "<index>", name) refers to one.  Only plans lowered with
     # the ``select_expressions`` opt-in carry any; plan strings written before the field existed load with none
     expressions: tuple[Operand, ...] = field(default_factory=tuple)
+    # FILTER only: the literal range sets that HipEngine.range_set_any answers -- ANY over two or more ranges, or its
+    # negation -- each one more conjunct beside the residuals (a single literal, ANY over one range, ALL and their
+    # negations are folded into the residuals when the plan is lowered).  Only plans lowered with the ``range_sets``
+    # opt-in carry any; plan strings written before the field existed load with none
+    range_sets: tuple[RangeSet, ...] = field(default_factory=tuple)
 
     def __post_init__(self) -> None:
         if self.kind not in KINDS:
@@ -173,6 +195,11 @@ class JoinPlan:
             raise ValueError("predicate 'within_distance' needs an integer max_distance")
         if self.expressions and self.kind not in PAIR_KINDS:
             raise ValueError(f"computed columns need an INNER or LEFT plan, not {self.kind}")
+        if self.range_sets and self.kind != "FILTER":
+            raise ValueError(f"literal range sets need a FILTER plan, not {self.kind}")
+        for rs in self.range_sets:
+            if rs.op not in RANGE_OPS or rs.quantifier not in RANGE_QUANTIFIERS or not rs.ranges:
+                raise ValueError(f"bad range set {rs.op!r} {rs.quantifier!r} over {len(rs.ranges)} ranges")
         for p in self.projection:
             if p.side == "agg" and not (self.kind == "MERGE" and p.column.isdigit()
                                         and int(p.column) < len(self.aggregates)):
@@ -190,6 +217,8 @@ class JoinPlan:
         d["having"] = [asdict(h) for h in self.having]
         d["order_by"] = [list(o) for o in self.order_by]
         d["expressions"] = [asdict(e) for e in self.expressions]
+        d["range_sets"] = [{"op": r.op, "quantifier": r.quantifier, "negated": r.negated,
+                            "ranges": [list(t) for t in r.ranges]} for r in self.range_sets]
         return d
 
     def to_string(self) -> str:
@@ -221,7 +250,10 @@ class JoinPlan:
             order_by=tuple((o[0], bool(o[1]), bool(o[2]) if len(o) > 2 else not bool(o[1])) for o in d.get("order_by", ())),
             limit=d.get("limit"), offset=d.get("offset"), output=tuple(d.get("output", ())),
             predicate=d.get("predicate", "intersects"), row_predicates=d.get("row_predicates", False),
-            expressions=tuple(Operand(**e) for e in d.get("expressions", ())))
+            expressions=tuple(Operand(**e) for e in d.get("expressions", ())),
+            range_sets=tuple(RangeSet(r["op"], r["quantifier"], bool(r["negated"]),
+                                      tuple((str(c), int(lo), int(hi)) for c, lo, hi in r["ranges"]))
+                             for r in d.get("range_sets", ())))
 
 
 def is_plan_string(text) -> bool:

@@ -48,7 +48,8 @@ def decline(reason: str) -> HipDeclined:
 # ------------------------------------------------------- boolean conditions -> CNF
 # Both front ends hand a condition over as a tree -- ("leaf", term) | ("and", [nodes]) |
 # ("or", [nodes]) | ("not", node), a term being a spatial predicate (SPATIAL_TERMS: ("intersects", ...),
-# ("contains", ...), ("within", ...), or their literal-range forms ("intersects_lit", ...) ...)
+# ("contains", ...), ("within", ...), their literal-range forms ("intersects_lit", ...) ..., or -- from a parser with
+# the ``range_sets`` opt-in -- ("range_set", op, quantifier, ColRef, literals, negated))
 # or ("cmp", lhs, op, rhs) -- and get the terms of its conjunctive normal form back: the
 # select kernel evaluates an AND of ORs (include/giql_hip.h, giql_pred.group).  The
 # reference inlines such extras as SQL text (_classify_extras, intersects_duckdb.py:889-912).
@@ -111,6 +112,8 @@ def _nnf(node, neg: bool = False):
         if not neg:
             return node
         t = node[1]
+        if t[0] == "range_set":     # (only a parser with the ``range_sets`` opt-in builds this term: its last field flips)
+            return ("leaf", t[:-1] + (not t[-1],))
         if t[0] != "cmp":
             raise decline("NOT over a spatial predicate")
         return ("leaf", ("cmp", t[1], NEGATED_OP[t[2]], t[3]))

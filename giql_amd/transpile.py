@@ -49,6 +49,7 @@ from .shape import comparison_leaf as _comparison_leaf
 from .shape import holds_distance as _holds_distance
 from .shape import norm as _norm
 from .shape import table_side as _table_side
+from . import range_sets as _range_sets
 from .table import Table, Tables, build_tables, encoding_of
 
 
@@ -80,11 +81,21 @@ class Tok:
     quoted: bool = False
 
 
-def _tokenize(sql: str) -> list[Tok]:
+_COMMENT = re.compile(r"\s*--[^\n]*")
+
+
+def _tokenize(sql: str, comments: bool = False) -> list[Tok]:
+    """``comments``: ``-- ...`` to the end of its line is skipped (the documented examples of the quantifiers
+    annotate their ranges that way)."""
     out: list[Tok] = []
     pos = 0
     n = len(sql)
     while pos < n:
+        if comments:
+            c = _COMMENT.match(sql, pos)
+            if c:
+                pos = c.end()
+                continue
         m = _TOKEN.match(sql, pos)
         if not m:
             if sql[pos:].strip() == "":
@@ -110,8 +121,11 @@ def _tokenize(sql: str) -> list[Tok]:
 
 # ------------------------------------------------------------------- parser
 class _Parser:
-    def __init__(self, sql: str):
-        self.toks = _tokenize(sql)
+    def __init__(self, sql: str, range_sets: bool = False):
+        # ``range_sets`` (the opt-in of build_plan): literal ranges and ANY / SOME / ALL over them parse to
+        # ("range_set", ...) terms, and ``--`` comments are skipped
+        self.range_sets = bool(range_sets)
+        self.toks = _tokenize(sql, comments=self.range_sets)
         self.i = 0
 
     # -- token helpers
@@ -423,6 +437,34 @@ def _no_arithmetic(p: _Parser) -> None:
         raise _decline("arithmetic in a join condition")
 
 
+def _at_quantifier(p: _Parser) -> bool:
+    """``ANY(`` / ``ALL(`` / ``SOME(`` at the cursor of a parser with the ``range_sets`` opt-in."""
+    if not p.range_sets or not (p.peek(1).kind == "punct" and p.peek(1).text == "("):
+        return False
+    return p.at_kw("ANY", "ALL") or _at_word(p, "SOME")
+
+
+def _parse_range_term(p: _Parser, word: str, col: _ColRef):
+    """The right operand of INTERSECTS / CONTAINS / WITHIN for a parser with the ``range_sets`` opt-in: one literal,
+    or ``ANY | SOME | ALL ( 'literal' [, ...] )`` (src/giql/dialect.py:110-126: SOME is ANY) -> the term
+    ``("range_set", op, quantifier, ColRef, literals, negated)``."""
+    if p.peek().kind == "str":
+        return ("leaf", ("range_set", word.lower(), "any", col, (p.next().text,), False))
+    quantifier = p.next().text.upper()
+    p.expect_punct("(")
+    literals = []
+    while True:
+        if p.peek().kind != "str":
+            raise _decline(f"{word} {quantifier} over something other than literal ranges")
+        literals.append(p.next().text)
+        if p.at_punct(","):
+            p.next()
+            continue
+        break
+    p.expect_punct(")")
+    return ("leaf", ("range_set", word.lower(), "all" if quantifier == "ALL" else "any", col, tuple(literals), False))
+
+
 def _parse_predicate(p: _Parser, allow_literal: bool, operand=None):
     """One predicate -> a condition tree node (``shape.condition_terms``): ``<col> INTERSECTS
     <col | 'chr:lo-hi'>``, ``<operand> op <operand>``, ``[NOT] BETWEEN``, ``[NOT] IN (literals)``,
@@ -435,9 +477,11 @@ def _parse_predicate(p: _Parser, allow_literal: bool, operand=None):
         p.next()
         if lhs[0] != "col":
             raise _decline("INTERSECTS with a literal on the left")
-        if p.peek().kind == "str":
+        if p.peek().kind == "str" or _at_quantifier(p):
             if not allow_literal:
                 raise _decline("literal-range INTERSECTS inside a join")
+            if p.range_sets:
+                return _parse_range_term(p, "INTERSECTS", lhs[1])
             return ("leaf", ("intersects_lit", lhs[1], p.next().text))
         if p.at_kw("ANY", "ALL"):
             raise _decline("INTERSECTS ANY/ALL")
@@ -448,9 +492,11 @@ def _parse_predicate(p: _Parser, allow_literal: bool, operand=None):
         word = p.next().text.upper()
         if lhs[0] != "col":
             raise _decline(f"{word} with a literal on the left")
-        if p.peek().kind == "str":
+        if p.peek().kind == "str" or _at_quantifier(p):
             if not allow_literal:
                 raise _decline(f"literal-range {word} inside a join")
+            if p.range_sets:
+                return _parse_range_term(p, word, lhs[1])
             return ("leaf", (word.lower() + "_lit", lhs[1], p.next().text))
         if p.at_kw("ANY", "ALL"):
             raise _decline(f"{word} ANY/ALL")
@@ -792,7 +838,8 @@ _LITERAL_TERMS = {"intersects_lit": ("<", "hi", ">", "lo"),
 
 
 def _is_single_table_filter(p: _Parser) -> bool:
-    """``... FROM <one table> WHERE ...`` with a literal-range INTERSECTS and no join."""
+    """``... FROM <one table> WHERE ...`` with a literal-range INTERSECTS and no join (a parser with the ``range_sets``
+    opt-in: or a quantified set of literal ranges)."""
     depth = 0
     seen_from = False
     k = 0
@@ -807,8 +854,15 @@ def _is_single_table_filter(p: _Parser) -> bool:
             elif seen_from and t.text in ("JOIN", "LATERAL"):
                 return False
             elif seen_from and t.text == "WHERE":
-                return any(a.kind == "kw" and a.text in ("INTERSECTS", "CONTAINS", "WITHIN") and b.kind == "str"
-                           for a, b in zip(toks[k:], toks[k + 1:]))
+                def ranges(b: Tok, c: Tok) -> bool:   # a literal; with the opt-in also ANY( / SOME( / ALL(
+                    if b.kind == "str":
+                        return True
+                    quantifier = (b.kind == "kw" and b.text in ("ANY", "ALL")) or \
+                        (b.kind == "id" and not b.quoted and b.text.upper() == "SOME")
+                    return p.range_sets and quantifier and c.kind == "punct" and c.text == "("
+
+                return any(a.kind == "kw" and a.text in ("INTERSECTS", "CONTAINS", "WITHIN") and ranges(b, c)
+                           for a, b, c in zip(toks[k:], toks[k + 1:], toks[k + 2:] + [toks[-1]]))
         if depth == 0 and seen_from and t.kind == "punct" and t.text == ",":
             return False
         k += 1
@@ -853,14 +907,29 @@ def _lower_filter(p: _Parser, tbls: Tables) -> JoinPlan:
         raise _decline(f"trailing input near {p.peek().text!r}")
     side = _table_side(ref_t, tbls)
     table = tbls.get(ref_t.name) or Table(ref_t.name)
-    lits = [t for t in terms if t[0] in _LITERAL_TERMS]
-    if len(lits) != 1 or any(t[0] in SPATIAL_TERMS for t in terms):
-        raise _decline("more than one spatial predicate")
 
     def own(refc: _ColRef) -> str:
         if refc.table is not None and _norm(refc.table, refc.table_quoted) != side.alias:
             raise ValueError(f"Unknown table qualifier {refc.table!r}; expected {side.alias!r}")
         return refc.column
+
+    def projection() -> tuple:
+        proj = []
+        for refc, alias in items:
+            if refc.star:
+                if refc.table:
+                    own(refc)
+                proj.append(Projection("star", "*", "*"))
+            else:
+                proj.append(Projection("l", own(refc), alias or refc.column))
+        return tuple(proj)
+
+    if p.range_sets:
+        residuals, sets = _range_set_conjuncts(terms, side, table, ref_t, own)
+        return JoinPlan("FILTER", side, None, projection(), residuals=tuple(residuals), range_sets=tuple(sets))
+    lits = [t for t in terms if t[0] in _LITERAL_TERMS]
+    if len(lits) != 1 or any(t[0] in SPATIAL_TERMS for t in terms):
+        raise _decline("more than one spatial predicate")
 
     lit_kind, col, text = lits[0]
     if own(col) != table.genomic_col:
@@ -881,15 +950,47 @@ def _lower_filter(p: _Parser, tbls: Tables) -> JoinPlan:
                  Residual("where", Operand("l", side.start_col), start_op, Operand("int", bound[start_v])),
                  Residual("where", Operand("l", side.end_col), end_op, Operand("int", bound[end_v]))]
     residuals += _own_table_residuals([t for t in terms if t[0] in ("cmp", "or")], own)
-    proj = []
-    for refc, alias in items:
-        if refc.star:
-            if refc.table:
-                own(refc)
-            proj.append(Projection("star", "*", "*"))
+    return JoinPlan("FILTER", side, None, projection(), residuals=tuple(residuals))
+
+
+#: predicates of one select call (``SEL_MAX_PREDS``, include/giql_hip.h); a range set the kernel answers is one of them
+_FILTER_MAX_PREDS = 16
+
+
+def _range_set_conjuncts(terms, side: PlanSide, table, ref_t: _TableRef, own) -> tuple:
+    """The WHERE conjuncts of a filter lowered with the ``range_sets`` opt-in -> ``(residuals, range sets)``: the
+    comparisons and OR-groups as they are, every literal / quantified predicate folded into residuals where it is a
+    conjunction of comparisons (``range_sets.fold``), the rest -- ANY over two or more ranges -- as the plan's
+    ``range_sets``."""
+    if any(t[0] in SPATIAL_TERMS for t in terms):
+        raise _decline("column-to-column spatial predicate over one table")
+    own_residuals = _own_table_residuals([t for t in terms if t[0] in ("cmp", "or")], own)
+    group = max([r.group for r in own_residuals], default=0)
+    plain, negated_groups, sets = [], [], []   # (the order of a single literal's plan: its comparisons, then the query's)
+    for t in terms:
+        if t[0] != "range_set":
+            continue
+        _, op, quantifier, col, literals, negated = t
+        if own(col) != table.genomic_col:
+            raise ValueError(f"{col.column!r} is not the genomic column of {ref_t.name}")
+        rs = _range_sets.make_set(op, quantifier, negated, literals)
+        if len(rs.ranges) > _range_sets.MAX_SET_RANGES and _range_sets.needs_kernel(rs):
+            raise _decline(f"more than {_range_sets.MAX_SET_RANGES} ranges in one ANY(...) set (load them into a table "
+                           "and use a SEMI JOIN)")
+        if _range_sets.needs_kernel(rs):
+            sets.append(rs)
+        elif rs.negated:
+            group += 1
+            negated_groups += _range_sets.fold(rs, side, group)
         else:
-            proj.append(Projection("l", own(refc), alias or refc.column))
-    return JoinPlan("FILTER", side, None, tuple(proj), residuals=tuple(residuals))
+            plain += _range_sets.fold(rs, side, 0)
+    residuals = plain + own_residuals + negated_groups
+    if len(sets) > _range_sets.MAX_KERNEL_SETS:
+        raise _decline(f"more than {_range_sets.MAX_KERNEL_SETS} ANY(...) sets of two or more ranges in one WHERE")
+    if len(residuals) + len(sets) > _FILTER_MAX_PREDS:
+        raise _decline(f"a range-set filter that needs more than {_FILTER_MAX_PREDS} predicates "
+                       f"({len(residuals)} comparisons and {len(sets)} sets)")
+    return residuals, sets
 
 
 def _has_cluster_or_merge(p: _Parser) -> bool:
@@ -1267,7 +1368,7 @@ def _lower_disjoin(p: _Parser, tbls: Tables) -> JoinPlan:
 
 
 def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predicates: bool = False,
-               select_expressions: bool = False, merge_aggregates: bool = False) -> JoinPlan:
+               select_expressions: bool = False, merge_aggregates: bool = False, range_sets: bool = False) -> JoinPlan:
     """Parse *giql* and lower the INTERSECTS / NEAREST join (or a CLUSTER / MERGE
     query) to a :class:`JoinPlan`.
 
@@ -1279,8 +1380,12 @@ def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predica
     over columns and literals, LEAST / GREATEST / ABS, a searched CASE, each with an alias (bedtools -wo / -wao:
     ``LEAST(a.end, b.end) - GREATEST(a.start, b.start) AS overlap_bp``) -- instead of declining them.
     ``merge_aggregates=True`` opts in to ``COUNT(col)`` / ``SUM`` / ``AVG`` / ``MIN`` / ``MAX`` of a table column
-    beside MERGE, each with an alias (bedtools ``merge -c 5 -o mean``: ``MERGE(interval), AVG(score) AS avg_score``)."""
-    probe = _Parser(giql)
+    beside MERGE, each with an alias (bedtools ``merge -c 5 -o mean``: ``MERGE(interval), AVG(score) AS avg_score``).
+    ``range_sets=True`` opts in to the quantified literal ranges of a single-table filter -- ``interval INTERSECTS |
+    CONTAINS | WITHIN ANY(...)`` / ``SOME(...)`` / ``ALL(...)``, a ``NOT`` in front of such a predicate or of a single
+    literal, several of them joined by AND -- with every literal format of the reference's parser and over a table of
+    any coordinate encoding (docs/dialect/quantifiers.rst); inside a join such a predicate declines as before."""
+    probe = _Parser(giql, range_sets=bool(range_sets))
     tbls = tables if isinstance(tables, Tables) else build_tables(tables)
     for routed, lower, what in ((_disjoin_from(probe) is not None, _lower_disjoin, "DISJOIN"),
                                 (probe.at_kw("SELECT") and _has_cluster_or_merge(probe), _lower_cluster, "CLUSTER / MERGE"),
@@ -1495,20 +1600,22 @@ def _render(toks: list[Tok]) -> str:
 
 def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins: bool = False,
               row_predicates: bool = False, select_expressions: bool = False,
-              merge_aggregates: bool = False) -> str:
+              merge_aggregates: bool = False, range_sets: bool = False) -> str:
     """Mirror of ``giql.transpile`` for this backend's path.
 
     ``dialect="hip"``: returns the plan string of the INTERSECTS / NEAREST join
     (hand it to :func:`giql_amd.execute`); ``outer_joins=True`` lets a LEFT [OUTER] JOIN lower too
     and ``row_predicates=True`` the per-row joins over CONTAINS / WITHIN / DISTANCE, ``select_expressions=True``
     computed columns such as ``overlap_bp`` in the SELECT list, ``merge_aggregates=True`` SUM / AVG / MIN / MAX /
-    COUNT(col) beside MERGE (:func:`build_plan`).  ``dialect=None``: returns SQL for the
+    COUNT(col) beside MERGE, ``range_sets=True`` ANY / SOME / ALL over literal ranges and NOT over a literal predicate
+    in a single-table filter (:func:`build_plan`).  ``dialect=None``: returns SQL for the
     literal-range predicate (plumbing, BASELINE config 1).  Other dialects belong to
     the reference package.
     """
     if dialect == "hip":
         return build_plan(giql, tables, outer_joins=outer_joins, row_predicates=row_predicates,
-                          select_expressions=select_expressions, merge_aggregates=merge_aggregates).to_string()
+                          select_expressions=select_expressions, merge_aggregates=merge_aggregates,
+                          range_sets=range_sets).to_string()
     if dialect is None:
         return _lower(giql, tables, want_sql=True)
     raise ValueError(
