@@ -42,6 +42,7 @@
 #include "index_nearest_kernels.hip.h"
 #include "host_pool.h"
 #include "plan_expand.h"
+#include "zero_ledger.h"
 
 using namespace giql;
 
@@ -90,8 +91,10 @@ constexpr int FILL_ITEMS_C2 = GIQL_FILL_ITEMS;  // pairs per thread of a fill bl
 #define GIQL_STREAM_GRID 16384u
 #endif
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline u32 cdiv(u64 a, u64 b) { return (u32)((a + b - 1) / b); }
+// a side's digit histogram replicas / the span pass's per-chromosome top-digit counts, as their owners zero them
+constexpr size_t HIST_BYTES = (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32);
+constexpr size_t TOP_BYTES = (size_t)LIN_HIST_REPLICAS * MM_TOP_WORDS * sizeof(u32);
 
 // ----------------------------------------------------------------- context
 struct SortBufs {
@@ -186,11 +189,10 @@ struct Guesses {
 // stats (and so of every attempt with_order_fallback repeats).  The values giql_hip_get_stats reports stay until
 // the next such call.
 struct CallState {
-  bool prezeroed = false;       // the call zeroed its histograms and status words in ONE memset up front
+  ZeroLedger zeroed;            // the bytes of the workspace this attempt zeroed in ONE memset up front (zero_ledger.h)
   // a sort's FIRST pass may rank its rows with LDS atomics (unstable: rows of equal digits in any order) when the caller
   // does not need equal keys in input order -- the INNER join's sides (onesweep.hip.h)
   bool first_unstable = false;
-  u32* span_hist_dirty[2] = {nullptr, nullptr};  // histograms the span pass counted into (a side that is linearized after all must zero its own again)
   int force_local = 0;          // +1 while a table index is built: the three-stage sort whatever the guesses say; -1: global passes only
   int index_bits = 16;          // the width of the index being built (force_local > 0)
   bool used_sorted[2] = {false, false};  // the call skipped that side's sort
@@ -311,18 +313,6 @@ struct giql_hip_ctx {
   giql_hip_stats stats;
 };
 
-struct Carver {
-  char* base;
-  size_t off = 0;
-  template <typename T>
-  T* take(size_t n) {
-    off = align_up(off, 256);
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += n * sizeof(T);
-    return p;
-  }
-};
-
 static int ensure_arena(giql_hip_ctx* ctx, size_t bytes, hipStream_t stream) {
   if (bytes <= ctx->arena.bytes()) return GIQL_OK;
   ctx->kept = Plan::NONE;  // (giql_hip_reserve: a new arena holds no plan)
@@ -418,14 +408,32 @@ static int check_rows_fit(size_t na, size_t nb) {
   return GIQL_OK;
 }
 
-// Clears the prezeroed state (and the unstable first pass that goes with the INNER plan's) when a call's frame ends:
-// the sort helpers zero their own histograms and status words again.
-struct PrezeroGuard {
+// The frame of a call that zeroes workspace up front (zero_span): when it ends nothing is known to be zero any more,
+// and the sort helpers zero their own histograms and status words again.
+struct ZeroedScope {
   giql_hip_ctx* c;
-  ~PrezeroGuard() {
-    c->call.prezeroed = false;
-    c->call.first_unstable = false;
-  }
+  ~ZeroedScope() { c->call.zeroed.reset(); }
+};
+
+// What a helper does with a buffer that has to start at zero: skip the memset where the ledger hands the buffer over.
+static int take_zeroed(giql_hip_ctx* ctx, hipStream_t st, void* p, size_t bytes) {
+  if (!ctx->call.zeroed.take(p, bytes)) HIP_TRY(hipMemsetAsync(p, 0, bytes, st));
+  return GIQL_OK;
+}
+
+// The one place that zeroes workspace up front: the memset, then the ledger's record of it.
+static int zero_span(giql_hip_ctx* ctx, hipStream_t st, ZeroSpan s) {
+  if (s.end <= s.off) return GIQL_OK;
+  HIP_TRY(hipMemsetAsync(ctx->arena + s.off, 0, s.end - s.off, st));
+  ctx->call.zeroed.add(ctx->arena + s.off, s.end - s.off);
+  return GIQL_OK;
+}
+
+// A sort's first pass may rank by LDS atomics for a scope (CallState::first_unstable).
+struct UnstableFirstPass {
+  giql_hip_ctx* c;
+  explicit UnstableFirstPass(giql_hip_ctx* ctx) : c(ctx) { c->call.first_unstable = true; }
+  ~UnstableFirstPass() { c->call.first_unstable = false; }
 };
 
 // The three-stage sort forced on (+1: an index build) or off (-1: an indexed join's query side) for a scope.
@@ -584,11 +592,19 @@ static int run_spans(giql_hip_ctx* ctx, hipStream_t st, const giql_side& a, cons
                      int n_chrom, const LinBufs& lb, int hist_side = -1, u32* hist_partial = nullptr, int pad = 0) {
   const bool hist = hist_side >= 0 && hist_partial && lb.abase && lb.top_partial &&
                     n_chrom <= MM_HIST_CHROMS && (hist_side ? b.n : a.n) > 0;
-  // both sides count their digits (lb.hist_partial2 / top_partial2 for the other one; prezeroed plans only)
-  const bool hist2 = hist && lb.hist_partial2 && lb.top_partial2 && ctx->call.prezeroed && (hist_side ? a.n : b.n) > 0;
-  if (hist && !ctx->call.prezeroed) {
-    HIP_TRY(hipMemsetAsync(hist_partial, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
-    HIP_TRY(hipMemsetAsync(lb.top_partial, 0, (size_t)LIN_HIST_REPLICAS * MM_TOP_WORDS * sizeof(u32), st));
+  // both sides count their digits (lb.hist_partial2 / top_partial2 for the other one: only where they were zeroed
+  // up front, there is no memset for them here)
+  const ZeroLedger& zeroed = ctx->call.zeroed;
+  const bool hist2 = hist && lb.hist_partial2 && lb.top_partial2 && (hist_side ? a.n : b.n) > 0 &&
+                     zeroed.covers(lb.hist_partial2, HIST_BYTES) && zeroed.covers(lb.top_partial2, TOP_BYTES);
+  // (the span pass takes every histogram it counts into: a side that is linearized after all finds its own taken)
+  if (hist) {
+    GIQL_TRY(take_zeroed(ctx, st, hist_partial, HIST_BYTES));
+    GIQL_TRY(take_zeroed(ctx, st, lb.top_partial, TOP_BYTES));
+  }
+  if (hist2) {
+    GIQL_TRY(take_zeroed(ctx, st, lb.hist_partial2, HIST_BYTES));
+    GIQL_TRY(take_zeroed(ctx, st, lb.top_partial2, TOP_BYTES));
   }
   Phase ph(ctx, st, GIQL_PH_SPAN, 4);
   hipLaunchKernelGGL(k_init_minmax, dim3(cdiv((u64)n_chrom + 1, 256)), dim3(256), 0, st, lb.gmin,
@@ -604,7 +620,6 @@ static int run_spans(giql_hip_ctx* ctx, hipStream_t st, const giql_side& a, cons
       const giql_side& s = *sides[k];
       const bool with_hist = hist && (k == hist_side || hist2);
       u32* const hp = k == hist_side ? hist_partial : lb.hist_partial2;
-      if (with_hist) ctx->call.span_hist_dirty[k] = hp;
       u32 grid = (u32)((double)MM_MAX_BLOCKS * (double)s.n / tot + 0.5);
       const u32 need = cdiv((u64)s.n, (u64)MM_NT_HIST * 4);   // a block per tile at most
       if (grid > need) grid = need;
@@ -630,7 +645,6 @@ static int run_spans(giql_hip_ctx* ctx, hipStream_t st, const giql_side& a, cons
     if (s.n == 0) continue;
     const bool with_hist = hist && (k == hist_side || hist2);
     u32* const hp = k == hist_side ? hist_partial : lb.hist_partial2;
-    if (with_hist) ctx->call.span_hist_dirty[k] = hp;
     u32* const tp = k == hist_side ? lb.top_partial : lb.top_partial2;
     u32 grid = cdiv((u64)s.n, (u64)(with_hist ? MM_NT_HIST : MM_NT) * MM_ITEMS);
     if (grid > (u32)MM_MAX_BLOCKS) grid = MM_MAX_BLOCKS;
@@ -664,17 +678,9 @@ static int run_linearize(giql_hip_ctx* ctx, hipStream_t st, const giql_side& s, 
   if (s.n == 0) return GIQL_OK;
   const int* end_col = skip_end ? (const int*)nullptr : s.end;  // a side known to hold no irregular row
   // (a plan zeroes its histograms once, up front -- but this one may hold the span pass's counts of a side that
-  // turned out to need the linearize pass after all: layout or form guess not taken)
-  bool dirty = false;
-  for (int k = 0; k < 2; k++)
-    if (hist_partial && ctx->call.span_hist_dirty[k] == hist_partial) {
-      dirty = true;
-      ctx->call.span_hist_dirty[k] = nullptr;
-    }
-  if (hist_partial && (!ctx->call.prezeroed || dirty))
-    HIP_TRY(hipMemsetAsync(hist_partial, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
-  if (hist_end && !ctx->call.prezeroed)
-    HIP_TRY(hipMemsetAsync(hist_end, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
+  // turned out to need the linearize pass after all, layout or form guess not taken: the span pass took it then)
+  if (hist_partial) GIQL_TRY(take_zeroed(ctx, st, hist_partial, HIST_BYTES));
+  if (hist_end) GIQL_TRY(take_zeroed(ctx, st, hist_end, HIST_BYTES));
   Phase ph(ctx, st, GIQL_PH_LINEARIZE, hist_partial ? 2 : 1);
   u32 grid = cdiv((u64)s.n, LIN_NT);
   if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
@@ -895,7 +901,7 @@ static int run_sort_onesweep(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u3
   const int n_pass = local ? local_passes(wbits) : 4 - skip_digits;
   const int first_digit = local ? 4 - n_pass : skip_digits;
   const size_t per_pass = os_pass_stride(ctx, n);
-  if (!ctx->call.prezeroed) HIP_TRY(hipMemsetAsync(status, 0, n_pass * per_pass * sizeof(u32), st));
+  GIQL_TRY(take_zeroed(ctx, st, status, n_pass * per_pass * sizeof(u32)));
   {
     // one event pair around the passes (an event record between two launches costs the
     // stream ~8 us of idle time; the per-launch time is phase time / launches)
@@ -1425,10 +1431,7 @@ struct InnerScratch {
   u32 *hist[2] = {nullptr, nullptr}, *gbase[2] = {nullptr, nullptr};  // [label]
   u32 *os_status = nullptr, *os_status2 = nullptr;  // status words: the larger side's, the smaller side's
   u64 *bsums = nullptr, *bsums1 = nullptr, *scan_chain = nullptr;
-  // arena offsets of the region zeroed up front ([zero_off, zero_end + the larger side's status words)), and how many
-  // passes of those status words are zeroed so far (zero_inner_scratch)
-  size_t zero_off = 0, zero_end = 0;
-  int big_passes_zeroed = 0;
+  ZeroSpan zero;  // what is zeroed up front, less the larger side's status words that follow it (zero_inner_scratch)
 };
 
 // What ONE attempt at a plan assumed.  begin_attempt fills the upper part right after the span pass; the forms add the
@@ -1504,8 +1507,7 @@ static size_t carve_inner(giql_hip_ctx* ctx, char* base, size_t na, size_t nb, i
   if (onesweep) {
     // everything that has to start at zero lies back to back, the larger side's status words last: ONE memset
     // up front instead of one per histogram and per sort (5 launches of ~5 us at the headline sizes)
-    c.off = align_up(c.off, 256);
-    W.zero_off = c.off;
+    c.open_zeroed();
     W.hist[0] = c.take<u32>((size_t)LIN_HIST_REPLICAS * 1024);
     W.hist[1] = c.take<u32>((size_t)LIN_HIST_REPLICAS * 1024);
     W.lb.top_partial = c.take<u32>((size_t)LIN_HIST_REPLICAS * MM_TOP_WORDS);
@@ -1514,8 +1516,7 @@ static size_t carve_inner(giql_hip_ctx* ctx, char* base, size_t na, size_t nb, i
     W.gbase[1] = c.take<u32>(1024);
     W.lb.abase = c.take<u32>(MM_HIST_CHROMS);
     W.os_status2 = c.take<u32>(4 * os_pass_words(na < nb ? na : nb));  // the smaller side's
-    c.off = align_up(c.off, 256);
-    W.zero_end = c.off;
+    W.zero = c.close_zeroed();
     W.os_status = c.take<u32>(4 * os_pass_words(n_max));               // the larger side's
   } else {
     W.tile_hist = c.take<u32>(n_tiles_max * RS_BINS);
@@ -1542,24 +1543,15 @@ static size_t carve_inner(giql_hip_ctx* ctx, char* base, size_t na, size_t nb, i
 }
 
 // The one place that knows how many passes of the larger side's status words are zeroed.  First call: the whole zero
-// region in ONE memset (the larger side takes at most 4 passes, 2 or 3 in the three-stage form).  Later calls: the
-// larger side turned out to take more global passes than expected (the density is known now): those need zeroed
-// status words too.
-static int zero_inner_scratch(giql_hip_ctx* ctx, hipStream_t st, InnerScratch& W, size_t n_max) {
+// span and those passes in ONE memset (the larger side takes at most 4 passes, 2 or 3 in the three-stage form).  Later
+// calls: the larger side turned out to take more global passes than expected (the density is known now): those need
+// zeroed status words too, and the zeroed range grows by them.
+static int zero_inner_scratch(giql_hip_ctx* ctx, hipStream_t st, const InnerScratch& W, size_t n_max) {
   const int passes = sort_is_local(ctx, n_max) ? local_passes(sort_local_bits(ctx, n_max)) : 4;
-  const size_t stride = os_pass_stride(ctx, n_max);
-  if (W.big_passes_zeroed == 0) {
-    HIP_TRY(hipMemsetAsync(ctx->arena + W.zero_off, 0,
-                           (W.zero_end - W.zero_off) + (size_t)passes * stride * sizeof(u32), st));
-    ctx->call.prezeroed = true;
-  } else if (W.big_passes_zeroed < passes) {
-    HIP_TRY(hipMemsetAsync(W.os_status + (size_t)W.big_passes_zeroed * stride, 0,
-                           (size_t)(passes - W.big_passes_zeroed) * stride * sizeof(u32), st));
-  } else {
-    return GIQL_OK;
-  }
-  W.big_passes_zeroed = passes;
-  return GIQL_OK;
+  const size_t want = W.zero.end + (size_t)passes * os_pass_stride(ctx, n_max) * sizeof(u32);  // (os_status starts at zero.end)
+  const char* const arena = ctx->arena;
+  const char* const have = ctx->call.zeroed.end();  // (nothing to do when the range reaches that far already)
+  return zero_span(ctx, st, {have ? (size_t)(have - arena) : W.zero.off, want});
 }
 
 // (the smaller side's passes use the smaller status buffer: both were zeroed up front, neither is reused; of two
@@ -2074,8 +2066,8 @@ static int inner_plan_core(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
   A.out_row = ctx->plan.swapped ? ctx->plan.fuse_b : ctx->plan.fuse_a;
   B.out_row = ctx->plan.swapped ? ctx->plan.fuse_a : ctx->plan.fuse_b;
 
-  PrezeroGuard prezero_guard{ctx};  // the helpers skip their own memsets while this plan runs
-  ctx->call.first_unstable = true;  // an INNER join needs no order among rows of equal keys: first passes rank by LDS atomics
+  ZeroedScope zeroed_scope{ctx};  // the helpers skip their own memsets on what zero_inner_scratch zeroes
+  UnstableFirstPass unstable_first{ctx};  // an INNER join needs no order among rows of equal keys: first passes rank by LDS atomics
   if (T.onesweep) GIQL_TRY(zero_inner_scratch(ctx, st, W, na > nb ? na : nb));
 
   GIQL_TRY(begin_attempt(ctx, st, A, B, n_chrom, W, T));
@@ -2496,33 +2488,30 @@ int giql_hip_index_create_dev(giql_hip_ctx* ctx, const giql_side* side, int32_t 
   LinBufs lb;
   SortBufs scratch;  // buffer 1 of the sort (buffer 0 = the index's own arrays)
   u32 *hist = nullptr, *gbase = nullptr, *status = nullptr;
-  size_t zero_off = 0, zero_end = 0;
+  ZeroSpan zero;
   auto carve = [&](char* base) {
     Carver c{base};
     common_sizes(c, n_chrom, lb);
     scratch.key[1] = c.take<u32>(n);
     scratch.end[1] = c.take<u32>(n);
     scratch.rid[1] = c.take<u32>(n);
-    c.off = align_up(c.off, 256);
-    zero_off = c.off;
+    c.open_zeroed();
     hist = c.take<u32>((size_t)LIN_HIST_REPLICAS * 1024);
     lb.top_partial = c.take<u32>((size_t)LIN_HIST_REPLICAS * MM_TOP_WORDS);
     gbase = c.take<u32>(1024);
     lb.abase = c.take<u32>(MM_HIST_CHROMS);
     status = c.take<u32>(3 * os_pass_words(n));
-    c.off = align_up(c.off, 256);
-    zero_end = c.off;
+    zero = c.close_zeroed();
     return c.off;
   };
   GIQL_TRY(claim_arena(ctx, st, carve));
   std::unique_ptr<giql_hip_index> idx(new (std::nothrow) giql_hip_index());  // released on every early way out
   if (!idx) return set_err(GIQL_ERR_NOMEM, "out of host memory");
-  PrezeroGuard prezero_guard{ctx};
+  ZeroedScope zeroed_scope{ctx};
   idx->device = ctx->device;
   idx->n = (u32)n;
   idx->n_chrom = n_chrom;
-  HIP_TRY(hipMemsetAsync(ctx->arena + zero_off, 0, zero_end - zero_off, st));
-  ctx->call.prezeroed = true;
+  GIQL_TRY(zero_span(ctx, st, zero));
   ForceLocal force_local{ctx, 1};
   ctx->call.index_bits = 15;  // (not 16: the span pass counts the bits 8-15 digit too -- the density is not known yet)
   giql_side none = *side;
@@ -2606,27 +2595,24 @@ int giql_hip_inner_join_indexed_dev(giql_hip_ctx* ctx, const giql_hip_index* idx
   if (na > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "side larger than 2^30 rows");
   SortBufs sa, sq;  // a's sort; buffer 1 of the index side (only a queued bucket's block ever touches it)
   u32 *hist = nullptr, *gbase = nullptr, *status = nullptr, *flags = nullptr;
-  size_t zero_off = 0, zero_end = 0;
+  ZeroSpan zero;
   auto carve = [&](char* base) {
     Carver c{base};
     sort_sizes(c, na, sa, true);
     sq.key[1] = c.take<u32>(nb);
     sq.rid[1] = c.take<u32>(nb);
     sq.end[1] = idx->general ? c.take<u32>(nb) : nullptr;
-    c.off = align_up(c.off, 256);
-    zero_off = c.off;
+    c.open_zeroed();
     hist = c.take<u32>((size_t)LIN_HIST_REPLICAS * 1024);
     gbase = c.take<u32>(1024);
     flags = c.take<u32>(64);
     status = c.take<u32>(4 * os_pass_words(na));
-    c.off = align_up(c.off, 256);
-    zero_end = c.off;
+    zero = c.close_zeroed();
     return c.off;
   };
   GIQL_TRY(claim_arena(ctx, st, carve));
-  PrezeroGuard prezero_guard{ctx};
-  HIP_TRY(hipMemsetAsync(ctx->arena + zero_off, 0, zero_end - zero_off, st));
-  ctx->call.prezeroed = true;
+  ZeroedScope zeroed_scope{ctx};
+  GIQL_TRY(zero_span(ctx, st, zero));
   const u32* first = idx->small + 1024;
   u32* const dead = flags;           // rows of a that cannot match (sorted last, skipped by the windows)
   u32* const irregular = flags + 1;
@@ -3018,11 +3004,13 @@ struct OsScratch {
   u32* status = nullptr;
 };
 
-static void os_scratch_sizes(Carver& c, size_t n_max, OsScratch& o) {
+// zero_upto_status: closes the carve's zeroed span where the status words begin (os_pair_sizes)
+static void os_scratch_sizes(Carver& c, size_t n_max, OsScratch& o, ZeroSpan* zero_upto_status = nullptr) {
   o.hist = c.take<u32>((size_t)LIN_HIST_REPLICAS * 1024);
   o.hist_e = c.take<u32>((size_t)LIN_HIST_REPLICAS * 1024);
   o.gbase = c.take<u32>(1024);
   o.gbase_e = c.take<u32>(1024);
+  if (zero_upto_status) *zero_upto_status = c.close_zeroed();
   o.status = c.take<u32>(4 * os_pass_words(n_max));
 }
 
@@ -3030,17 +3018,13 @@ static void os_scratch_sizes(Carver& c, size_t n_max, OsScratch& o) {
 // range of the workspace that only os_pair_sizes lays out.
 struct OsScratchPair {
   OsScratch a, b;
+  ZeroSpan zero;  // from a's histograms to where b's status words begin (os_pair_sizes)
   // ONE memset for everything the two sides' histograms and sort passes need at zero, instead of one per histogram and
-  // per sort (four launches of ~5 us on a path of ~60): from a's histograms to the end of b's four passes of status
-  // words for n_b rows.  Only for calls that sort each side ONCE (a second sort through the same status words must
-  // zero them again: ctx->call.prezeroed makes the helpers skip theirs).
+  // per sort (four launches of ~5 us on a path of ~60): the span and b's four passes of status words for n_b rows.
+  // It pays for calls that sort each side ONCE: a second sort through the same status words finds them taken and
+  // zeroes them again.
   int prezero(giql_hip_ctx* ctx, hipStream_t st, size_t n_b) const {
-    char* const lo = reinterpret_cast<char*>(a.hist);
-    char* const hi = reinterpret_cast<char*>(b.status + 4 * os_pass_stride(ctx, n_b));
-    if (!a.hist || hi <= lo) return GIQL_OK;
-    HIP_TRY(hipMemsetAsync(lo, 0, (size_t)(hi - lo), st));
-    ctx->call.prezeroed = true;
-    return GIQL_OK;
+    return zero_span(ctx, st, {zero.off, zero.end + 4 * os_pass_stride(ctx, n_b) * sizeof(u32)});
   }
 };
 
@@ -3051,9 +3035,10 @@ struct ExtraWords {
   size_t n;
 };
 static void os_pair_sizes(Carver& c, size_t na, size_t nb, OsScratchPair& o, std::initializer_list<ExtraWords> inside = {}) {
+  c.open_zeroed();
   os_scratch_sizes(c, na, o.a);
   for (const ExtraWords& x : inside) *x.at = c.take<u32>(x.n);
-  os_scratch_sizes(c, nb, o.b);
+  os_scratch_sizes(c, nb, o.b, &o.zero);
 }
 
 // The tail of SEMI / ANTI: the flags compacted to ascending row ids with the count straight into DevMeta::n_out (three
@@ -3099,7 +3084,7 @@ static int giql_hip_semi_anti_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
     return c.off;
   };
   GIQL_TRY(claim_arena(ctx, st, carve));
-  PrezeroGuard prezero_guard{ctx};
+  ZeroedScope zeroed_scope{ctx};
   GIQL_TRY(osp.prezero(ctx, st, nb ? nb : 1));  // each side is sorted once, in either form
 
   GIQL_TRY(run_spans(ctx, st, *a, *b, nch, lb));
@@ -3199,8 +3184,10 @@ static int giql_hip_count_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const 
   bool speculated = false;
   GIQL_TRY(row_form_guess(ctx, st, uni_len, speculated));
   const bool coarse_b = uni_len > 0 && coarse_b_ok(ctx, nb);
-  PrezeroGuard prezero_guard{ctx};
-  if (uni_len > 0) GIQL_TRY(osp.prezero(ctx, st, nb));  // (the general form sorts B twice through one set of status words)
+  ZeroedScope zeroed_scope{ctx};
+  // (a choice of speed: the general form sorts B twice through one set of status words, and its second sort would
+  // find them taken and zero them itself all the same)
+  if (uni_len > 0) GIQL_TRY(osp.prezero(ctx, st, nb));
   {
     SideChain sc(ctx, st, na);
     GIQL_TRY(run_linearize(ctx, sc.stream(), *a, n_chrom, lb, sa.key[0], sa.end[0], irr_a_list, 0, 0, os_a.hist,
@@ -3298,15 +3285,16 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
   GIQL_TRY(claim_arena(ctx, st, carve));
 
   const bool two_sorts = ctx->guess.nearest_two_sorts;
-  PrezeroGuard prezero_guard{ctx};
-  if (!two_sorts) GIQL_TRY(osp.prezero(ctx, st, nb));  // (the two-sort plan reuses B's status words)
+  ZeroedScope zeroed_scope{ctx};
+  // (a choice of speed: the two-sort plan reuses B's status words, its second sort would zero them itself all the same)
+  if (!two_sorts) GIQL_TRY(osp.prezero(ctx, st, nb));
   // Both sides sorted from their raw columns (round 3): with every chromosome base a multiple of 2^24 the span pass
   // counts the digits of the keys itself (k_chrom_minmax<1>, "Histogram in the span pass"), and the first sort pass
   // of each side builds key and end key from (chrom, start, end) -- no linearize pass (2 x 49 us at 10M x 10M against
   // ~2 x 22 more in the span pass and the first sort pass).  Every NEAREST row keeps its real key, zero-length rows
   // included, so the only guess is the layout: taken when the previous call's data took it, validated at the
   // read-back; a first call probes it (digits counted for B only) and sorts the ordinary way.
-  const bool hist_ok = !two_sorts && ctx->call.prezeroed && !ctx->sw.no_span_hist && ctx->sw.os_variant == 0 &&
+  const bool hist_ok = !two_sorts && ctx->call.zeroed.covers(os.hist, HIST_BYTES) && !ctx->sw.no_span_hist && ctx->sw.os_variant == 0 &&
                        n_chrom <= MM_HIST_CHROMS && !sort_is_local(ctx, na) && !sort_is_local(ctx, nb);
   const bool keygen = hist_ok && ctx->guess.nearest_aligned == 1;
   const bool probe = hist_ok && ctx->guess.nearest_aligned == -1;
