@@ -59,6 +59,9 @@ SYMBOLS = [
 #: every symbol include/giql_hip_range_sets.h declares (the extension header beside giql_hip.h)
 RANGE_SET_SYMBOLS = ["giql_hip_range_set_any_dev"]
 
+#: every symbol include/giql_hip_string_agg.h declares (STRING_AGG beside MERGE)
+STRING_AGG_SYMBOLS = ["giql_hip_merge_str_dev", "giql_hip_concat_utf8_fill_dev"]
+
 
 class GiqlHipUnavailable(RuntimeError):
     """libgiql_hip.so could not be loaded (not built, or no ROCm runtime)."""
@@ -170,6 +173,23 @@ class CRangeSet(ctypes.Structure):
     ]
 
 
+class CStrAgg(ctypes.Structure):
+    """``giql_str_agg`` (include/giql_hip_string_agg.h)."""
+
+    _fields_ = [
+        ("offsets", ctypes.c_void_p),
+        ("valid", ctypes.c_void_p),
+        ("sep_len", ctypes.c_int32),
+        ("out_offsets", ctypes.c_void_p),
+        ("out_nn", ctypes.c_void_p),
+        ("row_dst", ctypes.c_void_p),
+        ("n_bytes", ctypes.c_int64),
+    ]
+
+
+#: ``GIQL_STR_AGG_*``: string aggregates per call, separator bytes, the NULL mark of ``row_dst``
+STR_AGG_MAX, STR_AGG_MAX_SEP, STR_AGG_NULL_ROW = 4, 255, 0xFFFFFFFF
+
 #: ``GIQL_RANGE_*``: the operator of a literal range set, and the caps of one call
 RANGE_OPS = {"intersects": 0, "contains": 1, "within": 2}
 RANGE_MAX_SETS, RANGE_MAX_RANGES = 8, 1024
@@ -274,6 +294,9 @@ def load() -> ctypes.CDLL:
     L.giql_hip_merge_agg_dev.argtypes = [vp, P(CSide), i32, i64, P(CPred), i32, P(CAgg), i32, vp, vp, vp, vp, i64,
                                          P(i64), vp]
     L.giql_hip_range_set_any_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, P(CRangeSet), i32, vp]
+    L.giql_hip_merge_str_dev.argtypes = [vp, P(CSide), i32, i64, P(CPred), i32, P(CAgg), i32, P(CStrAgg), i32,
+                                         vp, vp, vp, vp, vp, i64, P(i64), vp]
+    L.giql_hip_concat_utf8_fill_dev.argtypes = [vp, vp, vp, i64, vp, vp, i64, ctypes.c_char_p, i32, vp, vp]
     _lib = L
     return L
 

@@ -19,6 +19,7 @@
 
 #include "../../include/giql_hip.h"
 #include "../../include/giql_hip_range_sets.h"
+#include "../../include/giql_hip_string_agg.h"
 #include "aux_kernels.hip.h"
 #include "take_kernels.hip.h"
 #include "select_kernels.hip.h"
@@ -26,6 +27,7 @@
 #include "outer_kernels.hip.h"
 #include "cluster_kernels.hip.h"
 #include "merge_agg_kernels.hip.h"
+#include "string_agg_kernels.hip.h"
 #include "range_set_kernels.hip.h"
 #include "disjoin_kernels.hip.h"
 #include "contain_kernels.hip.h"
@@ -3508,6 +3510,16 @@ struct ClusterBufs {
   u32* seg_end = nullptr;  // MERGE under a predicate: MAX(end) per region
   int n_aggs = 0;          // MERGE with aggregates: set before cluster_front
   u64* agg_ws = nullptr;   //   per aggregate the four per-tile carry arrays (merge_agg_kernels.hip.h)
+  bool strs = false;       // MERGE with STRING_AGG: set before cluster_front (string_agg_kernels.hip.h)
+  u64 *str_g = nullptr, *str_tot = nullptr;  //   G (n + 1), the totals of V and of the region bytes
+  u32 *str_v = nullptr, *str_bad = nullptr;  //   V (n + 1), one flag word per string aggregate
+};
+
+// MERGE with STRING_AGG: the caller's aggregates (n_bytes is written back) and the order output
+struct SaggCall {
+  giql_str_agg* strs;
+  int n;
+  int32_t* out_order;
 };
 
 static int cluster_front(giql_hip_ctx* ctx, hipStream_t st, const giql_side* s, int32_t n_chrom,
@@ -3534,6 +3546,10 @@ static int cluster_front(giql_hip_ctx* ctx, hipStream_t st, const giql_side* s, 
     cb.head_pos = want_heads ? c.take<u32>(n + 1) : nullptr;
     cb.seg_end = want_heads && preds && preds->n > 0 ? c.take<u32>(n + 1) : nullptr;
     cb.agg_ws = cb.n_aggs ? c.take<u64>((size_t)cb.n_aggs * 4 * cdiv(n, (size_t)MAGG_TILE)) : nullptr;
+    cb.str_g = cb.strs ? c.take<u64>(n + 1) : nullptr;
+    cb.str_v = cb.strs ? c.take<u32>(n + 1) : nullptr;
+    cb.str_tot = cb.strs ? c.take<u64>(2) : nullptr;
+    cb.str_bad = cb.strs ? c.take<u32>(SAGG_MAX) : nullptr;
     return c.off;
   };
   GIQL_TRY(claim_arena(ctx, st, carve));
@@ -3703,19 +3719,27 @@ int giql_hip_cluster_pred_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_c
 static int giql_hip_merge_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom, int64_t distance,
                        int32_t* out_chrom, int32_t* out_start, int32_t* out_end,
                        int64_t* out_count, int64_t capacity, int64_t* n_out, void* stream,
-                       const DevPreds* preds = nullptr, MaggArgs* aggs = nullptr) {
+                       const DevPreds* preds = nullptr, MaggArgs* aggs = nullptr, const SaggCall* sc = nullptr) {
   GIQL_TRY(check_cluster_args(ctx, s, n_chrom));
   if (!n_out) return set_err(GIQL_ERR_INVALID, "n_out is NULL");
   GIQL_TRY(begin_call(ctx, s->n));
   hipStream_t st = (hipStream_t)stream;
   *n_out = 0;
-  if (s->n == 0) return GIQL_OK;
+  if (s->n == 0) {
+    for (int a = 0; sc && a < sc->n; a++) {  // no region: the offsets of an empty string column
+      sc->strs[a].n_bytes = 0;
+      if (sc->strs[a].out_offsets) HIP_TRY(hipMemsetAsync(sc->strs[a].out_offsets, 0, sizeof(int32_t), st));
+    }
+    if (sc) HIP_TRY(hipStreamSynchronize(st));
+    return GIQL_OK;
+  }
   if (!out_chrom || !out_start || !out_end) return set_err(GIQL_ERR_INVALID, "output buffer is NULL");
   if (n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
   ClusterBufs cb;
   const bool pred = preds && preds->n > 0;
   cb.n_aggs = aggs ? aggs->n_aggs : 0;
-  GIQL_TRY(cluster_front(ctx, st, s, n_chrom, distance, pred || aggs, true, cb, preds));
+  cb.strs = sc != nullptr;
+  GIQL_TRY(cluster_front(ctx, st, s, n_chrom, distance, pred || aggs || sc, true, cb, preds));
   u64 h_total = 0;
   HIP_TRY(hipMemcpyAsync(&h_total, cb.total, sizeof(u64), hipMemcpyDeviceToHost, st));
   GIQL_TRY(cluster_status(ctx, st));
@@ -3750,9 +3774,57 @@ static int giql_hip_merge_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int32_
     }
     GIQL_TRY(post_launch("merge rows"));
   }
+  u64 str_total[SAGG_MAX] = {0, 0, 0, 0};
+  u32 str_bad[SAGG_MAX] = {0, 0, 0, 0};
+  if (sc) {
+    // The sort is done: its second buffers are free, and hold the per-position lengths, flags and the region bytes.
+    const u32 n = (u32)s->n, m = (u32)h_total;  // (m >= 1: the first row is a head)
+    u32 *c = cb.sb.key[1], *v = cb.sb.end[1], *rb = cb.sb.rid[1];
+    HIP_TRY(hipMemsetAsync(cb.str_bad, 0, SAGG_MAX * sizeof(u32), st));
+    for (int a = 0; a < sc->n; a++) {
+      const giql_str_agg& g = sc->strs[a];
+      {
+        Phase ph(ctx, st, GIQL_PH_COUNT, 1);
+        hipLaunchKernelGGL(k_sagg_len, dim3(cdiv((u64)n, SAGG_NT)), dim3(SAGG_NT), 0, st, cb.sb.rid[0], n, g.offsets,
+                           g.valid, (u32)g.sep_len, c, v, a == 0 ? sc->out_order : (int32_t*)nullptr, cb.str_bad + a);
+        GIQL_TRY(post_launch("string_agg lengths"));
+      }
+      GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, c, (u64)n, cb.str_g, cb.bsums, cb.str_g + n));
+      GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, v, (u64)n, cb.str_v, cb.bsums, cb.str_tot));
+      {
+        Phase ph(ctx, st, GIQL_PH_FILL, 1);
+        hipLaunchKernelGGL(k_sagg_regions, dim3(cdiv((u64)m, SAGG_NT)), dim3(SAGG_NT), 0, st, cb.head_pos, m, n,
+                           cb.str_g, cb.str_v, cb.str_tot, (u32)g.sep_len, rb, (i64*)g.out_nn);
+        GIQL_TRY(post_launch("string_agg regions"));
+      }
+      GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, rb, (u64)m, rb, cb.bsums, cb.str_tot + 1));
+      {
+        Phase ph(ctx, st, GIQL_PH_FILL, 1);
+        hipLaunchKernelGGL(k_sagg_rows, dim3(cdiv((u64)n, SAGG_NT)), dim3(SAGG_NT), 0, st, cb.excl, cb.flags, cb.head_pos,
+                           n, m, cb.str_g, cb.str_v, v, rb, cb.str_tot + 1, g.out_offsets, g.row_dst);
+        GIQL_TRY(post_launch("string_agg rows"));
+      }
+      // (a pageable destination: the copy has landed when the call returns, before the next aggregate's scan)
+      HIP_TRY(hipMemcpyAsync(&str_total[a], cb.str_tot + 1, sizeof(u64), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    HIP_TRY(hipMemcpyAsync(str_bad, cb.str_bad, sizeof(str_bad), hipMemcpyDeviceToHost, st));
+  }
   HIP_TRY(hipStreamSynchronize(st));
   collect_spans(ctx);
   *n_out = (int64_t)h_total;
+  for (int a = 0; sc && a < sc->n; a++)
+    if (str_bad[a])
+      return set_err(GIQL_ERR_INVALID, "string aggregate %d: an offset pair is negative or decreases", a);
+  int over = -1;
+  for (int a = 0; sc && a < sc->n; a++) {
+    const bool fits = str_total[a] < 0x7FFFFFFFull || (str_total[a] == 0x7FFFFFFFull && sc->strs[a].sep_len == 0);
+    sc->strs[a].n_bytes = fits ? (int64_t)str_total[a] : -1;
+    if (!fits && over < 0) over = a;
+  }
+  if (over >= 0)
+    return set_err(GIQL_ERR_CAPACITY, "string aggregate %d: output of %llu bytes or more exceeds int32 offsets", over,
+                   (unsigned long long)str_total[over]);  // (a single region past the limit was counted as 2^31 bytes)
   ctx->stats.n_out = (int64_t)h_total;
   ctx->stats.span = (int64_t)ctx->h_meta->total_span;
   return GIQL_OK;
@@ -3776,15 +3848,7 @@ int giql_hip_merge_pred_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chr
 
 // MERGE with aggregates: the host array of giql_agg -> the by-value kernel argument.  Aggregates that read the same
 // (data, valid, type) share one column, i.e. one gather; the kernel walks the aggregates column by column.
-int giql_hip_merge_agg_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom, int64_t distance,
-                           const giql_pred* preds, int32_t n_preds, const giql_agg* aggs, int32_t n_aggs,
-                           int32_t* out_chrom, int32_t* out_start, int32_t* out_end, int64_t* out_count,
-                           int64_t capacity, int64_t* n_out, void* stream) {
-  if (n_preds < 0 || n_preds > SEL_MAX_PREDS || (n_preds && !preds))
-    return set_err(GIQL_ERR_INVALID, "bad predicates (at most %d)", SEL_MAX_PREDS);
-  if (n_aggs < 1 || n_aggs > MAGG_MAX || !aggs)
-    return set_err(GIQL_ERR_INVALID, "%d aggregates: MERGE takes 1 to %d", n_aggs, MAGG_MAX);
-  MaggArgs ma;
+static int convert_aggs(const giql_agg* aggs, int32_t n_aggs, MaggArgs& ma) {
   memset(&ma, 0, sizeof(ma));
   ma.n_aggs = n_aggs;
   for (int k = 0; k < n_aggs; k++) {
@@ -3802,9 +3866,88 @@ int giql_hip_merge_agg_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chro
     ma.aggs[k].out = (u64*)g.out;
     ma.aggs[k].out_nn = (i64*)g.out_nn;
   }
+  return GIQL_OK;
+}
+
+int giql_hip_merge_agg_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom, int64_t distance,
+                           const giql_pred* preds, int32_t n_preds, const giql_agg* aggs, int32_t n_aggs,
+                           int32_t* out_chrom, int32_t* out_start, int32_t* out_end, int64_t* out_count,
+                           int64_t capacity, int64_t* n_out, void* stream) {
+  if (n_preds < 0 || n_preds > SEL_MAX_PREDS || (n_preds && !preds))
+    return set_err(GIQL_ERR_INVALID, "bad predicates (at most %d)", SEL_MAX_PREDS);
+  if (n_aggs < 1 || n_aggs > MAGG_MAX || !aggs)
+    return set_err(GIQL_ERR_INVALID, "%d aggregates: MERGE takes 1 to %d", n_aggs, MAGG_MAX);
+  MaggArgs ma;
+  GIQL_TRY(convert_aggs(aggs, n_aggs, ma));
   DevPreds ps;
   GIQL_TRY(convert_preds(preds, n_preds, ps, nullptr));
   return with_order_fallback(ctx, [&] { return giql_hip_merge_dev_impl(ctx, s, n_chrom, distance, out_chrom, out_start, out_end, out_count, capacity, n_out, stream, &ps, &ma); });
+}
+
+// MERGE with STRING_AGG (include/giql_hip_string_agg.h): giql_hip_merge_agg_dev with 0..8 numeric aggregates plus the
+// plan of 1..4 string aggregates; giql_hip_concat_utf8_fill_dev writes their bytes.  The caller owns every array the
+// fill reads: the pair keeps no plan in the context.
+int giql_hip_merge_str_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom, int64_t distance,
+                           const giql_pred* preds, int32_t n_preds, const giql_agg* aggs, int32_t n_aggs,
+                           giql_str_agg* strs, int32_t n_strs, int32_t* out_chrom, int32_t* out_start,
+                           int32_t* out_end, int64_t* out_count, int32_t* out_order, int64_t capacity, int64_t* n_out,
+                           void* stream) {
+  if (n_preds < 0 || n_preds > SEL_MAX_PREDS || (n_preds && !preds))
+    return set_err(GIQL_ERR_INVALID, "bad predicates (at most %d)", SEL_MAX_PREDS);
+  if (n_aggs < 0 || n_aggs > MAGG_MAX || (n_aggs && !aggs))
+    return set_err(GIQL_ERR_INVALID, "%d aggregates: MERGE with STRING_AGG takes 0 to %d", n_aggs, MAGG_MAX);
+  if (n_strs < 1 || n_strs > SAGG_MAX || !strs)
+    return set_err(GIQL_ERR_INVALID, "%d string aggregates: MERGE takes 1 to %d", n_strs, SAGG_MAX);
+  const bool rows = s && s->n > 0;
+  for (int k = 0; k < n_strs; k++) {
+    if (strs[k].sep_len < 0 || strs[k].sep_len > SAGG_SEP_MAX)
+      return set_err(GIQL_ERR_INVALID, "string aggregate %d: separator of %d bytes (0 to %d)", k, strs[k].sep_len,
+                     SAGG_SEP_MAX);
+    if (rows && (!strs[k].offsets || !strs[k].out_offsets || !strs[k].out_nn || !strs[k].row_dst))
+      return set_err(GIQL_ERR_INVALID, "string aggregate %d: offsets, out_offsets, out_nn or row_dst is NULL", k);
+  }
+  if (rows && !out_order) return set_err(GIQL_ERR_INVALID, "out_order is NULL");
+  MaggArgs ma;
+  GIQL_TRY(convert_aggs(aggs, n_aggs, ma));
+  DevPreds ps;
+  GIQL_TRY(convert_preds(preds, n_preds, ps, nullptr));
+  const SaggCall sc{strs, n_strs, out_order};
+  return with_order_fallback(ctx, [&] { return giql_hip_merge_dev_impl(ctx, s, n_chrom, distance, out_chrom, out_start, out_end, out_count, capacity, n_out, stream, &ps, n_aggs ? &ma : nullptr, &sc); });
+}
+
+int giql_hip_concat_utf8_fill_dev(giql_hip_ctx* ctx, const int32_t* offsets, const uint8_t* data, int64_t n_rows,
+                                  const int32_t* order, const uint32_t* row_dst, int64_t n, const uint8_t* sep,
+                                  int32_t sep_len, uint8_t* out_data, void* stream) {
+  if (!ctx || n < 0 || n > 0x7FFFFFF0ll || n_rows < 0 || n_rows > 0x7FFFFFFFll)
+    return set_err(GIQL_ERR_INVALID, "bad arguments");
+  if (sep_len < 0 || sep_len > SAGG_SEP_MAX || (sep_len && !sep))
+    return set_err(GIQL_ERR_INVALID, "separator of %d bytes (0 to %d, not NULL)", sep_len, SAGG_SEP_MAX);
+  if (n == 0) return GIQL_OK;
+  if (!order || !row_dst || (n_rows > 0 && !offsets)) return set_err(GIQL_ERR_INVALID, "NULL buffer");
+  GIQL_TRY(begin_call_beside_plan(ctx));
+  hipStream_t st = (hipStream_t)stream;
+  SaggSep sp;
+  memset(&sp, 0, sizeof(sp));
+  sp.len = (u32)sep_len;
+  if (sep_len) memcpy(sp.b, sep, (size_t)sep_len);
+  HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
+  u32 grid = cdiv((u64)n, (u64)SAGG_NT * 2);
+  if (grid > 2u * GIQL_STREAM_GRID) grid = 2u * GIQL_STREAM_GRID;
+  {
+    Phase ph(ctx, st, GIQL_PH_AUX);
+    hipLaunchKernelGGL(k_sagg_fill, dim3(grid), dim3(SAGG_NT), 0, st, offsets, data, (u32)n_rows, order, row_dst, (u64)n,
+                       sp, out_data, &ctx->d_meta->status);
+    GIQL_TRY(post_launch("concat_utf8_fill"));
+  }
+  int status = 0;
+  HIP_TRY(hipMemcpyAsync(&status, &ctx->d_meta->status, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  collect_spans(ctx);
+  if (status != 0)
+    return set_err(GIQL_ERR_INVALID, "concat_utf8_fill: a row id outside the column, a decreasing offset pair or a "
+                                     "separator before the output's start");
+  ctx->stats.n_out = n;
+  return GIQL_OK;
 }
 
 // ----------------------------------------------------------------- DISJOIN

@@ -977,8 +977,18 @@ class HipEngine:
         float32 / float64 (validity: uint8 / bool) device tensors of ``s.n`` rows.  ``valid`` is "the region has a
         non-NULL input" (COUNT: always).  SUM / MIN / MAX of an integer column are int64, of a float column float64;
         AVG is ``double(sum) / double(non-NULL count)`` computed on the device from the kernel's SUM, which a SUM
-        over the same column shares.  Float sums use no atomics: the same call returns the same bits."""
+        over the same column shares.  Float sums use no atomics: the same call returns the same bits.
+
+        An entry ``("STRING_AGG", offsets, data, valid_or_None, separator)`` joins a string column -- Arrow utf8 as
+        contiguous device tensors, int32 ``offsets`` of ``s.n + 1`` entries and uint8 ``data`` -- per region
+        (bedtools ``merge -o collapse``; ``giql_hip_merge_str_dev``): its result is ``(out_offsets, out_data, valid)``,
+        the utf8 layout of one string per region.  NULL rows are skipped, a region with no non-NULL row is NULL, an
+        empty string is a value; the members are joined in ascending start, then row order.  ``separator``: ``str``
+        or ``bytes`` of at most 255 bytes.  At most :attr:`MERGE_STR_AGG_MAX` such entries, and 2^31 - 1 bytes of
+        output each (``GIQL_ERR_CAPACITY`` past that)."""
         torch = _torch()
+        if any(str(a[0]).upper() == "STRING_AGG" for a in aggs):
+            return self._merge_agg_strings(s, n_chrom, distance, list(aggs), preds)
         aggs = [(str(a[0]).upper(), a[1], a[2] if len(a) > 2 else None) for a in aggs]
         if not 1 <= len(aggs) <= self.MERGE_AGG_MAX:
             raise ValueError(f"MERGE takes 1 to {self.MERGE_AGG_MAX} aggregates, got {len(aggs)}")
@@ -1014,9 +1024,128 @@ class HipEngine:
                                                        self._preds_of_rows(preds, rows)),
             lambda parts: wide.merge_agg(parts, self.device, dtypes), s, None, n_chrom)
 
-    def _merge_agg_once(self, s: DeviceSide, n_chrom: int, distance: int, aggs, preds=None):
+    #: STRING_AGG entries per :meth:`merge_agg` call (``GIQL_STR_AGG_MAX``)
+    MERGE_STR_AGG_MAX = _lib.STR_AGG_MAX
+
+    def _merge_agg_strings(self, s: DeviceSide, n_chrom: int, distance: int, aggs, preds):
+        """:meth:`merge_agg` with at least one STRING_AGG entry: the numeric entries keep their checks and their
+        kernel, the string entries add the variable-length plan and one fill each."""
+        torch = _torch()
+        entries = []   # ("num", func, values, valid) | ("str", offsets, data, valid, separator bytes)
+        for a in aggs:
+            func = str(a[0]).upper()
+            if func != "STRING_AGG":
+                entries.append(("num", func, a[1], a[2] if len(a) > 2 else None))
+                continue
+            if len(a) != 5:
+                raise ValueError("a STRING_AGG entry is (\"STRING_AGG\", offsets, data, valid_or_None, separator)")
+            _f, off, data, valid, sep = a
+            sep = sep.encode("utf-8") if isinstance(sep, str) else bytes(sep)
+            if len(sep) > _lib.STR_AGG_MAX_SEP:
+                raise ValueError(f"STRING_AGG separator of {len(sep)} bytes: at most {_lib.STR_AGG_MAX_SEP}")
+            if (off.dtype != torch.int32 or off.dim() != 1 or not off.is_contiguous() or int(off.shape[0]) != s.n + 1
+                    or data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous()):
+                raise ValueError("a STRING_AGG column is contiguous int32 offsets of one entry per row plus one, and "
+                                 "contiguous uint8 data")
+            if valid is not None and (valid.dtype not in (torch.uint8, torch.bool) or not valid.is_contiguous()
+                                      or valid.dim() != 1 or int(valid.shape[0]) != s.n):
+                raise ValueError("validity must be a contiguous uint8/bool tensor of the column's length")
+            entries.append(("str", off, data, valid, sep))
+        nums = [e for e in entries if e[0] == "num"]
+        n_str = len(entries) - len(nums)
+        if len(entries) > self.MERGE_AGG_MAX or n_str > self.MERGE_STR_AGG_MAX:
+            raise ValueError(f"MERGE takes at most {self.MERGE_AGG_MAX} aggregates, {self.MERGE_STR_AGG_MAX} of them "
+                             f"STRING_AGG; got {len(entries)} and {n_str}")
+        ok = (torch.int32, torch.int64, torch.float32, torch.float64)
+        for _k, func, t, valid in nums:
+            if func not in ("COUNT", "SUM", "MIN", "MAX", "AVG"):
+                raise ValueError(f"aggregate function {func!r}")
+            if t.dtype not in ok or t.dim() != 1 or not t.is_contiguous() or int(t.shape[0]) != s.n:
+                raise ValueError("an aggregate column must be a contiguous 1-D int32/int64/float32/float64 tensor "
+                                 "with one value per row of the table")
+            if valid is not None and (valid.dtype not in (torch.uint8, torch.bool) or valid.shape != t.shape
+                                      or not valid.is_contiguous()):
+                raise ValueError("validity must be a contiguous uint8/bool tensor of the column's length")
+        if preds:
+            self._check_pred_rows(s, preds)
+        dtypes = [wide.UTF8 if e[0] == "str" else
+                  torch.int64 if e[1] == "COUNT" else
+                  torch.float64 if e[1] == "AVG" or e[2].is_floating_point() else torch.int64 for e in entries]
+
+        def of_rows(rows):
+            if rows is None:
+                return entries
+            taken = {}   # one copy per tensor / string column: aggregates over one column keep sharing it
+
+            def take(t):
+                if t is not None and t.data_ptr() not in taken:
+                    taken[t.data_ptr()] = t[rows].contiguous()
+                return None if t is None else taken[t.data_ptr()]
+
+            def take_str(off, data):
+                key = (off.data_ptr(), data.data_ptr())
+                if key not in taken:
+                    taken[key] = self.take_utf8(off, data, rows.to(torch.int32).contiguous())
+                return taken[key]
+
+            return [(e[0], e[1], take(e[2]), take(e[3])) if e[0] == "num"
+                    else ("str",) + take_str(e[1], e[2]) + (take(e[3]), e[4]) for e in entries]
+
+        return self._wide(
+            lambda sub, _b, rows: self._merge_str_once(sub, n_chrom, distance, of_rows(rows),
+                                                       self._preds_of_rows(preds, rows)),
+            lambda parts: wide.merge_agg(parts, self.device, dtypes), s, None, n_chrom)
+
+    def _merge_str_once(self, s: DeviceSide, n_chrom: int, distance: int, entries, preds=None):
         torch = _torch()
         n = s.n
+        nums = [(e[1], e[2], e[3]) for e in entries if e[0] == "num"]
+        strs = [e for e in entries if e[0] == "str"]
+        c_aggs, kernel, slot = self._kernel_aggs(nums, n)
+        c_strs = (_lib.CStrAgg * len(strs))()
+        outs = []
+        for j, (_k, off, _data, valid, sep) in enumerate(strs):
+            out_off = torch.empty(n + 1, dtype=torch.int32, device=self.device)
+            nn = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+            row_dst = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)  # (uint32 words)
+            outs.append((out_off, nn, row_dst))
+            c_strs[j].offsets = off.data_ptr()
+            c_strs[j].valid = valid.data_ptr() if valid is not None and n else None
+            c_strs[j].sep_len = len(sep)
+            c_strs[j].out_offsets, c_strs[j].out_nn, c_strs[j].row_dst = out_off.data_ptr(), nn.data_ptr(), row_dst.data_ptr()
+        c = torch.empty(n, dtype=torch.int32, device=self.device)
+        st = torch.empty(n, dtype=torch.int32, device=self.device)
+        en = torch.empty(n, dtype=torch.int32, device=self.device)
+        cnt = torch.empty(n, dtype=torch.int64, device=self.device)
+        order = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        m = ctypes.c_int64(0)
+        c_preds, k = None, 0
+        if preds:
+            c_preds, k, _keep_alive, _nodes, n_nodes = self._c_preds(preds)
+            if n_nodes:
+                raise ValueError("arithmetic in a CLUSTER / MERGE predicate is not supported")
+        _lib.check(self._L.giql_hip_merge_str_dev(
+            self._h, s.c_struct(), int(n_chrom), int(distance), c_preds, k, c_aggs, len(kernel), c_strs, len(strs),
+            c.data_ptr() if n else None, st.data_ptr() if n else None, en.data_ptr() if n else None,
+            cnt.data_ptr() if n else None, order.data_ptr(), n, ctypes.byref(m), self._stream()))
+        r = int(m.value)
+        num_res = iter(self._agg_results(nums, kernel, slot, r))
+        str_res = []
+        for j, (_k, off, data, _valid, sep) in enumerate(strs):
+            out_off, nn, row_dst = outs[j]
+            out = torch.empty(int(c_strs[j].n_bytes), dtype=torch.uint8, device=self.device)
+            if out.numel():
+                _lib.check(self._L.giql_hip_concat_utf8_fill_dev(
+                    self._h, off.data_ptr(), data.data_ptr() if data.numel() else None, n, order.data_ptr(),
+                    row_dst.data_ptr(), n, sep, len(sep), out.data_ptr() if out.numel() else None, self._stream()))
+            str_res.append((out_off[: r + 1], out, nn[:r] > 0))
+        str_res = iter(str_res)
+        return (c[:r], st[:r], en[:r], cnt[:r]) + tuple(next(num_res) if e[0] == "num" else next(str_res)
+                                                        for e in entries)
+
+    def _kernel_aggs(self, aggs, n: int):
+        """The ``giql_agg`` array of numeric entries ``(func, values, valid)``: ``(array or None, kernel, slot)``."""
+        torch = _torch()
         types = {torch.int32: _lib.T_I32, torch.int64: _lib.T_I64, torch.float32: _lib.T_F32,
                  torch.float64: _lib.T_F64}
         # the kernel's aggregates: AVG asks for SUM, and a SUM and an AVG over one column share it
@@ -1036,6 +1165,27 @@ class HipEngine:
             c_aggs[j].valid = valid.data_ptr() if valid is not None and n else None
             c_aggs[j].out = out.data_ptr() if n else 1
             c_aggs[j].out_nn = nn.data_ptr() if n else None
+        return (c_aggs if kernel else None), kernel, slot
+
+    def _agg_results(self, aggs, kernel, slot, r: int):
+        """What :meth:`merge_agg` returns per numeric entry, from the kernel's outputs cut to ``r`` regions."""
+        torch = _torch()
+        res = []
+        for (func, _t, _v), j in zip(aggs, slot):
+            out, nn = kernel[j][3][:r], kernel[j][4][:r]
+            if func == "COUNT":
+                res.append((out, torch.ones(r, dtype=torch.bool, device=self.device)))
+                continue
+            valid = nn > 0
+            if func == "AVG":
+                out = out.double() / nn.double()
+            res.append((torch.where(valid, out, torch.zeros_like(out)), valid))
+        return res
+
+    def _merge_agg_once(self, s: DeviceSide, n_chrom: int, distance: int, aggs, preds=None):
+        torch = _torch()
+        n = s.n
+        c_aggs, kernel, slot = self._kernel_aggs(aggs, n)
         c = torch.empty(n, dtype=torch.int32, device=self.device)
         st = torch.empty(n, dtype=torch.int32, device=self.device)
         en = torch.empty(n, dtype=torch.int32, device=self.device)
@@ -1051,17 +1201,7 @@ class HipEngine:
             c.data_ptr() if n else None, st.data_ptr() if n else None, en.data_ptr() if n else None,
             cnt.data_ptr() if n else None, n, ctypes.byref(m), self._stream()))
         r = int(m.value)
-        res = []
-        for (func, _t, _v), j in zip(aggs, slot):
-            out, nn = kernel[j][3][:r], kernel[j][4][:r]
-            if func == "COUNT":
-                res.append((out, torch.ones(r, dtype=torch.bool, device=self.device)))
-                continue
-            valid = nn > 0
-            if func == "AVG":
-                out = out.double() / nn.double()
-            res.append((torch.where(valid, out, torch.zeros_like(out)), valid))
-        return (c[:r], st[:r], en[:r], cnt[:r]) + tuple(res)
+        return (c[:r], st[:r], en[:r], cnt[:r]) + tuple(self._agg_results(aggs, kernel, slot, r))
 
     # ------------------------------------------------------------- projection
     def take(self, cols, idx, outs=None):

@@ -12,10 +12,12 @@ returned row indices.  The join itself runs in ``libgiql_hip.so``.
 from __future__ import annotations
 
 import os
+import re
 import threading
 
 import numpy as np
 
+from ._lib import GIQL_ERR_CAPACITY, GiqlHipError
 from .engine import ENCODING_OFFSETS, DeviceSide, HipEngine, InvertedRows
 from .plan import JoinPlan, PlanSide, Projection, is_plan_string
 from .shape import operand_sides
@@ -881,6 +883,12 @@ def _merge_aggregate_inputs(plan: JoinPlan, tbl, keep, eng: HipEngine):
     res = _Residuals(plan, tbl, None, eng)
     inputs, types, taken = [], [], {}
     for ag in plan.aggregates:
+        if ag.func == "STRING_AGG":
+            if ("utf8", ag.column) not in taken:
+                taken[("utf8", ag.column)] = _string_agg_column(ag.column, _column(tbl, ag.column), keep, eng)
+            inputs.append(("STRING_AGG",) + taken[("utf8", ag.column)] + (ag.separator,))
+            types.append(pa.string())
+            continue
         col = res._arrow("l", ag.column)
         t = col.type
         if not (pa.types.is_integer(t) or pa.types.is_floating(t)):
@@ -897,6 +905,56 @@ def _merge_aggregate_inputs(plan: JoinPlan, tbl, keep, eng: HipEngine):
         inputs.append((ag.func,) + taken[ag.column])
         types.append(t)
     return inputs, types
+
+
+def _string_agg_column(name: str, col, keep, eng: HipEngine):
+    """A STRING_AGG column on the device: ``(offsets int32, data uint8, validity bytes or None)``.  Arrow ``string``
+    goes up as it lies in memory -- a sliced array keeps its offsets into the whole data buffer -- ``large_string`` and
+    dictionary-of-string are cast to ``string`` on the host first (pyarrow raises when the column does not fit int32
+    offsets); any other type is refused.  When the WHERE kept a subset the column is taken by ``keep`` on the device,
+    so the merge's row ids and the values stay aligned."""
+    import pyarrow as pa
+    import torch
+
+    if isinstance(col, pa.ChunkedArray):
+        col = col.combine_chunks() if col.num_chunks != 1 else col.chunk(0)
+    if not isinstance(col, pa.Array):
+        col = pa.array(np.asarray(col))
+    t = col.type
+    if pa.types.is_large_string(t) or (pa.types.is_dictionary(t) and (pa.types.is_string(t.value_type)
+                                                                      or pa.types.is_large_string(t.value_type))):
+        col = col.cast(pa.string())
+    elif not pa.types.is_string(t):
+        raise ValueError(f"STRING_AGG({name}): column {name!r} has type {t}; STRING_AGG beside MERGE takes string "
+                         "columns")
+    bufs = col.buffers()
+    n = len(col)
+    if bufs[1] is None:   # (an empty array may carry no offsets buffer)
+        off = np.zeros(n + 1, np.int32)
+    else:
+        off = np.frombuffer(bufs[1], dtype=np.int32, count=n + 1 + col.offset)[col.offset:]
+    data = np.frombuffer(bufs[2], dtype=np.uint8) if bufs[2] is not None else np.zeros(0, np.uint8)
+    off_dev = torch.from_numpy(np.ascontiguousarray(off)).to(eng.device)
+    data_dev = torch.from_numpy(np.ascontiguousarray(data)).to(eng.device)
+    valid = None
+    if col.null_count:
+        valid = torch.from_numpy(np.ascontiguousarray(
+            col.is_valid().to_numpy(zero_copy_only=False).astype(np.uint8))).to(eng.device)
+    if keep is not None:
+        off_dev, data_dev = eng.take_utf8(off_dev, data_dev, keep)
+        valid = None if valid is None else valid[keep.long()].contiguous()
+    return off_dev, data_dev, valid
+
+
+def _string_agg_array(offsets, data, valid):
+    """One STRING_AGG result of ``HipEngine.merge_agg`` as a nullable Arrow ``string`` column."""
+    import pyarrow as pa
+
+    ok = valid.cpu().numpy()
+    n = int(ok.shape[0])
+    vbuf = None if ok.all() else pa.py_buffer(np.packbits(ok, bitorder="little").tobytes())
+    return pa.Array.from_buffers(pa.string(), n, [vbuf, pa.py_buffer(_to_host(offsets.contiguous())),
+                                                  pa.py_buffer(_to_host(data))], null_count=int(n - ok.sum()))
 
 
 def _execute_cluster_merge(plan: JoinPlan, tables, eng: HipEngine, return_indices: bool):
@@ -976,7 +1034,15 @@ def _execute_cluster_merge(plan: JoinPlan, tables, eng: HipEngine, return_indice
     agg_out = ()
     if plan.aggregates:
         agg_in, agg_types = _merge_aggregate_inputs(plan, tbl, keep, eng)
-        merged = eng.merge_agg(dev_side, n_part, plan.distance, agg_in, preds=preds)
+        try:
+            merged = eng.merge_agg(dev_side, n_part, plan.distance, agg_in, preds=preds)
+        except GiqlHipError as exc:
+            over = re.search(r"string aggregate (\d+): output of (\d+) bytes", str(exc))
+            if exc.code != GIQL_ERR_CAPACITY or not over:
+                raise
+            ag = [a for a in plan.aggregates if a.func == "STRING_AGG"][int(over.group(1))]
+            raise ValueError(f"STRING_AGG({ag.column}) AS {ag.name}: at least {over.group(2)} bytes of output exceed "
+                             "the 2^31 - 1 bytes of one string column") from None
         agg_out = merged[4:]
     else:
         merged = eng.merge(dev_side, n_part, plan.distance, preds=preds)
@@ -997,7 +1063,11 @@ def _execute_cluster_merge(plan: JoinPlan, tables, eng: HipEngine, return_indice
         if p.side == "count":
             cols[p.name] = pa.array(cnt, type=pa.int64())
         elif p.side == "agg":
-            ag, (vals, valid) = plan.aggregates[int(p.column)], agg_out[int(p.column)]
+            ag = plan.aggregates[int(p.column)]
+            if ag.func == "STRING_AGG":
+                cols[p.name] = _string_agg_array(*agg_out[int(p.column)])
+                continue
+            vals, valid = agg_out[int(p.column)]
             arr = pa.array(vals.cpu().numpy(), mask=~valid.cpu().numpy())
             if ag.func in ("MIN", "MAX"):  # the column's own type (the device holds int64 / float64: exact)
                 arr = arr.cast(agg_types[int(p.column)])
@@ -1835,9 +1905,10 @@ def _execute_sharded(plan: JoinPlan, lt, rt, ia, ib, n_chrom, devices, return_in
 
 def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, return_indices=False,
             device_projection: bool = True, devices=None, outer_joins: bool = False, row_predicates: bool = False,
-            select_expressions: bool = False, merge_aggregates: bool = False, range_sets: bool = False):
+            select_expressions: bool = False, merge_aggregates: bool = False, range_sets: bool = False,
+            string_aggregates: bool = False):
     """Run *plan* (a :class:`JoinPlan`, its string form, or a GIQL query string; ``outer_joins``,
-    ``row_predicates``, ``select_expressions``, ``merge_aggregates`` and ``range_sets`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
+    ``row_predicates``, ``select_expressions``, ``merge_aggregates``, ``string_aggregates`` and ``range_sets`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
     (``{name: pyarrow.Table | dict of arrays}``).
 
     Returns a ``pyarrow.Table`` with the plan's projected columns (bag semantics,
@@ -1859,7 +1930,8 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
     if isinstance(plan, str):
         plan = JoinPlan.from_string(plan) if is_plan_string(plan) else build_plan(
             plan, giql_tables, outer_joins=outer_joins, row_predicates=row_predicates,
-            select_expressions=select_expressions, merge_aggregates=merge_aggregates, range_sets=range_sets)
+            select_expressions=select_expressions, merge_aggregates=merge_aggregates, range_sets=range_sets,
+            string_aggregates=string_aggregates)
     if not isinstance(plan, JoinPlan):
         raise ValueError("plan must be a JoinPlan, a plan string or a GIQL query")
     devices = [int(d) for d in devices] if devices is not None else None

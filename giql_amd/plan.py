@@ -91,11 +91,14 @@ class Aggregate:
     over the join's rows per ``group_by`` key (the reference rebuilds these over its wrapper
     relation, intersects_duckdb.py:1402-1644)."""
 
-    func: str      # COUNT SUM MIN MAX AVG
+    func: str      # COUNT SUM MIN MAX AVG; beside MERGE also STRING_AGG
     side: str      # "l" / "r", or "*" for COUNT(*)
     column: str
     name: str      # output column name
     distinct: bool = False
+    # STRING_AGG beside MERGE only (a plan lowered with the ``string_aggregates`` opt-in): the literal separator.
+    # None for every other aggregate; plan strings written before the field existed load with None
+    separator: str | None = None
 
 
 @dataclass(frozen=True)
@@ -200,6 +203,9 @@ class JoinPlan:
         for rs in self.range_sets:
             if rs.op not in RANGE_OPS or rs.quantifier not in RANGE_QUANTIFIERS or not rs.ranges:
                 raise ValueError(f"bad range set {rs.op!r} {rs.quantifier!r} over {len(rs.ranges)} ranges")
+        for a in self.aggregates:
+            if (a.func == "STRING_AGG") != (a.separator is not None) or (a.func == "STRING_AGG" and self.kind != "MERGE"):
+                raise ValueError(f"aggregate {a.name!r}: STRING_AGG, and only STRING_AGG beside MERGE, carries a separator")
         for p in self.projection:
             if p.side == "agg" and not (self.kind == "MERGE" and p.column.isdigit()
                                         and int(p.column) < len(self.aggregates)):

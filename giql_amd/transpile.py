@@ -1092,16 +1092,21 @@ def _parse_cluster_call(p: _Parser):
 #: the aggregates ``merge_aggregates`` lowers beside MERGE (merge.py:317-390 keeps any plain aggregate there)
 MERGE_AGG_FUNCS = ("COUNT", "SUM", "AVG", "MIN", "MAX")
 MERGE_AGG_MAX = 8
+#: ``string_aggregates``: STRING_AGG beside MERGE; the strings among the MERGE_AGG_MAX, the separator's UTF-8 bytes
+MERGE_STR_AGG_MAX = 4
+MERGE_STR_SEP_MAX = 255
 
 
-def _lower_cluster(p: _Parser, tbls: Tables, merge_aggregates: bool = False) -> JoinPlan:
+def _lower_cluster(p: _Parser, tbls: Tables, merge_aggregates: bool = False,
+                   string_aggregates: bool = False) -> JoinPlan:
     """``SELECT <cols | *>, CLUSTER(interval[, d][, stranded := b]) AS id FROM t [WHERE ...]`` and
     ``SELECT MERGE(interval[, d][, stranded := b]) [, COUNT(*) AS n] FROM t [WHERE ...]``
     (src/giql/expanders/cluster.py:81-205, src/giql/expanders/merge.py:62-183).  A WHERE
     of simple comparisons filters the rows before clustering, as in the reference, where
     it lands inside the inner ``__giql_lag_calc`` subquery (cluster.py:404-420).
     ``merge_aggregates``: ``COUNT(col)``, ``SUM(col)``, ``AVG(col)``, ``MIN(col)``, ``MAX(col)`` over a column of the
-    table, each with an alias, lower beside MERGE too (merge.py:317-390) instead of declining."""
+    table, each with an alias, lower beside MERGE too (merge.py:317-390) instead of declining.
+    ``string_aggregates``: so does ``STRING_AGG(col, '<literal>')`` with an alias (bedtools ``merge -o collapse``)."""
     p.expect_kw("SELECT")
     if p.at_kw("DISTINCT"):
         raise _decline("DISTINCT with CLUSTER / MERGE")
@@ -1123,14 +1128,18 @@ def _lower_cluster(p: _Parser, tbls: Tables, merge_aggregates: bool = False) -> 
             elif not merge_aggregates:
                 raise _decline("aggregate other than COUNT(*) beside MERGE")
             else:
-                items.append(("AGG", ("COUNT", _parse_merge_agg_arg(p, "COUNT"))))
-        elif merge_aggregates and t.kind == "id" and not t.quoted and p.peek(1).kind == "punct" \
-                and p.peek(1).text == "(" and t.text.upper() in MERGE_AGG_FUNCS + ("STRING_AGG",):
+                items.append(("AGG", ("COUNT", _parse_merge_agg_arg(p, "COUNT"), None)))
+        elif (merge_aggregates or string_aggregates) and t.kind == "id" and not t.quoted and p.peek(1).kind == "punct" \
+                and p.peek(1).text == "(" \
+                and t.text.upper() in (MERGE_AGG_FUNCS if merge_aggregates else ()) + ("STRING_AGG",):
             func = p.next().text.upper()
             p.next()
             if func == "STRING_AGG":
-                raise _decline("STRING_AGG beside MERGE (-o collapse)")
-            items.append(("AGG", (func, _parse_merge_agg_arg(p, func))))
+                if not string_aggregates:
+                    raise _decline("STRING_AGG beside MERGE (-o collapse)")
+                items.append(("AGG", ("STRING_AGG",) + _parse_string_agg_args(p)))
+            else:
+                items.append(("AGG", (func, _parse_merge_agg_arg(p, func), None)))
         elif t.kind in ("num", "str") or p.at_punct("("):
             raise _decline("expression in the SELECT list")
         else:
@@ -1195,6 +1204,8 @@ def _lower_cluster(p: _Parser, tbls: Tables, merge_aggregates: bool = False) -> 
         for kind, payload, alias in items:
             if kind == "CLUSTER":
                 proj.append(Projection("cluster", "", op_alias))
+            elif kind == "AGG" and payload[0] == "STRING_AGG":
+                raise _decline("STRING_AGG beside CLUSTER")
             elif kind in ("COUNT", "AGG"):
                 raise _decline("aggregate beside CLUSTER")
             elif payload.star:
@@ -1211,13 +1222,15 @@ def _lower_cluster(p: _Parser, tbls: Tables, merge_aggregates: bool = False) -> 
                     raise _decline("COUNT(*) without an alias beside MERGE")
                 proj.append(Projection("count", "*", alias))
             elif kind == "AGG":
-                func, refc = payload
+                func, refc, sep = payload
                 if not alias:
                     raise _decline(f"{func}({refc.column}) without an alias beside MERGE")
                 if len(aggregates) == MERGE_AGG_MAX:
                     raise _decline(f"more than {MERGE_AGG_MAX} aggregates beside MERGE")
+                if sep is not None and sum(1 for a in aggregates if a.separator is not None) == MERGE_STR_AGG_MAX:
+                    raise _decline(f"more than {MERGE_STR_AGG_MAX} STRING_AGG aggregates beside MERGE")
                 proj.append(Projection("agg", str(len(aggregates)), alias))
-                aggregates.append(Aggregate(func, "l", own(refc), alias))
+                aggregates.append(Aggregate(func, "l", own(refc), alias, separator=sep))
             elif payload.star:
                 raise ValueError("MERGE cannot be combined with a star projection (e.g. SELECT *, MERGE(...))")  # merge.py:96-133
             else:
@@ -1262,6 +1275,36 @@ def _parse_merge_agg_arg(p: _Parser, func: str) -> _ColRef:
         raise _decline(f"expression argument of {func}() beside MERGE")
     p.expect_punct(")")
     return ref
+
+
+def _parse_string_agg_args(p: _Parser) -> tuple:
+    """The arguments of STRING_AGG beside MERGE, after its ``(``, through the ``)``: one column of the table and a
+    string literal.  Returns ``(column reference, separator)``."""
+    if p.at_kw("DISTINCT"):
+        raise _decline("DISTINCT inside STRING_AGG() beside MERGE")
+    if p.peek().kind != "id":
+        raise _decline("expression argument of STRING_AGG() beside MERGE")
+    ref = p.colref()
+    if ref.star:
+        raise _decline("expression argument of STRING_AGG() beside MERGE")
+    if p.at_kw("ORDER"):
+        raise _decline("ORDER BY inside STRING_AGG() beside MERGE")
+    if p.at_punct(")"):
+        raise _decline("STRING_AGG() with one argument beside MERGE (give the separator)")
+    if not p.at_punct(","):
+        raise _decline("expression argument of STRING_AGG() beside MERGE")
+    p.next()
+    if p.peek().kind != "str":
+        raise _decline("STRING_AGG() separator that is not a string literal beside MERGE")
+    sep = p.next().text
+    if p.at_kw("ORDER"):
+        raise _decline("ORDER BY inside STRING_AGG() beside MERGE")
+    if not p.at_punct(")"):
+        raise _decline("STRING_AGG() separator that is not a string literal beside MERGE")
+    if len(sep.encode("utf-8")) > MERGE_STR_SEP_MAX:
+        raise _decline(f"STRING_AGG() separator longer than {MERGE_STR_SEP_MAX} UTF-8 bytes beside MERGE")
+    p.expect_punct(")")
+    return ref, sep
 
 
 def _disjoin_from(p: _Parser) -> int | None:
@@ -1368,7 +1411,8 @@ def _lower_disjoin(p: _Parser, tbls: Tables) -> JoinPlan:
 
 
 def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predicates: bool = False,
-               select_expressions: bool = False, merge_aggregates: bool = False, range_sets: bool = False) -> JoinPlan:
+               select_expressions: bool = False, merge_aggregates: bool = False, range_sets: bool = False,
+               string_aggregates: bool = False) -> JoinPlan:
     """Parse *giql* and lower the INTERSECTS / NEAREST join (or a CLUSTER / MERGE
     query) to a :class:`JoinPlan`.
 
@@ -1381,6 +1425,9 @@ def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predica
     ``LEAST(a.end, b.end) - GREATEST(a.start, b.start) AS overlap_bp``) -- instead of declining them.
     ``merge_aggregates=True`` opts in to ``COUNT(col)`` / ``SUM`` / ``AVG`` / ``MIN`` / ``MAX`` of a table column
     beside MERGE, each with an alias (bedtools ``merge -c 5 -o mean``: ``MERGE(interval), AVG(score) AS avg_score``).
+    ``string_aggregates=True`` opts in to ``STRING_AGG(<column>, '<literal>') AS alias`` beside MERGE (bedtools ``merge
+    -c 4 -o collapse``; docs/recipes/clustering.rst:267-279): NULLs are skipped, a region without a non-NULL name is
+    NULL, and the names of a region are joined in ascending start, then row order.
     ``range_sets=True`` opts in to the quantified literal ranges of a single-table filter -- ``interval INTERSECTS |
     CONTAINS | WITHIN ANY(...)`` / ``SOME(...)`` / ``ALL(...)``, a ``NOT`` in front of such a predicate or of a single
     literal, several of them joined by AND -- with every literal format of the reference's parser and over a table of
@@ -1395,7 +1442,8 @@ def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predica
             continue
         try:
             if lower is _lower_cluster:
-                return lower(probe, tbls, merge_aggregates=bool(merge_aggregates))
+                return lower(probe, tbls, merge_aggregates=bool(merge_aggregates),
+                             string_aggregates=bool(string_aggregates))
             return lower(probe, tbls)
         except HipDeclined as exc:
             # these operators compute no column: with the opt-in the decline names the operator
@@ -1600,14 +1648,14 @@ def _render(toks: list[Tok]) -> str:
 
 def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins: bool = False,
               row_predicates: bool = False, select_expressions: bool = False,
-              merge_aggregates: bool = False, range_sets: bool = False) -> str:
+              merge_aggregates: bool = False, range_sets: bool = False, string_aggregates: bool = False) -> str:
     """Mirror of ``giql.transpile`` for this backend's path.
 
     ``dialect="hip"``: returns the plan string of the INTERSECTS / NEAREST join
     (hand it to :func:`giql_amd.execute`); ``outer_joins=True`` lets a LEFT [OUTER] JOIN lower too
     and ``row_predicates=True`` the per-row joins over CONTAINS / WITHIN / DISTANCE, ``select_expressions=True``
     computed columns such as ``overlap_bp`` in the SELECT list, ``merge_aggregates=True`` SUM / AVG / MIN / MAX /
-    COUNT(col) beside MERGE, ``range_sets=True`` ANY / SOME / ALL over literal ranges and NOT over a literal predicate
+    COUNT(col) beside MERGE, ``string_aggregates=True`` STRING_AGG(col, 'sep') beside MERGE, ``range_sets=True`` ANY / SOME / ALL over literal ranges and NOT over a literal predicate
     in a single-table filter (:func:`build_plan`).  ``dialect=None``: returns SQL for the
     literal-range predicate (plumbing, BASELINE config 1).  Other dialects belong to
     the reference package.
@@ -1615,7 +1663,7 @@ def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins
     if dialect == "hip":
         return build_plan(giql, tables, outer_joins=outer_joins, row_predicates=row_predicates,
                           select_expressions=select_expressions, merge_aggregates=merge_aggregates,
-                          range_sets=range_sets).to_string()
+                          range_sets=range_sets, string_aggregates=string_aggregates).to_string()
     if dialect is None:
         return _lower(giql, tables, want_sql=True)
     raise ValueError(

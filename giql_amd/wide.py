@@ -110,14 +110,50 @@ def merge(parts, device):
     return tuple(t[order] for t in cols)
 
 
+#: the ``dtypes`` entry of :func:`merge_agg` for a STRING_AGG column
+UTF8 = "utf8"
+
+
+def utf8_in_order(columns, order, device):
+    """Region-order concatenation of string results: ``columns`` holds one ``(offsets int32 [m_k + 1], data uint8)``
+    per group, ``order`` indexes their rows laid end to end; returns ``(offsets, data)`` of the rows in that order,
+    an Arrow utf8 layout with int32 offsets starting at 0.  The bytes move with one gather; a result past 2^31 - 1
+    bytes does not fit one such column and is a ``ValueError``."""
+    import torch
+
+    lens = _cat([(o[1:] - o[:-1]).long() for o, _d in columns], torch.int64, device)
+    first, base = [], 0   # where every row starts in the groups' bytes laid end to end
+    for o, d in columns:
+        first.append(o[:-1].long() + base)
+        base += int(d.shape[0])
+    first = _cat(first, torch.int64, device)
+    data = _cat([d for _o, d in columns], torch.uint8, device)
+    lens, first = lens[order], first[order]
+    ends = torch.cumsum(lens, 0)
+    total = int(ends[-1]) if ends.numel() else 0
+    if total > 0x7FFFFFFF:
+        raise ValueError(f"string aggregate of {total} bytes: exceeds one string column's 2^31 - 1 bytes")
+    offsets = torch.zeros(lens.numel() + 1, dtype=torch.int32, device=device)
+    offsets[1:] = ends.to(torch.int32)
+    starts = ends - lens
+    src = torch.repeat_interleave(first - starts, lens) + torch.arange(total, dtype=torch.int64, device=device)
+    return offsets, data[src]
+
+
 def merge_agg(parts, device, dtypes):
     """MERGE with aggregates, result ``(chrom, start, end, count, (values, valid), ...)``: a region never spans two
     groups, so the groups' regions are concatenated and every column takes :func:`merge`'s order.  ``dtypes``: the
-    value dtype per aggregate (what no group at all returns)."""
+    value dtype per aggregate (what no group at all returns); :data:`UTF8` marks a STRING_AGG column, whose result
+    is ``(offsets, data, valid)`` and goes through :func:`utf8_in_order`."""
     import torch
 
     cols, order = _merge_columns(parts, device)
-    aggs = tuple((_cat([p[4 + j][0] for _rows, _rb, p in parts], dt, device)[order],
-                  _cat([p[4 + j][1] for _rows, _rb, p in parts], torch.bool, device)[order])
-                 for j, dt in enumerate(dtypes))
-    return tuple(t[order] for t in cols) + aggs
+    aggs = []
+    for j, dt in enumerate(dtypes):
+        if dt == UTF8:
+            valid = _cat([p[4 + j][2] for _rows, _rb, p in parts], torch.bool, device)[order]
+            aggs.append(utf8_in_order([p[4 + j][:2] for _rows, _rb, p in parts], order, device) + (valid,))
+        else:
+            aggs.append((_cat([p[4 + j][0] for _rows, _rb, p in parts], dt, device)[order],
+                         _cat([p[4 + j][1] for _rows, _rb, p in parts], torch.bool, device)[order]))
+    return tuple(t[order] for t in cols) + tuple(aggs)
