@@ -10,6 +10,7 @@
 #include <memory>
 #include <utility>
 #include <thread>
+#include <type_traits>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -45,6 +46,7 @@
 #include "host_pool.h"
 #include "plan_expand.h"
 #include "zero_ledger.h"
+#include "sort_plan.h"
 
 using namespace giql;
 
@@ -99,10 +101,35 @@ constexpr size_t HIST_BYTES = (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32);
 constexpr size_t TOP_BYTES = (size_t)LIN_HIST_REPLICAS * MM_TOP_WORDS * sizeof(u32);
 
 // ----------------------------------------------------------------- context
+// The ping-pong buffers of one sort.  "Buffer 0" is where the rows are: run_sort_onesweep reads them there and leaves
+// them there, whichever physical buffer its last pass wrote (flip()).
 struct SortBufs {
   u32* key[2];
   u32* end[2];
   u32* rid[2];
+  // which arrays travel with the keys (the kernels' MODE)
+  SortPayload payload() const { return (SortPayload)((rid[0] ? 1 : 0) | (end[0] ? 2 : 0)); }
+  // The ONLY exchange of the ping-pong pointers: a sort whose plan ends in physical buffer 1 makes that "buffer 0".
+  // A copy or view of the buffers made before the sort does not follow: take one afterwards (keyed_by_end / follow).
+  void flip() {
+    std::swap(key[0], key[1]);
+    std::swap(end[0], end[1]);
+    std::swap(rid[0], rid[1]);
+  }
+  // the view that sorts by the end column, with the keys as its payload ...
+  SortBufs keyed_by_end() const {
+    SortBufs v = *this;
+    std::swap(v.key, v.end);
+    return v;
+  }
+  // ... and the owner catching up with what a sort did to that view (its flip included)
+  void follow(const SortBufs& by_end) {
+    for (int k = 0; k < 2; k++) {
+      end[k] = by_end.key[k];
+      key[k] = by_end.end[k];
+      rid[k] = by_end.rid[k];
+    }
+  }
 };
 
 // Device pointers kept between inner_plan and inner_fill (all inside the arena).
@@ -314,6 +341,22 @@ struct giql_hip_ctx {
   size_t ev_used = 0;
   giql_hip_stats stats;
 };
+
+// What the sort decisions (sort_plan.h) read of the context, in one place.  The header restates four constants of
+// the kernel headers; they are the kernels' own.
+static_assert(SORT_OS_BINS == OS_BINS && SORT_OS_MIN_TILE == OS_MIN_TILE && SORT_MIN_WBITS == BS_MIN_WBITS &&
+              SORT_OS_DEFAULT_TILE == 1024 * 8, "sort_plan.h restates the kernel headers' constants");
+static inline SortTuning sort_tuning(const giql_hip_ctx* ctx) {
+  const Switches& sw = ctx->sw;
+  SortTuning t;
+  t.os_variant = sw.os_variant, t.local_min_rows = sw.local_min_rows, t.force_bits = sw.force_bits;
+  t.local_min_bucket_rows = sw.local_min_bucket_rows, t.local_max_bucket_rows = sw.local_max_bucket_rows;
+  t.no_narrow = sw.no_narrow, t.no_coarse_b = sw.no_coarse_b, t.coarse_max_group_rows = sw.coarse_max_group_rows;
+  t.local_sort = ctx->guess.local_sort, t.last_span = ctx->guess.last_span;
+  t.force_local = ctx->call.force_local, t.index_bits = ctx->call.index_bits, t.first_unstable = ctx->call.first_unstable;
+  t.bucket_buffers = ctx->bucket_bnd.get() != nullptr;
+  return t;
+}
 
 static int ensure_arena(giql_hip_ctx* ctx, size_t bytes, hipStream_t stream) {
   if (bytes <= ctx->arena.bytes()) return GIQL_OK;
@@ -569,8 +612,6 @@ struct LinBufs {
   u32* hist_partial2 = nullptr;
 };
 
-static inline int sort_local_bits(const giql_hip_ctx* ctx, size_t n);
-static inline bool sort_is_local(const giql_hip_ctx* ctx, size_t n) { return sort_local_bits(ctx, n) != 0; }
 
 // The range of the two sides' canonical offsets, widened by `pad`: the positions every chromosome gets beyond its
 // rows' range on either end (the within-distance forms: 1, for the clamped ends of their widened rows --
@@ -633,8 +674,7 @@ static int run_spans(giql_hip_ctx* ctx, hipStream_t st, const giql_side& a, cons
       ms[k].n = (i64)s.n;
       ms[k].len_bias = s.end_off - s.start_off;
       ms[k].start_off = with_hist ? s.start_off : 0;
-      // (16-bit buckets: the low digits are sorted in LDS and not counted; narrower ones need the bits 8-15 digit)
-      ms[k].hist = !with_hist ? 0 : (sort_local_bits(ctx, (size_t)s.n) == 16 ? 2 : 1);
+      ms[k].hist = !with_hist ? 0 : span_hist_mode(sort_tuning(ctx), (size_t)s.n);  // which digits: as the side's sort will need them
       ms[k].nblk = grid;
       ms[k].hist_partial = with_hist ? hp : nullptr;
       ms[k].top_partial = with_hist ? (k == hist_side ? lb.top_partial : lb.top_partial2) : nullptr;
@@ -651,7 +691,7 @@ static int run_spans(giql_hip_ctx* ctx, hipStream_t st, const giql_side& a, cons
     u32 grid = cdiv((u64)s.n, (u64)(with_hist ? MM_NT_HIST : MM_NT) * MM_ITEMS);
     if (grid > (u32)MM_MAX_BLOCKS) grid = MM_MAX_BLOCKS;
     nblk[k] = (int)grid;
-    if (with_hist && sort_local_bits(ctx, (size_t)s.n) == 16)  // the low digits are sorted in LDS: not counted
+    if (with_hist && span_hist_mode(sort_tuning(ctx), (size_t)s.n) == 2)  // the low digits are sorted in LDS: not counted
       hipLaunchKernelGGL((k_chrom_minmax<2, MM_NT_HIST>), dim3(grid), dim3(MM_NT_HIST), lds, st, s.chrom, s.start, s.end,
                          (i64)s.n, n_chrom, lb.gmin, lb.gmax, ctx->d_meta, s.end_off - s.start_off, k,
                          lb.len_part, s.start_off, hp, tp);
@@ -672,13 +712,45 @@ static int run_spans(giql_hip_ctx* ctx, hipStream_t st, const giql_side& a, cons
   return post_launch("spans");
 }
 
-// hist_partial / gbase non-NULL: also produce the onesweep digit offsets.
-static int run_linearize(giql_hip_ctx* ctx, hipStream_t st, const giql_side& s, int n_chrom,
-                         const LinBufs& lb, u32* keys, u32* ends, u32* irr_list, int which,
-                         int keep_irregular, u32* hist_partial = nullptr, u32* gbase = nullptr,
-                         u32* hist_end = nullptr, u32* gbase_end = nullptr, bool skip_end = false) {
+// A column's digit counts: the histogram replicas a pass counts into and the digit bases made of them (both or neither).
+struct DigitCounts {
+  u32* hist = nullptr;
+  u32* base = nullptr;
+};
+// Scratch shared by the single-output operators: histogram replicas, digit bases,
+// onesweep status words (+ tile-claim state) for one side at a time.
+struct OsScratch {
+  u32 *hist = nullptr, *gbase = nullptr, *hist_e = nullptr, *gbase_e = nullptr;
+  u32* status = nullptr;
+  DigitCounts starts() const { return {hist, gbase}; }
+  DigitCounts ends() const { return {hist_e, gbase_e}; }
+};
+
+// One linearize pass: whose rows, where they go, and what else the pass does on the way.
+enum class Side { A = 0, B = 1 };
+struct LinTarget {
+  u32* keys = nullptr;
+  u32* ends = nullptr;      // NULL: the end keys are not wanted
+  u32* irr_list = nullptr;
+  static LinTarget keys_only(u32* keys, u32* irr_list) { return {keys, nullptr, irr_list}; }
+  static LinTarget keys_ends(u32* keys, u32* ends, u32* irr_list) { return {keys, ends, irr_list}; }
+};
+struct LinOptions {
+  bool keep_irregular = false;  // irregular rows keep their real key (they are not listed and given the sentinel)
+  bool skip_end = false;        // a side known to hold no irregular row: its end column is not read
+  DigitCounts starts, ends;     // also produce the onesweep digit offsets of the start keys / of the end keys
+  LinOptions& keeping_irregular() { keep_irregular = true; return *this; }
+  LinOptions& without_end_column(bool yes = true) { skip_end = yes; return *this; }
+  LinOptions& counting_starts(DigitCounts d) { starts = d; return *this; }
+  LinOptions& counting_ends(DigitCounts d) { ends = d; return *this; }
+};
+
+static int run_linearize(giql_hip_ctx* ctx, hipStream_t st, const giql_side& s, int n_chrom, const LinBufs& lb,
+                         Side which, const LinTarget& out, const LinOptions& opt = LinOptions()) {
   if (s.n == 0) return GIQL_OK;
-  const int* end_col = skip_end ? (const int*)nullptr : s.end;  // a side known to hold no irregular row
+  const int* end_col = opt.skip_end ? (const int*)nullptr : s.end;
+  u32* const hist_partial = opt.starts.hist;
+  u32* const hist_end = opt.ends.hist;
   // (a plan zeroes its histograms once, up front -- but this one may hold the span pass's counts of a side that
   // turned out to need the linearize pass after all, layout or form guess not taken: the span pass took it then)
   if (hist_partial) GIQL_TRY(take_zeroed(ctx, st, hist_partial, HIST_BYTES));
@@ -688,102 +760,35 @@ static int run_linearize(giql_hip_ctx* ctx, hipStream_t st, const giql_side& s, 
   if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
   if (hist_end)
     hipLaunchKernelGGL((k_linearize<true>), dim3(grid), dim3(LIN_NT), 0, st, s.chrom, s.start, end_col,
-                       (u32)s.n, s.start_off, s.end_off, n_chrom, lb.chrom_base, keys, ends, irr_list,
-                       ctx->d_meta, which, keep_irregular, hist_partial, hist_end);
+                       (u32)s.n, s.start_off, s.end_off, n_chrom, lb.chrom_base, out.keys, out.ends, out.irr_list,
+                       ctx->d_meta, (int)which, opt.keep_irregular ? 1 : 0, hist_partial, hist_end);
   else
     hipLaunchKernelGGL((k_linearize<false>), dim3(grid), dim3(LIN_NT), 0, st, s.chrom, s.start, end_col,
-                       (u32)s.n, s.start_off, s.end_off, n_chrom, lb.chrom_base, keys, ends, irr_list,
-                       ctx->d_meta, which, keep_irregular, hist_partial, (u32*)nullptr);
+                       (u32)s.n, s.start_off, s.end_off, n_chrom, lb.chrom_base, out.keys, out.ends, out.irr_list,
+                       ctx->d_meta, (int)which, opt.keep_irregular ? 1 : 0, hist_partial, (u32*)nullptr);
   if (hist_partial)
     hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, hist_partial,
-                       (u32)LIN_HIST_REPLICAS, gbase);
+                       (u32)LIN_HIST_REPLICAS, opt.starts.base);
   if (hist_end)
     hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, hist_end, (u32)LIN_HIST_REPLICAS,
-                       gbase_end);
+                       opt.ends.base);
   return post_launch("linearize");
 }
 
-// Onesweep LSD sort (4 passes, one launch each); input and result in
-// buffer 0.  Payload of a sort = which of end / rid buffers the SortBufs carries.
-// status words of ONE pass: a {flag,count} word per (tile, digit) + the ticket word
-static inline size_t os_pass_words(size_t n) {
-  return (size_t)cdiv(n ? n : 1, OS_MIN_TILE) * OS_BINS + 16;
-}
-// ... and what a pass of this context really uses (the default 1024 x 8 block shape has 8192-row tiles: half
-// of the worst case, half the bytes to zero); the ticket word is the stride's 16th-last
-static inline size_t os_pass_stride(const giql_hip_ctx* ctx, size_t n) {
-  return ctx->sw.os_variant == 0 ? (size_t)cdiv(n ? n : 1, 8192) * OS_BINS + 16 : os_pass_words(n);
+// ---------------------------------------------------------------------------------------------- the sort driver
+// Onesweep LSD sort, one launch per global pass; input and result in buffer 0.  What a sort does -- how many passes,
+// on which digits, between which buffers, the bucket stage that follows, the status words to zero, the bytes each
+// phase reports -- is one SortPlan (sort_plan.h, plan_sort); run_sort_onesweep builds it, zeroes what it says and
+// launches what it says.
+
+// Calls f(std::integral_constant<int, M>{}) for the M among Ms that equals m: how a run-time payload, FUSE form or
+// bucket width reaches a kernel's template arguments -- the one dispatcher of every kernel the driver launches.
+// false: m is none of Ms and nothing was called (run_sort_onesweep refuses such a request before it launches anything).
+template <int... Ms, typename F>
+static inline bool dispatch_int(int m, F&& f) {
+  return ((m == Ms && (f(std::integral_constant<int, Ms>{}), true)) || ...);
 }
 
-template <int NT, int ITEMS>
-static void launch_onesweep(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, int src, int dst, bool first,
-                            u32 n, int shift, const u32* gbase, u32* status, DevMeta* meta, int unstable = 0) {
-  const u32 grid = cdiv(n, NT * ITEMS);  // one block per tile
-  u32* claim = status + os_pass_stride(ctx, n) - 16;  // the pass's ticket word
-  const u32* rin = (first || !sb.rid[0]) ? (const u32*)nullptr : sb.rid[src];
-  const int mode = (sb.rid[0] ? 1 : 0) | (sb.end[0] ? 2 : 0);
-#define GIQL_OS_LAUNCH(M)                                                                            \
-  hipLaunchKernelGGL((k_onesweep<M, NT, ITEMS>), dim3(grid), dim3(NT), 0, st, sb.key[src],           \
-                     sb.end[0] ? sb.end[src] : (const u32*)nullptr, rin, sb.key[dst],                 \
-                     sb.end[0] ? sb.end[dst] : (u32*)nullptr, sb.rid[0] ? sb.rid[dst] : (u32*)nullptr, \
-                     n, shift, gbase, status, claim, meta, ctx->guess.os_order, ctx->sw.os_help_after, (const u32*)nullptr, 0u, 0u,  \
-                     unstable)
-  switch (mode) {
-    case 0: GIQL_OS_LAUNCH(0); break;
-    case 1: GIQL_OS_LAUNCH(1); break;
-    case 2: GIQL_OS_LAUNCH(2); break;
-    default: GIQL_OS_LAUNCH(3); break;
-  }
-#undef GIQL_OS_LAUNCH
-}
-
-// keep_rids: the rid buffer already holds row ids (second sort of a two-key sort).
-// status: 4 * os_pass_words(n) words, zeroed here in one memset.
-// keygen (with abase): the first pass builds the keys from that side's raw (chrom, start)
-// columns instead of reading sb.key[0] (k_onesweep<.., KEYGEN>; (key, rid) sorts, default
-// block shape only).
-// Sides of ctx->sw.local_min_rows rows and more take the three-stage form: global passes on bits
-// 16-23 and 24-31 only, then every 16-bit bucket sorted on its low bits inside LDS, in place
-// (bucket_sort.hip.h) -- three trips through HBM instead of four.
-// the narrowest-needed bucket for a table of per_bucket rows per 65,536 keys on average (0: too dense for any)
-static inline int density_bits(const giql_hip_ctx* ctx, double per_bucket) {
-  int w = 16;
-  while (per_bucket > ctx->sw.local_max_bucket_rows && w > BS_MIN_WBITS && !ctx->sw.no_narrow) {
-    per_bucket *= 0.5;
-    w--;
-  }
-  return per_bucket <= ctx->sw.local_max_bucket_rows ? w : 0;
-}
-
-// Returns 0 (four global passes) or the key bits of a bucket: 16 (two global passes), or 15 / 14 / 13 for denser
-// tables (three global passes -- bits 8-15, 16-23, 24-31 -- and buckets of 2^W keys: bucket_sort.hip.h).
-static inline int sort_local_bits(const giql_hip_ctx* ctx, size_t n) {
-  if (ctx->call.force_local > 0 && ctx->bucket_bnd && ctx->sw.os_variant == 0) return ctx->call.index_bits;
-  if (ctx->call.force_local < 0) return 0;
-  if (!(ctx->guess.local_sort && ctx->bucket_bnd && ctx->sw.os_variant == 0 && n >= ctx->sw.local_min_rows)) return 0;
-  // The in-LDS stage holds 4096 rows per bucket; larger buckets go through a slow queue (one block each, two
-  // more passes: 30M x 300M reads, ~6000 rows per bucket, spent 10.4 of 21 ms there).  So the form is taken
-  // only while the AVERAGE bucket is comfortably below that -- by the span of the context's previous call
-  // (a human-genome-sized axis until one has run); denser tables take the four global passes.  The value is
-  // constant during a call (updated when it ends), so every decision of one call agrees.
-  // Round 4: what decides is the DENSITY, not the row count -- a 12.5M-row shard of an 8-GPU run has the headline's
-  // ~2,100 rows per bucket on an eighth of the axis and takes the same path (fused count, join in the bucket stage);
-  // a 10M-row table over the whole genome (212 rows per bucket) does not: a block per bucket is mostly overhead there
-  // (0.135 ms against 0.106 for the two passes it replaces).
-  // Round 4, bucket width by density: past 2,800 rows per 65,536 keys (132M rows on a human-genome axis) the bucket
-  // narrows -- 2^15, 2^14, 2^13 keys, up to ~1G rows -- instead of the form being given up.
-  const double span = ctx->guess.last_span ? (double)ctx->guess.last_span : 3.2e9;
-  double per_bucket = (double)n * 65536.0 / span;
-  if (per_bucket < ctx->sw.local_min_bucket_rows) return 0;
-  if (ctx->sw.force_bits) return ctx->sw.force_bits;
-  return density_bits(ctx, per_bucket);
-}
-static inline int local_passes(int wbits) { return wbits == 16 ? 2 : 3; }  // global passes before the bucket stage
-
-// skip_digits = 1 (four-pass form only): the lowest digit is left unsorted -- rows come out ordered
-// by key >> 8 and the result is left in buffer 0 by swapping the ping-pong pointers.  For QUERY
-// sides whose order only serves locality (neighbouring rows search neighbouring ranges): three
-// passes instead of four.
 // fuse (three-stage (key, rid) sorts only): the bucket sort also answers the range bounds of the
 // fixed-length INNER form's query rows and does not store the sorted keys (bucket_sort.hip.h).
 struct FuseCount {
@@ -798,228 +803,226 @@ struct FuseCount {
   bool join = false;    // FUSE == 2: the bucket blocks write the pairs themselves (dev.row_q / row_s / cap / cursor)
   bool general = false; // FUSE == 3: ... of the two-class join (rows of any length, (key, end, rid) sorts)
   const int* len_max_u = nullptr;  // DevMeta: longest row of the sorted side (general form: how far the windows reach up)
+  SortFuse kind() const { return general ? SortFuse::GENERAL_JOIN : join ? SortFuse::JOIN : SortFuse::BOUNDS; }
 };
 
-static int64_t bucket_stage_fused_bytes(u32 n, const FuseCount& fuse);
-// The bucket stage of a fused (key, rid) sort: bounds only (FUSE 1) or the whole join (FUSE 2).  Three launches,
-// each a phase of its own so that the stage's ONE heavy kernel can be timed alone: the bucket boundaries and query
-// windows (COUNT), the bucket kernel (SORT_LOCAL), the queue of buckets it could not take (AUX; almost always an
-// empty launch).
-static void launch_bucket_stage_fused(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u32 n, const u32* gbase,
-                                      const FuseCount& fuse_in, int wbits = 16) {
-  FuseCount fuse = fuse_in;
-  fuse.dev.wbits = (u32)wbits;
-  const u32 BS_BUCKETS = bs_n_buckets((u32)wbits);  // (shadows the 16-bit constant: every launch below is per bucket)
-  ctx->stats.phase_bytes[GIQL_PH_SORT_LOCAL] += bucket_stage_fused_bytes(n, fuse);
-  ctx->call.count_fused = true;
-  ctx->call.bucket_join = fuse.join;
-  ctx->call.last_local_bits = wbits;
-  {
-    Phase ph(ctx, st, GIQL_PH_COUNT, 1);
-    hipLaunchKernelGGL(k_bucket_bounds_fused, dim3(cdiv((u64)3 * BS_BUCKETS + 1, 256)), dim3(256), 0, st, sb.key[0], n,
-                       gbase + 3 * OS_BINS, ctx->bucket_bnd, ctx->bucket_big, fuse.dev, fuse.nq_total, fuse.irr_q,
-                       fuse.gbq3, fuse.key_mask, fuse.len_max_q, fuse.zero_ptr, fuse.zero_words, fuse.len_max_u);
+// One sort of n rows in a SortBufs.  rows() names what every sort has; the rest is set by name.
+struct SortRequest {
+  u32 n = 0;
+  const u32* digit_base = nullptr;  // [4][OS_BINS] exclusive digit offsets of the keys (k_digit_offsets)
+  u32* status = nullptr;            // 4 * os_pass_words(n) words; the passes' share is zeroed here unless the call's one memset covered it
+  bool keep_rids = false;           // the rid buffer already holds row ids (second sort of a two-key sort)
+  // the first pass builds the keys from that side's raw (chrom, start) columns and the 2^24-aligned chromosome bases
+  // instead of reading key[0] (k_onesweep<.., KEYGEN>; sorts with row ids, default block shape only)
+  const giql_side* keygen = nullptr;
+  const u32* abase = nullptr;
+  // global-passes form only: that many low digits are left unsorted -- rows come out ordered by key >> 8 (>> 16).  For
+  // QUERY sides whose order only serves locality (neighbouring rows search neighbouring ranges)
+  int skip_digits = 0;
+  const FuseCount* fuse = nullptr;  // the bucket stage also answers the other side's query rows
+  bool presorted = false;           // the side arrives sorted: no scatter pass
+
+  static SortRequest rows(u32 n, const u32* digit_base, u32* status) {
+    SortRequest r;
+    r.n = n, r.digit_base = digit_base, r.status = status;
+    return r;
   }
-  const bool w16 = wbits == 16;
-#define GIQL_BSF_LAUNCH(P, F, W)                                                                                    \
-  hipLaunchKernelGGL((k_bucket_sort<P, F, W>), dim3(BS_BUCKETS), dim3(BS_NT), 0, st, sb.key[0],                      \
-                     (P) == 3 ? sb.end[0] : (u32*)nullptr, sb.rid[0], ctx->bucket_bnd, ctx->d_meta, ctx->bucket_big, \
-                     fuse.dev)
-  if (fuse.general) {
-    {
-      Phase ph(ctx, st, GIQL_PH_SORT_LOCAL, 1);
-      if (w16) GIQL_BSF_LAUNCH(3, 3, true); else GIQL_BSF_LAUNCH(3, 3, false);
-    }
-    Phase ph(ctx, st, GIQL_PH_AUX, 1);
-    hipLaunchKernelGGL((k_bucket_sort_big<3, 3>), dim3(ctx->n_cu), dim3(BS_NT), 0, st, sb.key[0], sb.end[0], sb.rid[0],
-                       sb.key[1], sb.end[1], sb.rid[1], ctx->bucket_bnd, ctx->bucket_big, fuse.dev);
-    return;
+  SortRequest& keeping_rids() { keep_rids = true; return *this; }
+  SortRequest& keys_from(const giql_side* side, const u32* aligned_base) { keygen = side, abase = aligned_base; return *this; }
+  SortRequest& skipping_digits(int k) { skip_digits = k; return *this; }
+  SortRequest& fused_with(const FuseCount* f) { fuse = f; return *this; }
+  SortRequest& already_sorted(bool yes) { presorted = yes; return *this; }
+  SortOptions options() const {
+    SortOptions o;
+    o.keep_rids = keep_rids;
+    o.keygen = keygen != nullptr;
+    o.skip_digits = skip_digits;
+    o.fuse = fuse ? fuse->kind() : SortFuse::NONE;
+    o.fuse_queries = fuse ? fuse->nq_total : 0;
+    o.presorted = presorted;
+    return o;
   }
-  {
-    Phase ph(ctx, st, GIQL_PH_SORT_LOCAL, 1);
-    if (fuse.join) {
-      if (w16) GIQL_BSF_LAUNCH(1, 2, true); else GIQL_BSF_LAUNCH(1, 2, false);
-    } else {
-      if (w16) GIQL_BSF_LAUNCH(1, 1, true); else GIQL_BSF_LAUNCH(1, 1, false);
-    }
-  }
-#undef GIQL_BSF_LAUNCH
-  {
-    Phase ph(ctx, st, GIQL_PH_AUX, 1);
-    if (fuse.join)
-      hipLaunchKernelGGL((k_bucket_sort_big<1, 2>), dim3(ctx->n_cu), dim3(BS_NT), 0, st, sb.key[0], (u32*)nullptr,
-                         sb.rid[0], sb.key[1], (u32*)nullptr, sb.rid[1], ctx->bucket_bnd, ctx->bucket_big, fuse.dev);
-    else
-      hipLaunchKernelGGL((k_bucket_sort_big<1, 1>), dim3(ctx->n_cu), dim3(BS_NT), 0, st, sb.key[0], (u32*)nullptr,
-                         sb.rid[0], sb.key[1], (u32*)nullptr, sb.rid[1], ctx->bucket_bnd, ctx->bucket_big, fuse.dev);
-  }
-}
-// its algorithmic bytes up to the pairs (8 B each, added once the count is known): the rows' keys and ids read;
-// bounds form: the ids written, the queries' keys and end keys read, two bounds each written; join form: the
-// queries' keys, end keys and ids read
-static int64_t bucket_stage_fused_bytes(u32 n, const FuseCount& fuse) {
-  if (fuse.general) return (int64_t)12 * n + (int64_t)12 * fuse.nq_total;  // (key, end, rid) of both sides read
-  return fuse.join ? (int64_t)8 * n + (int64_t)12 * fuse.nq_total : (int64_t)12 * n + (int64_t)16 * fuse.nq_total;
+};
+// the sorts of an operator's scratch: by the digit bases of its start keys / of its end keys, through its status words
+static inline SortRequest sort_by_start(const OsScratch& os, size_t n) { return SortRequest::rows((u32)n, os.gbase, os.status); }
+static inline SortRequest sort_by_end(const OsScratch& os, size_t n) { return SortRequest::rows((u32)n, os.gbase_e, os.status); }
+static inline SortPlan plan_of(const giql_hip_ctx* ctx, const SortBufs& sb, const SortRequest& rq) {
+  return plan_sort(sort_tuning(ctx), rq.n, sb.payload(), rq.options());
 }
 
-static int run_sort_onesweep(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u32 n,
-                             const u32* gbase, u32* status, bool keep_rids = false,
-                             const giql_side* keygen = nullptr, const u32* abase = nullptr,
-                             int skip_digits = 0, const FuseCount* fuse = nullptr, bool presorted = false) {
-  if (n == 0) return GIQL_OK;
-  if (presorted) {
-    // the side arrives sorted: no scatter pass, one streaming pass for what a sort would have left in buffer 0
-    const int mode = (sb.rid[0] ? 1 : 0) | (sb.end[0] ? 2 : 0);
-    const int wbits_pre = sort_local_bits(ctx, n);
-    const bool local_fused = fuse && mode == (fuse->general ? 3 : 1) && wbits_pre != 0;
-    {
-      Phase ph(ctx, st, GIQL_PH_SORT_SCATTER, 1);
-      u32 grid = cdiv(n, 256 * 8);
-      if (grid > GIQL_STREAM_GRID) grid = GIQL_STREAM_GRID;
-      if (keygen) {
-        ctx->stats.phase_bytes[GIQL_PH_SORT_SCATTER] += (int64_t)4 * n * ((mode & 2 ? 3 : 2) + 1 + (mode & 1) + (mode & 2 ? 1 : 0));
-        const u32 so = (u32)keygen->start_off, eo = (u32)keygen->end_off;
-        switch (mode) {
-          case 0: hipLaunchKernelGGL(k_keygen_stream<0>, dim3(grid), dim3(256), 0, st, keygen->chrom, keygen->start, keygen->end, n, abase, so, eo, sb.key[0], (u32*)nullptr, (u32*)nullptr); break;
-          case 1: hipLaunchKernelGGL(k_keygen_stream<1>, dim3(grid), dim3(256), 0, st, keygen->chrom, keygen->start, keygen->end, n, abase, so, eo, sb.key[0], (u32*)nullptr, sb.rid[0]); break;
-          case 2: hipLaunchKernelGGL(k_keygen_stream<2>, dim3(grid), dim3(256), 0, st, keygen->chrom, keygen->start, keygen->end, n, abase, so, eo, sb.key[0], sb.end[0], (u32*)nullptr); break;
-          default: hipLaunchKernelGGL(k_keygen_stream<3>, dim3(grid), dim3(256), 0, st, keygen->chrom, keygen->start, keygen->end, n, abase, so, eo, sb.key[0], sb.end[0], sb.rid[0]); break;
-        }
-      } else if (sb.rid[0] && !keep_rids) {
-        ctx->stats.phase_bytes[GIQL_PH_SORT_SCATTER] += (int64_t)4 * n;
-        hipLaunchKernelGGL(k_iota, dim3(grid), dim3(256), 0, st, sb.rid[0], n);
-      }
-      GIQL_TRY(post_launch("sorted input (no sort)"));
+// one global pass that reads the keys (block shape NT x ITEMS)
+template <int NT, int ITEMS>
+static void launch_onesweep(giql_hip_ctx* ctx, hipStream_t st, const SortBufs& sb, const SortPass& p, u32 n,
+                            const u32* gbase, u32* status, u32* claim) {
+  const u32 grid = cdiv(n, NT * ITEMS);  // one block per tile
+  const u32* rin = (p.first || !sb.rid[0]) ? (const u32*)nullptr : sb.rid[p.src];
+  dispatch_int<0, 1, 2, 3>((int)sb.payload(), [&](auto mode) {
+    hipLaunchKernelGGL((k_onesweep<decltype(mode)::value, NT, ITEMS>), dim3(grid), dim3(NT), 0, st, sb.key[p.src],
+                       sb.end[0] ? sb.end[p.src] : (const u32*)nullptr, rin, sb.key[p.dst],
+                       sb.end[0] ? sb.end[p.dst] : (u32*)nullptr, sb.rid[0] ? sb.rid[p.dst] : (u32*)nullptr, n,
+                       p.digit * 8, gbase, status, claim, ctx->d_meta, ctx->guess.os_order, ctx->sw.os_help_after,
+                       (const u32*)nullptr, 0u, 0u, p.unstable ? 1 : 0);
+  });
+}
+
+// ... and the first pass that builds them from the raw columns
+static void launch_onesweep_keygen(giql_hip_ctx* ctx, hipStream_t st, const SortBufs& sb, const SortPass& p, u32 n,
+                                   const u32* gbase, u32* status, u32* claim, const giql_side& raw, const u32* abase) {
+  const u32 grid = cdiv(n, 1024 * 8);
+  const u32 *start = reinterpret_cast<const u32*>(raw.start), *chrom = reinterpret_cast<const u32*>(raw.chrom);
+  // (key, rid): start, chrom.  (key, end, rid): start, end, chrom -- the end keys are built from the raw end column as well
+  dispatch_int<1, 3>((int)sb.payload(), [&](auto mode) {
+    constexpr bool ENDS = decltype(mode)::value == 3;
+    hipLaunchKernelGGL((k_onesweep<decltype(mode)::value, 1024, 8, true>), dim3(grid), dim3(1024), 0, st, start,
+                       ENDS ? reinterpret_cast<const u32*>(raw.end) : chrom, ENDS ? chrom : (const u32*)nullptr,
+                       sb.key[p.dst], ENDS ? sb.end[p.dst] : (u32*)nullptr, sb.rid[p.dst], n, p.digit * 8, gbase, status, claim, ctx->d_meta,
+                       ctx->guess.os_order, ctx->sw.os_help_after, abase, (u32)raw.start_off,
+                       ENDS ? (u32)raw.end_off : 0u, p.unstable ? 1 : 0);
+  });
+}
+
+// The global passes of a plan: one event pair around them (an event record between two launches costs the
+// stream ~8 us of idle time; the per-launch time is phase time / launches).
+static void launch_passes(giql_hip_ctx* ctx, hipStream_t st, const SortBufs& sb, const SortRequest& rq, const SortPlan& plan) {
+  Phase ph(ctx, st, GIQL_PH_SORT_SCATTER, plan.n_pass);
+  for (int k = 0; k < plan.n_pass; k++) {
+    const SortPass& p = plan.pass[k];
+    u32* stat = rq.status + k * plan.pass_stride;
+    u32* claim = stat + plan.pass_stride - 16;  // the pass's ticket word
+    const u32* gb = rq.digit_base + p.digit * OS_BINS;
+    ctx->stats.phase_bytes[GIQL_PH_SORT_SCATTER] += p.bytes;
+    if (p.keygen) {
+      launch_onesweep_keygen(ctx, st, sb, p, rq.n, gb, stat, claim, *rq.keygen, rq.abase);
+      continue;
     }
-    if (!local_fused) return GIQL_OK;   // sorted already: the bucket stage only runs as the carrier of the fused count
-    ctx->call.last_sort_local = true;
-    launch_bucket_stage_fused(ctx, st, sb, n, gbase, *fuse, wbits_pre);
-    return post_launch("bucket stage (sorted input, fused count)");
-  }
-  const int wbits = sort_local_bits(ctx, n);
-  const bool local = wbits != 0;
-  if (local) ctx->call.last_sort_local = true;
-  if (local) skip_digits = 0;
-  const int n_pass = local ? local_passes(wbits) : 4 - skip_digits;
-  const int first_digit = local ? 4 - n_pass : skip_digits;
-  const size_t per_pass = os_pass_stride(ctx, n);
-  GIQL_TRY(take_zeroed(ctx, st, status, n_pass * per_pass * sizeof(u32)));
-  {
-    // one event pair around the passes (an event record between two launches costs the
-    // stream ~8 us of idle time; the per-launch time is phase time / launches)
-    Phase ph(ctx, st, GIQL_PH_SORT_SCATTER, n_pass);
-    for (int pass = 0; pass < n_pass; pass++) {
-      const int src = pass & 1, dst = src ^ 1;
-      const int digit = first_digit + pass;
-      u32* stat = status + pass * per_pass;
-      const bool first = pass == 0 && !keep_rids;
-      const u32* gb = gbase + digit * OS_BINS;
-      {
-        // algorithmic bytes of this pass: every array it reads + every array it writes, 4 B per row
-        // (KEYGEN reads chrom + start instead of the key; a first pass synthesises the row ids)
-        const int w_out = 1 + (sb.rid[0] ? 1 : 0) + (sb.end[0] ? 1 : 0);
-        const int w_in = (pass == 0 && keygen) ? 2 + (sb.end[0] ? 1 : 0)
-                                               : 1 + ((sb.rid[0] && !first) ? 1 : 0) + (sb.end[0] ? 1 : 0);
-        ctx->stats.phase_bytes[GIQL_PH_SORT_SCATTER] += (int64_t)4 * (w_in + w_out) * n;
-      }
-      const int unstable = (pass == 0 && !keep_rids && ctx->call.first_unstable) ? 1 : 0;
-      if (pass == 0 && keygen) {
-        const u32 grid = cdiv(n, 1024 * 8);
-        u32* claim = stat + per_pass - 16;
-        if (sb.end[0])  // (key, end, rid): the end keys are built from the raw end column as well
-          hipLaunchKernelGGL((k_onesweep<3, 1024, 8, true>), dim3(grid), dim3(1024), 0, st,
-                             reinterpret_cast<const u32*>(keygen->start), reinterpret_cast<const u32*>(keygen->end),
-                             reinterpret_cast<const u32*>(keygen->chrom), sb.key[dst], sb.end[dst], sb.rid[dst], n,
-                             digit * 8, gb, stat, claim, ctx->d_meta, ctx->guess.os_order, ctx->sw.os_help_after, abase,
-                             (u32)keygen->start_off, (u32)keygen->end_off, unstable);
-        else
-          hipLaunchKernelGGL((k_onesweep<1, 1024, 8, true>), dim3(grid), dim3(1024), 0, st,
-                             reinterpret_cast<const u32*>(keygen->start), reinterpret_cast<const u32*>(keygen->chrom),
-                             (const u32*)nullptr, sb.key[dst], (u32*)nullptr, sb.rid[dst], n, digit * 8, gb, stat, claim,
-                             ctx->d_meta, ctx->guess.os_order, ctx->sw.os_help_after, abase, (u32)keygen->start_off, 0u, unstable);
-        continue;
-      }
-      switch (ctx->sw.os_variant) {  // block-shape sweep (tools/os_variants.py); default 1024 x 8
-        case 1: launch_onesweep<512, 8>(ctx, st, sb, src, dst, first, n, digit * 8, gb, stat, ctx->d_meta, unstable); break;
-        case 2: launch_onesweep<512, 16>(ctx, st, sb, src, dst, first, n, digit * 8, gb, stat, ctx->d_meta, unstable); break;
-        case 3: launch_onesweep<256, 16>(ctx, st, sb, src, dst, first, n, digit * 8, gb, stat, ctx->d_meta, unstable); break;
-        case 4: launch_onesweep<1024, 4>(ctx, st, sb, src, dst, first, n, digit * 8, gb, stat, ctx->d_meta, unstable); break;
-        case 5: case 7: launch_onesweep<1024, 12>(ctx, st, sb, src, dst, first, n, digit * 8, gb, stat, ctx->d_meta, unstable); break;
-        default: launch_onesweep<1024, 8>(ctx, st, sb, src, dst, first, n, digit * 8, gb, stat, ctx->d_meta, unstable); break;
-      }
+    switch (ctx->sw.os_variant) {  // block-shape sweep (tools/os_variants.py); default 1024 x 8
+      case 1: launch_onesweep<512, 8>(ctx, st, sb, p, rq.n, gb, stat, claim); break;
+      case 2: launch_onesweep<512, 16>(ctx, st, sb, p, rq.n, gb, stat, claim); break;
+      case 3: launch_onesweep<256, 16>(ctx, st, sb, p, rq.n, gb, stat, claim); break;
+      case 4: launch_onesweep<1024, 4>(ctx, st, sb, p, rq.n, gb, stat, claim); break;
+      case 5: case 7: launch_onesweep<1024, 12>(ctx, st, sb, p, rq.n, gb, stat, claim); break;
+      default: launch_onesweep<1024, 8>(ctx, st, sb, p, rq.n, gb, stat, claim); break;
     }
   }
-  if (n_pass & 1) {  // an odd number of passes ends in buffer 1: make that "buffer 0"
-    u32* t;
-    t = sb.key[0], sb.key[0] = sb.key[1], sb.key[1] = t;
-    t = sb.end[0], sb.end[0] = sb.end[1], sb.end[1] = t;
-    t = sb.rid[0], sb.rid[0] = sb.rid[1], sb.rid[1] = t;
-  }
-  if (local) {
-    // the rows are back in buffer 0, ordered by key >> 16: bucket boundaries, then one block per bucket
-    const int mode = (sb.rid[0] ? 1 : 0) | (sb.end[0] ? 2 : 0);
-    if (fuse && mode == (fuse->general ? 3 : 1)) {
-      // (key, rid) rows + the query side's bounds: keys and rids read, rids written, the query rows' keys
-      // and ends read and their two bounds written -- the sorted keys never leave the CU
-      launch_bucket_stage_fused(ctx, st, sb, n, gbase, *fuse, wbits);
-      return post_launch("onesweep sort (fused count)");
-    }
-    BsFuse bw;  // the plain sort: only the bucket width travels
-    bw.wbits = (u32)wbits;
-    ctx->call.last_local_bits = wbits;
-    const u32 BS_BUCKETS = bs_n_buckets((u32)wbits);
+}
+
+// The presorted form: no scatter pass, one streaming pass for what a sort would have left in buffer 0.
+static int launch_sorted_input(giql_hip_ctx* ctx, hipStream_t st, const SortBufs& sb, const SortRequest& rq, const SortPlan& plan) {
+  Phase ph(ctx, st, GIQL_PH_SORT_SCATTER, 1);
+  const u32 n = rq.n;
+  u32 grid = cdiv(n, 256 * 8);
+  if (grid > GIQL_STREAM_GRID) grid = GIQL_STREAM_GRID;
+  ctx->stats.phase_bytes[GIQL_PH_SORT_SCATTER] += plan.stream_bytes;
+  if (plan.stream == StreamKernel::KEYGEN)
+    dispatch_int<0, 1, 2, 3>((int)sb.payload(), [&](auto mode) {
+      hipLaunchKernelGGL(k_keygen_stream<decltype(mode)::value>, dim3(grid), dim3(256), 0, st, rq.keygen->chrom,
+                         rq.keygen->start, rq.keygen->end, n, rq.abase, (u32)rq.keygen->start_off,
+                         (u32)rq.keygen->end_off, sb.key[0], sb.end[0], sb.rid[0]);
+    });
+  else if (plan.stream == StreamKernel::IOTA)
+    hipLaunchKernelGGL(k_iota, dim3(grid), dim3(256), 0, st, sb.rid[0], n);
+  return post_launch("sorted input (no sort)");
+}
+
+// The bucket stage: the rows are in buffer 0, ordered by key >> wbits; bucket boundaries, then one block per bucket,
+// then the queue of buckets too large for LDS (almost always an empty launch).
+//   plain: the three launches are one phase (SORT_LOCAL); only the bucket width travels to the kernels;
+//   fused (bounds only, FUSE 1; the whole join, FUSE 2 / 3): each launch a phase of its own so that the stage's ONE
+//     heavy kernel can be timed alone -- the boundaries and query windows (COUNT), the bucket kernel (SORT_LOCAL), the
+//     queue (AUX).  (key, rid) rows + the query side's bounds: the sorted keys never leave the CU.
+static int launch_bucket_stage(giql_hip_ctx* ctx, hipStream_t st, const SortBufs& sb, const SortPlan& plan, u32 n,
+                               const u32* digit_base, const FuseCount* fuse_count) {
+  const bool fused = plan.stage == BucketStage::FUSED;
+  const u32 wbits = (u32)plan.wbits;
+  const u32 buckets = bs_n_buckets(wbits);
+  const u32* gb3 = digit_base + 3 * OS_BINS;
+  BsFuse dev;
+  if (fused) dev = fuse_count->dev;
+  dev.wbits = wbits;
+  ctx->call.last_local_bits = plan.wbits;
+  ctx->stats.phase_bytes[GIQL_PH_SORT_LOCAL] += plan.stage_bytes;
+  auto sort_buckets = [&](auto payload, auto fuse) {
+    dispatch_int<0, 1>(wbits == 16 ? 1 : 0, [&](auto w16) {
+      hipLaunchKernelGGL((k_bucket_sort<decltype(payload)::value, decltype(fuse)::value, decltype(w16)::value != 0>),
+                         dim3(buckets), dim3(BS_NT), 0, st, sb.key[0], sb.end[0], sb.rid[0], ctx->bucket_bnd, ctx->d_meta,
+                         ctx->bucket_big, dev);
+    });
+  };
+  auto sort_queue = [&](auto payload, auto fuse) {
+    hipLaunchKernelGGL((k_bucket_sort_big<decltype(payload)::value, decltype(fuse)::value>), dim3(ctx->n_cu), dim3(BS_NT),
+                       0, st, sb.key[0], sb.end[0], sb.rid[0], sb.key[1], sb.end[0] ? sb.end[1] : (u32*)nullptr,
+                       sb.rid[0] ? sb.rid[1] : (u32*)nullptr, ctx->bucket_bnd, ctx->bucket_big, dev);
+  };
+  if (!fused) {
     HIP_TRY(hipMemsetAsync(ctx->bucket_big, 0, sizeof(u32), st));
     Phase ph(ctx, st, GIQL_PH_SORT_LOCAL, 3);
-    ctx->stats.phase_bytes[GIQL_PH_SORT_LOCAL] +=
-        (int64_t)8 * (1 + (sb.rid[0] ? 1 : 0) + (sb.end[0] ? 1 : 0)) * n;  // every array read once, written once
-    hipLaunchKernelGGL(k_bucket_bounds, dim3(cdiv((u64)BS_BUCKETS + 1, 256)), dim3(256), 0, st, sb.key[0], n,
-                       gbase + 3 * OS_BINS, ctx->bucket_bnd, (u32)wbits);
-#define GIQL_BS_LAUNCH(M)                                                                              \
-  if (wbits == 16)                                                                                     \
-    hipLaunchKernelGGL((k_bucket_sort<M, 0, true>), dim3(BS_BUCKETS), dim3(BS_NT), 0, st, sb.key[0],   \
-                       sb.end[0] ? sb.end[0] : (u32*)nullptr, sb.rid[0] ? sb.rid[0] : (u32*)nullptr,    \
-                       ctx->bucket_bnd, ctx->d_meta, ctx->bucket_big, bw);                             \
-  else                                                                                                 \
-  hipLaunchKernelGGL((k_bucket_sort<M>), dim3(BS_BUCKETS), dim3(BS_NT), 0, st, sb.key[0],              \
-                     sb.end[0] ? sb.end[0] : (u32*)nullptr, sb.rid[0] ? sb.rid[0] : (u32*)nullptr,      \
-                     ctx->bucket_bnd, ctx->d_meta, ctx->bucket_big, bw);                               \
-  hipLaunchKernelGGL((k_bucket_sort_big<M>), dim3(ctx->n_cu), dim3(BS_NT), 0, st, sb.key[0],           \
-                     sb.end[0] ? sb.end[0] : (u32*)nullptr, sb.rid[0] ? sb.rid[0] : (u32*)nullptr,      \
-                     sb.key[1], sb.end[0] ? sb.end[1] : (u32*)nullptr, sb.rid[0] ? sb.rid[1] : (u32*)nullptr, \
-                     ctx->bucket_bnd, ctx->bucket_big, bw)
-    switch (mode) {
-      case 0: GIQL_BS_LAUNCH(0); break;
-      case 1: GIQL_BS_LAUNCH(1); break;
-      case 2: GIQL_BS_LAUNCH(2); break;
-      default: GIQL_BS_LAUNCH(3); break;
-    }
-#undef GIQL_BS_LAUNCH
+    hipLaunchKernelGGL(k_bucket_bounds, dim3(cdiv((u64)buckets + 1, 256)), dim3(256), 0, st, sb.key[0], n, gb3,
+                       ctx->bucket_bnd, wbits);
+    dispatch_int<0, 1, 2, 3>(plan.stage_payload, [&](auto payload) {
+      sort_buckets(payload, std::integral_constant<int, 0>{});
+      sort_queue(payload, std::integral_constant<int, 0>{});
+    });
+    return GIQL_OK;
   }
-  return post_launch("onesweep sort");
+  const FuseCount& fc = *fuse_count;
+  ctx->call.count_fused = true;
+  ctx->call.bucket_join = fc.join;
+  {
+    Phase ph(ctx, st, GIQL_PH_COUNT, 1);
+    hipLaunchKernelGGL(k_bucket_bounds_fused, dim3(cdiv((u64)3 * buckets + 1, 256)), dim3(256), 0, st, sb.key[0], n, gb3,
+                       ctx->bucket_bnd, ctx->bucket_big, dev, fc.nq_total, fc.irr_q, fc.gbq3, fc.key_mask, fc.len_max_q,
+                       fc.zero_ptr, fc.zero_words, fc.len_max_u);
+  }
+  // the payload a fused form reads follows from the form: (key, end, rid) for the general join, else (key, rid)
+  auto with_form = [&](auto&& launch) {
+    dispatch_int<1, 2, 3>(plan.stage_fuse, [&](auto fuse) {
+      launch(std::integral_constant<int, decltype(fuse)::value == 3 ? 3 : 1>{}, fuse);
+    });
+  };
+  {
+    Phase ph(ctx, st, GIQL_PH_SORT_LOCAL, 1);
+    with_form(sort_buckets);
+  }
+  Phase ph(ctx, st, GIQL_PH_AUX, 1);
+  with_form(sort_queue);
+  return GIQL_OK;
+}
+
+static int run_sort_onesweep(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, const SortRequest& rq) {
+  if (rq.n == 0) return GIQL_OK;
+  const SortPlan plan = plan_of(ctx, sb, rq);
+  if (rq.keygen && !plan.presorted && !has_rid(sb.payload()))
+    return set_err(GIQL_ERR_STATE, "internal: a sort pass that builds its keys writes row ids, this sort carries none");
+  if (plan.presorted) {
+    GIQL_TRY(launch_sorted_input(ctx, st, sb, rq, plan));
+    if (plan.stage == BucketStage::NONE) return GIQL_OK;
+  } else {
+    GIQL_TRY(take_zeroed(ctx, st, rq.status, plan.status_words * sizeof(u32)));
+    launch_passes(ctx, st, sb, rq, plan);
+    if (plan.result_buf) sb.flip();  // the rows are in physical buffer 1: make that "buffer 0"
+  }
+  if (plan.stage != BucketStage::NONE) {
+    ctx->call.last_sort_local = true;
+    GIQL_TRY(launch_bucket_stage(ctx, st, sb, plan, rq.n, rq.digit_base, rq.fuse));
+  }
+  return post_launch(plan.presorted                         ? "bucket stage (sorted input, fused count)"
+                     : plan.stage == BucketStage::FUSED ? "onesweep sort (fused count)"
+                                                        : "onesweep sort");
 }
 
 // The stable two-key sort: (key, end) lexicographic order = stable sort by end, then stable sort by key (which keeps the
-// row ids the first sort left).  gbase_key / gbase_end: the digit bases of the two columns; both sorts go through the
-// one set of status words.
+// row ids the first sort left).  Both sorts go through the one set of status words; the digit bases are the scratch's
+// two (starts: the keys, ends: the end keys).
 // The FIRST sort runs on a view of the buffers with key and end exchanged.  run_sort_onesweep leaves its result in what
 // it then CALLS buffer 0 -- after an odd number of passes (three: a query side sorted without its lowest digit, a side
-// with buckets narrower than 2^16 keys) that is the other physical buffer, and it says so by exchanging the view's
-// pointers.  The owner of the buffers has to follow, or its second sort starts from the unsorted copy (round 4: found
-// by the soak on a context forced to 8,192-key buckets -- ties among equal starts came out in input order).
-static int run_sort_two_keys(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u32 n, const u32* gbase_key,
-                             const u32* gbase_end, u32* status) {
-  SortBufs by_end = sb;
-  for (int k = 0; k < 2; k++) {
-    by_end.key[k] = sb.end[k];
-    by_end.end[k] = sb.key[k];
-  }
-  GIQL_TRY(run_sort_onesweep(ctx, st, by_end, n, gbase_end, status));
-  for (int k = 0; k < 2; k++) {
-    sb.end[k] = by_end.key[k];
-    sb.key[k] = by_end.end[k];
-    sb.rid[k] = by_end.rid[k];
-  }
-  return run_sort_onesweep(ctx, st, sb, n, gbase_key, status, /*keep_rids=*/true);
+// with buckets narrower than 2^16 keys) that is the other physical buffer, and SortBufs::flip() says so on the view.
+// The owner of the buffers has to follow (SortBufs::follow), or its second sort starts from the unsorted copy (round 4:
+// found by the soak on a context forced to 8,192-key buckets -- ties among equal starts came out in input order).
+static int run_sort_two_keys(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u32 n, const OsScratch& os) {
+  SortBufs by_end = sb.keyed_by_end();
+  GIQL_TRY(run_sort_onesweep(ctx, st, by_end, sort_by_end(os, n)));
+  sb.follow(by_end);
+  return run_sort_onesweep(ctx, st, sb, sort_by_start(os, n).keeping_rids());
 }
 
 // Stable LSD radix sort; input in buffer 0, result in buffer 0 (4 passes).
@@ -1121,25 +1124,6 @@ static void sort_sizes_starts_ends(Carver& c, size_t n, SortBufs& sstart, SortBu
   }
 }
 
-// Low digits the per-row operators leave unsorted on their QUERY side (its order only serves locality: the
-// rows of a block should search neighbouring ranges of B).  One digit always; two (rows ordered by key >> 16
-// only: two passes instead of three) when B is sparse enough that a 65536-key range of it -- what a block's
-// bracket then covers at least -- still fits the LDS stage of k_nearest (cfg 5: 1.115 -> 1.063 ms).  The
-// density comes from the span of the context's previous per-row call: a guess that only ever costs speed.
-static inline int row_skip(const giql_hip_ctx* ctx, size_t nb) {
-  if (ctx->guess.last_span == 0) return 1;
-  return (double)nb * 65536.0 / (double)ctx->guess.last_span <= 1024.0 ? 2 : 1;
-}
-
-// Fixed-length B of the per-row operators (SEMI / ANTI / COUNT): sorted without its lowest digit (three passes
-// instead of four) when the rows sharing the upper 24 key bits are few enough to be looked at one by one
-// (aux_kernels.hip.h, "sorted COARSELY") -- by the density of the context's previous call, like row_skip(): a guess
-// that only costs speed.
-static inline bool coarse_b_ok(const giql_hip_ctx* ctx, size_t nb) {
-  if (ctx->sw.no_coarse_b || ctx->guess.last_span == 0 || sort_is_local(ctx, nb)) return false;
-  return (double)nb * 256.0 / (double)ctx->guess.last_span <= ctx->sw.coarse_max_group_rows;
-}
-
 // Fork / join of the context's second stream.  A side of a few million rows is a chain of ~10 launches
 // of 10-40 us each that do not fill the GPU (look-back latency, not bandwidth, bounds them): run beside
 // the other side's chain it costs almost nothing.  Work given to stream() is ordered after everything
@@ -1153,7 +1137,7 @@ struct SideChain {
   // kernels little (SEMI 1M x 10M: 0.378 -> 0.349 ms; 1M x 1M: 0.387 -> 0.351 ms).
   SideChain(giql_hip_ctx* c, hipStream_t m, size_t n_small) : ctx(c), main(m) {
     if (!c->side_stream || n_small == 0 || n_small > OVERLAP_MAX_ROWS) return;
-    if (sort_is_local(c, n_small)) return;  // the bucket sort's boundary / queue buffers are one per context
+    if (sort_is_local(sort_tuning(c), n_small)) return;  // the bucket sort's boundary / queue buffers are one per context
     if (hipEventRecord(c->ev_fork, m) != hipSuccess) return;
     if (hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) != hipSuccess) return;
     active = true;
@@ -1424,6 +1408,9 @@ struct PlanSide {
   const u32* irr = nullptr;      // DevMeta: its irregular rows
   const int* len_max = nullptr;  // DevMeta: its longest regular row
   int32_t* out_row = nullptr;    // one-call join: the caller's output row for this side's ids (else NULL)
+  Side which() const { return label ? Side::B : Side::A; }
+  DigitCounts starts() const { return {hist, gbase}; }
+  SortRequest sort_rows() const { return SortRequest::rows((u32)n, gbase, status); }
 };
 
 // The plan's scratch, as carve_inner lays it out in the arena.
@@ -1549,8 +1536,9 @@ static size_t carve_inner(giql_hip_ctx* ctx, char* base, size_t na, size_t nb, i
 // calls: the larger side turned out to take more global passes than expected (the density is known now): those need
 // zeroed status words too, and the zeroed range grows by them.
 static int zero_inner_scratch(giql_hip_ctx* ctx, hipStream_t st, const InnerScratch& W, size_t n_max) {
-  const int passes = sort_is_local(ctx, n_max) ? local_passes(sort_local_bits(ctx, n_max)) : 4;
-  const size_t want = W.zero.end + (size_t)passes * os_pass_stride(ctx, n_max) * sizeof(u32);  // (os_status starts at zero.end)
+  const SortTuning tune = sort_tuning(ctx);
+  const int passes = sort_is_local(tune, n_max) ? local_passes(sort_local_bits(tune, n_max)) : 4;
+  const size_t want = W.zero.end + (size_t)passes * os_pass_stride(tune, n_max) * sizeof(u32);  // (os_status starts at zero.end)
   const char* const arena = ctx->arena;
   const char* const have = ctx->call.zeroed.end();  // (nothing to do when the range reaches that far already)
   return zero_span(ctx, st, {have ? (size_t)(have - arena) : W.zero.off, want});
@@ -1618,10 +1606,10 @@ static int begin_attempt(giql_hip_ctx* ctx, hipStream_t st, PlanSide& A, PlanSid
     // already on this first plan (the one write of a guess outside settle_guesses).  The span pass counted its
     // digits for the form it expected: if the larger side leaves the three-stage sort, its high-digits-only
     // histogram is of no use and that side is linearized (which counts all four digits)
-    const int expected_bits = sort_local_bits(ctx, big.n);
+    const int expected_bits = sort_local_bits(sort_tuning(ctx), big.n);  // by the previous call's density ...
     ctx->guess.last_span = m.total_span;
     // (the high-digits-only histogram serves 16-bit buckets alone: narrower ones sort on bits 8-15 too)
-    if (expected_bits == 16 && sort_local_bits(ctx, big.n) != 16) T.aligned = false;
+    if (expected_bits == 16 && sort_local_bits(sort_tuning(ctx), big.n) != 16) T.aligned = false;  // ... and by this one's
     GIQL_TRY(zero_inner_scratch(ctx, st, W, big.n));
   }
   T.keygen_u = T.aligned && T.form == big_form;
@@ -1717,7 +1705,8 @@ static int plan_uniform(giql_hip_ctx* ctx, hipStream_t st, int n_chrom, PlanSide
   // Fused range count: when U takes the three-stage sort, its bucket sort answers the queries' bounds
   // (bucket_sort.hip.h) -- as long as no query row is longer than the windows allow for: known from the
   // read-back on a first plan, the previous plan's answer afterwards (validated like the other guesses)
-  T.fuse_cnt = !ctx->sw.no_fuse_count && sort_is_local(ctx, U.n) && T.fuse_len_ok;
+  const SortTuning tune = sort_tuning(ctx);  // (the density guess is settled before a form runs)
+  T.fuse_cnt = !ctx->sw.no_fuse_count && sort_is_local(tune, U.n) && T.fuse_len_ok;
   // KNOWN ODDITY (kept as it is): on a speculated attempt this is not the previous INNER plan's maximum but the last
   // read-back of ANY call on the context (h_meta is shared); it only sizes the window estimate below.
   const int q_len_max = len_max_of(*ctx->h_meta, Q.label);
@@ -1731,12 +1720,13 @@ static int plan_uniform(giql_hip_ctx* ctx, hipStream_t st, int n_chrom, PlanSide
   // (the fork comes AFTER the digit offsets above: the query side's sort on the second stream reads them)
   SideChain sc(ctx, st, (Q.n <= U.n && !T.fuse_cnt) ? Q.n : 0);
   if (!T.keygen_q) {
-    GIQL_TRY(run_linearize(ctx, sc.stream(), *Q.side, n_chrom, lb, sq.key[0], sq.end[0], Q.irr_list, Q.label, 0,
-                           Q.hist, Q.gbase));
+    GIQL_TRY(run_linearize(ctx, sc.stream(), *Q.side, n_chrom, lb, Q.which(),
+                           LinTarget::keys_ends(sq.key[0], sq.end[0], Q.irr_list), LinOptions().counting_starts(Q.starts())));
   }
   if (!T.keygen_u) {
-    GIQL_TRY(run_linearize(ctx, st, *U.side, n_chrom, lb, su.key[0], nullptr, U.irr_list, U.label, 0, U.hist,
-                           U.gbase, nullptr, nullptr, /*skip_end=*/true));  // uniform => no irregular row: `end` is not read
+    // uniform => no irregular row: `end` is not read
+    GIQL_TRY(run_linearize(ctx, st, *U.side, n_chrom, lb, U.which(), LinTarget::keys_only(su.key[0], U.irr_list),
+                           LinOptions().counting_starts(U.starts()).without_end_column()));
   }
   // The query side's order only serves locality (its bounds are searched per row, its pairs are laid
   // out by the scan), so its lowest digit stays unsorted: three passes.  Irregular rows would break
@@ -1745,13 +1735,14 @@ static int plan_uniform(giql_hip_ctx* ctx, hipStream_t st, int n_chrom, PlanSide
   // With the fused count the queries only have to be grouped by the bucket their key falls into (the windows
   // of k_bucket_bounds_fused are computed under the same mask and then cover whole query buckets): TWO digits
   // unsorted, two passes.
-  T.q_skip = (T.no_irr && !sort_is_local(ctx, Q.n)) ? 1 : 0;
+  T.q_skip = (T.no_irr && !sort_is_local(tune, Q.n)) ? 1 : 0;
   // (narrower buckets: the queries stay grouped by key >> 8 -- a window under the 16-bit mask would span 2-8 buckets)
-  const int wb_u = sort_local_bits(ctx, U.n);
+  const int wb_u = sort_local_bits(tune, U.n);
   if (T.q_skip && T.fuse_cnt && wb_u == 16) T.q_skip = 2;
   const u32 q_mask = skip_mask(T.q_skip);
-  GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sq, (u32)Q.n, Q.gbase, Q.status, false,
-                             T.keygen_q ? Q.side : nullptr, lb.abase, T.q_skip, nullptr, T.presorted[Q.label]));
+  GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sq,
+                             Q.sort_rows().keys_from(T.keygen_q ? Q.side : nullptr, lb.abase).skipping_digits(T.q_skip)
+                                 .already_sorted(T.presorted[Q.label])));
   // One-call join (giql_hip_inner_join_dev): the caller's buffers are here and everything about this plan is a
   // guess that has held so far (same form as last time, no irregular rows), so the fill is launched inside the
   // plan, with a grid bounded by the capacity and the true count read on the device.
@@ -1779,8 +1770,9 @@ static int plan_uniform(giql_hip_ctx* ctx, hipStream_t st, int n_chrom, PlanSide
     fc.dev.lo_out = S.lo2;
     fc.dev.hi_out = S.cnt2;  // the scan below turns the upper bounds into counts in place
   }
-  GIQL_TRY(run_sort_onesweep(ctx, st, su, (u32)U.n, U.gbase, U.status, false, T.keygen_u ? U.side : nullptr, lb.abase,
-                             0, T.fuse_cnt ? &fc : nullptr, T.presorted[U.label]));
+  GIQL_TRY(run_sort_onesweep(ctx, st, su,
+                             U.sort_rows().keys_from(T.keygen_u ? U.side : nullptr, lb.abase)
+                                 .fused_with(T.fuse_cnt ? &fc : nullptr).already_sorted(T.presorted[U.label])));
   GIQL_TRY(sc.join());
   constexpr u32 TQ = RC_NT * RC_ITEMS_C2;
   S.nt2 = cdiv(Q.n, TQ);
@@ -1896,7 +1888,7 @@ static int plan_general(giql_hip_ctx* ctx, hipStream_t st, int n_chrom, PlanSide
   // maxima, like the guess they validate)
   // KNOWN ODDITY (kept as it is): h_meta holds the last read-back of ANY call on the context, not of the last INNER
   // plan, so "the previous plan's maxima" may be another operator's numbers.  A candidate for a later fix with a test.
-  const int wb_b = sort_local_bits(ctx, B.n);
+  const int wb_b = sort_local_bits(sort_tuning(ctx), B.n);
   T.general_join = T.onesweep && A.out_row && T.no_irr && ctx->plan.fuse_cap > 0 && B.n >= A.n && wb_b != 0 &&
                    T.fuse_len_ok && ctx->guess.last_span > 0 &&
                    (double)A.n * ((double)(1u << (wb_b ? wb_b : 16)) + (double)ctx->h_meta->len_max_a +
@@ -1914,13 +1906,14 @@ static int plan_general(giql_hip_ctx* ctx, hipStream_t st, int n_chrom, PlanSide
       GIQL_TRY(span_digit_offsets(ctx, stream_of[s->label], lb, s->hist, s->gbase, nullptr, nullptr,
                                   "digit offsets (span histogram, general form)"));
     } else {
-      GIQL_TRY(run_linearize(ctx, stream_of[s->label], *s->side, n_chrom, lb, s->sort->key[0], s->sort->end[0],
-                             s->irr_list, s->label, 0, s->hist, s->gbase));
+      GIQL_TRY(run_linearize(ctx, stream_of[s->label], *s->side, n_chrom, lb, s->which(),
+                             LinTarget::keys_ends(s->sort->key[0], s->sort->end[0], s->irr_list),
+                             LinOptions().counting_starts(s->starts())));
     }
   }
   if (T.onesweep) {
-    GIQL_TRY(run_sort_onesweep(ctx, stream_of[0], sa, (u32)A.n, A.gbase, A.status, false, keygen_of[0], lb.abase, 0,
-                               nullptr, T.presorted[0]));
+    GIQL_TRY(run_sort_onesweep(ctx, stream_of[0], sa,
+                               A.sort_rows().keys_from(keygen_of[0], lb.abase).already_sorted(T.presorted[0])));
     FuseCount fg = {};
     if (T.general_join) {
       const FuseTarget out{A.out_row, B.out_row, ctx->plan.fuse_cap};
@@ -1928,8 +1921,9 @@ static int plan_general(giql_hip_ctx* ctx, hipStream_t st, int n_chrom, PlanSide
       fg = make_fuse_count(ctx, fuse_query(A), 1, 0xFFFFFFFFu, &out, true, B.len_max,
                            reinterpret_cast<u32*>(W.scan_chain));
     }
-    GIQL_TRY(run_sort_onesweep(ctx, stream_of[1], sbb, (u32)B.n, B.gbase, B.status, false, keygen_of[1], lb.abase, 0,
-                               T.general_join ? &fg : nullptr, T.presorted[1]));
+    GIQL_TRY(run_sort_onesweep(ctx, stream_of[1], sbb,
+                               B.sort_rows().keys_from(keygen_of[1], lb.abase).fused_with(T.general_join ? &fg : nullptr)
+                                   .already_sorted(T.presorted[1])));
     GIQL_TRY(sc.join());
   } else {
     GIQL_TRY(run_sort(ctx, st, sa, (u32)A.n, W.tile_hist, W.bsums));
@@ -2342,9 +2336,10 @@ static int giql_hip_window_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* a, 
   u32* const status_a = na <= nb ? W.os_status2 : W.os_status;
   u32* const status_b = na <= nb ? W.os_status : W.os_status2;
   GIQL_TRY(key_widened_side(ctx, st, *a, *b, n_chrom, W.lb, widen, sa, P.irr_a_list, W.hist[0], W.gbase[0]));
-  GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, W.lb, sbb.key[0], sbb.end[0], P.irr_b_list, 1, 0, W.hist[1], W.gbase[1]));
-  GIQL_TRY(run_sort_onesweep(ctx, st, sa, (u32)na, W.gbase[0], status_a));
-  GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, W.gbase[1], status_b));
+  GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, W.lb, Side::B, LinTarget::keys_ends(sbb.key[0], sbb.end[0], P.irr_b_list),
+                         LinOptions().counting_starts({W.hist[1], W.gbase[1]})));
+  GIQL_TRY(run_sort_onesweep(ctx, st, sa, SortRequest::rows((u32)na, W.gbase[0], status_a)));
+  GIQL_TRY(run_sort_onesweep(ctx, st, sbb, SortRequest::rows((u32)nb, W.gbase[1], status_b)));
   const u32* irr_a = &ctx->d_meta->irr_a;
   const u32* irr_b = &ctx->d_meta->irr_b;
   // the counts and scans of plan_general, over the widened A (class 1 and class 2 on the one stream)
@@ -2530,7 +2525,7 @@ int giql_hip_index_create_dev(giql_hip_ctx* ctx, const giql_side* side, int32_t 
   if (m.len_max_b > (int)BS_FUSE_WCAP)
     return set_err(GIQL_ERR_STATE, "a row of %d positions is longer than the bucket stage's windows allow (%u)", m.len_max_b, BS_FUSE_WCAP);
   const double per_bucket = (double)n * 65536.0 / (double)(m.total_span ? m.total_span : 1);
-  idx->wbits = ctx->sw.force_bits ? ctx->sw.force_bits : density_bits(ctx, per_bucket);
+  idx->wbits = ctx->sw.force_bits ? ctx->sw.force_bits : density_bits(sort_tuning(ctx), per_bucket);
   if (idx->wbits == 0)
     return set_err(GIQL_ERR_STATE, "%.0f rows per 65,536 positions: too dense for the in-LDS bucket stage (at most %.0f per %d)",
                    per_bucket, ctx->sw.local_max_bucket_rows, 1 << BS_MIN_WBITS);
@@ -2550,16 +2545,11 @@ int giql_hip_index_create_dev(giql_hip_ctx* ctx, const giql_side* side, int32_t 
   sb.rid[0] = idx->rid;
   sb.end[0] = idx->general ? idx->end : nullptr;
   if (!idx->general) sb.end[1] = nullptr;
-  if (local_passes(idx->wbits) & 1) {
-    // three global passes end in the buffer they did not start from (run_sort_onesweep then calls THAT "buffer 0"):
-    // the index's own arrays start as buffer 1
-    u32* t;
-    t = sb.key[0], sb.key[0] = sb.key[1], sb.key[1] = t;
-    t = sb.rid[0], sb.rid[0] = sb.rid[1], sb.rid[1] = t;
-    t = sb.end[0], sb.end[0] = sb.end[1], sb.end[1] = t;
-  }
-  // two (three) global passes from the raw columns + every bucket sorted in LDS, in place: the result is in buffer 0
-  GIQL_TRY(run_sort_onesweep(ctx, st, sb, (u32)n, gbase, status, false, side, lb.abase, 0, nullptr, false));
+  // two (three) global passes from the raw columns + every bucket sorted in LDS, in place.  Three passes end in the
+  // physical buffer they did not start from: the plan says which, and the index's own arrays start as the other one
+  const SortRequest build = SortRequest::rows((u32)n, gbase, status).keys_from(side, lb.abase);
+  if (plan_of(ctx, sb, build).result_buf == 1) sb.flip();
+  GIQL_TRY(run_sort_onesweep(ctx, st, sb, build));
   if (sb.key[0] != idx->key) return set_err(GIQL_ERR_HIP, "internal: the sort did not end in the index's buffers");
   HIP_TRY(hipMemcpyAsync(idx->small, gbase, 1024 * sizeof(u32), hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemcpyAsync(idx->small + 1024, lb.chrom_first, ((size_t)n_chrom + 1) * sizeof(u32), hipMemcpyDeviceToDevice, st));
@@ -2638,7 +2628,7 @@ int giql_hip_inner_join_indexed_dev(giql_hip_ctx* ctx, const giql_hip_index* idx
   const int q_skip = idx->general ? 0 : (idx->wbits == 16 ? 2 : 1);
   {
     ForceLocal global_only{ctx, -1};  // a's own sort: global passes only (its bucket stage would reuse the context's boundary arrays)
-    GIQL_TRY(run_sort_onesweep(ctx, st, sa, (u32)na, gbase, status, false, nullptr, nullptr, q_skip, nullptr, false));
+    GIQL_TRY(run_sort_onesweep(ctx, st, sa, SortRequest::rows((u32)na, gbase, status).skipping_digits(q_skip)));
   }
   const FuseTarget out{row_a, row_idx, (u64)capacity};
   const FuseCount fc = make_fuse_count(ctx, FuseQuery{&sa, na, dead, gbase, len_max_q}, idx->general ? 1 : 1 - idx->uni_len,
@@ -2648,7 +2638,8 @@ int giql_hip_inner_join_indexed_dev(giql_hip_ctx* ctx, const giql_hip_index* idx
   sb.rid[0] = idx->rid;
   sb.end[0] = idx->end;
   ctx->call.last_sort_local = true;
-  launch_bucket_stage_fused(ctx, st, sb, (u32)nb, idx->small, fc, idx->wbits);
+  GIQL_TRY(launch_bucket_stage(ctx, st, sb, plan_fused_stage(idx->wbits, (u32)nb, fc.kind(), fc.nq_total), (u32)nb,
+                               idx->small, &fc));
   GIQL_TRY(post_launch("bucket stage (index)"));
   u32 h_flags[4] = {0, 0, 0, 0};
   HIP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, st));
@@ -2725,11 +2716,16 @@ static int index_prepare_rows_core(giql_hip_ctx* ctx, giql_hip_index* idx, hipSt
     GIQL_TRY(claim_arena(ctx, st, carve));
     se.key[0] = end_sorted;
     se.end[0] = se.end[1] = se.rid[0] = se.rid[1] = nullptr;
+    // global passes only.  The plan says in which physical buffer they end: the rows start in the index's new array
+    // when that is where they end, in the arena's otherwise
+    const SortRequest end_sort = SortRequest::rows((u32)n, gbase, status);
+    ForceLocal global_only{ctx, -1};  // (until the sort below has run; nothing else in between sorts)
+    if (plan_of(ctx, se, end_sort).result_buf == 1) se.flip();
     HIP_TRY(hipMemsetAsync(hist, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
     {
       Phase ph(ctx, st, GIQL_PH_AUX);  // the copy of the end keys the sort starts from: read once, written once
       ctx->stats.phase_bytes[GIQL_PH_AUX] += (int64_t)8 * n;
-      HIP_TRY(hipMemcpyAsync(end_sorted, idx->end, n * sizeof(u32), hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(se.key[0], idx->end, n * sizeof(u32), hipMemcpyDeviceToDevice, st));
     }
     {
       Phase ph(ctx, st, GIQL_PH_SORT_HIST, 3);  // the end keys' digit histogram: every key read once
@@ -2741,10 +2737,7 @@ static int index_prepare_rows_core(giql_hip_ctx* ctx, giql_hip_index* idx, hipSt
       hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, hist, (u32)LIN_HIST_REPLICAS, gbase);
       GIQL_TRY(post_launch("end-key digits (index)"));
     }
-    {
-      ForceLocal global_only{ctx, -1};  // four global passes: the result is back in buffer 0
-      GIQL_TRY(run_sort_onesweep(ctx, st, se, (u32)n, gbase, status));
-    }
+    GIQL_TRY(run_sort_onesweep(ctx, st, se, end_sort));
     if (se.key[0] != end_sorted) return set_err(GIQL_ERR_HIP, "internal: the sort did not end in the index's buffer");
     {
       Phase ph(ctx, st, GIQL_PH_AUX);
@@ -2999,12 +2992,6 @@ int giql_hip_nearest_indexed_dev(giql_hip_ctx* ctx, giql_hip_index* idx, const g
   return GIQL_OK;
 }
 
-// Scratch shared by the single-output operators: histogram replicas, digit bases,
-// onesweep status words (+ tile-claim state) for one side at a time.
-struct OsScratch {
-  u32 *hist = nullptr, *gbase = nullptr, *hist_e = nullptr, *gbase_e = nullptr;
-  u32* status = nullptr;
-};
 
 // zero_upto_status: closes the carve's zeroed span where the status words begin (os_pair_sizes)
 static void os_scratch_sizes(Carver& c, size_t n_max, OsScratch& o, ZeroSpan* zero_upto_status = nullptr) {
@@ -3026,7 +3013,7 @@ struct OsScratchPair {
   // It pays for calls that sort each side ONCE: a second sort through the same status words finds them taken and
   // zeroes them again.
   int prezero(giql_hip_ctx* ctx, hipStream_t st, size_t n_b) const {
-    return zero_span(ctx, st, {zero.off, zero.end + 4 * os_pass_stride(ctx, n_b) * sizeof(u32)});
+    return zero_span(ctx, st, {zero.off, zero.end + 4 * os_pass_stride(sort_tuning(ctx), n_b) * sizeof(u32)});
   }
 };
 
@@ -3093,30 +3080,31 @@ static int giql_hip_semi_anti_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
   i64 uni_len = 0;
   bool speculated = false;
   if (nb > 0) GIQL_TRY(row_form_guess(ctx, st, uni_len, speculated));
-  const bool coarse_b = nb > 0 && uni_len > 0 && coarse_b_ok(ctx, nb);
+  const SortTuning tune = sort_tuning(ctx);  // (after the form guess: a first call has noted the density there)
+  const bool coarse_b = nb > 0 && uni_len > 0 && coarse_b_ok(tune, nb);
   {
     // the query side's chain (linearize + sort) beside B's when it is small
     SideChain sc(ctx, st, nb > 0 ? na : 0);
-    GIQL_TRY(run_linearize(ctx, sc.stream(), *a, nch, lb, sa.key[0], sa.end[0], dummy_irr + 8, 0, 1, os_a.hist, os_a.gbase));
-    GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sa, (u32)na, os_a.gbase, os_a.status, false, nullptr, nullptr,
-                               /*skip_digits=*/row_skip(ctx, nb)));  // the query side's order only serves locality; every row keeps its real key here
+    GIQL_TRY(run_linearize(ctx, sc.stream(), *a, nch, lb, Side::A, LinTarget::keys_ends(sa.key[0], sa.end[0], dummy_irr + 8),
+                           LinOptions().keeping_irregular().counting_starts(os_a.starts())));
+    // the query side's order only serves locality; every row keeps its real key here
+    GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sa, sort_by_start(os_a, na).skipping_digits(row_skip(tune, nb))));
     if (nb > 0 && uni_len > 0) {
       // fixed-length B: keys only (its `end` column is not read again), no prefix max
       sbb.end[0] = sbb.end[1] = nullptr;
-      GIQL_TRY(run_linearize(ctx, st, *b, nch, lb, sbb.key[0], nullptr, dummy_irr, 1, 1, os.hist, os.gbase,
-                             nullptr, nullptr, /*skip_end=*/true));
-      GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase, os.status, false, nullptr, nullptr,
-                                 /*skip_digits=*/coarse_b ? 1 : 0));
+      GIQL_TRY(run_linearize(ctx, st, *b, nch, lb, Side::B, LinTarget::keys_only(sbb.key[0], dummy_irr),
+                             LinOptions().keeping_irregular().counting_starts(os.starts()).without_end_column()));
+      GIQL_TRY(run_sort_onesweep(ctx, st, sbb, sort_by_start(os, nb).skipping_digits(coarse_b ? 1 : 0)));
     } else if (nb > 0) {
       // every B row keeps its real key: the prefix-max test is exact for any row
-      GIQL_TRY(run_linearize(ctx, st, *b, nch, lb, sbb.key[0], sbb.end[0], dummy_irr, 1, 1, os.hist,
-                             os.gbase));
+      GIQL_TRY(run_linearize(ctx, st, *b, nch, lb, Side::B, LinTarget::keys_ends(sbb.key[0], sbb.end[0], dummy_irr),
+                             LinOptions().keeping_irregular().counting_starts(os.starts())));
 #if defined(GIQL_LIN_ABLATE)  // timing-only builds stop here: their keys / histograms are not valid
       GIQL_TRY(read_meta(ctx, st));
       collect_spans(ctx);
       return GIQL_OK;
 #endif
-      GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase, os.status));
+      GIQL_TRY(run_sort_onesweep(ctx, st, sbb, sort_by_start(os, nb)));
       GIQL_TRY(run_pmax(ctx, st, sbb.end[0], (u32)nb, pmax, bmax));
     }
     GIQL_TRY(sc.join());
@@ -3185,28 +3173,28 @@ static int giql_hip_count_dev_impl(giql_hip_ctx* ctx, const giql_side* a, const 
   i64 uni_len = 0;
   bool speculated = false;
   GIQL_TRY(row_form_guess(ctx, st, uni_len, speculated));
-  const bool coarse_b = uni_len > 0 && coarse_b_ok(ctx, nb);
+  const SortTuning tune = sort_tuning(ctx);  // (after the form guess: a first call has noted the density there)
+  const bool coarse_b = uni_len > 0 && coarse_b_ok(tune, nb);
   ZeroedScope zeroed_scope{ctx};
   // (a choice of speed: the general form sorts B twice through one set of status words, and its second sort would
   // find them taken and zero them itself all the same)
   if (uni_len > 0) GIQL_TRY(osp.prezero(ctx, st, nb));
   {
     SideChain sc(ctx, st, na);
-    GIQL_TRY(run_linearize(ctx, sc.stream(), *a, n_chrom, lb, sa.key[0], sa.end[0], irr_a_list, 0, 0, os_a.hist,
-                           os_a.gbase));
-    GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sa, (u32)na, os_a.gbase, os_a.status, false, nullptr, nullptr,
-                               /*skip_digits=*/row_skip(ctx, nb)));  // locality only: k_count_rows tells irregular rows by their key
+    GIQL_TRY(run_linearize(ctx, sc.stream(), *a, n_chrom, lb, Side::A, LinTarget::keys_ends(sa.key[0], sa.end[0], irr_a_list),
+                           LinOptions().counting_starts(os_a.starts())));
+    // locality only: k_count_rows tells irregular rows by their key
+    GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sa, sort_by_start(os_a, na).skipping_digits(row_skip(tune, nb))));
     if (uni_len > 0) {
       // fixed-length B: one sorted array (its sorted ends are its sorted starts + L)
-      GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, sstart.key[0], nullptr, irr_b_list, 1, 0, os.hist,
-                             os.gbase, nullptr, nullptr, /*skip_end=*/true));
-      GIQL_TRY(run_sort_onesweep(ctx, st, sstart, (u32)nb, os.gbase, os.status, false, nullptr, nullptr,
-                                 /*skip_digits=*/coarse_b ? 1 : 0));
+      GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, Side::B, LinTarget::keys_only(sstart.key[0], irr_b_list),
+                             LinOptions().counting_starts(os.starts()).without_end_column()));
+      GIQL_TRY(run_sort_onesweep(ctx, st, sstart, sort_by_start(os, nb).skipping_digits(coarse_b ? 1 : 0)));
     } else {
-      GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, sstart.key[0], send.key[0], irr_b_list, 1, 0,
-                             os.hist, os.gbase, os.hist_e, os.gbase_e));
-      GIQL_TRY(run_sort_onesweep(ctx, st, sstart, (u32)nb, os.gbase, os.status));
-      GIQL_TRY(run_sort_onesweep(ctx, st, send, (u32)nb, os.gbase_e, os.status));
+      GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, Side::B, LinTarget::keys_ends(sstart.key[0], send.key[0], irr_b_list),
+                             LinOptions().counting_starts(os.starts()).counting_ends(os.ends())));
+      GIQL_TRY(run_sort_onesweep(ctx, st, sstart, sort_by_start(os, nb)));
+      GIQL_TRY(run_sort_onesweep(ctx, st, send, sort_by_end(os, nb)));
     }
     GIQL_TRY(sc.join());
   }
@@ -3296,8 +3284,9 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
   // ~2 x 22 more in the span pass and the first sort pass).  Every NEAREST row keeps its real key, zero-length rows
   // included, so the only guess is the layout: taken when the previous call's data took it, validated at the
   // read-back; a first call probes it (digits counted for B only) and sorts the ordinary way.
+  const SortTuning tune = sort_tuning(ctx);
   const bool hist_ok = !two_sorts && ctx->call.zeroed.covers(os.hist, HIST_BYTES) && !ctx->sw.no_span_hist && ctx->sw.os_variant == 0 &&
-                       n_chrom <= MM_HIST_CHROMS && !sort_is_local(ctx, na) && !sort_is_local(ctx, nb);
+                       n_chrom <= MM_HIST_CHROMS && !sort_is_local(tune, na) && !sort_is_local(tune, nb);
   const bool keygen = hist_ok && ctx->guess.nearest_aligned == 1;
   const bool probe = hist_ok && ctx->guess.nearest_aligned == -1;
   if (keygen) lb.hist_partial2 = os_a.hist;
@@ -3313,19 +3302,22 @@ static int giql_hip_nearest_dev_impl(giql_hip_ctx* ctx, const giql_side* a, cons
   }
   SideChain sc(ctx, st, na);
   if (!keygen)
-    GIQL_TRY(run_linearize(ctx, sc.stream(), *a, n_chrom, lb, sa.key[0], sa.end[0], dummy_irr + 8, 0, 1, os_a.hist,
-                           os_a.gbase));
-  GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sa, (u32)na, os_a.gbase, os_a.status, false, keygen ? a : nullptr,
-                             lb.abase, /*skip_digits=*/row_skip(ctx, nb)));  // the query side's order only serves locality; every row keeps its real key here
+    GIQL_TRY(run_linearize(ctx, sc.stream(), *a, n_chrom, lb, Side::A, LinTarget::keys_ends(sa.key[0], sa.end[0], dummy_irr + 8),
+                           LinOptions().keeping_irregular().counting_starts(os_a.starts())));
+  // the query side's order only serves locality; every row keeps its real key here
+  GIQL_TRY(run_sort_onesweep(ctx, sc.stream(), sa,
+                             sort_by_start(os_a, na).keys_from(keygen ? a : nullptr, lb.abase)
+                                 .skipping_digits(row_skip(tune, nb))));
   if (!keygen)
-    GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, sbb.key[0], sbb.end[0], dummy_irr, 1, 1, os.hist,
-                           os.gbase, two_sorts ? os.hist_e : nullptr, two_sorts ? os.gbase_e : nullptr));
+    GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, Side::B, LinTarget::keys_ends(sbb.key[0], sbb.end[0], dummy_irr),
+                           LinOptions().keeping_irregular().counting_starts(os.starts())
+                               .counting_ends(two_sorts ? os.ends() : DigitCounts())));
   // (an inverted B row -- NEAREST needs start <= end on both sides -- is reported by the span pass: DevMeta::inverted_b)
   if (two_sorts) {
-    GIQL_TRY(run_sort_two_keys(ctx, st, sbb, (u32)nb, os.gbase, os.gbase_e, os.status));  // (start, end) order
+    GIQL_TRY(run_sort_two_keys(ctx, st, sbb, (u32)nb, os));  // (start, end) order
   } else {
     // one sort by start; the (short) runs of equal starts are ordered by end in place
-    GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase, os.status, false, keygen ? b : nullptr, lb.abase));
+    GIQL_TRY(run_sort_onesweep(ctx, st, sbb, sort_by_start(os, nb).keys_from(keygen ? b : nullptr, lb.abase)));
     Phase ph(ctx, st, GIQL_PH_AUX);
     hipLaunchKernelGGL(k_fix_start_ties, dim3(cdiv(nb, 256)), dim3(256), 0, st, sbb.key[0], sbb.end[0],
                        sbb.rid[0], (u32)nb, ctx->d_meta);
@@ -3426,25 +3418,25 @@ static int giql_hip_nearest_k_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
   GIQL_TRY(run_spans(ctx, st, *a, *b, n_chrom, lb));
   // Two sorted views of B from ONE linearize pass (it counts the digits of the starts and of the ends):
   //   by (start, end) and by (end, start).
-  GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, sbb.key[0], sbb.end[0], dummy_irr, 1, 1, os.hist, os.gbase,
-                         os.hist_e, os.gbase_e));
+  GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, Side::B, LinTarget::keys_ends(sbb.key[0], sbb.end[0], dummy_irr),
+                         LinOptions().keeping_irregular().counting_starts(os.starts()).counting_ends(os.ends())));
   const bool two_sorts = ctx->guess.nearest_two_sorts;
   if (two_sorts) {
     // tables with long runs of equal starts or ends: stable two-key sorts -- (start, end) = by end, then stably by
     // start; (end, start) = that order stably re-sorted by end
-    GIQL_TRY(run_sort_two_keys(ctx, st, sbb, (u32)nb, os.gbase, os.gbase_e, os.status));
+    GIQL_TRY(run_sort_two_keys(ctx, st, sbb, (u32)nb, os));
     HIP_TRY(hipMemcpyAsync(se.key[0], sbb.end[0], nb * sizeof(u32), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(se.end[0], sbb.key[0], nb * sizeof(u32), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(se.rid[0], sbb.rid[0], nb * sizeof(u32), hipMemcpyDeviceToDevice, st));
-    GIQL_TRY(run_sort_onesweep(ctx, st, se, (u32)nb, os.gbase_e, os.status, /*keep_rids=*/true));
+    GIQL_TRY(run_sort_onesweep(ctx, st, se, sort_by_end(os, nb).keeping_rids()));
   } else {
     // ONE sort per view (eight passes instead of twelve): each view sorted on its first key from the linearized
     // columns, the -- short -- runs of equal first keys ordered by the second key in place (k_fix_start_ties; a run
     // too long for that flags the table for the two-key plan above, as in NEAREST k = 1)
     HIP_TRY(hipMemcpyAsync(se.key[0], sbb.end[0], nb * sizeof(u32), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(se.end[0], sbb.key[0], nb * sizeof(u32), hipMemcpyDeviceToDevice, st));
-    GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase, os.status));
-    GIQL_TRY(run_sort_onesweep(ctx, st, se, (u32)nb, os.gbase_e, os.status));
+    GIQL_TRY(run_sort_onesweep(ctx, st, sbb, sort_by_start(os, nb)));
+    GIQL_TRY(run_sort_onesweep(ctx, st, se, sort_by_end(os, nb)));
     Phase ph(ctx, st, GIQL_PH_AUX, 2);
     hipLaunchKernelGGL(k_fix_start_ties, dim3(cdiv(nb, 256)), dim3(256), 0, st, sbb.key[0], sbb.end[0], sbb.rid[0],
                        (u32)nb, ctx->d_meta);
@@ -3452,9 +3444,10 @@ static int giql_hip_nearest_k_dev_impl(giql_hip_ctx* ctx, const giql_side* a, co
                        (u32)nb, ctx->d_meta);
   }
   GIQL_TRY(run_pmax(ctx, st, sbb.end[0], (u32)nb, pmax, bmax));
-  GIQL_TRY(run_linearize(ctx, st, *a, n_chrom, lb, sa.key[0], sa.end[0], dummy_irr, 0, 1, os.hist, os.gbase));
-  GIQL_TRY(run_sort_onesweep(ctx, st, sa, (u32)na, os.gbase, os.status, false, nullptr, nullptr,
-                             /*skip_digits=*/row_skip(ctx, nb)));  // the query side's order only serves locality; every row keeps its real key here
+  GIQL_TRY(run_linearize(ctx, st, *a, n_chrom, lb, Side::A, LinTarget::keys_ends(sa.key[0], sa.end[0], dummy_irr),
+                         LinOptions().keeping_irregular().counting_starts(os.starts())));
+  // the query side's order only serves locality; every row keeps its real key here
+  GIQL_TRY(run_sort_onesweep(ctx, st, sa, sort_by_start(os, na).skipping_digits(row_skip(sort_tuning(ctx), nb))));
   {
     Phase ph(ctx, st, GIQL_PH_COUNT, 4);
     hipLaunchKernelGGL(k_chrom_bounds, dim3(cdiv((u64)n_chrom + 1, 256)), dim3(256), 0, st, lb.chrom_first, n_chrom,
@@ -3556,14 +3549,14 @@ static int cluster_front(giql_hip_ctx* ctx, hipStream_t st, const giql_side* s, 
   giql_side none;
   memset(&none, 0, sizeof(none));
   GIQL_TRY(run_spans(ctx, st, *s, none, n_chrom, cb.lb));
-  GIQL_TRY(run_linearize(ctx, st, *s, n_chrom, cb.lb, cb.sb.key[0], cb.sb.end[0], cb.dummy_irr, 0, 1,
-                         cb.os.hist, cb.os.gbase));
+  GIQL_TRY(run_linearize(ctx, st, *s, n_chrom, cb.lb, Side::A, LinTarget::keys_ends(cb.sb.key[0], cb.sb.end[0], cb.dummy_irr),
+                         LinOptions().keeping_irregular().counting_starts(cb.os.starts())));
   {
     Phase ph(ctx, st, GIQL_PH_AUX);
     hipLaunchKernelGGL(k_check_not_inverted, dim3(cdiv(n, 256)), dim3(256), 0, st, view_of(*s),
                        ctx->d_meta);
   }
-  GIQL_TRY(run_sort_onesweep(ctx, st, cb.sb, (u32)n, cb.os.gbase, cb.os.status));
+  GIQL_TRY(run_sort_onesweep(ctx, st, cb.sb, sort_by_start(cb.os, n)));
   GIQL_TRY(run_pmax(ctx, st, cb.sb.end[0], (u32)n, cb.pmax, cb.bmax));
   HIP_TRY(hipMemsetAsync(cb.flags, 0, n * sizeof(u32), st));
   {
@@ -4022,7 +4015,7 @@ static int giql_hip_disjoin_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* t,
     hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, W.os.hist, (u32)LIN_HIST_REPLICAS, W.os.gbase);
     GIQL_TRY(post_launch("disjoin events"));
   }
-  GIQL_TRY(run_sort_onesweep(ctx, st, W.sb, (u32)nev, W.os.gbase, W.os.status));
+  GIQL_TRY(run_sort_onesweep(ctx, st, W.sb, sort_by_start(W.os, nev)));
   if (nev > 0) {
     Phase ph(ctx, st, GIQL_PH_COUNT, 1);
     ctx->stats.phase_bytes[GIQL_PH_COUNT] += (int64_t)16 * nev;  // keys + ids read, two flags written
@@ -4165,19 +4158,19 @@ static int contain_candidates(giql_hip_ctx* ctx, hipStream_t st, const giql_side
   ctx->guess.last_span = ctx->h_meta->total_span;  // known before anything is sorted: the sort form follows the real density
   const i64 uni_len = (ctx->sw.no_uniform || force_general) ? 0 : uniform_len_b(*ctx->h_meta);
   P.form = uni_len > 0 ? 1 : 0;
-  GIQL_TRY(run_linearize(ctx, st, *o, n_chrom, W.lb, P.so.key[0], P.so.end[0], P.irr_o_list, 0, 0, W.os_o.hist,
-                         W.os_o.gbase));
-  GIQL_TRY(run_sort_onesweep(ctx, st, P.so, (u32)no, W.os_o.gbase, W.os_o.status));
+  GIQL_TRY(run_linearize(ctx, st, *o, n_chrom, W.lb, Side::A, LinTarget::keys_ends(P.so.key[0], P.so.end[0], P.irr_o_list),
+                         LinOptions().counting_starts(W.os_o.starts())));
+  GIQL_TRY(run_sort_onesweep(ctx, st, P.so, sort_by_start(W.os_o, no)));
   if (P.form == 1) {
     // every inner row is regular and uni_len long: keys and row ids only, its `end` column is not read again
     P.si.end[0] = P.si.end[1] = nullptr;
-    GIQL_TRY(run_linearize(ctx, st, *in, n_chrom, W.lb, P.si.key[0], nullptr, P.irr_i_list, 1, 0, W.os_i.hist,
-                           W.os_i.gbase, nullptr, nullptr, /*skip_end=*/true));
+    GIQL_TRY(run_linearize(ctx, st, *in, n_chrom, W.lb, Side::B, LinTarget::keys_only(P.si.key[0], P.irr_i_list),
+                           LinOptions().counting_starts(W.os_i.starts()).without_end_column()));
   } else {
-    GIQL_TRY(run_linearize(ctx, st, *in, n_chrom, W.lb, P.si.key[0], P.si.end[0], P.irr_i_list, 1, 0, W.os_i.hist,
-                           W.os_i.gbase));
+    GIQL_TRY(run_linearize(ctx, st, *in, n_chrom, W.lb, Side::B, LinTarget::keys_ends(P.si.key[0], P.si.end[0], P.irr_i_list),
+                           LinOptions().counting_starts(W.os_i.starts())));
   }
-  GIQL_TRY(run_sort_onesweep(ctx, st, P.si, (u32)ni, W.os_i.gbase, W.os_i.status));
+  GIQL_TRY(run_sort_onesweep(ctx, st, P.si, sort_by_start(W.os_i, ni)));
   const u32* irr_o = &ctx->d_meta->irr_a;
   const u32* irr_i = &ctx->d_meta->irr_b;
   {
@@ -4417,20 +4410,22 @@ static int giql_hip_semi_anti_pred_dev_impl(giql_hip_ctx* ctx, const giql_side* 
   if (dist) {
     GIQL_TRY(key_widened_side(ctx, st, *a, *b, nch, lb, clamp_widen(max_distance), sa, nullptr, os_a.hist, os_a.gbase));
   } else {
-    GIQL_TRY(run_linearize(ctx, st, *a, nch, lb, sa.key[0], sa.end[0], dummy_irr + 8, 0, 1, os_a.hist, os_a.gbase));
+    GIQL_TRY(run_linearize(ctx, st, *a, nch, lb, Side::A, LinTarget::keys_ends(sa.key[0], sa.end[0], dummy_irr + 8),
+                           LinOptions().keeping_irregular().counting_starts(os_a.starts())));
   }
-  GIQL_TRY(run_sort_onesweep(ctx, st, sa, (u32)na, os_a.gbase, os_a.status, false, nullptr, nullptr,
-                             /*skip_digits=*/row_skip(ctx, nb)));
+  GIQL_TRY(run_sort_onesweep(ctx, st, sa, sort_by_start(os_a, na).skipping_digits(row_skip(sort_tuning(ctx), nb))));
   // B: every row on its real key.  WITHIN and DISTANCE sort it by start with the end keys as payload; CONTAINS sorts
   // it by END with the start keys as payload -- a SortBufs is only pointers, and the linearize pass counts the end
   // keys' digits on the way (os.hist_e / os.gbase_e, as the COUNT path's second sort does).
   if (pred == GIQL_ROWPRED_CONTAINS) {
-    GIQL_TRY(run_linearize(ctx, st, *b, nch, lb, sbb.end[0], sbb.key[0], dummy_irr, 1, 1, os.hist, os.gbase, os.hist_e,
-                           os.gbase_e));
-    GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase_e, os.status));
+    // (the start keys land in the PAYLOAD array, the end keys in the key array)
+    GIQL_TRY(run_linearize(ctx, st, *b, nch, lb, Side::B, LinTarget::keys_ends(sbb.end[0], sbb.key[0], dummy_irr),
+                           LinOptions().keeping_irregular().counting_starts(os.starts()).counting_ends(os.ends())));
+    GIQL_TRY(run_sort_onesweep(ctx, st, sbb, sort_by_end(os, nb)));
   } else {
-    GIQL_TRY(run_linearize(ctx, st, *b, nch, lb, sbb.key[0], sbb.end[0], dummy_irr, 1, 1, os.hist, os.gbase));
-    GIQL_TRY(run_sort_onesweep(ctx, st, sbb, (u32)nb, os.gbase, os.status));
+    GIQL_TRY(run_linearize(ctx, st, *b, nch, lb, Side::B, LinTarget::keys_ends(sbb.key[0], sbb.end[0], dummy_irr),
+                           LinOptions().keeping_irregular().counting_starts(os.starts())));
+    GIQL_TRY(run_sort_onesweep(ctx, st, sbb, sort_by_start(os, nb)));
   }
   GIQL_TRY(run_pmax(ctx, st, sbb.end[0], (u32)nb, pmax, bmax));
   {
@@ -4491,12 +4486,12 @@ static int count_window(giql_hip_ctx* ctx, hipStream_t st, const giql_side* a, c
   }
   const i64 widen = clamp_widen(max_distance);
   GIQL_TRY(key_widened_side(ctx, st, *a, *b, n_chrom, lb, widen, sa, irr_a_list, os_a.hist, os_a.gbase));
-  GIQL_TRY(run_sort_onesweep(ctx, st, sa, (u32)na, os_a.gbase, os_a.status, false, nullptr, nullptr,
-                             /*skip_digits=*/row_skip(ctx, nb)));  // locality only: the kernel tells listed rows by their key
-  GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, sstart.key[0], send.key[0], irr_b_list, 1, 0, os.hist, os.gbase,
-                         os.hist_e, os.gbase_e));
-  GIQL_TRY(run_sort_onesweep(ctx, st, sstart, (u32)nb, os.gbase, os.status));
-  GIQL_TRY(run_sort_onesweep(ctx, st, send, (u32)nb, os.gbase_e, os.status));
+  // locality only: the kernel tells listed rows by their key
+  GIQL_TRY(run_sort_onesweep(ctx, st, sa, sort_by_start(os_a, na).skipping_digits(row_skip(sort_tuning(ctx), nb))));
+  GIQL_TRY(run_linearize(ctx, st, *b, n_chrom, lb, Side::B, LinTarget::keys_ends(sstart.key[0], send.key[0], irr_b_list),
+                         LinOptions().counting_starts(os.starts()).counting_ends(os.ends())));
+  GIQL_TRY(run_sort_onesweep(ctx, st, sstart, sort_by_start(os, nb)));
+  GIQL_TRY(run_sort_onesweep(ctx, st, send, sort_by_end(os, nb)));
   {
     Phase ph(ctx, st, GIQL_PH_COUNT);
     hipLaunchKernelGGL(k_rp_count_window_rows, dim3(cdiv(na, 256)), dim3(256), 0, st, sa.key[0], sa.end[0], sa.rid[0],
@@ -4669,12 +4664,13 @@ static int giql_hip_group_rows_dev_impl(giql_hip_ctx* ctx, const giql_side* s, i
   memset(&none, 0, sizeof(none));
   const bool two_sorts = ctx->guess.nearest_two_sorts;
   GIQL_TRY(run_spans(ctx, st, raw, none, n_chrom, lb));
-  GIQL_TRY(run_linearize(ctx, st, raw, n_chrom, lb, sb.key[0], sb.end[0], dummy_irr, 0, 1, os.hist,
-                         os.gbase, two_sorts ? os.hist_e : nullptr, two_sorts ? os.gbase_e : nullptr));
+  GIQL_TRY(run_linearize(ctx, st, raw, n_chrom, lb, Side::A, LinTarget::keys_ends(sb.key[0], sb.end[0], dummy_irr),
+                         LinOptions().keeping_irregular().counting_starts(os.starts())
+                             .counting_ends(two_sorts ? os.ends() : DigitCounts())));
   if (two_sorts) {
-    GIQL_TRY(run_sort_two_keys(ctx, st, sb, (u32)n, os.gbase, os.gbase_e, os.status));  // (start, end) order
+    GIQL_TRY(run_sort_two_keys(ctx, st, sb, (u32)n, os));  // (start, end) order
   } else {
-    GIQL_TRY(run_sort_onesweep(ctx, st, sb, (u32)n, os.gbase, os.status));
+    GIQL_TRY(run_sort_onesweep(ctx, st, sb, sort_by_start(os, n)));
     Phase ph(ctx, st, GIQL_PH_AUX);
     hipLaunchKernelGGL(k_fix_start_ties, dim3(cdiv(n, 256)), dim3(256), 0, st, sb.key[0], sb.end[0],
                        sb.rid[0], (u32)n, ctx->d_meta);
