@@ -11,10 +11,12 @@ was found by a long random soak.  So here:
 * Walk 1: per operator family, one fresh context walks an Eulerian circuit of the complete directed graph over the
   input classes (self-loops included): every ordered pair (X, Y) is a call on Y right after the context's last call
   on X.  Each visit runs the family twice; the second run must reach the path its class names (``SIGNATURES``).
-  The ``row_pred`` family is SEMI / ANTI / COUNT over CONTAINS, WITHIN and DISTANCE and the within-distance join.
-* Walk 2: one context, all twelve operators, DISJOIN's three and CONTAINS' three in a shuffled order per visit, with
-  ``select`` / ``take_utf8`` / a plan of another operator put between some plans and their fill -- which must then
-  refuse (``GIQL_ERR_STATE``): those calls reuse the workspace the plan lives in.
+  The ``row_pred`` family is SEMI / ANTI / COUNT over CONTAINS, WITHIN and DISTANCE and the within-distance join; the
+  ``one_table`` family is CLUSTER, MERGE, MERGE with aggregates and MERGE with STRING_AGG over the class's B table,
+  against the vectorised reference of ``tests/_one_table_ref.py``.
+* Walk 2: one context, all sixteen operators, DISJOIN's three and CONTAINS' three in a shuffled order per visit, with
+  ``select`` / ``take_utf8`` / a plan of another operator / a call of the one-table family put between some plans and
+  their fill -- which must then refuse (``GIQL_ERR_STATE``): those calls reuse the workspace the plan lives in.
 * DISJOIN (self mode, reference mode, plan + fill through the raw ABI) walks the classes on which its path can
   differ, against the brute force of ``tests/_disjoin_ref.py``; its plan lives in the same workspace, and the
   context keeps one plan at a time (``ctx->kept``; ``tests/test_plan_lifetime_gpu.py`` has the rule cell by cell).
@@ -168,6 +170,12 @@ WIDTH_FAMILIES = ("row", "nearest")   # sorts on the tight span: every settled c
 # density before it sorts -- but the statistics name the side sorted LAST, and COUNT over WITHIN sorts the small left
 # table last (it is the inner side of the CONTAINS plan): its settled calls report A's form, not the width B's density
 # asks for, so the family is not one of these)
+# (the ``one_table`` family -- CLUSTER, MERGE and its aggregates -- is not one either: cluster_front sorts before anything
+# of its own call is read back, on ``guess.last_span`` as the previous call left it, and its callers end in
+# collect_spans and ``stats.span`` without note_span -- they read the density and never set it, as DISJOIN does.  A
+# context that only ever ran this family keeps the fresh context's guess (a human-genome-sized axis), under which
+# every class here is sparse: four passes on every call, asserted in Walk 1; the widths are met in Walk 2, after other
+# operators' spans, and forced one by one in tests/test_one_table_paths.py)
 
 
 @functools.lru_cache(maxsize=None)
@@ -207,6 +215,19 @@ def test_class_constructions_are_what_they_claim():
     assert cl["many_chroms"][2] == 40 and cl["negative"][0].start.min() < 0 and cl["negative"][1].start.min() < 0
     a, b, _ = _oversized()
     assert np.sum(b.start < 4000) > BS_BIG_MAX and b.start.max() > 9_000_000
+    # the merged regions of the B tables at distance 0 (the ``one_table`` family): between them every band of region
+    # lengths on which the aggregate kernels take another path -- one row, inside a wave, inside a 256-row tile, across
+    # tiles inside one 64-tile fold step, across fold steps
+    import _one_table_ref as V
+
+    lengths = {name: V.Layout(cl[name][1].chrom, cl[name][1].start, cl[name][1].end, 0).count for name in NAMES}
+    bands = {"1": (1, 1), "2-63": (2, 63), "64-255": (64, 255), "256-16383": (256, 16_383), "16384-": (16_384, 2**31)}
+    met = {band: [name for name in NAMES if np.any((lengths[name] >= lo) & (lengths[name] <= hi))] for band, (lo, hi) in bands.items()}
+    assert all(met.values()), met
+    assert lengths["general"].max() <= 63 and "general" in met["1"] and "general" in met["2-63"]
+    assert "w16" in met["64-255"] and "w15" in met["256-16383"] and "w15" in met["16384-"]
+    assert all(lengths[name].max() >= 16_384 for name in ("w14", "w13"))
+    assert all(lengths[name].sum() == cl[name][1].n for name in NAMES)
 
 
 # ---------------------------------------------------------------- GPU side: resident sides, cached oracle answers
@@ -280,7 +301,7 @@ class Log:
         return set(zip(seq, seq[1:]))
 
 
-# ---- the twelve operators: each runs one call sequence on (class) and checks it against the oracle
+# ---- the operators: each runs one call sequence on (class) and checks it against the oracle
 def op_inner_join(eng, name, log, fam, rnd):
     _a, _b, nch, da, db = resident(name)
     ra, rb = eng.inner_join(da, db, nch)
@@ -662,6 +683,99 @@ def op_window_join(eng, name, log, fam, rnd):
     assert np.all((a.chrom[ra] == b.chrom[rb]) & (a.cs[ra] - n < b.ce[rb]) & (a.ce[ra] + n > b.cs[rb])), (name, "window_join")
 
 
+# ---- CLUSTER, MERGE, MERGE with aggregates and with STRING_AGG over the class's B (raw coordinates: its offsets are 0),
+# distance 0; truth = the vectorised reference of tests/_one_table_ref.py (held to the row-by-row ones in
+# tests/test_one_table_ref.py), once per class and kept on the device.  All four go through cluster_front: they sort by
+# start on the density another call left (``guess.last_span``), and leave it as they found it.
+ONE_TABLE_AGGS = (("SUM", "f"), ("MAX", "f"), ("SUM", "i"), ("MIN", "i"))
+
+
+@functools.lru_cache(maxsize=None)
+def one_table(name):
+    """``(layout, device inputs, device answers)`` of the class's B table."""
+    import _one_table_ref as V
+
+    _a, b, _nch, _da, _db = resident(name)
+    r = np.random.default_rng(7000 + NAMES.index(name) if name in NAMES else 7099)
+    lay = V.Layout(b.chrom, b.start, b.end, 0)
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to("cuda:0")
+    cols = {"f": ((r.normal(0, 1000, b.n) * r.choice([1e-3, 1.0, 1e3], b.n)), r.random(b.n) >= 0.3),
+            "i": (r.integers(-1_000_000, 1_000_000, b.n), r.random(b.n) >= 0.3)}
+    letters, null = r.integers(97, 123, (b.n, 3), dtype=np.uint8), r.random(b.n) < 0.2
+    words = [None if null[i] else b"%d:" % i + bytes(letters[i, :i % 4]) for i in range(b.n)]      # every value names its row
+    lens = np.array([0 if w is None else len(w) for w in words], np.int64)
+    inputs = {k: (dev(v), dev(ok.astype(np.uint8))) for k, (v, ok) in cols.items()}
+    inputs["words"] = (dev(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)),
+                       dev(np.frombuffer(b"".join(w or b"" for w in words), np.uint8).copy()), dev((~null).astype(np.uint8)))
+    answers = {"ids": dev(lay.cluster_ids()),
+               "rows": [dev(x.astype(np.int64 if k == 3 else np.int32)) for k, x in enumerate(lay.merge_rows())]}
+    for func, c in ONE_TABLE_AGGS:
+        vals, ok = lay.aggregate(func, *cols[c])
+        answers[func, c] = (dev(vals), dev(ok))
+    # a float SUM over k non-NULL values: within k * 2^-52 * sum|x_i| of fsum (tests/test_merge_aggregates_gpu.py)
+    answers["bound"] = dev(lay.non_null(cols["f"][1]) * 2.0**-52 * lay.abs_sum(*cols["f"]))
+    off, data, ok = lay.string_agg(words, b",")
+    answers["str"] = (dev(off.astype(np.int32)), dev(np.frombuffer(data, np.uint8).copy()), dev(ok))
+    return lay, inputs, answers
+
+
+@functools.lru_cache(maxsize=None)
+def _inverted_raw():
+    """``irregular``'s A with its offsets set to 0, as CLUSTER / MERGE take a table: its inverted rows stay."""
+    a = classes()["irregular"][0]
+    assert np.any(a.end < a.start)
+    return _dev(ora.Side(a.chrom, a.start, a.end))
+
+
+def _merge_rows_equal(out, answers, what):
+    assert all(g.shape == w.shape and torch.equal(g, w) for g, w in zip(out[:4], answers["rows"])), what
+
+
+def op_cluster(eng, name, log, fam, rnd):
+    from giql_amd import _lib
+
+    _a, _b, nch, _da, db = resident(name)
+    if name == "irregular":      # inverted rows are refused, and the very next call on the context is right
+        with pytest.raises(_lib.GiqlHipError, match="need start <= end") as exc:
+            eng.cluster(_inverted_raw(), nch, 0)
+        assert exc.value.code == _lib.GIQL_ERR_INVALID, exc.value
+    ids = eng.cluster(db, nch, 0)
+    log.add(eng, fam, name, rnd, "cluster")
+    assert torch.equal(ids, one_table(name)[2]["ids"]), (name, "cluster")
+
+
+def op_merge(eng, name, log, fam, rnd):
+    _a, _b, nch, _da, db = resident(name)
+    out = eng.merge(db, nch, 0)
+    log.add(eng, fam, name, rnd, "merge")
+    _merge_rows_equal(out, one_table(name)[2], (name, "merge"))
+
+
+def op_merge_agg(eng, name, log, fam, rnd):
+    _a, _b, nch, _da, db = resident(name)
+    _lay, inputs, answers = one_table(name)
+    out = eng.merge_agg(db, nch, 0, [(f,) + inputs[c] for f, c in ONE_TABLE_AGGS])
+    log.add(eng, fam, name, rnd, "merge_agg")
+    _merge_rows_equal(out, answers, (name, "merge_agg"))
+    for (func, c), (vals, ok) in zip(ONE_TABLE_AGGS, out[4:]):
+        want, want_ok = answers[func, c]
+        assert torch.equal(ok, want_ok) and vals.dtype == want.dtype, (name, func, c, "validity")
+        if (func, c) == ("SUM", "f"):
+            assert bool(((vals - want).abs() <= answers["bound"]).all()), (name, "SUM(f)")
+        else:
+            assert torch.equal(vals, want), (name, func, c)
+
+
+def op_merge_str(eng, name, log, fam, rnd):
+    _a, _b, nch, _da, db = resident(name)
+    _lay, inputs, answers = one_table(name)
+    out = eng.merge_agg(db, nch, 0, [("STRING_AGG",) + inputs["words"] + (b",",)])
+    log.add(eng, fam, name, rnd, "merge_str")       # (the string fill is the last call: these stats name no sort)
+    _merge_rows_equal(out, answers, (name, "merge_str"))
+    assert all(g.shape == w.shape and torch.equal(g, w) for g, w in zip(out[4], answers["str"])), (name, "merge_str")
+
+
+ONE_TABLE_OPS = [op_cluster, op_merge, op_merge_agg, op_merge_str]
 FAMILIES = {
     "inner": [op_inner_join, op_into_exact, op_into_short, op_into_ample, op_plan_fill],
     "row": [op_semi, op_anti, op_count],
@@ -669,8 +783,9 @@ FAMILIES = {
     "group_rows": [op_group_rows],
     "index": [op_index],
     "row_pred": [op_semi_pred, op_count_pred, op_window_join],
+    "one_table": ONE_TABLE_OPS,
 }
-ALL_OPS = [op for fam, ops in FAMILIES.items() if fam != "row_pred" for op in ops]   # (Walk 2 and Leg 3: the twelve)
+ALL_OPS = [op for fam, ops in FAMILIES.items() if fam != "row_pred" for op in ops]   # (Walk 2 and Leg 3: the sixteen)
 
 
 def _check_signature(log, name):
@@ -723,6 +838,12 @@ def test_walk_every_ordered_pair_of_classes(monkeypatch, family):
             assert crossed, (family, name)
     if family == "inner":
         assert any(c[4]["bucket_join"] for c in log.calls if c[2] == 2), "no settled INNER call joined in the bucket stage"
+    if family == "one_table":
+        # the family reads the density guess and never sets it: this context keeps the fresh one's, every sort takes
+        # four passes (a call of the family that set ``last_span`` would send w16 - w13 to the bucket stage here)
+        assert not any(c[4]["sort_local"] or c[4]["sort_resorted"] for c in log.calls)
+        refused = [k for k, c in enumerate(log.calls) if c[1] == "irregular" and c[3] == "cluster"]
+        assert len(refused) == 2 * len(NAMES)       # each behind a refused CLUSTER of inverted rows, each right
 
 
 @pytest.mark.gpu
@@ -817,60 +938,116 @@ def _intrude_contain_plan(eng, name):
     assert _contain_plan_raw(eng, da, db, nch) == (0, want_contain("general", "contains").shape[0])
 
 
+def _intrude_one_table(op):
+    """A call of the one-table family between a plan and its fill: every one of its entry points begins a call and
+    carves the workspace anew, so whatever plan the context keeps is dropped (the cells ``cluster``, ``merge``,
+    ``merge_agg`` of tests/test_plan_lifetime_gpu.py: all dropped; ``giql_hip_merge_str_dev``:
+    tests/test_string_agg_gpu.py::test_merge_str_drops_a_plan_the_context_keeps)."""
+    def intruder(eng, name):
+        op(eng, name, Log(), "intruder", 1)
+    intruder.__name__ = "_intrude_" + op.__name__[3:]
+    return intruder
+
+
 INTRUDERS = {"select": _intrude_select, "take_utf8": _intrude_take_utf8, "inner_plan": _intrude_inner_plan,
-             "disjoin_plan": _intrude_disjoin_plan, "contain_plan": _intrude_contain_plan, None: None}
+             "disjoin_plan": _intrude_disjoin_plan, "contain_plan": _intrude_contain_plan, None: None,
+             **{op.__name__[3:]: _intrude_one_table(op) for op in ONE_TABLE_OPS}}
+ONE_TABLE_INTRUDERS = tuple(op.__name__[3:] for op in ONE_TABLE_OPS)      # cluster, merge, merge_agg, merge_str
 MIXED_OPS = ALL_OPS + DISJOIN_OPS + CONTAIN_OPS
+
+
+def _which_intruder(r, others, turn, met):
+    """What comes between the ``turn``-th plan of a kind and its fill: every third time a call of the one-table family,
+    its four operators in turn (noted in ``met``); else one of ``others``."""
+    if turn % 3 != 2:
+        return others[int(r.integers(0, len(others)))]
+    met.append(ONE_TABLE_INTRUDERS[turn // 3 % len(ONE_TABLE_INTRUDERS)])
+    return met[-1]
+
+
+PLAN_OPS = {   # a plan + fill operator -> (the plan's kind, what may come between the two besides a one-table call)
+    op_plan_fill: ("inner", ("select", "take_utf8", None, "disjoin_plan", "contain_plan")),
+    op_disjoin_plan_fill: ("disjoin", ("select", "take_utf8", "inner_plan", None, "contain_plan")),
+    op_contain_plan_fill: ("contain", ("select", "take_utf8", "inner_plan", "disjoin_plan", None)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def mixed_schedule():
+    """Walk 2, call by call: ``(class, operator, what comes between its plan and its fill)`` -- every class twice, the
+    operators shuffled per visit.  Pure, so that what the walk meets can be checked without a GPU."""
+    r = np.random.default_rng(2027)
+    visits = list(r.permutation(len(NAMES))) + list(r.permutation(len(NAMES)))
+    turns = {kind: 0 for kind, _others in PLAN_OPS.values()}
+    out = []
+    for v in visits:
+        for k in r.permutation(len(MIXED_OPS)):
+            op, which = MIXED_OPS[k], None
+            if op in PLAN_OPS:
+                kind, others = PLAN_OPS[op]
+                which = _which_intruder(r, others, turns[kind], [])
+                turns[kind] += 1
+            out.append((NAMES[v], op, which))
+    return out
+
+
+def interruptions(schedule):
+    """plan kind -> {what interrupted it: times}.  (A DISJOIN plan on ``irregular`` is refused: nothing to interrupt.)"""
+    met = {kind: {} for kind, _others in PLAN_OPS.values()}
+    for name, op, which in schedule:
+        if which is not None and not (op is op_disjoin_plan_fill and name == "irregular"):
+            kind = PLAN_OPS[op][0]
+            met[kind][which] = met[kind].get(which, 0) + 1
+    return met
+
+
+def test_mixed_schedule_meets_every_interruption():
+    """CPU: every plan kind is interrupted by every call that can drop it -- the four one-table operators among them --
+    and every operator runs on every class."""
+    met = interruptions(mixed_schedule())
+    for _kind, others in PLAN_OPS.values():
+        assert all(met[_kind].get(w, 0) > 0 for w in others if w is not None), (_kind, met[_kind])
+        assert all(met[_kind].get(w, 0) > 0 for w in ONE_TABLE_INTRUDERS), (_kind, met[_kind])
+    assert {(name, op) for name, op, _w in mixed_schedule()} == {(name, op) for name in NAMES for op in MIXED_OPS}
 
 
 @pytest.mark.gpu
 def test_walk_mixed_operators_with_interrupted_plans(monkeypatch):
     eng = _density_engine(monkeypatch)
     log = Log()
-    r = np.random.default_rng(2027)
-    visits = list(r.permutation(len(NAMES))) + list(r.permutation(len(NAMES)))
-    interrupted = {"select": 0, "take_utf8": 0}
-    dj_interrupted = {"select": 0, "take_utf8": 0, "inner_plan": 0, "contain_plan": 0}
-    ct_interrupted = {"select": 0, "take_utf8": 0, "inner_plan": 0, "disjoin_plan": 0}
-    inner_by_disjoin = inner_by_contain = 0
     try:
-        for v in visits:
-            name = NAMES[v]
-            for k in r.permutation(len(MIXED_OPS)):
-                op = MIXED_OPS[k]
-                if op is op_plan_fill:
-                    which = ("select", "take_utf8", None, "disjoin_plan", "contain_plan")[int(r.integers(0, 5))]
-                    op(eng, name, log, "mixed", 1, intruder=INTRUDERS[which])
-                    if which == "disjoin_plan":
-                        inner_by_disjoin += 1
-                    elif which == "contain_plan":
-                        inner_by_contain += 1
-                    elif which:
-                        interrupted[which] += 1
-                elif op is op_disjoin_plan_fill:
-                    which = ("select", "take_utf8", "inner_plan", None, "contain_plan")[int(r.integers(0, 5))]
-                    op(eng, name, log, "mixed", 1, intruder=INTRUDERS[which])
-                    if which and name != "irregular":
-                        dj_interrupted[which] += 1
-                elif op is op_contain_plan_fill:
-                    which = ("select", "take_utf8", "inner_plan", "disjoin_plan", None)[int(r.integers(0, 5))]
-                    op(eng, name, log, "mixed", 1, intruder=INTRUDERS[which])
-                    if which:
-                        ct_interrupted[which] += 1
-                else:
-                    op(eng, name, log, "mixed", 1)
+        for name, op, which in mixed_schedule():
+            if op in PLAN_OPS:
+                op(eng, name, log, "mixed", 1, intruder=INTRUDERS[which])
+            else:
+                op(eng, name, log, "mixed", 1)
     finally:
         eng.close()
+    met = interruptions(mixed_schedule())
+    interrupted = {w: met["inner"].get(w, 0) for w in ("select", "take_utf8")}
+    dj_interrupted = {w: met["disjoin"].get(w, 0) for w in ("select", "take_utf8", "inner_plan", "contain_plan")}
+    ct_interrupted = {w: met["contain"].get(w, 0) for w in ("select", "take_utf8", "inner_plan", "disjoin_plan")}
+    inner_by_disjoin, inner_by_contain = met["inner"].get("disjoin_plan", 0), met["inner"].get("contain_plan", 0)
+    by_one_table = {kind: {w: met[kind].get(w, 0) for w in ONE_TABLE_INTRUDERS} for kind in met}
     dj = [c[4] for c in log.calls if c[3].startswith("disjoin") and c[1] != "irregular"]
     forms = sorted({(st["sort_local"], st["bucket_bits"]) for st in dj})
     print(f"\n[mixed] ordered class pairs covered: {len(log.transitions('mixed'))}; interrupted plans: {interrupted}; "
           f"DISJOIN plans interrupted: {dj_interrupted}; INNER plans interrupted by a DISJOIN plan: {inner_by_disjoin}; "
           f"DISJOIN (three-stage sort, bucket bits) seen: {forms}; CONTAINS plans interrupted: {ct_interrupted}; "
-          f"INNER plans interrupted by a CONTAINS plan: {inner_by_contain}")
+          f"INNER plans interrupted by a CONTAINS plan: {inner_by_contain}; plans interrupted by a one-table call: {by_one_table}")
     assert interrupted["select"] > 0 and interrupted["take_utf8"] > 0
     assert all(v > 0 for v in dj_interrupted.values()) and inner_by_disjoin > 0
     assert all(v > 0 for v in ct_interrupted.values()) and inner_by_contain > 0
     # DISJOIN takes its bucket width from the span another operator left on the context: both sort forms were met
     assert any(st["sort_local"] for st in dj) and any(not st["sort_local"] for st in dj)
+    # every plan kind was dropped by each of the four one-table operators (the refusal is asserted where it happens)
+    assert all(v > 0 for kind in by_one_table.values() for v in kind.values()), by_one_table
+    # ... which take their bucket width from the span another operator left, too: four passes and narrow buckets
+    ot = [c[4] for c in log.calls if c[3] in ("cluster", "merge", "merge_agg")]
+    ot_forms = sorted({(st["sort_local"], st["bucket_bits"] if st["sort_local"] else None) for st in ot}, key=str)
+    print(f"[mixed] one-table (three-stage sort, bucket bits) seen: {ot_forms}")
+    assert any(not st["sort_local"] for st in ot) and {st["bucket_bits"] for st in ot if st["sort_local"]} & {13, 14, 15}
+    assert not any(st["sort_resorted"] for st in ot)
 
 
 # ---------------------------------------------------------------- Leg 3: the sticky four-pass fallback
