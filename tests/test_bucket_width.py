@@ -15,6 +15,7 @@ tests take the width from the density alone, on default contexts.
 import numpy as np
 import pytest
 
+from _nearest_cases import assert_groups
 from oracle import pyoracle as ora
 from test_gpu_parity import dev, rand_side, uniform_side
 from test_sort_stages import _all_ops, _fused_inner, _inner, _join_into, _plain
@@ -293,7 +294,7 @@ def test_narrow_buckets_keep_the_two_key_sorts_stable(eng_narrow):
         j = idx.cpu().numpy()
         assert np.array_equal(b.start[j], b.start[oi]) and np.array_equal(b.end[j], b.end[oi])
     gid, rep = eng_narrow.group_rows(dev(b), 1)
-    assert rep.shape[0] == len({(int(x), int(y)) for x, y in zip(b.start, b.end)})
+    assert_groups(b.chrom, b.start, b.end, gid.cpu().numpy(), rep.cpu().numpy(), "narrow buckets, two-sort plan")
     assert eng_narrow.stats()["sort_local"]
     # the context stays on the two-sort plan: a table WITHOUT long runs (many rows per start all the same: ~4 rows on each
     # of 66,000 positions, 33 chromosomes -- the soak's case), every overlapping tie decided by the end

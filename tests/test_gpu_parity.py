@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import _golden as G
+from _nearest_cases import assert_groups
 from oracle import pyoracle as ora
 
 pytestmark = pytest.mark.gpu
@@ -1159,7 +1160,7 @@ def test_group_rows_and_segment_sum(eng):
     # a pile-up of equal starts (two-sort plan) still groups exactly
     s2 = ora.Side(np.zeros(500, np.int32), np.full(500, 77, np.int32), (77 + rng.integers(0, 7, 500)).astype(np.int32))
     g2, r2 = eng.group_rows(dev(s2), 1)
-    assert r2.shape[0] == len(set(s2.end.tolist()))
+    assert_groups(s2.chrom, s2.start, s2.end, g2.cpu().numpy(), r2.cpu().numpy(), "a pile-up of equal starts")
 
 
 @pytest.mark.parametrize("seed", range(24))
@@ -1196,7 +1197,7 @@ def test_randomized_sweep_all_operators(eng, seed):
         c, s, e, n = (t.cpu().numpy() for t in eng.merge(dev(raw), n_chrom, d))
         assert list(zip(c, s, e, n)) == list(zip(*ora.c_merge(raw, d)))
     gid, rep = eng.group_rows(dev(a), max(n_chrom, 1))
-    assert rep.shape[0] == len({(int(x), int(y), int(z)) for x, y, z in zip(a.chrom, a.start, a.end)})
+    assert_groups(a.chrom, a.start, a.end, gid.cpu().numpy(), rep.cpu().numpy(), seed)
 
 
 def test_fused_inner_join_into_caller_buffers():

@@ -11,6 +11,7 @@ sort when a bucket is too large for LDS.
 import numpy as np
 import pytest
 
+from _nearest_cases import assert_groups
 from oracle import pyoracle as ora
 from test_gpu_parity import dev, rand_side, uniform_side
 
@@ -117,7 +118,7 @@ def test_three_stage_sort_is_stable_for_the_two_key_sorts(eng_local):
         j = idx.cpu().numpy()
         assert np.array_equal(b.start[j], b.start[oi]) and np.array_equal(b.end[j], b.end[oi])
     gid, rep = eng_local.group_rows(dev(b), 1)
-    assert rep.shape[0] == len({(int(x), int(y)) for x, y in zip(b.start, b.end)})
+    assert_groups(b.chrom, b.start, b.end, gid.cpu().numpy(), rep.cpu().numpy(), "three-stage sort, two-sort plan")
     assert eng_local.stats()["sort_local"]
 
 
