@@ -62,6 +62,9 @@ RANGE_SET_SYMBOLS = ["giql_hip_range_set_any_dev"]
 #: every symbol include/giql_hip_string_agg.h declares (STRING_AGG beside MERGE)
 STRING_AGG_SYMBOLS = ["giql_hip_merge_str_dev", "giql_hip_concat_utf8_fill_dev"]
 
+#: every symbol include/giql_hip_pair_agg.h declares (aggregates over a join's pairs, per left row)
+PAIR_AGG_SYMBOLS = ["giql_hip_pair_agg_dev"]
+
 
 class GiqlHipUnavailable(RuntimeError):
     """libgiql_hip.so could not be loaded (not built, or no ROCm runtime)."""
@@ -297,6 +300,7 @@ def load() -> ctypes.CDLL:
     L.giql_hip_merge_str_dev.argtypes = [vp, P(CSide), i32, i64, P(CPred), i32, P(CAgg), i32, P(CStrAgg), i32,
                                          vp, vp, vp, vp, vp, i64, P(i64), vp]
     L.giql_hip_concat_utf8_fill_dev.argtypes = [vp, vp, vp, i64, vp, vp, i64, ctypes.c_char_p, i32, vp, vp]
+    L.giql_hip_pair_agg_dev.argtypes = [vp, vp, vp, i64, i64, i64, P(CAgg), i32, vp, vp]
     _lib = L
     return L
 

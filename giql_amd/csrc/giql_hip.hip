@@ -21,6 +21,7 @@
 #include "../../include/giql_hip.h"
 #include "../../include/giql_hip_range_sets.h"
 #include "../../include/giql_hip_string_agg.h"
+#include "../../include/giql_hip_pair_agg.h"
 #include "aux_kernels.hip.h"
 #include "take_kernels.hip.h"
 #include "select_kernels.hip.h"
@@ -29,6 +30,7 @@
 #include "cluster_kernels.hip.h"
 #include "merge_agg_kernels.hip.h"
 #include "string_agg_kernels.hip.h"
+#include "pair_agg_kernels.hip.h"
 #include "range_set_kernels.hip.h"
 #include "disjoin_kernels.hip.h"
 #include "contain_kernels.hip.h"
@@ -1026,12 +1028,15 @@ static int run_sort_two_keys(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u3
 }
 
 // Stable LSD radix sort; input in buffer 0, result in buffer 0 (4 passes).
-// rids: identity on the first pass.  Payload-less when bufs.end[0] == nullptr.
+// rids: identity on the first pass.  Payload-less when bufs.end[0] == nullptr; (key, payload) rows without row ids
+// when only bufs.rid[0] is.
+// passes (0..4): keys below 2^(8 * passes) need no pass on their upper digits; after an odd number the result lies in
+// the other physical buffer, which then becomes "buffer 0" (SortBufs::flip).
 static int run_sort(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u32 n, u32* tile_hist,
-                    u64* bsums) {
-  if (n == 0) return GIQL_OK;
+                    u64* bsums, int passes = 4) {
+  if (n == 0 || passes == 0) return GIQL_OK;
   const u32 n_tiles = cdiv(n, RS_TILE);
-  for (int pass = 0; pass < 4; pass++) {
+  for (int pass = 0; pass < passes; pass++) {
     const int src = pass & 1, dst = src ^ 1;
     const int shift = pass * 8;
     {
@@ -1043,7 +1048,11 @@ static int run_sort(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u32 n, u32*
                            bsums, nullptr));
     {
       Phase ph(ctx, st, GIQL_PH_SORT_SCATTER);
-      if (sb.end[0]) {
+      if (sb.end[0] && !sb.rid[0]) {  // (key, payload) rows without row ids
+        hipLaunchKernelGGL((k_radix_scatter<true, false>), dim3(n_tiles), dim3(RS_NT), 0, st, sb.key[src],
+                           sb.end[src], (const u32*)nullptr, sb.key[dst], sb.end[dst], (u32*)nullptr, n, shift,
+                           n_tiles, tile_hist);
+      } else if (sb.end[0]) {
         hipLaunchKernelGGL((k_radix_scatter<true>), dim3(n_tiles), dim3(RS_NT), 0, st, sb.key[src],
                            sb.end[src], pass == 0 ? (const u32*)nullptr : sb.rid[src], sb.key[dst],
                            sb.end[dst], sb.rid[dst], n, shift, n_tiles, tile_hist);
@@ -1054,6 +1063,7 @@ static int run_sort(giql_hip_ctx* ctx, hipStream_t st, SortBufs& sb, u32 n, u32*
       }
     }
   }
+  if (passes & 1) sb.flip();
   return post_launch("radix sort");
 }
 
@@ -3940,6 +3950,141 @@ int giql_hip_concat_utf8_fill_dev(giql_hip_ctx* ctx, const int32_t* offsets, con
     return set_err(GIQL_ERR_INVALID, "concat_utf8_fill: a row id outside the column, a decreasing offset pair or a "
                                      "separator before the output's start");
   ctx->stats.n_out = n;
+  return GIQL_OK;
+}
+
+// ------------------------------------------------ aggregates over a join's pairs, per left row
+// include/giql_hip_pair_agg.h.  A post-pass over the caller's pair arrays (pair_agg_kernels.hip.h): check + load ->
+// stable sort by row_b (only where a float SUM / MIN / MAX makes the order matter) -> stable sort by row_a -> region flags ->
+// scan -> k_magg_tiles / k_magg_fold over the regions -> scatter to the A rows.  The sorts are run_sort with as many
+// passes as the ids have digits: the same launches on every context, whatever its sort switches say.
+static int pagg_digits(int64_t n_rows) {
+  int p = 0;
+  while (p < 4 && ((u64)(n_rows > 0 ? n_rows - 1 : 0) >> (8 * p)) != 0) p++;
+  return p;
+}
+
+int giql_hip_pair_agg_dev(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t* row_b, int64_t n_pairs, int64_t n_a,
+                          int64_t n_b, const giql_agg* aggs, int32_t n_aggs, int64_t* pairs_out, void* stream) {
+  if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
+  // Begins a call before its own checks: whatever it goes on to return, a plan the context held is gone.
+  GIQL_TRY(begin_call(ctx, n_a, n_b));
+  if (n_pairs < 0 || n_a < 0 || n_b < 0 || n_a > 0x7FFFFFFFll || n_b > 0x7FFFFFFFll)
+    return set_err(GIQL_ERR_INVALID, "bad arguments (n_pairs, n_a, n_b: 0 to 2^31 - 1)");
+  if (n_pairs >= ((int64_t)1 << 31))
+    return set_err(GIQL_ERR_INVALID, "%lld pairs: one call aggregates fewer than 2^31", (long long)n_pairs);
+  if (n_aggs < 0 || n_aggs > MAGG_MAX || (n_aggs && !aggs))
+    return set_err(GIQL_ERR_INVALID, "%d aggregates: a pair aggregate takes 0 to %d", n_aggs, MAGG_MAX);
+  MaggArgs ma;
+  memset(&ma, 0, sizeof(ma));
+  ma.n_aggs = n_aggs;
+  // a float SUM, MIN or MAX: the aggregates whose bits depend on the order of their inputs (a sum's rounding; which of
+  // +0.0 and -0.0 a MIN / MAX keeps)
+  bool ordered = false;
+  for (int k = 0; k < n_aggs; k++) {
+    const giql_agg& g = aggs[k];
+    if (g.func < GIQL_AGG_COUNT || g.func > GIQL_AGG_MAX)
+      return set_err(GIQL_ERR_INVALID, "aggregate %d: function %d", k, g.func);
+    if (g.type < GIQL_T_I32 || g.type > GIQL_T_F64)
+      return set_err(GIQL_ERR_INVALID, "aggregate %d: column type %d (int32, int64, float32 or float64)", k, g.type);
+    if (!g.out) return set_err(GIQL_ERR_INVALID, "aggregate %d: out is NULL", k);
+    if (!g.data && g.func != GIQL_AGG_COUNT)
+      return set_err(GIQL_ERR_INVALID, "aggregate %d: data is NULL (only COUNT reads validity alone)", k);
+    // COUNT never reads the values: its column is the validity alone, shared by every COUNT over it
+    const MaggCol want = g.func == GIQL_AGG_COUNT ? MaggCol{nullptr, (const unsigned char*)g.valid, MAGG_T_NONE}
+                                                  : MaggCol{g.data, (const unsigned char*)g.valid, g.type};
+    int c = 0;
+    while (c < ma.n_cols && !(ma.cols[c].data == want.data && ma.cols[c].valid == want.valid && ma.cols[c].type == want.type)) c++;
+    if (c == ma.n_cols) ma.cols[ma.n_cols++] = want;
+    ma.aggs[k].func = g.func;
+    ma.aggs[k].col = c;
+    if (g.func != GIQL_AGG_COUNT && (g.type == GIQL_T_F32 || g.type == GIQL_T_F64)) ordered = true;
+  }
+  if (n_a > 0 && !pairs_out) return set_err(GIQL_ERR_INVALID, "pairs_out is NULL");
+  if (n_a > 0 && n_pairs > 0 && (!row_a || !row_b)) return set_err(GIQL_ERR_INVALID, "row_a or row_b is NULL");
+  if (n_a == 0) return GIQL_OK;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(pairs_out, 0, (size_t)n_a * sizeof(int64_t), st));
+  for (int k = 0; k < n_aggs; k++) {
+    HIP_TRY(hipMemsetAsync(aggs[k].out, 0, (size_t)n_a * sizeof(u64), st));
+    if (aggs[k].out_nn) HIP_TRY(hipMemsetAsync(aggs[k].out_nn, 0, (size_t)n_a * sizeof(i64), st));
+  }
+  if (n_pairs == 0) {
+    HIP_TRY(hipStreamSynchronize(st));
+    return GIQL_OK;
+  }
+  if (n_b == 0) return set_err(GIQL_ERR_INVALID, "pair aggregate: pairs over a B table without rows");
+  const size_t n = (size_t)n_pairs;
+  const size_t m_max = n < (size_t)n_a ? n : (size_t)n_a;  // regions: distinct A rows among the pairs
+  const u32 n_tiles = cdiv(n, MAGG_TILE), rs_tiles = cdiv(n, RS_TILE);
+  SortBufs sb;
+  u32 *tile_hist = nullptr, *flags = nullptr, *excl = nullptr, *head_pos = nullptr;
+  u64 *bsums = nullptr, *total = nullptr, *seg = nullptr, *carry = nullptr;
+  auto carve = [&](char* base) {
+    Carver c{base};
+    sort_sizes_key_payload(c, n, sb);  // 16 bytes per pair: (row_b, row_a) twice -- no row id column, nothing reads one
+    tile_hist = c.take<u32>((size_t)rs_tiles * RS_BINS);
+    const size_t scan_max = (size_t)rs_tiles * RS_BINS > n ? (size_t)rs_tiles * RS_BINS : n;
+    bsums = c.take<u64>(cdiv(scan_max, SCAN_TILE) + 2);
+    total = c.take<u64>(1);
+    flags = c.take<u32>(n);
+    excl = c.take<u32>(n + 1);
+    head_pos = c.take<u32>(m_max + 1);
+    seg = c.take<u64>((size_t)n_aggs * 2 * m_max);
+    carry = c.take<u64>((size_t)n_aggs * 4 * n_tiles);
+    return c.off;
+  };
+  GIQL_TRY(claim_arena(ctx, st, carve));
+  HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
+  const u32 grid = cdiv(n, PAGG_NT);
+  {
+    Phase ph(ctx, st, GIQL_PH_AUX);
+    hipLaunchKernelGGL(k_pagg_load, dim3(grid), dim3(PAGG_NT), 0, st, row_a, row_b, (u32)n, (u32)n_a, (u32)n_b,
+                       sb.key[0], sb.end[0], &ctx->d_meta->status);
+    GIQL_TRY(post_launch("pair aggregate (load)"));
+  }
+  if (ordered) GIQL_TRY(run_sort(ctx, st, sb, (u32)n, tile_hist, bsums, pagg_digits(n_b)));
+  SortBufs by_a = sb.keyed_by_end();  // (taken after the first sort: a view does not follow a flip)
+  GIQL_TRY(run_sort(ctx, st, by_a, (u32)n, tile_hist, bsums, pagg_digits(n_a)));
+  const u32 *sorted_a = by_a.key[0], *sorted_b = by_a.end[0];
+  {
+    Phase ph(ctx, st, GIQL_PH_COUNT);
+    hipLaunchKernelGGL(k_pagg_heads, dim3(grid), dim3(PAGG_NT), 0, st, sorted_a, (u32)n, flags);
+    GIQL_TRY(post_launch("pair aggregate (heads)"));
+  }
+  GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, flags, (u64)n, excl, bsums, total));
+  PaggScatter sc;
+  memset(&sc, 0, sizeof(sc));
+  sc.n_aggs = n_aggs;
+  for (int k = 0; k < n_aggs; k++) {
+    u64* sv = seg + (size_t)k * 2 * m_max;
+    u64* w = carry + (size_t)k * 4 * n_tiles;
+    ma.aggs[k].out = sv, ma.aggs[k].out_nn = (i64*)(sv + m_max);
+    ma.aggs[k].first_v = w, ma.aggs[k].last_v = w + n_tiles;
+    ma.aggs[k].first_c = (i64*)(w + 2 * (size_t)n_tiles), ma.aggs[k].last_c = (i64*)(w + 3 * (size_t)n_tiles);
+    sc.a[k] = PaggOut{sv, (const i64*)(sv + m_max), (u64*)aggs[k].out, (i64*)aggs[k].out_nn};
+  }
+  {
+    Phase ph(ctx, st, GIQL_PH_FILL, 2 + (n_aggs ? (n_tiles > 1 ? 2 : 1) : 0));
+    hipLaunchKernelGGL(k_merge_heads, dim3(grid), dim3(256), 0, st, flags, excl, (u32)n, head_pos);
+    if (n_aggs) {
+      hipLaunchKernelGGL(k_magg_tiles, dim3(n_tiles), dim3(MAGG_TILE), 0, st, sorted_b, excl, flags, (u32)n, ma);
+      if (n_tiles > 1)
+        hipLaunchKernelGGL(k_magg_fold, dim3(cdiv((u64)n_tiles - 1, 256 / WAVE)), dim3(256), 0, st, excl, flags, (u32)n,
+                           n_tiles, ma);
+    }
+    hipLaunchKernelGGL(k_pagg_scatter, dim3(grid), dim3(PAGG_NT), 0, st, sorted_a, flags, excl, head_pos, total, (u32)n,
+                       (u32)n_a, (i64*)pairs_out, sc);
+    GIQL_TRY(post_launch("pair aggregate"));
+  }
+  int status = 0;
+  HIP_TRY(hipMemcpyAsync(&status, &ctx->d_meta->status, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  collect_spans(ctx);
+  if (status != 0)
+    return set_err(GIQL_ERR_INVALID, "pair aggregate: a row_a outside [0, %lld) or a row_b outside [0, %lld)",
+                   (long long)n_a, (long long)n_b);
+  ctx->stats.n_out = n_a;
   return GIQL_OK;
 }
 

@@ -29,8 +29,9 @@ enum { MAGG_COUNT = 0, MAGG_SUM = 1, MAGG_MIN = 2, MAGG_MAX_ = 3 };  // = GIQL_A
 struct MaggCol {
   const void* data;
   const unsigned char* valid;  // nullptr: all valid
-  int type;                    // GIQL_T_I32 / I64 / F32 / F64
+  int type;                    // GIQL_T_I32 / I64 / F32 / F64, or MAGG_T_NONE
 };
+constexpr int MAGG_T_NONE = -1;  // a column read for its validity alone (COUNT over a column with no numeric data)
 struct MaggAgg {
   int func, col;  // MAGG_*, index into cols
   u64* out;       // per region: the int64 / binary64 pattern (COUNT: the count)
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(MAGG_TILE) void k_magg_tiles(const u32* __restrict_
       if (col.type == 0) x = (u64)(i64) reinterpret_cast<const int*>(col.data)[r];
       else if (col.type == 1) x = (u64) reinterpret_cast<const i64*>(col.data)[r];
       else if (col.type == 2) x = (u64)__double_as_longlong((double)reinterpret_cast<const float*>(col.data)[r]);
-      else x = reinterpret_cast<const u64*>(col.data)[r];
+      else if (col.type == 3) x = reinterpret_cast<const u64*>(col.data)[r];
     }
     for (int a = 0; a < A.n_aggs; a++) {
       const MaggAgg ag = A.aggs[a];

@@ -1203,6 +1203,80 @@ class HipEngine:
         r = int(m.value)
         return (c[:r], st[:r], en[:r], cnt[:r]) + tuple(self._agg_results(aggs, kernel, slot, r))
 
+    #: aggregates per :meth:`pair_aggregate` call, as asked for (``GIQL_PAIR_AGG_MAX`` kernel aggregates)
+    PAIR_AGG_MAX = 8
+
+    def pair_aggregate(self, row_a, row_b, n_a: int, n_b: int, aggs):
+        """Aggregates over a join's pairs per left row (``giql_hip_pair_agg_dev``; bedtools ``map``): ``row_a`` /
+        ``row_b`` are the int32 device pair arrays of a join of ``n_a`` x ``n_b`` rows, in any order.  ``aggs`` takes
+        the tuples of :meth:`merge_agg` -- ``(func, values, valid_or_None)`` with ``func`` in COUNT, SUM, MIN, MAX,
+        AVG -- over columns of ``n_b`` rows; a COUNT may give ``None`` for ``values`` (it reads validity alone, so
+        ``COUNT(b.name)`` needs no numeric column).
+
+        Returns ``(pairs, results)``: ``pairs`` the int64 pair count of every A row, ``results`` one ``(values,
+        non_null)`` per entry, both of ``n_a`` rows in A's order; ``non_null`` is the int64 number of non-NULL inputs
+        (0: the value is NULL and reads 0).  SUM / MIN / MAX of an integer column are int64, of a float column
+        float64; AVG is ``double(sum) / double(non_null)``; COUNT is ``non_null``.  A row's values are reduced in
+        ascending ``row_b`` without atomics: the result does not depend on the order of the pairs, float sums
+        included.  Ids outside their table raise ``GiqlHipError``."""
+        torch = _torch()
+        aggs = [(str(a[0]).upper(), a[1], a[2] if len(a) > 2 else None) for a in aggs]
+        n_a, n_b = int(n_a), int(n_b)
+        if len(aggs) > self.PAIR_AGG_MAX:
+            raise ValueError(f"a pair aggregate takes at most {self.PAIR_AGG_MAX} aggregates, got {len(aggs)}")
+        n = int(row_a.shape[0])
+        if int(row_b.shape[0]) != n or row_a.dim() != 1 or row_b.dim() != 1:
+            raise ValueError("row_a and row_b must have one entry per pair")
+        ok = (torch.int32, torch.int64, torch.float32, torch.float64)
+        types = {torch.int32: _lib.T_I32, torch.int64: _lib.T_I64, torch.float32: _lib.T_F32,
+                 torch.float64: _lib.T_F64}
+        for func, t, valid in aggs:
+            if func not in ("COUNT", "SUM", "MIN", "MAX", "AVG"):
+                raise ValueError(f"aggregate function {func!r}")
+            if t is None and func != "COUNT":
+                raise ValueError(f"{func} needs a values tensor (only COUNT reads validity alone)")
+            if t is not None and (t.dtype not in ok or t.dim() != 1 or not t.is_contiguous()
+                                  or int(t.shape[0]) != n_b):
+                raise ValueError("an aggregate column must be a contiguous 1-D int32/int64/float32/float64 tensor "
+                                 "with one value per row of the right table")
+            if valid is not None and (valid.dtype not in (torch.uint8, torch.bool) or valid.dim() != 1
+                                      or int(valid.shape[0]) != n_b or not valid.is_contiguous()):
+                raise ValueError("validity must be a contiguous uint8/bool tensor of one entry per right row")
+        # the kernel's aggregates: AVG asks for SUM, a SUM and an AVG over one column share it, COUNT shares by validity
+        kernel, slot = [], []
+        for func, t, valid in aggs:
+            f = "SUM" if func == "AVG" else func
+            vkey = None if valid is None else valid.data_ptr()
+            key = (f, None, vkey, None) if f == "COUNT" else (f, t.data_ptr(), vkey, t.dtype)
+            if key not in [k[0] for k in kernel]:
+                flt = f != "COUNT" and t.is_floating_point()
+                kernel.append((key, None if f == "COUNT" else t, valid,
+                               torch.empty(n_a, dtype=torch.float64 if flt else torch.int64, device=self.device),
+                               torch.empty(n_a, dtype=torch.int64, device=self.device)))
+            slot.append([k[0] for k in kernel].index(key))
+        c_aggs = (_lib.CAgg * max(len(kernel), 1))()
+        for j, (key, t, valid, out, nn) in enumerate(kernel):
+            c_aggs[j].func = _lib.AGG_FUNCS[key[0]]
+            c_aggs[j].type = _lib.T_I32 if t is None else types[t.dtype]
+            c_aggs[j].data = self._dev_ptr(t, "an aggregate column")
+            if t is not None and c_aggs[j].data is None:
+                c_aggs[j].data = 1  # (an empty right table: never dereferenced)
+            c_aggs[j].valid = self._dev_ptr(valid, "a validity column")
+            c_aggs[j].out = out.data_ptr() if n_a else 1
+            c_aggs[j].out_nn = nn.data_ptr() if n_a else None
+        pairs = torch.empty(n_a, dtype=torch.int64, device=self.device)
+        _lib.check(self._L.giql_hip_pair_agg_dev(
+            self._h, self._dev_ptr(row_a, "row_a", torch.int32), self._dev_ptr(row_b, "row_b", torch.int32), n,
+            n_a, n_b, c_aggs, len(kernel), pairs.data_ptr() if n_a else None, self._stream()))
+        res = []
+        for (func, _t, _v), j in zip(aggs, slot):
+            out, nn = kernel[j][3], kernel[j][4]
+            if func == "AVG":
+                out = torch.where(nn > 0, out.double() / nn.double(), torch.zeros(n_a, dtype=torch.float64,
+                                                                                  device=self.device))
+            res.append((out, nn))
+        return pairs, res
+
     # ------------------------------------------------------------- projection
     def take(self, cols, idx, outs=None):
         """Arrow ``take`` of fixed-width device columns by int32 row ids ``idx``

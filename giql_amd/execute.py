@@ -1282,6 +1282,203 @@ def _finish_count(plan, lt, rt, counts, n_chrom, eng, ia, return_indices, a_dev=
     return out.select([p.name for p in plan.projection])
 
 
+# ------------------------------------------------------------- grouped aggregates over a join (the map shape)
+def _aggregated_types(plan: JoinPlan, rt) -> dict:
+    """``{column: Arrow type}`` of the right-table columns a plan's aggregates read (None: no such column)."""
+    import pyarrow as pa
+
+    types = {}
+    for a in plan.aggregates:
+        if a.side != "r" or a.column in types:
+            continue
+        try:
+            col = _column(rt, a.column)
+        except (KeyError, ValueError):
+            types[a.column] = None
+            continue
+        t = getattr(col, "type", None)
+        if t is None:
+            try:
+                t = pa.from_numpy_dtype(np.asarray(col).dtype)
+            except (pa.ArrowNotImplementedError, TypeError):
+                t = pa.string()    # (an object array: not a numeric column, whatever it holds)
+        types[a.column] = t.value_type if pa.types.is_dictionary(t) else t
+    return types
+
+
+def _routes_join_aggregates(plan: JoinPlan, right_types: dict, return_indices: bool, devices) -> bool:
+    """Whether ``execute`` answers a plan through ``_execute_join_aggregates``: a plan lowered in the map shape
+    (``join_aggregates``; shape.is_map_shape) -- INNER, or LEFT with ON residuals only, grouped by left-side columns,
+    every projected column a key, 1..8 aggregates that are COUNT(*), COUNT(<right column>) of any type, or SUM / AVG /
+    MIN / MAX of a signed-integer or float32 / float64 right column (``right_types``: column -> Arrow type) -- asked
+    for as a table, on one device.  Anything else takes the path it takes without the flag."""
+    import pyarrow as pa
+
+    from .shape import MAP_AGG_MAX, map_aggregate_ok
+
+    if not plan.join_aggregates or plan.kind not in ("INNER", "LEFT") or return_indices:
+        return False
+    if devices is not None and len(devices) > 1:
+        return False
+    if plan.kind == "LEFT" and any(r.clause != "on" for r in plan.residuals):
+        return False
+    if not plan.group_by or not 1 <= len(plan.aggregates) <= MAP_AGG_MAX or plan.expressions:
+        return False
+    if any(p.side != "l" or p.column == "*" or p.name not in plan.group_by for p in plan.projection):
+        return False
+    for a in plan.aggregates:
+        if not map_aggregate_ok(a.func, a.side, a.distinct):
+            return False
+        if a.side == "*":
+            continue
+        t = right_types.get(a.column)
+        if t is None:
+            return False
+        if a.func != "COUNT" and not (pa.types.is_signed_integer(t) or pa.types.is_float32(t) or pa.types.is_float64(t)):
+            return False
+    return True
+
+
+def _check_pair_int_sum(column: str, col, n_pairs: int) -> None:
+    """SUM / AVG over the integer column ``col`` of the right table accumulate in int64 over a join's pairs: refuse
+    when ``n_pairs * max(|min|, |max|)`` could reach 2^63 instead of wrapping (as ``_check_int_sum``)."""
+    import pyarrow.compute as pc
+
+    mm = pc.min_max(col)
+    lo, hi = mm["min"].as_py(), mm["max"].as_py()
+    if lo is None:
+        return
+    if n_pairs * max(abs(lo), abs(hi)) >= 2**63:
+        raise ValueError(f"SUM / AVG over column {column!r}: {n_pairs} pairs of magnitude up to {max(abs(lo), abs(hi))} "
+                         "can overflow the int64 sum; cast the column to a float type")
+
+
+def _execute_join_aggregates(plan: JoinPlan, lt, rt, eng: HipEngine, pins: dict | None = None):
+    """A map-shape plan (``_routes_join_aggregates``): the join's unpadded pairs, reduced per left row on the device
+    (``HipEngine.pair_aggregate``: no gather per pair, nothing per pair comes to the host), then the per-row partials
+    combined per distinct left key on the host over ``n_left`` rows (``_combine_join_partials``).  The pairs come from
+    where the same join takes them without the flag: a pinned table's index (``_indexed_inner``) where one serves, else
+    ``_spatial_join`` / ``_join_with_residuals``.  Returns the finished table, or None when the join yields 2^31 pairs
+    or more (the caller takes the other path, which joins again)."""
+    import pyarrow as pa
+    from dataclasses import replace
+
+    inner = replace(plan, kind="INNER", join_aggregates=False)   # ON residuals take part in matching, as an INNER join's
+    got = None
+    if (plan.predicate == "intersects" and not plan.residuals and pins
+            and any(p is not None and p.index for p in pins.values())):
+        got = _indexed_inner(inner, lt, rt, pins, eng)   # (None: the index does not serve this pair of tables)
+    if got is not None:
+        ra, rb = got
+    else:
+        ia, ib, dictionary = encode_chroms(_column(lt, plan.left.chrom_col), _column(rt, plan.right.chrom_col))
+        n_chrom = len(dictionary)
+        a = _device_side(lt, plan.left, ia, eng)
+        b = _device_side(rt, plan.right, ib, eng)
+        if plan.residuals:
+            ra, rb = _join_with_residuals(inner, lt, rt, a, b, n_chrom, eng)
+        else:
+            ra, rb = _spatial_join(inner, a, b, n_chrom, eng)
+    n_left, n_right = _n_rows(lt), _n_rows(rt)
+    n_pairs = int(ra.shape[0])
+    if n_pairs >= 2**31:
+        return None
+    res = _Residuals(plan, lt, rt, eng)
+    asked, slot, types = [], {}, {}   # the engine's aggregates, one per distinct (function, column); AVG asks for SUM
+    for ag in plan.aggregates:
+        if ag.side == "*":
+            continue
+        func = "SUM" if ag.func == "AVG" else ag.func
+        if (func, ag.column) in slot:
+            continue
+        col = res._arrow("r", ag.column)
+        types[ag.column] = col.type
+        if func == "COUNT":
+            entry = ("COUNT", None, res._valid(col))
+        else:
+            if func == "SUM" and pa.types.is_integer(col.type):
+                _check_pair_int_sum(ag.column, col, n_pairs)
+            entry = (func,) + res._numeric("r", ag.column)
+        slot[(func, ag.column)] = len(asked)
+        asked.append(entry)
+    pairs, parts = eng.pair_aggregate(ra.contiguous(), rb.contiguous(), n_left, n_right, asked)
+    partials = {key: (parts[j][0].cpu().numpy(), parts[j][1].cpu().numpy()) for key, j in slot.items()}
+    return _finish_grouped(_combine_join_partials(plan, lt, pairs.cpu().numpy(), partials, types), plan)
+
+
+def _combine_join_partials(plan: JoinPlan, lt, pairs: np.ndarray, partials: dict, types: dict):
+    """The per-left-row partials of a map-shape plan combined per distinct left key, on the host with pyarrow over
+    ``n_left`` rows: counts, sums and non-NULL counts add, MIN / MAX combine, AVG is ``double(total sum) / double(total
+    non-NULL count)`` (NULL at 0).  ``pairs``: the pair count per left row; ``partials``: ``(function, right column) ->
+    (values, non-NULL counts)`` as ``HipEngine.pair_aggregate`` returns them, AVG under SUM; ``types``: right column ->
+    Arrow type (MIN / MAX come back in it).  INNER drops the keys whose rows have no pair; LEFT keeps them: COUNT(col)
+    = 0, COUNT(*) = 1 per unmatched row (the padded row SQL counts), everything else NULL."""
+    import pyarrow as pa
+    import pyarrow.compute as pc
+
+    keys = [p for p in plan.projection if p.side == "l"]
+    cols = {p.name: _column(lt, p.column) for p in keys}
+    cols = {k: (v if isinstance(v, (pa.Array, pa.ChunkedArray)) else pa.array(np.asarray(v))) for k, v in cols.items()}
+    specs, finish = [], []      # pyarrow aggregations over the partial columns; how each output column is read
+    for i, ag in enumerate(plan.aggregates):
+        c = f"__giql_p{i}"
+        if ag.side == "*":
+            cols[c] = pa.array(np.maximum(pairs, 1) if plan.kind == "LEFT" else pairs, type=pa.int64())
+            specs.append((c, "sum"))
+            finish.append((ag, lambda t, c=c: t.column(c + "_sum")))
+            continue
+        vals, nn = partials[("SUM" if ag.func == "AVG" else ag.func, ag.column)]
+        if ag.func == "COUNT":
+            cols[c] = pa.array(nn, type=pa.int64())
+            specs.append((c, "sum"))
+            finish.append((ag, lambda t, c=c: t.column(c + "_sum")))
+            continue
+        null = nn == 0
+        t_col = types[ag.column]
+        if ag.func in ("SUM", "AVG"):
+            cols[c] = pa.array(vals, mask=null)
+            specs.append((c, "sum"))
+            if ag.func == "SUM":
+                finish.append((ag, lambda t, c=c: t.column(c + "_sum")))
+            else:
+                cols[c + "n"] = pa.array(nn, type=pa.int64())
+                specs.append((c + "n", "sum"))
+                # double(sum) / double(count), as the engine's AVG: an int64 sum past 2^53 rounds, it is no error
+                finish.append((ag, lambda t, c=c: pc.divide(pc.cast(t.column(c + "_sum"), pa.float64(), safe=False),
+                                                           pc.cast(t.column(c + "n_sum"), pa.float64()))))
+            continue
+        fn = ag.func.lower()
+        if vals.dtype.kind != "f":
+            cols[c] = pa.array(vals, mask=null)
+            specs.append((c, fn))
+            finish.append((ag, lambda t, c=c, fn=fn, ty=t_col: pc.cast(t.column(f"{c}_{fn}"), ty)))
+            continue
+        # a float MIN / MAX keeps the device's NaN order (NaN above every number) across the rows of a key: the
+        # numbers combine by min / max, the NaNs by a flag -- MAX is NaN where any row's is, MIN only where no row
+        # holds a number
+        nan = np.isnan(vals) & ~null
+        cols[c] = pa.array(vals, mask=null | nan)
+        cols[c + "f"] = pa.array(nan.astype(np.int8))
+        specs += [(c, fn), (c + "f", "max")]
+
+        def read(t, c=c, fn=fn, ty=t_col):
+            num, flag = t.column(f"{c}_{fn}"), pc.equal(t.column(c + "f_max"), 1)
+            use_nan = flag if fn == "max" else pc.and_(flag, pc.is_null(num))
+            return pc.cast(pc.if_else(use_nan, pa.scalar(float("nan"), pa.float64()), num), ty)
+        finish.append((ag, read))
+    tbl = pa.table(cols)
+    if plan.kind == "INNER":
+        tbl = tbl.filter(pa.array(pairs > 0))
+    names = [p.name for p in keys]
+    grouped = tbl.group_by(names, use_threads=False).aggregate(specs)   # use_threads=False: stable group order
+    out = {n: grouped.column(n) for n in names}
+    for ag, read in finish:
+        out[ag.name] = read(grouped)
+    order = list(plan.output) if plan.output else list(out)
+    keep = [n for n in order if n in out] + [n for n in out if n not in order]
+    return pa.Table.from_arrays([out[n] for n in keep], names=keep)
+
+
 _PINNED_MIN_BYTES = 64 << 20
 # plan kinds execute() answers from a pinned right table's index without sorting either side, and the index forms it
 # does so for.  Both forms are on because both measured faster than the ordinary operators for all three kinds
@@ -1906,9 +2103,10 @@ def _execute_sharded(plan: JoinPlan, lt, rt, ia, ib, n_chrom, devices, return_in
 def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, return_indices=False,
             device_projection: bool = True, devices=None, outer_joins: bool = False, row_predicates: bool = False,
             select_expressions: bool = False, merge_aggregates: bool = False, range_sets: bool = False,
-            string_aggregates: bool = False):
+            string_aggregates: bool = False, join_aggregates: bool = False):
     """Run *plan* (a :class:`JoinPlan`, its string form, or a GIQL query string; ``outer_joins``,
-    ``row_predicates``, ``select_expressions``, ``merge_aggregates``, ``string_aggregates`` and ``range_sets`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
+    ``row_predicates``, ``select_expressions``, ``merge_aggregates``, ``string_aggregates``, ``range_sets`` and
+    ``join_aggregates`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
     (``{name: pyarrow.Table | dict of arrays}``).
 
     Returns a ``pyarrow.Table`` with the plan's projected columns (bag semantics,
@@ -1927,11 +2125,16 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
     entry = that device; the single-table operators (CLUSTER / MERGE / literal-range FILTER) run on the
     first one.
     """
+    relower = None   # a query string lowered with ``join_aggregates``: how to lower it again without the flag
     if isinstance(plan, str):
-        plan = JoinPlan.from_string(plan) if is_plan_string(plan) else build_plan(
-            plan, giql_tables, outer_joins=outer_joins, row_predicates=row_predicates,
-            select_expressions=select_expressions, merge_aggregates=merge_aggregates, range_sets=range_sets,
-            string_aggregates=string_aggregates)
+        if is_plan_string(plan):
+            plan = JoinPlan.from_string(plan)
+        else:
+            query, opts = plan, dict(outer_joins=outer_joins, row_predicates=row_predicates,
+                                     select_expressions=select_expressions, merge_aggregates=merge_aggregates,
+                                     range_sets=range_sets, string_aggregates=string_aggregates)
+            plan = build_plan(query, giql_tables, join_aggregates=join_aggregates, **opts)
+            relower = lambda: build_plan(query, giql_tables, **opts)  # noqa: E731
     if not isinstance(plan, JoinPlan):
         raise ValueError("plan must be a JoinPlan, a plan string or a GIQL query")
     devices = [int(d) for d in devices] if devices is not None else None
@@ -1953,6 +2156,17 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
             raise ValueError(f"table {side.table!r} was not provided")
     lt, rt = tables[plan.left.table], tables[plan.right.table]
     pins = {"l": pinned.get(plan.left.table), "r": pinned.get(plan.right.table)}
+    if plan.join_aggregates:
+        # the map shape: the join's pairs stay on the device and are aggregated per left row there
+        got = None
+        if _routes_join_aggregates(plan, _aggregated_types(plan, rt), return_indices, devices):
+            got = _execute_join_aggregates(plan, lt, rt, eng, pins)
+        if got is not None:
+            return got
+        # outside the shape (a column type, return_indices, several devices) or 2^31 pairs and more: the query runs
+        # -- or declines -- exactly as it does without the flag
+        from dataclasses import replace
+        plan = relower() if relower is not None else replace(plan, join_aggregates=False)
     if plan.expressions and devices is not None and len(devices) > 1:
         raise ValueError(f"a computed column is evaluated on one device; devices={devices!r} names {len(devices)}")
     if plan.kind == "LEFT" and devices is not None and len(devices) > 1:
@@ -2048,6 +2262,14 @@ def _finish_outer(out, plan: JoinPlan):
         if plan.output:
             out = out.select([n for n in plan.output if n in out.column_names] +
                              [n for n in out.column_names if n not in plan.output])
+    return _finish_grouped(out, plan)
+
+
+def _finish_grouped(out, plan: JoinPlan):
+    """The tail of :func:`_finish_outer` on a table that is aggregated already (or needs no aggregation): HAVING,
+    DISTINCT, ORDER BY, OFFSET / LIMIT, and the hidden ``__giql_*`` columns dropped."""
+    import pyarrow as pa
+
     if plan.having:
         import pyarrow.compute as pc
 

@@ -184,6 +184,11 @@ class JoinPlan:
     # negations are folded into the residuals when the plan is lowered).  Only plans lowered with the ``range_sets``
     # opt-in carry any; plan strings written before the field existed load with none
     range_sets: tuple[RangeSet, ...] = field(default_factory=tuple)
+    # INNER / LEFT only: a grouped plan in the map shape (shape.is_map_shape; bedtools ``map``) lowered with the
+    # ``join_aggregates`` opt-in -- grouped by left-side columns, its aggregates over the right side computed per left
+    # row on the device (HipEngine.pair_aggregate) and combined per key.  A LEFT plan so marked needs no padded pair.
+    # The string form carries the key only when it is set: every other plan serialises as it did before the field
+    join_aggregates: bool = False
 
     def __post_init__(self) -> None:
         if self.kind not in KINDS:
@@ -200,6 +205,8 @@ class JoinPlan:
             raise ValueError(f"computed columns need an INNER or LEFT plan, not {self.kind}")
         if self.range_sets and self.kind != "FILTER":
             raise ValueError(f"literal range sets need a FILTER plan, not {self.kind}")
+        if self.join_aggregates and not (self.kind in PAIR_KINDS and self.aggregates and self.group_by):
+            raise ValueError("join_aggregates marks a grouped INNER / LEFT plan with aggregates only")
         for rs in self.range_sets:
             if rs.op not in RANGE_OPS or rs.quantifier not in RANGE_QUANTIFIERS or not rs.ranges:
                 raise ValueError(f"bad range set {rs.op!r} {rs.quantifier!r} over {len(rs.ranges)} ranges")
@@ -225,6 +232,8 @@ class JoinPlan:
         d["expressions"] = [asdict(e) for e in self.expressions]
         d["range_sets"] = [{"op": r.op, "quantifier": r.quantifier, "negated": r.negated,
                             "ranges": [list(t) for t in r.ranges]} for r in self.range_sets]
+        if not self.join_aggregates:
+            del d["join_aggregates"]
         return d
 
     def to_string(self) -> str:
@@ -259,7 +268,8 @@ class JoinPlan:
             expressions=tuple(Operand(**e) for e in d.get("expressions", ())),
             range_sets=tuple(RangeSet(r["op"], r["quantifier"], bool(r["negated"]),
                                       tuple((str(c), int(lo), int(hi)) for c, lo, hi in r["ranges"]))
-                             for r in d.get("range_sets", ())))
+                             for r in d.get("range_sets", ())),
+            join_aggregates=bool(d.get("join_aggregates", False)))
 
 
 def is_plan_string(text) -> bool:

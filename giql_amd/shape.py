@@ -278,6 +278,9 @@ class JoinShape:
     # opt-in: arithmetic / searched-CASE items of the SELECT list (SelItem.expr) lower to computed columns of an INNER
     # or LEFT plan; a front end that does not parse them never sets SelItem.expr
     select_expressions: bool = False
+    # opt-in: a grouped aggregate over a join in the map shape (is_map_shape) lowers to an INNER / LEFT plan marked
+    # ``join_aggregates``, whose aggregates execute() computes per left row on the device (HipEngine.pair_aggregate)
+    join_aggregates: bool = False
 
 
 # ------------------------------------------------------------------ helpers
@@ -793,6 +796,61 @@ def _resolve_order(shape: JoinShape, proj, aggs, left: PlanSide, right: PlanSide
     return tuple(hidden), tuple(order)
 
 
+#: aggregates of one map-shape plan, hidden HAVING aggregates included (``GIQL_PAIR_AGG_MAX``)
+MAP_AGG_MAX = 8
+
+
+def _is_qualified(ref, alias: str) -> bool:
+    return ref is not None and not ref.star and ref.table is not None and norm(ref.table, ref.table_quoted) == alias
+
+
+def map_aggregate_ok(func: str, side: str, distinct: bool) -> bool:
+    """An aggregate the map shape computes per left row: ``COUNT(*)``, ``COUNT(<right column>)``, or SUM / AVG / MIN /
+    MAX of a right-side column, without DISTINCT (the column's type is execute()'s to check: the plan has no schema)."""
+    if distinct:
+        return False
+    return (func == "COUNT" and side in ("*", "r")) or (func in ("SUM", "AVG", "MIN", "MAX") and side == "r")
+
+
+def is_map_shape(shape: JoinShape, left: PlanSide, right: PlanSide) -> bool:
+    """The routing decision of the ``join_aggregates`` opt-in, on the parsed shape alone (bedtools ``map``): an INNER
+    join, or a LEFT join with its spatial predicate in ON and no WHERE, grouped by qualified left-side columns only,
+    every projected plain column a group key, and 1..8 aliased aggregates over the right side (map_aggregate_ok).  A
+    lone ``COUNT(b.col)`` under a bare LEFT ... ON is the count_overlaps shape and stays with it."""
+    if not shape.join_aggregates or shape.kind not in ("INNER", "LEFT") or left.alias == right.alias:
+        return False
+    cmp_terms = [t for t in list(shape.on_terms) + list(shape.where_terms) if t[0] not in JOIN_TERMS]
+    if shape.kind == "LEFT" and (shape.where_terms or not any(t[0] in JOIN_TERMS for t in shape.on_terms)):
+        return False
+    if not shape.group_by or not all(_is_qualified(g, left.alias) for g in shape.group_by):
+        return False
+    keys = {g.column for g in shape.group_by}
+    aggs = []
+    for it in shape.items:
+        if it.distance is not None or it.expr is not None:
+            return False
+        if it.func is None:
+            if not _is_qualified(it.ref, left.alias) or it.ref.count or it.ref.column not in keys:
+                return False
+            continue
+        if it.func not in AGG_FUNCS or not it.alias:
+            return False
+        if it.ref is None:
+            side = "*"
+        elif _is_qualified(it.ref, right.alias):
+            side = "r"
+        else:
+            return False
+        if not map_aggregate_ok(it.func, side, it.distinct):
+            return False
+        aggs.append((it.func, side))
+    if not 1 <= len(aggs) <= MAP_AGG_MAX:
+        return False
+    if shape.kind == "LEFT" and aggs == [("COUNT", "r")] and not cmp_terms:
+        return False   # count_overlaps
+    return True
+
+
 # ------------------------------------------------------------------- the gate
 def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
     """:class:`JoinShape` -> :class:`JoinPlan`, or :class:`HipDeclined` / ``ValueError``."""
@@ -804,6 +862,9 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
         left = table_side(shape.from_ref, tables)
         right = table_side(shape.join_ref, tables)
     has_count_item = any((it.func == "COUNT" and it.ref is not None and not it.distinct) for it in items)
+    # the ``join_aggregates`` opt-in: a LEFT join in the map shape is neither count_overlaps nor in need of
+    # ``outer_joins`` -- its aggregates are computed per left row, no padded pair is ever produced
+    map_shape = is_map_shape(shape, left, right)
     dist_items = [it for it in items if it.distance is not None]
     if dist_items and kind != "INNER":
         # the value is defined per PAIR: SEMI / ANTI keep left rows, count_overlaps counts them
@@ -817,9 +878,9 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
         # count_overlaps: LEFT [OUTER] JOIN ... COUNT(b.col) ... GROUP BY left keys
         # (_match_count_overlaps, intersects_duckdb.py:432-548); every other outer join declines (:661-662)
         # unless the caller opted in (JoinShape.outer_joins): then it is a LEFT plan
-        if has_count_item:
+        if has_count_item and not map_shape:
             kind = "COUNT"
-        elif not shape.outer_joins:
+        elif not shape.outer_joins and not map_shape:
             raise decline("LEFT outer join")
     if kind == "COUNT" and not shape.on_seen:
         raise decline("count_overlaps without an ON clause")
@@ -917,6 +978,11 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
             # HAVING over the whole result as ONE group, nothing aggregated in the SELECT list: the plain
             # columns it projects are neither grouped nor aggregated
             raise ValueError("a projected column must appear in GROUP BY or inside an aggregate")
+        if map_shape and not (len(aggs) <= MAP_AGG_MAX and all(map_aggregate_ok(a.func, a.side, a.distinct) for a in aggs)):
+            # an aggregate that only HAVING names falls outside the shape: the query lowers as it does without the flag
+            from dataclasses import replace
+
+            return lower_join_shape(replace(shape, join_aggregates=False), tables)
     else:
         proj, aggs, groups = resolve_projection(items, left, right, left_only, tables=tables, strands_out=strands,
                                                 exprs_out=exprs, stars=stars), (), ()
@@ -934,7 +1000,7 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
                     residuals=residuals, strand_col=strand_col,
                     aggregates=aggs, group_by=groups, having=having, order_by=order,
                     limit=shape.limit, offset=shape.offset, output=output, predicate=predicate,
-                    row_predicates=row_pred, expressions=tuple(exprs))
+                    row_predicates=row_pred, expressions=tuple(exprs), join_aggregates=map_shape)
 
 
 def _col_refs(x):

@@ -1412,7 +1412,7 @@ def _lower_disjoin(p: _Parser, tbls: Tables) -> JoinPlan:
 
 def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predicates: bool = False,
                select_expressions: bool = False, merge_aggregates: bool = False, range_sets: bool = False,
-               string_aggregates: bool = False) -> JoinPlan:
+               string_aggregates: bool = False, join_aggregates: bool = False) -> JoinPlan:
     """Parse *giql* and lower the INTERSECTS / NEAREST join (or a CLUSTER / MERGE
     query) to a :class:`JoinPlan`.
 
@@ -1431,7 +1431,13 @@ def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predica
     ``range_sets=True`` opts in to the quantified literal ranges of a single-table filter -- ``interval INTERSECTS |
     CONTAINS | WITHIN ANY(...)`` / ``SOME(...)`` / ``ALL(...)``, a ``NOT`` in front of such a predicate or of a single
     literal, several of them joined by AND -- with every literal format of the reference's parser and over a table of
-    any coordinate encoding (docs/dialect/quantifiers.rst); inside a join such a predicate declines as before."""
+    any coordinate encoding (docs/dialect/quantifiers.rst); inside a join such a predicate declines as before.
+    ``join_aggregates=True`` opts in to the map shape (bedtools ``map -c 5 -o mean,count,max``): an INNER join, or a
+    LEFT join with its spatial predicate in ON and no WHERE, grouped by left-side columns, with 1..8 aliased aggregates
+    -- ``COUNT(*)``, ``COUNT(b.col)``, ``SUM`` / ``AVG`` / ``MIN`` / ``MAX`` of a right-side numeric column -- lowers to
+    an INNER / LEFT plan marked ``join_aggregates`` whose aggregates are computed per left row on the device.  The LEFT
+    form needs no ``outer_joins``; a ``COUNT`` beside other aggregates, which declines without the flag, lowers too.  A
+    query outside the shape lowers (or declines) exactly as it does without the flag."""
     probe = _Parser(giql, range_sets=bool(range_sets))
     tbls = tables if isinstance(tables, Tables) else build_tables(tables)
     for routed, lower, what in ((_disjoin_from(probe) is not None, _lower_disjoin, "DISJOIN"),
@@ -1451,13 +1457,13 @@ def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predica
                 raise _decline(f"expression in the SELECT list of {what}") from None
             raise
     plan = _lower(giql, tables, want_sql=False, outer_joins=outer_joins, row_predicates=row_predicates,
-                  select_expressions=select_expressions)
+                  select_expressions=select_expressions, join_aggregates=join_aggregates)
     assert isinstance(plan, JoinPlan)
     return plan
 
 
 def _lower(giql: str, tables, want_sql: bool, outer_joins: bool = False, row_predicates: bool = False,
-           select_expressions: bool = False):
+           select_expressions: bool = False, join_aggregates: bool = False):
     tbls = tables if isinstance(tables, Tables) else build_tables(tables)
     p = _Parser(giql)
     if p.at_kw("WITH"):
@@ -1562,7 +1568,7 @@ def _lower(giql: str, tables, want_sql: bool, outer_joins: bool = False, row_pre
 
     shape = JoinShape(items=items, from_ref=from_ref, join_ref=join_ref, kind=kind, on_seen=on_seen, using=using,
                       distinct=distinct, outer_joins=bool(outer_joins), row_predicates=bool(row_predicates),
-                      select_expressions=bool(select_expressions))
+                      select_expressions=bool(select_expressions), join_aggregates=bool(join_aggregates))
     if on_seen:
         if p.peek().kind not in ("id", "num", "str") and not p.at_punct("-") and not p.at_punct("(") \
                 and not p.at_kw("NOT"):
@@ -1648,7 +1654,8 @@ def _render(toks: list[Tok]) -> str:
 
 def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins: bool = False,
               row_predicates: bool = False, select_expressions: bool = False,
-              merge_aggregates: bool = False, range_sets: bool = False, string_aggregates: bool = False) -> str:
+              merge_aggregates: bool = False, range_sets: bool = False, string_aggregates: bool = False,
+              join_aggregates: bool = False) -> str:
     """Mirror of ``giql.transpile`` for this backend's path.
 
     ``dialect="hip"``: returns the plan string of the INTERSECTS / NEAREST join
@@ -1656,14 +1663,16 @@ def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins
     and ``row_predicates=True`` the per-row joins over CONTAINS / WITHIN / DISTANCE, ``select_expressions=True``
     computed columns such as ``overlap_bp`` in the SELECT list, ``merge_aggregates=True`` SUM / AVG / MIN / MAX /
     COUNT(col) beside MERGE, ``string_aggregates=True`` STRING_AGG(col, 'sep') beside MERGE, ``range_sets=True`` ANY / SOME / ALL over literal ranges and NOT over a literal predicate
-    in a single-table filter (:func:`build_plan`).  ``dialect=None``: returns SQL for the
+    in a single-table filter, ``join_aggregates=True`` grouped aggregates over a join in the map shape
+    (:func:`build_plan`).  ``dialect=None``: returns SQL for the
     literal-range predicate (plumbing, BASELINE config 1).  Other dialects belong to
     the reference package.
     """
     if dialect == "hip":
         return build_plan(giql, tables, outer_joins=outer_joins, row_predicates=row_predicates,
                           select_expressions=select_expressions, merge_aggregates=merge_aggregates,
-                          range_sets=range_sets, string_aggregates=string_aggregates).to_string()
+                          range_sets=range_sets, string_aggregates=string_aggregates,
+                          join_aggregates=join_aggregates).to_string()
     if dialect is None:
         return _lower(giql, tables, want_sql=True)
     raise ValueError(

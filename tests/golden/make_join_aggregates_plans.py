@@ -1,0 +1,35 @@
+#!/usr/bin/env python3
+"""Record tests/golden/join_aggregates_plans.json: what every query of tests/_join_agg_queries.py lowers to WITHOUT
+the ``join_aggregates`` opt-in -- its plan string, or the class and message of its error -- under each set of the
+other opt-ins the list names.
+
+Run it against the package of the commit BEFORE the opt-in existed (the fixture names that commit), never against the
+code under test:
+
+    git archive <commit> giql_amd | tar -x -C <dir>
+    PYTHONPATH=<dir> python tests/golden/make_join_aggregates_plans.py <commit>
+"""
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, ".."))
+
+import _join_agg_queries as Q  # noqa: E402
+from giql_amd.transpile import build_plan  # noqa: E402  (the package on PYTHONPATH)
+
+
+def main() -> None:
+    commit = sys.argv[1]
+    assert len(commit) == 40, "name the full commit the package was taken from"
+    cases = {}
+    for name, query in {**Q.MAP_SHAPE, **Q.OUTSIDE}.items():
+        cases[name] = {opt: Q.outcome(build_plan, query, **kw) for opt, kw in Q.OPTIONS.items()}
+    with open(os.path.join(HERE, "join_aggregates_plans.json"), "w") as f:
+        json.dump({"recorded_at_commit": commit, "cases": cases}, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
