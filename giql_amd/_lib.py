@@ -65,6 +65,12 @@ STRING_AGG_SYMBOLS = ["giql_hip_merge_str_dev", "giql_hip_concat_utf8_fill_dev"]
 #: every symbol include/giql_hip_pair_agg.h declares (aggregates over a join's pairs, per left row)
 PAIR_AGG_SYMBOLS = ["giql_hip_pair_agg_dev"]
 
+#: every symbol include/giql_hip_coverage.h declares (coverage depth per DISJOIN segment)
+COVERAGE_SYMBOLS = ["giql_hip_coverage_dev"]
+
+#: ``GIQL_COV_RUNS``: merge abutting segments of equal depth
+COV_RUNS = 1
+
 
 class GiqlHipUnavailable(RuntimeError):
     """libgiql_hip.so could not be loaded (not built, or no ROCm runtime)."""
@@ -301,6 +307,7 @@ def load() -> ctypes.CDLL:
                                          vp, vp, vp, vp, vp, i64, P(i64), vp]
     L.giql_hip_concat_utf8_fill_dev.argtypes = [vp, vp, vp, i64, vp, vp, i64, ctypes.c_char_p, i32, vp, vp]
     L.giql_hip_pair_agg_dev.argtypes = [vp, vp, vp, i64, i64, i64, P(CAgg), i32, vp, vp]
+    L.giql_hip_coverage_dev.argtypes = [vp, P(CSide), i32, ctypes.c_uint32, vp, vp, vp, vp, i64, P(i64), vp]
     _lib = L
     return L
 

@@ -22,6 +22,7 @@
 #include "../../include/giql_hip_range_sets.h"
 #include "../../include/giql_hip_string_agg.h"
 #include "../../include/giql_hip_pair_agg.h"
+#include "../../include/giql_hip_coverage.h"
 #include "aux_kernels.hip.h"
 #include "take_kernels.hip.h"
 #include "select_kernels.hip.h"
@@ -33,6 +34,7 @@
 #include "pair_agg_kernels.hip.h"
 #include "range_set_kernels.hip.h"
 #include "disjoin_kernels.hip.h"
+#include "coverage_kernels.hip.h"
 #include "contain_kernels.hip.h"
 #include "distance_kernels.hip.h"
 #include "row_pred_kernels.hip.h"
@@ -4248,6 +4250,123 @@ int giql_hip_disjoin_fill_dev(giql_hip_ctx* ctx, int32_t* parent_out, int32_t* s
     GIQL_TRY(post_launch("disjoin fill"));
   }
   return GIQL_OK;
+}
+
+// ------------------------------------------------------- coverage segments
+// include/giql_hip_coverage.h.  DISJOIN's front in self mode (spans -> 2n event keys -> ONE (key, id) sort -> the two
+// flag scans), then coverage_kernels.hip.h: breakpoints with their whole depth -> keep flags -> scan -> one row per kept
+// breakpoint.  No per-row count, no offsets, no output-major fill: the output has at most 2n - 1 rows.
+static int giql_hip_coverage_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom, uint32_t flags,
+                                      int32_t* chrom_out, int32_t* start_out, int32_t* end_out, int64_t* depth_out,
+                                      int64_t capacity, int64_t* n_out, void* stream) {
+  if (!ctx || !n_out) return set_err(GIQL_ERR_INVALID, "ctx/n_out is NULL");
+  GIQL_TRY(check_side(s, "side"));
+  if (n_chrom < 0) return set_err(GIQL_ERR_INVALID, "n_chrom < 0");
+  if (flags & ~GIQL_COV_RUNS) return set_err(GIQL_ERR_INVALID, "coverage: unknown flags 0x%x", flags);
+  if ((u64)s->n * 2 > OS_MAX_ROWS) return set_err(GIQL_ERR_INVALID, "coverage of a table larger than 2^29 rows");
+  GIQL_TRY(begin_call(ctx, s->n));
+  hipStream_t st = (hipStream_t)stream;
+  *n_out = 0;
+  if (s->n == 0) return GIQL_OK;
+  if (n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
+  const bool runs = (flags & GIQL_COV_RUNS) != 0;
+  const size_t n = (size_t)s->n, nev = 2 * n;
+  LinBufs lb;
+  SortBufs sb;
+  OsScratch os;
+  u32 *last = nullptr, *is_start = nullptr, *last_excl = nullptr, *start_excl = nullptr, *keep = nullptr, *slot = nullptr;
+  u64 *bsums = nullptr, *n_bp = nullptr, *scratch_total = nullptr, *total = nullptr;
+  auto carve = [&](char* base) {
+    Carver c{base};
+    common_sizes(c, n_chrom, lb);
+    for (int k = 0; k < 2; k++) {
+      sb.key[k] = c.take<u32>(nev);
+      sb.end[k] = nullptr;
+      sb.rid[k] = c.take<u32>(nev);
+    }
+    os_scratch_sizes(c, nev, os);
+    last = c.take<u32>(nev);
+    is_start = c.take<u32>(nev);
+    last_excl = c.take<u32>(nev + 1);
+    start_excl = c.take<u32>(nev + 1);
+    keep = c.take<u32>(nev);
+    slot = c.take<u32>(nev + 1);
+    bsums = c.take<u64>(cdiv((u64)nev + 1, SCAN_TILE) + 1);
+    n_bp = c.take<u64>(1);
+    scratch_total = c.take<u64>(1);
+    total = c.take<u64>(1);
+    return c.off;
+  };
+  GIQL_TRY(claim_arena(ctx, st, carve));
+  giql_side none;
+  memset(&none, 0, sizeof(none));
+  GIQL_TRY(run_spans(ctx, st, *s, none, n_chrom, lb));
+  {
+    HIP_TRY(hipMemsetAsync(os.hist, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
+    Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
+    ctx->stats.phase_bytes[GIQL_PH_LINEARIZE] += (int64_t)20 * n;  // three columns read, two keys written
+    u32 grid = cdiv((u64)n, LIN_NT);
+    if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_dj_events, dim3(grid), dim3(LIN_NT), 0, st, view_of(*s), n_chrom, lb.chrom_base, sb.key[0],
+                       os.hist, ctx->d_meta, DJ_BAD_TARGET);
+    hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, os.hist, (u32)LIN_HIST_REPLICAS, os.gbase);
+    GIQL_TRY(post_launch("coverage events"));
+  }
+  GIQL_TRY(run_sort_onesweep(ctx, st, sb, sort_by_start(os, nev)));
+  {
+    Phase ph(ctx, st, GIQL_PH_COUNT, 1);
+    ctx->stats.phase_bytes[GIQL_PH_COUNT] += (int64_t)16 * nev;  // keys + ids read, two flags written
+    hipLaunchKernelGGL(k_dj_flags, dim3(cdiv(nev, 256)), dim3(256), 0, st, sb.key[0], sb.rid[0], (u32)nev, (u32)n, last,
+                       is_start);
+    GIQL_TRY(post_launch("coverage flags"));
+  }
+  GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, last, (u64)nev, last_excl, bsums, n_bp));
+  GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, is_start, (u64)nev, start_excl, bsums, scratch_total));
+  // The sort is done: its second buffers are free, and hold the breakpoints and their depths (at most nev of each).
+  u32 *bp = sb.key[1], *depth = sb.rid[1];
+  HIP_TRY(hipMemsetAsync(keep, 0, nev * sizeof(u32), st));  // (the scan runs over nev flags, the breakpoints are fewer)
+  {
+    Phase ph(ctx, st, GIQL_PH_AUX, runs ? 2 : 1);
+    ctx->stats.phase_bytes[GIQL_PH_AUX] += (int64_t)(runs ? 40 : 32) * nev;  // (at most: every key distinct)
+    hipLaunchKernelGGL(k_cov_depth, dim3(cdiv(nev, 256)), dim3(256), 0, st, sb.key[0], last, last_excl, is_start,
+                       start_excl, (u32)nev, bp, depth, runs ? (u32*)nullptr : keep);
+    if (runs) hipLaunchKernelGGL(k_cov_run_heads, dim3(cdiv(nev, 256)), dim3(256), 0, st, depth, n_bp, keep);
+    GIQL_TRY(post_launch("coverage breakpoints"));
+  }
+  GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, keep, (u64)nev, slot, bsums, total, &ctx->d_meta->n_out));
+  HIP_TRY(hipMemcpyAsync(ctx->h_meta, ctx->d_meta, sizeof(DevMeta), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (ctx->h_meta->aux0 & DJ_BAD_TARGET)
+    return set_err(GIQL_ERR_INVALID, "DISJOIN needs start <= end on every row: the target has a row with start > end");
+  GIQL_TRY(read_meta(ctx, st));
+  const u64 h_total = ctx->h_meta->n_out;
+  *n_out = (int64_t)h_total;
+  if (capacity < 0 || (u64)capacity < h_total) {
+    collect_spans(ctx);
+    return set_err(GIQL_ERR_CAPACITY, "%llu coverage rows, capacity %lld", (unsigned long long)h_total, (long long)capacity);
+  }
+  if (h_total) {
+    if (!chrom_out || !start_out || !end_out) return set_err(GIQL_ERR_INVALID, "output buffer is NULL");
+    Phase ph(ctx, st, GIQL_PH_FILL, 1);
+    ctx->stats.phase_bytes[GIQL_PH_FILL] += (int64_t)16 * nev + (int64_t)(depth_out ? 20 : 12) * (int64_t)h_total;
+    hipLaunchKernelGGL(k_cov_fill, dim3(cdiv(nev, 256)), dim3(256), 0, st, bp, depth, keep, slot, n_bp, lb.chrom_first,
+                       lb.chrom_base, n_chrom, (int)s->start_off, (int)s->end_off, runs ? 1 : 0, (u32)h_total, chrom_out,
+                       start_out, end_out, (i64*)depth_out);
+    GIQL_TRY(post_launch("coverage rows"));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  collect_spans(ctx);
+  ctx->stats.n_out = (int64_t)h_total;
+  ctx->stats.span = (int64_t)ctx->h_meta->total_span;
+  return GIQL_OK;
+}
+
+int giql_hip_coverage_dev(giql_hip_ctx* ctx, const giql_side* side, int32_t n_chrom, uint32_t flags, int32_t* chrom_out,
+                          int32_t* start_out, int32_t* end_out, int64_t* depth_out, int64_t capacity, int64_t* n_out,
+                          void* stream) {
+  return with_order_fallback(ctx, [&] {
+    return giql_hip_coverage_dev_impl(ctx, side, n_chrom, flags, chrom_out, start_out, end_out, depth_out, capacity, n_out, stream);
+  });
 }
 
 // ------------------------------------------------------- CONTAINS / WITHIN

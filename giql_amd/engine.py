@@ -760,6 +760,47 @@ class HipEngine:
                                                          outs[2].data_ptr(), rows, self._stream()))
         return tuple(outs)
 
+    # ------------------------------------------------------ coverage segments
+    def coverage(self, side: DeviceSide, n_chrom: int, runs: bool = False, with_depth: bool = True):
+        """Coverage profile of one table: ``SELECT disjoin_chrom, disjoin_start, disjoin_end, COUNT(*) FROM
+        DISJOIN(side) GROUP BY`` the three (``bedtools genomecov -bg``, Bioconductor ``disjoin()``), computed from the
+        breakpoints without DISJOIN's per-piece rows.
+
+        Returns ``(chrom, start, end, depth)``: int32 / int32 / int32 / int64 device tensors ordered by (chrom,
+        start), start and end in the side's declared encoding; ``depth`` is ``None`` with ``with_depth=False``.
+        ``runs=True``: maximal runs of abutting segments of equal depth are one row each (``MERGE(interval,
+        predicate := depth = PREV(depth))`` over the segments).  ``start > end`` on a row is a ``ValueError``."""
+        self._check_sides(side, side)
+
+        torch = _torch()
+
+        def once(sub, _b, rows):
+            c, st, en, d = self._coverage_once(sub, n_chrom, runs, with_depth)
+            if d is None and rows is not None:  # per group: the combine orders MERGE's four columns
+                d = torch.zeros(c.shape[0], dtype=torch.int64, device=self.device)
+            return c, st, en, d
+
+        out = self._wide(once, lambda parts: wide.merge(parts, self.device), side, None, n_chrom)
+        return out if with_depth else out[:3] + (None,)
+
+    def _coverage_once(self, s: DeviceSide, n_chrom: int, runs: bool, with_depth: bool):
+        torch = _torch()
+        cap = 2 * s.n
+        c, st, en = (torch.empty(cap, dtype=torch.int32, device=self.device) for _ in range(3))
+        d = torch.empty(cap if with_depth else 0, dtype=torch.int64, device=self.device)
+        m = ctypes.c_int64(0)
+        try:
+            _lib.check(self._L.giql_hip_coverage_dev(
+                self._h, s.c_struct(), int(n_chrom), _lib.COV_RUNS if runs else 0,
+                c.data_ptr() if cap else None, st.data_ptr() if cap else None, en.data_ptr() if cap else None,
+                d.data_ptr() if cap and with_depth else None, cap, ctypes.byref(m), self._stream()))
+        except _lib.GiqlHipError as exc:
+            if exc.code == _lib.GIQL_ERR_INVALID and "start > end" in str(exc):
+                raise ValueError(str(exc)) from exc
+            raise
+        k = int(m.value)
+        return c[:k], st[:k], en[:k], (d[:k] if with_depth else None)
+
     # ------------------------------------------------------ CONTAINS / WITHIN
     def contain_plan(self, outer: DeviceSide, inner: DeviceSide, n_chrom: int) -> int:
         self._check_sides(outer, inner)

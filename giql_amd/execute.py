@@ -1225,6 +1225,41 @@ def _execute_disjoin(plan: JoinPlan, tables, eng: HipEngine, return_indices: boo
     return _finish_outer(pa.Table.from_arrays(arrays, names=names), plan)
 
 
+def _execute_disjoin_segments(plan: JoinPlan, tables, eng: HipEngine, return_indices: bool):
+    """A self-mode DISJOIN plan answered from the target's coverage segments (``plan.segments``; lowered with
+    ``disjoin_aggregates``): ``HipEngine.coverage`` on the one device side, then ``disjoin_chrom`` = the dictionary
+    taken at the segments' chromosome ids, ``disjoin_start`` / ``disjoin_end`` int32 in the target's declared
+    encoding and every ``COUNT(*)`` as int64 under its alias.  ``"runs"`` merges abutting segments of equal depth;
+    ``"distinct"`` needs no depth.  ``return_indices=True``: the four numpy arrays (chromosome ids of the sorted
+    dictionary, start, end, depth -- ``None`` for ``"distinct"``).  Runs on one device."""
+    import pyarrow as pa
+    from dataclasses import replace
+
+    if plan.left.table not in tables:
+        raise ValueError(f"table {plan.left.table!r} was not provided")
+    tt = tables[plan.left.table]
+    t_chrom = _column(tt, plan.left.chrom_col)
+    ia, _ib, dictionary = encode_chroms(t_chrom, t_chrom)
+    target = _device_side(tt, plan.left, ia, eng)
+    with_depth = plan.segments != "distinct"
+    try:
+        c, s, e, d = eng.coverage(target, len(dictionary), runs=plan.segments == "runs", with_depth=with_depth)
+    except ValueError as exc:
+        raise ValueError(f"DISJOIN: table {plan.left.table!r} has a row with start > end ({exc})") from exc
+    c, s, e = c.cpu().numpy(), s.cpu().numpy(), e.cpu().numpy()
+    d = d.cpu().numpy() if d is not None else None
+    if return_indices:
+        return c, s, e, d
+    names = pa.array(dictionary).take(pa.array(c))
+    if isinstance(t_chrom, (pa.Array, pa.ChunkedArray)) and names.type != t_chrom.type:
+        names = names.cast(t_chrom.type)      # the column's own type, as the gather of the ungrouped plan returns it
+    made = {"disjoin_chrom": names, "disjoin_start": pa.array(s, type=pa.int32()),
+            "disjoin_end": pa.array(e, type=pa.int32())}
+    cols = [made[p.column] if p.side == "disjoin" else pa.array(d, type=pa.int64()) for p in plan.projection]
+    out = pa.Table.from_arrays(cols, names=[p.name for p in plan.projection])
+    return _finish_outer(out, replace(plan, distinct=False))   # (the segments are distinct already)
+
+
 def _finish_count(plan, lt, rt, counts, n_chrom, eng, ia, return_indices, a_dev=None):
     """count_overlaps: COUNT(b.col) per distinct left key, zero-filled
     (src/giql/expanders/intersects_duckdb.py:806-854; oracle semantics of
@@ -2103,10 +2138,10 @@ def _execute_sharded(plan: JoinPlan, lt, rt, ia, ib, n_chrom, devices, return_in
 def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, return_indices=False,
             device_projection: bool = True, devices=None, outer_joins: bool = False, row_predicates: bool = False,
             select_expressions: bool = False, merge_aggregates: bool = False, range_sets: bool = False,
-            string_aggregates: bool = False, join_aggregates: bool = False):
+            string_aggregates: bool = False, join_aggregates: bool = False, disjoin_aggregates: bool = False):
     """Run *plan* (a :class:`JoinPlan`, its string form, or a GIQL query string; ``outer_joins``,
-    ``row_predicates``, ``select_expressions``, ``merge_aggregates``, ``string_aggregates``, ``range_sets`` and
-    ``join_aggregates`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
+    ``row_predicates``, ``select_expressions``, ``merge_aggregates``, ``string_aggregates``, ``range_sets``,
+    ``join_aggregates`` and ``disjoin_aggregates`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
     (``{name: pyarrow.Table | dict of arrays}``).
 
     Returns a ``pyarrow.Table`` with the plan's projected columns (bag semantics,
@@ -2132,7 +2167,8 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
         else:
             query, opts = plan, dict(outer_joins=outer_joins, row_predicates=row_predicates,
                                      select_expressions=select_expressions, merge_aggregates=merge_aggregates,
-                                     range_sets=range_sets, string_aggregates=string_aggregates)
+                                     range_sets=range_sets, string_aggregates=string_aggregates,
+                                     disjoin_aggregates=disjoin_aggregates)
             plan = build_plan(query, giql_tables, join_aggregates=join_aggregates, **opts)
             relower = lambda: build_plan(query, giql_tables, **opts)  # noqa: E731
     if not isinstance(plan, JoinPlan):
@@ -2150,6 +2186,8 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
     if plan.kind == "FILTER":
         return _execute_filter(plan, tables, eng, return_indices)
     if plan.kind == "DISJOIN":
+        if plan.segments is not None:
+            return _execute_disjoin_segments(plan, tables, eng, return_indices)
         return _execute_disjoin(plan, tables, eng, return_indices)
     for side in (plan.left, plan.right):
         if side.table not in tables:

@@ -28,6 +28,9 @@ PREDICATES = ("intersects", "contains", "within", "within_distance")
 #: the three columns DISJOIN appends to the target's row (src/giql/expanders/disjoin.py:191-198)
 DISJOIN_COLUMNS = ("disjoin_chrom", "disjoin_start", "disjoin_end")
 
+#: what JoinPlan.segments may say: the query forms answered from a table's coverage segments
+SEGMENT_FORMS = ("distinct", "depth", "runs")
+
 
 @dataclass(frozen=True)
 class PlanSide:
@@ -58,7 +61,7 @@ class Projection:
                    # "star" (every table column), "cluster" (the id), "count" (COUNT(*)), "agg" (MERGE: an
                    # aggregate of a value column, column = the index into JoinPlan.aggregates as text); DISJOIN: "l" (a
                    # target column), "disjoin" (column = one of DISJOIN_COLUMNS), "star" (the target's
-                   # columns, then the three)
+                   # columns, then the three); a plan with ``segments`` set: "disjoin" and "count" (COUNT(*)) only
     column: str
     name: str      # output column name
 
@@ -189,6 +192,12 @@ class JoinPlan:
     # row on the device (HipEngine.pair_aggregate) and combined per key.  A LEFT plan so marked needs no padded pair.
     # The string form carries the key only when it is set: every other plan serialises as it did before the field
     join_aggregates: bool = False
+    # DISJOIN in self mode only, lowered with the ``disjoin_aggregates`` opt-in: the query is answered from the coverage
+    # segments of the target (HipEngine.coverage) instead of DISJOIN's per-piece rows.  "distinct": SELECT DISTINCT over
+    # exactly the three disjoin_* columns; "depth": GROUP BY the three with COUNT(*) (a Projection("count", "*", name)
+    # per count); "runs": MERGE(interval, predicate := depth = PREV(depth)) over the "depth" query as a sub-query --
+    # abutting segments of equal depth merged, output chrom / start / end.  Absent from the string form when None
+    segments: str | None = None
 
     def __post_init__(self) -> None:
         if self.kind not in KINDS:
@@ -207,6 +216,9 @@ class JoinPlan:
             raise ValueError(f"literal range sets need a FILTER plan, not {self.kind}")
         if self.join_aggregates and not (self.kind in PAIR_KINDS and self.aggregates and self.group_by):
             raise ValueError("join_aggregates marks a grouped INNER / LEFT plan with aggregates only")
+        if self.segments is not None and not (self.segments in SEGMENT_FORMS and self.kind == "DISJOIN"
+                                              and self.right is None):
+            raise ValueError(f"segments {self.segments!r} marks a self-mode DISJOIN plan as one of {SEGMENT_FORMS}")
         for rs in self.range_sets:
             if rs.op not in RANGE_OPS or rs.quantifier not in RANGE_QUANTIFIERS or not rs.ranges:
                 raise ValueError(f"bad range set {rs.op!r} {rs.quantifier!r} over {len(rs.ranges)} ranges")
@@ -234,6 +246,8 @@ class JoinPlan:
                             "ranges": [list(t) for t in r.ranges]} for r in self.range_sets]
         if not self.join_aggregates:
             del d["join_aggregates"]
+        if self.segments is None:
+            del d["segments"]
         return d
 
     def to_string(self) -> str:
@@ -269,7 +283,7 @@ class JoinPlan:
             range_sets=tuple(RangeSet(r["op"], r["quantifier"], bool(r["negated"]),
                                       tuple((str(c), int(lo), int(hi)) for c, lo, hi in r["ranges"]))
                              for r in d.get("range_sets", ())),
-            join_aggregates=bool(d.get("join_aggregates", False)))
+            join_aggregates=bool(d.get("join_aggregates", False)), segments=d.get("segments"))
 
 
 def is_plan_string(text) -> bool:

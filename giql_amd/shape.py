@@ -1074,22 +1074,33 @@ class DisjoinShape:
     limit: int | None = None
     offset: int | None = None
     sides: tuple[PlanSide, PlanSide | None] | None = None   # as resolved by the caller (the plugin), else from ``tables``
+    # the GROUP BY column list, where the front end read it (the text front end under ``disjoin_aggregates``); None:
+    # only seen (``group_by``), and declined
+    group_cols: list[ColRef] | None = None
 
 
-def lower_disjoin_shape(shape: DisjoinShape, tables: Tables) -> JoinPlan:
+def lower_disjoin_shape(shape: DisjoinShape, tables: Tables, disjoin_aggregates: bool = False) -> JoinPlan:
     """The gate of DISJOIN, shared by both front ends (src/giql/expanders/disjoin.py:102-202): projections over
     the target's columns and the three ``disjoin_*`` columns, DISTINCT, ORDER BY output names, LIMIT / OFFSET.
-    WHERE, GROUP BY / aggregates and HAVING over the operator's rows decline."""
+    WHERE, GROUP BY / aggregates and HAVING over the operator's rows decline.
+
+    ``disjoin_aggregates``: in self mode, ``GROUP BY`` the three ``disjoin_*`` columns with ``COUNT(*) AS <alias>``
+    lowers to a plan answered from the coverage segments (``segments="depth"``,
+    docs/recipes/clustering.rst "Reconstruct disjoin() Coverage Segments"), and ``SELECT DISTINCT`` over exactly
+    the three columns is marked ``segments="distinct"`` (docs/recipes/disjoin.rst "Build a Disjoint Partition")."""
     names = [shape.target.name] + ([shape.reference.name] if shape.reference is not None else [])
     for n in names + ([shape.alias] if shape.alias else []):
         if n.casefold().startswith(DISJOIN_RESERVED_PREFIX):
             raise decline(f"the name {n!r} uses the reserved prefix {DISJOIN_RESERVED_PREFIX!r} of DISJOIN")
     if shape.where:
         raise decline("WHERE over the rows of DISJOIN")
-    if shape.group_by or any(it.func is not None or (it.ref is not None and it.ref.count) for it in shape.items):
+    grouped = shape.group_by or any(it.func is not None or (it.ref is not None and it.ref.count) for it in shape.items)
+    if grouped and not (disjoin_aggregates and shape.group_cols is not None):
         raise decline("GROUP BY / aggregates over the rows of DISJOIN")
     if shape.having:
         raise decline("HAVING over the rows of DISJOIN")
+    if grouped and shape.reference is not None:
+        raise decline("GROUP BY over DISJOIN with reference := (the coverage segments are those of self mode)")
     if shape.sides is not None:
         left, right = shape.sides
     else:
@@ -1102,6 +1113,8 @@ def lower_disjoin_shape(shape: DisjoinShape, tables: Tables) -> JoinPlan:
             raise ValueError(f"Unknown table qualifier {ref.table!r} in {where}")
         return ref.column
 
+    if grouped:
+        return _lower_disjoin_depth(shape, left, own)
     proj, out_names = [], []
     for it in shape.items:
         ref = it.ref
@@ -1133,5 +1146,59 @@ def lower_disjoin_shape(shape: DisjoinShape, tables: Tables) -> JoinPlan:
             name = hidden
         nulls_first = o.nulls_first if o.nulls_first is not None else not o.desc
         order.append((name, o.desc, nulls_first))
+    # DISTINCT over exactly the three appended columns is the set of coverage segments, whatever their depth
+    segments = None
+    if disjoin_aggregates and shape.distinct and right is None \
+            and all(p.side == "disjoin" for p in proj) and sorted(p.column for p in proj) == sorted(DISJOIN_COLUMNS):
+        segments = "distinct"
     return JoinPlan("DISJOIN", left, right, tuple(proj), shape.distinct, order_by=tuple(order), limit=shape.limit,
-                    offset=shape.offset)
+                    offset=shape.offset, segments=segments)
+
+
+def _lower_disjoin_depth(shape: DisjoinShape, left: PlanSide, own) -> JoinPlan:
+    """``SELECT <disjoin_* columns, COUNT(*) AS alias> FROM DISJOIN(t) GROUP BY`` the three ``disjoin_*`` columns:
+    one row per coverage segment with the number of target rows over it (``segments="depth"``)."""
+    if shape.distinct:
+        raise decline("DISTINCT beside GROUP BY over DISJOIN")
+    keys = [own(ref, "GROUP BY") for ref in shape.group_cols]
+    if any(ref.star for ref in shape.group_cols) or sorted(keys) != sorted(DISJOIN_COLUMNS):
+        raise decline("GROUP BY over DISJOIN other than exactly disjoin_chrom, disjoin_start, disjoin_end")
+    proj, out_names = [], []
+    for it in shape.items:
+        if it.distance is not None or it.expr is not None:
+            raise decline("expression in the SELECT list of a grouped DISJOIN")
+        if it.func is not None:
+            if it.func != "COUNT" or it.distinct:
+                raise decline(f"{it.func}({'DISTINCT ' if it.distinct else ''}...) over the rows of DISJOIN: only "
+                              "COUNT(*) is computed per segment")
+            if it.ref is not None:
+                raise decline(f"COUNT({it.ref.column}) over the rows of DISJOIN: only COUNT(*) is computed per segment")
+            if not it.alias:
+                raise decline("COUNT(*) without an alias over the rows of DISJOIN")
+            proj.append(Projection("count", "*", it.alias))
+            out_names.append(it.alias)
+            continue
+        if it.ref.star:
+            raise decline("star projection beside GROUP BY over DISJOIN")
+        column = own(it.ref, "the SELECT list")
+        if column not in DISJOIN_COLUMNS:
+            raise decline(f"target column {column!r} beside GROUP BY over DISJOIN (it is not a GROUP BY key)")
+        proj.append(Projection("disjoin", column, it.alias or column))
+        out_names.append(it.alias or column)
+    if not proj:
+        raise decline("empty SELECT list")
+    if len(set(out_names)) != len(out_names):
+        raise decline("two output columns of one name over a grouped DISJOIN")
+    order = []
+    for o in shape.order_by:
+        name = own(o.ref, "ORDER BY")
+        if name not in out_names:
+            if name not in DISJOIN_COLUMNS:
+                raise decline(f"ORDER BY {name!r}: not an output name or GROUP BY key of the grouped DISJOIN")
+            hidden = f"__giql_o{len(order)}"     # carried for the sort only, as the ungrouped plan does
+            proj.append(Projection("disjoin", name, hidden))
+            name = hidden
+        nulls_first = o.nulls_first if o.nulls_first is not None else not o.desc
+        order.append((name, o.desc, nulls_first))
+    return JoinPlan("DISJOIN", left, None, tuple(proj), False, order_by=tuple(order), limit=shape.limit,
+                    offset=shape.offset, segments="depth")

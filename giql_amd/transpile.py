@@ -36,7 +36,7 @@ from __future__ import annotations
 import re
 from dataclasses import dataclass
 
-from .plan import Aggregate, JoinPlan, Operand, PlanSide, Projection, Residual
+from .plan import DISJOIN_COLUMNS, Aggregate, JoinPlan, Operand, PlanSide, Projection, Residual
 from .shape import AGG_FUNCS, ColRef as _ColRef, HipDeclined, JoinShape, OrderKey, SelItem, TableRef as _TableRef
 from .shape import bind_expression as _bind_expression
 from .shape import condition_terms as _condition_terms
@@ -1098,7 +1098,7 @@ MERGE_STR_SEP_MAX = 255
 
 
 def _lower_cluster(p: _Parser, tbls: Tables, merge_aggregates: bool = False,
-                   string_aggregates: bool = False) -> JoinPlan:
+                   string_aggregates: bool = False, disjoin_aggregates: bool = False) -> JoinPlan:
     """``SELECT <cols | *>, CLUSTER(interval[, d][, stranded := b]) AS id FROM t [WHERE ...]`` and
     ``SELECT MERGE(interval[, d][, stranded := b]) [, COUNT(*) AS n] FROM t [WHERE ...]``
     (src/giql/expanders/cluster.py:81-205, src/giql/expanders/merge.py:62-183).  A WHERE
@@ -1106,7 +1106,8 @@ def _lower_cluster(p: _Parser, tbls: Tables, merge_aggregates: bool = False,
     it lands inside the inner ``__giql_lag_calc`` subquery (cluster.py:404-420).
     ``merge_aggregates``: ``COUNT(col)``, ``SUM(col)``, ``AVG(col)``, ``MIN(col)``, ``MAX(col)`` over a column of the
     table, each with an alias, lower beside MERGE too (merge.py:317-390) instead of declining.
-    ``string_aggregates``: so does ``STRING_AGG(col, '<literal>')`` with an alias (bedtools ``merge -o collapse``)."""
+    ``string_aggregates``: so does ``STRING_AGG(col, '<literal>')`` with an alias (bedtools ``merge -o collapse``).
+    ``disjoin_aggregates``: a sub-query in FROM goes to :func:`_lower_coverage_runs` instead of declining."""
     p.expect_kw("SELECT")
     if p.at_kw("DISTINCT"):
         raise _decline("DISTINCT with CLUSTER / MERGE")
@@ -1162,7 +1163,9 @@ def _lower_cluster(p: _Parser, tbls: Tables, merge_aggregates: bool = False,
         break
     p.expect_kw("FROM")
     if p.at_punct("("):
-        raise _decline("CLUSTER / MERGE over a sub-query")
+        if not disjoin_aggregates:
+            raise _decline("CLUSTER / MERGE over a sub-query")
+        return _lower_coverage_runs(p, tbls, items)
     ref = p.table_ref()
     where_terms = []
     if p.at_kw("WHERE"):
@@ -1321,9 +1324,47 @@ def _disjoin_from(p: _Parser) -> int | None:
     return None
 
 
-def _lower_disjoin(p: _Parser, tbls: Tables) -> JoinPlan:
+def _parse_order_limit(p: _Parser, shape: DisjoinShape) -> None:
+    """``[ORDER BY <column> [ASC | DESC] [NULLS FIRST | LAST], ...] [LIMIT n] [OFFSET m]`` into ``shape``."""
+    if p.at_kw("ORDER"):
+        p.next()
+        p.expect_kw("BY")
+        while True:
+            if p.peek().kind != "id":
+                raise _decline("ORDER BY expression")
+            ref = p.colref()
+            if p.at_punct("(") or (p.peek().kind == "punct" and p.peek().text in "+-/*"):
+                raise _decline("ORDER BY expression")
+            desc = False
+            if p.peek().kind == "id" and not p.peek().quoted and p.peek().text.upper() in ("ASC", "DESC"):
+                desc = p.next().text.upper() == "DESC"
+            nulls_first = None
+            if p.peek().kind == "id" and not p.peek().quoted and p.peek().text.upper() == "NULLS":
+                p.next()
+                t = p.next()
+                if t.kind not in ("id", "kw") or t.text.upper() not in ("FIRST", "LAST"):
+                    raise ValueError("ORDER BY ... NULLS must be followed by FIRST or LAST")
+                nulls_first = t.text.upper() == "FIRST"
+            shape.order_by.append(OrderKey(ref, desc, nulls_first))
+            if p.at_punct(","):
+                p.next()
+                continue
+            break
+    for _ in range(2):
+        for clause in ("LIMIT", "OFFSET"):
+            if p.at_kw(clause) and getattr(shape, clause.lower()) is None:
+                p.next()
+                t = p.next()
+                if t.kind != "num" or "." in t.text:
+                    raise _decline(f"{clause} that is not an integer literal")
+                setattr(shape, clause.lower(), int(t.text))
+
+
+def _lower_disjoin(p: _Parser, tbls: Tables, disjoin_aggregates: bool = False, nested: bool = False) -> JoinPlan:
     """``SELECT [DISTINCT] <* | columns> FROM DISJOIN(target [, reference := ref]) [[AS] alias] [ORDER BY ...]
-    [LIMIT n] [OFFSET m]`` (docs/dialect/set-operators.rst, DISJOIN; src/giql/expanders/disjoin.py:102-202)."""
+    [LIMIT n] [OFFSET m]`` (docs/dialect/set-operators.rst, DISJOIN; src/giql/expanders/disjoin.py:102-202).
+    ``disjoin_aggregates``: a ``GROUP BY <columns>`` is read, for :func:`shape.lower_disjoin_shape` to judge.
+    ``nested``: the statement is a sub-query and ends before its closing parenthesis."""
     if p.at_kw("WITH"):
         raise _decline("DISJOIN over a CTE (top-level WITH)")
     p.expect_kw("SELECT")
@@ -1368,51 +1409,124 @@ def _lower_disjoin(p: _Parser, tbls: Tables) -> JoinPlan:
         shape.where = True
     elif p.at_kw("GROUP"):
         shape.group_by = True
-    elif p.at_kw("HAVING"):
-        shape.having = True
-    if not (shape.where or shape.group_by or shape.having):
-        if p.at_kw("ORDER"):
+        if disjoin_aggregates:
             p.next()
             p.expect_kw("BY")
+            shape.group_cols = []
             while True:
                 if p.peek().kind != "id":
-                    raise _decline("ORDER BY expression")
-                ref = p.colref()
+                    raise _decline("GROUP BY expression over DISJOIN")
+                shape.group_cols.append(p.colref())
                 if p.at_punct("(") or (p.peek().kind == "punct" and p.peek().text in "+-/*"):
-                    raise _decline("ORDER BY expression")
-                desc = False
-                if p.peek().kind == "id" and not p.peek().quoted and p.peek().text.upper() in ("ASC", "DESC"):
-                    desc = p.next().text.upper() == "DESC"
-                nulls_first = None
-                if p.peek().kind == "id" and not p.peek().quoted and p.peek().text.upper() == "NULLS":
-                    p.next()
-                    t = p.next()
-                    if t.kind not in ("id", "kw") or t.text.upper() not in ("FIRST", "LAST"):
-                        raise ValueError("ORDER BY ... NULLS must be followed by FIRST or LAST")
-                    nulls_first = t.text.upper() == "FIRST"
-                shape.order_by.append(OrderKey(ref, desc, nulls_first))
-                if p.at_punct(","):
-                    p.next()
-                    continue
-                break
-        for _ in range(2):
-            for clause in ("LIMIT", "OFFSET"):
-                if p.at_kw(clause) and getattr(shape, clause.lower()) is None:
-                    p.next()
-                    t = p.next()
-                    if t.kind != "num" or "." in t.text:
-                        raise _decline(f"{clause} that is not an integer literal")
-                    setattr(shape, clause.lower(), int(t.text))
+                    raise _decline("GROUP BY expression over DISJOIN")
+                if not p.at_punct(","):
+                    break
+                p.next()
+            shape.having = p.at_kw("HAVING")
+    elif p.at_kw("HAVING"):
+        shape.having = True
+    if not (shape.where or shape.having or (shape.group_by and shape.group_cols is None)):
+        _parse_order_limit(p, shape)
         if p.peek().kind == "kw":
             raise _decline(f"{p.peek().text} clause after DISJOIN")
-        if p.peek().kind != "end" and not p.at_punct(";"):
+        if p.peek().kind != "end" and not p.at_punct(";") and not (nested and p.at_punct(")")):
             raise _decline(f"trailing input near {p.peek().text!r}")
-    return lower_disjoin_shape(shape, tbls)
+    return lower_disjoin_shape(shape, tbls, disjoin_aggregates=disjoin_aggregates)
+
+
+def _lower_coverage_runs(p: _Parser, tbls: Tables, items) -> JoinPlan:
+    """``SELECT MERGE(interval, predicate := depth = PREV(depth)) FROM (<the grouped DISJOIN query>) [[AS] alias]
+    [ORDER BY ...] [LIMIT n] [OFFSET m]`` (docs/recipes/clustering.rst, "Reconstruct disjoin() Coverage Segments";
+    docs/dialect/aggregation-operators.rst, "Predicate-Gated Merge"): abutting coverage segments of equal depth,
+    merged.  ``p`` stands at the sub-query's parenthesis; ``items`` is the outer SELECT list as ``_lower_cluster``
+    read it.  The inner query names its columns ``chrom``, ``start``, ``end`` and its ``COUNT(*)`` as the predicate
+    does.  Output: ``chrom``, ``start``, ``end``."""
+    other = "CLUSTER / MERGE over a sub-query other than the coverage segments of DISJOIN"
+    p.expect_punct("(")
+    depth, k, inner_disjoin = 0, p.i, False
+    while k + 2 < len(p.toks):
+        t = p.toks[k]
+        if t.kind == "punct" and t.text == "(":
+            depth += 1
+        elif t.kind == "punct" and t.text == ")":
+            if depth == 0:
+                break
+            depth -= 1
+        elif t.kind == "kw" and t.text == "FROM" and depth == 0:
+            a, b = p.toks[k + 1], p.toks[k + 2]
+            inner_disjoin = a.kind == "id" and not a.quoted and a.text.upper() == "DISJOIN" and b.kind == "punct" \
+                and b.text == "("
+            break
+        k += 1
+    if not p.at_kw("SELECT") or not inner_disjoin:
+        raise _decline(other)
+    inner = _lower_disjoin(p, tbls, disjoin_aggregates=True, nested=True)
+    p.expect_punct(")")
+    if inner.segments != "depth":
+        raise _decline(other)
+    if inner.order_by or inner.limit is not None or inner.offset is not None:
+        raise _decline("ORDER BY / LIMIT inside the coverage sub-query of MERGE")
+    alias = None
+    if p.at_kw("AS"):
+        p.next()
+        alias = p.ident().text
+    elif p.peek().kind == "id":
+        alias = p.next().text
+    tail = DisjoinShape(items=[], target=None)
+    _parse_order_limit(p, tail)
+    if p.peek().kind == "kw" or p.at_punct(","):
+        raise _decline(f"{p.peek().text} clause with MERGE over the coverage segments")
+    if p.peek().kind != "end" and not p.at_punct(";"):
+        raise _decline(f"trailing input near {p.peek().text!r}")
+
+    if any(it[0] == "CLUSTER" for it in items):
+        raise _decline("CLUSTER over a sub-query")
+    if any(it[0] in ("COUNT", "AGG") for it in items):
+        raise _decline("aggregate beside MERGE over the coverage segments")
+    if len(items) != 1:
+        raise _decline("column beside MERGE over the coverage segments (it returns chrom, start, end)")
+    this, distance, stranded, predicate = items[0][1]
+    names = {pp.column: pp.name for pp in inner.projection if pp.side == "disjoin"}
+    if [names.get(c) for c in DISJOIN_COLUMNS] != ["chrom", "start", "end"]:
+        raise _decline("coverage sub-query that does not name disjoin_chrom, disjoin_start, disjoin_end as chrom, "
+                       "start, end")
+    if this.star or this.column != "interval" or (this.table is not None and (alias is None or _norm(
+            this.table, this.table_quoted) != _norm(alias))):
+        raise ValueError("MERGE operand must be the sub-query's genomic column ('interval')")
+    if distance:
+        raise _decline("MERGE distance over the coverage segments")
+    if stranded:
+        raise _decline("MERGE(stranded := true) over the coverage segments")
+    counts = {pp.name for pp in inner.projection if pp.side == "count"}
+
+    def depth_col(o, kind) -> bool:
+        return o[0] == kind and not o[1].star and o[1].column in counts and (
+            o[1].table is None or (alias is not None and _norm(o[1].table, o[1].table_quoted) == _norm(alias)))
+
+    ok = len(predicate) == 1 and predicate[0][0] == "cmp" and predicate[0][2] in ("=", "==")
+    if ok:
+        _, lhs, _op, rhs = predicate[0]
+        ok = (depth_col(lhs, "col") and depth_col(rhs, "prev") or depth_col(lhs, "prev") and depth_col(rhs, "col")) \
+            and lhs[1].column == rhs[1].column
+    if not ok:
+        raise _decline("MERGE over the coverage segments with a predicate other than <depth> = PREV(<depth>)")
+    if inner.left.interval_type == "closed":
+        raise _decline("coverage runs over a closed-interval target: MERGE compares raw coordinates, where abutting "
+                       "closed segments ([0, 9], [10, 19]) never touch, so nothing would merge")
+    out = ("chrom", "start", "end")
+    order = []
+    for o in tail.order_by:
+        if o.ref.table is not None or o.ref.column not in out:
+            raise _decline(f"ORDER BY {o.ref.column!r} over the merged coverage segments (chrom, start, end)")
+        order.append((o.ref.column, o.desc, o.nulls_first if o.nulls_first is not None else not o.desc))
+    return JoinPlan("DISJOIN", inner.left, None, tuple(Projection("disjoin", c, n) for c, n in zip(DISJOIN_COLUMNS, out)),
+                    order_by=tuple(order), limit=tail.limit, offset=tail.offset, segments="runs")
 
 
 def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predicates: bool = False,
                select_expressions: bool = False, merge_aggregates: bool = False, range_sets: bool = False,
-               string_aggregates: bool = False, join_aggregates: bool = False) -> JoinPlan:
+               string_aggregates: bool = False, join_aggregates: bool = False,
+               disjoin_aggregates: bool = False) -> JoinPlan:
     """Parse *giql* and lower the INTERSECTS / NEAREST join (or a CLUSTER / MERGE
     query) to a :class:`JoinPlan`.
 
@@ -1437,7 +1551,13 @@ def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predica
     -- ``COUNT(*)``, ``COUNT(b.col)``, ``SUM`` / ``AVG`` / ``MIN`` / ``MAX`` of a right-side numeric column -- lowers to
     an INNER / LEFT plan marked ``join_aggregates`` whose aggregates are computed per left row on the device.  The LEFT
     form needs no ``outer_joins``; a ``COUNT`` beside other aggregates, which declines without the flag, lowers too.  A
-    query outside the shape lowers (or declines) exactly as it does without the flag."""
+    query outside the shape lowers (or declines) exactly as it does without the flag.
+    ``disjoin_aggregates=True`` opts in to the coverage profile of one table, answered from DISJOIN's breakpoints
+    without its per-piece rows (``bedtools genomecov -bg``, Bioconductor ``disjoin()``): ``SELECT <disjoin_* columns>,
+    COUNT(*) AS depth FROM DISJOIN(t) GROUP BY disjoin_chrom, disjoin_start, disjoin_end`` (``segments="depth"``),
+    ``SELECT DISTINCT`` over exactly those three columns (``"distinct"``), and ``SELECT MERGE(interval, predicate :=
+    depth = PREV(depth)) FROM (<the grouped query, its columns named chrom, start, end>)`` over a half-open target
+    (``"runs"``).  Self mode only; HAVING, WHERE and other aggregates decline."""
     probe = _Parser(giql, range_sets=bool(range_sets))
     tbls = tables if isinstance(tables, Tables) else build_tables(tables)
     for routed, lower, what in ((_disjoin_from(probe) is not None, _lower_disjoin, "DISJOIN"),
@@ -1449,7 +1569,9 @@ def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predica
         try:
             if lower is _lower_cluster:
                 return lower(probe, tbls, merge_aggregates=bool(merge_aggregates),
-                             string_aggregates=bool(string_aggregates))
+                             string_aggregates=bool(string_aggregates), disjoin_aggregates=bool(disjoin_aggregates))
+            if lower is _lower_disjoin:
+                return lower(probe, tbls, disjoin_aggregates=bool(disjoin_aggregates))
             return lower(probe, tbls)
         except HipDeclined as exc:
             # these operators compute no column: with the opt-in the decline names the operator
@@ -1655,7 +1777,7 @@ def _render(toks: list[Tok]) -> str:
 def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins: bool = False,
               row_predicates: bool = False, select_expressions: bool = False,
               merge_aggregates: bool = False, range_sets: bool = False, string_aggregates: bool = False,
-              join_aggregates: bool = False) -> str:
+              join_aggregates: bool = False, disjoin_aggregates: bool = False) -> str:
     """Mirror of ``giql.transpile`` for this backend's path.
 
     ``dialect="hip"``: returns the plan string of the INTERSECTS / NEAREST join
@@ -1663,7 +1785,8 @@ def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins
     and ``row_predicates=True`` the per-row joins over CONTAINS / WITHIN / DISTANCE, ``select_expressions=True``
     computed columns such as ``overlap_bp`` in the SELECT list, ``merge_aggregates=True`` SUM / AVG / MIN / MAX /
     COUNT(col) beside MERGE, ``string_aggregates=True`` STRING_AGG(col, 'sep') beside MERGE, ``range_sets=True`` ANY / SOME / ALL over literal ranges and NOT over a literal predicate
-    in a single-table filter, ``join_aggregates=True`` grouped aggregates over a join in the map shape
+    in a single-table filter, ``join_aggregates=True`` grouped aggregates over a join in the map shape,
+    ``disjoin_aggregates=True`` the coverage profile (GROUP BY / COUNT(*) over DISJOIN and its run form)
     (:func:`build_plan`).  ``dialect=None``: returns SQL for the
     literal-range predicate (plumbing, BASELINE config 1).  Other dialects belong to
     the reference package.
@@ -1672,7 +1795,7 @@ def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins
         return build_plan(giql, tables, outer_joins=outer_joins, row_predicates=row_predicates,
                           select_expressions=select_expressions, merge_aggregates=merge_aggregates,
                           range_sets=range_sets, string_aggregates=string_aggregates,
-                          join_aggregates=join_aggregates).to_string()
+                          join_aggregates=join_aggregates, disjoin_aggregates=disjoin_aggregates).to_string()
     if dialect is None:
         return _lower(giql, tables, want_sql=True)
     raise ValueError(
