@@ -65,6 +65,9 @@ STRING_AGG_SYMBOLS = ["giql_hip_merge_str_dev", "giql_hip_concat_utf8_fill_dev"]
 #: every symbol include/giql_hip_pair_agg.h declares (aggregates over a join's pairs, per left row)
 PAIR_AGG_SYMBOLS = ["giql_hip_pair_agg_dev"]
 
+#: every symbol include/giql_hip_pair_expr_agg.h declares (aggregates of per-pair expressions over a join's pairs)
+PAIR_EXPR_AGG_SYMBOLS = ["giql_hip_pair_expr_agg_dev"]
+
 #: every symbol include/giql_hip_coverage.h declares (coverage depth per DISJOIN segment)
 COVERAGE_SYMBOLS = ["giql_hip_coverage_dev"]
 
@@ -163,6 +166,21 @@ class CAgg(ctypes.Structure):
         ("type", ctypes.c_int32),
         ("data", ctypes.c_void_p),
         ("valid", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("out_nn", ctypes.c_void_p),
+    ]
+
+
+class CPairExprAgg(ctypes.Structure):
+    """``giql_pair_expr_agg`` (include/giql_hip_pair_expr_agg.h)."""
+
+    _fields_ = [
+        ("func", ctypes.c_int32),
+        ("type", ctypes.c_int32),
+        ("data", ctypes.c_void_p),
+        ("valid", ctypes.c_void_p),
+        ("first", ctypes.c_int32),
+        ("count", ctypes.c_int32),
         ("out", ctypes.c_void_p),
         ("out_nn", ctypes.c_void_p),
     ]
@@ -307,6 +325,7 @@ def load() -> ctypes.CDLL:
                                          vp, vp, vp, vp, vp, i64, P(i64), vp]
     L.giql_hip_concat_utf8_fill_dev.argtypes = [vp, vp, vp, i64, vp, vp, i64, ctypes.c_char_p, i32, vp, vp]
     L.giql_hip_pair_agg_dev.argtypes = [vp, vp, vp, i64, i64, i64, P(CAgg), i32, vp, vp]
+    L.giql_hip_pair_expr_agg_dev.argtypes = [vp, vp, vp, i64, i64, i64, P(COperand), i32, P(CPairExprAgg), i32, vp, vp]
     L.giql_hip_coverage_dev.argtypes = [vp, P(CSide), i32, ctypes.c_uint32, vp, vp, vp, vp, i64, P(i64), vp]
     _lib = L
     return L

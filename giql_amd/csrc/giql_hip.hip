@@ -22,6 +22,7 @@
 #include "../../include/giql_hip_range_sets.h"
 #include "../../include/giql_hip_string_agg.h"
 #include "../../include/giql_hip_pair_agg.h"
+#include "../../include/giql_hip_pair_expr_agg.h"
 #include "../../include/giql_hip_coverage.h"
 #include "aux_kernels.hip.h"
 #include "take_kernels.hip.h"
@@ -32,6 +33,7 @@
 #include "merge_agg_kernels.hip.h"
 #include "string_agg_kernels.hip.h"
 #include "pair_agg_kernels.hip.h"
+#include "pair_expr_agg_kernels.hip.h"
 #include "range_set_kernels.hip.h"
 #include "disjoin_kernels.hip.h"
 #include "coverage_kernels.hip.h"
@@ -3966,8 +3968,12 @@ static int pagg_digits(int64_t n_rows) {
   return p;
 }
 
-int giql_hip_pair_agg_dev(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t* row_b, int64_t n_pairs, int64_t n_a,
-                          int64_t n_b, const giql_agg* aggs, int32_t n_aggs, int64_t* pairs_out, void* stream) {
+// One pipeline for both entry points: an aggregate's value source is a column of B (count == 0) or a program over the
+// staged nodes (include/giql_hip_pair_expr_agg.h).  Without a program the reduction is k_magg_tiles, as it was before
+// programs existed; with one it is k_pxagg_tiles, which also gathers the column sources of the same call.
+static int pair_agg_impl(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t* row_b, int64_t n_pairs, int64_t n_a,
+                         int64_t n_b, const giql_operand* nodes, int32_t n_nodes, const giql_pair_expr_agg* aggs,
+                         int32_t n_aggs, int64_t* pairs_out, void* stream) {
   if (!ctx) return set_err(GIQL_ERR_INVALID, "ctx is NULL");
   // Begins a call before its own checks: whatever it goes on to return, a plan the context held is gone.
   GIQL_TRY(begin_call(ctx, n_a, n_b));
@@ -3977,27 +3983,50 @@ int giql_hip_pair_agg_dev(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t
     return set_err(GIQL_ERR_INVALID, "%lld pairs: one call aggregates fewer than 2^31", (long long)n_pairs);
   if (n_aggs < 0 || n_aggs > MAGG_MAX || (n_aggs && !aggs))
     return set_err(GIQL_ERR_INVALID, "%d aggregates: a pair aggregate takes 0 to %d", n_aggs, MAGG_MAX);
-  MaggArgs ma;
-  memset(&ma, 0, sizeof(ma));
+  if (n_nodes < 0 || n_nodes > SEL_MAX_NODES || (n_nodes && !nodes))
+    return set_err(GIQL_ERR_INVALID, "%d expression nodes: a pair aggregate takes 0 to %d", n_nodes, SEL_MAX_NODES);
+  PxaggArgs xa;
+  memset(&xa, 0, sizeof(xa));
+  MaggArgs& ma = xa.M;
   ma.n_aggs = n_aggs;
+  bool any_prog = false;
   // a float SUM, MIN or MAX: the aggregates whose bits depend on the order of their inputs (a sum's rounding; which of
   // +0.0 and -0.0 a MIN / MAX keeps)
   bool ordered = false;
   for (int k = 0; k < n_aggs; k++) {
-    const giql_agg& g = aggs[k];
+    const giql_pair_expr_agg& g = aggs[k];
     if (g.func < GIQL_AGG_COUNT || g.func > GIQL_AGG_MAX)
       return set_err(GIQL_ERR_INVALID, "aggregate %d: function %d", k, g.func);
     if (g.type < GIQL_T_I32 || g.type > GIQL_T_F64)
       return set_err(GIQL_ERR_INVALID, "aggregate %d: column type %d (int32, int64, float32 or float64)", k, g.type);
     if (!g.out) return set_err(GIQL_ERR_INVALID, "aggregate %d: out is NULL", k);
-    if (!g.data && g.func != GIQL_AGG_COUNT)
-      return set_err(GIQL_ERR_INVALID, "aggregate %d: data is NULL (only COUNT reads validity alone)", k);
-    // COUNT never reads the values: its column is the validity alone, shared by every COUNT over it
-    const MaggCol want = g.func == GIQL_AGG_COUNT ? MaggCol{nullptr, (const unsigned char*)g.valid, MAGG_T_NONE}
-                                                  : MaggCol{g.data, (const unsigned char*)g.valid, g.type};
+    if (g.count < 0) return set_err(GIQL_ERR_INVALID, "aggregate %d: a program of %d nodes", k, g.count);
+    MaggCol want;
+    PxaggProg prog{0, 0};
+    if (g.count > 0) {  // an expression source: checked and typed as giql_hip_eval_expr_dev does it
+      if (g.type != GIQL_T_I64 && g.type != GIQL_T_F64)
+        return set_err(GIQL_ERR_INVALID, "aggregate %d: result type %d of a program (GIQL_T_I64 or GIQL_T_F64)", k, g.type);
+      bool uses[2] = {false, false}, can_float = false;
+      GIQL_TRY(check_program(nodes, n_nodes, g.first, g.count, k, "program", uses, "aggregate", &can_float));
+      if (can_float && g.type == GIQL_T_I64)
+        return set_err(GIQL_ERR_INVALID, "aggregate %d: the program can yield a float, its result type is GIQL_T_I64", k);
+      want = MaggCol{nullptr, nullptr, g.type};  // (k_magg_fold reads the type alone)
+      prog = PxaggProg{g.first, g.count};
+      any_prog = true;
+    } else {
+      if (!g.data && g.func != GIQL_AGG_COUNT)
+        return set_err(GIQL_ERR_INVALID, "aggregate %d: data is NULL (only COUNT reads validity alone)", k);
+      // COUNT never reads the values: its column is the validity alone, shared by every COUNT over it
+      want = g.func == GIQL_AGG_COUNT ? MaggCol{nullptr, (const unsigned char*)g.valid, MAGG_T_NONE}
+                                      : MaggCol{g.data, (const unsigned char*)g.valid, g.type};
+    }
     int c = 0;
-    while (c < ma.n_cols && !(ma.cols[c].data == want.data && ma.cols[c].valid == want.valid && ma.cols[c].type == want.type)) c++;
-    if (c == ma.n_cols) ma.cols[ma.n_cols++] = want;
+    while (c < ma.n_cols && !(ma.cols[c].data == want.data && ma.cols[c].valid == want.valid && ma.cols[c].type == want.type &&
+                              xa.prog[c].first == prog.first && xa.prog[c].count == prog.count)) c++;
+    if (c == ma.n_cols) {
+      xa.prog[c] = prog;
+      ma.cols[ma.n_cols++] = want;
+    }
     ma.aggs[k].func = g.func;
     ma.aggs[k].col = c;
     if (g.func != GIQL_AGG_COUNT && (g.type == GIQL_T_F32 || g.type == GIQL_T_F64)) ordered = true;
@@ -4022,6 +4051,7 @@ int giql_hip_pair_agg_dev(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t
   SortBufs sb;
   u32 *tile_hist = nullptr, *flags = nullptr, *excl = nullptr, *head_pos = nullptr;
   u64 *bsums = nullptr, *total = nullptr, *seg = nullptr, *carry = nullptr;
+  DevOperand* d_nodes = nullptr;
   auto carve = [&](char* base) {
     Carver c{base};
     sort_sizes_key_payload(c, n, sb);  // 16 bytes per pair: (row_b, row_a) twice -- no row id column, nothing reads one
@@ -4034,10 +4064,13 @@ int giql_hip_pair_agg_dev(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t
     head_pos = c.take<u32>(m_max + 1);
     seg = c.take<u64>((size_t)n_aggs * 2 * m_max);
     carry = c.take<u64>((size_t)n_aggs * 4 * n_tiles);
+    if (any_prog) d_nodes = c.take<DevOperand>(SEL_MAX_NODES);
     return c.off;
   };
   GIQL_TRY(claim_arena(ctx, st, carve));
   HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
+  // (pageable source: staged by the runtime before the call returns)
+  if (any_prog) HIP_TRY(hipMemcpyAsync(d_nodes, nodes, (size_t)n_nodes * sizeof(DevOperand), hipMemcpyHostToDevice, st));
   const u32 grid = cdiv(n, PAGG_NT);
   {
     Phase ph(ctx, st, GIQL_PH_AUX);
@@ -4070,7 +4103,11 @@ int giql_hip_pair_agg_dev(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t
     Phase ph(ctx, st, GIQL_PH_FILL, 2 + (n_aggs ? (n_tiles > 1 ? 2 : 1) : 0));
     hipLaunchKernelGGL(k_merge_heads, dim3(grid), dim3(256), 0, st, flags, excl, (u32)n, head_pos);
     if (n_aggs) {
-      hipLaunchKernelGGL(k_magg_tiles, dim3(n_tiles), dim3(MAGG_TILE), 0, st, sorted_b, excl, flags, (u32)n, ma);
+      if (any_prog)
+        hipLaunchKernelGGL(k_pxagg_tiles, dim3(n_tiles), dim3(MAGG_TILE), 0, st, sorted_a, sorted_b, excl, flags, (u32)n,
+                           (const DevOperand*)d_nodes, xa);
+      else
+        hipLaunchKernelGGL(k_magg_tiles, dim3(n_tiles), dim3(MAGG_TILE), 0, st, sorted_b, excl, flags, (u32)n, ma);
       if (n_tiles > 1)
         hipLaunchKernelGGL(k_magg_fold, dim3(cdiv((u64)n_tiles - 1, 256 / WAVE)), dim3(256), 0, st, excl, flags, (u32)n,
                            n_tiles, ma);
@@ -4088,6 +4125,20 @@ int giql_hip_pair_agg_dev(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t
                    (long long)n_a, (long long)n_b);
   ctx->stats.n_out = n_a;
   return GIQL_OK;
+}
+
+int giql_hip_pair_agg_dev(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t* row_b, int64_t n_pairs, int64_t n_a,
+                          int64_t n_b, const giql_agg* aggs, int32_t n_aggs, int64_t* pairs_out, void* stream) {
+  giql_pair_expr_agg cols[MAGG_MAX];
+  for (int k = 0; aggs && k < n_aggs && k < MAGG_MAX; k++)
+    cols[k] = giql_pair_expr_agg{aggs[k].func, aggs[k].type, aggs[k].data, aggs[k].valid, 0, 0, aggs[k].out, aggs[k].out_nn};
+  return pair_agg_impl(ctx, row_a, row_b, n_pairs, n_a, n_b, nullptr, 0, aggs ? cols : nullptr, n_aggs, pairs_out, stream);
+}
+
+int giql_hip_pair_expr_agg_dev(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t* row_b, int64_t n_pairs,
+                               int64_t n_a, int64_t n_b, const giql_operand* nodes, int32_t n_nodes,
+                               const giql_pair_expr_agg* aggs, int32_t n_aggs, int64_t* pairs_out, void* stream) {
+  return pair_agg_impl(ctx, row_a, row_b, n_pairs, n_a, n_b, nodes, n_nodes, aggs, n_aggs, pairs_out, stream);
 }
 
 // ----------------------------------------------------------------- DISJOIN

@@ -74,6 +74,48 @@ __device__ __forceinline__ u32 magg_region(const u32* __restrict__ excl, const u
   return excl[i] + flags[i] - 1u;  // (every partition's first row is a head)
 }
 
+// One aggregate of one value source over the tile: the part every tile kernel shares (k_magg_tiles here,
+// k_pxagg_tiles of pair_expr_agg_kernels.hip.h).  `x` / `ok` are the thread's value pattern and "is not NULL", `g` its
+// region; s_g holds every wave's last region (written before the first call), s_v / s_c the waves' tails, in buffer
+// `buf` (the callers alternate two: a wave one aggregate ahead writes the other one).  Holds one __syncthreads():
+// every thread of the block calls it, for the same aggregates in the same order.
+__device__ __forceinline__ void magg_reduce(const MaggAgg& ag, bool flt, bool ok, u64 x, u32 g, int lane, int w,
+                                            bool wave_end, bool began_here, bool closed, int buf, const u32* s_g,
+                                            u64 (*s_v)[MAGG_TILE / WAVE], u32 (*s_c)[MAGG_TILE / WAVE]) {
+  u64 v = ok ? x : magg_identity(ag.func, flt);
+  u32 cnt = ok ? 1u : 0u;
+#pragma unroll
+  for (int d = 1; d < WAVE; d <<= 1) {
+    const u64 ov = __shfl_up((unsigned long long)v, d);
+    const u32 oc = (u32)__shfl_up((int)cnt, d);
+    const u32 og = (u32)__shfl_up((int)g, d);
+    if (lane >= d && og == g) {
+      v = magg_combine(ag.func, flt, ov, v);
+      cnt += oc;
+    }
+  }
+  if (lane == WAVE - 1) {
+    s_v[buf][w] = v;
+    s_c[buf][w] = cnt;
+  }
+  __syncthreads();
+  if (!wave_end) return;
+  // g never decreases along the tile: an earlier wave whose tail is g is g to its end, and the run is contiguous
+  for (int pw = w - 1; pw >= 0 && s_g[pw] == g; pw--) {
+    v = magg_combine(ag.func, flt, s_v[buf][pw], v);
+    cnt += s_c[buf][pw];
+  }
+  if (began_here && closed) {
+    ag.out[g] = ag.func == MAGG_COUNT ? (u64)cnt : (cnt ? v : 0);  // (no non-NULL input: NULL, value 0)
+    if (ag.out_nn) ag.out_nn[g] = (i64)cnt;
+  } else if (closed || threadIdx.x == MAGG_TILE - 1) {  // (an open run ends at the tile's last thread)
+    u64* cv = began_here ? ag.last_v : ag.first_v;
+    i64* cc = began_here ? ag.last_c : ag.first_c;
+    cv[blockIdx.x] = v;
+    cc[blockIdx.x] = (i64)cnt;
+  }
+}
+
 __global__ __launch_bounds__(MAGG_TILE) void k_magg_tiles(const u32* __restrict__ rids, const u32* __restrict__ excl,
                                                           const u32* __restrict__ flags, u32 n, MaggArgs A) {
   constexpr int NW = MAGG_TILE / WAVE;
@@ -107,40 +149,8 @@ __global__ __launch_bounds__(MAGG_TILE) void k_magg_tiles(const u32* __restrict_
     for (int a = 0; a < A.n_aggs; a++) {
       const MaggAgg ag = A.aggs[a];
       if (ag.col != c) continue;  // (uniform)
-      u64 v = ok ? x : magg_identity(ag.func, flt);
-      u32 cnt = ok ? 1u : 0u;
-#pragma unroll
-      for (int d = 1; d < WAVE; d <<= 1) {
-        const u64 ov = __shfl_up((unsigned long long)v, d);
-        const u32 oc = (u32)__shfl_up((int)cnt, d);
-        const u32 og = (u32)__shfl_up((int)g, d);
-        if (lane >= d && og == g) {
-          v = magg_combine(ag.func, flt, ov, v);
-          cnt += oc;
-        }
-      }
-      const int buf = k & 1;  // (two buffers: a wave one aggregate ahead writes the other one)
+      magg_reduce(ag, flt, ok, x, g, lane, w, wave_end, began_here, closed, k & 1, s_g, s_v, s_c);
       k++;
-      if (lane == WAVE - 1) {
-        s_v[buf][w] = v;
-        s_c[buf][w] = cnt;
-      }
-      __syncthreads();
-      if (!wave_end) continue;
-      // g never decreases along the tile: an earlier wave whose tail is g is g to its end, and the run is contiguous
-      for (int pw = w - 1; pw >= 0 && s_g[pw] == g; pw--) {
-        v = magg_combine(ag.func, flt, s_v[buf][pw], v);
-        cnt += s_c[buf][pw];
-      }
-      if (began_here && closed) {
-        ag.out[g] = ag.func == MAGG_COUNT ? (u64)cnt : (cnt ? v : 0);  // (no non-NULL input: NULL, value 0)
-        if (ag.out_nn) ag.out_nn[g] = (i64)cnt;
-      } else if (closed || threadIdx.x == MAGG_TILE - 1) {  // (an open run ends at the tile's last thread)
-        u64* cv = began_here ? ag.last_v : ag.first_v;
-        i64* cc = began_here ? ag.last_c : ag.first_c;
-        cv[blockIdx.x] = v;
-        cc[blockIdx.x] = (i64)cnt;
-      }
     }
   }
 }

@@ -1259,7 +1259,14 @@ class HipEngine:
         (0: the value is NULL and reads 0).  SUM / MIN / MAX of an integer column are int64, of a float column
         float64; AVG is ``double(sum) / double(non_null)``; COUNT is ``non_null``.  A row's values are reduced in
         ascending ``row_b`` without atomics: the result does not depend on the order of the pairs, float sums
-        included.  Ids outside their table raise ``GiqlHipError``."""
+        included.  Ids outside their table raise ``GiqlHipError``.
+
+        In place of the values tensor an entry may give ``("expr", tree)``: the aggregate of an EXPRESSION evaluated at
+        every pair (``giql_hip_pair_expr_agg_dev``), ``tree`` being what :meth:`eval_exprs` takes, ``("if", ...)`` and
+        ``("null",)`` included; its ``"a"`` columns hold ``n_a`` rows, its ``"b"`` columns ``n_b``.  A pair at which
+        the tree is NULL is no input.  SUM / MIN / MAX are float64 where :func:`expr_can_float` says the tree can
+        yield a float, else int64.  The values are reduced as they are computed: no per-pair array is made.  A call
+        takes at most 256 expression nodes in total; a call without such an entry is ``giql_hip_pair_agg_dev``'s."""
         torch = _torch()
         aggs = [(str(a[0]).upper(), a[1], a[2] if len(a) > 2 else None) for a in aggs]
         n_a, n_b = int(n_a), int(n_b)
@@ -1268,6 +1275,8 @@ class HipEngine:
         n = int(row_a.shape[0])
         if int(row_b.shape[0]) != n or row_a.dim() != 1 or row_b.dim() != 1:
             raise ValueError("row_a and row_b must have one entry per pair")
+        if any(isinstance(a[1], tuple) for a in aggs):
+            return self._pair_expr_aggregate(row_a, row_b, n, n_a, n_b, aggs)
         ok = (torch.int32, torch.int64, torch.float32, torch.float64)
         types = {torch.int32: _lib.T_I32, torch.int64: _lib.T_I64, torch.float32: _lib.T_F32,
                  torch.float64: _lib.T_F64}
@@ -1312,6 +1321,94 @@ class HipEngine:
         res = []
         for (func, _t, _v), j in zip(aggs, slot):
             out, nn = kernel[j][3], kernel[j][4]
+            if func == "AVG":
+                out = torch.where(nn > 0, out.double() / nn.double(), torch.zeros(n_a, dtype=torch.float64,
+                                                                                  device=self.device))
+            res.append((out, nn))
+        return pairs, res
+
+    def _expr_key(self, tree, n_a: int, n_b: int):
+        """A hashable restatement of ``tree`` (columns by address): equal keys are one program.  Checks every column's
+        row count against its table on the way -- the kernel reads a column at the pair's row id."""
+        kind = tree[0]
+        if kind in ("a", "b"):
+            t, valid = tree[1], tree[2] if len(tree) > 2 else None
+            if int(t.shape[0]) != (n_a if kind == "a" else n_b):
+                raise ValueError(f"a column of side {kind!r} must have one value per row of its table")
+            return (kind, t.data_ptr(), str(t.dtype), None if valid is None else valid.data_ptr())
+        if kind == "lit":
+            return ("lit", type(tree[1]).__name__, tree[1])
+        return (kind,) + tuple(self._expr_key(c, n_a, n_b) for c in tree[1:])
+
+    def _pair_expr_aggregate(self, row_a, row_b, n: int, n_a: int, n_b: int, aggs):
+        """:meth:`pair_aggregate` with at least one ``("expr", tree)`` entry: ``giql_hip_pair_expr_agg_dev``."""
+        torch = _torch()
+        ok = (torch.int32, torch.int64, torch.float32, torch.float64)
+        types = {torch.int32: _lib.T_I32, torch.int64: _lib.T_I64, torch.float32: _lib.T_F32,
+                 torch.float64: _lib.T_F64}
+        nodes, keep_alive, progs = [], [], {}   # progs: tree key -> (first, count, can_float)
+        kernel, slot = [], []
+        for func, t, valid in aggs:
+            if func not in ("COUNT", "SUM", "MIN", "MAX", "AVG"):
+                raise ValueError(f"aggregate function {func!r}")
+            f = "SUM" if func == "AVG" else func
+            if isinstance(t, tuple):
+                if len(t) != 2 or t[0] != "expr":
+                    raise ValueError('an expression source is ("expr", tree)')
+                if valid is not None:
+                    raise ValueError("an expression source takes no validity column: its tree names them")
+                tkey = self._expr_key(t[1], n_a, n_b)
+                if tkey not in progs:
+                    first = len(nodes)
+                    self._flatten_expr(t[1], nodes, keep_alive)
+                    progs[tkey] = (first, len(nodes) - first, expr_can_float(t[1]))
+                flt = progs[tkey][2]
+                key = (f, "expr", tkey)
+                src = ("expr",) + progs[tkey]
+            else:
+                if t is None and func != "COUNT":
+                    raise ValueError(f"{func} needs a values tensor (only COUNT reads validity alone)")
+                if t is not None and (t.dtype not in ok or t.dim() != 1 or not t.is_contiguous()
+                                      or int(t.shape[0]) != n_b):
+                    raise ValueError("an aggregate column must be a contiguous 1-D int32/int64/float32/float64 tensor "
+                                     "with one value per row of the right table")
+                if valid is not None and (valid.dtype not in (torch.uint8, torch.bool) or valid.dim() != 1
+                                          or int(valid.shape[0]) != n_b or not valid.is_contiguous()):
+                    raise ValueError("validity must be a contiguous uint8/bool tensor of one entry per right row")
+                vkey = None if valid is None else valid.data_ptr()
+                key = (f, None, vkey, None) if f == "COUNT" else (f, t.data_ptr(), vkey, t.dtype)
+                flt = t is not None and t.is_floating_point()
+                src = ("col", None if f == "COUNT" else t, valid)
+            if key not in [k[0] for k in kernel]:
+                kernel.append((key, src, torch.empty(n_a, dtype=torch.float64 if flt and f != "COUNT" else torch.int64,
+                                                     device=self.device),
+                               torch.empty(n_a, dtype=torch.int64, device=self.device)))
+            slot.append([k[0] for k in kernel].index(key))
+        if len(nodes) > 256:
+            raise ValueError(f"a pair aggregate takes at most 256 expression nodes per call, got {len(nodes)}")
+        c_nodes = (_lib.COperand * max(len(nodes), 1))(*nodes)
+        c_aggs = (_lib.CPairExprAgg * max(len(kernel), 1))()
+        for j, (key, src, out, nn) in enumerate(kernel):
+            c_aggs[j].func = _lib.AGG_FUNCS[key[0]]
+            if src[0] == "expr":
+                c_aggs[j].first, c_aggs[j].count = src[1], src[2]
+                c_aggs[j].type = _lib.T_F64 if src[3] else _lib.T_I64
+            else:
+                t, valid = src[1], src[2]
+                c_aggs[j].type = _lib.T_I32 if t is None else types[t.dtype]
+                c_aggs[j].data = self._dev_ptr(t, "an aggregate column")
+                if t is not None and c_aggs[j].data is None:
+                    c_aggs[j].data = 1  # (an empty right table: never dereferenced)
+                c_aggs[j].valid = self._dev_ptr(valid, "a validity column")
+            c_aggs[j].out = out.data_ptr() if n_a else 1
+            c_aggs[j].out_nn = nn.data_ptr() if n_a else None
+        pairs = torch.empty(n_a, dtype=torch.int64, device=self.device)
+        _lib.check(self._L.giql_hip_pair_expr_agg_dev(
+            self._h, self._dev_ptr(row_a, "row_a", torch.int32), self._dev_ptr(row_b, "row_b", torch.int32), n,
+            n_a, n_b, c_nodes, len(nodes), c_aggs, len(kernel), pairs.data_ptr() if n_a else None, self._stream()))
+        res = []
+        for (func, _t, _v), j in zip(aggs, slot):
+            out, nn = kernel[j][2], kernel[j][3]
             if func == "AVG":
                 out = torch.where(nn > 0, out.double() / nn.double(), torch.zeros(n_a, dtype=torch.float64,
                                                                                   device=self.device))

@@ -1345,8 +1345,9 @@ def _routes_join_aggregates(plan: JoinPlan, right_types: dict, return_indices: b
     """Whether ``execute`` answers a plan through ``_execute_join_aggregates``: a plan lowered in the map shape
     (``join_aggregates``; shape.is_map_shape) -- INNER, or LEFT with ON residuals only, grouped by left-side columns,
     every projected column a key, 1..8 aggregates that are COUNT(*), COUNT(<right column>) of any type, or SUM / AVG /
-    MIN / MAX of a signed-integer or float32 / float64 right column (``right_types``: column -> Arrow type) -- asked
-    for as a table, on one device.  Anything else takes the path it takes without the flag."""
+    MIN / MAX of a signed-integer or float32 / float64 right column (``right_types``: column -> Arrow type), or any of
+    the five over an expression of the pair (side "x": the plan's expressions are exactly those such aggregates name)
+    -- asked for as a table, on one device.  Anything else takes the path it takes without the flag."""
     import pyarrow as pa
 
     from .shape import MAP_AGG_MAX, map_aggregate_ok
@@ -1357,14 +1358,17 @@ def _routes_join_aggregates(plan: JoinPlan, right_types: dict, return_indices: b
         return False
     if plan.kind == "LEFT" and any(r.clause != "on" for r in plan.residuals):
         return False
-    if not plan.group_by or not 1 <= len(plan.aggregates) <= MAP_AGG_MAX or plan.expressions:
+    if not plan.group_by or not 1 <= len(plan.aggregates) <= MAP_AGG_MAX:
+        return False
+    # expressions: only those that aggregates (side "x") refer to, and every one of them
+    if {int(a.column) for a in plan.aggregates if a.side == "x"} != set(range(len(plan.expressions))):
         return False
     if any(p.side != "l" or p.column == "*" or p.name not in plan.group_by for p in plan.projection):
         return False
     for a in plan.aggregates:
         if not map_aggregate_ok(a.func, a.side, a.distinct):
             return False
-        if a.side == "*":
+        if a.side in ("*", "x"):
             continue
         t = right_types.get(a.column)
         if t is None:
@@ -1388,18 +1392,103 @@ def _check_pair_int_sum(column: str, col, n_pairs: int) -> None:
                          "can overflow the int64 sum; cast the column to a float type")
 
 
+def expression_abs_bound(tree, column_info):
+    """An absolute bound of an integer expression tree (the plan's serialised form: ``[kind, value]`` leaves,
+    ``["fn", op, [children]]``) by interval arithmetic, or None where the tree can yield a float -- a float sum does not
+    wrap.  ``column_info(side, column) -> (max |value|, is_float)`` for the columns it reads.  ``+`` and ``-`` add the
+    bounds, ``*`` multiplies them, NEG / ABS keep theirs, LEAST / GREATEST / a CASE take their largest argument (a
+    CASE's condition does not count), a comparison or boolean is at most 1, NULL is 0; ``/`` is a float."""
+    if tree[0] != "fn":
+        kind, value = tree[0], tree[1]
+        if kind == "int":
+            return abs(int(value))
+        if kind == "float":
+            return None
+        if kind == "str":
+            return 0
+        bound, is_float = column_info(kind, value)
+        return None if is_float else int(bound)
+    op, kids = tree[1], tree[2]
+    if op == "null":
+        return 0
+    if op in ("=", "!=", "<", "<=", ">", ">=", "isnull", "notnull", "and", "or", "not"):
+        return 1
+    if op == "/":
+        return None
+    bounds = [expression_abs_bound(k, column_info) for k in (kids[1:] if op == "if" else kids)]
+    if any(b is None for b in bounds):
+        return None
+    if op in ("+", "-"):
+        return sum(bounds)
+    if op == "*":
+        out = 1
+        for b in bounds:
+            out *= b
+        return out
+    if op in ("neg", "abs", "least", "greatest", "if"):
+        return max(bounds)
+    raise ValueError(f"expression operator {op!r}")
+
+
+def check_pair_expr_int_sum(name: str, tree, column_info, n_inputs: int) -> None:
+    """SUM / AVG of an integer expression accumulate in int64: refuse, naming the aggregate, when ``n_inputs`` values
+    of magnitude up to the tree's bound (``expression_abs_bound``) could reach 2^63, instead of wrapping.  A tree that
+    can yield a float is exempt."""
+    bound = expression_abs_bound(tree, column_info)
+    if bound is not None and n_inputs * bound >= 2**63:
+        raise ValueError(f"SUM / AVG in aggregate {name!r}: {n_inputs} values of magnitude up to {bound} can overflow "
+                         "the int64 sum; make the expression a float (multiply by 1.0)")
+
+
+def _column_info(res: "_Residuals"):
+    """``column_info`` of ``expression_abs_bound`` over a plan's tables: (max |value| from the column's min / max,
+    is it a float column); a column that is no number (a string under a comparison) counts 0."""
+    import pyarrow as pa
+    import pyarrow.compute as pc
+
+    def info(side: str, column: str):
+        col = res._arrow(side, column)
+        if pa.types.is_floating(col.type):
+            return 0, True
+        if pa.types.is_boolean(col.type):
+            return 1, False
+        if not pa.types.is_integer(col.type):
+            return 0, False
+        mm = pc.min_max(col)
+        lo, hi = mm["min"].as_py(), mm["max"].as_py()
+        return (0 if lo is None else max(abs(lo), abs(hi))), False
+    return info
+
+
+#: how an aggregate over expression <index> is keyed among the partials of ``_combine_join_partials``, which knows
+#: right-table columns only (names beginning ``__giql_`` are the project's own)
+_X_COLUMN = "__giql_x{}"
+
+
 def _execute_join_aggregates(plan: JoinPlan, lt, rt, eng: HipEngine, pins: dict | None = None):
     """A map-shape plan (``_routes_join_aggregates``): the join's unpadded pairs, reduced per left row on the device
     (``HipEngine.pair_aggregate``: no gather per pair, nothing per pair comes to the host), then the per-row partials
     combined per distinct left key on the host over ``n_left`` rows (``_combine_join_partials``).  The pairs come from
     where the same join takes them without the flag: a pinned table's index (``_indexed_inner``) where one serves, else
     ``_spatial_join`` / ``_join_with_residuals``.  Returns the finished table, or None when the join yields 2^31 pairs
-    or more (the caller takes the other path, which joins again)."""
+    or more (the caller takes the other path, which joins again).
+
+    An aggregate over an expression (side "x"; the ``aggregate_expressions`` opt-in) goes to the same call as
+    ``("expr", tree)``: the value is computed at the pair inside the reduction, no per-pair array exists.  SUM / MIN /
+    MAX of it come back as int64 or float64 by the rule of the computed columns (``expr_can_float``).  Under a LEFT
+    plan SQL evaluates the expression on the padded row of a left row without a pair too -- LEAST / GREATEST skip the
+    NULLs, so ``SUM(LEAST(a.end, b.end) - GREATEST(a.start, b.start))`` of such a row is ``a.end - a.start``: those rows
+    get one value each from ``eval_exprs`` (right id -1 = the NULL row), folded in as a partial of one input."""
     import pyarrow as pa
     from dataclasses import replace
 
-    inner = replace(plan, kind="INNER", join_aggregates=False)   # ON residuals take part in matching, as an INNER join's
+    from .engine import expr_can_float
+
+    # (an aggregate over an expression plays no part in finding the pairs)
+    inner = replace(plan, kind="INNER", join_aggregates=False, expressions=(),
+                    aggregates=tuple(a for a in plan.aggregates if a.side != "x"))
     got = None
+    a = b = None
     if (plan.predicate == "intersects" and not plan.residuals and pins
             and any(p is not None and p.index for p in pins.values())):
         got = _indexed_inner(inner, lt, rt, pins, eng)   # (None: the index does not serve this pair of tables)
@@ -1418,12 +1507,25 @@ def _execute_join_aggregates(plan: JoinPlan, lt, rt, eng: HipEngine, pins: dict 
     n_pairs = int(ra.shape[0])
     if n_pairs >= 2**31:
         return None
-    res = _Residuals(plan, lt, rt, eng)
+    res = _Residuals(plan, lt, rt, eng, dev_sides={"l": a, "r": b})
     asked, slot, types = [], {}, {}   # the engine's aggregates, one per distinct (function, column); AVG asks for SUM
+    trees = {}                        # expression index -> the engine's tree
     for ag in plan.aggregates:
         if ag.side == "*":
             continue
         func = "SUM" if ag.func == "AVG" else ag.func
+        if ag.side == "x":            # equal (function, tree) are asked for once: equal trees share an index
+            k, column = int(ag.column), _X_COLUMN.format(ag.column)
+            if k not in trees:
+                trees[k] = res._spec(plan.expressions[k], where="aggregate")
+                types[column] = pa.float64() if expr_can_float(trees[k][1]) else pa.int64()
+            if func == "SUM":
+                unmatched = n_left if plan.kind == "LEFT" else 0     # (at most: every such row adds one input)
+                check_pair_expr_int_sum(ag.name, plan.expressions[k].value, _column_info(res), n_pairs + unmatched)
+            if (func, column) not in slot:
+                slot[(func, column)] = len(asked)
+                asked.append((func, trees[k]))
+            continue
         if (func, ag.column) in slot:
             continue
         col = res._arrow("r", ag.column)
@@ -1438,7 +1540,47 @@ def _execute_join_aggregates(plan: JoinPlan, lt, rt, eng: HipEngine, pins: dict 
         asked.append(entry)
     pairs, parts = eng.pair_aggregate(ra.contiguous(), rb.contiguous(), n_left, n_right, asked)
     partials = {key: (parts[j][0].cpu().numpy(), parts[j][1].cpu().numpy()) for key, j in slot.items()}
-    return _finish_grouped(_combine_join_partials(plan, lt, pairs.cpu().numpy(), partials, types), plan)
+    pairs = pairs.cpu().numpy()
+    if trees and plan.kind == "LEFT":
+        partials = _fold_unmatched_rows(partials, trees, pairs, n_left, n_right, eng)
+    # _combine_join_partials knows right-table columns: an aggregate over expression k reads "column" __giql_x<k>
+    combine = replace(plan, expressions=(), aggregates=tuple(
+        replace(a, side="r", column=_X_COLUMN.format(a.column)) if a.side == "x" else a for a in plan.aggregates))
+    return _finish_grouped(_combine_join_partials(combine, lt, pairs, partials, types), plan)
+
+
+def _fold_unmatched_rows(partials: dict, trees: dict, pairs: np.ndarray, n_left: int, n_right: int, eng: HipEngine):
+    """A LEFT map-shape plan's aggregates over expressions: every left row without a pair contributes the expression's
+    value on its padded row (right id -1: the NULL row) as a partial of ONE input -- the value and a non-NULL count of
+    1, or NULL and 0.  ``partials``: ``(function, __giql_x<k>) -> (values, non-NULL counts)`` among others; ``trees``:
+    ``k -> ("expr", tree)``."""
+    import torch
+
+    rows = np.flatnonzero(pairs == 0).astype(np.int32)
+    if not rows.size:
+        return partials
+    idx_a = torch.from_numpy(rows).to(eng.device)
+    order = sorted(trees)
+    outs = eng.eval_exprs([trees[k] for k in order], idx_a=idx_a, idx_b=torch.full_like(idx_a, -1), n_rows_a=n_left,
+                          n_rows_b=n_right)
+    padded = {_X_COLUMN.format(k): (v.cpu().numpy(), None if ok is None else ok.cpu().numpy()) for k, (v, ok) in zip(order, outs)}
+    return _fold_padded_values(partials, padded, rows)
+
+
+def _fold_padded_values(partials: dict, padded: dict, rows: np.ndarray) -> dict:
+    """``partials`` with the rows ``rows`` (no pair) of every aggregate over an expression set to one input each:
+    ``padded``: ``__giql_x<k> -> (values, valid or None)`` of those rows.  COUNT is 1 where the value is not NULL."""
+    out = dict(partials)
+    for (func, column), (vals, nn) in partials.items():
+        if column not in padded:
+            continue
+        v, ok = padded[column]
+        ok = np.ones(rows.size, np.int64) if ok is None else (ok != 0).astype(np.int64)
+        vals, nn = vals.copy(), nn.copy()
+        nn[rows] = ok
+        vals[rows] = ok if func == "COUNT" else np.where(ok != 0, v, 0).astype(vals.dtype)
+        out[(func, column)] = (vals, nn)
+    return out
 
 
 def _combine_join_partials(plan: JoinPlan, lt, pairs: np.ndarray, partials: dict, types: dict):
@@ -2138,10 +2280,11 @@ def _execute_sharded(plan: JoinPlan, lt, rt, ia, ib, n_chrom, devices, return_in
 def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, return_indices=False,
             device_projection: bool = True, devices=None, outer_joins: bool = False, row_predicates: bool = False,
             select_expressions: bool = False, merge_aggregates: bool = False, range_sets: bool = False,
-            string_aggregates: bool = False, join_aggregates: bool = False, disjoin_aggregates: bool = False):
+            string_aggregates: bool = False, join_aggregates: bool = False, disjoin_aggregates: bool = False,
+            aggregate_expressions: bool = False):
     """Run *plan* (a :class:`JoinPlan`, its string form, or a GIQL query string; ``outer_joins``,
     ``row_predicates``, ``select_expressions``, ``merge_aggregates``, ``string_aggregates``, ``range_sets``,
-    ``join_aggregates`` and ``disjoin_aggregates`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
+    ``join_aggregates``, ``aggregate_expressions`` and ``disjoin_aggregates`` as in :func:`giql_amd.transpile.build_plan`, for a query string) against ``tables``
     (``{name: pyarrow.Table | dict of arrays}``).
 
     Returns a ``pyarrow.Table`` with the plan's projected columns (bag semantics,
@@ -2169,7 +2312,8 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
                                      select_expressions=select_expressions, merge_aggregates=merge_aggregates,
                                      range_sets=range_sets, string_aggregates=string_aggregates,
                                      disjoin_aggregates=disjoin_aggregates)
-            plan = build_plan(query, giql_tables, join_aggregates=join_aggregates, **opts)
+            plan = build_plan(query, giql_tables, join_aggregates=join_aggregates,
+                              aggregate_expressions=aggregate_expressions, **opts)
             relower = lambda: build_plan(query, giql_tables, **opts)  # noqa: E731
     if not isinstance(plan, JoinPlan):
         raise ValueError("plan must be a JoinPlan, a plan string or a GIQL query")
@@ -2201,6 +2345,10 @@ def execute(plan, tables, engine: HipEngine | None = None, *, giql_tables=None, 
             got = _execute_join_aggregates(plan, lt, rt, eng, pins)
         if got is not None:
             return got
+        if any(a.side == "x" for a in plan.aggregates):
+            # no other path computes an aggregate over an expression
+            raise ValueError("an aggregate over an expression runs in the map shape only: on one device, as a table "
+                             "(not return_indices), over fewer than 2^31 pairs, a LEFT join without WHERE residuals")
         # outside the shape (a column type, return_indices, several devices) or 2^31 pairs and more: the query runs
         # -- or declines -- exactly as it does without the flag
         from dataclasses import replace

@@ -95,7 +95,8 @@ class Aggregate:
     relation, intersects_duckdb.py:1402-1644)."""
 
     func: str      # COUNT SUM MIN MAX AVG; beside MERGE also STRING_AGG
-    side: str      # "l" / "r", or "*" for COUNT(*)
+    side: str      # "l" / "r", or "*" for COUNT(*); "x": an expression over the pair, ``column`` its index into
+                   # JoinPlan.expressions as text (a map-shape plan lowered with the ``aggregate_expressions`` opt-in)
     column: str
     name: str      # output column name
     distinct: bool = False
@@ -180,7 +181,9 @@ class JoinPlan:
     # GREATEST(a.start, b.start) AS overlap_bp"), each an Operand("expr", tree) in the serialised form the residuals
     # use -- a searched CASE is ["fn", "if", [cond, then, else]], a missing ELSE ["fn", "null", []] -- evaluated per
     # result row by HipEngine.eval_exprs; a Projection("expr", "<index>", name) refers to one.  Only plans lowered with
-    # the ``select_expressions`` opt-in carry any; plan strings written before the field existed load with none
+    # the ``select_expressions`` opt-in carry any; plan strings written before the field existed load with none.
+    # A map-shape plan (``join_aggregates``) lowered with the ``aggregate_expressions`` opt-in keeps here the trees its
+    # aggregates of side "x" reduce (SUM(LEAST(a.end, b.end) - GREATEST(a.start, b.start))): no projection names them
     expressions: tuple[Operand, ...] = field(default_factory=tuple)
     # FILTER only: the literal range sets that HipEngine.range_set_any answers -- ANY over two or more ranges, or its
     # negation -- each one more conjunct beside the residuals (a single literal, ANY over one range, ALL and their
@@ -223,6 +226,9 @@ class JoinPlan:
             if rs.op not in RANGE_OPS or rs.quantifier not in RANGE_QUANTIFIERS or not rs.ranges:
                 raise ValueError(f"bad range set {rs.op!r} {rs.quantifier!r} over {len(rs.ranges)} ranges")
         for a in self.aggregates:
+            if a.side == "x" and not (self.join_aggregates and a.column.isdigit() and int(a.column) < len(self.expressions)):
+                raise ValueError(f"aggregate {a.name!r} names expression {a.column!r} of {len(self.expressions)} "
+                                 "(a map-shape plan's aggregate over an expression)")
             if (a.func == "STRING_AGG") != (a.separator is not None) or (a.func == "STRING_AGG" and self.kind != "MERGE"):
                 raise ValueError(f"aggregate {a.name!r}: STRING_AGG, and only STRING_AGG beside MERGE, carries a separator")
         for p in self.projection:

@@ -236,7 +236,8 @@ class SelItem:
     distance: tuple | None = None
     # a computed column (``select_expressions``): an operand term as the residuals' operands are -- ("col", ColRef) /
     # ("lit", v) / ("fn", op, [terms]), a searched CASE as ("fn", "if", [condition, then, else]) over a condition
-    # term (``case_term``), a missing ELSE as ("fn", "null", []); ``ref`` is None then and ``alias`` is set
+    # term (``case_term``), a missing ELSE as ("fn", "null", []); ``ref`` is None then and ``alias`` is set.  With
+    # ``func`` set too (``aggregate_expressions``): the argument of that aggregate, ``SUM(<expr>)``
     expr: tuple | None = None
 
 
@@ -281,6 +282,9 @@ class JoinShape:
     # opt-in: a grouped aggregate over a join in the map shape (is_map_shape) lowers to an INNER / LEFT plan marked
     # ``join_aggregates``, whose aggregates execute() computes per left row on the device (HipEngine.pair_aggregate)
     join_aggregates: bool = False
+    # opt-in, together with ``join_aggregates``: an aggregate of the map shape may take an expression over both tables
+    # (SelItem.func AND SelItem.expr set); a front end that does not parse them never sets both
+    aggregate_expressions: bool = False
 
 
 # ------------------------------------------------------------------ helpers
@@ -523,6 +527,34 @@ def expression_operand(it: SelItem, left: PlanSide, right: PlanSide) -> Operand:
     return op
 
 
+def aggregate_operand(it: SelItem, left: PlanSide, right: PlanSide) -> Operand:
+    """The argument of an aggregate over an expression (``aggregate_expressions``) bound to the two sides, as
+    ``expression_operand`` binds a computed column; every decline names the aggregate's own case."""
+    if holds_distance(it.expr):
+        raise decline("DISTANCE inside an aggregate over an expression")
+    if _string_valued(it.expr):
+        raise decline("aggregate over a string-valued expression")
+
+    def bind(o) -> Operand:
+        if o[0] == "lit":
+            v = o[1]
+            return Operand("str" if isinstance(v, str) else ("float" if isinstance(v, float) else "int"), v)
+        ref: ColRef = o[1]
+        if ref.star:
+            raise decline("star in an expression inside an aggregate")
+        return Operand(_side_of(ref, left, right, "an aggregate argument"), ref.column)
+
+    op = bind_expression(it.expr, bind)
+    if not operand_sides(op):
+        raise decline("aggregate over a constant expression")
+    nodes, depth = expression_cost(op)
+    if depth > MAX_EXPR_DEPTH:
+        raise decline(f"aggregate over an expression too deep for the kernel ({depth} values live, at most {MAX_EXPR_DEPTH})")
+    if nodes > MAX_EXPR_NODES:
+        raise decline(f"aggregate over an expression too large for one call ({nodes} nodes, at most {MAX_EXPR_NODES})")
+    return op
+
+
 def check_expression_sizes(residuals, kind: str) -> None:
     """Decline (never a run-time error) a condition whose arithmetic one select call cannot hold: an operand deeper
     than ``MAX_EXPR_DEPTH``, or more than ``MAX_EXPR_NODES`` nodes among the residuals ``execute()`` evaluates in
@@ -635,7 +667,7 @@ def resolve_count_projection(items, group_cols, left: PlanSide, right: PlanSide)
     return tuple(out)
 
 
-def _resolve_grouped(shape: JoinShape, left: PlanSide, right: PlanSide, left_only: bool):
+def _resolve_grouped(shape: JoinShape, left: PlanSide, right: PlanSide, left_only: bool, exprs_out: list | None = None):
     """Projection with plain aggregates and / or a GROUP BY: key columns + aggregates, finished on
     the projected table (the reference rebuilds them over the wrapper relation,
     intersects_duckdb.py:1402-1644).  Returns (projection, aggregates, group names)."""
@@ -661,7 +693,12 @@ def _resolve_grouped(shape: JoinShape, left: PlanSide, right: PlanSide, left_onl
             raise decline(f"aggregate {it.func}")
         if it.distinct and it.func != "COUNT":
             raise decline(f"{it.func}(DISTINCT ...)")
-        if ref is None:                       # COUNT(*)
+        if it.expr is not None:               # an aggregate over an expression: the tree goes to the plan's expressions
+            bound = aggregate_operand(it, left, right)
+            if bound not in exprs_out:
+                exprs_out.append(bound)
+            side, column = "x", str(exprs_out.index(bound))
+        elif ref is None:                     # COUNT(*)
             if it.func != "COUNT":
                 raise decline(f"{it.func}(*)")
             side, column = "*", "*"
@@ -806,9 +843,12 @@ def _is_qualified(ref, alias: str) -> bool:
 
 def map_aggregate_ok(func: str, side: str, distinct: bool) -> bool:
     """An aggregate the map shape computes per left row: ``COUNT(*)``, ``COUNT(<right column>)``, or SUM / AVG / MIN /
-    MAX of a right-side column, without DISTINCT (the column's type is execute()'s to check: the plan has no schema)."""
+    MAX of a right-side column, without DISTINCT (the column's type is execute()'s to check: the plan has no schema);
+    side "x": any of the five over an expression of the pair (the ``aggregate_expressions`` opt-in)."""
     if distinct:
         return False
+    if side == "x":     # an expression over the pair (``aggregate_expressions``): its type is the tree's
+        return func in ("COUNT", "SUM", "AVG", "MIN", "MAX")
     return (func == "COUNT" and side in ("*", "r")) or (func in ("SUM", "AVG", "MIN", "MAX") and side == "r")
 
 
@@ -827,7 +867,7 @@ def is_map_shape(shape: JoinShape, left: PlanSide, right: PlanSide) -> bool:
     keys = {g.column for g in shape.group_by}
     aggs = []
     for it in shape.items:
-        if it.distance is not None or it.expr is not None:
+        if it.distance is not None or (it.expr is not None and (it.func is None or not shape.aggregate_expressions)):
             return False
         if it.func is None:
             if not _is_qualified(it.ref, left.alias) or it.ref.count or it.ref.column not in keys:
@@ -835,7 +875,9 @@ def is_map_shape(shape: JoinShape, left: PlanSide, right: PlanSide) -> bool:
             continue
         if it.func not in AGG_FUNCS or not it.alias:
             return False
-        if it.ref is None:
+        if it.expr is not None:
+            side = "x"
+        elif it.ref is None:
             side = "*"
         elif _is_qualified(it.ref, right.alias):
             side = "r"
@@ -871,7 +913,10 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
         raise decline(f"{'count_overlaps / outer' if kind == 'LEFT' else kind} join with a DISTANCE in the SELECT list")
     if dist_items and (shape.group_by or shape.having or any(it.func is not None for it in items)):
         raise decline("DISTANCE in the SELECT list beside GROUP BY / HAVING / aggregates")
-    expr_items = [it for it in items if it.expr is not None]
+    if any(it.expr is not None and it.func is not None for it in items) and not map_shape:
+        raise decline("aggregate over an expression outside the map shape (an INNER join, or a LEFT join with its "
+                      "predicate in ON and no WHERE; GROUP BY qualified left-side columns; 1 to 8 aliased aggregates)")
+    expr_items = [it for it in items if it.expr is not None and it.func is None]
     if expr_items and (shape.group_by or shape.having or any(it.func is not None for it in items)):
         raise decline("expression in the SELECT list beside GROUP BY / HAVING / aggregates")
     if kind == "LEFT":
@@ -971,7 +1016,7 @@ def lower_join_shape(shape: JoinShape, tables: Tables) -> JoinPlan:
     # columns may share names, which a DISTINCT by output name cannot tell apart)
     stars = bool(expr_items) and kind in ("INNER", "LEFT") and not shape.distinct
     if grouped:
-        proj, aggs, groups, output = _resolve_grouped(shape, left, right, left_only)
+        proj, aggs, groups, output = _resolve_grouped(shape, left, right, left_only, exprs_out=exprs)
         visible_aggs = aggs
         aggs, having = _resolve_having(shape, proj, aggs, left, right, left_only)
         if not visible_aggs and not groups and aggs:

@@ -643,8 +643,55 @@ def _own_table_residuals(terms, own) -> list:
 _UNSUPPORTED_TAIL = ("GROUP", "ORDER", "HAVING", "LIMIT", "OFFSET", "UNION")
 
 
-def _parse_aggregate_call(p: _Parser, where: str):
-    """``FUNC([DISTINCT] <col> | *)`` at the cursor -> (func, distinct, ColRef | None)."""
+def _plain_aggregate_argument(p: _Parser) -> bool:
+    """Is the aggregate's argument at the cursor one column reference (``x`` / ``t.x`` / ``t.*``) and nothing more?"""
+    if p.peek().kind != "id":
+        return False
+    k = 3 if p.peek(1).kind == "punct" and p.peek(1).text == "." else 1
+    return p.peek(k).kind == "punct" and p.peek(k).text == ")"
+
+
+def _parse_aggregate_expression(p: _Parser, func: str, distinct: bool):
+    """The argument of an aggregate in the grammar of the computed columns (``aggregate_expressions``): ``+ - * /``,
+    unary minus, parentheses, LEAST / GREATEST / ABS, a searched CASE -> the operand term of ``SelItem.expr``."""
+    def no_boolean():
+        t = p.peek()
+        if (t.kind == "punct" and t.text in "=<>!") or (t.kind == "kw" and t.text in _BOOL_WORDS):
+            raise _decline("comparison or boolean as the value of an aggregate")
+
+    if p.at_kw("NOT"):
+        raise _decline("comparison or boolean as the value of an aggregate")
+    p.case_ok = True
+    try:
+        try:
+            term = _parse_operand(p)
+        except HipDeclined as exc:
+            if str(exc).startswith("function call in a join condition:"):    # (the operand parser's wording)
+                raise _decline("function call in an expression inside an aggregate") from None
+            raise
+        except ValueError:
+            no_boolean()    # "SUM((a.x > 1))": the operand parser met a comparison where it wanted ")"
+            raise
+        no_boolean()
+    finally:
+        p.case_ok = False
+    if p.peek().kind == "punct" and p.peek().text in "%|&^":
+        raise _decline(f"operator {p.peek().text!r} in an expression inside an aggregate")
+    if term[0] == "col":                    # a parenthesised plain column
+        return term
+    if term[0] == "distfn":
+        raise _decline("DISTANCE inside an aggregate")
+    if term[0] == "lit":
+        raise _decline(f"aggregate over a constant ({func}({term[1]!r}))")
+    if distinct:
+        raise _decline(f"{func}(DISTINCT <expression>)")
+    return term
+
+
+def _parse_aggregate_call(p: _Parser, where: str, expressions: bool = False):
+    """``FUNC([DISTINCT] <col> | *)`` at the cursor -> (func, distinct, ColRef | None, None); with ``expressions``
+    (the SELECT list under the ``aggregate_expressions`` opt-in) the argument may be an expression: (func, distinct,
+    None, operand term)."""
     func = p.peek().text.upper()
     if func == "DISTANCE":
         raise _decline(f"DISTANCE in {where}")
@@ -658,11 +705,17 @@ def _parse_aggregate_call(p: _Parser, where: str):
         distinct = True
     if _at_distance_call(p):
         raise _decline("DISTANCE inside an aggregate")
+    expr = None
     if p.at_punct("*"):
         p.next()
         ref = None
         if func != "COUNT" or distinct:
             raise _decline(f"{func}(*)")
+    elif expressions and not _plain_aggregate_argument(p):
+        term = _parse_aggregate_expression(p, func, distinct)
+        ref, expr = (term[1], None) if term[0] == "col" else (None, term)
+        if ref is not None and ref.star:
+            raise _decline("star inside an aggregate")
     else:
         if p.peek().kind != "id":
             raise _decline("aggregate over an expression")
@@ -674,10 +727,27 @@ def _parse_aggregate_call(p: _Parser, where: str):
     p.expect_punct(")")
     if p.peek().kind == "id" and not p.peek().quoted and p.peek().text.upper() in ("OVER", "FILTER"):
         raise _decline("window aggregate / FILTER clause")
-    return func, distinct, ref
+    return func, distinct, ref, expr
 
 
-def _parse_having(p: _Parser):
+def _aggregate_expression_elsewhere(p: _Parser, where: str) -> None:
+    """With the ``aggregate_expressions`` opt-in: an aggregate over an expression at the cursor, in a clause that takes
+    none (HAVING, ORDER BY), declines with a text of its own; anything else is left to the clause's own parser."""
+    t = p.peek()
+    if not (t.kind == "id" and not t.quoted and t.text.upper() in AGG_FUNCS and p.peek(1).kind == "punct"
+            and p.peek(1).text == "("):
+        return
+    save = p.i
+    try:
+        expr = _parse_aggregate_call(p, where, expressions=True)[3]
+    except (HipDeclined, ValueError):
+        expr = None
+    p.i = save
+    if expr is not None:
+        raise _decline(f"aggregate over an expression in {where} (alias it in the SELECT list and name the alias)")
+
+
+def _parse_having(p: _Parser, aggregate_expressions: bool = False):
     """A boolean condition over comparisons ``<operand> op <operand>`` (also BETWEEN / IN / IS NULL), an operand
     being a plain aggregate, a column (qualified key or output name) or a literal -> the terms of its conjunctive
     normal form (the reference hands HAVING to the engine verbatim, intersects_duckdb.py:1336-1400; sub-queries
@@ -688,7 +758,9 @@ def _parse_having(p: _Parser):
         if p.at_kw("EXISTS", "SELECT"):
             raise _decline("sub-query HAVING condition")
         if t.kind == "id" and not t.quoted and p.peek(1).kind == "punct" and p.peek(1).text == "(":
-            func, distinct, ref = _parse_aggregate_call(p, "HAVING")
+            if aggregate_expressions:
+                _aggregate_expression_elsewhere(p, "HAVING")
+            func, distinct, ref, _expr = _parse_aggregate_call(p, "HAVING")
             return ("agg", SelItem(ref, None, func, distinct))
         return _parse_atom(p)
 
@@ -698,7 +770,8 @@ def _parse_having(p: _Parser):
     return terms
 
 
-def _parse_projection(p: _Parser, select_expressions: bool = False) -> list[SelItem]:
+def _parse_projection(p: _Parser, select_expressions: bool = False,
+                      aggregate_expressions: bool = False) -> list[SelItem]:
     """SELECT list: qualified columns and plain aggregates ``FUNC([DISTINCT] <col>)`` / ``COUNT(*)``
     (the projections ``_resolve_projections`` can rebuild, intersects_duckdb.py:1402-1644); every
     other expression declines (#204, #205) -- unless ``select_expressions`` opts in to computed columns:
@@ -721,10 +794,11 @@ def _parse_projection(p: _Parser, select_expressions: bool = False) -> list[SelI
         func = None
         distinct = False
         distance = None
+        expr = None
         if _at_distance_call(p):
             ref, distance = None, _parse_distance_call(p)[1:]
         elif is_call:
-            func, distinct, ref = _parse_aggregate_call(p, "the SELECT list")
+            func, distinct, ref, expr = _parse_aggregate_call(p, "the SELECT list", expressions=aggregate_expressions)
             if ref is not None and func == "COUNT" and not distinct:
                 ref.count = True
         else:
@@ -739,7 +813,7 @@ def _parse_projection(p: _Parser, select_expressions: bool = False) -> list[SelI
             alias = p.next().text
         elif p.peek().kind == "id":
             alias = p.next().text
-        items.append(SelItem(ref, alias, func, distinct, distance))
+        items.append(SelItem(ref, alias, func, distinct, distance, expr))
         if p.at_punct(","):
             p.next()
             continue
@@ -1526,7 +1600,7 @@ def _lower_coverage_runs(p: _Parser, tbls: Tables, items) -> JoinPlan:
 def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predicates: bool = False,
                select_expressions: bool = False, merge_aggregates: bool = False, range_sets: bool = False,
                string_aggregates: bool = False, join_aggregates: bool = False,
-               disjoin_aggregates: bool = False) -> JoinPlan:
+               disjoin_aggregates: bool = False, aggregate_expressions: bool = False) -> JoinPlan:
     """Parse *giql* and lower the INTERSECTS / NEAREST join (or a CLUSTER / MERGE
     query) to a :class:`JoinPlan`.
 
@@ -1552,6 +1626,12 @@ def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predica
     an INNER / LEFT plan marked ``join_aggregates`` whose aggregates are computed per left row on the device.  The LEFT
     form needs no ``outer_joins``; a ``COUNT`` beside other aggregates, which declines without the flag, lowers too.  A
     query outside the shape lowers (or declines) exactly as it does without the flag.
+    ``aggregate_expressions=True``, together with ``join_aggregates=True`` (alone it changes nothing), lets an
+    aggregate of the map shape take an EXPRESSION over both tables -- ``SUM(LEAST(a.end, b.end) - GREATEST(a.start,
+    b.start)) AS total_overlap_bp`` -- in the grammar of the computed columns: the plan carries the tree in
+    ``expressions`` and the aggregate as ``Aggregate(func, "x", "<index>", name)``, reduced per left row on the device
+    without a per-pair value array.  DISTINCT, a constant, a string or boolean value, DISTANCE inside, HAVING / ORDER
+    BY over such an aggregate (name its alias instead) and any query outside the map shape decline.
     ``disjoin_aggregates=True`` opts in to the coverage profile of one table, answered from DISJOIN's breakpoints
     without its per-piece rows (``bedtools genomecov -bg``, Bioconductor ``disjoin()``): ``SELECT <disjoin_* columns>,
     COUNT(*) AS depth FROM DISJOIN(t) GROUP BY disjoin_chrom, disjoin_start, disjoin_end`` (``segments="depth"``),
@@ -1579,14 +1659,16 @@ def build_plan(giql: str, tables=None, *, outer_joins: bool = False, row_predica
                 raise _decline(f"expression in the SELECT list of {what}") from None
             raise
     plan = _lower(giql, tables, want_sql=False, outer_joins=outer_joins, row_predicates=row_predicates,
-                  select_expressions=select_expressions, join_aggregates=join_aggregates)
+                  select_expressions=select_expressions, join_aggregates=join_aggregates,
+                  aggregate_expressions=aggregate_expressions)
     assert isinstance(plan, JoinPlan)
     return plan
 
 
 def _lower(giql: str, tables, want_sql: bool, outer_joins: bool = False, row_predicates: bool = False,
-           select_expressions: bool = False, join_aggregates: bool = False):
+           select_expressions: bool = False, join_aggregates: bool = False, aggregate_expressions: bool = False):
     tbls = tables if isinstance(tables, Tables) else build_tables(tables)
+    agg_exprs = bool(aggregate_expressions) and bool(join_aggregates)   # (alone the opt-in changes nothing)
     p = _Parser(giql)
     if p.at_kw("WITH"):
         raise _decline("top-level WITH")
@@ -1607,7 +1689,7 @@ def _lower(giql: str, tables, want_sql: bool, outer_joins: bool = False, row_pre
         proj_text = _render(p.toks[proj_start:p.i])
         items = None
     else:
-        items = _parse_projection(p, select_expressions=bool(select_expressions))
+        items = _parse_projection(p, select_expressions=bool(select_expressions), aggregate_expressions=agg_exprs)
         proj_text = ""
     p.expect_kw("FROM")
     from_ref = p.table_ref()
@@ -1690,7 +1772,8 @@ def _lower(giql: str, tables, want_sql: bool, outer_joins: bool = False, row_pre
 
     shape = JoinShape(items=items, from_ref=from_ref, join_ref=join_ref, kind=kind, on_seen=on_seen, using=using,
                       distinct=distinct, outer_joins=bool(outer_joins), row_predicates=bool(row_predicates),
-                      select_expressions=bool(select_expressions), join_aggregates=bool(join_aggregates))
+                      select_expressions=bool(select_expressions), join_aggregates=bool(join_aggregates),
+                      aggregate_expressions=agg_exprs)
     if on_seen:
         if p.peek().kind not in ("id", "num", "str") and not p.at_punct("-") and not p.at_punct("(") \
                 and not p.at_kw("NOT"):
@@ -1717,11 +1800,13 @@ def _lower(giql: str, tables, want_sql: bool, outer_joins: bool = False, row_pre
             break
     if p.at_kw("HAVING"):
         p.next()
-        shape.having = _parse_having(p)
+        shape.having = _parse_having(p, aggregate_expressions=agg_exprs)
     if p.at_kw("ORDER"):
         p.next()
         p.expect_kw("BY")
         while True:
+            if agg_exprs:
+                _aggregate_expression_elsewhere(p, "ORDER BY")
             if p.peek().kind != "id":
                 raise _decline("ORDER BY expression")
             ref = p.colref()
@@ -1777,7 +1862,8 @@ def _render(toks: list[Tok]) -> str:
 def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins: bool = False,
               row_predicates: bool = False, select_expressions: bool = False,
               merge_aggregates: bool = False, range_sets: bool = False, string_aggregates: bool = False,
-              join_aggregates: bool = False, disjoin_aggregates: bool = False) -> str:
+              join_aggregates: bool = False, disjoin_aggregates: bool = False,
+              aggregate_expressions: bool = False) -> str:
     """Mirror of ``giql.transpile`` for this backend's path.
 
     ``dialect="hip"``: returns the plan string of the INTERSECTS / NEAREST join
@@ -1785,7 +1871,9 @@ def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins
     and ``row_predicates=True`` the per-row joins over CONTAINS / WITHIN / DISTANCE, ``select_expressions=True``
     computed columns such as ``overlap_bp`` in the SELECT list, ``merge_aggregates=True`` SUM / AVG / MIN / MAX /
     COUNT(col) beside MERGE, ``string_aggregates=True`` STRING_AGG(col, 'sep') beside MERGE, ``range_sets=True`` ANY / SOME / ALL over literal ranges and NOT over a literal predicate
-    in a single-table filter, ``join_aggregates=True`` grouped aggregates over a join in the map shape,
+    in a single-table filter, ``join_aggregates=True`` grouped aggregates over a join in the map shape (with
+    ``aggregate_expressions=True`` also over expressions such as ``SUM(LEAST(a.end, b.end) - GREATEST(a.start,
+    b.start))``),
     ``disjoin_aggregates=True`` the coverage profile (GROUP BY / COUNT(*) over DISJOIN and its run form)
     (:func:`build_plan`).  ``dialect=None``: returns SQL for the
     literal-range predicate (plumbing, BASELINE config 1).  Other dialects belong to
@@ -1795,7 +1883,8 @@ def transpile(giql: str, tables=None, *, dialect: str | None = None, outer_joins
         return build_plan(giql, tables, outer_joins=outer_joins, row_predicates=row_predicates,
                           select_expressions=select_expressions, merge_aggregates=merge_aggregates,
                           range_sets=range_sets, string_aggregates=string_aggregates,
-                          join_aggregates=join_aggregates, disjoin_aggregates=disjoin_aggregates).to_string()
+                          join_aggregates=join_aggregates, disjoin_aggregates=disjoin_aggregates,
+                          aggregate_expressions=aggregate_expressions).to_string()
     if dialect is None:
         return _lower(giql, tables, want_sql=True)
     raise ValueError(
