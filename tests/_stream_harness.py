@@ -15,6 +15,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import functools
+import glob
 import math
 import os
 import re
@@ -838,6 +839,27 @@ case(id="disjoin[reference]", symbols=("disjoin_plan", "disjoin_fill"), make=two
      ref=lambda inp: _disjoin_ref(inp, "reference"),
      run=lambda eng, bufs, _p: eng.disjoin(dside(bufs, "a"), dside(bufs, "b"), 4))
 
+
+# ---- coverage: DISJOIN's front (spans, events, one sort, two flag scans) and its own breakpoint rows, in one call
+def _coverage_ref(inp, runs=False, with_depth=True):
+    from _coverage_ref import sweep_arrays
+
+    rows = sweep_arrays(inp["a.chrom"], inp["a.start"], inp["a.end"], runs=runs)
+    return rows if with_depth else rows[:, :3].copy()
+
+
+def _coverage_canon(out, _inp):
+    return np.stack([np.asarray(x, np.int64) for x in out if x is not None], 1)
+
+
+case(id="coverage[depth]", symbols=("coverage",), make=one_table(), ref=_coverage_ref, canon=_coverage_canon,
+     run=lambda eng, bufs, _p: eng.coverage(dside(bufs, "a"), 5))
+case(id="coverage[runs]", symbols=("coverage",), make=one_table(), canon=_coverage_canon,
+     ref=lambda inp: _coverage_ref(inp, runs=True), run=lambda eng, bufs, _p: eng.coverage(dside(bufs, "a"), 5, runs=True))
+case(id="coverage[distinct]", symbols=("coverage",), make=one_table(), canon=_coverage_canon,
+     ref=lambda inp: _coverage_ref(inp, with_depth=False),
+     run=lambda eng, bufs, _p: eng.coverage(dside(bufs, "a"), 5, with_depth=False))
+
 # ---- the other joins
 case(id="contain_join[a contains b]", symbols=("contain_plan", "contain_fill"), make=two_tables("general"),
      ref=lambda inp: pairs_where(hside(inp, "a"), hside(inp, "b"), contains), canon=_pairs_canon,
@@ -1025,6 +1047,97 @@ def _eval_run(eng, bufs, _p):
 
 case(id="eval_exprs", symbols=("eval_expr",), make=_select_make, ref=_eval_ref, canon=_identity, run=_eval_run)
 
+# ---- aggregates over a join's pairs per left row: ids in, one row per A row out
+PAGG_NA, PAGG_NB, PAGG_PAIRS = 40, 600, 5000
+PAGG_AGGS = (("SUM", "vf"), ("AVG", "vf"), ("MIN", "vf"), ("MAX", "vf"), ("COUNT", "vf"), ("SUM", "vi"), ("MIN", "vi"),
+             ("MAX", "vi"))
+
+
+def _pagg_make(seed):
+    """~5,000 pairs of a 40 x 600 join (every id in range, none -1, some pairs twice), a nullable float64 and an int64
+    column of B, a nullable int64 column of A (read by the expression case only)."""
+    r = np.random.default_rng(seed)
+    return {"ra": r.integers(0, PAGG_NA, PAGG_PAIRS).astype(np.int32), "rb": r.integers(0, PAGG_NB, PAGG_PAIRS).astype(np.int32),
+            "vf": (r.normal(0, 1000, PAGG_NB) * r.choice([1e-3, 1.0, 1e3], PAGG_NB)).astype(np.float64),
+            "vf.valid": (r.random(PAGG_NB) >= 0.3).astype(np.uint8),
+            "vi": r.integers(-1_000_000, 1_000_000, PAGG_NB).astype(np.int64),
+            "ca": r.integers(-1000, 1000, PAGG_NA).astype(np.int64), "ca.valid": (r.random(PAGG_NA) >= 0.3).astype(np.uint8)}
+
+
+def _py_column(inp, name):
+    ok = inp[name + ".valid"] if name + ".valid" in inp else np.ones(inp[name].shape[0], np.uint8)
+    return [v.item() if k else None for v, k in zip(inp[name], ok)]
+
+
+def _pagg_leaf(func, want, inputs, flt):
+    """One aggregate of the reference as ``(values, non_null)``: NULL reads 0; a float SUM of k values carries
+    ``_agg_ref``'s bound k * 2^-52 * sum|x|, a float AVG that over k plus one ulp of the result; the rest is exact."""
+    import _pair_agg_ref as R
+
+    nn = np.array([sum(x is not None for x in xs) for xs in inputs], np.int64)
+    vals = [0 if w is None else w for w in want]
+    if func == "COUNT":
+        return np.array(vals, np.int64), nn
+    if not (flt or func == "AVG"):
+        return np.array(vals, np.int64), nn
+    bounds = []
+    for w, xs, k in zip(want, inputs, nn.tolist()):
+        bound = 0.0
+        if w is not None and flt and func in ("SUM", "AVG"):
+            bound = k * 2.0 ** -52 * R.abs_sum(xs)
+            bound = bound if func == "SUM" else bound / k + math.ulp(w)
+        bounds.append(bound)
+    return Approx(np.array(vals, np.float64), bounds), nn
+
+
+def _pagg_ref(inp):
+    import _pair_agg_ref as R
+
+    cols = {name: _py_column(inp, name) for name in ("vf", "vi")}
+    pairs, results = R.pair_aggregate(inp["ra"], inp["rb"], PAGG_NA, cols, [(f, c) for f, c in PAGG_AGGS])
+    mem = R.members(inp["ra"], inp["rb"], PAGG_NA)
+    return (np.array(pairs, np.int64),) + tuple(
+        _pagg_leaf(f, want, [[cols[c][b] for b in m] for m in mem], c == "vf") for (f, c), want in zip(PAGG_AGGS, results))
+
+
+def _pagg_canon(out, _inp):
+    pairs, results = out
+    return (np.asarray(pairs),) + tuple((np.asarray(v), np.asarray(nn)) for v, nn in results)
+
+
+def _pagg_run(eng, bufs, _p):
+    valid = {"vf": bufs["vf.valid"], "vi": None}
+    return eng.pair_aggregate(bufs["ra"], bufs["rb"], PAGG_NA, PAGG_NB, [(f, bufs[c], valid[c]) for f, c in PAGG_AGGS])
+
+
+case(id="pair_aggregate", symbols=("pair_agg",), make=_pagg_make, ref=_pagg_ref, canon=_pagg_canon, run=_pagg_run)
+
+PXAGG_FUNCS = ("SUM", "MAX", "COUNT", "AVG")     # of the tree ``a.ca + b.vi * 3`` (a NULL ``a.ca``: no input); then SUM(b.vf)
+
+
+def _pxagg_tree(inp):
+    return ("+", ("a", inp["ca"], inp["ca.valid"]), ("*", ("b", inp["vi"]), ("lit", 3)))
+
+
+def _pxagg_ref(inp):
+    import _pair_expr_agg_ref as X
+
+    tree = _pxagg_tree({k: np.asarray(v) for k, v in inp.items()})
+    plain = ("col", _py_column(inp, "vf"))
+    aggs = [(f, tree) for f in PXAGG_FUNCS] + [("SUM", plain)]
+    pairs, results, inputs = X.pair_expr_aggregate(inp["ra"], inp["rb"], PAGG_NA, aggs)
+    return (np.array(pairs, np.int64),) + tuple(
+        _pagg_leaf(f, want, xs, src is plain) for (f, src), want, xs in zip(aggs, results, inputs))
+
+
+def _pxagg_run(eng, bufs, _p):
+    tree = ("expr", _pxagg_tree(bufs))
+    return eng.pair_aggregate(bufs["ra"], bufs["rb"], PAGG_NA, PAGG_NB,
+                              [(f, tree) for f in PXAGG_FUNCS] + [("SUM", bufs["vf"], bufs["vf.valid"])])
+
+
+case(id="pair_aggregate[expr]", symbols=("pair_expr_agg",), make=_pagg_make, ref=_pxagg_ref, canon=_pagg_canon, run=_pxagg_run)
+
 RANGE_SETS = [("intersects", [0, 1, 3], [40_000, 90_000, 70_000], [10_000, 60_000, 65_000]),      # (op, codes, hi, lo)
               ("within", [0, 2], [20_000, 0], [21_000, 50_000]),
               ("contains", [1, 4], [30_020, 5_010], [30_030, 5_015])]
@@ -1160,6 +1273,8 @@ case(id="inner_join[wide]", symbols=("chrom_spans", "inner_plan", "inner_fill"),
 case(id="merge_agg[wide]", symbols=("chrom_spans", "merge_agg"), make=_wide_make, canon=_agg_canon,
      ref=lambda inp: _agg_ref({k: v for k, v in inp.items() if not k.startswith("vf")}, 0),
      run=lambda eng, bufs, _p: eng.merge_agg(dside(bufs, "a"), 2, 0, [(f, bufs["vi"], bufs["vi.valid"]) for f in AGG_FUNCS]))
+case(id="coverage[wide]", symbols=("chrom_spans", "coverage"), make=_wide_make, ref=_coverage_ref, canon=_coverage_canon,
+     run=lambda eng, bufs, _p: eng.coverage(dside(bufs, "a"), 2))      # (one call per chromosome group, then wide.merge)
 
 
 # ---------------------------------------------------------------------------------------------- the ABI's stream entry points
@@ -1167,12 +1282,24 @@ case(id="merge_agg[wide]", symbols=("chrom_spans", "merge_agg"), make=_wide_make
 NO_CHECKABLE_OUTPUT = ("copy_probe", "stream_probe")
 
 
+def abi_symbols():
+    """Every symbol ``giql_amd/_lib.py`` binds: its module-level lists named ``SYMBOLS`` or ``..._SYMBOLS``, in the
+    order the module defines them -- found by name, so that the list of the next extension header is one of them
+    without an edit here.  The completeness gates of tests/test_streams_gpu.py and tests/test_plan_lifetime_gpu.py
+    both run over this."""
+    from giql_amd import _lib
+
+    lists = [v for k, v in vars(_lib).items() if (k == "SYMBOLS" or k.endswith("_SYMBOLS")) and isinstance(v, (list, tuple))]
+    assert lists and all(isinstance(s, str) and s.startswith("giql_hip_") for symbols in lists for s in symbols)
+    return [s for symbols in lists for s in symbols]
+
+
 def stream_entry_points():
-    """Every function the three headers declare with a ``void* stream`` parameter, without the ``giql_hip_`` prefix
-    and the ``_dev`` suffix (``_lib.py``'s prototypes are lists of ctypes types: the headers name the parameter)."""
+    """Every function a header ``include/giql_hip*.h`` declares with a ``void* stream`` parameter, under its full
+    name (``_lib.py``'s prototypes are lists of ctypes types: the headers name the parameter)."""
     out = []
-    for name in ("giql_hip.h", "giql_hip_range_sets.h", "giql_hip_string_agg.h"):
-        with open(os.path.join(os.path.dirname(HERE), "include", name)) as f:
+    for path in sorted(glob.glob(os.path.join(os.path.dirname(HERE), "include", "giql_hip*.h"))):
+        with open(path) as f:
             text = re.sub(r"/\*.*?\*/", "", re.sub(r"//[^\n]*", "", f.read()), flags=re.S)
         for m in re.finditer(r"\b(giql_hip_\w+)\s*\(([^;{]*)\)\s*;", text):
             if re.search(r"\bvoid\s*\*\s*stream\b", m.group(2)):

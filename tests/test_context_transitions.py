@@ -12,11 +12,13 @@ was found by a long random soak.  So here:
   input classes (self-loops included): every ordered pair (X, Y) is a call on Y right after the context's last call
   on X.  Each visit runs the family twice; the second run must reach the path its class names (``SIGNATURES``).
   The ``row_pred`` family is SEMI / ANTI / COUNT over CONTAINS, WITHIN and DISTANCE and the within-distance join; the
-  ``one_table`` family is CLUSTER, MERGE, MERGE with aggregates and MERGE with STRING_AGG over the class's B table,
-  against the vectorised reference of ``tests/_one_table_ref.py``.
-* Walk 2: one context, all sixteen operators, DISJOIN's three and CONTAINS' three in a shuffled order per visit, with
-  ``select`` / ``take_utf8`` / a plan of another operator / a call of the one-table family put between some plans and
-  their fill -- which must then refuse (``GIQL_ERR_STATE``): those calls reuse the workspace the plan lives in.
+  ``one_table`` family is CLUSTER, MERGE, MERGE with aggregates, MERGE with STRING_AGG and coverage (depth rows, then
+  runs) over the class's B table, against the vectorised references of ``tests/_one_table_ref.py`` and
+  ``tests/_coverage_ref.py``.
+* Walk 2: one context, all seventeen operators, DISJOIN's three, CONTAINS' three and the two pair aggregates (over
+  columns, over a per-pair expression) in a shuffled order per visit, with ``select`` / ``take_utf8`` / a plan of another
+  operator / a pair aggregate / a call of the one-table family put between some plans and their fill -- which must then
+  refuse (``GIQL_ERR_STATE``), as their columns of tests/test_plan_lifetime_gpu.py say: all of them begin a call.
 * DISJOIN (self mode, reference mode, plan + fill through the raw ABI) walks the classes on which its path can
   differ, against the brute force of ``tests/_disjoin_ref.py``; its plan lives in the same workspace, and the
   context keeps one plan at a time (``ctx->kept``; ``tests/test_plan_lifetime_gpu.py`` has the rule cell by cell).
@@ -170,12 +172,12 @@ WIDTH_FAMILIES = ("row", "nearest")   # sorts on the tight span: every settled c
 # density before it sorts -- but the statistics name the side sorted LAST, and COUNT over WITHIN sorts the small left
 # table last (it is the inner side of the CONTAINS plan): its settled calls report A's form, not the width B's density
 # asks for, so the family is not one of these)
-# (the ``one_table`` family -- CLUSTER, MERGE and its aggregates -- is not one either: cluster_front sorts before anything
-# of its own call is read back, on ``guess.last_span`` as the previous call left it, and its callers end in
-# collect_spans and ``stats.span`` without note_span -- they read the density and never set it, as DISJOIN does.  A
-# context that only ever ran this family keeps the fresh context's guess (a human-genome-sized axis), under which
-# every class here is sparse: four passes on every call, asserted in Walk 1; the widths are met in Walk 2, after other
-# operators' spans, and forced one by one in tests/test_one_table_paths.py)
+# (the ``one_table`` family -- CLUSTER, MERGE and its aggregates, coverage -- is not one either: cluster_front and
+# coverage's front sort before anything of their own call is read back, on ``guess.last_span`` as the previous call left
+# it, and end in collect_spans and ``stats.span`` without note_span -- they read the density and never set it, as
+# DISJOIN does.  A context that only ever ran this family keeps the fresh context's guess (a human-genome-sized axis),
+# under which every class here is sparse: four passes on every call, asserted in Walk 1; the widths are met in Walk 2,
+# after other operators' spans, and forced one by one in tests/test_one_table_paths.py)
 
 
 @functools.lru_cache(maxsize=None)
@@ -775,7 +777,119 @@ def op_merge_str(eng, name, log, fam, rnd):
     assert all(g.shape == w.shape and torch.equal(g, w) for g, w in zip(out[4], answers["str"])), (name, "merge_str")
 
 
-ONE_TABLE_OPS = [op_cluster, op_merge, op_merge_agg, op_merge_str]
+# ---- coverage over the class's B (raw coordinates, like the rest of the family): DISJOIN's front -- spans, 2n events,
+# ONE sort by start, two flag scans -- in the workspace every other call carves, then its own breakpoint rows.  Like
+# DISJOIN and the four operators above it sorts on the density another call left (``guess.last_span``) and leaves it as
+# it found it: giql_hip_coverage_dev_impl ends in collect_spans and ``stats.span`` without note_span, and DESIGN.md says
+# so.  Truth = the vectorised sweep of tests/_coverage_ref.py (held to the row-by-row one and to the sqlite-minted
+# golden in tests/test_coverage.py), once per class and form, kept on the device.
+@functools.lru_cache(maxsize=None)
+def want_coverage(name, runs):
+    from _coverage_ref import sweep_arrays
+
+    _a, b, _nch, _da, _db = resident(name)
+    rows = sweep_arrays(b.chrom, b.start, b.end, runs=runs)
+    assert 0 < rows.shape[0] < 2 * b.n
+    return [torch.from_numpy(np.ascontiguousarray(rows[:, k]).astype(np.int64 if k == 3 else np.int32)).to("cuda:0")
+            for k in range(4)]
+
+
+def op_coverage(eng, name, log, fam, rnd):
+    """Depth rows in round 1, runs in round 2.  On ``irregular`` a table with inverted rows is refused first, naming the
+    table; the call that follows on the same context must be right."""
+    _a, _b, nch, _da, db = resident(name)
+    runs = rnd == 2
+    if name == "irregular":
+        with pytest.raises(ValueError, match="the target has a row with start > end"):
+            eng.coverage(_inverted_raw(), nch, runs=runs)
+    out = eng.coverage(db, nch, runs=runs)
+    log.add(eng, fam, name, rnd, "coverage")
+    want = want_coverage(name, runs)
+    assert all(g.dtype == w.dtype and g.shape == w.shape and torch.equal(g, w) for g, w in zip(out, want)), (name, "coverage", runs)
+    assert log.calls[-1][4]["n_out"] == want[0].shape[0], (name, "coverage rows")
+
+
+ONE_TABLE_OPS = [op_cluster, op_merge, op_merge_agg, op_merge_str, op_coverage]
+
+
+# ---- the aggregates over a join's pairs per left row, over columns and over a per-pair expression.  They take ids, not
+# tables: pair_agg_impl reads and writes no guess (its sorts are run_sort with as many passes as the ids have digits,
+# whatever the context's sort switches and density say), so they have no Walk 1 of their own -- what they share with the
+# rest is the workspace (claim_arena), the scans' status words and the plan the context keeps.  Their pairs are the
+# class's own INNER join, sorted, at most PAIR_AGG_MAX_PAIRS of them from the front (every left row of the prefix but
+# the last keeps all its pairs), handed over in a shuffled order; truth = tests/_pair_agg_ref.py and
+# tests/_pair_expr_agg_ref.py on the same prefix, with the float SUM bound of tests/_stream_harness.py.
+PAIR_AGG_MAX_PAIRS = 50_000
+PAIR_AGGS = (("SUM", "vf"), ("AVG", "vf"), ("MIN", "vf"), ("MAX", "vf"), ("COUNT", "vf"), ("SUM", "vi"), ("MAX", "vi"))
+PAIR_EXPR_FUNCS = ("SUM", "MIN", "COUNT")      # of ``a.ca + b.vi * 3``; beside them SUM(b.vf)
+
+
+@functools.lru_cache(maxsize=None)
+def pair_agg_case(name):
+    """``(device inputs, host inputs)`` of the class: the pair prefix and the columns the aggregates read."""
+    a, b, _nch, _da, _db = resident(name)
+    r = np.random.default_rng(7500 + NAMES.index(name))
+    pairs = want(name, "pairs")[:PAIR_AGG_MAX_PAIRS]
+    pairs = pairs[r.permutation(pairs.shape[0])]
+    host = {"ra": pairs[:, 0].astype(np.int32), "rb": pairs[:, 1].astype(np.int32),
+            "vf": r.normal(0, 1000, b.n) * r.choice([1e-3, 1.0, 1e3], b.n), "vf.valid": (r.random(b.n) >= 0.3).astype(np.uint8),
+            "vi": r.integers(-1_000_000, 1_000_000, b.n).astype(np.int64),
+            "ca": r.integers(-1000, 1000, a.n).astype(np.int64), "ca.valid": (r.random(a.n) >= 0.3).astype(np.uint8)}
+    assert host["ra"].shape[0] > 0
+    return {k: torch.from_numpy(np.ascontiguousarray(v)).to("cuda:0") for k, v in host.items()}, host
+
+
+@functools.lru_cache(maxsize=None)
+def want_pair_agg(name, expr):
+    import _pair_agg_ref as R
+    import _pair_expr_agg_ref as X
+    import _stream_harness as H
+
+    a = resident(name)[0]
+    _dev_in, host = pair_agg_case(name)
+    vf, vi = H._py_column(host, "vf"), H._py_column(host, "vi")
+    if not expr:
+        cols = {"vf": vf, "vi": vi}
+        pairs, results = R.pair_aggregate(host["ra"], host["rb"], a.n, cols, list(PAIR_AGGS))
+        mem = R.members(host["ra"], host["rb"], a.n)
+        leaves = [H._pagg_leaf(f, w, [[cols[c][j] for j in m] for m in mem], c == "vf") for (f, c), w in zip(PAIR_AGGS, results)]
+    else:
+        tree, plain = _pair_tree(host), ("col", vf)
+        aggs = [(f, tree) for f in PAIR_EXPR_FUNCS] + [("SUM", plain)]
+        pairs, results, inputs = X.pair_expr_aggregate(host["ra"], host["rb"], a.n, aggs)
+        leaves = [H._pagg_leaf(f, w, xs, src is plain) for (f, src), w, xs in zip(aggs, results, inputs)]
+    return (np.array(pairs, np.int64),) + tuple(leaves)
+
+
+def _pair_tree(cols):
+    return ("+", ("a", cols["ca"], cols["ca.valid"]), ("*", ("b", cols["vi"]), ("lit", 3)))
+
+
+def _pair_agg_call(eng, name, log, fam, rnd, expr):
+    import _stream_harness as H
+
+    a, b, _nch, _da, _db = resident(name)
+    d, _host = pair_agg_case(name)
+    if expr:
+        aggs = [(f, ("expr", _pair_tree(d))) for f in PAIR_EXPR_FUNCS] + [("SUM", d["vf"], d["vf.valid"])]
+    else:
+        aggs = [(f, d[c], d["vf.valid"] if c == "vf" else None) for f, c in PAIR_AGGS]
+    pairs, results = eng.pair_aggregate(d["ra"], d["rb"], a.n, b.n, aggs)
+    what = "pair_expr_agg" if expr else "pair_agg"
+    log.add(eng, fam, name, rnd, what)
+    got = (pairs.cpu().numpy(),) + tuple((v.cpu().numpy(), nn.cpu().numpy()) for v, nn in results)
+    assert H.same(got, want_pair_agg(name, expr)), (name, what)
+
+
+def op_pair_agg(eng, name, log, fam, rnd):
+    _pair_agg_call(eng, name, log, fam, rnd, False)
+
+
+def op_pair_expr_agg(eng, name, log, fam, rnd):
+    _pair_agg_call(eng, name, log, fam, rnd, True)
+
+
+PAIR_AGG_OPS = [op_pair_agg, op_pair_expr_agg]      # the ``pair_agg`` family: Walk 2 and the intruders only (above)
 FAMILIES = {
     "inner": [op_inner_join, op_into_exact, op_into_short, op_into_ample, op_plan_fill],
     "row": [op_semi, op_anti, op_count],
@@ -785,7 +899,7 @@ FAMILIES = {
     "row_pred": [op_semi_pred, op_count_pred, op_window_join],
     "one_table": ONE_TABLE_OPS,
 }
-ALL_OPS = [op for fam, ops in FAMILIES.items() if fam != "row_pred" for op in ops]   # (Walk 2 and Leg 3: the sixteen)
+ALL_OPS = [op for fam, ops in FAMILIES.items() if fam != "row_pred" for op in ops]   # (Walk 2 and Leg 3: the seventeen)
 
 
 def _check_signature(log, name):
@@ -844,6 +958,15 @@ def test_walk_every_ordered_pair_of_classes(monkeypatch, family):
         assert not any(c[4]["sort_local"] or c[4]["sort_resorted"] for c in log.calls)
         refused = [k for k, c in enumerate(log.calls) if c[1] == "irregular" and c[3] == "cluster"]
         assert len(refused) == 2 * len(NAMES)       # each behind a refused CLUSTER of inverted rows, each right
+        # coverage is one of the family in this, too ("reads the context's density guess like DISJOIN and
+        # never sets it"): the operator that runs right after it -- CLUSTER of the same class, or of the next one on
+        # every ordered pair of classes -- sorted in four passes (above) and was right (asserted where it ran)
+        after = {(p[1], c[1]) for p, c in zip(log.calls, log.calls[1:]) if p[3] == "coverage"}
+        assert all(c[3] == "cluster" for p, c in zip(log.calls, log.calls[1:]) if p[3] == "coverage")
+        assert after == {(x, y) for x in NAMES for y in NAMES}, "a class pair without a call right after coverage"
+        cov = [c for c in log.calls if c[3] == "coverage"]
+        assert len(cov) == 2 * (len(NAMES) ** 2 + 1) and all(c[4]["span"] > 0 for c in cov)
+        assert len([c for c in cov if c[1] == "irregular"]) == 2 * len(NAMES)      # each behind a refused coverage call
 
 
 @pytest.mark.gpu
@@ -939,10 +1062,10 @@ def _intrude_contain_plan(eng, name):
 
 
 def _intrude_one_table(op):
-    """A call of the one-table family between a plan and its fill: every one of its entry points begins a call and
-    carves the workspace anew, so whatever plan the context keeps is dropped (the cells ``cluster``, ``merge``,
-    ``merge_agg`` of tests/test_plan_lifetime_gpu.py: all dropped; ``giql_hip_merge_str_dev``:
-    tests/test_string_agg_gpu.py::test_merge_str_drops_a_plan_the_context_keeps)."""
+    """A call of the one-table family, or a pair aggregate, between a plan and its fill: every one of their entry points
+    begins a call and carves the workspace anew, so whatever plan the context keeps is dropped (the columns ``cluster``,
+    ``merge``, ``merge_agg``, ``merge_str``, ``coverage``, ``pair_agg`` and ``pair_expr_agg`` of
+    tests/test_plan_lifetime_gpu.py: all dropped)."""
     def intruder(eng, name):
         op(eng, name, Log(), "intruder", 1)
     intruder.__name__ = "_intrude_" + op.__name__[3:]
@@ -951,24 +1074,25 @@ def _intrude_one_table(op):
 
 INTRUDERS = {"select": _intrude_select, "take_utf8": _intrude_take_utf8, "inner_plan": _intrude_inner_plan,
              "disjoin_plan": _intrude_disjoin_plan, "contain_plan": _intrude_contain_plan, None: None,
-             **{op.__name__[3:]: _intrude_one_table(op) for op in ONE_TABLE_OPS}}
-ONE_TABLE_INTRUDERS = tuple(op.__name__[3:] for op in ONE_TABLE_OPS)      # cluster, merge, merge_agg, merge_str
-MIXED_OPS = ALL_OPS + DISJOIN_OPS + CONTAIN_OPS
+             **{op.__name__[3:]: _intrude_one_table(op) for op in ONE_TABLE_OPS + PAIR_AGG_OPS}}
+ONE_TABLE_INTRUDERS = tuple(op.__name__[3:] for op in ONE_TABLE_OPS)      # cluster, merge, merge_agg, merge_str, coverage
+PAIR_AGG_INTRUDERS = tuple(op.__name__[3:] for op in PAIR_AGG_OPS)        # pair_agg, pair_expr_agg
+MIXED_OPS = ALL_OPS + DISJOIN_OPS + CONTAIN_OPS + PAIR_AGG_OPS
 
 
-def _which_intruder(r, others, turn, met):
+def _which_intruder(others, turn, met):
     """What comes between the ``turn``-th plan of a kind and its fill: every third time a call of the one-table family,
-    its four operators in turn (noted in ``met``); else one of ``others``."""
-    if turn % 3 != 2:
-        return others[int(r.integers(0, len(others)))]
+    its five operators in turn (noted in ``met``); else one of ``others``, in turn."""
+    if turn % 3 != 2:       # in turn, too: seven choices over the twenty such plans of a kind (a draw missed some)
+        return others[(turn - turn // 3) % len(others)]
     met.append(ONE_TABLE_INTRUDERS[turn // 3 % len(ONE_TABLE_INTRUDERS)])
     return met[-1]
 
 
 PLAN_OPS = {   # a plan + fill operator -> (the plan's kind, what may come between the two besides a one-table call)
-    op_plan_fill: ("inner", ("select", "take_utf8", None, "disjoin_plan", "contain_plan")),
-    op_disjoin_plan_fill: ("disjoin", ("select", "take_utf8", "inner_plan", None, "contain_plan")),
-    op_contain_plan_fill: ("contain", ("select", "take_utf8", "inner_plan", "disjoin_plan", None)),
+    op_plan_fill: ("inner", ("select", "take_utf8", None, "disjoin_plan", "contain_plan") + PAIR_AGG_INTRUDERS),
+    op_disjoin_plan_fill: ("disjoin", ("select", "take_utf8", "inner_plan", None, "contain_plan") + PAIR_AGG_INTRUDERS),
+    op_contain_plan_fill: ("contain", ("select", "take_utf8", "inner_plan", "disjoin_plan", None) + PAIR_AGG_INTRUDERS),
 }
 
 
@@ -985,7 +1109,7 @@ def mixed_schedule():
             op, which = MIXED_OPS[k], None
             if op in PLAN_OPS:
                 kind, others = PLAN_OPS[op]
-                which = _which_intruder(r, others, turns[kind], [])
+                which = _which_intruder(others, turns[kind], [])
                 turns[kind] += 1
             out.append((NAMES[v], op, which))
     return out
@@ -1002,13 +1126,15 @@ def interruptions(schedule):
 
 
 def test_mixed_schedule_meets_every_interruption():
-    """CPU: every plan kind is interrupted by every call that can drop it -- the four one-table operators among them --
-    and every operator runs on every class."""
+    """CPU: every plan kind is interrupted by every call that can drop it -- the five one-table operators and the two
+    pair aggregates among them -- and every operator runs on every class."""
     met = interruptions(mixed_schedule())
     for _kind, others in PLAN_OPS.values():
         assert all(met[_kind].get(w, 0) > 0 for w in others if w is not None), (_kind, met[_kind])
         assert all(met[_kind].get(w, 0) > 0 for w in ONE_TABLE_INTRUDERS), (_kind, met[_kind])
     assert {(name, op) for name, op, _w in mixed_schedule()} == {(name, op) for name in NAMES for op in MIXED_OPS}
+    assert "coverage" in ONE_TABLE_INTRUDERS and set(PAIR_AGG_INTRUDERS) == {"pair_agg", "pair_expr_agg"}
+    assert len(ALL_OPS) == 17 and len(MIXED_OPS) == 17 + 3 + 3 + 2
 
 
 @pytest.mark.gpu
@@ -1040,14 +1166,26 @@ def test_walk_mixed_operators_with_interrupted_plans(monkeypatch):
     assert all(v > 0 for v in ct_interrupted.values()) and inner_by_contain > 0
     # DISJOIN takes its bucket width from the span another operator left on the context: both sort forms were met
     assert any(st["sort_local"] for st in dj) and any(not st["sort_local"] for st in dj)
-    # every plan kind was dropped by each of the four one-table operators (the refusal is asserted where it happens)
+    # every plan kind was dropped by each of the five one-table operators (the refusal is asserted where it happens)
     assert all(v > 0 for kind in by_one_table.values() for v in kind.values()), by_one_table
+    # ... and by both pair aggregates
+    by_pair_agg = {kind: {w: met[kind].get(w, 0) for w in PAIR_AGG_INTRUDERS} for kind in met}
+    print(f"[mixed] plans interrupted by a pair aggregate: {by_pair_agg}")
+    assert all(v > 0 for kind in by_pair_agg.values() for v in kind.values()), by_pair_agg
+    # both ran on every class, in the shuffled order (their results are asserted where they ran)
+    assert {(c[1], c[3]) for c in log.calls if c[3] in PAIR_AGG_INTRUDERS} == {(x, w) for x in NAMES for w in PAIR_AGG_INTRUDERS}
     # ... which take their bucket width from the span another operator left, too: four passes and narrow buckets
     ot = [c[4] for c in log.calls if c[3] in ("cluster", "merge", "merge_agg")]
     ot_forms = sorted({(st["sort_local"], st["bucket_bits"] if st["sort_local"] else None) for st in ot}, key=str)
     print(f"[mixed] one-table (three-stage sort, bucket bits) seen: {ot_forms}")
     assert any(not st["sort_local"] for st in ot) and {st["bucket_bits"] for st in ot if st["sort_local"]} & {13, 14, 15}
     assert not any(st["sort_resorted"] for st in ot)
+    # coverage sorts 2n events on the span another operator left, like DISJOIN: four passes and narrow buckets were both met
+    cov = [c[4] for c in log.calls if c[3] == "coverage"]
+    cov_forms = sorted({(st["sort_local"], st["bucket_bits"] if st["sort_local"] else None) for st in cov}, key=str)
+    print(f"[mixed] coverage (three-stage sort, bucket bits) seen: {cov_forms}")
+    assert any(not st["sort_local"] for st in cov) and {st["bucket_bits"] for st in cov if st["sort_local"]} & {13, 14, 15}
+    assert not any(st["sort_resorted"] for st in cov)
 
 
 # ---------------------------------------------------------------- Leg 3: the sticky four-pass fallback

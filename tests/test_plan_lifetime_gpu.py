@@ -2,8 +2,9 @@
 
 A context keeps at most one plan -- INNER (the within-distance plan is one), DISJOIN or CONTAINS -- between the plan
 call and its fill.  The rule: the plan is consumed by its own fill and export entry points until the next call on
-the context that BEGINS A CALL; five calls that use no workspace (distance, take, take_utf8_fill, mark, segment_sum)
-keep an INNER or DISJOIN plan; calls that launch nothing keep every plan.  Whether a call that begins a call then
+the context that BEGINS A CALL; six calls that use no workspace (distance, take, take_utf8_fill, mark, segment_sum and
+concat_utf8_fill, STRING_AGG's byte fill, which include/giql_hip_string_agg.h adds to the five of giql_hip.h) keep an
+INNER or DISJOIN plan; calls that launch nothing keep every plan.  Whether a call that begins a call then
 returns at once -- an empty side, no candidates, nothing to do -- makes no difference: it has dropped the plan.
 
 ``TABLE`` below is that rule written out: one line per entry point of the ABI that takes a context (and per form of
@@ -41,7 +42,7 @@ ROWS = ("INNER", "WINDOW", "DISJOIN", "CONTAINS")
 
 K, D, R = "kept", "dropped", "replaced"
 ALL_KEPT, ALL_DROPPED = (K, K, K, K), (D, D, D, D)
-KEEPER = (K, K, K, D)            # the five calls beside a plan: INNER and DISJOIN plans stay, a CONTAINS plan goes
+KEEPER = (K, K, K, D)            # the six calls beside a plan: INNER and DISJOIN plans stay, a CONTAINS plan goes
 INNER_PLAN = (R, R, D, D)        # a successful INNER plan call (the within-distance plan is one)
 
 #     column                          INNER, WINDOW, DISJOIN, CONTAINS
@@ -66,13 +67,15 @@ TABLE = {
     "take_no_rows":                   ALL_KEPT,
     "take_utf8_fill_no_rows":         ALL_KEPT,
     "mark_no_rows":                   ALL_KEPT,
-    # ---- the five calls beside a plan
+    "concat_utf8_fill_no_rows":       ALL_KEPT,
+    # ---- the six calls beside a plan
     "distance":                       KEEPER,
     "take":                           KEEPER,
     "take_utf8_fill":                 KEEPER,
     "mark":                           KEEPER,
     "segment_sum":                    KEEPER,
     "segment_sum_no_rows":            KEEPER,       # (begins its call before it looks at n)
+    "concat_utf8_fill":               KEEPER,       # STRING_AGG's byte fill: begin_call_beside_plan, like take_utf8_fill
     # ---- the plan calls
     "inner_plan":                     INNER_PLAN,
     "inner_plan_empty_side":          INNER_PLAN,
@@ -141,6 +144,16 @@ TABLE = {
     "host_semi_anti":                 ALL_DROPPED,
     "host_count":                     ALL_DROPPED,
     "host_nearest":                   ALL_DROPPED,
+    # ---- the extension headers' entry points: each begins a call before its first way out
+    "range_set_any":                  ALL_DROPPED,
+    "range_set_any_no_rows":          ALL_DROPPED,
+    "merge_str":                      ALL_DROPPED,  # giql_hip_merge_dev_impl's begin_call, as merge / merge_agg
+    "merge_str_empty":                ALL_DROPPED,
+    "pair_agg":                       ALL_DROPPED,  # pair_agg_impl begins its call before its own checks
+    "pair_agg_no_pairs":              ALL_DROPPED,
+    "pair_expr_agg":                  ALL_DROPPED,
+    "coverage":                       ALL_DROPPED,  # begin_call, then the way out with no rows, then claim_arena
+    "coverage_empty":                 ALL_DROPPED,
 }
 CELLS = [(row, col) for col in TABLE for row in ROWS]
 SENTINEL = -7
@@ -167,22 +180,27 @@ COLUMN_OF = {   # entry point (without giql_hip_ and _dev) -> its first column; 
     "index_prepare_rows": "index_prepare_rows", "count_indexed": "count_indexed", "semi_anti_indexed": "semi_indexed",
     "index_prepare_nearest": "index_prepare_nearest", "nearest_indexed": "nearest_indexed", "left_pad": "left_pad",
     "semi_anti_pred": "semi_pred_contains", "count_pred": "count_pred_contains", "eval_expr": "eval_expr",
-    "merge_agg": "merge_agg",
+    "merge_agg": "merge_agg", "range_set_any": "range_set_any", "merge_str": "merge_str",
+    "concat_utf8_fill": "concat_utf8_fill", "pair_agg": "pair_agg", "pair_expr_agg": "pair_expr_agg", "coverage": "coverage",
 }
 
 
 def test_the_table_is_complete():
     """CPU: a column for every entry point of the ABI that takes a context, the early-return forms the rule is
     about, and nothing in a cell but the three words, where the rule allows each."""
-    from giql_amd import _lib
+    from _stream_harness import abi_symbols
 
-    for s in _lib.SYMBOLS:
+    missing = []
+    for s in abi_symbols():       # every ``..._SYMBOLS`` list of ``_lib``: the extension headers' entry points too
         name = s[len("giql_hip_"):]
         if name in NO_CONTEXT:
             continue
         key = name[:-4] if name.endswith("_dev") else "host:" + name if name in ("inner", "semi_anti", "count", "nearest") else name
-        assert key in COLUMN_OF, s
+        if key not in COLUMN_OF:
+            missing.append(key)
+            continue
         assert COLUMN_OF[key] is None or COLUMN_OF[key] in TABLE, s
+    assert not missing, f"entry points that take a context and have no column in TABLE: {missing}"
     assert {w for words in TABLE.values() for w in words} == {K, D, R}
     for needed in ("semi", "count", "nearest", "nearest_k", "semi_pred_contains", "semi_pred_within", "semi_pred_distance",
                    "count_pred_contains", "count_pred_within", "count_pred_distance", "count_indexed", "semi_indexed",
@@ -190,15 +208,17 @@ def test_the_table_is_complete():
         assert needed in TABLE and needed + "_empty_left" in TABLE, needed
     for needed in ("cluster_empty", "merge_empty", "merge_agg_empty", "group_rows_empty", "inner_plan_empty_side",
                    "window_plan_empty_side", "contain_plan_empty_side", "disjoin_plan_empty_target", "select_no_candidates",
-                   "eval_expr_no_candidates", "take_utf8_plan_no_rows", "left_pad_no_pairs", "index_prepare_rows_prepared"):
+                   "eval_expr_no_candidates", "take_utf8_plan_no_rows", "left_pad_no_pairs", "index_prepare_rows_prepared",
+                   "range_set_any_no_rows", "merge_str_empty", "concat_utf8_fill_no_rows", "pair_agg_no_pairs", "coverage_empty"):
         assert needed in TABLE, needed
-    # the rule, restated: only a plan call replaces, and only on rows of its own kind; only the five calls beside a
+    # the rule, restated: only a plan call replaces, and only on rows of its own kind; only the six calls beside a
     # plan tell a CONTAINS plan from the others; everything else is one word for all four plans
     for col, words in TABLE.items():
         if R in words:
             assert col in REPLACED_BY and words in (INNER_PLAN, (D, D, R, D), (D, D, D, R)), col
         elif words == KEEPER:
-            assert col in ("distance", "take", "take_utf8_fill", "mark", "segment_sum", "segment_sum_no_rows"), col
+            assert col in ("distance", "take", "take_utf8_fill", "mark", "segment_sum", "segment_sum_no_rows",
+                           "concat_utf8_fill"), col
         else:
             assert words in (ALL_KEPT, ALL_DROPPED), col
 
@@ -428,7 +448,7 @@ def _columns(f):
     out["index_prepare_rows_prepared"] = lambda: L.giql_hip_index_prepare_rows_dev(h, f.index, st())
     out["index_prepare_nearest_prepared"] = lambda: L.giql_hip_index_prepare_nearest_dev(h, f.index, st())
 
-    # -- the five calls beside a plan, and their ways out with nothing to do
+    # -- the calls beside a plan, and their ways out with nothing to do
     def distance(n):
         return L.giql_hip_distance_dev(h, ref("a"), ref("b"), p(f.zeros4), p(f.zeros4), n, None, None, 0, p(i64[0]), p(u8), st())
 
@@ -539,6 +559,59 @@ def _columns(f):
                 "eval_expr": lambda: eval_expr(na), "eval_expr_no_candidates": lambda: eval_expr(0),
                 "take_utf8_plan": lambda: f.take_utf8_plan(64), "take_utf8_plan_no_rows": lambda: f.take_utf8_plan(0),
                 "left_pad": lambda: left_pad(4, na), "left_pad_no_pairs": lambda: left_pad(0, 0)})
+
+    # -- the extension headers: literal range sets, STRING_AGG beside MERGE, the pair aggregates, coverage
+    cu = dict(device="cuda:0")
+    set_out = [torch.zeros(4096, dtype=torch.uint8, **cu) for _ in range(2)]
+    set_host = (np.array([0], np.int32), np.array([3000], np.int64), np.array([1000], np.int64))     # chrom 0, [1000, 3000)
+    sets = (f.lib.CRangeSet * 1)(f.lib.CRangeSet(f.lib.RANGE_OPS["intersects"], 1, set_host[0].ctypes.data,
+                                                 set_host[1].ctypes.data, set_host[2].ctypes.data, p(set_out[0]), p(set_out[1])))
+
+    def range_set_any(n, _alive=(set_host, set_out)):      # (the struct points into both: they live as long as it does)
+        d = f.dev["a"]
+        return L.giql_hip_range_set_any_dev(h, p(d.chrom), p(d.start), p(d.end), None, None, None, n, sets, 1, st())
+
+    # a string column over table "a"; one merge_str up front leaves the order and the destinations the fill reads
+    names = [b"n%d" % i * (i % 4) for i in range(na)]
+    name_off = torch.from_numpy(np.concatenate([[0], np.cumsum([len(w) for w in names])]).astype(np.int32)).to("cuda:0")
+    name_data = torch.from_numpy(np.frombuffer(b"".join(names), np.uint8).copy()).to("cuda:0")
+    str_out = torch.zeros(1 << 16, dtype=torch.uint8, **cu)
+
+    def str_bufs():
+        return {"off": torch.zeros(4097, dtype=torch.int32, **cu), "nn": torch.zeros(4096, dtype=torch.int64, **cu),
+                "dst": torch.zeros(4096, dtype=torch.int32, **cu), "order": torch.zeros(4096, dtype=torch.int32, **cu)}
+
+    def merge_str(s, b):
+        strs = (f.lib.CStrAgg * 1)(f.lib.CStrAgg(p(name_off), None, 1, p(b["off"]), p(b["nn"]), p(b["dst"]), -7))
+        rc = L.giql_hip_merge_str_dev(h, ref(s), N_CHROM, 0, None, 0, None, 0, strs, 1, p(i32[0]), p(i32[1]), p(i32[2]), p(i64[0]),
+                                      p(b["order"]), 4096, ctypes.byref(n64()), st())
+        return rc, int(strs[0].n_bytes)
+
+    kept_str, scratch_str = str_bufs(), str_bufs()
+    rc, n_bytes = merge_str("a", kept_str)
+    assert rc == 0 and 0 < n_bytes <= str_out.numel(), (rc, n_bytes, L.giql_hip_last_error())
+
+    def concat_utf8_fill(n):
+        return L.giql_hip_concat_utf8_fill_dev(h, p(name_off), p(name_data), na, p(kept_str["order"]), p(kept_str["dst"]), n,
+                                               b",", 1, p(str_out), st())
+
+    expr_agg = (f.lib.CPairExprAgg * 1)(f.lib.CPairExprAgg(f.lib.AGG_FUNCS["SUM"], f.lib.T_I64, None, None, 0, 1,
+                                                           p(i64[1]), None))
+
+    def pair_agg(n_pairs):      # COUNT over a column of B: four pairs (row 0, row 0), or none
+        return L.giql_hip_pair_agg_dev(h, p(f.zeros4), p(f.zeros4), n_pairs, na, f.n["b"], f.agg, 1, p(i64[0]), st())
+
+    def coverage(s):
+        return L.giql_hip_coverage_dev(h, ref(s), N_CHROM, 0, p(i32[0]), p(i32[1]), p(i32[2]), p(i64[0]), 4096,
+                                       ctypes.byref(n64()), st())
+
+    out.update({"range_set_any": lambda: range_set_any(na), "range_set_any_no_rows": lambda: range_set_any(0),
+                "merge_str": lambda: merge_str("a", scratch_str)[0], "merge_str_empty": lambda: merge_str("none", scratch_str)[0],
+                "concat_utf8_fill": lambda: concat_utf8_fill(na), "concat_utf8_fill_no_rows": lambda: concat_utf8_fill(0),
+                "pair_agg": lambda: pair_agg(4), "pair_agg_no_pairs": lambda: pair_agg(0),
+                "pair_expr_agg": lambda: L.giql_hip_pair_expr_agg_dev(h, p(f.zeros4), p(f.zeros4), 4, na, f.n["b"], f.node, 1,
+                                                                      expr_agg, 1, p(i64[0]), st()),
+                "coverage": lambda: coverage("a"), "coverage_empty": lambda: coverage("none")})
 
     # -- the host-buffer entry points (host columns in, library-owned or caller-owned host results out)
     t = tables()

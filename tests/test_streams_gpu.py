@@ -22,6 +22,10 @@ order computes a wrong answer, never an out-of-range access.
 The delay, measured on an MI355X (warm contexts, the default stream): the slowest call sequence of a case takes
 ``t_host`` = 2.4 ms of host time (``merge_agg[wide]``: three ABI calls per chromosome group and torch indexing between
 them; ``inner_join[wide]`` 1.6 ms, every other case under 0.8 ms) and the slowest ``execute()`` query below 2.1 ms.
+The cases of the pair aggregates and of coverage, measured the same way when they were added, stay under that:
+``coverage[wide]`` 0.93 ms (``merge_agg[wide]`` 1.45 ms and ``inner_join[wide]`` 1.14 ms in that run), ``pair_aggregate``
+0.29 ms, ``pair_aggregate[expr]`` 0.27 ms, the three one-call coverage cases 0.16 ms; their ``execute()`` queries
+1.81 ms (join aggregates), 1.42 ms (aggregate expressions) and 0.48 ms (coverage).  ``t_host`` stays 2.4 ms.
 The delay ``D`` is 40 ms -- at least ``2 * t_host``, at least 20 ms, under the cap of 200 ms -- and
 ``torch.cuda._sleep`` counts 2.4 million cycles per millisecond there.  The fixtures calibrate that with event pairs at
 every run, ask for a quarter more than ``D`` and check what they get with another pair on ``s``: 50.0 ms.
@@ -64,10 +68,9 @@ DELAY_CAP_MS = 200.0
 def test_every_stream_entry_point_has_a_case():
     """Every symbol of ``_lib`` whose declaration takes a stream maps to a case; the two probes are the only
     exemptions: they return one bandwidth figure, which has no checkable value."""
-    from giql_amd import _lib
-
     declared = H.stream_entry_points()
-    symbols = _lib.SYMBOLS + _lib.RANGE_SET_SYMBOLS + _lib.STRING_AGG_SYMBOLS
+    symbols = H.abi_symbols()      # every ``..._SYMBOLS`` list of ``_lib``, found by name
+    assert len(symbols) == len(set(symbols))
     assert set(declared) <= set(symbols) and len(declared) == len(set(declared))
     assert sum(s.endswith("_dev") for s in symbols) == len(declared)      # (every *_dev entry point takes one)
     covered = {}
@@ -105,6 +108,13 @@ def test_ids_and_offsets_stay_inside_their_tables():
             inp = H.CASES[cid].inputs(which)
             for k in names:
                 assert inp[k].min() >= -1 and inp[k].max() < n_rows, (cid, k)
+        for cid in ("pair_aggregate", "pair_aggregate[expr]"):      # pair ids: no -1, the kernel refuses one
+            inp = H.CASES[cid].inputs(which)
+            assert inp["ra"].shape == inp["rb"].shape == (H.PAGG_PAIRS,), cid
+            assert inp["ra"].min() >= 0 and inp["ra"].max() < H.PAGG_NA and inp["rb"].min() >= 0 and inp["rb"].max() < H.PAGG_NB, cid
+            assert inp["ca"].shape == inp["ca.valid"].shape == (H.PAGG_NA,), cid        # columns as long as their table
+            assert all(inp[k].shape == (H.PAGG_NB,) for k in ("vf", "vf.valid", "vi")), cid
+            assert np.bincount(inp["ra"], minlength=H.PAGG_NA).min() > 0, cid            # every A row has pairs
         plan = H.CASES["fill_from_plan"].inputs(which)
         assert plan["lo"].min() >= 0 and plan["lo"].max() + H.PLAN_MAX_CNT <= H.PLAN_NS and plan["cnt"].max() < H.PLAN_MAX_CNT
         for cid, off, data in (("take_utf8", "off", "data"), ("merge_agg[STRING_AGG]", "w.off", "w.data")):
@@ -390,10 +400,46 @@ def _execute_cases():
     cases["range set"] = lambda eng: pa.table({"row": execute(
         "SELECT * FROM t WHERE " + rs["where"], {"t": _arrow_table(rs)}, eng, giql_tables=_giql_tables(rs),
         return_indices=True, range_sets=True)})
+    # the three opt-ins that end in the pair aggregates and in coverage: a query of each fixed list, on the tables of
+    # tests/test_join_aggregates_gpu.py (300 x 700 rows; the coverage recipe reads the left one)
+    import _agg_expr_queries as XQ
+    import _coverage_queries as CQ
+    import _join_agg_queries as JQ
+    import test_join_aggregates_gpu as JA
+
+    r = np.random.default_rng(2026)
+    ab = {"a": JA._arrow(JA._table(r, 300, ["g1", "g2", "g3", "g4", "g5", "g6", "g7"])),
+          "b": JA._arrow(JA._table(r, 700, ["x", "y", "z"]))}
+    cases["join aggregates"] = lambda eng: execute(JQ.MAP_SHAPE["eight_aggregates"], ab, eng, giql_tables=JQ.TABLES,
+                                                   join_aggregates=True)
+    cases["aggregate expressions"] = lambda eng: execute(XQ.IN_SHAPE["weighted"], ab, eng, giql_tables=XQ.TABLES,
+                                                         join_aggregates=True, aggregate_expressions=True)
+    cases["coverage"] = lambda eng: execute(CQ.DEPTH, {"features": ab["a"]}, eng, giql_tables=CQ.TABLES,
+                                            disjoin_aggregates=True)
     return cases
 
 
-EXECUTE_QUERIES = ["INNER", "SEMI", "NEAREST k=2", "MERGE with aggregates", "DISJOIN", "range set"]
+EXECUTE_QUERIES = ["INNER", "SEMI", "NEAREST k=2", "MERGE with aggregates", "DISJOIN", "range set", "join aggregates",
+                   "aggregate expressions", "coverage"]
+
+
+def test_the_execute_queries_have_a_case_each_and_lower_under_their_opt_in():
+    """CPU: the three queries added for the pair aggregates and coverage are inside the shape their opt-in lowers --
+    the plan says so -- so the GPU test below reaches ``pair_agg``, ``pair_expr_agg`` and ``coverage`` and not an
+    older route."""
+    import _agg_expr_queries as XQ
+    import _coverage_queries as CQ
+    import _join_agg_queries as JQ
+    from giql_amd.transpile import build_plan
+
+    assert set(EXECUTE_QUERIES) >= {"join aggregates", "aggregate expressions", "coverage"}
+    plan = build_plan(JQ.MAP_SHAPE["eight_aggregates"], JQ.TABLES, join_aggregates=True)
+    assert plan.join_aggregates and len(plan.aggregates) == 8 and not plan.expressions, plan.to_string()
+    plan = build_plan(XQ.IN_SHAPE["weighted"], XQ.TABLES, join_aggregates=True, aggregate_expressions=True)
+    assert plan.join_aggregates and len(plan.expressions) == 1, plan.to_string()
+    assert [(a.func, a.side) for a in plan.aggregates] == [("SUM", "x"), ("AVG", "r")]      # a tree beside a plain column
+    assert CQ.ACCEPTED["depth_recipe"] == (CQ.DEPTH, "depth")
+    assert build_plan(CQ.DEPTH, CQ.TABLES, disjoin_aggregates=True).segments == "depth"
 
 
 @gpu

@@ -14,7 +14,13 @@ full of its own arrays, and then the calls in which a buffer is used a second ti
   the span pass counted into is linearized after all;
 * (d) INNER plans at densities on either side of a bucket-width change (16-bit buckets: two global passes, narrower
   ones: three, none: four) -- the larger side needs more zeroed passes than the first memset gave it;
-* (e) index create, then the indexed join, on a fixed-length table of 30,000 rows.
+* (e) index create, then the indexed join, on a fixed-length table of 30,000 rows;
+* (f) coverage, then an INNER plan of the general form -- coverage's event sort and its three scans carve status words
+  and histograms where the plan's two sides then carve theirs;
+* (g) an INNER plan over a fixed-length B (its span pass counts into the histogram), then coverage of that B;
+* (h) a pair aggregate (two radix sorts and a scan of its own carve), then NEAREST on pile-ups: the two-sort plan;
+* (i) NEAREST, then both pair aggregates, then coverage;
+* (j) coverage runs, DISJOIN of the same table, coverage depth: the two entry points share the front's carves.
 
 One context with the production density rules and no row floor; each call runs twice (on the previous call's guesses,
 then on its own) and is checked against the C oracle.  The classes, their resident copies and their cached oracle
@@ -146,3 +152,61 @@ def test_index_create_then_indexed_join(eng, fixed_30k):
             assert np.array_equal(tr._pairs(ra, rb), want)
         finally:
             index.close()
+
+
+def _in_turn(eng, steps, fam):
+    """``steps`` = ``[(operator, class)]``, the whole sequence twice on the dirtied workspace: every call runs right
+    after the one before it in the list, first on that call's leavings alone and then on its own as well."""
+    import test_context_transitions as tr
+
+    log = tr.Log()
+    _dirty(eng)
+    for rnd in (1, 2):
+        for op, name in steps:
+            op(eng, name, log, fam, rnd)
+    return log
+
+
+def test_coverage_then_inner_plan(eng):
+    import test_context_transitions as tr
+
+    log = _in_turn(eng, [(tr.op_coverage, "general"), (tr.op_plan_fill, "general")], "mixed")
+    assert [c[3] for c in log.calls] == ["coverage", "plan"] * 2
+    assert log.calls[-1][4]["join_form"] == "general"
+
+
+def test_inner_plan_over_a_fixed_length_b_then_coverage(eng):
+    import test_context_transitions as tr
+
+    log = _in_turn(eng, [(tr.op_plan_fill, "uniform_b"), (tr.op_coverage, "uniform_b")], "mixed")
+    plans = [c[4] for c in log.calls if c[3] == "plan"]
+    assert plans[-1]["join_form"] == "uniform_b", plans[-1]["join_form"]
+
+
+def test_pair_aggregate_then_nearest_with_two_sorts(eng):
+    import test_context_transitions as tr
+
+    _in_turn(eng, [(tr.op_pair_agg, "pileups"), (tr.op_nearest, "pileups")], "mixed")
+
+
+def test_nearest_then_pair_aggregates_then_coverage(eng):
+    import test_context_transitions as tr
+
+    _in_turn(eng, [(tr.op_nearest, "general"), (tr.op_pair_agg, "general"), (tr.op_pair_expr_agg, "general"),
+                   (tr.op_coverage, "general")], "mixed")
+
+
+def test_coverage_runs_then_disjoin_then_coverage_depth(eng):
+    """One table through the three calls that carve DISJOIN's front: spans, 2n events, one sort, two flag scans."""
+    import test_context_transitions as tr
+    from _disjoin_ref import brute_force_arrays
+
+    _a, b, nch, _da, db = tr.resident("general")
+    pieces = brute_force_arrays(b.chrom.astype(np.int64), b.start.astype(np.int64), b.end.astype(np.int64))
+    same = lambda out, want: all(g.shape == w.shape and torch.equal(g, w) for g, w in zip(out, want))  # noqa: E731
+    _dirty(eng)
+    for _rnd in (1, 2):
+        assert same(eng.coverage(db, nch, runs=True), tr.want_coverage("general", True)), "coverage runs"
+        got = tr._pieces(*eng.disjoin(db, None, nch))
+        assert got.shape == pieces.shape and np.array_equal(got, pieces), "disjoin"
+        assert same(eng.coverage(db, nch), tr.want_coverage("general", False)), "coverage depth"
