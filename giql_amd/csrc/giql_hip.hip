@@ -1111,22 +1111,21 @@ static void common_sizes(Carver& c, int n_chrom, LinBufs& lb) {
   lb.len_part = c.take<int>((size_t)2 * MM_MAX_BLOCKS * 2);
 }
 
-static void sort_sizes(Carver& c, size_t n, SortBufs& sb, bool payload) {
+static void sort_sizes(Carver& c, size_t n, SortBufs& sb, bool end, bool rid) {
   for (int k = 0; k < 2; k++) {
     sb.key[k] = c.take<u32>(n);
-    sb.end[k] = payload ? c.take<u32>(n) : nullptr;
-    sb.rid[k] = payload ? c.take<u32>(n) : nullptr;
+    sb.end[k] = end ? c.take<u32>(n) : nullptr;
+    sb.rid[k] = rid ? c.take<u32>(n) : nullptr;
   }
 }
+static void sort_sizes(Carver& c, size_t n, SortBufs& sb, bool payload) { sort_sizes(c, n, sb, payload, payload); }
 
-// (sort key, one payload column), no row ids: B of SEMI / ANTI and of their predicate form
-static void sort_sizes_key_payload(Carver& c, size_t n, SortBufs& sb) {
-  for (int k = 0; k < 2; k++) {
-    sb.key[k] = c.take<u32>(n);
-    sb.end[k] = c.take<u32>(n);
-    sb.rid[k] = nullptr;
-  }
-}
+// (sort key, one payload column), no row ids: B of SEMI / ANTI and of their predicate form, the pairs of an aggregate,
+// plain MERGE
+static void sort_sizes_key_payload(Carver& c, size_t n, SortBufs& sb) { sort_sizes(c, n, sb, true, false); }
+
+// (sort key, row id), no end column: the event keys of DISJOIN and of the coverage segments
+static void sort_sizes_key_rid(Carver& c, size_t n, SortBufs& sb) { sort_sizes(c, n, sb, false, true); }
 
 // two keys-only sorts of one side, its starts and its ends: B of COUNT and of COUNT over DISTANCE
 static void sort_sizes_starts_ends(Carver& c, size_t n, SortBufs& sstart, SortBufs& send) {
@@ -3503,6 +3502,177 @@ int giql_hip_nearest_k_dev(giql_hip_ctx* ctx, const giql_side* a, const giql_sid
   return with_order_fallback(ctx, [&] { return giql_hip_nearest_k_dev_impl(ctx, a, b, n_chrom, k, is_signed, max_distance, idx_b_out, dist_out, stream); });
 }
 
+// ------------------------------------- stages of the one-table and aggregate operators
+// The status-word frame of a call whose kernels report through DevMeta::status alone: zero the word before the
+// launches; after them read it back, wait, and collect the spans.  The caller words what a set word means.
+static int begin_status(giql_hip_ctx* ctx, hipStream_t st) {
+  HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
+  return GIQL_OK;
+}
+static int finish_status(giql_hip_ctx* ctx, hipStream_t st, int& status) {
+  status = 0;
+  HIP_TRY(hipMemcpyAsync(&status, &ctx->d_meta->status, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  collect_spans(ctx);
+  return GIQL_OK;
+}
+
+// The event sweep of DISJOIN's plan and of the coverage segments (disjoin_kernels.hip.h): the 2n start / end events of
+// one table as keys on the linear axis -> ONE (key, id) sort -> per sorted event "the last of its key" and "a start",
+// and the exclusive scans of both.  What an operator makes of the breakpoints stays in the operator.
+struct EventBufs {
+  LinBufs lb;
+  SortBufs sb;
+  OsScratch os;
+  u32 *last = nullptr, *is_start = nullptr, *last_excl = nullptr, *start_excl = nullptr;
+  u64 *bsums = nullptr, *n_bp = nullptr, *scratch_total = nullptr;  // carved by the operator, behind the prefix
+};
+
+// the prefix the two operators' workspaces share
+static void event_sizes(Carver& c, int n_chrom, size_t nev, EventBufs& E) {
+  common_sizes(c, n_chrom, E.lb);
+  sort_sizes_key_rid(c, nev, E.sb);
+  os_scratch_sizes(c, nev, E.os);
+  E.last = c.take<u32>(nev);
+  E.is_start = c.take<u32>(nev);
+  E.last_excl = c.take<u32>(nev + 1);
+  E.start_excl = c.take<u32>(nev + 1);
+}
+
+// t: the table whose rows the operator goes on to cut; r: the table of the events, nullptr = t itself (DISJOIN's self
+// mode, coverage).  A table of no rows has no event: no key, no flag, and the sort and the scans run over nothing.
+static int run_events(giql_hip_ctx* ctx, hipStream_t st, const giql_side& t, const giql_side* r, int n_chrom,
+                      EventBufs& E, const char* op) {
+  const giql_side& ref = r ? *r : t;
+  const size_t nr = (size_t)ref.n, nev = 2 * nr;
+  char what[32];
+  giql_side none;
+  memset(&none, 0, sizeof(none));
+  GIQL_TRY(run_spans(ctx, st, t, r ? *r : none, n_chrom, E.lb));
+  if (nev > 0) {
+    HIP_TRY(hipMemsetAsync(E.os.hist, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
+    Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
+    ctx->stats.phase_bytes[GIQL_PH_LINEARIZE] += (int64_t)20 * nr;  // three columns read, two keys written
+    u32 grid = cdiv((u64)nr, LIN_NT);
+    if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_dj_events, dim3(grid), dim3(LIN_NT), 0, st, view_of(ref), n_chrom, E.lb.chrom_base,
+                       E.sb.key[0], E.os.hist, ctx->d_meta, r ? DJ_BAD_REFERENCE : DJ_BAD_TARGET);
+    hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, E.os.hist, (u32)LIN_HIST_REPLICAS, E.os.gbase);
+    snprintf(what, sizeof(what), "%s events", op);
+    GIQL_TRY(post_launch(what));
+  }
+  GIQL_TRY(run_sort_onesweep(ctx, st, E.sb, sort_by_start(E.os, nev)));
+  if (nev > 0) {
+    Phase ph(ctx, st, GIQL_PH_COUNT, 1);
+    ctx->stats.phase_bytes[GIQL_PH_COUNT] += (int64_t)16 * nev;  // keys + ids read, two flags written
+    hipLaunchKernelGGL(k_dj_flags, dim3(cdiv(nev, 256)), dim3(256), 0, st, E.sb.key[0], E.sb.rid[0], (u32)nev, (u32)nr,
+                       E.last, E.is_start);
+    snprintf(what, sizeof(what), "%s flags", op);
+    GIQL_TRY(post_launch(what));
+  }
+  GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, E.last, (u64)nev, E.last_excl, E.bsums, E.n_bp));
+  return run_scan<u32>(ctx, st, GIQL_PH_SCAN, E.is_start, (u64)nev, E.start_excl, E.bsums, E.scratch_total);
+}
+
+// The call's read-back: DevMeta, the `start > end` bits of k_dj_events / k_dj_count the caller looks at, the status.
+static int finish_events(giql_hip_ctx* ctx, hipStream_t st, u32 bad_bits) {
+  HIP_TRY(hipMemcpyAsync(ctx->h_meta, ctx->d_meta, sizeof(DevMeta), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (ctx->h_meta->aux0 & bad_bits & DJ_BAD_TARGET)
+    return set_err(GIQL_ERR_INVALID, "DISJOIN needs start <= end on every row: the target has a row with start > end");
+  if (ctx->h_meta->aux0 & bad_bits & DJ_BAD_REFERENCE)
+    return set_err(GIQL_ERR_INVALID, "DISJOIN needs start <= end on every row: the reference has a row with start > end");
+  return read_meta(ctx, st);
+}
+
+// The caller's aggregates -> the by-value kernel argument of the segmented reduction (merge_agg_kernels.hip.h).
+// Aggregates over one source share one column, i.e. one gather; the kernels walk the aggregates column by column.
+// over_pairs: a pair aggregate's sources (include/giql_hip_pair_expr_agg.h) -- a program over `nodes`, or a column,
+// where a COUNT reads validity alone (data may be NULL; every COUNT over one validity shares a column); MERGE's are
+// columns with data, keyed by (data, valid, type) whatever the function.  ordered: a float SUM, MIN or MAX -- their
+// bits depend on the order of their inputs (a sum's rounding; which of +0.0 and -0.0 a MIN / MAX keeps).
+static int check_program(const giql_operand* nodes, int32_t n_nodes, int first, int count, int k, const char* which,
+                         bool* uses, const char* owner, bool* can_float);
+static int convert_aggs(const giql_pair_expr_agg* aggs, int32_t n_aggs, bool over_pairs, const giql_operand* nodes,
+                        int32_t n_nodes, PxaggArgs& xa, bool* any_prog = nullptr, bool* ordered = nullptr) {
+  memset(&xa, 0, sizeof(xa));
+  MaggArgs& ma = xa.M;
+  ma.n_aggs = n_aggs;
+  for (int k = 0; k < n_aggs; k++) {
+    const giql_pair_expr_agg& g = aggs[k];
+    if (g.func < GIQL_AGG_COUNT || g.func > GIQL_AGG_MAX)
+      return set_err(GIQL_ERR_INVALID, "aggregate %d: function %d", k, g.func);
+    if (g.type < GIQL_T_I32 || g.type > GIQL_T_F64)
+      return set_err(GIQL_ERR_INVALID, "aggregate %d: column type %d (int32, int64, float32 or float64)", k, g.type);
+    if (!over_pairs && (!g.data || !g.out)) return set_err(GIQL_ERR_INVALID, "aggregate %d: data or out is NULL", k);
+    if (!g.out) return set_err(GIQL_ERR_INVALID, "aggregate %d: out is NULL", k);
+    if (g.count < 0) return set_err(GIQL_ERR_INVALID, "aggregate %d: a program of %d nodes", k, g.count);
+    MaggCol want{g.data, g.valid, g.type};
+    PxaggProg prog{0, 0};
+    if (g.count > 0) {  // an expression source: checked and typed as giql_hip_eval_expr_dev does it
+      if (g.type != GIQL_T_I64 && g.type != GIQL_T_F64)
+        return set_err(GIQL_ERR_INVALID, "aggregate %d: result type %d of a program (GIQL_T_I64 or GIQL_T_F64)", k, g.type);
+      bool uses[2] = {false, false}, can_float = false;
+      GIQL_TRY(check_program(nodes, n_nodes, g.first, g.count, k, "program", uses, "aggregate", &can_float));
+      if (can_float && g.type == GIQL_T_I64)
+        return set_err(GIQL_ERR_INVALID, "aggregate %d: the program can yield a float, its result type is GIQL_T_I64", k);
+      want = MaggCol{nullptr, nullptr, g.type};  // (k_magg_fold reads the type alone)
+      prog = PxaggProg{g.first, g.count};
+      if (any_prog) *any_prog = true;
+    } else if (over_pairs) {
+      if (!g.data && g.func != GIQL_AGG_COUNT)
+        return set_err(GIQL_ERR_INVALID, "aggregate %d: data is NULL (only COUNT reads validity alone)", k);
+      if (g.func == GIQL_AGG_COUNT) want = MaggCol{nullptr, g.valid, MAGG_T_NONE};  // COUNT never reads the values
+    }
+    int c = 0;
+    while (c < ma.n_cols && !(ma.cols[c].data == want.data && ma.cols[c].valid == want.valid && ma.cols[c].type == want.type &&
+                              xa.prog[c].first == prog.first && xa.prog[c].count == prog.count)) c++;
+    if (c == ma.n_cols) {
+      xa.prog[c] = prog;
+      ma.cols[ma.n_cols++] = want;
+    }
+    ma.aggs[k].func = g.func;
+    ma.aggs[k].col = c;
+    ma.aggs[k].out = (u64*)g.out;
+    ma.aggs[k].out_nn = (i64*)g.out_nn;
+    if (ordered && g.func != GIQL_AGG_COUNT && (g.type == GIQL_T_F32 || g.type == GIQL_T_F64)) *ordered = true;
+  }
+  return GIQL_OK;
+}
+
+// giql_agg[] as column sources of giql_pair_expr_agg[] (at most MAGG_MAX are copied: the callers check the count)
+static const giql_pair_expr_agg* column_sources(const giql_agg* aggs, int32_t n_aggs, giql_pair_expr_agg* out) {
+  for (int k = 0; aggs && k < n_aggs && k < MAGG_MAX; k++)
+    out[k] = giql_pair_expr_agg{aggs[k].func, aggs[k].type, aggs[k].data, aggs[k].valid, 0, 0, aggs[k].out, aggs[k].out_nn};
+  return aggs ? out : nullptr;
+}
+
+// The segmented reduction of MERGE's aggregates and of the pair aggregates: per aggregate four carry words per tile of
+// MAGG_TILE sorted positions; one launch over the tiles, and a fold of the carries when there is more than one.  The
+// launches belong to the caller's Phase.  xa: the programs of a pair aggregate -- k_pxagg_tiles evaluates them at
+// (rows_a, rows) and gathers the column sources of the same call; without one it is k_magg_tiles over `rows`.
+static size_t magg_sizes(int n_aggs, size_t n) { return (size_t)n_aggs * 4 * cdiv(n, (size_t)MAGG_TILE); }
+
+static void bind_magg(MaggArgs& ma, u64* ws, size_t n) {
+  const size_t n_tiles = cdiv(n, (size_t)MAGG_TILE);
+  for (int a = 0; a < ma.n_aggs; a++) {
+    u64* w = ws + (size_t)a * 4 * n_tiles;
+    ma.aggs[a].first_v = w, ma.aggs[a].last_v = w + n_tiles;
+    ma.aggs[a].first_c = (i64*)(w + 2 * n_tiles), ma.aggs[a].last_c = (i64*)(w + 3 * n_tiles);
+  }
+}
+
+static void run_magg(hipStream_t st, const u32* rows, const u32* excl, const u32* flags, u32 n, const MaggArgs& ma,
+                     const PxaggArgs* xa = nullptr, const u32* rows_a = nullptr, const DevOperand* nodes = nullptr) {
+  const u32 n_tiles = cdiv((u64)n, MAGG_TILE);
+  if (xa)
+    hipLaunchKernelGGL(k_pxagg_tiles, dim3(n_tiles), dim3(MAGG_TILE), 0, st, rows_a, rows, excl, flags, n, nodes, *xa);
+  else
+    hipLaunchKernelGGL(k_magg_tiles, dim3(n_tiles), dim3(MAGG_TILE), 0, st, rows, excl, flags, n, ma);
+  if (n_tiles > 1)
+    hipLaunchKernelGGL(k_magg_fold, dim3(cdiv((u64)n_tiles - 1, 256 / WAVE)), dim3(256), 0, st, excl, flags, n, n_tiles, ma);
+}
+
 // ---------------------------------------------------------- CLUSTER / MERGE
 // Shared front half: keys + ends on the linear axis, sorted by start, inclusive
 // prefix max of the ends, new-cluster flags and their exclusive scan.
@@ -3536,11 +3706,7 @@ static int cluster_front(giql_hip_ctx* ctx, hipStream_t st, const giql_side* s, 
   auto carve = [&](char* base) {
     Carver c{base};
     common_sizes(c, n_chrom, cb.lb);
-    for (int k = 0; k < 2; k++) {
-      cb.sb.key[k] = c.take<u32>(n);
-      cb.sb.end[k] = c.take<u32>(n);
-      cb.sb.rid[k] = want_rids ? c.take<u32>(n) : nullptr;
-    }
+    sort_sizes(c, n, cb.sb, true, want_rids);
     os_scratch_sizes(c, n, cb.os);
     cb.pmax = c.take<u32>(n);
     cb.bmax = c.take<u32>(cdiv(n, PM_TILE) + 1);
@@ -3552,7 +3718,7 @@ static int cluster_front(giql_hip_ctx* ctx, hipStream_t st, const giql_side* s, 
     cb.dummy_irr = c.take<u32>(16);
     cb.head_pos = want_heads ? c.take<u32>(n + 1) : nullptr;
     cb.seg_end = want_heads && preds && preds->n > 0 ? c.take<u32>(n + 1) : nullptr;
-    cb.agg_ws = cb.n_aggs ? c.take<u64>((size_t)cb.n_aggs * 4 * cdiv(n, (size_t)MAGG_TILE)) : nullptr;
+    cb.agg_ws = cb.n_aggs ? c.take<u64>(magg_sizes(cb.n_aggs, n)) : nullptr;
     cb.str_g = cb.strs ? c.take<u64>(n + 1) : nullptr;
     cb.str_v = cb.strs ? c.take<u32>(n + 1) : nullptr;
     cb.str_tot = cb.strs ? c.take<u64>(2) : nullptr;
@@ -3767,17 +3933,8 @@ static int giql_hip_merge_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int32_
                          (u32)h_total, (u32)s->n, cb.sb.key[0], cb.pmax, pred ? cb.seg_end : (u32*)nullptr, cb.lb.chrom_first,
                          cb.lb.chrom_base, n_chrom, out_chrom, out_start, out_end, (i64*)out_count);
     if (aggs && h_total) {  // one segmented reduction over the sorted order; every region gets exactly one writer
-      const u32 n_tiles = cdiv((u64)s->n, MAGG_TILE);
-      for (int a = 0; a < aggs->n_aggs; a++) {
-        u64* w = cb.agg_ws + (size_t)a * 4 * n_tiles;
-        aggs->aggs[a].first_v = w, aggs->aggs[a].last_v = w + n_tiles;
-        aggs->aggs[a].first_c = (i64*)(w + 2 * (size_t)n_tiles), aggs->aggs[a].last_c = (i64*)(w + 3 * (size_t)n_tiles);
-      }
-      hipLaunchKernelGGL(k_magg_tiles, dim3(n_tiles), dim3(MAGG_TILE), 0, st, cb.sb.rid[0], cb.excl, cb.flags,
-                         (u32)s->n, *aggs);
-      if (n_tiles > 1)
-        hipLaunchKernelGGL(k_magg_fold, dim3(cdiv((u64)n_tiles - 1, 256 / WAVE)), dim3(256), 0, st, cb.excl, cb.flags,
-                           (u32)s->n, n_tiles, *aggs);
+      bind_magg(*aggs, cb.agg_ws, (size_t)s->n);
+      run_magg(st, cb.sb.rid[0], cb.excl, cb.flags, (u32)s->n, *aggs);
     }
     GIQL_TRY(post_launch("merge rows"));
   }
@@ -3853,29 +4010,6 @@ int giql_hip_merge_pred_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chr
   return with_order_fallback(ctx, [&] { return giql_hip_merge_dev_impl(ctx, s, n_chrom, distance, out_chrom, out_start, out_end, out_count, capacity, n_out, stream, &ps); });
 }
 
-// MERGE with aggregates: the host array of giql_agg -> the by-value kernel argument.  Aggregates that read the same
-// (data, valid, type) share one column, i.e. one gather; the kernel walks the aggregates column by column.
-static int convert_aggs(const giql_agg* aggs, int32_t n_aggs, MaggArgs& ma) {
-  memset(&ma, 0, sizeof(ma));
-  ma.n_aggs = n_aggs;
-  for (int k = 0; k < n_aggs; k++) {
-    const giql_agg& g = aggs[k];
-    if (g.func < GIQL_AGG_COUNT || g.func > GIQL_AGG_MAX)
-      return set_err(GIQL_ERR_INVALID, "aggregate %d: function %d", k, g.func);
-    if (g.type < GIQL_T_I32 || g.type > GIQL_T_F64)
-      return set_err(GIQL_ERR_INVALID, "aggregate %d: column type %d (int32, int64, float32 or float64)", k, g.type);
-    if (!g.data || !g.out) return set_err(GIQL_ERR_INVALID, "aggregate %d: data or out is NULL", k);
-    int c = 0;
-    while (c < ma.n_cols && !(ma.cols[c].data == g.data && ma.cols[c].valid == g.valid && ma.cols[c].type == g.type)) c++;
-    if (c == ma.n_cols) ma.cols[ma.n_cols++] = MaggCol{g.data, g.valid, g.type};
-    ma.aggs[k].func = g.func;
-    ma.aggs[k].col = c;
-    ma.aggs[k].out = (u64*)g.out;
-    ma.aggs[k].out_nn = (i64*)g.out_nn;
-  }
-  return GIQL_OK;
-}
-
 int giql_hip_merge_agg_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom, int64_t distance,
                            const giql_pred* preds, int32_t n_preds, const giql_agg* aggs, int32_t n_aggs,
                            int32_t* out_chrom, int32_t* out_start, int32_t* out_end, int64_t* out_count,
@@ -3884,11 +4018,12 @@ int giql_hip_merge_agg_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chro
     return set_err(GIQL_ERR_INVALID, "bad predicates (at most %d)", SEL_MAX_PREDS);
   if (n_aggs < 1 || n_aggs > MAGG_MAX || !aggs)
     return set_err(GIQL_ERR_INVALID, "%d aggregates: MERGE takes 1 to %d", n_aggs, MAGG_MAX);
-  MaggArgs ma;
-  GIQL_TRY(convert_aggs(aggs, n_aggs, ma));
+  giql_pair_expr_agg cols[MAGG_MAX];
+  PxaggArgs xa;
+  GIQL_TRY(convert_aggs(column_sources(aggs, n_aggs, cols), n_aggs, false, nullptr, 0, xa));
   DevPreds ps;
   GIQL_TRY(convert_preds(preds, n_preds, ps, nullptr));
-  return with_order_fallback(ctx, [&] { return giql_hip_merge_dev_impl(ctx, s, n_chrom, distance, out_chrom, out_start, out_end, out_count, capacity, n_out, stream, &ps, &ma); });
+  return with_order_fallback(ctx, [&] { return giql_hip_merge_dev_impl(ctx, s, n_chrom, distance, out_chrom, out_start, out_end, out_count, capacity, n_out, stream, &ps, &xa.M); });
 }
 
 // MERGE with STRING_AGG (include/giql_hip_string_agg.h): giql_hip_merge_agg_dev with 0..8 numeric aggregates plus the
@@ -3914,12 +4049,13 @@ int giql_hip_merge_str_dev(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chro
       return set_err(GIQL_ERR_INVALID, "string aggregate %d: offsets, out_offsets, out_nn or row_dst is NULL", k);
   }
   if (rows && !out_order) return set_err(GIQL_ERR_INVALID, "out_order is NULL");
-  MaggArgs ma;
-  GIQL_TRY(convert_aggs(aggs, n_aggs, ma));
+  giql_pair_expr_agg cols[MAGG_MAX];
+  PxaggArgs xa;
+  GIQL_TRY(convert_aggs(column_sources(aggs, n_aggs, cols), n_aggs, false, nullptr, 0, xa));
   DevPreds ps;
   GIQL_TRY(convert_preds(preds, n_preds, ps, nullptr));
   const SaggCall sc{strs, n_strs, out_order};
-  return with_order_fallback(ctx, [&] { return giql_hip_merge_dev_impl(ctx, s, n_chrom, distance, out_chrom, out_start, out_end, out_count, capacity, n_out, stream, &ps, n_aggs ? &ma : nullptr, &sc); });
+  return with_order_fallback(ctx, [&] { return giql_hip_merge_dev_impl(ctx, s, n_chrom, distance, out_chrom, out_start, out_end, out_count, capacity, n_out, stream, &ps, n_aggs ? &xa.M : nullptr, &sc); });
 }
 
 int giql_hip_concat_utf8_fill_dev(giql_hip_ctx* ctx, const int32_t* offsets, const uint8_t* data, int64_t n_rows,
@@ -3937,7 +4073,7 @@ int giql_hip_concat_utf8_fill_dev(giql_hip_ctx* ctx, const int32_t* offsets, con
   memset(&sp, 0, sizeof(sp));
   sp.len = (u32)sep_len;
   if (sep_len) memcpy(sp.b, sep, (size_t)sep_len);
-  HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
+  GIQL_TRY(begin_status(ctx, st));
   u32 grid = cdiv((u64)n, (u64)SAGG_NT * 2);
   if (grid > 2u * GIQL_STREAM_GRID) grid = 2u * GIQL_STREAM_GRID;
   {
@@ -3946,10 +4082,8 @@ int giql_hip_concat_utf8_fill_dev(giql_hip_ctx* ctx, const int32_t* offsets, con
                        sp, out_data, &ctx->d_meta->status);
     GIQL_TRY(post_launch("concat_utf8_fill"));
   }
-  int status = 0;
-  HIP_TRY(hipMemcpyAsync(&status, &ctx->d_meta->status, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  collect_spans(ctx);
+  int status;
+  GIQL_TRY(finish_status(ctx, st, status));
   if (status != 0)
     return set_err(GIQL_ERR_INVALID, "concat_utf8_fill: a row id outside the column, a decreasing offset pair or a "
                                      "separator before the output's start");
@@ -3986,51 +4120,9 @@ static int pair_agg_impl(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t*
   if (n_nodes < 0 || n_nodes > SEL_MAX_NODES || (n_nodes && !nodes))
     return set_err(GIQL_ERR_INVALID, "%d expression nodes: a pair aggregate takes 0 to %d", n_nodes, SEL_MAX_NODES);
   PxaggArgs xa;
-  memset(&xa, 0, sizeof(xa));
   MaggArgs& ma = xa.M;
-  ma.n_aggs = n_aggs;
-  bool any_prog = false;
-  // a float SUM, MIN or MAX: the aggregates whose bits depend on the order of their inputs (a sum's rounding; which of
-  // +0.0 and -0.0 a MIN / MAX keeps)
-  bool ordered = false;
-  for (int k = 0; k < n_aggs; k++) {
-    const giql_pair_expr_agg& g = aggs[k];
-    if (g.func < GIQL_AGG_COUNT || g.func > GIQL_AGG_MAX)
-      return set_err(GIQL_ERR_INVALID, "aggregate %d: function %d", k, g.func);
-    if (g.type < GIQL_T_I32 || g.type > GIQL_T_F64)
-      return set_err(GIQL_ERR_INVALID, "aggregate %d: column type %d (int32, int64, float32 or float64)", k, g.type);
-    if (!g.out) return set_err(GIQL_ERR_INVALID, "aggregate %d: out is NULL", k);
-    if (g.count < 0) return set_err(GIQL_ERR_INVALID, "aggregate %d: a program of %d nodes", k, g.count);
-    MaggCol want;
-    PxaggProg prog{0, 0};
-    if (g.count > 0) {  // an expression source: checked and typed as giql_hip_eval_expr_dev does it
-      if (g.type != GIQL_T_I64 && g.type != GIQL_T_F64)
-        return set_err(GIQL_ERR_INVALID, "aggregate %d: result type %d of a program (GIQL_T_I64 or GIQL_T_F64)", k, g.type);
-      bool uses[2] = {false, false}, can_float = false;
-      GIQL_TRY(check_program(nodes, n_nodes, g.first, g.count, k, "program", uses, "aggregate", &can_float));
-      if (can_float && g.type == GIQL_T_I64)
-        return set_err(GIQL_ERR_INVALID, "aggregate %d: the program can yield a float, its result type is GIQL_T_I64", k);
-      want = MaggCol{nullptr, nullptr, g.type};  // (k_magg_fold reads the type alone)
-      prog = PxaggProg{g.first, g.count};
-      any_prog = true;
-    } else {
-      if (!g.data && g.func != GIQL_AGG_COUNT)
-        return set_err(GIQL_ERR_INVALID, "aggregate %d: data is NULL (only COUNT reads validity alone)", k);
-      // COUNT never reads the values: its column is the validity alone, shared by every COUNT over it
-      want = g.func == GIQL_AGG_COUNT ? MaggCol{nullptr, (const unsigned char*)g.valid, MAGG_T_NONE}
-                                      : MaggCol{g.data, (const unsigned char*)g.valid, g.type};
-    }
-    int c = 0;
-    while (c < ma.n_cols && !(ma.cols[c].data == want.data && ma.cols[c].valid == want.valid && ma.cols[c].type == want.type &&
-                              xa.prog[c].first == prog.first && xa.prog[c].count == prog.count)) c++;
-    if (c == ma.n_cols) {
-      xa.prog[c] = prog;
-      ma.cols[ma.n_cols++] = want;
-    }
-    ma.aggs[k].func = g.func;
-    ma.aggs[k].col = c;
-    if (g.func != GIQL_AGG_COUNT && (g.type == GIQL_T_F32 || g.type == GIQL_T_F64)) ordered = true;
-  }
+  bool any_prog = false, ordered = false;
+  GIQL_TRY(convert_aggs(aggs, n_aggs, true, nodes, n_nodes, xa, &any_prog, &ordered));
   if (n_a > 0 && !pairs_out) return set_err(GIQL_ERR_INVALID, "pairs_out is NULL");
   if (n_a > 0 && n_pairs > 0 && (!row_a || !row_b)) return set_err(GIQL_ERR_INVALID, "row_a or row_b is NULL");
   if (n_a == 0) return GIQL_OK;
@@ -4063,12 +4155,12 @@ static int pair_agg_impl(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t*
     excl = c.take<u32>(n + 1);
     head_pos = c.take<u32>(m_max + 1);
     seg = c.take<u64>((size_t)n_aggs * 2 * m_max);
-    carry = c.take<u64>((size_t)n_aggs * 4 * n_tiles);
+    carry = c.take<u64>(magg_sizes(n_aggs, n));
     if (any_prog) d_nodes = c.take<DevOperand>(SEL_MAX_NODES);
     return c.off;
   };
   GIQL_TRY(claim_arena(ctx, st, carve));
-  HIP_TRY(hipMemsetAsync(&ctx->d_meta->status, 0, sizeof(int), st));
+  GIQL_TRY(begin_status(ctx, st));
   // (pageable source: staged by the runtime before the call returns)
   if (any_prog) HIP_TRY(hipMemcpyAsync(d_nodes, nodes, (size_t)n_nodes * sizeof(DevOperand), hipMemcpyHostToDevice, st));
   const u32 grid = cdiv(n, PAGG_NT);
@@ -4091,35 +4183,22 @@ static int pair_agg_impl(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t*
   PaggScatter sc;
   memset(&sc, 0, sizeof(sc));
   sc.n_aggs = n_aggs;
-  for (int k = 0; k < n_aggs; k++) {
+  for (int k = 0; k < n_aggs; k++) {  // the reduction writes per region, the scatter carries that to the A rows
     u64* sv = seg + (size_t)k * 2 * m_max;
-    u64* w = carry + (size_t)k * 4 * n_tiles;
     ma.aggs[k].out = sv, ma.aggs[k].out_nn = (i64*)(sv + m_max);
-    ma.aggs[k].first_v = w, ma.aggs[k].last_v = w + n_tiles;
-    ma.aggs[k].first_c = (i64*)(w + 2 * (size_t)n_tiles), ma.aggs[k].last_c = (i64*)(w + 3 * (size_t)n_tiles);
     sc.a[k] = PaggOut{sv, (const i64*)(sv + m_max), (u64*)aggs[k].out, (i64*)aggs[k].out_nn};
   }
+  bind_magg(ma, carry, n);
   {
     Phase ph(ctx, st, GIQL_PH_FILL, 2 + (n_aggs ? (n_tiles > 1 ? 2 : 1) : 0));
     hipLaunchKernelGGL(k_merge_heads, dim3(grid), dim3(256), 0, st, flags, excl, (u32)n, head_pos);
-    if (n_aggs) {
-      if (any_prog)
-        hipLaunchKernelGGL(k_pxagg_tiles, dim3(n_tiles), dim3(MAGG_TILE), 0, st, sorted_a, sorted_b, excl, flags, (u32)n,
-                           (const DevOperand*)d_nodes, xa);
-      else
-        hipLaunchKernelGGL(k_magg_tiles, dim3(n_tiles), dim3(MAGG_TILE), 0, st, sorted_b, excl, flags, (u32)n, ma);
-      if (n_tiles > 1)
-        hipLaunchKernelGGL(k_magg_fold, dim3(cdiv((u64)n_tiles - 1, 256 / WAVE)), dim3(256), 0, st, excl, flags, (u32)n,
-                           n_tiles, ma);
-    }
+    if (n_aggs) run_magg(st, sorted_b, excl, flags, (u32)n, ma, any_prog ? &xa : nullptr, sorted_a, d_nodes);
     hipLaunchKernelGGL(k_pagg_scatter, dim3(grid), dim3(PAGG_NT), 0, st, sorted_a, flags, excl, head_pos, total, (u32)n,
                        (u32)n_a, (i64*)pairs_out, sc);
     GIQL_TRY(post_launch("pair aggregate"));
   }
-  int status = 0;
-  HIP_TRY(hipMemcpyAsync(&status, &ctx->d_meta->status, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  collect_spans(ctx);
+  int status;
+  GIQL_TRY(finish_status(ctx, st, status));
   if (status != 0)
     return set_err(GIQL_ERR_INVALID, "pair aggregate: a row_a outside [0, %lld) or a row_b outside [0, %lld)",
                    (long long)n_a, (long long)n_b);
@@ -4130,9 +4209,7 @@ static int pair_agg_impl(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t*
 int giql_hip_pair_agg_dev(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t* row_b, int64_t n_pairs, int64_t n_a,
                           int64_t n_b, const giql_agg* aggs, int32_t n_aggs, int64_t* pairs_out, void* stream) {
   giql_pair_expr_agg cols[MAGG_MAX];
-  for (int k = 0; aggs && k < n_aggs && k < MAGG_MAX; k++)
-    cols[k] = giql_pair_expr_agg{aggs[k].func, aggs[k].type, aggs[k].data, aggs[k].valid, 0, 0, aggs[k].out, aggs[k].out_nn};
-  return pair_agg_impl(ctx, row_a, row_b, n_pairs, n_a, n_b, nullptr, 0, aggs ? cols : nullptr, n_aggs, pairs_out, stream);
+  return pair_agg_impl(ctx, row_a, row_b, n_pairs, n_a, n_b, nullptr, 0, column_sources(aggs, n_aggs, cols), n_aggs, pairs_out, stream);
 }
 
 int giql_hip_pair_expr_agg_dev(giql_hip_ctx* ctx, const int32_t* row_a, const int32_t* row_b, int64_t n_pairs,
@@ -4145,13 +4222,9 @@ int giql_hip_pair_expr_agg_dev(giql_hip_ctx* ctx, const int32_t* row_a, const in
 // Count-then-fill, like the INNER pair.  Stages (disjoin_kernels.hip.h): spans of both sides on one axis ->
 // the reference's 2n event keys -> ONE (key, id) sort -> breakpoints + coverage through two scans -> per-target
 // counts in input order -> int64 offsets; the fill is output-major.
-struct DisjoinBufs {
-  LinBufs lb;
-  SortBufs sb;
-  OsScratch os;
-  u32 *last = nullptr, *is_start = nullptr, *last_excl = nullptr, *start_excl = nullptr;
+struct DisjoinBufs : EventBufs {
   u32 *bp = nullptr, *cov = nullptr, *ncov = nullptr, *cbp = nullptr, *cnt = nullptr, *lo_first = nullptr;
-  u64 *bsums = nullptr, *n_bp = nullptr, *scratch_total = nullptr, *off = nullptr, *total = nullptr;
+  u64 *off = nullptr, *total = nullptr;
 };
 
 static int giql_hip_disjoin_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* t, const giql_side* r, int32_t n_chrom,
@@ -4172,17 +4245,7 @@ static int giql_hip_disjoin_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* t,
   DisjoinBufs W;
   auto carve = [&](char* base) {
     Carver c{base};
-    common_sizes(c, n_chrom, W.lb);
-    for (int k = 0; k < 2; k++) {
-      W.sb.key[k] = c.take<u32>(nev);
-      W.sb.end[k] = nullptr;
-      W.sb.rid[k] = c.take<u32>(nev);
-    }
-    os_scratch_sizes(c, nev, W.os);
-    W.last = c.take<u32>(nev);
-    W.is_start = c.take<u32>(nev);
-    W.last_excl = c.take<u32>(nev + 1);
-    W.start_excl = c.take<u32>(nev + 1);
+    event_sizes(c, n_chrom, nev, W);
     W.bsums = c.take<u64>(cdiv((u64)(nev + 1 > nt ? nev + 1 : nt), SCAN_TILE) + 1);
     W.n_bp = c.take<u64>(1);
     W.scratch_total = c.take<u64>(1);
@@ -4199,30 +4262,7 @@ static int giql_hip_disjoin_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* t,
     return c.off;
   };
   GIQL_TRY(claim_arena(ctx, st, carve));
-  giql_side none;
-  memset(&none, 0, sizeof(none));
-  GIQL_TRY(run_spans(ctx, st, *t, self ? none : *r, n_chrom, W.lb));
-  if (nev > 0) {
-    HIP_TRY(hipMemsetAsync(W.os.hist, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
-    Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
-    ctx->stats.phase_bytes[GIQL_PH_LINEARIZE] += (int64_t)20 * nr;  // three columns read, two keys written
-    u32 grid = cdiv((u64)nr, LIN_NT);
-    if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
-    hipLaunchKernelGGL(k_dj_events, dim3(grid), dim3(LIN_NT), 0, st, view_of(*ref), n_chrom, W.lb.chrom_base,
-                       W.sb.key[0], W.os.hist, ctx->d_meta, self ? DJ_BAD_TARGET : DJ_BAD_REFERENCE);
-    hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, W.os.hist, (u32)LIN_HIST_REPLICAS, W.os.gbase);
-    GIQL_TRY(post_launch("disjoin events"));
-  }
-  GIQL_TRY(run_sort_onesweep(ctx, st, W.sb, sort_by_start(W.os, nev)));
-  if (nev > 0) {
-    Phase ph(ctx, st, GIQL_PH_COUNT, 1);
-    ctx->stats.phase_bytes[GIQL_PH_COUNT] += (int64_t)16 * nev;  // keys + ids read, two flags written
-    hipLaunchKernelGGL(k_dj_flags, dim3(cdiv(nev, 256)), dim3(256), 0, st, W.sb.key[0], W.sb.rid[0], (u32)nev, (u32)nr,
-                       W.last, W.is_start);
-    GIQL_TRY(post_launch("disjoin flags"));
-  }
-  GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, W.last, (u64)nev, W.last_excl, W.bsums, W.n_bp));
-  GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, W.is_start, (u64)nev, W.start_excl, W.bsums, W.scratch_total));
+  GIQL_TRY(run_events(ctx, st, *t, r, n_chrom, W, "disjoin"));
   if (!self) HIP_TRY(hipMemsetAsync(W.cov, 0, (nev + 1) * sizeof(u32), st));
   if (nev > 0) {
     Phase ph(ctx, st, GIQL_PH_AUX, 1);
@@ -4249,13 +4289,7 @@ static int giql_hip_disjoin_plan_dev_impl(giql_hip_ctx* ctx, const giql_side* t,
     GIQL_TRY(post_launch("disjoin count"));
   }
   GIQL_TRY(run_scan<u64>(ctx, st, GIQL_PH_SCAN, W.cnt, (u64)nt, W.off, W.bsums, W.total, &ctx->d_meta->n_out));
-  HIP_TRY(hipMemcpyAsync(ctx->h_meta, ctx->d_meta, sizeof(DevMeta), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (ctx->h_meta->aux0 & DJ_BAD_TARGET)
-    return set_err(GIQL_ERR_INVALID, "DISJOIN needs start <= end on every row: the target has a row with start > end");
-  if (ctx->h_meta->aux0 & DJ_BAD_REFERENCE)
-    return set_err(GIQL_ERR_INVALID, "DISJOIN needs start <= end on every row: the reference has a row with start > end");
-  GIQL_TRY(read_meta(ctx, st));
+  GIQL_TRY(finish_events(ctx, st, DJ_BAD_TARGET | DJ_BAD_REFERENCE));
   collect_spans(ctx);
   DisjoinPlan& P = ctx->dj;
   P.target = *t;
@@ -4304,8 +4338,8 @@ int giql_hip_disjoin_fill_dev(giql_hip_ctx* ctx, int32_t* parent_out, int32_t* s
 }
 
 // ------------------------------------------------------- coverage segments
-// include/giql_hip_coverage.h.  DISJOIN's front in self mode (spans -> 2n event keys -> ONE (key, id) sort -> the two
-// flag scans), then coverage_kernels.hip.h: breakpoints with their whole depth -> keep flags -> scan -> one row per kept
+// include/giql_hip_coverage.h.  DISJOIN's front in self mode (run_events: spans -> 2n event keys -> ONE (key, id) sort
+// -> the two flag scans), then coverage_kernels.hip.h: breakpoints with their whole depth -> keep flags -> scan -> one row per kept
 // breakpoint.  No per-row count, no offsets, no output-major fill: the output has at most 2n - 1 rows.
 static int giql_hip_coverage_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int32_t n_chrom, uint32_t flags,
                                       int32_t* chrom_out, int32_t* start_out, int32_t* end_out, int64_t* depth_out,
@@ -4322,74 +4356,35 @@ static int giql_hip_coverage_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int
   if (n_chrom == 0) return set_err(GIQL_ERR_CHROM, "rows but n_chrom = 0");
   const bool runs = (flags & GIQL_COV_RUNS) != 0;
   const size_t n = (size_t)s->n, nev = 2 * n;
-  LinBufs lb;
-  SortBufs sb;
-  OsScratch os;
-  u32 *last = nullptr, *is_start = nullptr, *last_excl = nullptr, *start_excl = nullptr, *keep = nullptr, *slot = nullptr;
-  u64 *bsums = nullptr, *n_bp = nullptr, *scratch_total = nullptr, *total = nullptr;
+  EventBufs E;
+  u32 *keep = nullptr, *slot = nullptr;
+  u64* total = nullptr;
   auto carve = [&](char* base) {
     Carver c{base};
-    common_sizes(c, n_chrom, lb);
-    for (int k = 0; k < 2; k++) {
-      sb.key[k] = c.take<u32>(nev);
-      sb.end[k] = nullptr;
-      sb.rid[k] = c.take<u32>(nev);
-    }
-    os_scratch_sizes(c, nev, os);
-    last = c.take<u32>(nev);
-    is_start = c.take<u32>(nev);
-    last_excl = c.take<u32>(nev + 1);
-    start_excl = c.take<u32>(nev + 1);
+    event_sizes(c, n_chrom, nev, E);
     keep = c.take<u32>(nev);
     slot = c.take<u32>(nev + 1);
-    bsums = c.take<u64>(cdiv((u64)nev + 1, SCAN_TILE) + 1);
-    n_bp = c.take<u64>(1);
-    scratch_total = c.take<u64>(1);
+    E.bsums = c.take<u64>(cdiv((u64)nev + 1, SCAN_TILE) + 1);
+    E.n_bp = c.take<u64>(1);
+    E.scratch_total = c.take<u64>(1);
     total = c.take<u64>(1);
     return c.off;
   };
   GIQL_TRY(claim_arena(ctx, st, carve));
-  giql_side none;
-  memset(&none, 0, sizeof(none));
-  GIQL_TRY(run_spans(ctx, st, *s, none, n_chrom, lb));
-  {
-    HIP_TRY(hipMemsetAsync(os.hist, 0, (size_t)LIN_HIST_REPLICAS * 1024 * sizeof(u32), st));
-    Phase ph(ctx, st, GIQL_PH_LINEARIZE, 2);
-    ctx->stats.phase_bytes[GIQL_PH_LINEARIZE] += (int64_t)20 * n;  // three columns read, two keys written
-    u32 grid = cdiv((u64)n, LIN_NT);
-    if (grid > (u32)LIN_MAX_BLOCKS) grid = LIN_MAX_BLOCKS;
-    hipLaunchKernelGGL(k_dj_events, dim3(grid), dim3(LIN_NT), 0, st, view_of(*s), n_chrom, lb.chrom_base, sb.key[0],
-                       os.hist, ctx->d_meta, DJ_BAD_TARGET);
-    hipLaunchKernelGGL(k_digit_offsets, dim3(4), dim3(256), 0, st, os.hist, (u32)LIN_HIST_REPLICAS, os.gbase);
-    GIQL_TRY(post_launch("coverage events"));
-  }
-  GIQL_TRY(run_sort_onesweep(ctx, st, sb, sort_by_start(os, nev)));
-  {
-    Phase ph(ctx, st, GIQL_PH_COUNT, 1);
-    ctx->stats.phase_bytes[GIQL_PH_COUNT] += (int64_t)16 * nev;  // keys + ids read, two flags written
-    hipLaunchKernelGGL(k_dj_flags, dim3(cdiv(nev, 256)), dim3(256), 0, st, sb.key[0], sb.rid[0], (u32)nev, (u32)n, last,
-                       is_start);
-    GIQL_TRY(post_launch("coverage flags"));
-  }
-  GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, last, (u64)nev, last_excl, bsums, n_bp));
-  GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, is_start, (u64)nev, start_excl, bsums, scratch_total));
+  GIQL_TRY(run_events(ctx, st, *s, nullptr, n_chrom, E, "coverage"));
   // The sort is done: its second buffers are free, and hold the breakpoints and their depths (at most nev of each).
-  u32 *bp = sb.key[1], *depth = sb.rid[1];
+  u32 *bp = E.sb.key[1], *depth = E.sb.rid[1];
   HIP_TRY(hipMemsetAsync(keep, 0, nev * sizeof(u32), st));  // (the scan runs over nev flags, the breakpoints are fewer)
   {
     Phase ph(ctx, st, GIQL_PH_AUX, runs ? 2 : 1);
     ctx->stats.phase_bytes[GIQL_PH_AUX] += (int64_t)(runs ? 40 : 32) * nev;  // (at most: every key distinct)
-    hipLaunchKernelGGL(k_cov_depth, dim3(cdiv(nev, 256)), dim3(256), 0, st, sb.key[0], last, last_excl, is_start,
-                       start_excl, (u32)nev, bp, depth, runs ? (u32*)nullptr : keep);
-    if (runs) hipLaunchKernelGGL(k_cov_run_heads, dim3(cdiv(nev, 256)), dim3(256), 0, st, depth, n_bp, keep);
+    hipLaunchKernelGGL(k_cov_depth, dim3(cdiv(nev, 256)), dim3(256), 0, st, E.sb.key[0], E.last, E.last_excl, E.is_start,
+                       E.start_excl, (u32)nev, bp, depth, runs ? (u32*)nullptr : keep);
+    if (runs) hipLaunchKernelGGL(k_cov_run_heads, dim3(cdiv(nev, 256)), dim3(256), 0, st, depth, E.n_bp, keep);
     GIQL_TRY(post_launch("coverage breakpoints"));
   }
-  GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, keep, (u64)nev, slot, bsums, total, &ctx->d_meta->n_out));
-  HIP_TRY(hipMemcpyAsync(ctx->h_meta, ctx->d_meta, sizeof(DevMeta), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (ctx->h_meta->aux0 & DJ_BAD_TARGET)
-    return set_err(GIQL_ERR_INVALID, "DISJOIN needs start <= end on every row: the target has a row with start > end");
-  GIQL_TRY(read_meta(ctx, st));
+  GIQL_TRY(run_scan<u32>(ctx, st, GIQL_PH_SCAN, keep, (u64)nev, slot, E.bsums, total, &ctx->d_meta->n_out));
+  GIQL_TRY(finish_events(ctx, st, DJ_BAD_TARGET));  // (the text is DISJOIN's: coverage is its GROUP BY)
   const u64 h_total = ctx->h_meta->n_out;
   *n_out = (int64_t)h_total;
   if (capacity < 0 || (u64)capacity < h_total) {
@@ -4400,8 +4395,8 @@ static int giql_hip_coverage_dev_impl(giql_hip_ctx* ctx, const giql_side* s, int
     if (!chrom_out || !start_out || !end_out) return set_err(GIQL_ERR_INVALID, "output buffer is NULL");
     Phase ph(ctx, st, GIQL_PH_FILL, 1);
     ctx->stats.phase_bytes[GIQL_PH_FILL] += (int64_t)16 * nev + (int64_t)(depth_out ? 20 : 12) * (int64_t)h_total;
-    hipLaunchKernelGGL(k_cov_fill, dim3(cdiv(nev, 256)), dim3(256), 0, st, bp, depth, keep, slot, n_bp, lb.chrom_first,
-                       lb.chrom_base, n_chrom, (int)s->start_off, (int)s->end_off, runs ? 1 : 0, (u32)h_total, chrom_out,
+    hipLaunchKernelGGL(k_cov_fill, dim3(cdiv(nev, 256)), dim3(256), 0, st, bp, depth, keep, slot, E.n_bp, E.lb.chrom_first,
+                       E.lb.chrom_base, n_chrom, (int)s->start_off, (int)s->end_off, runs ? 1 : 0, (u32)h_total, chrom_out,
                        start_out, end_out, (i64*)depth_out);
     GIQL_TRY(post_launch("coverage rows"));
   }

@@ -1010,6 +1010,23 @@ class HipEngine:
 
     #: aggregates per :meth:`merge_agg` call, as asked for (the C ABI takes 8 kernel aggregates)
     MERGE_AGG_MAX = 8
+    #: STRING_AGG entries per :meth:`merge_agg` call (``GIQL_STR_AGG_MAX``)
+    MERGE_STR_AGG_MAX = _lib.STR_AGG_MAX
+
+    @staticmethod
+    def _check_agg_column(func: str, t, valid, n: int, table: str, validity_of: str) -> None:
+        """A numeric entry of :meth:`merge_agg` / :meth:`pair_aggregate` over a table of ``n`` rows; ``table`` and
+        ``validity_of`` word the two messages.  ``t`` may be ``None`` where the caller allows it."""
+        torch = _torch()
+        if func not in ("COUNT", "SUM", "MIN", "MAX", "AVG"):
+            raise ValueError(f"aggregate function {func!r}")
+        if t is not None and (t.dtype not in (torch.int32, torch.int64, torch.float32, torch.float64) or t.dim() != 1
+                              or not t.is_contiguous() or int(t.shape[0]) != n):
+            raise ValueError("an aggregate column must be a contiguous 1-D int32/int64/float32/float64 tensor "
+                             f"with one value per row of the {table}")
+        if valid is not None and (valid.dtype not in (torch.uint8, torch.bool) or valid.dim() != 1
+                                  or int(valid.shape[0]) != n or not valid.is_contiguous()):
+            raise ValueError(f"validity must be a contiguous uint8/bool tensor of {validity_of}")
 
     def merge_agg(self, s: DeviceSide, n_chrom: int, distance: int, aggs, preds=None):
         """MERGE with aggregates per merged region (``src/giql/expanders/merge.py:317-390``): the four tensors of
@@ -1026,57 +1043,13 @@ class HipEngine:
         the utf8 layout of one string per region.  NULL rows are skipped, a region with no non-NULL row is NULL, an
         empty string is a value; the members are joined in ascending start, then row order.  ``separator``: ``str``
         or ``bytes`` of at most 255 bytes.  At most :attr:`MERGE_STR_AGG_MAX` such entries, and 2^31 - 1 bytes of
-        output each (``GIQL_ERR_CAPACITY`` past that)."""
+        output each (``GIQL_ERR_CAPACITY`` past that).  A call without such an entry is ``giql_hip_merge_agg_dev``'s."""
         torch = _torch()
-        if any(str(a[0]).upper() == "STRING_AGG" for a in aggs):
-            return self._merge_agg_strings(s, n_chrom, distance, list(aggs), preds)
-        aggs = [(str(a[0]).upper(), a[1], a[2] if len(a) > 2 else None) for a in aggs]
-        if not 1 <= len(aggs) <= self.MERGE_AGG_MAX:
-            raise ValueError(f"MERGE takes 1 to {self.MERGE_AGG_MAX} aggregates, got {len(aggs)}")
-        ok = (torch.int32, torch.int64, torch.float32, torch.float64)
-        for func, t, valid in aggs:
-            if func not in ("COUNT", "SUM", "MIN", "MAX", "AVG"):
-                raise ValueError(f"aggregate function {func!r}")
-            if t.dtype not in ok or t.dim() != 1 or not t.is_contiguous() or int(t.shape[0]) != s.n:
-                raise ValueError("an aggregate column must be a contiguous 1-D int32/int64/float32/float64 tensor "
-                                 "with one value per row of the table")
-            if valid is not None and (valid.dtype not in (torch.uint8, torch.bool) or valid.shape != t.shape
-                                      or not valid.is_contiguous()):
-                raise ValueError("validity must be a contiguous uint8/bool tensor of the column's length")
-        if preds:
-            self._check_pred_rows(s, preds)
-        dtypes = [torch.int64 if f == "COUNT" else torch.float64 if f == "AVG" or t.is_floating_point() else torch.int64
-                  for f, t, _v in aggs]
-
-        def of_rows(rows):
-            if rows is None:
-                return aggs
-            taken = {}  # one copy per tensor: aggregates over one column keep sharing it
-
-            def take(t):
-                if t is not None and t.data_ptr() not in taken:
-                    taken[t.data_ptr()] = t[rows].contiguous()
-                return None if t is None else taken[t.data_ptr()]
-
-            return [(f, take(t), take(v)) for f, t, v in aggs]
-
-        return self._wide(
-            lambda sub, _b, rows: self._merge_agg_once(sub, n_chrom, distance, of_rows(rows),
-                                                       self._preds_of_rows(preds, rows)),
-            lambda parts: wide.merge_agg(parts, self.device, dtypes), s, None, n_chrom)
-
-    #: STRING_AGG entries per :meth:`merge_agg` call (``GIQL_STR_AGG_MAX``)
-    MERGE_STR_AGG_MAX = _lib.STR_AGG_MAX
-
-    def _merge_agg_strings(self, s: DeviceSide, n_chrom: int, distance: int, aggs, preds):
-        """:meth:`merge_agg` with at least one STRING_AGG entry: the numeric entries keep their checks and their
-        kernel, the string entries add the variable-length plan and one fill each."""
-        torch = _torch()
-        entries = []   # ("num", func, values, valid) | ("str", offsets, data, valid, separator bytes)
+        entries = []   # (func, values, valid) | ("STRING_AGG", offsets, data, valid, separator bytes)
         for a in aggs:
             func = str(a[0]).upper()
             if func != "STRING_AGG":
-                entries.append(("num", func, a[1], a[2] if len(a) > 2 else None))
+                entries.append((func, a[1], a[2] if len(a) > 2 else None))
                 continue
             if len(a) != 5:
                 raise ValueError("a STRING_AGG entry is (\"STRING_AGG\", offsets, data, valid_or_None, separator)")
@@ -1088,30 +1061,22 @@ class HipEngine:
                     or data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous()):
                 raise ValueError("a STRING_AGG column is contiguous int32 offsets of one entry per row plus one, and "
                                  "contiguous uint8 data")
-            if valid is not None and (valid.dtype not in (torch.uint8, torch.bool) or not valid.is_contiguous()
-                                      or valid.dim() != 1 or int(valid.shape[0]) != s.n):
-                raise ValueError("validity must be a contiguous uint8/bool tensor of the column's length")
-            entries.append(("str", off, data, valid, sep))
-        nums = [e for e in entries if e[0] == "num"]
-        n_str = len(entries) - len(nums)
+            self._check_agg_column("COUNT", None, valid, s.n, "table", "the column's length")
+            entries.append((func, off, data, valid, sep))
+        n_str = sum(e[0] == "STRING_AGG" for e in entries)
+        if not n_str and not 1 <= len(entries) <= self.MERGE_AGG_MAX:
+            raise ValueError(f"MERGE takes 1 to {self.MERGE_AGG_MAX} aggregates, got {len(entries)}")
         if len(entries) > self.MERGE_AGG_MAX or n_str > self.MERGE_STR_AGG_MAX:
             raise ValueError(f"MERGE takes at most {self.MERGE_AGG_MAX} aggregates, {self.MERGE_STR_AGG_MAX} of them "
                              f"STRING_AGG; got {len(entries)} and {n_str}")
-        ok = (torch.int32, torch.int64, torch.float32, torch.float64)
-        for _k, func, t, valid in nums:
-            if func not in ("COUNT", "SUM", "MIN", "MAX", "AVG"):
-                raise ValueError(f"aggregate function {func!r}")
-            if t.dtype not in ok or t.dim() != 1 or not t.is_contiguous() or int(t.shape[0]) != s.n:
-                raise ValueError("an aggregate column must be a contiguous 1-D int32/int64/float32/float64 tensor "
-                                 "with one value per row of the table")
-            if valid is not None and (valid.dtype not in (torch.uint8, torch.bool) or valid.shape != t.shape
-                                      or not valid.is_contiguous()):
-                raise ValueError("validity must be a contiguous uint8/bool tensor of the column's length")
+        for e in entries:
+            if e[0] != "STRING_AGG":
+                self._check_agg_column(*e, s.n, "table", "the column's length")
         if preds:
             self._check_pred_rows(s, preds)
-        dtypes = [wide.UTF8 if e[0] == "str" else
-                  torch.int64 if e[1] == "COUNT" else
-                  torch.float64 if e[1] == "AVG" or e[2].is_floating_point() else torch.int64 for e in entries]
+        dtypes = [wide.UTF8 if e[0] == "STRING_AGG" else
+                  torch.float64 if e[0] == "AVG" or (e[0] != "COUNT" and e[1].is_floating_point()) else torch.int64
+                  for e in entries]
 
         def of_rows(rows):
             if rows is None:
@@ -1129,104 +1094,73 @@ class HipEngine:
                     taken[key] = self.take_utf8(off, data, rows.to(torch.int32).contiguous())
                 return taken[key]
 
-            return [(e[0], e[1], take(e[2]), take(e[3])) if e[0] == "num"
-                    else ("str",) + take_str(e[1], e[2]) + (take(e[3]), e[4]) for e in entries]
+            return [(e[0],) + take_str(e[1], e[2]) + (take(e[3]), e[4]) if e[0] == "STRING_AGG"
+                    else (e[0], take(e[1]), take(e[2])) for e in entries]
 
         return self._wide(
-            lambda sub, _b, rows: self._merge_str_once(sub, n_chrom, distance, of_rows(rows),
+            lambda sub, _b, rows: self._merge_agg_once(sub, n_chrom, distance, of_rows(rows),
                                                        self._preds_of_rows(preds, rows)),
             lambda parts: wide.merge_agg(parts, self.device, dtypes), s, None, n_chrom)
 
-    def _merge_str_once(self, s: DeviceSide, n_chrom: int, distance: int, entries, preds=None):
-        torch = _torch()
-        n = s.n
-        nums = [(e[1], e[2], e[3]) for e in entries if e[0] == "num"]
-        strs = [e for e in entries if e[0] == "str"]
-        c_aggs, kernel, slot = self._kernel_aggs(nums, n)
-        c_strs = (_lib.CStrAgg * len(strs))()
-        outs = []
-        for j, (_k, off, _data, valid, sep) in enumerate(strs):
-            out_off = torch.empty(n + 1, dtype=torch.int32, device=self.device)
-            nn = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
-            row_dst = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)  # (uint32 words)
-            outs.append((out_off, nn, row_dst))
-            c_strs[j].offsets = off.data_ptr()
-            c_strs[j].valid = valid.data_ptr() if valid is not None and n else None
-            c_strs[j].sep_len = len(sep)
-            c_strs[j].out_offsets, c_strs[j].out_nn, c_strs[j].row_dst = out_off.data_ptr(), nn.data_ptr(), row_dst.data_ptr()
-        c = torch.empty(n, dtype=torch.int32, device=self.device)
-        st = torch.empty(n, dtype=torch.int32, device=self.device)
-        en = torch.empty(n, dtype=torch.int32, device=self.device)
-        cnt = torch.empty(n, dtype=torch.int64, device=self.device)
-        order = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
-        m = ctypes.c_int64(0)
-        c_preds, k = None, 0
-        if preds:
-            c_preds, k, _keep_alive, _nodes, n_nodes = self._c_preds(preds)
-            if n_nodes:
-                raise ValueError("arithmetic in a CLUSTER / MERGE predicate is not supported")
-        _lib.check(self._L.giql_hip_merge_str_dev(
-            self._h, s.c_struct(), int(n_chrom), int(distance), c_preds, k, c_aggs, len(kernel), c_strs, len(strs),
-            c.data_ptr() if n else None, st.data_ptr() if n else None, en.data_ptr() if n else None,
-            cnt.data_ptr() if n else None, order.data_ptr(), n, ctypes.byref(m), self._stream()))
-        r = int(m.value)
-        num_res = iter(self._agg_results(nums, kernel, slot, r))
-        str_res = []
-        for j, (_k, off, data, _valid, sep) in enumerate(strs):
-            out_off, nn, row_dst = outs[j]
-            out = torch.empty(int(c_strs[j].n_bytes), dtype=torch.uint8, device=self.device)
-            if out.numel():
-                _lib.check(self._L.giql_hip_concat_utf8_fill_dev(
-                    self._h, off.data_ptr(), data.data_ptr() if data.numel() else None, n, order.data_ptr(),
-                    row_dst.data_ptr(), n, sep, len(sep), out.data_ptr() if out.numel() else None, self._stream()))
-            str_res.append((out_off[: r + 1], out, nn[:r] > 0))
-        str_res = iter(str_res)
-        return (c[:r], st[:r], en[:r], cnt[:r]) + tuple(next(num_res) if e[0] == "num" else next(str_res)
-                                                        for e in entries)
-
-    def _kernel_aggs(self, aggs, n: int):
-        """The ``giql_agg`` array of numeric entries ``(func, values, valid)``: ``(array or None, kernel, slot)``."""
+    def _kernel_aggs(self, entries, n_out: int, ctype=_lib.CAgg):
+        """The kernel's aggregates for the entries ``(func, key, source)`` of one call, ``n_out`` outputs each: AVG
+        asks for SUM, and entries of equal function and ``key`` -- the caller's name for the source: a column, a
+        validity alone, an expression program -- share one.  ``source``: ``("col", values_or_None, valid_or_None)`` or
+        ``("expr", first node, nodes, can_float)``.  Returns ``(array of ctype, [(out, non_null)], slot per entry)``."""
         torch = _torch()
         types = {torch.int32: _lib.T_I32, torch.int64: _lib.T_I64, torch.float32: _lib.T_F32,
                  torch.float64: _lib.T_F64}
-        # the kernel's aggregates: AVG asks for SUM, and a SUM and an AVG over one column share it
-        kernel, slot = [], []
-        for func, t, valid in aggs:
-            key = ("SUM" if func == "AVG" else func, t.data_ptr(), None if valid is None else valid.data_ptr(), t.dtype)
-            if key not in [k[0] for k in kernel]:
-                flt = t.is_floating_point() and key[0] != "COUNT"
-                kernel.append((key, t, valid, torch.empty(n, dtype=torch.float64 if flt else torch.int64,
-                                                          device=self.device),
-                               torch.empty(n, dtype=torch.int64, device=self.device)))
-            slot.append([k[0] for k in kernel].index(key))
-        c_aggs = (_lib.CAgg * len(kernel))()
-        for j, (key, t, valid, out, nn) in enumerate(kernel):
-            c_aggs[j].func, c_aggs[j].type = _lib.AGG_FUNCS[key[0]], types[t.dtype]
-            c_aggs[j].data = t.data_ptr() if n else 1  # never dereferenced when empty
-            c_aggs[j].valid = valid.data_ptr() if valid is not None and n else None
-            c_aggs[j].out = out.data_ptr() if n else 1
-            c_aggs[j].out_nn = nn.data_ptr() if n else None
-        return (c_aggs if kernel else None), kernel, slot
+        kernel, slot = {}, []
+        for func, key, src in entries:
+            key = ("SUM" if func == "AVG" else func, key)
+            if key not in kernel:
+                flt = key[0] != "COUNT" and (src[3] if src[0] == "expr" else src[1] is not None and src[1].is_floating_point())
+                kernel[key] = (src, torch.empty(n_out, dtype=torch.float64 if flt else torch.int64, device=self.device),
+                               torch.empty(n_out, dtype=torch.int64, device=self.device))
+            slot.append(list(kernel).index(key))
+        c_aggs = (ctype * max(len(kernel), 1))()
+        for c, (key, (src, out, nn)) in zip(c_aggs, kernel.items()):
+            c.func = _lib.AGG_FUNCS[key[0]]
+            if src[0] == "expr":
+                c.first, c.count, c.type = src[1], src[2], _lib.T_F64 if src[3] else _lib.T_I64
+            else:
+                c.type = _lib.T_I32 if src[1] is None else types[src[1].dtype]
+                c.data = self._dev_ptr(src[1], "an aggregate column")
+                if src[1] is not None and c.data is None:
+                    c.data = 1  # (a table without rows: never dereferenced)
+                c.valid = self._dev_ptr(src[2], "a validity column")
+            c.out = out.data_ptr() if n_out else 1
+            c.out_nn = nn.data_ptr() if n_out else None
+        return c_aggs, [(out, nn) for _src, out, nn in kernel.values()], slot
 
-    def _agg_results(self, aggs, kernel, slot, r: int):
-        """What :meth:`merge_agg` returns per numeric entry, from the kernel's outputs cut to ``r`` regions."""
+    @staticmethod
+    def _agg_value(func: str, out, nn):
+        """An entry's values from its kernel aggregate: AVG is ``double(sum) / double(non_null)``; NULL reads 0."""
         torch = _torch()
-        res = []
-        for (func, _t, _v), j in zip(aggs, slot):
-            out, nn = kernel[j][3][:r], kernel[j][4][:r]
-            if func == "COUNT":
-                res.append((out, torch.ones(r, dtype=torch.bool, device=self.device)))
-                continue
-            valid = nn > 0
-            if func == "AVG":
-                out = out.double() / nn.double()
-            res.append((torch.where(valid, out, torch.zeros_like(out)), valid))
-        return res
+        if func != "AVG":
+            return out
+        return torch.where(nn > 0, out.double() / nn.double(), torch.zeros(out.shape[0], dtype=torch.float64, device=out.device))
 
-    def _merge_agg_once(self, s: DeviceSide, n_chrom: int, distance: int, aggs, preds=None):
+    def _merge_agg_once(self, s: DeviceSide, n_chrom: int, distance: int, entries, preds=None):
+        """One library call of :meth:`merge_agg` over its checked entries: ``giql_hip_merge_str_dev`` and one fill per
+        string where there is a STRING_AGG entry, else ``giql_hip_merge_agg_dev``."""
         torch = _torch()
         n = s.n
-        c_aggs, kernel, slot = self._kernel_aggs(aggs, n)
+        nums = [e for e in entries if e[0] != "STRING_AGG"]
+        strs = [e for e in entries if e[0] == "STRING_AGG"]
+        c_aggs, kernel, slot = self._kernel_aggs(
+            [(f, (t.data_ptr(), None if v is None else v.data_ptr(), t.dtype), ("col", t, v)) for f, t, v in nums], n)
+        c_strs = (_lib.CStrAgg * len(strs))()
+        str_outs = []
+        for cs, (_f, off, _data, valid, sep) in zip(c_strs, strs):
+            out_off = torch.empty(n + 1, dtype=torch.int32, device=self.device)
+            nn = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+            row_dst = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)  # (uint32 words)
+            str_outs.append((out_off, nn, row_dst))
+            cs.offsets = off.data_ptr()
+            cs.valid = valid.data_ptr() if valid is not None and n else None
+            cs.sep_len = len(sep)
+            cs.out_offsets, cs.out_nn, cs.row_dst = out_off.data_ptr(), nn.data_ptr(), row_dst.data_ptr()
         c = torch.empty(n, dtype=torch.int32, device=self.device)
         st = torch.empty(n, dtype=torch.int32, device=self.device)
         en = torch.empty(n, dtype=torch.int32, device=self.device)
@@ -1237,12 +1171,35 @@ class HipEngine:
             c_preds, k, _keep_alive, _nodes, n_nodes = self._c_preds(preds)
             if n_nodes:
                 raise ValueError("arithmetic in a CLUSTER / MERGE predicate is not supported")
-        _lib.check(self._L.giql_hip_merge_agg_dev(
-            self._h, s.c_struct(), int(n_chrom), int(distance), c_preds, k, c_aggs, len(kernel),
-            c.data_ptr() if n else None, st.data_ptr() if n else None, en.data_ptr() if n else None,
-            cnt.data_ptr() if n else None, n, ctypes.byref(m), self._stream()))
+        head = (self._h, s.c_struct(), int(n_chrom), int(distance), c_preds, k, c_aggs if nums else None, len(kernel))
+        rows = (c.data_ptr() if n else None, st.data_ptr() if n else None, en.data_ptr() if n else None,
+                cnt.data_ptr() if n else None)
+        if strs:
+            order = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+            _lib.check(self._L.giql_hip_merge_str_dev(*head, c_strs, len(strs), *rows, order.data_ptr(), n,
+                                                      ctypes.byref(m), self._stream()))
+        else:
+            _lib.check(self._L.giql_hip_merge_agg_dev(*head, *rows, n, ctypes.byref(m), self._stream()))
         r = int(m.value)
-        return (c[:r], st[:r], en[:r], cnt[:r]) + tuple(self._agg_results(aggs, kernel, slot, r))
+        num_res = []
+        for (func, _t, _v), j in zip(nums, slot):
+            out, nn = kernel[j][0][:r], kernel[j][1][:r]
+            if func == "COUNT":
+                num_res.append((out, torch.ones(r, dtype=torch.bool, device=self.device)))
+                continue
+            out = self._agg_value(func, out, nn)
+            num_res.append((torch.where(nn > 0, out, torch.zeros_like(out)), nn > 0))
+        str_res = []
+        for cs, (out_off, nn, row_dst), (_f, off, data, _valid, sep) in zip(c_strs, str_outs, strs):
+            out = torch.empty(int(cs.n_bytes), dtype=torch.uint8, device=self.device)
+            if out.numel():
+                _lib.check(self._L.giql_hip_concat_utf8_fill_dev(
+                    self._h, off.data_ptr(), data.data_ptr() if data.numel() else None, n, order.data_ptr(),
+                    row_dst.data_ptr(), n, sep, len(sep), out.data_ptr(), self._stream()))
+            str_res.append((out_off[: r + 1], out, nn[:r] > 0))
+        num_res, str_res = iter(num_res), iter(str_res)
+        return (c[:r], st[:r], en[:r], cnt[:r]) + tuple(next(str_res if e[0] == "STRING_AGG" else num_res)
+                                                        for e in entries)
 
     #: aggregates per :meth:`pair_aggregate` call, as asked for (``GIQL_PAIR_AGG_MAX`` kernel aggregates)
     PAIR_AGG_MAX = 8
@@ -1275,57 +1232,43 @@ class HipEngine:
         n = int(row_a.shape[0])
         if int(row_b.shape[0]) != n or row_a.dim() != 1 or row_b.dim() != 1:
             raise ValueError("row_a and row_b must have one entry per pair")
-        if any(isinstance(a[1], tuple) for a in aggs):
-            return self._pair_expr_aggregate(row_a, row_b, n, n_a, n_b, aggs)
-        ok = (torch.int32, torch.int64, torch.float32, torch.float64)
-        types = {torch.int32: _lib.T_I32, torch.int64: _lib.T_I64, torch.float32: _lib.T_F32,
-                 torch.float64: _lib.T_F64}
+        nodes, keep_alive, progs = [], [], {}   # progs: tree key -> (first, count, can_float)
+        entries = []
         for func, t, valid in aggs:
-            if func not in ("COUNT", "SUM", "MIN", "MAX", "AVG"):
-                raise ValueError(f"aggregate function {func!r}")
-            if t is None and func != "COUNT":
+            if isinstance(t, tuple):
+                self._check_agg_column(func, None, None, n_b, "", "")
+                if len(t) != 2 or t[0] != "expr":
+                    raise ValueError('an expression source is ("expr", tree)')
+                if valid is not None:
+                    raise ValueError("an expression source takes no validity column: its tree names them")
+                tkey = self._expr_key(t[1], n_a, n_b)
+                if tkey not in progs:
+                    first = len(nodes)
+                    self._flatten_expr(t[1], nodes, keep_alive)
+                    progs[tkey] = (first, len(nodes) - first, expr_can_float(t[1]))
+                entries.append((func, ("expr", tkey), ("expr",) + progs[tkey]))
+                continue
+            if func in ("SUM", "MIN", "MAX", "AVG") and t is None:
                 raise ValueError(f"{func} needs a values tensor (only COUNT reads validity alone)")
-            if t is not None and (t.dtype not in ok or t.dim() != 1 or not t.is_contiguous()
-                                  or int(t.shape[0]) != n_b):
-                raise ValueError("an aggregate column must be a contiguous 1-D int32/int64/float32/float64 tensor "
-                                 "with one value per row of the right table")
-            if valid is not None and (valid.dtype not in (torch.uint8, torch.bool) or valid.dim() != 1
-                                      or int(valid.shape[0]) != n_b or not valid.is_contiguous()):
-                raise ValueError("validity must be a contiguous uint8/bool tensor of one entry per right row")
-        # the kernel's aggregates: AVG asks for SUM, a SUM and an AVG over one column share it, COUNT shares by validity
-        kernel, slot = [], []
-        for func, t, valid in aggs:
-            f = "SUM" if func == "AVG" else func
+            self._check_agg_column(func, t, valid, n_b, "right table", "one entry per right row")
             vkey = None if valid is None else valid.data_ptr()
-            key = (f, None, vkey, None) if f == "COUNT" else (f, t.data_ptr(), vkey, t.dtype)
-            if key not in [k[0] for k in kernel]:
-                flt = f != "COUNT" and t.is_floating_point()
-                kernel.append((key, None if f == "COUNT" else t, valid,
-                               torch.empty(n_a, dtype=torch.float64 if flt else torch.int64, device=self.device),
-                               torch.empty(n_a, dtype=torch.int64, device=self.device)))
-            slot.append([k[0] for k in kernel].index(key))
-        c_aggs = (_lib.CAgg * max(len(kernel), 1))()
-        for j, (key, t, valid, out, nn) in enumerate(kernel):
-            c_aggs[j].func = _lib.AGG_FUNCS[key[0]]
-            c_aggs[j].type = _lib.T_I32 if t is None else types[t.dtype]
-            c_aggs[j].data = self._dev_ptr(t, "an aggregate column")
-            if t is not None and c_aggs[j].data is None:
-                c_aggs[j].data = 1  # (an empty right table: never dereferenced)
-            c_aggs[j].valid = self._dev_ptr(valid, "a validity column")
-            c_aggs[j].out = out.data_ptr() if n_a else 1
-            c_aggs[j].out_nn = nn.data_ptr() if n_a else None
+            if func == "COUNT":  # COUNT reads validity alone: every COUNT over one validity shares
+                entries.append((func, (None, vkey, None), ("col", None, valid)))
+            else:
+                entries.append((func, (t.data_ptr(), vkey, t.dtype), ("col", t, valid)))
+        if len(nodes) > 256:
+            raise ValueError(f"a pair aggregate takes at most 256 expression nodes per call, got {len(nodes)}")
+        c_aggs, kernel, slot = self._kernel_aggs(entries, n_a, _lib.CPairExprAgg if progs else _lib.CAgg)
         pairs = torch.empty(n_a, dtype=torch.int64, device=self.device)
-        _lib.check(self._L.giql_hip_pair_agg_dev(
-            self._h, self._dev_ptr(row_a, "row_a", torch.int32), self._dev_ptr(row_b, "row_b", torch.int32), n,
-            n_a, n_b, c_aggs, len(kernel), pairs.data_ptr() if n_a else None, self._stream()))
-        res = []
-        for (func, _t, _v), j in zip(aggs, slot):
-            out, nn = kernel[j][3], kernel[j][4]
-            if func == "AVG":
-                out = torch.where(nn > 0, out.double() / nn.double(), torch.zeros(n_a, dtype=torch.float64,
-                                                                                  device=self.device))
-            res.append((out, nn))
-        return pairs, res
+        rows = (self._h, self._dev_ptr(row_a, "row_a", torch.int32), self._dev_ptr(row_b, "row_b", torch.int32), n,
+                n_a, n_b)
+        tail = (c_aggs, len(kernel), pairs.data_ptr() if n_a else None, self._stream())
+        if progs:
+            c_nodes = (_lib.COperand * len(nodes))(*nodes)
+            _lib.check(self._L.giql_hip_pair_expr_agg_dev(*rows, c_nodes, len(nodes), *tail))
+        else:
+            _lib.check(self._L.giql_hip_pair_agg_dev(*rows, *tail))
+        return pairs, [(self._agg_value(func, *kernel[j]), kernel[j][1]) for (func, _t, _v), j in zip(aggs, slot)]
 
     def _expr_key(self, tree, n_a: int, n_b: int):
         """A hashable restatement of ``tree`` (columns by address): equal keys are one program.  Checks every column's
@@ -1339,81 +1282,6 @@ class HipEngine:
         if kind == "lit":
             return ("lit", type(tree[1]).__name__, tree[1])
         return (kind,) + tuple(self._expr_key(c, n_a, n_b) for c in tree[1:])
-
-    def _pair_expr_aggregate(self, row_a, row_b, n: int, n_a: int, n_b: int, aggs):
-        """:meth:`pair_aggregate` with at least one ``("expr", tree)`` entry: ``giql_hip_pair_expr_agg_dev``."""
-        torch = _torch()
-        ok = (torch.int32, torch.int64, torch.float32, torch.float64)
-        types = {torch.int32: _lib.T_I32, torch.int64: _lib.T_I64, torch.float32: _lib.T_F32,
-                 torch.float64: _lib.T_F64}
-        nodes, keep_alive, progs = [], [], {}   # progs: tree key -> (first, count, can_float)
-        kernel, slot = [], []
-        for func, t, valid in aggs:
-            if func not in ("COUNT", "SUM", "MIN", "MAX", "AVG"):
-                raise ValueError(f"aggregate function {func!r}")
-            f = "SUM" if func == "AVG" else func
-            if isinstance(t, tuple):
-                if len(t) != 2 or t[0] != "expr":
-                    raise ValueError('an expression source is ("expr", tree)')
-                if valid is not None:
-                    raise ValueError("an expression source takes no validity column: its tree names them")
-                tkey = self._expr_key(t[1], n_a, n_b)
-                if tkey not in progs:
-                    first = len(nodes)
-                    self._flatten_expr(t[1], nodes, keep_alive)
-                    progs[tkey] = (first, len(nodes) - first, expr_can_float(t[1]))
-                flt = progs[tkey][2]
-                key = (f, "expr", tkey)
-                src = ("expr",) + progs[tkey]
-            else:
-                if t is None and func != "COUNT":
-                    raise ValueError(f"{func} needs a values tensor (only COUNT reads validity alone)")
-                if t is not None and (t.dtype not in ok or t.dim() != 1 or not t.is_contiguous()
-                                      or int(t.shape[0]) != n_b):
-                    raise ValueError("an aggregate column must be a contiguous 1-D int32/int64/float32/float64 tensor "
-                                     "with one value per row of the right table")
-                if valid is not None and (valid.dtype not in (torch.uint8, torch.bool) or valid.dim() != 1
-                                          or int(valid.shape[0]) != n_b or not valid.is_contiguous()):
-                    raise ValueError("validity must be a contiguous uint8/bool tensor of one entry per right row")
-                vkey = None if valid is None else valid.data_ptr()
-                key = (f, None, vkey, None) if f == "COUNT" else (f, t.data_ptr(), vkey, t.dtype)
-                flt = t is not None and t.is_floating_point()
-                src = ("col", None if f == "COUNT" else t, valid)
-            if key not in [k[0] for k in kernel]:
-                kernel.append((key, src, torch.empty(n_a, dtype=torch.float64 if flt and f != "COUNT" else torch.int64,
-                                                     device=self.device),
-                               torch.empty(n_a, dtype=torch.int64, device=self.device)))
-            slot.append([k[0] for k in kernel].index(key))
-        if len(nodes) > 256:
-            raise ValueError(f"a pair aggregate takes at most 256 expression nodes per call, got {len(nodes)}")
-        c_nodes = (_lib.COperand * max(len(nodes), 1))(*nodes)
-        c_aggs = (_lib.CPairExprAgg * max(len(kernel), 1))()
-        for j, (key, src, out, nn) in enumerate(kernel):
-            c_aggs[j].func = _lib.AGG_FUNCS[key[0]]
-            if src[0] == "expr":
-                c_aggs[j].first, c_aggs[j].count = src[1], src[2]
-                c_aggs[j].type = _lib.T_F64 if src[3] else _lib.T_I64
-            else:
-                t, valid = src[1], src[2]
-                c_aggs[j].type = _lib.T_I32 if t is None else types[t.dtype]
-                c_aggs[j].data = self._dev_ptr(t, "an aggregate column")
-                if t is not None and c_aggs[j].data is None:
-                    c_aggs[j].data = 1  # (an empty right table: never dereferenced)
-                c_aggs[j].valid = self._dev_ptr(valid, "a validity column")
-            c_aggs[j].out = out.data_ptr() if n_a else 1
-            c_aggs[j].out_nn = nn.data_ptr() if n_a else None
-        pairs = torch.empty(n_a, dtype=torch.int64, device=self.device)
-        _lib.check(self._L.giql_hip_pair_expr_agg_dev(
-            self._h, self._dev_ptr(row_a, "row_a", torch.int32), self._dev_ptr(row_b, "row_b", torch.int32), n,
-            n_a, n_b, c_nodes, len(nodes), c_aggs, len(kernel), pairs.data_ptr() if n_a else None, self._stream()))
-        res = []
-        for (func, _t, _v), j in zip(aggs, slot):
-            out, nn = kernel[j][2], kernel[j][3]
-            if func == "AVG":
-                out = torch.where(nn > 0, out.double() / nn.double(), torch.zeros(n_a, dtype=torch.float64,
-                                                                                  device=self.device))
-            res.append((out, nn))
-        return pairs, res
 
     # ------------------------------------------------------------- projection
     def take(self, cols, idx, outs=None):

@@ -860,17 +860,23 @@ def _left_join_rows(plan: JoinPlan, lt, rt, a: DeviceSide, b: DeviceSide, n_chro
     return torch.cat([ka, kp]), torch.cat([kb, torch.full_like(kp, -1)])
 
 
-def _check_int_sum(column: str, col) -> None:
-    """SUM / AVG over the integer Arrow column ``col`` accumulate in int64 on the device, where DuckDB sums into a
-    128-bit integer: refuse the column when ``n_rows * max(|min|, |max|)`` could reach 2^63 instead of wrapping."""
+def _abs_max(col) -> int:
+    """``max(|min|, |max|)`` of an integer Arrow column; 0 for a column of NULLs alone."""
     import pyarrow.compute as pc
 
     mm = pc.min_max(col)
     lo, hi = mm["min"].as_py(), mm["max"].as_py()
-    if lo is None:
-        return
-    if len(col) * max(abs(lo), abs(hi)) >= 2**63:
-        raise ValueError(f"SUM / AVG over column {column!r}: {len(col)} rows of magnitude up to {max(abs(lo), abs(hi))} "
+    return 0 if lo is None else max(abs(lo), abs(hi))
+
+
+def _check_int_sum(column: str, col, n_inputs: int | None = None, noun: str = "rows") -> None:
+    """SUM / AVG over the integer Arrow column ``col`` accumulate in int64 on the device, where DuckDB sums into a
+    128-bit integer: refuse the column when ``n_inputs * max(|min|, |max|)`` could reach 2^63 instead of wrapping.
+    ``n_inputs`` values are summed at most: the column's rows under MERGE, a join's ``"pairs"`` (``noun``) over it."""
+    n_inputs = len(col) if n_inputs is None else n_inputs
+    bound = _abs_max(col)
+    if n_inputs * bound >= 2**63:
+        raise ValueError(f"SUM / AVG over column {column!r}: {n_inputs} {noun} of magnitude up to {bound} "
                          "can overflow the int64 sum; cast the column to a float type")
 
 
@@ -1378,20 +1384,6 @@ def _routes_join_aggregates(plan: JoinPlan, right_types: dict, return_indices: b
     return True
 
 
-def _check_pair_int_sum(column: str, col, n_pairs: int) -> None:
-    """SUM / AVG over the integer column ``col`` of the right table accumulate in int64 over a join's pairs: refuse
-    when ``n_pairs * max(|min|, |max|)`` could reach 2^63 instead of wrapping (as ``_check_int_sum``)."""
-    import pyarrow.compute as pc
-
-    mm = pc.min_max(col)
-    lo, hi = mm["min"].as_py(), mm["max"].as_py()
-    if lo is None:
-        return
-    if n_pairs * max(abs(lo), abs(hi)) >= 2**63:
-        raise ValueError(f"SUM / AVG over column {column!r}: {n_pairs} pairs of magnitude up to {max(abs(lo), abs(hi))} "
-                         "can overflow the int64 sum; cast the column to a float type")
-
-
 def expression_abs_bound(tree, column_info):
     """An absolute bound of an integer expression tree (the plan's serialised form: ``[kind, value]`` leaves,
     ``["fn", op, [children]]``) by interval arithmetic, or None where the tree can yield a float -- a float sum does not
@@ -1444,7 +1436,6 @@ def _column_info(res: "_Residuals"):
     """``column_info`` of ``expression_abs_bound`` over a plan's tables: (max |value| from the column's min / max,
     is it a float column); a column that is no number (a string under a comparison) counts 0."""
     import pyarrow as pa
-    import pyarrow.compute as pc
 
     def info(side: str, column: str):
         col = res._arrow(side, column)
@@ -1454,9 +1445,7 @@ def _column_info(res: "_Residuals"):
             return 1, False
         if not pa.types.is_integer(col.type):
             return 0, False
-        mm = pc.min_max(col)
-        lo, hi = mm["min"].as_py(), mm["max"].as_py()
-        return (0 if lo is None else max(abs(lo), abs(hi))), False
+        return _abs_max(col), False
     return info
 
 
@@ -1534,7 +1523,7 @@ def _execute_join_aggregates(plan: JoinPlan, lt, rt, eng: HipEngine, pins: dict 
             entry = ("COUNT", None, res._valid(col))
         else:
             if func == "SUM" and pa.types.is_integer(col.type):
-                _check_pair_int_sum(ag.column, col, n_pairs)
+                _check_int_sum(ag.column, col, n_pairs, "pairs")
             entry = (func,) + res._numeric("r", ag.column)
         slot[(func, ag.column)] = len(asked)
         asked.append(entry)

@@ -332,7 +332,13 @@ def test_the_kernel_shares_the_reduce_function_and_adds_no_atomics_or_lds():
     assert re.findall(r"__shared__\s+(\w+)\s+(\w+)", new) == re.findall(r"__shared__\s+(\w+)\s+(\w+)", old)
     host = open(os.path.join(csrc, "giql_hip.hip")).read()
     body = host[host.index("static int pair_agg_impl("):host.index("int giql_hip_pair_agg_dev(giql_hip_ctx")]
-    for stage in ("begin_call(", "check_program(", "k_pagg_load", "run_sort(", "k_pagg_heads", "run_scan<u32>", "k_pxagg_tiles",
-                  "k_magg_tiles", "k_magg_fold", "k_pagg_scatter"):
-        assert stage in body, stage
-    assert body.index("check_program(") < body.index("hipMemsetAsync(") < body.index("k_pagg_load")
+    at = [body.index(stage) for stage in ("begin_call(", "convert_aggs(", "hipMemsetAsync(", "k_pagg_load", "run_sort(",
+                                          "k_pagg_heads", "run_scan<u32>", "run_magg(", "k_pagg_scatter")]
+    assert at == sorted(at)                     # in this order: the programs are checked before anything is written
+    # the two stages MERGE shares with it: the conversion checks the programs, the reduction
+    # launches the tiles -- this kernel or MERGE's -- and then the fold
+    convert = host[host.index("static int convert_aggs("):host.index("static const giql_pair_expr_agg* column_sources(")]
+    reduce_ = host[host.index("static void run_magg("):host.index("// ---------------------------------------------------------- CLUSTER / MERGE")]
+    assert "check_program(" in convert and "hipMemsetAsync(" not in convert and "hipLaunchKernelGGL" not in convert
+    at = [reduce_.index(k) for k in ("k_pxagg_tiles", "k_magg_tiles", "k_magg_fold")]
+    assert at == sorted(at)

@@ -273,10 +273,15 @@ def test_the_entry_point_lives_in_an_extension_header_of_its_own():
 def test_the_kernels_reuse_disjoins_stages_and_need_no_atomics():
     host = open(os.path.join(ROOT, "giql_amd", "csrc", "giql_hip.hip")).read()
     body = host[host.index("static int giql_hip_coverage_dev_impl"):host.index("int giql_hip_coverage_dev(giql_hip_ctx")]
-    for stage in ("begin_call(", "run_spans(", "k_dj_events", "k_digit_offsets", "run_sort_onesweep(ctx, st, sb, sort_by_start(",
-                  "k_dj_flags", "k_cov_depth", "k_cov_run_heads", "k_cov_fill"):
+    for stage in ("begin_call(", "run_events(", "k_cov_depth", "k_cov_run_heads", "k_cov_fill"):
         assert stage in body, stage
-    assert body.count("run_scan<u32>") == 3 and "with_order_fallback" in host[host.index("int giql_hip_coverage_dev(giql_hip_ctx"):][:600]
+    # DISJOIN's front is one stage that DISJOIN's plan calls as well
+    sweep = host[host.index("static int run_events("):host.index("static int finish_events(")]
+    for stage in ("run_spans(", "k_dj_events", "k_digit_offsets", "run_sort_onesweep(ctx, st, E.sb, sort_by_start(", "k_dj_flags"):
+        assert stage in sweep, stage
+    assert "run_events(" in host[host.index("static int giql_hip_disjoin_plan_dev_impl"):host.index("int giql_hip_disjoin_plan_dev(giql_hip_ctx")]
+    assert sweep.count("run_scan<u32>") == 2 and body.count("run_scan<u32>") == 1
+    assert "with_order_fallback" in host[host.index("int giql_hip_coverage_dev(giql_hip_ctx"):][:600]
     for gone in ("k_dj_count", "k_dj_fill", "k_dj_covered", "lo_first"):
         assert gone not in body
     kernels = open(os.path.join(ROOT, "giql_amd", "csrc", "coverage_kernels.hip.h")).read()

@@ -229,11 +229,11 @@ def test_the_flag_reaches_every_entry_point():
 
 def test_an_integer_sum_that_could_overflow_refuses():
     big = pa.array([2**40, -(2**41), None], pa.int64())
-    X._check_pair_int_sum("weight", big, 2**21)                  # 2^62: fits
+    X._check_int_sum("weight", big, 2**21, "pairs")                # 2^62: fits
     with pytest.raises(ValueError, match=r"SUM / AVG over column 'weight': 4194304 pairs .* can overflow the int64 sum"):
-        X._check_pair_int_sum("weight", big, 2**22)              # 2^63: could wrap
-    X._check_pair_int_sum("weight", pa.array([None, None], pa.int64()), 2**62)
-    X._check_pair_int_sum("weight", pa.array([0, 0], pa.int8()), 2**62)
+        X._check_int_sum("weight", big, 2**22, "pairs")            # 2^63: could wrap
+    X._check_int_sum("weight", pa.array([None, None], pa.int64()), 2**62, "pairs")
+    X._check_int_sum("weight", pa.array([0, 0], pa.int8()), 2**62, "pairs")
 
 
 # ---------------------------------------------------------------- the C ABI

@@ -247,7 +247,7 @@ def test_a_genome_wider_than_the_32_bit_axis(eng):
     names = _values(r, n, lengths=LENGTHS[:12])
     off, data, valid = _utf8(names)
     with pytest.raises(_lib.GiqlHipError) as exc:
-        eng._merge_str_once(_side(chrom, start, end), 2, 0, [("str", off, data, valid, b",")])
+        eng._merge_agg_once(_side(chrom, start, end), 2, 0, [("STRING_AGG", off, data, valid, b",")])
     assert exc.value.code == _lib.GIQL_ERR_SPAN
     score = _dev(r.integers(-50, 50, n))
     out = run_and_check(eng, chrom, start, end, 2, 0, {"name": names}, [("name", b","), ("name", b"")],
